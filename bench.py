@@ -11,7 +11,14 @@
   N GPUs   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
            strong scaling: the frame is fixed, tiles shard across ranks.
 
-Prints ONE JSON line on rank 0.  `roofline` names the roof that binds the workload:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, the config and the launch).  --dump-outputs DIR also writes what the last timed step
+computed (rank 0's tile accumulators and RGBA8 image, as float32 .npy files; the accumulators' NaN / inf entries
+-- the reference's NaN samples -- as 0 plus a code array accum_nonfinite; a fixed seeded sample of the pixels when
+they exceed the size cap).  Everything else below -- hardware counters, `roofline`, `cpu_baseline`,
+`hbm_point` -- is measured only with --full.
+
+With --full, `roofline` names the roof that binds the workload:
   * the BASELINE configs are cache-resident (BVH 129 KB): bound = "valu-issue".  achieved = VALU
     wave-instructions per second (hardware counter SQ_INSTS_VALU of one launch / the kernel time measured
     live with HIP events), peak = CUs x 4 SIMDs x clock / 2 cycles per wave64 instruction
@@ -363,13 +370,40 @@ def roofline_block(bound, pmc, pmc_source, avg_kernel_ms, alg_bytes_per_launch, 
     return r
 
 
+DUMP_BYTES = 60 * 1000 * 1000  # the whole dump stays under 64 MB
+
+
+def split_nonfinite(a):
+    """(a with every NaN / +inf / -inf replaced by 0, a code array of a's shape: 0 finite, 1 NaN, 2 +inf, 3 -inf).
+    The accumulators hold NaN where the reference's arithmetic makes one (the r = 0 ground BRDF's NaN samples poison a
+    pixel's sum, srt_path.h), bit-exact with the oracle; the pair keeps that information in finite numbers."""
+    import numpy as np
+    code = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1.0, 2.0, 3.0], 0.0).astype(np.float32)
+    return np.where(code == 0, a, np.float32(0)), code
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes each {name: float32 array} as out_dir/<name>.npy, in its own shape.  An array larger than its share of
+    DUMP_BYTES becomes a fixed, seeded, sorted sample of its rows (the last axis' 4-vectors: one RGBA or one accumulator
+    record per pixel), the same for every run of the same arguments and for arrays of the same shape."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = share // rows[0].nbytes
+            a = rows[np.sort(np.random.default_rng(12345).choice(len(rows), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def hbm_point(args):
     """The BASELINE scenes are cache-resident, so the headline line says nothing about HBM.  This adds one HBM-bound point
     to the same JSON line, measured in the same run: a seeded 4 M-triangle soup (far beyond the 256 MB of cache), tree
     built on the device, closest-hit traversal -- the fast mode for such scenes, not a parity path -- rendered by a child
     run of this script (own counters, own HIP-event timing) after this process has released the GPU's queues."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", args.hbm_point_workload, "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--seed", str(args.seed)]
+           "--full", "--no-cpu-baseline", "--seed", str(args.seed)]
     if args.no_pmc:
         cmd.append("--no-pmc")
     try:
@@ -407,7 +441,16 @@ def main():
                     help="headline workload only: do not add the HBM-bound point (4 M-triangle soup, device-built tree, "
                          "closest-hit traversal) measured in a child run of this script")
     ap.add_argument("--hbm-point-workload", default="soup_4m_ploc_closest_720p_16spp")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: hardware counters and the roofline block, "
+                         "the CPU baseline and (headline workload) the HBM-bound point")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.save_pmc and not args.full:
+        ap.error("--save-pmc records the counters of a --full run")
 
     # before anything initialises HIP/HSA in this process: dmabuf IPC for RCCL
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -426,11 +469,11 @@ def main():
     if args.spp > 0:
         spp = args.spp
 
-    # ---- hardware counters of one launch of this workload, collected by child processes before this
+    # ---- (--full) hardware counters of one launch of this workload, collected by child processes before this
     # process initialises the GPU
     pmc, pmc_source = None, "none"
     ksrc = kernel_source_id()
-    if world == 1 and not args.no_pmc and not under_profiler():
+    if args.full and world == 1 and not args.no_pmc and not under_profiler():
         try:
             t = time.time()
             pmc = collect_pmc(args, args.workload, spp, args.pmc_timeout)
@@ -438,7 +481,7 @@ def main():
         except Exception as e:  # fall back to the recorded counters, and say so
             sys.stderr.write("bench.py: in-run counter collection failed: %s\n" % e)
             pmc = None
-    if pmc is None:
+    if args.full and pmc is None:
         try:
             rec = json.load(open(pmc_file(args.workload)))
             if rec.get("spp") == spp and world == 1:
@@ -474,10 +517,6 @@ def main():
     sb = build_scene(srt, scene_name, builder)
     ctx.upload_scene(sb)  # scene resident in HBM before the timed region
     t_build = time.time() - t_build
-    n_tris = int(sb.desc().numTriangles)
-    n_nodes = len(ctx.bvh(0)) if n_tris < 2000000 else 2 * n_tris
-    scene_footprint = "BVH %.0f KB, %d triangles %.0f KB, %d spheres, textures %.1f MB" % (
-        n_nodes * 32 / 1e3, n_tris, n_tris * 112 / 1e3, len(sb.spheres), len(sb.texels) / 1e6)
     cam_params = abi.default_camera_params()
     ctx.set_camera(dev.make_camera(cam_params))
 
@@ -525,6 +564,7 @@ def main():
             gathered = gather_tiles(local, rank, world)
         if rank == 0:
             ctx.resolve_tiles(params, gathered.data_ptr(), rgba.data_ptr(), None, stream)
+        return gathered
 
     def fence():
         torch.cuda.synchronize()
@@ -537,7 +577,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        gathered = step(True)
     fence()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -551,36 +591,18 @@ def main():
     else:
         avg_kernel_ms = sum(kernel_ms) / max(1, len(kernel_ms))
 
-    # algorithmic bytes per sample: the counting variant of the same kernel on the same scene and
-    # seed at a reduced spp (outside the timed region); the traversal is identical sample for sample.
-    count_spp = min(spp, 8)
-    cparams = abi.default_render_params(W, H, count_spp, max_bounce, seed=args.seed, tile_first=rank, tile_stride=world,
-                                        count_stats=1, traversal=trav)
-    ctx.render_tiles(cparams, local.data_ptr(), stream)
-    torch.cuda.synchronize()
-    st = ctx.stats()
-    if world > 1:
-        keys = sorted(st)
-        v = torch.tensor([st[k] for k in keys], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(v)
-        st = dict(zip(keys, [int(x) for x in v.tolist()]))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the tile accumulators (rank 0's gathered buffer, its
+        # non-finite entries as a separate code array) and the resolved RGBA8 image
+        accum, nonfinite = split_nonfinite(gathered.cpu().numpy())
+        dump_outputs(args.dump_outputs, {"accum_tiles": accum, "accum_nonfinite": nonfinite,
+                                         "rgba": rgba.cpu().numpy().astype("float32")})
+
+    line = None
     if rank == 0:
-        samples_counted = W * H * count_spp
-        bytes_per_sample = (algorithmic_bytes(st, W, H) - 16 * W * H) / samples_counted
-        samples_per_launch = W * H * spp  # whole frame; per rank it is 1/world of this
-        bytes_per_launch = (bytes_per_sample * samples_per_launch + 16 * W * H) / world
-        if pmc is not None:
-            pmc = dict(pmc)
-            pmc["_samples"] = samples_per_launch
         total_samples = W * H * spp * args.steps
         value = total_samples / elapsed / 1e6
         mode = launch.get("lds_tree_mode")
-        # (the bench scenes have one root; the hybrid form's single-root instance serves trees of up to 2^20 nodes: srt_launch_render_wf)
-        kernel_name = ("srt_render_wf_kernel<%s,false,true>" % ("true" if n_nodes <= (1 << 20) else "false") if mode == 4 else
-                       "srt_render_wf_kernel<true,false,false>" if mode == 3 else
-                       "srt_render_kernel<%s,false,true,%s,%s>" % ("true" if traversal == "closest" else "false",
-                                                                   "true" if launch["lds_tree"] else "false",
-                                                                   "true" if launch.get("lds_tree_mode") == 2 else "false"))
         line = {
             "metric": "Msamples/s (WxHxspp/s), 720p masterchief @5k spp" if args.workload == "masterchief_720p_5000spp"
                       else "Msamples/s (WxHxspp/s), " + args.workload,
@@ -601,22 +623,57 @@ def main():
                        "kernel_form": ("path pool: lanes traverse, full waves shade contexts from per-class LDS rings (srt_wavefront.hip)"
                                        + (", hybrid form" if mode == 4 else "") if mode in (3, 4) else "step scheduler: one path per lane (srt_kernels.hip)"),
                        "attenuation_stacks": "global memory" if mode in (1, 3, 4) else "LDS"},
-            "roofline": roofline_block(bound, pmc, pmc_source, avg_kernel_ms, bytes_per_launch, bytes_per_sample, st, info,
-                                       scene_footprint, kernel_name),
         }
-        if args.save_pmc and pmc is not None and pmc_source.startswith("in-run"):
-            rec = {"workload": args.workload, "spp": spp, "spp_chunks": chunks, "kernel_source_id": ksrc,
-                   "recorded": time.strftime("%Y-%m-%d"), "device": info, "kernel_ms_at_recording": round(avg_kernel_ms, 3),
-                   "counters": {k: v for k, v in pmc.items() if not k.startswith("_")},
-                   "how": "bench.py --save-pmc: rocprofv3 --pmc, separate passes %s" % [c for _, c in PMC_PASSES]}
-            os.makedirs(os.path.dirname(pmc_file(args.workload)), exist_ok=True)
-            json.dump(rec, open(pmc_file(args.workload), "w"), indent=1)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(sb, cam_params, abi, W, H, spp, max_bounce, args.seed, args.cpu_budget)
-        else:
-            line["cpu_baseline"] = None
-        if args.workload == "masterchief_720p_5000spp" and world == 1 and not args.no_hbm_point and not under_profiler():
-            line["hbm_point"] = hbm_point(args)
+
+    if args.full:
+        # algorithmic bytes per sample: the counting variant of the same kernel on the same scene and
+        # seed at a reduced spp (outside the timed region); the traversal is identical sample for sample.
+        count_spp = min(spp, 8)
+        cparams = abi.default_render_params(W, H, count_spp, max_bounce, seed=args.seed, tile_first=rank, tile_stride=world,
+                                            count_stats=1, traversal=trav)
+        ctx.render_tiles(cparams, local.data_ptr(), stream)
+        torch.cuda.synchronize()
+        st = ctx.stats()
+        if world > 1:
+            keys = sorted(st)
+            v = torch.tensor([st[k] for k in keys], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(v)
+            st = dict(zip(keys, [int(x) for x in v.tolist()]))
+        if rank == 0:
+            n_tris = int(sb.desc().numTriangles)
+            n_nodes = len(ctx.bvh(0)) if n_tris < 2000000 else 2 * n_tris
+            scene_footprint = "BVH %.0f KB, %d triangles %.0f KB, %d spheres, textures %.1f MB" % (
+                n_nodes * 32 / 1e3, n_tris, n_tris * 112 / 1e3, len(sb.spheres), len(sb.texels) / 1e6)
+            samples_counted = W * H * count_spp
+            bytes_per_sample = (algorithmic_bytes(st, W, H) - 16 * W * H) / samples_counted
+            samples_per_launch = W * H * spp  # whole frame; per rank it is 1/world of this
+            bytes_per_launch = (bytes_per_sample * samples_per_launch + 16 * W * H) / world
+            if pmc is not None:
+                pmc = dict(pmc)
+                pmc["_samples"] = samples_per_launch
+            # (the bench scenes have one root; the hybrid form's single-root instance serves trees of up to 2^20 nodes: srt_launch_render_wf)
+            kernel_name = ("srt_render_wf_kernel<%s,false,true>" % ("true" if n_nodes <= (1 << 20) else "false") if mode == 4 else
+                           "srt_render_wf_kernel<true,false,false>" if mode == 3 else
+                           "srt_render_kernel<%s,false,true,%s,%s>" % ("true" if traversal == "closest" else "false",
+                                                                       "true" if launch["lds_tree"] else "false",
+                                                                       "true" if launch.get("lds_tree_mode") == 2 else "false"))
+            line["roofline"] = roofline_block(bound, pmc, pmc_source, avg_kernel_ms, bytes_per_launch, bytes_per_sample, st, info,
+                                              scene_footprint, kernel_name)
+            if args.save_pmc and pmc is not None and pmc_source.startswith("in-run"):
+                rec = {"workload": args.workload, "spp": spp, "spp_chunks": chunks, "kernel_source_id": ksrc,
+                       "recorded": time.strftime("%Y-%m-%d"), "device": info, "kernel_ms_at_recording": round(avg_kernel_ms, 3),
+                       "counters": {k: v for k, v in pmc.items() if not k.startswith("_")},
+                       "how": "bench.py --save-pmc: rocprofv3 --pmc, separate passes %s" % [c for _, c in PMC_PASSES]}
+                os.makedirs(os.path.dirname(pmc_file(args.workload)), exist_ok=True)
+                json.dump(rec, open(pmc_file(args.workload), "w"), indent=1)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(sb, cam_params, abi, W, H, spp, max_bounce, args.seed, args.cpu_budget)
+            else:
+                line["cpu_baseline"] = None
+            if args.workload == "masterchief_720p_5000spp" and world == 1 and not args.no_hbm_point and not under_profiler():
+                line["hbm_point"] = hbm_point(args)
+
+    if rank == 0:
         if args.save_png:
             from PIL import Image
             Image.fromarray(rgba.cpu().numpy()).save(args.save_png)

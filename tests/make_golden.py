@@ -13,6 +13,9 @@
   bvh_topology.json       pre-order node arrays of the config scenes (count, depth, sha1, first nodes).
   render_<scene>.npz      tiny full renders by the oracle in COUNTER and MT mode
                           (float accumulators + RGBA8).
+  reference_models.tar.xz the model files of the reference's data/ directory that test_host_cpp.py loads, packed
+                          small (pack_reference_models: data: URIs decoded, the assets/ images they embed cut out,
+                          sha256 of every file as shipped); the textures they name are not included.
 """
 import importlib
 import json
@@ -85,6 +88,53 @@ def primary_classes(W, H):
     return cls.reshape(H, W)
 
 
+REFERENCE_MODELS = ("square.gltf", "cube.gltf", "masterchief.gltf", "masterchief2.gltf", "masterchief.glb", "halo.glb",
+                    "scene.gltf", "scene.bin", "masterchief-sep.gltf", "masterchief-sep.bin", "masterchief2-separate.gltf",
+                    "masterchief2-separate.bin")
+SHARED_ASSETS = ("Image_0.png", "Image_1.png")  # embedded byte for byte in masterchief2.gltf and halo.glb
+
+
+def pack_reference_models(data_dir):
+    """The reference's model files in a form the repository can hold: base64 data: URIs decoded to their bytes (they
+    compress far better), and every copy of an assets/ image cut out.  manifest.json says, per file, where the images go
+    back (offsets into the decoded bytes, ascending), which byte ranges are base64 again afterwards, and the sha256 of
+    the file as shipped; tests/test_host_cpp.py rebuilds the files from it and checks that hash."""
+    import base64
+    import hashlib
+    import io
+    import lzma
+    import re
+    import tarfile
+    shared = {a: open(os.path.join(ROOT, "assets", a), "rb").read() for a in SHARED_ASSETS}
+    blobs, manifest = {}, {}
+    for name in REFERENCE_MODELS:
+        orig = open(os.path.join(data_dir, name), "rb").read()
+        b, b64 = orig, []
+        if name.endswith(".gltf"):
+            out, pos = b"", 0
+            for m in re.finditer(rb"data:[^;\"]*;base64,([A-Za-z0-9+/=]*)", orig):
+                raw = base64.b64decode(m.group(1))
+                assert base64.b64encode(raw) == m.group(1), name  # re-encoding gives the same text
+                out += orig[pos:m.start(1)]
+                b64.append([len(out), len(out) + len(raw)])
+                out += raw
+                pos = m.end(1)
+            b = out + orig[pos:]
+        cuts = sorted([k.start(), a] for a, ab in shared.items() for k in re.finditer(re.escape(ab), b))
+        out, pos = b"", 0
+        for k, a in cuts:
+            out += b[pos:k]
+            pos = k + len(shared[a])
+        blobs[name] = out + b[pos:]
+        manifest[name] = {"b64": b64, "assets": cuts, "sha256": hashlib.sha256(orig).hexdigest()}
+    blobs["manifest.json"] = json.dumps(manifest, indent=1, sort_keys=True).encode()
+    with tarfile.open(os.path.join(GOLD, "reference_models.tar.xz"), "w:xz", preset=9 | lzma.PRESET_EXTREME) as t:
+        for name in sorted(blobs):
+            info = tarfile.TarInfo(name)
+            info.size, info.mtime, info.mode = len(blobs[name]), 0, 0o644
+            t.addfile(info, io.BytesIO(blobs[name]))
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     from PIL import Image
@@ -114,6 +164,7 @@ def main():
                                      for k, (y0, y1, x0, x1) in REGIONS.items()},
                          "black_pixels": int((im.sum(2) == 0).sum())}
         json.dump(out, open(os.path.join(GOLD, "published_regions.json"), "w"), indent=1)
+        pack_reference_models(os.path.join(os.path.dirname(ref), "data"))
 
     kat = {"mt19937_default_seed_uniform_float": [float(x) for x in O.rng_kat(16, libstdcxx=True)],
            "survey_first_six": [0.81472367, 0.135477006, 0.905791938, 0.835008562, 0.126986817, 0.968867779],
