@@ -219,8 +219,9 @@ typedef struct SrtStats {
   uint64_t samples, rays;
   uint64_t nodeVisits, boxPasses, triTests, sphereTests;
   uint64_t shadedTriHits, texelFetches;
-  /* wave-scheduler profile of the counting variant (diagnostics, not part of any parity claim):
-   * shader clocks spent in, executions of, and lanes active in each step kind, summed over waves */
+  /* wave-scheduler profile of the step-scheduler kernel's counting variant (diagnostics, not part of any parity claim):
+   * shader clocks spent in, executions of, and lanes active in each step kind, summed over waves.  Zero after a counting
+   * launch of the path-pool kernel (srtGetLaunchInfo mode 3 or 4; tunable "wavefront" = 0 selects the step scheduler) */
   uint64_t cyclesNode, cyclesPrim, cyclesShade, cyclesTotal;
   uint64_t stepsNode, stepsPrim, stepsShade;
   uint64_t lanesNode, lanesPrim, lanesShade;

@@ -22,10 +22,12 @@ extern "C" {
 int srtScatterTest(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, float* out13);
 
 /* Per-ray view into the RENDER kernel's own traversal (not srtTraceRays' kernel): renders sample
- * p->sampleFirst of every pixel with the counting variant of srt_render_kernel and records, per pixel, the
- * ray that path traced at bounce `depth` (0 = the camera ray) and what the kernel's node / primitive steps
- * made of it.  Feeding the recorded rays to the oracle's world.hit() checks the render kernel's slab-test
- * certificate, stack handling and step scheduler ray by ray.  hOut: W*H records in image order. */
+ * p->sampleFirst of every pixel with the counting variant of the kernel the same launch without counting would run
+ * (srt_render_kernel, or the path-pool kernel srt_render_wf_kernel in its whole-tree or hybrid form: srtGetLaunchInfo
+ * tells which) and records, per pixel, the ray that path traced at bounce `depth` (0 = the camera ray) and what the
+ * kernel's node / primitive steps made of it.  Feeding the recorded rays to the oracle's world.hit() checks the render
+ * kernel's slab-test certificate, stack or thread-link handling and scheduler ray by ray.  hOut: W*H records in image
+ * order. */
 typedef struct SrtAovRecord {
   float o[3], d[3], time; /* the ray (tMin = p->tMin, tMax = +inf, main.cpp:39) */
   int32_t valid;          /* 0: the pixel's path ended before this bounce */
@@ -36,7 +38,8 @@ typedef struct SrtAovRecord {
 } SrtAovRecord;
 int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAovRecord* hOut);
 
-/* Sub-step profile of the most recent countStats launch (shader clocks summed over waves, diagnostics only):
+/* Sub-step profile of the most recent countStats launch of the step-scheduler kernel (shader clocks summed over waves,
+ * diagnostics only; zero after one of the path-pool kernel, which a counting launch runs where the production launch would):
  * out10 = { hit step: hit record, textures, direction draw, BRDF + bookkeeping; restart step;
  *           hit-step executions, hit-step lanes, restart-step executions, restart-step lanes, reserved }. */
 int srtGetShadeProfile(SrtContext* ctx, uint64_t* out10);

@@ -26,7 +26,7 @@
 extern "C" {
 int srt_launch_render(const RenderArgs* a, int traversal, int count, int ldsTree, int grid, size_t ldsBytes, hipStream_t stream);
 int srt_render_occupancy(int traversal, int count, int ldsTree, size_t ldsBytes, int* blocksPerCU);
-int srt_launch_render_wf(const RenderArgs* a, int profile, int grid, size_t ldsBytes, hipStream_t stream);
+int srt_launch_render_wf(const RenderArgs* a, int profile, int count, int grid, size_t ldsBytes, hipStream_t stream);
 int srt_launch_finalize(const SrtFixedAccum* fix, float4* out, int n, int samples, hipStream_t stream);
 int srt_launch_sum_chunks(const float4* buf, float4* out, int n, int chunks, float limit, hipStream_t stream);
 int srt_launch_resolve(const ResolveArgs* a, hipStream_t stream);
@@ -1257,14 +1257,15 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
   const size_t lds = ldsTreeMode == 2 ? ldsTreeBytes + attBytes : ldsTree ? ldsTreeBytes : ldsBytesFor(ctx, p->maxBounce, a.scene.stackDepth, attGlobal256);
   if (lds > 160 * 1024) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->scene.stackDepth, lds);
   // The path-pool kernel (srt_wavefront.hip) serves what the LDS-resident tree serves, when its rings fit behind the
-  // tree: one 1024-thread workgroup per CU, wfPool contexts each.  The counting variant stays with srt_render_kernel.
+  // tree: one 1024-thread workgroup per CU, wfPool contexts each.  A counting launch runs the counting instance of the
+  // kernel the same launch without counting runs (srt_launch_render_wf): the counters belong to the kernel under test.
   // LDS behind the tree: 64 control words, six rings of 16-bit slots, and per context the (t, primitive) its walk ended at:
   // 18 bytes per context.  Ring capacity = pool size = the largest of 1024, 1536, 2048, 3072, 4096 that fits and does not
   // exceed the tunable (the headline scene's 129 KB tree leaves room for 1536).
   int wfPoolSize = 0, wfRingCap = 0, wfRingShift = 0, wfRingMul3 = 0;
   // Hybrid form: the tree's top in LDS, the rest read from global memory (scene.nodesWf, built at upload when the tree does
   // not fit or the tunable wf_resident_max asks for it).
-  const bool hybrid = p->traversal == SRT_TRAVERSE_FAITHFUL && ctx->scene.nodesWf != nullptr && ctx->tun.wavefront > 0 && !p->countStats &&
+  const bool hybrid = p->traversal == SRT_TRAVERSE_FAITHFUL && ctx->scene.nodesWf != nullptr && ctx->tun.wavefront > 0 &&
                       ctx->scene.primClass != nullptr;
   const size_t wfFixed = (size_t)(hybrid ? ctx->scene.wfResident : ctx->scene.numNodes) * 32 + 64 * sizeof(int32_t);
   const size_t wfPerContext = hybrid ? 20 : 18;  // six ring slots of 16 bits, t, the primitive (16 bits; 32 in the hybrid form)
@@ -1284,7 +1285,7 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
     wfPoolSize = wfRingCap;
   }
   const size_t wfLds = wfFixed + wfPerContext * wfRingCap;
-  const bool wavefront = wfRingCap > 0 && (hybrid || (ldsTree && ctx->tun.wavefront > 0 && ctx->scene.numNodes >= ctx->tun.wavefront && !p->countStats &&
+  const bool wavefront = wfRingCap > 0 && (hybrid || (ldsTree && ctx->tun.wavefront > 0 && ctx->scene.numNodes >= ctx->tun.wavefront &&
                                                       ctx->scene.primClass != nullptr));
   if (!(wavefront && hybrid)) a.scene.nodesWf = nullptr;  // srt_launch_render_wf picks the form by this pointer
   int perCU = 0;
@@ -1329,7 +1330,7 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
   ctx->lastLaunch[1] = grid;
   ctx->lastLaunch[2] = ldsTree || wavefront ? 1024 : 256;
   ctx->lastLaunch[3] = (int32_t)(wavefront ? wfLds : lds);
-  int rc = wavefront ? srt_launch_render_wf(&a, ctx->tun.wfProfile > 0, grid, wfLds, stream) : srt_launch_render(&a, p->traversal, p->countStats, ldsTreeMode, grid, lds, stream);
+  int rc = wavefront ? srt_launch_render_wf(&a, ctx->tun.wfProfile > 0, p->countStats, grid, wfLds, stream) : srt_launch_render(&a, p->traversal, p->countStats, ldsTreeMode, grid, lds, stream);
   if (rc) return fail(ctx, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
   HIP_OK(ctx, hipEventRecord(ctx->evStop, stream));
   ctx->timed = true;
@@ -1528,7 +1529,7 @@ static int srtRenderAovImpl(SrtContext* ctx, const SrtRenderParams* pIn, int32_t
 }
 int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAovRecord* hOut) { SRT_GUARDED(ctx, srtRenderAovImpl(ctx, p, depth, hOut)); }
 
-/* include/srt_hip_test.h: sub-step profile of the counting variant's last launch */
+/* include/srt_hip_test.h: the most recent render-kernel launch */
 int srtGetLaunchInfo(SrtContext* ctx, int32_t* out4) {
   if (!ctx || !out4) return 1;
   memcpy(out4, ctx->lastLaunch, sizeof ctx->lastLaunch);

@@ -145,7 +145,7 @@ struct RenderArgs {
   SrtFixedAccum* fix;   // atomic path: [localTile][64], items add their fixed-point partial sums here (null otherwise)
   float fixLimit;       // exact chunk sums: a partial sum of this much or more counts as infinite (toFixed36)
   unsigned long long* stats;  // 8 counters (SrtStats order) or nullptr
-  SrtAovRecord* aov;          // counting variant only: per-pixel record of the ray at bounce aovDepth (srtRenderAov)
+  SrtAovRecord* aov;          // counting variants only: per-pixel record of the ray at bounce aovDepth (srtRenderAov)
   int32_t aovDepth;
   float* attScratch;          // LDS-resident-tree variant: [3 * maxBounce + 3][grid * 1024] attenuation slots in global memory
   // work-item decomposition without divisions (restart step): groups of 64 items per unit, float reciprocals of

@@ -72,7 +72,10 @@ __device__ __forceinline__ uint32_t bufLoad1(Rsrc r, int off) { return __builtin
 // HYBRID: the tree does not fit into LDS.  Its top -- the first `resident` records of DevScene::nodesWf, the boxes a ray is
 // most likely to meet -- is kept there, the other records are read from global memory where the walk reaches them; a
 // node round asks for the global lanes' records first and visits LDS nodes with the other lanes while they are on the way.
-template <bool SINGLE, bool PROFILE, bool HYBRID>
+// COUNT (a countStats launch): the eight SrtStats counters with srt_render_kernel's definitions -> RenderArgs::stats[0..7],
+// and with RenderArgs::aov set the srtRenderAov record of every walk at bounce aovDepth of sample sampleFirst.  A walk
+// never leaves its lane before it ends (swapStep hands over finished walks only), so its counters stay in registers.
+template <bool SINGLE, bool PROFILE, bool HYBRID, bool COUNT>
 __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const RenderArgs a) {
 
   // whole tree in LDS: 16-bit references, DONE = the 16-bit "no reference" sign-extended, a link = two of them.
@@ -267,6 +270,12 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   V3 rcpD = mk(0.0f, 0.0f, 0.0f), negOR = mk(0.0f, 0.0f, 0.0f);
   auto atNode = [&]() { return cur >= 0; };
   auto atPrim = [&]() { return (uint32_t)cur > (uint32_t)DONE; };
+  // COUNT: samples, rays, node visits, box passes, triangle / sphere tests, shaded triangle hits, texel fetches (SrtStats
+  // order); the counters at the start of the lane's walk, and the pixel its walk is the srtRenderAov record of (-1: none).
+  // Every use is under `if constexpr`: the other instances' lambdas capture none of it, and their code stays as it was.
+  unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t walk0[4] = {0, 0, 0, 0};
+  int aovPixel = -1;
   auto popNext = [&]() {
     int next;
     if (HYBRID) {
@@ -286,6 +295,10 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     cur = next;
   };
   auto startTraversal = [&]() {  // world.hit(r, 0.001, infinity, rec)
+    if constexpr (COUNT) {
+      cnt[1]++;
+      for (int k = 0; k < 4; ++k) walk0[k] = (uint32_t)cnt[2 + k];
+    }
     rayA = lenSq(ray.d);
     const bool certified = (sc.fastDivScene != 0) & fastDivOperandOk(ray.o.x, ray.d.x) & fastDivOperandOk(ray.o.y, ray.d.y) &
                            fastDivOperandOk(ray.o.z, ray.d.z);
@@ -307,6 +320,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     Ray r;
     const DevCamera cam = cameraFromKernarg();
     cameraRay(cam, u, v, rng, r);
+    if constexpr (COUNT) cnt[0]++;
     bufStore4(rsPool, at, make_float4(r.o.x, r.o.y, r.o.z, r.time));
     bufStore4(rsPool, at + 16, make_float4(r.d.x, r.d.y, r.d.z, 0.0f));
     u32x4 Cn;
@@ -350,6 +364,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           float t;
           bool ok;
           if (pr & 1) {
+            if constexpr (COUNT) cnt[5]++;
             const int off = (pr >> 1) * 48;
             const float4 s0 = bufLoad4(rsSpheres, off), s1 = bufLoad4(rsSpheres, off + 16);
             V3 center = mk(s0.x, s0.y, s0.z);
@@ -359,6 +374,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
             }
             ok = sphereHitV(center, s0.w, ray, rayA, a.tMin, closest, t);
           } else {
+            if constexpr (COUNT) cnt[4]++;
             const int off = (pr >> 1) * 48;
             ok = triHitV<false>(bufLoad4(rsTris, off), bufLoad4(rsTris, off + 16), bufLoad4(rsTris, off + 32), ray, a.tMin, closest, t);
           }
@@ -390,6 +406,10 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           pLanes[7] += mu != 0 ? 1 : 0;
         }
         if (undecided) hitBox = boxHit(n0, n1, ray, a.tMin, closest);
+        if constexpr (COUNT) {
+          cnt[2]++;
+          if (hitBox) cnt[3]++;
+        }
         link = __float_as_int(n1.w);
         cur = hitBox ? __float_as_int(n0.w) : (link >> LINK_SHIFT);
         if (!SINGLE && !singleRoot && cur == DONE && ++w < sc.numWorld) {
@@ -478,6 +498,28 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
       }
       asm volatile("" ::: "memory");  // the ring slot is written after them (one wave's LDS operations execute in order)
       enqueue(!fin ? -1 : (hit ? WF_RING_HIT + cls : WF_RING_RESTART), path);
+      if constexpr (COUNT) {
+        if (fin && aovPixel >= 0) {  // as srt_render_kernel's writeAov: the finished walk's ray, hit and counters
+          SrtAovRecord r;
+          r.o[0] = ray.o.x; r.o[1] = ray.o.y; r.o[2] = ray.o.z;
+          r.d[0] = ray.d.x; r.d[1] = ray.d.y; r.d[2] = ray.d.z;
+          r.time = ray.time;
+          r.valid = 1;
+          r.prim = SRT_NO_HIT;
+          r.t = 0.0f;
+          if (hitRef != DONE) {
+            const int pr = ~hitRef;
+            r.prim = (pr & 1) ? sc.sphPrimId[pr >> 1] : sc.triPrimId[pr >> 1];
+            r.t = closest;
+          }
+          r.nodeVisits = (int32_t)((uint32_t)cnt[2] - walk0[0]);
+          r.boxPasses = (int32_t)((uint32_t)cnt[3] - walk0[1]);
+          r.triTests = (int32_t)((uint32_t)cnt[4] - walk0[2]);
+          r.sphereTests = (int32_t)((uint32_t)cnt[5] - walk0[3]);
+          r.pad[0] = r.pad[1] = 0;
+          a.aov[aovPixel] = r;
+        }
+      }
       if (fin) {
         path = -1;
         hitRef = DONE;
@@ -489,6 +531,16 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
         ray.time = A.w;
         path = id;
         startTraversal();
+        if constexpr (COUNT) {
+          // the new ray's bounce, sample and pixel (context words C.w, E.y, E.w): is its walk the AOV record of its pixel?
+          aovPixel = -1;
+          if (a.aov) {
+            const uint32_t cw = bufLoad1(rsPool, (id << 7) + 44);
+            const u32x4 E = __builtin_amdgcn_raw_buffer_load_b128(rsPool, (id << 7) + 64, 0, 0);
+            const int px = (int)(E.w & 0xffffu), py = (int)(E.w >> 16);
+            if ((int)(cw & 0xffu) == a.aovDepth && (int)E.y == a.sampleFirst) aovPixel = py * a.imageWidth + px;
+          }
+        }
       }
       if (PROFILE) {
         const unsigned long long q3 = clock64();
@@ -534,8 +586,10 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           V3 att, emitted;
           Ray next;
           uint32_t fetches = 0;
+          if constexpr (COUNT) cnt[6] += rec.isTri ? 1 : 0;
           const unsigned long long h2 = PROFILE ? clock64() : 0;
-          const bool scattered = shade<false, true>(sc, rsTexels, rIn, rec, rng, att, next, emitted, fetches, nullptr);
+          const bool scattered = shade<COUNT, true>(sc, rsTexels, rIn, rec, rng, att, next, emitted, fetches, nullptr);
+          if constexpr (COUNT) cnt[7] += fetches;
           if (PROFILE && bestRing == WF_RING_HIT + 1) {  // the ground's class: claim + context / record / shade (lane 0's clocks)
             const unsigned long long h3 = clock64();
             pSaw[1] += h1 - h0;
@@ -842,18 +896,35 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     }
   }
   flushProfile();
+  if constexpr (COUNT) {  // (every lane of the wave is here: the loop above is left by wave-uniform decisions only)
+    if (a.stats) {
+      for (int k = 0; k < 8; ++k) {
+        unsigned long long x = cnt[k];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+        if (lane == 0) atomicAdd(&a.stats[k], x);
+      }
+    }
+  }
 }
 
 extern "C" {
-int srt_launch_render_wf(const RenderArgs* a, int profile, int grid, size_t ldsBytes, hipStream_t stream) {
+// count: the COUNT instance of the kernel the same launch without counting runs (a counting launch takes no profile)
+int srt_launch_render_wf(const RenderArgs* a, int profile, int count, int grid, size_t ldsBytes, hipStream_t stream) {
   typedef void (*Kernel)(const RenderArgs);
   // (hybrid form: the single-root instance is worth +12 to +15 % on cache-resident trees and costs 5 % on the HBM-bound
   // soups of 4 M triangles and more, where the shorter visit only crowds the memory system: profiles/r03/hybrid.txt)
-  const Kernel k = a->scene.nodesWf ? (profile ? srt_render_wf_kernel<false, true, true>
-                                       : a->scene.numWorld == 1 && a->scene.numNodes <= (1 << 20) ? srt_render_wf_kernel<true, false, true>
-                                                                                                   : srt_render_wf_kernel<false, false, true>)
-                   : profile       ? srt_render_wf_kernel<false, true, false>
-                                   : (a->scene.numWorld == 1 ? srt_render_wf_kernel<true, false, false> : srt_render_wf_kernel<false, false, false>);
+  Kernel k;
+  if (a->scene.nodesWf) {
+    const bool single = a->scene.numWorld == 1 && a->scene.numNodes <= (1 << 20);
+    k = count     ? (single ? srt_render_wf_kernel<true, false, true, true> : srt_render_wf_kernel<false, false, true, true>)
+        : profile ? srt_render_wf_kernel<false, true, true, false>
+                  : (single ? srt_render_wf_kernel<true, false, true, false> : srt_render_wf_kernel<false, false, true, false>);
+  } else {
+    const bool single = a->scene.numWorld == 1;
+    k = count     ? (single ? srt_render_wf_kernel<true, false, false, true> : srt_render_wf_kernel<false, false, false, true>)
+        : profile ? srt_render_wf_kernel<false, true, false, false>
+                  : (single ? srt_render_wf_kernel<true, false, false, false> : srt_render_wf_kernel<false, false, false, false>);
+  }
   if (ldsBytes > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
     if (e != hipSuccess) return (int)e;

@@ -364,12 +364,12 @@ def test_scatter_known_answers(ctx, oracle, abi, scenes):
 @pytest.mark.parametrize("name,bounces", [("masterchief", 4), ("spheres", 8), ("iron", 4)])
 def test_render_kernel_traversal_per_ray_vs_oracle(ctx, oracle, abi, scenes, camera, name, bounces, node_path):
     """srtTraceRays runs its own kernel; this pins the RENDER kernel's node / primitive steps ray by ray
-    (VERDICT r1 item 4): srtRenderAov records, per pixel, the ray srt_render_kernel traced at bounce
-    `depth` of the first sample and the hit, t and counters its scheduler-driven traversal (one-FMA slab
-    certificate, LDS stack with sentinel, node bursts) produced; the oracle's world.hit() (bvh.h:97-105
-    recursion, IEEE divisions) on the same rays must agree bit for bit, counters included."""
-    if node_path in ("wavefront", "hybrid"):
-        pytest.skip("a counting launch of the path-pool kernel IS the step-scheduler kernel over the same threaded tree (lds_tree)")
+    (VERDICT r1 item 4): srtRenderAov records, per pixel, the ray the render kernel traced at bounce `depth` of the first
+    sample and the hit, t and counters its traversal produced -- the counting instance of whichever kernel the same launch
+    without counting runs: the step scheduler's walk (one-FMA slab certificate, stack or thread links, node bursts) for
+    lds_tree / l1_nodes, the path-pool kernel's for wavefront / hybrid (lanes as traversal engines, hybrid form: resident /
+    far records, 32-bit links).  The oracle's world.hit() (bvh.h:97-105 recursion, IEEE divisions) on the same rays must
+    agree bit for bit, counters included."""
     sb = scenes[name]
     ctx.upload_scene(sb)
     ctx.set_camera(camera)
@@ -379,17 +379,236 @@ def test_render_kernel_traversal_per_ray_vs_oracle(ctx, oracle, abi, scenes, cam
     seen = 0
     for depth in range(3):
         aov = ctx.render_aov(p, depth).reshape(-1)
-        rec = aov[aov["valid"] == 1]
-        if depth == 0:
-            assert len(rec) == W * H  # every pixel traces a camera ray
-        assert len(rec) > 1000
-        rays = np.zeros(len(rec), abi.RAY_DTYPE)
-        rays["o"], rays["d"], rays["time"] = rec["o"], rec["d"], rec["time"]
-        rays["tMin"], rays["tMax"] = 0.001, np.inf
-        want = osc.trace(rays)
-        assert np.array_equal(rec["prim"], want["prim"]), (name, depth)
-        m = want["prim"] >= 0
-        assert np.array_equal(_bits(rec["t"][m]), _bits(want["t"][m])), (name, depth)
-        assert_counters_equal(rec, want)
-        seen += len(rec)
+        mode = ctx.launch_info()["lds_tree_mode"]
+        if node_path == "wavefront":
+            assert mode == 3, (name, mode)
+        elif node_path == "hybrid":  # (wf_resident_max = 24: a tree of no more than 24 nodes is not split)
+            assert mode == (4 if len(ctx.bvh(0)) > 24 else 3), (name, mode)
+        else:
+            assert mode in ((1, 2) if node_path == "lds_tree" else (0,)), (name, mode)
+        seen += assert_aov_matches_oracle(aov, osc, abi, (name, depth), min_rays=W * H if depth == 0 else 1001)
     assert seen > 1.5 * W * H
+
+
+def assert_aov_matches_oracle(aov, osc, abi, what, min_rays=1):
+    """srtRenderAov's records (valid ones) against the oracle's world.hit() on the same rays: primitive, the bits of t and
+    the four traversal counters exactly.  Returns the number of records."""
+    rec = aov.reshape(-1)
+    rec = rec[rec["valid"] == 1]
+    assert len(rec) >= min_rays, (what, len(rec))
+    rays = np.zeros(len(rec), abi.RAY_DTYPE)
+    rays["o"], rays["d"], rays["time"] = rec["o"], rec["d"], rec["time"]
+    rays["tMin"], rays["tMax"] = 0.001, np.inf
+    want = osc.trace(rays)
+    assert np.array_equal(rec["prim"], want["prim"]), what
+    m = want["prim"] >= 0
+    assert np.array_equal(_bits(rec["t"][m]), _bits(want["t"][m])), what
+    for f in ("nodeVisits", "boxPasses", "triTests", "sphereTests"):
+        bad = np.flatnonzero(rec[f] != want[f])
+        assert len(bad) == 0, (what, f, len(bad), rec[f][bad[:4]], want[f][bad[:4]])
+    return len(rec)
+
+
+class path_pool_form:
+    """Tunables for one form of the path-pool kernel for the scenes uploaded inside the block: "wavefront" (the whole tree
+    in LDS) or "hybrid" (only `resident` nodes in LDS, the rest read from global memory; read at upload), or "natural"
+    (the library's defaults: a tree beyond LDS gets the hybrid form by itself).  Restores the tunables afterwards."""
+
+    def __init__(self, ctx, form, resident=24):
+        self.ctx, self.form, self.resident = ctx, form, resident
+
+    def __enter__(self):
+        self.saved = {k: self.ctx.get_tunable(k) for k in ("lds_tree", "wavefront", "wf_resident_max", "wf_hybrid")}
+        if self.form != "natural":
+            self.ctx.set_tunable("lds_tree", 1)
+            self.ctx.set_tunable("wavefront", 1)  # every tree that fits, however small
+            self.ctx.set_tunable("wf_hybrid", 1)
+            self.ctx.set_tunable("wf_resident_max", self.resident if self.form == "hybrid" else 0)
+        return self
+
+    def __exit__(self, *exc):
+        for k, v in self.saved.items():
+            self.ctx.set_tunable(k, v)
+
+    def mode(self):
+        return {"wavefront": 3, "hybrid": 4, "natural": 4}[self.form]
+
+
+def aov_per_ray_vs_oracle_and_step_scheduler(ctx, osc, abi, p, depths, mode, what, min_rays=1):
+    """For each bounce depth: the path-pool kernel's AOV launch runs `mode` (3 whole tree in LDS, 4 hybrid form), its
+    records match the oracle's world.hit() per ray, and they are byte-identical to the step-scheduler kernel's records
+    (tunable wavefront = 0) -- the same rays at the same bounces, so the path pool's depth bookkeeping is pinned too.
+    Returns the number of records per depth."""
+    counts = []
+    wf = ctx.get_tunable("wavefront")
+    for depth in depths:
+        aov = ctx.render_aov(p, depth)
+        assert ctx.launch_info()["lds_tree_mode"] == mode, (what, depth, ctx.launch_info())
+        counts.append(assert_aov_matches_oracle(aov, osc, abi, (what, depth), min_rays))
+        ctx.set_tunable("wavefront", 0)
+        try:
+            step = ctx.render_aov(p, depth)
+            assert not ctx.launch_info()["wavefront"], ctx.launch_info()
+        finally:
+            ctx.set_tunable("wavefront", wf)
+        assert aov.tobytes() == step.tobytes(), (what, depth, int((aov != step).sum()))
+    return counts
+
+
+def test_path_pool_per_ray_on_a_tree_beyond_lds(ctx, oracle, abi, srt, camera):
+    """The 20k-triangle soup: some 24 k nodes (750 KB), far beyond LDS, and primitive references beyond 16 bits -- the
+    hybrid form the library picks by itself (the LDS keeps the top of the tree, the walk reads the rest from global memory, 32-bit thread
+    links, primSecond for leaves whose two objects are not neighbours).  Per ray at bounces 0, 1, 2 against the oracle and
+    the step scheduler, then a small frame's counters EXACTLY equal to the oracle's."""
+    sb = srt.scenes.scene_soup(20000, seed=3)
+    with path_pool_form(ctx, "natural"):
+        ctx.upload_scene(sb)
+        ctx.set_camera(camera)
+        assert len(ctx.bvh(0)) * 32 > 160 * 1024 and 2 * 20000 > 0x7fff  # beyond LDS; 32-bit links (~(index << 1 | sphere))
+        osc = oracle.OracleScene(sb)
+        W, H = 320, 180
+        p = abi.default_render_params(W, H, 1, 4, seed=13)
+        n = aov_per_ray_vs_oracle_and_step_scheduler(ctx, osc, abi, p, (0, 1, 2), 4, "soup20k", min_rays=1000)
+        assert n[0] == W * H
+        p = abi.default_render_params(96, 54, 2, 4, seed=14, count_stats=1)
+        acc, _ = ctx.render_image(p)
+        assert ctx.launch_info()["lds_tree_mode"] == 4
+        st = ctx.stats()
+        want_acc, _, want_st = osc.render(camera, p, oracle.RNG_COUNTER, threads=min(16, os.cpu_count() or 8))
+        for k in ("samples", "rays", "nodeVisits", "boxPasses", "triTests", "sphereTests", "shadedTriHits", "texelFetches"):
+            assert st[k] == want_st[k], (k, st[k], want_st[k])
+        assert (_bits(acc) == _bits(want_acc)).all(axis=-1).mean() >= 0.995
+
+
+def _multi_root_worlds(abi):
+    """Worlds of more than one root (hittableList over several items, main.cpp:153): "two_bvh" of
+    test_world_and_material_variants_vs_oracle (a single-object leaf and a two-sphere node as two trees), and a list of
+    plain spheres around a tree (primitive roots before and after it)."""
+    def spheres(sb, n):
+        mats = (sb.metal((0.8, 0.7, 0.6), 0.2), sb.dielectric(1.5), sb.pbr(albedo_tex=sb.checker((0.2, 0.3, 0.1), (0.9, 0.9, 0.9))))
+        rng = np.random.default_rng(n)
+        for i in range(n):
+            sb.add_sphere(tuple(rng.uniform(-3, 3, 3) + np.array([0.0, 2.0, -1.0])), float(rng.uniform(0.3, 0.9)), mats[i % 3])
+        sb.add_sphere((0.0, -1000.0, 0.0), 1000.0, mats[2])
+    out = {}
+    sb = abi.SceneBuilder()
+    m1, m2 = sb.metal((0.8, 0.7, 0.6), 0.2), sb.dielectric(1.5)
+    sb.add_sphere((0.0, 2.0, 0.0), 1.0, m1)
+    sb.add_sphere((-2.2, 2.0, 0.0), 1.0, m2)
+    sb.add_sphere((0.0, -1000.0, 0.0), 1000.0, sb.pbr(albedo_tex=sb.checker((0.2, 0.3, 0.1), (0.9, 0.9, 0.9))))
+    sb.world_bvh(0, 1)
+    sb.world_bvh(1, 2)
+    out["two_bvh"] = sb
+    sb = abi.SceneBuilder()
+    spheres(sb, 9)
+    sb.world_prim(0)
+    sb.world_bvh(1, 8)
+    sb.world_prim(9)  # the ground
+    out["list_around_bvh"] = sb
+    return out
+
+
+@pytest.mark.parametrize("form", ["wavefront", "hybrid"])
+@pytest.mark.parametrize("variant", ["two_bvh", "list_around_bvh"])
+def test_path_pool_per_ray_multi_root_worlds(ctx, oracle, abi, camera, variant, form):
+    """Several roots: the path-pool kernel's SINGLE = false instance, which walks on to the next root of the world list
+    (worldRef: DevScene::world in the whole-tree form, worldWf in the hybrid form) when a walk is done.  The hybrid form is
+    forced with one resident node, so that roots lie outside LDS.  Per ray at bounces 0, 1, 2."""
+    sb = _multi_root_worlds(abi)[variant]
+    with path_pool_form(ctx, form, resident=1):
+        ctx.upload_scene(sb)
+        ctx.set_camera(camera)
+        osc = oracle.OracleScene(sb)
+        p = abi.default_render_params(160, 90, 1, 6, seed=78)
+        n = aov_per_ray_vs_oracle_and_step_scheduler(ctx, osc, abi, p, (0, 1, 2), path_pool_form(ctx, form).mode(), variant, min_rays=500)
+        assert n[0] == 160 * 90
+
+
+def _mirror_room(abi):
+    """A closed room: the camera and a few spheres inside a fuzzy-metal sphere, lit by a small light.  Nearly every path
+    goes on bouncing until maxBounce (only the light ends one early), so deep bounces are the rule."""
+    sb = abi.SceneBuilder()
+    sb.add_sphere((0.0, 0.0, 0.0), 30.0, sb.metal((0.9, 0.85, 0.8), 0.3))
+    sb.add_sphere((0.0, 1.0, 0.0), 1.0, sb.pbr(albedo=(0.7, 0.5, 0.3, 1.0), roughness=0.6))
+    sb.add_sphere((-2.5, 1.5, -1.0), 1.2, sb.dielectric(1.5))
+    sb.add_sphere((2.5, 1.2, -0.5), 0.9, sb.metal((0.6, 0.7, 0.8), 0.05))
+    sb.add_sphere((0.0, 8.0, -3.0), 4.0, sb.light((6.0, 5.0, 4.0)))
+    sb.add_sphere((1.0, -0.5, 2.0), 0.4, sb.pbr(albedo_tex=sb.checker((0.2, 0.3, 0.1), (0.9, 0.9, 0.9))))
+    sb.world_bvh(0, None, 0.0, 1.0)
+    return sb
+
+
+@pytest.mark.parametrize("form", ["wavefront", "hybrid"])
+def test_path_pool_per_ray_deep_bounces(ctx, oracle, abi, camera, form):
+    """Bounces past the four a context line holds attenuations for (wfAttHi) and the depth bookkeeping of the hit step:
+    maxBounce 10, per ray at bounces 5 and 8; the frame's accumulators bit-identical to the step-scheduler kernel's and
+    close to the oracle's (deep paths through pbr surfaces carry more libm-ulp differences than the other frames)."""
+    sb = _mirror_room(abi)
+    with path_pool_form(ctx, form, resident=2):
+        ctx.upload_scene(sb)
+        ctx.set_camera(camera)
+        osc = oracle.OracleScene(sb)
+        W, H = 160, 90
+        p = abi.default_render_params(W, H, 1, 10, seed=41)
+        n = aov_per_ray_vs_oracle_and_step_scheduler(ctx, osc, abi, p, (5, 8), path_pool_form(ctx, form).mode(), "mirror room",
+                                                     min_rays=W * H // 4)
+        assert n[0] >= n[1] > 0
+        p = abi.default_render_params(W, H, 4, 10, seed=42)
+        acc, _ = ctx.render_image(p)
+        assert ctx.launch_info()["lds_tree_mode"] == path_pool_form(ctx, form).mode()
+        ctx.set_tunable("wavefront", 0)
+        step, _ = ctx.render_image(p)
+        assert not ctx.launch_info()["wavefront"]
+    assert _bits(acc).tobytes() == _bits(step).tobytes()
+    want, _, _ = osc.render(camera, p, oracle.RNG_COUNTER, threads=min(16, os.cpu_count() or 8), want_rgba=False, want_stats=False)
+    assert np.array_equal(np.isnan(acc), np.isnan(want)) and np.array_equal(acc[..., 3], want[..., 3])
+    assert (_bits(acc[..., :3]) == _bits(want[..., :3])).all(axis=-1).mean() >= 0.9
+    fin = np.isfinite(want[..., :3])
+    rel = np.abs(acc[..., :3][fin].astype(np.float64) - want[..., :3][fin]) / np.maximum(np.abs(want[..., :3][fin]), 1e-3)
+    assert rel.mean() < 1e-3, rel.mean()
+
+
+@pytest.mark.parametrize("form", ["wavefront", "hybrid"])
+def test_path_pool_per_ray_frame_smaller_than_a_pool(ctx, oracle, abi, scenes, camera, form):
+    """A 33 x 17 frame: fewer work items than a workgroup has contexts (partial tiles, most contexts never get an item).
+    Per ray at bounces 0, 1, 2 on the main.cpp scene, and its counters exactly equal to the oracle's."""
+    sb = scenes["masterchief"]
+    with path_pool_form(ctx, form, resident=300):
+        ctx.upload_scene(sb)
+        ctx.set_camera(camera)
+        osc = oracle.OracleScene(sb)
+        p = abi.default_render_params(33, 17, 1, 4, seed=6)
+        n = aov_per_ray_vs_oracle_and_step_scheduler(ctx, osc, abi, p, (0, 1, 2), path_pool_form(ctx, form).mode(), "33x17")
+        assert n[0] == 33 * 17
+        p = abi.default_render_params(33, 17, 3, 4, seed=6, count_stats=1)
+        acc, _ = ctx.render_image(p)
+        assert ctx.launch_info()["lds_tree_mode"] == path_pool_form(ctx, form).mode()
+        st = ctx.stats()
+        _, _, want_st = osc.render(camera, p, oracle.RNG_COUNTER, threads=4, want_rgba=False)
+        for k in ("samples", "rays", "nodeVisits", "boxPasses", "triTests", "sphereTests"):
+            assert st[k] == want_st[k], (k, st[k], want_st[k])
+
+
+@pytest.mark.parametrize("form", ["wavefront", "hybrid"])
+@pytest.mark.parametrize("case", ["config1", "masterchief_240p", "sphere_field"])
+def test_path_pool_counting_instance_does_not_perturb_the_path(ctx, abi, srt, scenes, camera, case, form):
+    """A counting launch runs the counting instance of the kernel the production launch runs (same form, same launch
+    mode); its counters must come from the very paths the production kernel traces: the accumulators are the same bits."""
+    name, W, H, spp, mb, seed, resident = {"config1": ("spheres", 426, 240, 64, 8, 2024, 1),
+                                           "masterchief_240p": ("masterchief", 426, 240, 16, 4, 99, 300),
+                                           "sphere_field": ("sphere_field", 426, 240, 8, 8, 31, 100)}[case]
+    sb = srt.scenes.scene_sphere_field() if name == "sphere_field" else scenes[name]
+    with path_pool_form(ctx, form, resident=resident):
+        ctx.upload_scene(sb)
+        ctx.set_camera(camera)
+        p = abi.default_render_params(W, H, spp, mb, seed=seed)
+        acc, rgba = ctx.render_image(p)
+        mode = ctx.launch_info()["lds_tree_mode"]
+        assert mode == path_pool_form(ctx, form).mode(), (case, mode)
+        p.countStats = 1
+        acc_c, rgba_c = ctx.render_image(p)
+        assert ctx.launch_info()["lds_tree_mode"] == mode
+        st = ctx.stats()
+    assert _bits(acc_c).tobytes() == _bits(acc).tobytes(), (case, form)
+    assert np.array_equal(rgba_c, rgba)
+    assert st["samples"] == W * H * spp and st["rays"] >= st["samples"] and st["nodeVisits"] > st["rays"], st

@@ -1,4 +1,6 @@
-"""Scheduler profile of the counting variant: time share, executions and lane fill per step kind."""
+"""Scheduler profile of the step-scheduler kernel's counting variant: time share, executions and lane fill per step kind.
+(The path-pool kernel's counting instance has no such profile -- tools/wf_profile.py profiles that kernel -- so the
+step scheduler is asked for with tunable wavefront = 0.)"""
 import importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,6 +11,7 @@ scene = sys.argv[1] if len(sys.argv) > 1 else "masterchief"
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 W, H, mb = 1280, 720, 4
 ctx = dev.Context(0)
+ctx.set_tunable("wavefront", 0)  # a counting launch runs the counting instance of whichever kernel the launch would run
 ctx.upload_scene(srt.scenes.SCENES[scene]())
 ctx.set_camera(dev.make_camera(abi.default_camera_params()))
 local = torch.zeros((dev.num_local_tiles(W, H, 1), 64, 4), dtype=torch.float32, device="cuda")
