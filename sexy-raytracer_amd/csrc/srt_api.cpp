@@ -24,9 +24,6 @@
 #include "srt_thread.h"
 
 extern "C" {
-int srt_launch_render(const RenderArgs* a, int traversal, int count, int ldsTree, int grid, size_t ldsBytes, hipStream_t stream);
-int srt_render_occupancy(int traversal, int count, int ldsTree, size_t ldsBytes, int* blocksPerCU);
-int srt_launch_render_wf(const RenderArgs* a, int profile, int count, int grid, size_t ldsBytes, hipStream_t stream);
 int srt_launch_finalize(const SrtFixedAccum* fix, float4* out, int n, int samples, hipStream_t stream);
 int srt_launch_sum_chunks(const float4* buf, float4* out, int n, int chunks, float limit, hipStream_t stream);
 int srt_launch_resolve(const ResolveArgs* a, hipStream_t stream);
@@ -36,7 +33,6 @@ int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0,
 int srt_ploc_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
                    uint8_t* outAxis, int base, int radius, int* depthOut);
 int srt_pair_nodes(const DevScene* sc, float time0, float time1, float4* out);
-int srt_wide_nodes(const float4* nodes2, int numNodes, float4* out);
 int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint64_t seed, int n,
                        hipStream_t stream);
 }
@@ -235,7 +231,6 @@ struct Tunables {
   int keepEighths;
   int ldsTree;
   int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
-  int wideNodes, attGlobal;
   int wfHybrid, wfResidentMax, wfFarRounds;
 };
 
@@ -268,7 +263,8 @@ struct SrtContext {
   int32_t* dWfError = nullptr;
   DeviceBuffer tileTable;   // RenderArgs::tileXY for the image size and tile order below
   int32_t tileTableKey[3] = {0, 0, 0};
-  int32_t lastLaunch[4] = {0, 0, 0, 0};  // srtGetLaunchInfo
+  RenderPlan lastPlan{};  // the most recent render launch (srtGetLaunchInfo)
+  int32_t lastGrid = 0;
   hipEvent_t evStart = nullptr, evStop = nullptr;
   bool timed = false;
   SrtStats lastStats{};
@@ -357,13 +353,6 @@ const TunableName kTunables[] = {
     {"wf_swap_min", "SRT_WF_SWAP_MIN", &Tunables::wfSwapMin, 0},
     {"wf_swap_big", "SRT_WF_SWAP_BIG", &Tunables::wfSwapBig, 32},
     {"wf_profile", "SRT_WF_PROFILE", &Tunables::wfProfile, 0},  // 1: the profiling variant (tools/wf_profile.py, srtGetWfProfile)
-    // closest-hit traversal: 128-byte records with four boxes (1, read at srtUploadScene) instead of the 64-byte two-box
-    // records (0).  Measured, not faster: the same bytes in half as many, twice as large random requests, at 2 instead
-    // of 3 workgroups per CU (three pending references per level) -- profiles/r03/wide_nodes.txt.  Off.
-    {"wide_nodes", "SRT_WIDE_NODES", &Tunables::wideNodes, 0},
-    // closest-hit traversal of trees with at least this many nodes: attenuation stacks in global memory (4 instead of 3
-    // workgroups per CU); 0 = never.  +3 % at 4 M triangles, -5 % at 10 M (same file).  Off.
-    {"att_global", "SRT_ATT_GLOBAL", &Tunables::attGlobal, 0},
     // path-pool kernel over a tree that does not fit into LDS: its top (the boxes with the largest surface, closed upward)
     // stays in LDS, the rest is read from global memory (srt_wavefront.hip HYBRID).  wf_hybrid 0 = never (such scenes run
     // the 256-thread kernel); wf_resident_max > 0 caps the resident nodes, which also sends trees that WOULD fit down
@@ -376,9 +365,9 @@ const TunableName kTunables[] = {
     {"wf_far_rounds", "SRT_WF_FAR_ROUNDS", &Tunables::wfFarRounds, 0},
 };
 
-size_t ldsBytesFor(const SrtContext* ctx, int maxBounce, int stackDepth, bool attGlobal = false) {
+size_t ldsBytesFor(const SrtContext* ctx, int maxBounce, int stackDepth) {
   // per-thread stacks plus one word of queue state per wave (srt_render_kernel)
-  return (size_t)(stackDepth + 2 + (attGlobal ? 0 : 3 * maxBounce + 3)) * 256 * sizeof(int32_t) + 4 * sizeof(int32_t);
+  return (size_t)(stackDepth + 2 + 3 * maxBounce + 3) * SRT_BLOCK * sizeof(int32_t) + 4 * sizeof(int32_t);
 }
 
 }  // namespace
@@ -954,18 +943,6 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
     s.nodes2 = static_cast<const float4*>(b2.p);
     int rc2 = srt_pair_nodes(&s, t0, t1, static_cast<float4*>(b2.p));
     if (rc2) return fail(ctx, "pairing the node records failed: %s", hipGetErrorString((hipError_t)rc2));
-    // ... and the 128-byte records with four boxes, for trees big enough to be fetched from HBM (and small enough for
-    // index * 128 to stay a 31-bit byte offset)
-    if (ctx->tun.wideNodes > 0 && s.numNodes >= 2 && s.numNodes < (1 << 24)) {
-      DeviceBuffer b4;
-      b4.bytes = (size_t)s.numNodes * 128;
-      HIP_OK(ctx, hipMalloc(&b4.p, b4.bytes));
-      ctx->sceneBuffers.push_back(b4);
-      rc2 = srt_wide_nodes(s.nodes2, s.numNodes, static_cast<float4*>(b4.p));
-      if (rc2) return fail(ctx, "building the four-box records failed: %s", hipGetErrorString((hipError_t)rc2));
-      s.nodes4 = static_cast<const float4*>(b4.p);
-      s.wideStackDepth = 3 * ((ctx->bvhDepth + 1) / 2 + 1) + 1;
-    }
   }
   const bool lbvhOk = lbvhCertificate;
   if (nodes.size() / 2 > (size_t)SRT_MAX_NODES) return fail(ctx, "scene: %zu BVH nodes exceed the %d the device references can address", nodes.size() / 2, SRT_MAX_NODES);
@@ -1096,6 +1073,68 @@ static int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
   if (p->tileStride < 1 || p->tileFirst < 0 || p->tileFirst >= p->tileStride) return fail(ctx, "render: bad tile split %d/%d", p->tileFirst, p->tileStride);
   if (p->sppChunks < 0 || p->sppChunks > p->spp) return fail(ctx, "render: sppChunks must be in [0, spp] (0 = library default)");
   return 0;
+}
+
+// The render launch for these parameters: the kernel form and the instance of it, workgroup and LDS size, the path-pool
+// kernel's rings.  Every choice of kernel is made here; srtRenderTilesImpl allocates and launches what it says.
+static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p) {
+  const DevScene& sc = ctx->scene;
+  const Tunables& tun = ctx->tun;
+  RenderPlan plan{};
+  const bool faithful = p->traversal == SRT_TRAVERSE_FAITHFUL;
+  plan.closest = p->traversal == SRT_TRAVERSE_CLOSEST;
+  plan.count = p->countStats != 0;
+  // FAITHFUL on a scene whose whole node array fits into a CU's LDS: the LDS-resident-tree kernel (srt_render_kernel
+  // LDSTREE), one workgroup of 1024 threads per CU, walking the threaded copy of the tree (no per-lane stack).
+  const size_t ldsTreeBytes = (size_t)sc.numNodes * 32 + 16 * sizeof(int32_t);  // threaded tree: no stacks
+  // (Even trees of a few dozen nodes gain: their frames are shading-bound, and the 128-register kernel keeps a hit's
+  // texel loads in flight together where the 96-register one spills, profiles/r02/lds_tree.txt.)
+  const bool ldsTree = faithful && tun.ldsTree > 0 && sc.numNodes >= tun.ldsTree && ldsTreeBytes <= 160 * 1024 &&
+                       sc.nodeThread != nullptr;  // thread links exist: host-built trees, 15-bit references (srtUploadScene)
+  // ... and when the attenuation stacks fit behind them as well they stay in LDS (form 2): +2 to +5 % on the small
+  // BASELINE scenes; the headline scene's tree leaves no room (form 1: they live in global memory)
+  const size_t attBytes = (size_t)(3 * p->maxBounce + 3) * SRT_BLOCK_TREE * sizeof(float);
+  // The path-pool kernel (srt_wavefront.hip) serves what the LDS-resident tree serves, when its rings fit behind the
+  // tree: one 1024-thread workgroup per CU, wfPool contexts each.  A counting launch runs the counting instance of the
+  // kernel the same launch without counting runs: the counters belong to the kernel under test.
+  // LDS behind the tree: 64 control words, six rings of 16-bit slots, and per context the (t, primitive) its walk ended at:
+  // 18 bytes per context.  Ring capacity = pool size = the largest of 1024, 1536, 2048, 3072, 4096 that fits and does not
+  // exceed the tunable (the headline scene's 129 KB tree leaves room for 1536).
+  // Hybrid form: the tree's top in LDS, the rest read from global memory (scene.nodesWf, built at upload when the tree does
+  // not fit or the tunable wf_resident_max asks for it).
+  const bool hybrid = faithful && sc.nodesWf != nullptr && tun.wavefront > 0 && sc.primClass != nullptr;
+  const size_t wfFixed = (size_t)(hybrid ? sc.wfResident : sc.numNodes) * 32 + 64 * sizeof(int32_t);
+  const size_t wfPerContext = hybrid ? 20 : 18;  // six ring slots of 16 bits, t, the primitive (16 bits; 32 in the hybrid form)
+  // ring counters are 32-bit and a 3 * 2^j ring cannot take their wrap-around: such rings only while a workgroup's
+  // enqueues stay far below 2^32 (about three per sample)
+  const int numLocalTiles = srtNumLocalTiles(p->imageWidth, p->imageHeight, p->tileStride);
+  const double enqueuesPerGroup = 4.0 * (double)numLocalTiles * SRT_TILE_PIXELS * (double)p->spp / std::max(1, ctx->prop.multiProcessorCount);
+  static const struct { int cap, shift, mul3; } kRings[] = {{4096, 12, 0}, {3072, 10, 1}, {2048, 11, 0}, {1536, 9, 1}, {1024, 10, 0}};
+  for (const auto& r : kRings) {
+    if (r.cap > std::max(1024, tun.wfPool) || wfFixed + wfPerContext * r.cap > 160 * 1024) continue;
+    if (r.mul3 && enqueuesPerGroup > 2.0e9) continue;
+    plan.wfRingCap = r.cap;
+    plan.wfRingShift = r.shift;
+    plan.wfRingMul3 = r.mul3;
+    break;
+  }
+  const bool wavefront = plan.wfRingCap > 0 && (hybrid || (ldsTree && tun.wavefront > 0 && sc.numNodes >= tun.wavefront && sc.primClass != nullptr));
+  if (wavefront) {
+    plan.form = hybrid ? 4 : 3;
+    plan.block = SRT_BLOCK_TREE;
+    plan.lds = wfFixed + wfPerContext * plan.wfRingCap;
+    plan.profile = !plan.count && tun.wfProfile > 0;  // a counting launch takes no profile
+    // (hybrid form: the single-root instance is worth +12 to +15 % on cache-resident trees and costs 5 % on the HBM-bound
+    // soups of 4 M triangles and more, where the shorter visit only crowds the memory system: profiles/r03/hybrid.txt)
+    plan.single = !plan.profile && sc.numWorld == 1 && (!hybrid || sc.numNodes <= (1 << 20));
+    return plan;
+  }
+  plan.wfRingCap = plan.wfRingShift = plan.wfRingMul3 = 0;
+  plan.form = !ldsTree ? 0 : ldsTreeBytes + attBytes <= 160 * 1024 ? 2 : 1;
+  plan.block = ldsTree ? SRT_BLOCK_TREE : SRT_BLOCK;
+  plan.lds = plan.form == 2 ? ldsTreeBytes + attBytes : ldsTree ? ldsTreeBytes : ldsBytesFor(ctx, p->maxBounce, sc.stackDepth);
+  plan.single = !plan.count && sc.numWorld == 1;  // (the counting instances serve single-root worlds as well)
+  return plan;
 }
 
 static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr) {
@@ -1230,69 +1269,16 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
       HIP_OK(ctx, hipMemsetAsync(a.fix, 0, tilePixels * sizeof(SrtFixedAccum), stream));
     }
   }
-  // FAITHFUL on a scene whose whole node array fits into a CU's LDS: the LDS-resident-tree kernel (srt_render_kernel
-  // LDSTREE), one workgroup of 1024 threads per CU, walking the threaded copy of the tree (no per-lane stack).
-  const size_t ldsTreeBytes = (size_t)ctx->scene.numNodes * 32 + 16 * sizeof(int32_t);  // threaded tree: no stacks
-  // (Even trees of a few dozen nodes gain: their frames are shading-bound, and the 128-register kernel keeps a hit's
-  // texel loads in flight together where the 96-register one spills, profiles/r02/lds_tree.txt.)
-  const bool ldsTree = p->traversal == SRT_TRAVERSE_FAITHFUL && ctx->tun.ldsTree > 0 && ctx->scene.numNodes >= ctx->tun.ldsTree && ldsTreeBytes <= 160 * 1024 &&
-                       ctx->scene.nodeThread != nullptr;  // thread links exist: host-built trees, 15-bit references (srtUploadScene)
-  // ... and when the attenuation stacks fit behind them as well they stay in LDS (ldsTreeMode 2): +2 to +5 % on the
-  // small BASELINE scenes; the headline scene's tree leaves no room (mode 1: they live in global memory)
-  const size_t attBytes = (size_t)(3 * p->maxBounce + 3) * 1024 * sizeof(float);
-  const int ldsTreeMode = !ldsTree ? 0 : (ldsTreeBytes + attBytes <= 160 * 1024 ? 2 : 1);
-  // closest-hit traversal over the four-box records: its stack holds up to three pending references per wide level; a
-  // tree too deep for that beside the attenuation stacks (64 KB per workgroup at most: two workgroups per CU) walks the
-  // two-box records instead
-  const bool attGlobal256 = !ldsTree && p->traversal == SRT_TRAVERSE_CLOSEST && ctx->tun.attGlobal > 0 && ctx->scene.numNodes >= ctx->tun.attGlobal;
-  if (p->traversal == SRT_TRAVERSE_CLOSEST && a.scene.nodes4) {
-    const int need = std::max(a.scene.stackDepth, a.scene.wideStackDepth);
-    if (ldsBytesFor(ctx, p->maxBounce, need, attGlobal256) <= 80 * 1024)
-      a.scene.stackDepth = need;
-    else
-      a.scene.nodes4 = nullptr;
-  } else {
-    a.scene.nodes4 = nullptr;
-  }
-  const size_t lds = ldsTreeMode == 2 ? ldsTreeBytes + attBytes : ldsTree ? ldsTreeBytes : ldsBytesFor(ctx, p->maxBounce, a.scene.stackDepth, attGlobal256);
-  if (lds > 160 * 1024) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->scene.stackDepth, lds);
-  // The path-pool kernel (srt_wavefront.hip) serves what the LDS-resident tree serves, when its rings fit behind the
-  // tree: one 1024-thread workgroup per CU, wfPool contexts each.  A counting launch runs the counting instance of the
-  // kernel the same launch without counting runs (srt_launch_render_wf): the counters belong to the kernel under test.
-  // LDS behind the tree: 64 control words, six rings of 16-bit slots, and per context the (t, primitive) its walk ended at:
-  // 18 bytes per context.  Ring capacity = pool size = the largest of 1024, 1536, 2048, 3072, 4096 that fits and does not
-  // exceed the tunable (the headline scene's 129 KB tree leaves room for 1536).
-  int wfPoolSize = 0, wfRingCap = 0, wfRingShift = 0, wfRingMul3 = 0;
-  // Hybrid form: the tree's top in LDS, the rest read from global memory (scene.nodesWf, built at upload when the tree does
-  // not fit or the tunable wf_resident_max asks for it).
-  const bool hybrid = p->traversal == SRT_TRAVERSE_FAITHFUL && ctx->scene.nodesWf != nullptr && ctx->tun.wavefront > 0 &&
-                      ctx->scene.primClass != nullptr;
-  const size_t wfFixed = (size_t)(hybrid ? ctx->scene.wfResident : ctx->scene.numNodes) * 32 + 64 * sizeof(int32_t);
-  const size_t wfPerContext = hybrid ? 20 : 18;  // six ring slots of 16 bits, t, the primitive (16 bits; 32 in the hybrid form)
-  {
-    // ring counters are 32-bit and a 3 * 2^j ring cannot take their wrap-around: such rings only while a workgroup's
-    // enqueues stay far below 2^32 (about three per sample)
-    const double enqueuesPerGroup = 4.0 * (double)a.numLocalTiles * SRT_TILE_PIXELS * (double)p->spp / std::max(1, ctx->prop.multiProcessorCount);
-    static const struct { int cap, shift, mul3; } kRings[] = {{4096, 12, 0}, {3072, 10, 1}, {2048, 11, 0}, {1536, 9, 1}, {1024, 10, 0}};
-    for (const auto& r : kRings) {
-      if (r.cap > std::max(1024, ctx->tun.wfPool) || wfFixed + wfPerContext * r.cap > 160 * 1024) continue;
-      if (r.mul3 && enqueuesPerGroup > 2.0e9) continue;
-      wfRingCap = r.cap;
-      wfRingShift = r.shift;
-      wfRingMul3 = r.mul3;
-      break;
-    }
-    wfPoolSize = wfRingCap;
-  }
-  const size_t wfLds = wfFixed + wfPerContext * wfRingCap;
-  const bool wavefront = wfRingCap > 0 && (hybrid || (ldsTree && ctx->tun.wavefront > 0 && ctx->scene.numNodes >= ctx->tun.wavefront &&
-                                                      ctx->scene.primClass != nullptr));
-  if (!(wavefront && hybrid)) a.scene.nodesWf = nullptr;  // srt_launch_render_wf picks the form by this pointer
-  int perCU = 0;
-  if (wavefront || srt_render_occupancy(p->traversal, p->countStats, ldsTreeMode, lds, &perCU) != 0 || perCU < 1) perCU = 1;
-  // persistent waves: enough workgroups to fill every CU, never more than there is work (4 or 16 waves each)
-  const int wgWaves = ldsTree || wavefront ? 16 : 4;
-  int grid = std::min(ctx->prop.multiProcessorCount * perCU, (a.numWork + SRT_TILE_PIXELS * wgWaves - 1) / (SRT_TILE_PIXELS * wgWaves));
+  const RenderPlan plan = renderPlan(ctx, p);
+  if (plan.lds > 160 * 1024) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->scene.stackDepth, plan.lds);
+  const RenderKernel kernel = plan.form >= 3 ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
+  if (plan.lds > 64 * 1024)
+    HIP_OK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+  // persistent waves: enough workgroups to fill every CU (the path-pool kernel: one), never more than there is work
+  int perCU = 1;
+  if (plan.form < 3 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, plan.block, plan.lds) != hipSuccess || perCU < 1)) perCU = 1;
+  const int wgItems = SRT_TILE_PIXELS * (plan.block / 64);
+  int grid = std::min(ctx->prop.multiProcessorCount * perCU, (a.numWork + wgItems - 1) / wgItems);
   if (grid < 1) grid = 1;
   auto ensure = [&](DeviceBuffer& b, size_t need) -> int {
     if (b.bytes >= need) return 0;
@@ -1302,35 +1288,34 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
     b.bytes = need;
     return 0;
   };
-  if (wavefront) {
+  if (plan.form >= 3) {
     // a workgroup never needs more contexts than it has work items
     const int64_t itemsPerGroup = ((int64_t)a.numWork + grid - 1) / grid;
-    wfPoolSize = (int)std::max<int64_t>(64, std::min<int64_t>(wfPoolSize, itemsPerGroup + 63));
+    const int wfPoolSize = (int)std::max<int64_t>(64, std::min<int64_t>(plan.wfRingCap, itemsPerGroup + 63));
     if (ensure(ctx->wfPool, (size_t)grid * wfPoolSize * 128)) return 1;
     const int hiLevels = std::max(0, p->maxBounce - 4);
     if (ensure(ctx->wfAttHi, std::max<size_t>(16, (size_t)grid * 3 * hiLevels * wfPoolSize * sizeof(float)))) return 1;
     a.wfPool = static_cast<char*>(ctx->wfPool.p);
     a.wfAttHi = static_cast<float*>(ctx->wfAttHi.p);
     a.wfPoolSize = wfPoolSize;
-    a.wfRingCap = wfRingCap;
-    a.wfRingShift = wfRingShift;
-    a.wfRingMul3 = wfRingMul3;
-    a.wfSwapMin = ctx->tun.wfSwapMin > 0 ? std::min(64, ctx->tun.wfSwapMin) : (hybrid ? 16 : 32);
+    a.wfRingCap = plan.wfRingCap;
+    a.wfRingShift = plan.wfRingShift;
+    a.wfRingMul3 = plan.wfRingMul3;
+    a.wfSwapMin = ctx->tun.wfSwapMin > 0 ? std::min(64, ctx->tun.wfSwapMin) : (plan.form == 4 ? 16 : 32);
     a.wfFarRounds = ctx->tun.wfFarRounds > 0 ? std::min(4, ctx->tun.wfFarRounds) : (ctx->scene.numNodes <= (1 << 20) ? 2 : 1);
     a.wfSwapBig = std::max(a.wfSwapMin, std::min(64, ctx->tun.wfSwapBig));
     HIP_OK(ctx, hipHostGetDevicePointer((void**)&a.wfError, ctx->dWfError, 0));
-  } else if (ldsTreeMode == 1 || attGlobal256) {
-    if (ensure(ctx->attScratch, (size_t)(3 * p->maxBounce + 3) * grid * (ldsTree ? 1024 : 256) * sizeof(float))) return 1;
+  } else if (plan.form == 1) {
+    if (ensure(ctx->attScratch, (size_t)(3 * p->maxBounce + 3) * grid * SRT_BLOCK_TREE * sizeof(float))) return 1;
     a.attScratch = static_cast<float*>(ctx->attScratch.p);
   }
   HIP_OK(ctx, hipMemsetAsync(ctx->dQueue, 0, sizeof(int32_t) * 16 * a.numQueues, stream));
   if (a.stats) HIP_OK(ctx, hipMemsetAsync(ctx->dStats, 0, 96 * sizeof(unsigned long long), stream));
   HIP_OK(ctx, hipEventRecord(ctx->evStart, stream));
-  ctx->lastLaunch[0] = wavefront ? (hybrid ? 4 : 3) : ldsTreeMode;
-  ctx->lastLaunch[1] = grid;
-  ctx->lastLaunch[2] = ldsTree || wavefront ? 1024 : 256;
-  ctx->lastLaunch[3] = (int32_t)(wavefront ? wfLds : lds);
-  int rc = wavefront ? srt_launch_render_wf(&a, ctx->tun.wfProfile > 0, p->countStats, grid, wfLds, stream) : srt_launch_render(&a, p->traversal, p->countStats, ldsTreeMode, grid, lds, stream);
+  ctx->lastPlan = plan;
+  ctx->lastGrid = grid;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(plan.block), plan.lds, stream, a);
+  int rc = (int)hipGetLastError();
   if (rc) return fail(ctx, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
   HIP_OK(ctx, hipEventRecord(ctx->evStop, stream));
   ctx->timed = true;
@@ -1532,7 +1517,10 @@ int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAo
 /* include/srt_hip_test.h: the most recent render-kernel launch */
 int srtGetLaunchInfo(SrtContext* ctx, int32_t* out4) {
   if (!ctx || !out4) return 1;
-  memcpy(out4, ctx->lastLaunch, sizeof ctx->lastLaunch);
+  out4[0] = ctx->lastPlan.form;
+  out4[1] = ctx->lastGrid;
+  out4[2] = ctx->lastPlan.block;
+  out4[3] = (int32_t)ctx->lastPlan.lds;
   return 0;
 }
 int srtGetWfProfile(SrtContext* ctx, uint64_t* out46) {

@@ -22,6 +22,8 @@
 #define SRT_NODE_INDEX(ref) ((int32_t)(ref) >> 5)
 #define SRT_MAX_NODES (1 << 25) /* byte offsets (index * 64 in the closest-hit records) stay below 2^31 */
 #define SRT_MAX_QUEUES 64
+#define SRT_BLOCK 256        // threads per workgroup of the render kernel over node records read through the L1
+#define SRT_BLOCK_TREE 1024  // ... over the LDS-resident tree, and of the path-pool kernel: one workgroup per CU
 // a primitive's material word: material index, the material's type (SRT_MAT_*) and SRT_MAT_NEEDS_* flags,
 // (spheres) bit 30 = moving
 #define SRT_MAT_INDEX_MASK 0x00ffffff
@@ -61,11 +63,6 @@ struct DevScene {
   // (index * 64); built from `nodes` on the device after upload (srt_lbvh.hip, srt_pair_nodes).  One 64-byte request
   // per visit tests two boxes; the 32-byte records use half of every request they cause.
   const float4* nodes2;
-  // SRT_TRAVERSE_CLOSEST, wide form: one 128-byte record per node with the boxes of its (up to) four grandchildren,
-  // slot k: (min_k.xyz, reference_k) at +16k, (max_k.xyz, -) at +64 + 16k, node references = byte offsets into this array
-  // (index * 128), SRT_REF_DONE = unused slot; built from nodes2 (srt_lbvh.hip wideNodes).  Null: walk nodes2.
-  const float4* nodes4;
-  int32_t wideStackDepth;  // pending references the wide walk can pile up: 3 per wide level
   // 1 byte per node: the axis its children are split on (left = lower side), 3 = unknown.  Read only by
   // SRT_TRAVERSE_CLOSEST, which visits the nearer child first; FAITHFUL keeps bvh.h's left-then-right.
   const uint8_t* nodeAxis;
@@ -164,6 +161,21 @@ struct RenderArgs {
   int32_t wfFarRounds;  // hybrid form: node visits per round (the last one serves the lanes outside LDS as well)
   int32_t* wfError;
 };
+
+// One render launch, decided by srt_api.cpp renderPlan.  form: srtGetLaunchInfo's codes -- 0 srt_render_kernel over node
+// records read through the L1, 1 / 2 srt_render_kernel over the LDS-resident tree with the attenuation stacks in global
+// memory / in LDS, 3 srt_render_wf_kernel over the LDS-resident tree, 4 its hybrid form.  closest, single, count and
+// profile are the template arguments of the instance that runs (srt_render_kernel_for, srt_render_wf_kernel_for).
+struct RenderPlan {
+  int32_t form;
+  bool closest, single, count, profile;
+  int32_t block;  // threads per workgroup
+  size_t lds;     // dynamic LDS bytes per workgroup
+  int32_t wfRingCap, wfRingShift, wfRingMul3;  // forms 3 and 4: RenderArgs::wfRingCap = (wfRingMul3 ? 3 : 1) << wfRingShift
+};
+typedef void (*RenderKernel)(const RenderArgs);
+extern "C" RenderKernel srt_render_kernel_for(const RenderPlan* p);     // srt_kernels.hip, forms 0-2
+extern "C" RenderKernel srt_render_wf_kernel_for(const RenderPlan* p);  // srt_wavefront.hip, forms 3 and 4
 
 struct TraceArgs {
   DevScene scene;

@@ -14,8 +14,6 @@
 
 #include "srt_device.h"
 
-#define SRT_BLOCK 256
-#define SRT_BLOCK_TREE 1024      // LDS-resident tree: one workgroup per CU
 #define SRT_TREE_WAVES_PER_SIMD 4
 #ifndef SRT_NODE_UNROLL
 #define SRT_NODE_UNROLL 4  // node visits per evaluation of the burst loop's exit test

@@ -908,28 +908,15 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
 }
 
 extern "C" {
-// count: the COUNT instance of the kernel the same launch without counting runs (a counting launch takes no profile)
-int srt_launch_render_wf(const RenderArgs* a, int profile, int count, int grid, size_t ldsBytes, hipStream_t stream) {
-  typedef void (*Kernel)(const RenderArgs);
-  // (hybrid form: the single-root instance is worth +12 to +15 % on cache-resident trees and costs 5 % on the HBM-bound
-  // soups of 4 M triangles and more, where the shorter visit only crowds the memory system: profiles/r03/hybrid.txt)
-  Kernel k;
-  if (a->scene.nodesWf) {
-    const bool single = a->scene.numWorld == 1 && a->scene.numNodes <= (1 << 20);
-    k = count     ? (single ? srt_render_wf_kernel<true, false, true, true> : srt_render_wf_kernel<false, false, true, true>)
-        : profile ? srt_render_wf_kernel<false, true, true, false>
-                  : (single ? srt_render_wf_kernel<true, false, true, false> : srt_render_wf_kernel<false, false, true, false>);
-  } else {
-    const bool single = a->scene.numWorld == 1;
-    k = count     ? (single ? srt_render_wf_kernel<true, false, false, true> : srt_render_wf_kernel<false, false, false, true>)
-        : profile ? srt_render_wf_kernel<false, true, false, false>
-                  : (single ? srt_render_wf_kernel<true, false, false, false> : srt_render_wf_kernel<false, false, false, false>);
-  }
-  if (ldsBytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(WF_BLOCK), ldsBytes, stream, *a);
-  return (int)hipGetLastError();
+// the srt_render_wf_kernel instance a plan of form 3 or 4 names (srt_api.cpp renderPlan)
+RenderKernel srt_render_wf_kernel_for(const RenderPlan* p) {
+  static_assert(WF_BLOCK == SRT_BLOCK_TREE, "srt_api.cpp launches the path-pool kernel with SRT_BLOCK_TREE threads");
+  if (p->form == 4)
+    return p->count     ? (p->single ? srt_render_wf_kernel<true, false, true, true> : srt_render_wf_kernel<false, false, true, true>)
+           : p->profile ? srt_render_wf_kernel<false, true, true, false>
+                        : (p->single ? srt_render_wf_kernel<true, false, true, false> : srt_render_wf_kernel<false, false, true, false>);
+  return p->count     ? (p->single ? srt_render_wf_kernel<true, false, false, true> : srt_render_wf_kernel<false, false, false, true>)
+         : p->profile ? srt_render_wf_kernel<false, true, false, false>
+                      : (p->single ? srt_render_wf_kernel<true, false, false, false> : srt_render_wf_kernel<false, false, false, false>);
 }
 }
