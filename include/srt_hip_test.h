@@ -15,12 +15,6 @@
 extern "C" {
 #endif
 
-/* Test hook: material::scatter + emitted (material.h:15-21) through the kernel's own
- * shading function for n (ray, hit record) pairs; entry i draws from the counter RNG
- * keyed (seed, pixel=i, sample=0).  out13 per entry: attenuation[3], scattered dir[3],
- * scattered origin[3], scatter's bool, emitted[3].  HOST pointers. */
-int srtScatterTest(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, float* out13);
-
 /* Per-ray view into the RENDER kernel's own traversal (not srtTraceRays' kernel): renders sample
  * p->sampleFirst of every pixel with the counting variant of the kernel the same launch without counting would run
  * (srt_render_kernel, or the path-pool kernel srt_render_wf_kernel in its whole-tree or hybrid form: srtGetLaunchInfo

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "srt_buffer.h"
 #include "srt_device.h"
 
 extern "C" {
@@ -110,54 +111,41 @@ int srtRenderImageRanks(SrtContext* ctx, const SrtRenderParams* pIn, float* hAcc
   if (hipSetDevice(srtCtxDevice(ctx)) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: hipSetDevice failed");
   const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
   const size_t localBytes = (size_t)srtNumLocalTiles(p.imageWidth, p.imageHeight, numRanks) * SRT_TILE_PIXELS * sizeof(float4);
-  void *dLocal = nullptr, *dGathered = nullptr, *dRgba = nullptr, *dAcc = nullptr;
-  int32_t* dAgree = nullptr;
-  int rc = 1;
-  do {
-    // Everything that can fail on ONE rank happens before the gather, and the ranks agree on it first: a rank that
-    // broke out here while the others entered ncclGather would leave them waiting for ever.  The agreement is a
-    // 4-byte all-reduce (minimum of the ranks' status); only a rank that cannot even allocate those 4 bytes leaves
-    // without taking part -- its peers then need ncclCommAbort (srtCommDestroy), as after any lost rank.
-    if (numRanks > 1 && hipMalloc((void**)&dAgree, sizeof(int32_t)) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc (4 bytes)"); break; }
-    int32_t ok = 1;
-    if (hipMalloc(&dLocal, localBytes) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
-    if (ok && rank == 0) {
-      if (hipMalloc(&dGathered, localBytes * numRanks) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
-      if (ok && hRgba && hipMalloc(&dRgba, nPix * 4) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
-      if (ok && hAccum && hipMalloc(&dAcc, nPix * sizeof(float4)) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
-    }
-    if (ok && srtRenderTiles(ctx, &p, dLocal, nullptr)) ok = 0;
-    if (ok && hipDeviceSynchronize() != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: render kernel failed"); ok = 0; }
-    if (numRanks > 1) {
-      ncclComm_t comm = static_cast<ncclComm_t>(*srtCtxCommSlot(ctx));
-      int32_t agreed = 0;
-      if (!comm) { srtCtxFail(ctx, "srtRenderImageRanks: no communicator (srtCommInit)"); break; }
-      if (hipMemcpy(dAgree, &ok, sizeof ok, hipMemcpyHostToDevice) != hipSuccess ||
-          ncclAllReduce(dAgree, dAgree, 1, ncclInt32, ncclMin, comm, nullptr) != ncclSuccess ||
-          hipMemcpy(&agreed, dAgree, sizeof agreed, hipMemcpyDeviceToHost) != hipSuccess) {
-        srtCtxFail(ctx, "srtRenderImageRanks: the ranks could not agree on the render's status");
-        break;
-      }
-      if (!agreed) {
-        if (ok) srtCtxFail(ctx, "srtRenderImageRanks: another rank failed before the gather");
-        break;
-      }
-    } else if (!ok) {
-      break;
-    }
-    if (srtGatherTiles(ctx, &p, dLocal, dGathered, nullptr)) break;
-    if (rank == 0 && srtResolveTiles(ctx, &p, dGathered, dRgba, dAcc, nullptr)) break;
-    if (hipDeviceSynchronize() != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: gather or resolve failed"); break; }
-    if (rank == 0) {
-      if (hRgba && hipMemcpy(hRgba, dRgba, nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: copy rgba"); break; }
-      if (hAccum && hipMemcpy(hAccum, dAcc, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: copy accum"); break; }
-    }
-    rc = 0;
-  } while (0);
-  if (dAgree) (void)hipFree(dAgree);
-  for (void* q : {dLocal, dGathered, dRgba, dAcc})
-    if (q) (void)hipFree(q);
-  return rc;
+  DeviceBuffer local, gathered, rgba, acc, agree;
+  // Everything that can fail on ONE rank happens before the gather, and the ranks agree on it first: a rank that
+  // returned here while the others entered ncclGather would leave them waiting for ever.  The agreement is a
+  // 4-byte all-reduce (minimum of the ranks' status); only a rank that cannot even allocate those 4 bytes leaves
+  // without taking part -- its peers then need ncclCommAbort (srtCommDestroy), as after any lost rank.
+  if (numRanks > 1 && agree.reserve(sizeof(int32_t)) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc (4 bytes)");
+  int32_t ok = 1;
+  if (local.reserve(localBytes) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+  if (ok && rank == 0) {
+    if (gathered.reserve(localBytes * numRanks) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+    if (ok && hRgba && rgba.reserve(nPix * 4) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+    if (ok && hAccum && acc.reserve(nPix * sizeof(float4)) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+  }
+  if (ok && srtRenderTiles(ctx, &p, local.get(), nullptr)) ok = 0;
+  if (ok && hipDeviceSynchronize() != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: render kernel failed"); ok = 0; }
+  if (numRanks > 1) {
+    ncclComm_t comm = static_cast<ncclComm_t>(*srtCtxCommSlot(ctx));
+    int32_t agreed = 0;
+    if (!comm) return srtCtxFail(ctx, "srtRenderImageRanks: no communicator (srtCommInit)");
+    if (hipMemcpy(agree.get(), &ok, sizeof ok, hipMemcpyHostToDevice) != hipSuccess ||
+        ncclAllReduce(agree.get(), agree.get(), 1, ncclInt32, ncclMin, comm, nullptr) != ncclSuccess ||
+        hipMemcpy(&agreed, agree.get(), sizeof agreed, hipMemcpyDeviceToHost) != hipSuccess)
+      return srtCtxFail(ctx, "srtRenderImageRanks: the ranks could not agree on the render's status");
+    if (!agreed) return ok ? srtCtxFail(ctx, "srtRenderImageRanks: another rank failed before the gather") : 1;
+  } else if (!ok) {
+    return 1;
+  }
+  if (srtGatherTiles(ctx, &p, local.get(), gathered.get(), nullptr)) return 1;
+  if (rank == 0 && srtResolveTiles(ctx, &p, gathered.get(), rgba.get(), acc.get(), nullptr)) return 1;
+  if (hipDeviceSynchronize() != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: gather or resolve failed");
+  if (rank == 0) {
+    if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: copy rgba");
+    if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: copy accum");
+  }
+  return 0;
 }
 
 }  // extern "C"

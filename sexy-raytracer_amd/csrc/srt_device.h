@@ -70,7 +70,7 @@ struct DevScene {
   // word per node, two 16-bit references -- low half: what follows a leaf's first object (its second object, or the high
   // half again for a single-object leaf); high half: where the traversal goes when this node's subtree is done (node
   // INDEX, primitive reference, or 0x8000 = done).  Null unless every tree was built on the host, every node's children
-  // are two nodes or two primitives, and every reference fits 15 bits (srt_api.cpp threadTree).
+  // are two nodes or two primitives, and every reference fits 15 bits (srt_scene.cpp flattenScene).
   const int32_t* nodeThread;
   // path-pool kernel (srt_wavefront.hip): the material CLASS of every primitive, indexed by ~reference
   // (index << 1 | sphere): 0 triangle with a pbr material, 1 sphere with a pbr material that reads neither uv nor a normal
@@ -80,7 +80,7 @@ struct DevScene {
   // path-pool kernel, hybrid form (a tree that does not fit into LDS): threaded records with 32-bit references --
   // (bmin.xyz, reference taken on a box hit) (bmax.xyz, successor << 2 | what follows a leaf's first object: 0 nothing,
   // 1 the next primitive of the same array, 2 primSecond[~first]) -- renumbered so that the wfResident nodes kept in LDS
-  // come first (srt_api.cpp: the boxes of largest surface, closed upward), the world list's roots in that numbering, and
+  // come first (srt_scene.cpp: the boxes of largest surface, closed upward), the world list's roots in that numbering, and
   // the second object of the leaves whose objects are not neighbours in one array (indexed like primClass).  "Done" is
   // -2^29 here.  Null when the tree fits (or is not a host-built tree of two-node / two-primitive nodes).
   const float4* nodesWf;

@@ -1,0 +1,612 @@
+// srt_scene.cpp -- the host stage of srtUploadScene (srt_scene.h): scene validation, the reference-order BVH build,
+// the flattening of a scene into the device record formats, and the host arithmetic of the C ABI (the global
+// generator, srtMakeCamera).  No HIP runtime calls: everything here runs and is tested without a device.
+//
+// Host arithmetic that feeds the kernels (BVH boxes, per-triangle normals and tangent frames, the camera frame) keeps
+// the reference's operation order; this file is built with -ffp-contract=off and without -march so it rounds like the
+// reference's x86-64 build.
+
+#include "srt_scene.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <random>
+
+#include "srt_thread.h"
+
+namespace {
+
+// ------------------------------------------------------------------ host vector math
+struct H3 {
+  float x, y, z;
+};
+inline H3 h3(const float* p) { return H3{p[0], p[1], p[2]}; }
+inline H3 operator+(H3 a, H3 b) { return H3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+inline H3 operator-(H3 a, H3 b) { return H3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+inline H3 operator*(float s, H3 a) { return H3{s * a.x, s * a.y, s * a.z}; }
+inline H3 operator/(H3 a, float s) { return H3{a.x / s, a.y / s, a.z / s}; }
+inline H3 crossH(H3 a, H3 b) { return H3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+inline float lenSqH(H3 v) { return v.x * v.x + v.y * v.y + v.z * v.z; }  // vec3.h:29-31
+inline H3 unitH(H3 v) {                                                    // vec3.h:54-60
+  float len = sqrtf(lenSqH(v));
+  if (len != 0) return H3{v.x / len, v.y / len, v.z / len};
+  return v;
+}
+
+inline Box surrounding(const Box& a, const Box& b) {  // aabb.h:33-43
+  Box r;
+  for (int k = 0; k < 3; ++k) {
+    r.mn[k] = fminf(a.mn[k], b.mn[k]);
+    r.mx[k] = fmaxf(a.mx[k], b.mx[k]);
+  }
+  return r;
+}
+
+// ------------------------------------------------------------------ the global generator
+// globals.h:30-35: function-local static default-seeded mt19937 + uniform_real_distribution<float>(0,1)
+std::mt19937& hostGenerator() {
+  static std::mt19937 generator;
+  return generator;
+}
+float hostRandomFloat() {
+  static std::uniform_real_distribution<float> distribution(0.0f, 1.0f);
+  return distribution(hostGenerator());
+}
+int hostRandomInt(int lo, int hi) {  // globals.h:37-43
+  float a = (float)lo, b = (float)(hi + 1);
+  return static_cast<int>(a + (b - a) * hostRandomFloat());
+}
+
+// ------------------------------------------------------------------ primitives on the host
+Box sphereBoxAt(const SrtSphereIn& s, float time) {  // sphere.h:47-52, 86-89
+  H3 c0 = h3(s.center0), c1 = h3(s.center1);
+  H3 c = c0;
+  if (c0.x != c1.x || c0.y != c1.y || c0.z != c1.z) c = c0 + ((time - s.time0) / (s.time1 - s.time0)) * (c1 - c0);
+  Box b;
+  b.mn[0] = c.x - s.radius; b.mn[1] = c.y - s.radius; b.mn[2] = c.z - s.radius;
+  b.mx[0] = c.x + s.radius; b.mx[1] = c.y + s.radius; b.mx[2] = c.z + s.radius;
+  return b;
+}
+Box sphereBox(const SrtSphereIn& s, float t0, float t1) {  // sphere.h:85-94
+  return surrounding(sphereBoxAt(s, t0), sphereBoxAt(s, t1));
+}
+Box triangleBox(const SrtTriangleIn& t) {  // model.h:183-212
+  const float inf = std::numeric_limits<float>::infinity();
+  Box b;
+  for (int a = 0; a < 3; ++a) {
+    b.mn[a] = inf;
+    b.mx[a] = -inf;
+  }
+  for (int k = 0; k < 3; ++k)
+    for (int a = 0; a < 3; ++a) {
+      b.mn[a] = std::min(b.mn[a], t.p[k][a]);
+      b.mx[a] = std::max(b.mx[a], t.p[k][a]);
+    }
+  for (int a = 0; a < 3; ++a)
+    if (b.mn[a] == b.mx[a]) {
+      b.mn[a] -= 0.0001f;
+      b.mx[a] += 0.0001f;
+    }
+  return surrounding(b, b);
+}
+Box primBox(const SrtSceneDesc* d, int32_t prim, float t0, float t1) {
+  const SrtPrimRef& pr = d->prims[prim];
+  return pr.type == SRT_PRIM_SPHERE ? sphereBox(d->spheres[pr.index], t0, t1) : triangleBox(d->triangles[pr.index]);
+}
+
+// fastDiv's operand certificate for the box coordinates (srt_kernels.hip): 0 or 2^-77 <= |c| <= 2^30
+bool fastDivOperand(float c) {
+  const float ac = fabsf(c);
+  return c == 0.0f || (ac >= 0x1p-77f && ac <= 0x1p30f);
+}
+
+std::string format(const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return buf;
+}
+
+template <typename T>
+T bitsAs(const void* p) {
+  T v;
+  memcpy(&v, p, sizeof v);
+  return v;
+}
+
+}  // namespace
+
+Box Builder::childBox(int32_t ref) const { return ref >= 0 ? nodes[ref].box : primBox(d, ~ref, time0, time1); }
+
+// The reference copies the object vector at each node (bvh.h:57) and sorts [start,end) of the copy; sibling subtrees
+// only touch disjoint sub-ranges, so one shared vector sorted in place gives the same tree.  Nodes are emitted in
+// pre-order (the order populateVector walks them, bvh.h:112-148).
+int32_t Builder::build(size_t start, size_t end, int pending) {
+  int axis = hostRandomInt(0, 2);  // bvh.h:60: one draw per node, pre-order
+  auto comparator = [this, axis](int32_t a, int32_t b) { return sortKey[3 * a + axis] < sortKey[3 * b + axis]; };
+  int32_t me = (int32_t)nodes.size();
+  nodes.emplace_back();
+  size_t span = end - start;
+  int32_t left, right;
+  if (span == 1) {
+    left = right = ~objects[start];
+  } else if (span == 2) {
+    if (comparator(objects[start], objects[start + 1])) {
+      left = ~objects[start];
+      right = ~objects[start + 1];
+    } else {
+      left = ~objects[start + 1];
+      right = ~objects[start];
+    }
+    maxPending = std::max(maxPending, pending + 1);
+  } else {
+    std::sort(objects.begin() + start, objects.begin() + end, comparator);
+    size_t mid = start + span / 2;
+    maxPending = std::max(maxPending, pending + 1);
+    // capacity must hold for either visiting order (CLOSEST descends into the near child first and
+    // leaves the other one pending), so both children are entered with one more pending entry
+    left = build(start, mid, pending + 1);
+    right = build(mid, end, pending + 1);
+  }
+  BuildNode& n = nodes[me];
+  n.left = left;
+  n.right = right;
+  n.axis = (uint8_t)axis;
+  n.box = surrounding(childBox(left), childBox(right));  // bvh.h:88-94
+  return me;
+}
+
+void Builder::toBvhNodes(SrtBvhNode* out) const {
+  for (size_t i = 0; i < nodes.size(); ++i) {
+    memcpy(out[i].bmin, nodes[i].box.mn, 12);
+    memcpy(out[i].bmax, nodes[i].box.mx, 12);
+    out[i].left = nodes[i].left;
+    out[i].right = nodes[i].right;
+  }
+}
+
+void buildItem(const SrtSceneDesc* d, const SrtWorldItem& it, Builder& b) {
+  b.d = d;
+  b.time0 = it.time0;
+  b.time1 = it.time1;
+  if (it.nodes) {
+    b.nodes.resize(it.numNodes);
+    std::vector<int> pending(it.numNodes, 0);  // stack entries held when the node is entered
+    for (int i = 0; i < it.numNodes; ++i) {
+      const SrtBvhNode& n = it.nodes[i];
+      memcpy(b.nodes[i].box.mn, n.bmin, 12);
+      memcpy(b.nodes[i].box.mx, n.bmax, 12);
+      b.nodes[i].left = n.left;
+      b.nodes[i].right = n.right;
+      const bool two = n.right != n.left;
+      if (two) b.maxPending = std::max(b.maxPending, pending[i] + 1);
+      if (n.left >= 0) pending[n.left] = pending[i] + (two ? 1 : 0);
+      if (two && n.right >= 0) pending[n.right] = pending[i] + 1;  // either child may be the one left pending
+    }
+    return;
+  }
+  b.sortKey.resize((size_t)d->numPrims * 3);
+  b.objects.resize(it.count);
+  for (int i = 0; i < it.count; ++i) {
+    int prim = it.first + i;
+    b.objects[i] = prim;
+    Box bx = primBox(d, prim, 0, 0);  // boxCompare uses boundingBox(0, 0, ...) (bvh.h:37)
+    for (int k = 0; k < 3; ++k) b.sortKey[3 * prim + k] = bx.mn[k];
+  }
+  b.nodes.reserve((size_t)it.count * 2);
+  b.build(0, it.count, 0);
+}
+
+std::string validateScene(const SrtSceneDesc* d) {
+  // counts and pointers first: everything below indexes these arrays and sizes std::vectors with the counts
+  if (d->numTriangles < 0 || d->numSpheres < 0 || d->numPrims < 0 || d->numWorld < 0 || d->numMaterials < 0 ||
+      d->numTextures < 0 || d->numTexelBytes < 0)
+    return "scene: negative element count";
+  if ((d->numTriangles > 0 && !d->triangles) || (d->numSpheres > 0 && !d->spheres) || (d->numPrims > 0 && !d->prims) ||
+      (d->numWorld > 0 && !d->world) || (d->numMaterials > 0 && !d->materials) || (d->numTextures > 0 && !d->textures) ||
+      (d->numTexelBytes > 0 && !d->texels))
+    return "scene: null array with a non-zero count";
+  if ((int64_t)d->numTriangles > 0x3fffffff || (int64_t)d->numSpheres > 0x3fffffff)
+    return "scene: too many primitives for 31-bit device references";
+  for (int i = 0; i < d->numTextures; ++i) {
+    const SrtTextureIn& t = d->textures[i];
+    if (t.kind == SRT_TEX_CHECKER) {
+      for (int c : {t.even, t.odd})
+        if (c < 0 || c >= d->numTextures || d->textures[c].kind == SRT_TEX_CHECKER)
+          return format("texture %d: checker children must be solid or image textures", i);
+    } else if (t.kind == SRT_TEX_IMAGE) {
+      if (t.width < 0 || t.height < 0 || (t.width > 0 && (t.bpp < 1 || t.bpp > 4)))
+        return format("texture %d: bad image dimensions", i);
+      if (t.width > 0 && (t.texelOffset < 0 || t.texelOffset + (int64_t)t.width * t.height * t.bpp > d->numTexelBytes))
+        return format("texture %d: texels out of range", i);
+    } else if (t.kind != SRT_TEX_SOLID)
+      return format("texture %d: unknown kind %d", i, t.kind);
+  }
+  auto texOk = [&](int id) { return id >= -1 && id < d->numTextures; };
+  for (int i = 0; i < d->numMaterials; ++i) {
+    const SrtMaterialIn& m = d->materials[i];
+    if (m.type < SRT_MAT_PBR || m.type > SRT_MAT_LIGHT) return format("material %d: unknown type %d", i, m.type);
+    if (!texOk(m.albedoTex) || !texOk(m.normalTex) || !texOk(m.metallicTex) || !texOk(m.roughnessTex))
+      return format("material %d: texture id out of range", i);
+    if (m.type == SRT_MAT_LIGHT && m.albedoTex < 0) return format("material %d: light without emit texture", i);
+  }
+  for (int i = 0; i < d->numTriangles; ++i)
+    if (d->triangles[i].material < 0 || d->triangles[i].material >= d->numMaterials)
+      return format("triangle %d: material out of range", i);
+  for (int i = 0; i < d->numSpheres; ++i)
+    if (d->spheres[i].material < 0 || d->spheres[i].material >= d->numMaterials)
+      return format("sphere %d: material out of range", i);
+  for (int i = 0; i < d->numPrims; ++i) {
+    const SrtPrimRef& p = d->prims[i];
+    int lim = p.type == SRT_PRIM_SPHERE ? d->numSpheres : p.type == SRT_PRIM_TRIANGLE ? d->numTriangles : -1;
+    if (p.index < 0 || p.index >= lim) return format("prim %d: bad type/index", i);
+  }
+  if (d->numWorld < 1) return "scene has an empty world list";
+  for (int w = 0; w < d->numWorld; ++w) {
+    const SrtWorldItem& it = d->world[w];
+    if (it.first < 0 || it.count < 1 || it.first + it.count > d->numPrims || (it.kind != SRT_WORLD_PRIM && it.kind != SRT_WORLD_BVH))
+      return format("world item %d: bad range", w);
+    if (it.kind == SRT_WORLD_BVH && it.nodes) {
+      // a caller-built tree must be finite and acyclic: children point forward (pre-order)
+      // ... and a tree: every node but the root has exactly one parent (the pending-stack capacity is
+      // derived per node from its single parent, buildItem)
+      if (it.numNodes < 1) return format("world item %d: prebuilt tree without nodes", w);
+      std::vector<uint8_t> parents(it.numNodes, 0);
+      for (int i = 0; i < it.numNodes; ++i) {
+        const int32_t l = it.nodes[i].left, r = it.nodes[i].right;
+        for (int32_t c : {l, r}) {
+          if (c >= 0 ? (c <= i || c >= it.numNodes) : (~c < it.first || ~c >= it.first + it.count))
+            return format("world item %d: prebuilt node %d has a bad child reference %d", w, i, c);
+        }
+        if (l >= 0 && ++parents[l] > 1) return format("world item %d: prebuilt node %d has more than one parent", w, l);
+        if (r >= 0 && r != l && ++parents[r] > 1) return format("world item %d: prebuilt node %d has more than one parent", w, r);
+        if (r >= 0 && r == l) return format("world item %d: prebuilt node %d lists one subtree twice", w, i);
+      }
+      for (int i = 1; i < it.numNodes; ++i)
+        if (!parents[i]) return format("world item %d: prebuilt node %d is unreachable", w, i);
+    }
+  }
+  return std::string();
+}
+
+std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene& h) {
+  // ---- primitive records.  Device arrays are indexed by the scene's own triangle /
+  // sphere indices; the owning list index is kept for srtTraceRays' prim output.
+  h.triPrimId.assign(d->numTriangles, -1);
+  h.sphPrimId.assign(d->numSpheres, -1);
+  for (int i = 0; i < d->numPrims; ++i) {
+    const SrtPrimRef& p = d->prims[i];
+    (p.type == SRT_PRIM_SPHERE ? h.sphPrimId : h.triPrimId)[p.index] = i;
+  }
+  h.triTest.resize((size_t)d->numTriangles * 3);
+  h.triShade.resize((size_t)d->numTriangles * 4);
+  const float eps = std::numeric_limits<float>::epsilon();
+  for (int i = 0; i < d->numTriangles; ++i) {
+    const SrtTriangleIn& t = d->triangles[i];
+    H3 v0 = h3(t.p[0]), v1 = h3(t.p[1]), v2 = h3(t.p[2]);
+    H3 n = crossH(v1 - v0, v2 - v0);  // getNormal, model.h:276-283
+    h.triTest[3 * i + 0] = make_float4(v0.x, v0.y, v0.z, n.x);
+    h.triTest[3 * i + 1] = make_float4(v1.x, v1.y, v1.z, n.y);
+    h.triTest[3 * i + 2] = make_float4(v2.x, v2.y, v2.z, n.z);
+    H3 nu = unitH(n);  // model.h:172
+    // calcTangentBasis, model.h:214-235
+    H3 e0 = v1 - v0, e1 = v2 - v0;
+    float du0 = t.uv[1][0] - t.uv[0][0], dv0 = t.uv[1][1] - t.uv[0][1];
+    float du1 = t.uv[2][0] - t.uv[0][0], dv1 = t.uv[2][1] - t.uv[0][1];
+    float f = (du0 * dv1 - du1 * dv0);
+    if (f == 0) f += eps;
+    f = 1.0f / f;
+    H3 tg = unitH(H3{f * (dv1 * e0.x - dv0 * e1.x), f * (dv1 * e0.y - dv0 * e1.y), f * (dv1 * e0.z - dv0 * e1.z)});
+    H3 bt = unitH(H3{f * (-du1 * e0.x + du0 * e1.x), f * (-du1 * e0.y + du0 * e1.y), f * (-du1 * e0.z + du0 * e1.z)});
+    h.triShade[4 * i + 0] = make_float4(nu.x, nu.y, nu.z, t.uv[0][0]);
+    h.triShade[4 * i + 1] = make_float4(tg.x, tg.y, tg.z, t.uv[0][1]);
+    h.triShade[4 * i + 2] = make_float4(bt.x, bt.y, bt.z, t.uv[1][0]);
+    h.triShade[4 * i + 3] = make_float4(t.uv[1][1], t.uv[2][0], t.uv[2][1], bitsAs<float>(&t.material));
+  }
+  h.spheres.resize((size_t)d->numSpheres * 3);
+  for (int i = 0; i < d->numSpheres; ++i) {
+    const SrtSphereIn& s = d->spheres[i];
+    bool moving = s.center0[0] != s.center1[0] || s.center0[1] != s.center1[1] || s.center0[2] != s.center1[2];
+    int32_t bits = s.material | (moving ? (1 << 30) : 0);
+    h.spheres[3 * i + 0] = make_float4(s.center0[0], s.center0[1], s.center0[2], s.radius);
+    h.spheres[3 * i + 1] = make_float4(s.center1[0], s.center1[1], s.center1[2], bitsAs<float>(&bits));
+    h.spheres[3 * i + 2] = make_float4(s.time0, s.time1, 0.0f, 0.0f);
+  }
+  // device index of a triangle: identity until the trees are built, then the order in which the host-built
+  // trees' leaves reference the triangles (below), so that a leaf's records and its neighbours' sit together
+  std::vector<int32_t> triDevIndex;
+  auto devRef = [&](int32_t listRef) -> int32_t {  // ~primListIndex -> device prim ref
+    const SrtPrimRef& p = d->prims[~listRef];
+    if (p.type == SRT_PRIM_SPHERE) return ~((p.index << 1) | 1);
+    return ~((triDevIndex.empty() ? p.index : triDevIndex[p.index]) << 1);
+  };
+
+  // ---- world: build each bvhNode (consumes the global generator in scene order)
+  h.itemNodes.resize(d->numWorld);
+  for (int w = 0; w < d->numWorld; ++w) {
+    const SrtWorldItem& it = d->world[w];
+    if (it.kind == SRT_WORLD_PRIM) {
+      h.world.push_back(devRef(~it.first));
+      continue;
+    }
+    if (!it.nodes && (it.builder == SRT_BUILDER_LBVH || it.builder == SRT_BUILDER_PLOC)) {
+      // device build (srt_lbvh.hip) after the primitive arrays are uploaded: reserve the node slots
+      int32_t base = (int32_t)(h.nodes.size() / 2), cnt = std::max(it.count - 1, 1);
+      h.nodes.resize(h.nodes.size() + 2 * (size_t)cnt, make_float4(0, 0, 0, 0));
+      h.nodeAxis.resize(h.nodeAxis.size() + cnt, 3);
+      h.deviceBuilds.push_back(DeviceBuild{w, base, cnt, it.builder, it.time0, it.time1, {}});
+      h.world.push_back(SRT_NODE_REF(base));
+      continue;
+    }
+    Builder b;
+    buildItem(d, it, b);
+    // (A device order with the two children of a node in one 64-byte line -- root, then sibling pairs depth-first --
+    // was measured against this pre-order, where the LEFT child follows its parent: headline +0.3 %, 1 M-triangle
+    // soup -5 %, 10 M +1.7 %, profiles/r02/node_pairs.txt.  Not kept.)
+    int32_t base = (int32_t)(h.nodes.size() / 2);
+    h.itemNodes[w].resize(b.nodes.size());
+    b.toBvhNodes(h.itemNodes[w].data());
+    for (const BuildNode& n : b.nodes) {
+      int32_t l = n.left >= 0 ? SRT_NODE_REF(n.left + base) : devRef(n.left);
+      int32_t r = n.right >= 0 ? SRT_NODE_REF(n.right + base) : devRef(n.right);
+      h.nodes.push_back(make_float4(n.box.mn[0], n.box.mn[1], n.box.mn[2], bitsAs<float>(&l)));
+      h.nodes.push_back(make_float4(n.box.mx[0], n.box.mx[1], n.box.mx[2], bitsAs<float>(&r)));
+      h.nodeAxis.push_back(n.axis);
+    }
+    h.world.push_back(SRT_NODE_REF(base));
+    h.stackDepth = std::max(h.stackDepth, b.maxPending);
+    // tree depth for reporting: longest root->node chain
+    std::vector<int> depth(b.nodes.size(), 1);
+    for (size_t i = 0; i < b.nodes.size(); ++i) {  // pre-order: parents precede children
+      h.bvhDepth = std::max(h.bvhDepth, depth[i]);
+      if (b.nodes[i].left >= 0) depth[b.nodes[i].left] = depth[i] + 1;
+      if (b.nodes[i].right >= 0) depth[b.nodes[i].right] = depth[i] + 1;
+    }
+  }
+  if (h.nodes.size() / 2 > (size_t)SRT_MAX_NODES)
+    return format("scene: %zu BVH nodes exceed the %d the device references can address", h.nodes.size() / 2, SRT_MAX_NODES);
+
+  // ---- materials / textures.  typeBits: the material's type and SRT_MAT_TEXTURED, as the primitives' material words
+  // and the shading records carry them
+  h.materials.resize(d->numMaterials);
+  std::vector<int32_t> typeBits(d->numMaterials);
+  for (int i = 0; i < d->numMaterials; ++i) {
+    const SrtMaterialIn& m = d->materials[i];
+    DevMaterial& dm = h.materials[i];
+    memset(&dm, 0, sizeof dm);
+    dm.type = m.type;
+    dm.albedoTex = m.albedoTex; dm.normalTex = m.normalTex; dm.metallicTex = m.metallicTex; dm.roughnessTex = m.roughnessTex;
+    memcpy(dm.albedo, m.albedo, 16);
+    dm.metalness = m.type == SRT_MAT_METAL ? (m.fuzz < 1.0f ? m.fuzz : 1.0f)  // material.h:89
+                   : m.type == SRT_MAT_DIELECTRIC ? m.ir : m.metalness;
+    dm.roughness = m.roughness;
+    // which hitRecord fields this material can observe (srt_kernels.hip sphereRecord/triRecord)
+    auto readsUv = [&](int tex) {
+      if (tex < 0) return false;
+      const SrtTextureIn& t = d->textures[tex];
+      if (t.kind == SRT_TEX_IMAGE) return true;
+      if (t.kind == SRT_TEX_CHECKER) return d->textures[t.even].kind == SRT_TEX_IMAGE || d->textures[t.odd].kind == SRT_TEX_IMAGE;
+      return false;
+    };
+    bool uv = readsUv(m.albedoTex);
+    if (m.type == SRT_MAT_PBR) uv = uv || readsUv(m.normalTex) || readsUv(m.metallicTex) || readsUv(m.roughnessTex);
+    dm.flags = (uv ? 1 : 0) | ((m.type == SRT_MAT_PBR && m.normalTex >= 0) ? 2 : 0);
+    const bool textured = m.type == SRT_MAT_PBR && (m.albedoTex >= 0 || m.normalTex >= 0 || m.metallicTex >= 0 || m.roughnessTex >= 0);
+    typeBits[i] = (m.type & 3) | (textured ? SRT_MAT_TEXTURED : 0);
+  }
+  // textures: 3-byte images are padded to one aligned dword per texel, so a lookup is one
+  // buffer_load_dword; 1- and 2-byte images keep their byte rows (the 1-bpp quirk of texture.h:147 reads the
+  // neighbouring texels)
+  h.textures.resize(d->numTextures);
+  for (int i = 0; i < d->numTextures; ++i) {
+    const SrtTextureIn& t = d->textures[i];
+    DevTexture& dt = h.textures[i];
+    memset(&dt, 0, sizeof dt);
+    dt.kind = t.kind; dt.width = t.width; dt.height = t.height; dt.bpp = t.bpp;
+    dt.even = t.even; dt.odd = t.odd;
+    memcpy(dt.color, t.color, 12);
+    if (t.kind != SRT_TEX_IMAGE || t.width == 0) continue;
+    const size_t n = (size_t)t.width * t.height;
+    const uint8_t* src = d->texels + t.texelOffset;
+    h.texels.resize((h.texels.size() + 3) & ~(size_t)3);  // dword aligned
+    dt.offset = (int64_t)h.texels.size();
+    if (t.bpp == 3) {
+      const size_t at = h.texels.size();
+      h.texels.resize(at + 4 * n);
+      for (size_t k = 0; k < n; ++k) {
+        h.texels[at + 4 * k + 0] = src[3 * k + 0];
+        h.texels[at + 4 * k + 1] = src[3 * k + 1];
+        h.texels[at + 4 * k + 2] = src[3 * k + 2];
+        h.texels[at + 4 * k + 3] = 255;
+      }
+    } else {
+      h.texels.insert(h.texels.end(), src, src + n * t.bpp);
+    }
+    if (h.texels.size() > (size_t)0x7fffff00) return "scene: more than 2 GiB of texels";
+  }
+  // ---- the material's flags ride in every primitive's material word (srt_device.h SRT_MAT_FLAGS_SHIFT), and the hit
+  // step's 128-byte shading records (srt_kernels.hip shade)
+  if (d->numMaterials > SRT_MAT_INDEX_MASK) return format("scene: more than %d materials", SRT_MAT_INDEX_MASK);
+  auto withFlags = [&](float& word) {
+    int32_t bits = bitsAs<int32_t>(&word);
+    const int32_t m = bits & SRT_MAT_INDEX_MASK;
+    if (m < d->numMaterials) bits |= (h.materials[m].flags & 3) << SRT_MAT_FLAGS_SHIFT | typeBits[m] << SRT_MAT_TYPE_SHIFT;
+    word = bitsAs<float>(&bits);
+  };
+  for (int i = 0; i < d->numTriangles; ++i) withFlags(h.triShade[4 * (size_t)i + 3].w);
+  for (int i = 0; i < d->numSpheres; ++i) withFlags(h.spheres[3 * (size_t)i + 1].w);
+  h.shadeRecs.assign((size_t)8 * d->numMaterials, make_uint4(0, 0, 0, 0));
+  for (int i = 0; i < d->numMaterials; ++i) {
+    const DevMaterial& m = h.materials[i];
+    auto f2u = [](float f) { return bitsAs<uint32_t>(&f); };
+    uint4* r = &h.shadeRecs[(size_t)8 * i];
+    r[0] = make_uint4((uint32_t)typeBits[i], (uint32_t)m.flags, f2u(m.metalness), f2u(m.roughness));
+    r[1] = make_uint4(f2u(m.albedo[0]), f2u(m.albedo[1]), f2u(m.albedo[2]), f2u(m.albedo[3]));
+    const int32_t ids[4] = {m.albedoTex, m.normalTex, m.metallicTex, m.roughnessTex};
+    // +32: the emit texture of a light, in full
+    if (m.type == SRT_MAT_LIGHT && ids[0] >= 0) {
+      const DevTexture& t = h.textures[ids[0]];
+      if (t.kind == SRT_TEX_SOLID)
+        r[2] = make_uint4(1, f2u(t.color[0]), f2u(t.color[1]), f2u(t.color[2]));
+      else if (t.kind == SRT_TEX_IMAGE && t.width == 0)
+        r[2] = make_uint4(1, f2u(1.0f), f2u(0.0f), f2u(1.0f));  // failed load: magenta (texture.h:130-131)
+      else if (t.kind == SRT_TEX_IMAGE && t.bpp >= 3)
+        r[2] = make_uint4(2, (uint32_t)t.width, (uint32_t)t.height, (uint32_t)t.offset);
+      else
+        r[2] = make_uint4(3, (uint32_t)ids[0], 0, 0);  // checker, 1- and 2-byte images: texValue
+    }
+    // +48, +64: the four pbr slots, two dwords each
+    uint32_t packed[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < 4; ++k) {
+      if (ids[k] < 0) continue;  // mode 0: no texture
+      const DevTexture& t = h.textures[ids[k]];
+      if (t.kind == SRT_TEX_IMAGE && t.bpp >= 3 && t.width > 0 && t.width < 32768 && t.height < 32768) {
+        packed[2 * k] = 2u | (uint32_t)t.width << 2 | (uint32_t)t.height << 17;
+        packed[2 * k + 1] = (uint32_t)t.offset;
+      } else {
+        packed[2 * k] = 3u;  // everything else goes through texValue on the id
+        packed[2 * k + 1] = (uint32_t)ids[k];
+      }
+    }
+    // an albedo slot that is checker(solidColor, solidColor): both colours into the record (+80 even, +96 odd)
+    if (m.type == SRT_MAT_PBR && ids[0] >= 0 && h.textures[ids[0]].kind == SRT_TEX_CHECKER) {
+      const DevTexture& c = h.textures[ids[0]];
+      if (c.even >= 0 && c.odd >= 0 && c.even < (int)h.textures.size() && c.odd < (int)h.textures.size() && h.textures[c.even].kind == SRT_TEX_SOLID &&
+          h.textures[c.odd].kind == SRT_TEX_SOLID) {
+        packed[0] = 7u;  // SRT_SLOT_CHECKER2
+        r[5] = make_uint4(f2u(h.textures[c.even].color[0]), f2u(h.textures[c.even].color[1]), f2u(h.textures[c.even].color[2]), 0);
+        r[6] = make_uint4(f2u(h.textures[c.odd].color[0]), f2u(h.textures[c.odd].color[1]), f2u(h.textures[c.odd].color[2]), 0);
+      }
+    }
+    r[3] = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+    r[4] = make_uint4(packed[4], packed[5], packed[6], packed[7]);
+  }
+  // ---- triangle records in tree order.  Device arrays were filled in the scene's own triangle order; a tree's
+  // leaves reference them at random (a mesh's index order has nothing to do with the median splits), and with
+  // millions of triangles every test is then a 48-byte gather from a cold place.  Renumber the triangles by
+  // their first appearance in the (pre-order) node arrays of the host-built trees: the two triangles of a leaf
+  // and the leaves of a subtree become neighbours in memory.  Triangles no host-built tree references keep
+  // their relative order behind them.  References are rewritten, nothing else changes (primitive ids reported
+  // by srtTraceRays go through triPrimId, which is permuted along).
+  if (d->numTriangles > 1 && !h.nodes.empty()) {
+    std::vector<int32_t> order(d->numTriangles, -1);
+    int32_t next = 0;
+    auto visit = [&](float bits) {
+      const int32_t r = bitsAs<int32_t>(&bits);
+      if (r >= 0 || r == SRT_REF_DONE) return;
+      const int32_t pr = ~r;
+      if ((pr & 1) == 0 && (pr >> 1) < d->numTriangles && order[pr >> 1] < 0) order[pr >> 1] = next++;
+    };
+    for (size_t i = 0; i + 1 < h.nodes.size(); i += 2) {
+      visit(h.nodes[i].w);
+      visit(h.nodes[i + 1].w);
+    }
+    if (next > 0) {
+      for (int32_t i = 0; i < d->numTriangles; ++i)
+        if (order[i] < 0) order[i] = next++;
+      auto remap = [&](int32_t r) {
+        if (r >= 0 || r == SRT_REF_DONE || (~r & 1)) return r;
+        return ~(order[~r >> 1] << 1);
+      };
+      for (float4& v : h.nodes) {
+        const int32_t r = remap(bitsAs<int32_t>(&v.w));
+        v.w = bitsAs<float>(&r);
+      }
+      for (int32_t& wr : h.world) wr = remap(wr);
+      std::vector<float4> tt(h.triTest.size()), ts(h.triShade.size());
+      std::vector<int32_t> tp(h.triPrimId.size());
+      for (int32_t i = 0; i < d->numTriangles; ++i) {
+        const int32_t j = order[i];
+        for (int k = 0; k < 3; ++k) tt[3 * (size_t)j + k] = h.triTest[3 * (size_t)i + k];
+        for (int k = 0; k < 4; ++k) ts[4 * (size_t)j + k] = h.triShade[4 * (size_t)i + k];
+        tp[j] = h.triPrimId[i];
+      }
+      h.triTest.swap(tt);
+      h.triShade.swap(ts);
+      h.triPrimId.swap(tp);
+      triDevIndex.swap(order);  // devRef of the device-built trees below
+    }
+  }
+  // ---- device-built trees: their primitives as device references.  Their node boxes are unions of primitive boxes, so
+  // fastDiv's certificate covers those as well as the host-built nodes.
+  bool certified = true;
+  for (const float4& v : h.nodes) certified = certified && fastDivOperand(v.x) && fastDivOperand(v.y) && fastDivOperand(v.z);
+  for (DeviceBuild& db : h.deviceBuilds) {
+    const SrtWorldItem& it = d->world[db.item];
+    db.refs.resize(it.count);
+    for (int i = 0; i < it.count; ++i) {
+      db.refs[i] = devRef(~(it.first + i));
+      const Box bx = primBox(d, it.first + i, it.time0, it.time1);
+      for (int k = 0; k < 3; ++k) certified = certified && fastDivOperand(bx.mn[k]) && fastDivOperand(bx.mx[k]);
+    }
+  }
+  h.fastDivScene = certified ? o.fastDiv : 0;
+  // ---- thread links (srt_thread.h): the 16-bit form the LDS-resident-tree kernels walk (DevScene::nodeThread), and for a
+  // tree that does not fit into LDS the path-pool kernel's hybrid records (32-bit references, resident nodes first)
+  if (h.deviceBuilds.empty() && !h.nodes.empty()) {
+    srtThreadLinks16(h.nodes, h.world, d->numTriangles, d->numSpheres, h.nodeThread);
+    if (o.wfHybrid > 0) {
+      const size_t n = h.nodes.size() / 2;
+      const size_t fits = (160 * 1024 - 64 * sizeof(int32_t) - 20 * 2048) / 32;       // beside a pool of 2048 contexts
+      const size_t fitsWhole = (160 * 1024 - 64 * sizeof(int32_t) - 18 * 1024) / 32;  // the whole-tree form's smallest pool
+      const size_t cap = o.wfResidentMax > 0 ? std::min<size_t>(fits, (size_t)o.wfResidentMax) : fits;
+      if (n > (o.wfResidentMax > 0 ? cap : fitsWhole))
+        h.wfResident = srtHybridRecords(h.nodes, h.world, d->numTriangles, d->numSpheres, cap, h.nodesWf, h.worldWf, h.primSecond);
+    }
+  }
+  // ---- material class per primitive reference (DevScene::primClass)
+  auto classOf = [&](float word, bool sphere) -> uint8_t {
+    const int32_t bits = bitsAs<int32_t>(&word);
+    const int type = (bits >> SRT_MAT_TYPE_SHIFT) & 3, flags = (bits >> SRT_MAT_FLAGS_SHIFT) & 3;
+    if (type != SRT_MAT_PBR) return 2;
+    if (!sphere) return 0;
+    // a sphere whose pbr material reads uv or a normal map (the textured iron sphere: acosf / atan2f, a tangent frame,
+    // four lookups) would make every hit step of the plain spheres (the ground) run that code too: it goes with "the rest"
+    return flags ? 2 : 1;
+  };
+  h.primClass.assign((size_t)2 * std::max(d->numTriangles, d->numSpheres) + 2, 2);
+  for (int i = 0; i < d->numTriangles; ++i) h.primClass[(size_t)i << 1] = classOf(h.triShade[4 * (size_t)i + 3].w, false);
+  for (int i = 0; i < d->numSpheres; ++i) h.primClass[((size_t)i << 1) | 1] = classOf(h.spheres[3 * (size_t)i + 1].w, true);
+  return std::string();
+}
+
+extern "C" {
+
+float srtHostRandomFloat(void) { return hostRandomFloat(); }
+void srtHostRandomReset(void) { hostGenerator().seed(std::mt19937::default_seed); }
+
+// camera.h:10-38
+int srtMakeCamera(const SrtCameraParams* in, SrtCamera* out) {
+  if (!in || !out) return 1;
+  const float pi = 3.1415926535897932385f;
+  H3 eye = h3(in->eye), lookAt = h3(in->lookAt), up = h3(in->up);
+  float theta = in->vfovDegrees * pi / 180.0f;  // deg2rad, globals.h:26-28
+  double h = tan((double)(theta / 2.0f));       // camera.h:20: tan(float) is the double overload
+  double vpHeight = 2.0f * h;
+  double vpWidth = in->aspect * vpHeight;
+  H3 w = unitH(eye - lookAt);
+  H3 hor = unitH(crossH(up, w));
+  H3 vert = unitH(crossH(w, hor));
+  H3 horizontal = (float)(in->focusDist * vpWidth) * hor;  // Eigen casts the double scalar to float
+  H3 vertical = (float)(in->focusDist * vpHeight) * vert;
+  H3 lleft = eye - horizontal / 2.0f - vertical / 2.0f - in->focusDist * w;
+  const H3* src[] = {&eye, &lleft, &horizontal, &vertical, &w, &hor, &vert};
+  float* dst[] = {out->origin, out->lleft, out->horizontal, out->vertical, out->w, out->hor, out->vert};
+  for (int i = 0; i < 7; ++i) {
+    dst[i][0] = src[i]->x;
+    dst[i][1] = src[i]->y;
+    dst[i][2] = src[i]->z;
+  }
+  out->lensRadius = in->aperture / 2.0f;
+  out->time0 = in->time0;
+  out->time1 = in->time1;
+  return 0;
+}
+
+}  // extern "C"

@@ -35,7 +35,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
-TEST_EXPORTS = ["srtScatterTest", "srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
+TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
                 "srtTestThreadLinks16", "srtTestHybridRecords"]
 
 _vp = C.c_void_p
@@ -71,7 +71,6 @@ lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
 lib.srtGatherTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
 lib.srtRenderImageRanks.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp]
 lib.srtCommDestroy.argtypes = [_vp]
-lib.srtScatterTest.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp]
 lib.srtScatterRays.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp]
 lib.srtSetTunable.argtypes = [_vp, C.c_char_p, C.c_int32]
 lib.srtGetTunable.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_int32)]
@@ -278,7 +277,7 @@ class Context:
         rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)
         hits = np.ascontiguousarray(hits, abi.HIT_DTYPE)
         out = np.zeros((len(rays), 13), np.float32)
-        self._check(lib.srtScatterTest(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), seed, out.ctypes.data))
+        self._check(lib.srtScatterRays(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), seed, out.ctypes.data))
         return out
 
     def set_tunable(self, name, value):

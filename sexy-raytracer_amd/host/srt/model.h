@@ -1,6 +1,6 @@
 // model.h -- host mirror of triangle / mesh / model and gltfLoad (model.h:18-460).
 // triangle::hit, getNormal and calcTangentBasis are device / upload-time code
-// (srt_kernels.hip triHit, srt_api.cpp srtUploadScene); this file keeps the containers, the bounding
+// (srt_kernels.hip triHit, srt_scene.cpp flattenScene); this file keeps the containers, the bounding
 // box the BVH build needs, and a glTF loader with gltfLoad's semantics.
 #ifndef SRT_HOST_MODEL_H
 #define SRT_HOST_MODEL_H

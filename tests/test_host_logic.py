@@ -40,7 +40,7 @@ def test_abi_struct_sizes(abi):
 
 @pytest.mark.parametrize("name", ["spheres", "iron", "masterchief"])
 def test_host_bvh_matches_oracle(dev, oracle, srt, name):
-    """bvh.h:55-95 restated twice (product host builder in srt_api.cpp, oracle): same topology,
+    """bvh.h:55-95 restated twice (product host builder in srt_scene.cpp, oracle): same topology,
     same box bits, same pre-order numbering."""
     sb = srt.scenes.SCENES[name]()
     nodes, stack_depth = dev.build_bvh_host(sb)
