@@ -4,7 +4,9 @@
 // the pixel loop is hipDevice::rtFrame instead of the CPU loops.
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
+//                  [--denoise FILE.png]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
+//   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   SRT_DATA_DIR selects the directory of the glTF's images (default "../data/", as the reference).
 #include <chrono>
 #include <cstdlib>
@@ -71,7 +73,7 @@ static bool writeFeaturePng(const std::string& path, const std::vector<float>& p
 
 int main(int argc, char** argv) {
   int imageHeight = 720, numSamples = 5000, maxBounce = 4, chunks = 0;
-  std::string out = "test.png", features;
+  std::string out = "test.png", features, denoise;
   for (int i = 1; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--gltf")) gltfPath = argv[i + 1];
     else if (!strcmp(argv[i], "--height")) imageHeight = atoi(argv[i + 1]);
@@ -80,6 +82,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--chunks")) chunks = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
     else if (!strcmp(argv[i], "--features")) features = argv[i + 1];
+    else if (!strcmp(argv[i], "--denoise")) denoise = argv[i + 1];
   }
   const float aspect = 16.0f / 9.0f;
   const int imageWidth = static_cast<int>(imageHeight * aspect);
@@ -95,7 +98,14 @@ int main(int argc, char** argv) {
   if (!device.init(imageWidth, imageHeight, world)) return 1;
   device.sppChunks = chunks;
   auto t0 = std::chrono::steady_clock::now();
-  if (!device.rtFrame(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
+  std::vector<uint8_t> denoised;
+  if (denoise.empty()) {
+    if (!device.rtFrame(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
+  } else {  // one render: the noisy frame and the denoised one
+    denoised.resize((size_t)4 * imageWidth * imageHeight);
+    if (!device.rtFrameDenoised(target, denoised.data(), imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce))
+      return 1;
+  }
   double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (!features.empty()) {
     std::vector<float> albedo, normal;
@@ -109,6 +119,10 @@ int main(int argc, char** argv) {
   device.terminate();
 
   stbi_write_png(out.c_str(), imageWidth, imageHeight, 4, target, 4 * imageWidth);
+  if (!denoise.empty() && !stbi_write_png(denoise.c_str(), imageWidth, imageHeight, 4, denoised.data(), 4 * imageWidth)) {
+    std::cerr << "ERROR: could not write " << denoise << "\n";
+    return 1;
+  }
   free(target);
   std::cerr << imageWidth << "x" << imageHeight << " @" << numSamples << " spp: " << device.numPrims << " primitives, kernel "
             << device.lastKernelMs << " ms (" << (double)imageWidth * imageHeight * numSamples / device.lastKernelMs / 1e3

@@ -324,6 +324,67 @@ enum { SRT_FEATURE_ALBEDO = 1, SRT_FEATURE_NORMAL = 2, SRT_FEATURE_POSITION = 4,
 int srtRenderFeatureTiles(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* stream);
 int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, float* const hPlanes[4]);
 
+/* Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) in the spatial form of SVGF, guided by the
+ * feature planes' normals and depths, luminance-stopped by a variance estimate carried from level to level, optionally
+ * demodulated by albedo.  Single frames: there is no temporal part.  fp32 throughout.
+ *
+ * Inputs, every buffer image-order float4[W*H] as srtResolveTiles(..., dAccumImage) writes it: dBeauty = rgb sums, w = the
+ * sample count; dPlanes[k] = the resolved feature plane of bit 1 << k (sums with counts).  NORMAL and DEPTH are required,
+ * ALBEDO only when demodulating, POSITION is ignored.  Means are a float division, sum / count (0 where count == 0), as
+ * srtRenderFeatureImage takes them.  Per pixel p:
+ *   c_p = beauty.rgb / n; p is VALID if n > 0 and all three channels are finite
+ *   a~_p = max(albedo mean, 1e-3) per channel when demodulating, else 1;  e_p = c_p / a~_p;
+ *   l_p = 0.2126 e.r + 0.7152 e.g + 0.0722 e.b
+ *   p is a HIT if the normal plane's count is > 0: n_p = the mean normal normalised (0 if its length is 0), z_p = the
+ *   depth plane's mean x (t).  Depth gradient (zx, zy): per axis the one-sided difference to a hit neighbour with the
+ *   smaller magnitude (a tie takes the backward one); 0 when no neighbour on that axis is a hit
+ *   edge weights between p and q at pixel offset D (step included):
+ *     w_n = max(0, n_p.n_q)^sigmaN if both are hits, 1 if both are misses, 0 otherwise
+ *     a_z = |z_p - z_q| / (sigmaZ |zx D.x + zy D.y| + 1e-3 z_p) if both are hits, else 0
+ *   level-0 variance: v_p = max(0, mu2 - mu1^2) over the valid pixels q of the 7x7 window, mu1 and mu2 the means of l
+ *     and l^2 weighted by w_n exp(-a_z) at step 1 (0 when those weights sum to 0)
+ *   level i = 0 .. iterations-1, step s = 2^i: the taps q = p + s (dx, dy), dx, dy in -2..2, inside the image and valid,
+ *     w = h[dx] h[dy] exp(sigmaN ln(n_p.n_q) - a_z - a_l), h = [1, 4, 6, 4, 1] / 16 (w = 0 where w_n = 0; between two
+ *     misses the normal and depth terms are 1), a_l = |l_p - l_q| / (sigmaL sqrt(g_p) + 1e-10), g_p = the 3x3
+ *     [1, 2, 1]/4 blur of v around p (taps outside the image dropped, the rest renormalised); a_l = 0 for a centre that
+ *     is not valid.  e'_p = sum w e_q / sum w, v'_p = sum w^2 v_q / (sum w)^2, and p becomes valid (NaN, inf and the
+ *     white overflowed chunk sums are filled from their neighbours); if sum w = 0, e' = 0, v' = 0 and p stays invalid
+ *   output: e' a~ after the last level (0 for a pixel still invalid)
+ * Sums are taken about the centre (sum w (e_q - e_p), the moments of l about l_p; 0 for a centre that is not valid): the
+ * same math, but a constant neighbourhood comes back exactly.
+ * The kernel computes the exponentials as one v_exp_f32 and the normal power as one v_log_f32 per tap: it agrees with a
+ * libm evaluation of these formulas within a few 1e-6 relative (measured: DESIGN.md 5.6).
+ *
+ * srtDenoise      DEVICE buffers, asynchronous on `stream`.  dOut (may be NULL) = float4[W*H]: rgb = the denoised mean
+ *                 radiance, w = the beauty count; dRgba (may be NULL, not both) = uchar4[W*H], srtResolveTiles's
+ *                 quantisation of that mean (sqrt, clamp to 0.999, x256 truncated, NaN -> 0, alpha 255).  The context holds
+ *                 the scratch, SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL bytes per pixel of the largest image denoised, until
+ *                 srtDestroy; calls on one context share it, so they are ordered on one stream.
+ * srtRenderDenoisedImage  blocking: the beauty render (hAccum is bit-identical to srtRenderImage's), the feature pass of
+ *                 the same parameters, the denoiser; HOST buffers float[W*H*4], float[W*H*4] and uint8[W*H*4], each may be
+ *                 NULL.
+ * Errors (non-zero, message in srtLastError; no kernel launched): a missing NORMAL or DEPTH plane, demodulate without
+ * ALBEDO, a size <= 0, iterations outside 0..8, a negative sigma.  Neither entry changes the tunables, the chunk scratch,
+ * srtLastKernelMs or srtGetLaunchInfo beyond what the render and the feature pass of the blocking entry do. */
+#define SRT_DENOISE_MAX_ITERATIONS 8
+#define SRT_DENOISE_DEFAULT_ITERATIONS 5
+#define SRT_DENOISE_DEFAULT_SIGMA_LUMINANCE 4.0f
+#define SRT_DENOISE_DEFAULT_SIGMA_NORMAL 16.0f
+#define SRT_DENOISE_DEFAULT_SIGMA_DEPTH 1.0f
+#define SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL 56
+typedef struct SrtDenoiseParams { /* a field of 0 takes its default */
+  int32_t iterations;   /* a-trous levels, step 2^i for level i: 1..8, default 5 */
+  int32_t demodulate;   /* non-zero: filter beauty / albedo and multiply back (needs the ALBEDO plane) */
+  float sigmaLuminance; /* default 4 */
+  float sigmaNormal;    /* default 16 (128 keeps the noise of normal-mapped surfaces) */
+  float sigmaDepth;     /* default 1 */
+  int32_t pad[3];
+} SrtDenoiseParams;
+int srtDenoise(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
+               const void* const dPlanes[4], void* dOut, void* dRgba, void* stream);
+int srtRenderDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
+                           float* hDenoised, uint8_t* hRgba);
+
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the
  * ranks' equal-sized tile buffers to rank 0 over RCCL (ncclGather), after which rank 0 calls

@@ -19,6 +19,10 @@ SRT_NO_HIT = -1
 SRT_FEATURE_ALBEDO, SRT_FEATURE_NORMAL, SRT_FEATURE_POSITION, SRT_FEATURE_DEPTH = 1, 2, 4, 8
 SRT_FEATURE_ALL = 15
 FEATURE_PLANES = ("albedo", "normal", "position", "depth")  # names of the planes, in bit order
+# denoiser (srtDenoise / srtRenderDenoisedImage): defaults a field of 0 takes, and the context's scratch per pixel
+SRT_DENOISE_MAX_ITERATIONS, SRT_DENOISE_DEFAULT_ITERATIONS = 8, 5
+SRT_DENOISE_DEFAULT_SIGMA_LUMINANCE, SRT_DENOISE_DEFAULT_SIGMA_NORMAL, SRT_DENOISE_DEFAULT_SIGMA_DEPTH = 4.0, 16.0, 1.0
+SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL = 56
 
 f32, i32, i64, u64 = C.c_float, C.c_int32, C.c_int64, C.c_uint64
 
@@ -94,6 +98,11 @@ class SrtRenderParams(C.Structure):
                 ("sampleFirst", i32)]
 
 
+class SrtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", i32), ("demodulate", i32), ("sigmaLuminance", f32), ("sigmaNormal", f32),
+                ("sigmaDepth", f32), ("pad", i32 * 3)]
+
+
 class SrtStats(C.Structure):
     _fields_ = [("samples", u64), ("rays", u64), ("nodeVisits", u64), ("boxPasses", u64),
                 ("triTests", u64), ("sphereTests", u64), ("shadedTriHits", u64), ("texelFetches", u64),
@@ -130,6 +139,14 @@ def default_render_params(width, height, spp, max_bounce, seed=1, background=(0.
     p.tileFirst, p.tileStride, p.sppChunks, p.countStats = tile_first, tile_stride, spp_chunks, count_stats
     p.sampleFirst = sample_first
     return p
+
+
+def default_denoise_params(iterations=0, demodulate=0, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0):
+    """include/srt_hip.h SrtDenoiseParams: a field of 0 takes the library's default."""
+    d = SrtDenoiseParams()
+    d.iterations, d.demodulate = iterations, demodulate
+    d.sigmaLuminance, d.sigmaNormal, d.sigmaDepth = sigma_luminance, sigma_normal, sigma_depth
+    return d
 
 
 def default_camera_params(aspect=16.0 / 9.0):

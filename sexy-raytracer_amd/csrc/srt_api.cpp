@@ -31,6 +31,7 @@ int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hit
                        hipStream_t stream);
 int srt_features_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU);
 int srt_launch_features(const FeatureArgs* a, int closest, int ldsTree, int grid, size_t lds, hipStream_t stream);
+int srt_launch_denoise(const DenoiseArgs* a, int iterations, int ldsMaxStep, hipStream_t stream);
 }
 
 // Diagnostic tunables of the work distribution and the wave scheduler.  Environment variables give the
@@ -46,6 +47,7 @@ struct Tunables {
   int ldsTree;
   int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
   int wfHybrid, wfResidentMax, wfFarRounds;
+  int denoiseLdsStep;
 };
 
 struct SrtContext {
@@ -73,6 +75,7 @@ struct SrtContext {
   DeviceBuffer wfPool, wfAttHi;  // path-pool kernel: contexts and upper attenuation levels (srt_wavefront.hip)
   int32_t* dWfError = nullptr;
   DeviceBuffer dFeatureCounter;  // the feature pass's tile counter (its own: a render's queues are never touched)
+  DeviceBuffer denoiseScratch;   // srtDenoise: guide records, depth gradients, two colour buffers (56 B per pixel)
   DeviceBuffer tileTable;   // RenderArgs::tileXY for the image size and tile order below
   int32_t tileTableKey[3] = {0, 0, 0};
   RenderPlan lastPlan{};  // the most recent render launch (srtGetLaunchInfo)
@@ -167,6 +170,9 @@ const TunableName kTunables[] = {
     // 0 = 2 for trees of up to 2^20 nodes (cache-resident: +10 % and more), 1 beyond (HBM-bound soups of 4 M and 10 M
     // triangles lose 5-10 % with 2) -- profiles/r03/hybrid.txt
     {"wf_far_rounds", "SRT_WF_FAR_ROUNDS", &Tunables::wfFarRounds, 0},
+    // srtDenoise: a-trous levels of step <= this stage their (16 + 4 step)^2 window in LDS, larger steps read through the
+    // caches (srt_denoise.hip; 8 at most, 0 = never) -- profiles/r05/denoise_bench.json
+    {"denoise_lds_step", "SRT_DENOISE_LDS_STEP", &Tunables::denoiseLdsStep, 4},
 };
 
 // The fields a launch over the image shares (RenderArgs, FeatureArgs): the scene, the camera, the image, its samples and
@@ -876,6 +882,117 @@ int srtRenderFeatureTiles(SrtContext* ctx, const SrtRenderParams* p, int32_t pla
 }
 int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, float* const hPlanes[4]) {
   SRT_GUARDED(ctx, srtRenderFeatureImageImpl(ctx, p, planes, hPlanes));
+}
+
+/* Denoiser (srt_denoise.hip).  Reads the tunable denoise_lds_step; writes only the caller's outputs and its own scratch. */
+static int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, DenoiseArgs& a,
+                              int& iterations) {
+  if (!d) return fail(ctx, "denoise: null parameters");
+  if (width <= 0 || height <= 0) return fail(ctx, "denoise: image size %dx%d must be positive", width, height);
+  if ((int64_t)width * height > 0x7fffffff) return fail(ctx, "denoise: image of %dx%d pixels is too large", width, height);
+  iterations = d->iterations == 0 ? SRT_DENOISE_DEFAULT_ITERATIONS : d->iterations;
+  if (iterations < 1 || iterations > SRT_DENOISE_MAX_ITERATIONS)
+    return fail(ctx, "denoise: iterations %d not in [1, %d] (0 = %d)", d->iterations, SRT_DENOISE_MAX_ITERATIONS,
+                SRT_DENOISE_DEFAULT_ITERATIONS);
+  const float sig[3] = {d->sigmaLuminance, d->sigmaNormal, d->sigmaDepth};
+  const float dflt[3] = {SRT_DENOISE_DEFAULT_SIGMA_LUMINANCE, SRT_DENOISE_DEFAULT_SIGMA_NORMAL, SRT_DENOISE_DEFAULT_SIGMA_DEPTH};
+  float use[3];
+  for (int k = 0; k < 3; ++k) {
+    if (!(sig[k] >= 0.0f && sig[k] < 1e30f)) return fail(ctx, "denoise: sigma %g must be finite and >= 0 (0 = default)", sig[k]);
+    use[k] = sig[k] == 0.0f ? dflt[k] : sig[k];
+  }
+  memset(&a, 0, sizeof a);
+  a.width = width;
+  a.height = height;
+  a.sigmaL = use[0];
+  a.sigmaN = use[1];
+  a.sigmaZ = use[2];
+  return 0;
+}
+
+static int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
+                          const void* const dPlanes[4], void* dOut, void* dRgba, void* streamPtr) {
+  if (!ctx) return 1;
+  DenoiseArgs a;
+  int iterations = 0;
+  if (checkDenoiseParams(ctx, d, width, height, a, iterations)) return 1;
+  if (!dBeauty) return fail(ctx, "denoise: null beauty buffer");
+  if (!dPlanes) return fail(ctx, "denoise: null plane array");
+  if (!dPlanes[1]) return fail(ctx, "denoise: the NORMAL plane is required");
+  if (!dPlanes[3]) return fail(ctx, "denoise: the DEPTH plane is required");
+  if (d->demodulate && !dPlanes[0]) return fail(ctx, "denoise: demodulate needs the ALBEDO plane");
+  if (!dOut && !dRgba) return fail(ctx, "denoise: no output buffer");
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const size_t nPix = (size_t)width * height;
+  HIP_OK(ctx, ctx->denoiseScratch.reserve(nPix * SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL));
+  char* s = ctx->denoiseScratch.get<char>();
+  a.beauty = static_cast<const float4*>(dBeauty);
+  a.normal = static_cast<const float4*>(dPlanes[1]);
+  a.depth = static_cast<const float4*>(dPlanes[3]);
+  a.albedo = d->demodulate ? static_cast<const float4*>(dPlanes[0]) : nullptr;
+  a.guide = reinterpret_cast<float4*>(s);
+  a.col[0] = reinterpret_cast<float4*>(s + 16 * nPix);
+  a.col[1] = reinterpret_cast<float4*>(s + 32 * nPix);
+  a.grad = reinterpret_cast<float2*>(s + 48 * nPix);
+  a.out = static_cast<float4*>(dOut);
+  a.rgba = static_cast<uint8_t*>(dRgba);
+  const int rc = srt_launch_denoise(&a, iterations, std::max(0, ctx->tun.denoiseLdsStep), static_cast<hipStream_t>(streamPtr));
+  if (rc) return fail(ctx, "denoise launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static int srtRenderDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtDenoiseParams* d, float* hAccum,
+                                      float* hDenoised, uint8_t* hRgba) {
+  if (!ctx) return 1;
+  if (!pIn) return fail(ctx, "denoise: null render parameters");
+  DenoiseArgs check;
+  int iterations = 0;
+  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, check, iterations)) return 1;
+  SrtRenderParams p = *pIn;
+  p.tileFirst = 0;
+  p.tileStride = 1;
+  if (checkParams(ctx, &p)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
+  const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
+  const int32_t planes = SRT_FEATURE_NORMAL | SRT_FEATURE_DEPTH | (d->demodulate ? SRT_FEATURE_ALBEDO : 0);
+  // the beauty render and its resolve exactly as srtRenderImage does them, then the feature pass of the same parameters
+  DeviceBuffer tiles, accum, featTiles[4], featImage[4], out, rgba;
+  if (tiles.reserve(tileBytes) != hipSuccess || accum.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
+  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
+  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
+  void* dTiles[4] = {nullptr, nullptr, nullptr, nullptr};
+  const void* dPlanes[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < 4; ++k) {
+    if (!(planes >> k & 1)) continue;
+    if (featTiles[k].reserve(tileBytes) != hipSuccess || featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess)
+      return fail(ctx, "denoise: hipMalloc");
+    dTiles[k] = featTiles[k].get();
+    dPlanes[k] = featImage[k].get();
+  }
+  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr)) return 1;
+  if (srtResolveTiles(ctx, &p, tiles.get(), nullptr, accum.get(), nullptr)) return 1;
+  if (srtRenderFeatureTilesImpl(ctx, &p, planes, dTiles, nullptr)) return 1;
+  for (int k = 0; k < 4; ++k)
+    if (dTiles[k] && srtResolveTiles(ctx, &p, dTiles[k], nullptr, featImage[k].get(), nullptr)) return 1;
+  if (hDenoised || hRgba) {
+    if (srtDenoiseImpl(ctx, d, p.imageWidth, p.imageHeight, accum.get(), dPlanes, out.get(), rgba.get(), nullptr)) return 1;
+  }
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "denoise: kernel failed: %s", hipGetErrorString(hipGetLastError()));
+  if (wfCheck(ctx)) return 1;
+  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy accum");
+  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy denoised");
+  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy rgba");
+  return 0;
+}
+
+int srtDenoise(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
+               const void* const dPlanes[4], void* dOut, void* dRgba, void* stream) {
+  SRT_GUARDED(ctx, srtDenoiseImpl(ctx, d, width, height, dBeauty, dPlanes, dOut, dRgba, stream));
+}
+int srtRenderDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
+                           float* hDenoised, uint8_t* hRgba) {
+  SRT_GUARDED(ctx, srtRenderDenoisedImageImpl(ctx, p, d, hAccum, hDenoised, hRgba));
 }
 
 /* include/srt_hip_test.h: the render kernel's own traversal, ray by ray */

@@ -200,6 +200,22 @@ struct FeatureArgs {
   int32_t* counter;   // next local tile to take (zeroed before launch)
 };
 
+// srtDenoise (srt_denoise.hip): the edge-aware a-trous filter over image-order planes.  Scratch in the context, 56 B per
+// pixel: guide, gradient and the two colour buffers.
+struct DenoiseArgs {
+  int32_t width, height;
+  const float4* beauty;  // rgb sums, w = sample count
+  const float4* normal;  // sums with counts, as the resolve of a feature tile buffer gives them
+  const float4* depth;
+  const float4* albedo;  // null unless demodulating
+  float sigmaL, sigmaN, sigmaZ;
+  float4* guide;         // {n.xyz, z}; z NaN: a miss
+  float2* grad;          // the depth gradient (zx, zy), centre-only
+  float4* col[2];        // {e.rgb, v}; e.x NaN: not valid
+  float4* out;           // may be null: rgb = denoised mean, w = the beauty count
+  uint8_t* rgba;         // may be null
+};
+
 struct ResolveArgs {
   const float4* gathered;  // [rank][localTile][64]
   int32_t imageWidth, imageHeight, tilesX;

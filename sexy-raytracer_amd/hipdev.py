@@ -31,7 +31,8 @@ lib = C.CDLL(LIB_PATH)
 
 EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostRandomFloat", "srtHostRandomReset",
            "srtUploadScene", "srtSetCamera", "srtBuildBvh", "srtGetBvh", "srtGetBvhDepth", "srtNumTiles", "srtNumLocalTiles", "srtDefaultSppChunks", "srtPlanSppChunks",
-           "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage", "srtTraceRays", "srtScatterRays",
+           "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
+           "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtScatterRays",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -65,6 +66,9 @@ lib.srtResolveTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _
 lib.srtRenderImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp]
 lib.srtRenderFeatureTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, C.POINTER(_vp), _vp]
 lib.srtRenderFeatureImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, C.POINTER(C.POINTER(C.c_float))]
+lib.srtDenoise.argtypes = [_vp, C.POINTER(abi.SrtDenoiseParams), C.c_int32, C.c_int32, _vp, C.POINTER(_vp), _vp, _vp, _vp]
+lib.srtRenderDenoisedImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtDenoiseParams),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -241,6 +245,28 @@ class Context:
         1 << k (None otherwise)."""
         arr = (_vp * 4)(*[(p if p else None) for p in list(ptrs) + [None] * (4 - len(ptrs))])
         self._check(lib.srtRenderFeatureTiles(self.h, C.byref(params), int(planes), arr, stream))
+
+    def denoise(self, dparams, width, height, d_beauty_ptr, plane_ptrs, d_out_ptr=None, d_rgba_ptr=None, stream=None):
+        """Asynchronous denoiser over DEVICE image-order buffers (include/srt_hip.h srtDenoise): d_beauty_ptr = float4[W*H]
+        sums with counts, plane_ptrs[k] = the resolved feature plane of bit 1 << k (None where not given)."""
+        arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
+        self._check(lib.srtDenoise(self.h, C.byref(dparams), int(width), int(height), d_beauty_ptr, arr, d_out_ptr,
+                                   d_rgba_ptr, stream))
+
+    def render_denoised(self, params, dparams=None):
+        """Beauty render, feature pass and denoiser of one frame (srtRenderDenoisedImage).  Returns (accum, denoised, rgba):
+        (H, W, 4) float32 sums with counts, bit-identical to render_image's; (H, W, 4) float32, rgb = the denoised mean,
+        w = the count; (H, W, 4) uint8 of the denoised mean."""
+        if dparams is None:
+            dparams = abi.default_denoise_params()
+        W, H = params.imageWidth, params.imageHeight
+        accum = np.zeros((H, W, 4), np.float32)
+        denoised = np.zeros((H, W, 4), np.float32)
+        rgba = np.zeros((H, W, 4), np.uint8)
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtRenderDenoisedImage(self.h, C.byref(params), C.byref(dparams), accum.ctypes.data_as(fp),
+                                               denoised.ctypes.data_as(fp), rgba.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return accum, denoised, rgba
 
     def render_tiles(self, params, d_accum_ptr, stream=None):
         self._check(lib.srtRenderTiles(self.h, C.byref(params), d_accum_ptr, stream))

@@ -4,6 +4,8 @@
 //   rtFrame(target, w, h, cam, bg, spp, b)  render the frame into the caller-owned RGBA8 target
 //   rtFeatures(cam, bg, spp, seed, ...)     the feature pass of the same frame: albedo / normal / position / depth at
 //                                           the first hit of the camera rays rtFrame traces (a denoiser's guides)
+//   rtFrameDenoised(target, denoised, ...)  rtFrame's frame, its feature pass and the library's a-trous denoiser: the
+//                                           noisy and the denoised RGBA8 frames of one render
 //   terminate()
 //   uniqueId / initRanks                    multi-GPU: one process per GPU; rtFrame then renders this rank's
 //                                           tiles, the library gathers them with ONE ncclGather and rank 0's
@@ -12,6 +14,7 @@
 #ifndef SRT_HOST_DEVICE_H
 #define SRT_HOST_DEVICE_H
 
+#include <cmath>
 #include <iostream>
 #include <vector>
 
@@ -95,6 +98,48 @@ class hipDevice {
     }
     if (mask == 0) return true;
     if (srtRenderFeatureImage(ctx, &p, mask, out) != 0) return error();
+    return true;
+  }
+
+  // rtFrame plus the denoiser (include/srt_hip.h "Denoiser"): frameData (may be null) receives the frame rtFrame would
+  // write, denoisedData (may be null) the denoised frame with the same quantisation; accum / denoised (float[w*h*4], may be
+  // null) the sums with counts and the denoised means.  d = null: the library's defaults.  Single-process only.
+  bool rtFrameDenoised(void* frameData, void* denoisedData, int w, int h, const camera& cam, const color3f& background,
+                       int numSamples, int maxBounce, uint64_t seed = 1, const SrtDenoiseParams* d = nullptr,
+                       float* accum = nullptr, float* denoised = nullptr) {
+    if (!ctx) return false;
+    if (ranks > 1) {
+      std::cerr << "ERROR: rtFrameDenoised renders on one GPU\n";
+      return false;
+    }
+    if (srtSetCamera(ctx, &cam.data()) != 0) return error();
+    SrtRenderParams p{};
+    p.imageWidth = w; p.imageHeight = h; p.spp = numSamples; p.maxBounce = maxBounce; p.seed = seed;
+    for (int i = 0; i < 3; ++i) p.background[i] = background(i);
+    p.tMin = 0.001f;  // main.cpp:39
+    p.traversal = SRT_TRAVERSE_FAITHFUL;
+    p.tileFirst = 0; p.tileStride = 1;
+    p.sppChunks = sppChunks;
+    const SrtDenoiseParams defaults{};
+    std::vector<float> sums;
+    if (!accum && frameData) {
+      sums.resize((size_t)w * h * 4);
+      accum = sums.data();
+    }
+    if (srtRenderDenoisedImage(ctx, &p, d ? d : &defaults, accum, denoised, static_cast<uint8_t*>(denoisedData)) != 0) return error();
+    (void)srtLastKernelMs(ctx, &lastKernelMs);
+    if (frameData) {  // the resolve's quantisation (color.h:25-41) of the sums
+      uint8_t* px = static_cast<uint8_t*>(frameData);
+      const float scale = 1.0f / (float)numSamples;
+      for (size_t i = 0; i < (size_t)w * h; ++i) {
+        for (int c = 0; c < 3; ++c) {
+          const float g = std::sqrt(accum[4 * i + c] * scale);
+          const float q = 256.0f * (g < 0.0f ? 0.0f : (g > 0.999f ? 0.999f : g));
+          px[4 * i + c] = (q == q) ? (uint8_t)q : (uint8_t)0;  // NaN -> 0
+        }
+        px[4 * i + 3] = 255;
+      }
+    }
     return true;
   }
 
