@@ -4,9 +4,11 @@
 // the pixel loop is hipDevice::rtFrame instead of the CPU loops.
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
-//                  [--denoise FILE.png]
+//                  [--denoise FILE.png [--sample-variance]]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
+//   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
+//                     sample variance, srtRenderDenoisedImageMoments) instead of the spatial one
 //   SRT_DATA_DIR selects the directory of the glTF's images (default "../data/", as the reference).
 #include <chrono>
 #include <cstdlib>
@@ -74,7 +76,14 @@ static bool writeFeaturePng(const std::string& path, const std::vector<float>& p
 int main(int argc, char** argv) {
   int imageHeight = 720, numSamples = 5000, maxBounce = 4, chunks = 0;
   std::string out = "test.png", features, denoise;
-  for (int i = 1; i + 1 < argc; i += 2) {
+  bool sampleVariance = false;
+  for (int i = 1; i < argc; i += 2) {
+    if (!strcmp(argv[i], "--sample-variance")) {  // the one flag without a value
+      sampleVariance = true;
+      --i;
+      continue;
+    }
+    if (i + 1 >= argc) break;
     if (!strcmp(argv[i], "--gltf")) gltfPath = argv[i + 1];
     else if (!strcmp(argv[i], "--height")) imageHeight = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--spp")) numSamples = atoi(argv[i + 1]);
@@ -103,7 +112,8 @@ int main(int argc, char** argv) {
     if (!device.rtFrame(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
   } else {  // one render: the noisy frame and the denoised one
     denoised.resize((size_t)4 * imageWidth * imageHeight);
-    if (!device.rtFrameDenoised(target, denoised.data(), imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce))
+    if (!device.rtFrameDenoised(target, denoised.data(), imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce,
+                                1, nullptr, nullptr, nullptr, sampleVariance))
       return 1;
   }
   double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -289,6 +289,28 @@ int32_t srtPlanSppChunks(int32_t imageWidth, int32_t imageHeight, int32_t spp, i
  * rgb = sum over samples of rayColor, a = sample count. */
 int srtRenderTiles(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* stream);
 
+/* Per-pixel sample moments: srtRenderTiles with a second plane that carries the luminance moments of the samples, the
+ * per-pixel noise estimate a denoiser needs (srtDenoiseMoments) and a convergence check can use.
+ * dAccumTiles comes out bit-identical to srtRenderTiles with the same parameters (any kernel form, chunk-sum path or tile
+ * split).  dMomentTiles: DEVICE float4[numLocalTiles * 64] in the beauty tiles' layout and split:
+ *   x = sum over the samples of l_s, y = sum of l_s * l_s, z = 0, w = the sample count (the beauty's w),
+ *   l_s = 0.2126f * L.r + 0.7152f * L.g + 0.0722f * L.b of sample s's rayColor L, evaluated left to right in float.
+ * Sums follow the beauty's rules channel by channel: a float running sum in sample-index order inside a work item, the exact
+ * 2^-36 fixed-point sum of the chunk partials when sppChunks > 1 (independent of the tile split, the chunk-sum path and
+ * the order in which chunks finish), NaN / infinite samples poison x and y as they poison rgb, and a chunk partial at or
+ * beyond the fixed-point limit (SrtRenderParams.sppChunks) counts as +inf -- y, a sum of squares, reaches that limit long
+ * before rgb does (a chunk whose mean luminance exceeds sqrt(limit / samples in the chunk)).
+ * srtGatherTiles and srtResolveTiles(..., dRgba = NULL, dAccumImage) work on the moments plane unchanged.
+ * The launch runs the same kernel form with the same grid, block and LDS as srtRenderTiles (srtLastKernelMs and
+ * srtGetLaunchInfo describe it); it ignores the wf_profile tunable and leaves srtGetStats as it was.  countStats = 1 is an
+ * error, as is a NULL dMomentTiles (no kernel launched).  Device memory held by the context: the chunk scratch of
+ * SrtRenderParams.sppChunks doubles -- 32 bytes per pixel per chunk on the scratch path (which the moments launch takes
+ * while twice the slots fit the same budget), 64 bytes per pixel on the atomic path.
+ * srtRenderImageMoments: the blocking form, whole image, HOST buffers: hAccum / hRgba bit-identical to srtRenderImage,
+ * hMoments = float[W*H*4] in image order (sums with counts, not means); each may be NULL. */
+int srtRenderTilesMoments(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* dMomentTiles, void* stream);
+int srtRenderImageMoments(SrtContext* ctx, const SrtRenderParams* p, float* hAccum, float* hMoments, uint8_t* hRgba);
+
 /* color.h:25-41 (writeColorTarget) over a gathered, rank-major tile buffer
  * float4[tileStride][numLocalTiles*64]: un-permutes tiles into image order.
  * dRgba: DEVICE uint8[W*H*4] or NULL; dAccumImage: DEVICE float4[W*H] or NULL. */
@@ -384,6 +406,24 @@ int srtDenoise(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_
                const void* const dPlanes[4], void* dOut, void* dRgba, void* stream);
 int srtRenderDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
                            float* hDenoised, uint8_t* hRgba);
+
+/* Sample variance: the denoiser with the level-0 variance taken from the render's own samples (srtRenderTilesMoments).
+ * dMoments = the resolved moments plane, image-order float4[W*H] {S1 = sum l, S2 = sum l^2, 0, n}.  For a pixel with
+ * n >= 2 and finite S1, S2
+ *   v_p = max(0, S2 - S1^2 / n) / (n (n - 1)),  the subtraction in double,
+ * the unbiased variance of the pixel's MEAN luminance (the units of the spatial estimate, a variance of means); when
+ * demodulating it is divided by lum(a~_p)^2, a~_p the clamped albedo divisor above -- exact for grey noise, an
+ * approximation otherwise.  Other pixels (n < 2, non-finite moments) keep the spatial 7x7 estimate.  Everything after
+ * level 0 -- the 3x3 blur g, the w^2 propagation, the taps -- is the math above.  sigmaLuminance = 0 takes
+ * SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE when dMoments is set.
+ *   srtDenoiseMoments  as srtDenoise; dMoments == NULL: srtDenoise bit for bit
+ *   srtRenderDenoisedImageMoments  as srtRenderDenoisedImage with the moments render (hAccum bit-identical to
+ *                      srtRenderImage); hMoments (may be NULL) = float[W*H*4], the resolved moments plane */
+#define SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE 4.0f
+int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
+                      const void* const dPlanes[4], const void* dMoments, void* dOut, void* dRgba, void* stream);
+int srtRenderDenoisedImageMoments(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
+                                  float* hMoments, float* hDenoised, uint8_t* hRgba);
 
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the

@@ -23,6 +23,8 @@ FEATURE_PLANES = ("albedo", "normal", "position", "depth")  # names of the plane
 SRT_DENOISE_MAX_ITERATIONS, SRT_DENOISE_DEFAULT_ITERATIONS = 8, 5
 SRT_DENOISE_DEFAULT_SIGMA_LUMINANCE, SRT_DENOISE_DEFAULT_SIGMA_NORMAL, SRT_DENOISE_DEFAULT_SIGMA_DEPTH = 4.0, 16.0, 1.0
 SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL = 56
+# sample variance (srtDenoiseMoments / srtRenderDenoisedImageMoments): the luminance default with a moments plane
+SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE = 4.0
 
 f32, i32, i64, u64 = C.c_float, C.c_int32, C.c_int64, C.c_uint64
 

@@ -445,13 +445,15 @@ static int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
 
 // The render launch for these parameters: the kernel form and the instance of it, workgroup and LDS size, the path-pool
 // kernel's rings.  Every choice of kernel is made here; srtRenderTilesImpl allocates and launches what it says.
-static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p) {
+// moments: srtRenderTilesMoments -- the same form, grid, block and LDS, its MOMENTS instance (never counting or profiling).
+static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bool moments = false) {
   const DevScene& sc = ctx->scene;
   const Tunables& tun = ctx->tun;
   RenderPlan plan{};
   const bool faithful = p->traversal == SRT_TRAVERSE_FAITHFUL;
   plan.closest = p->traversal == SRT_TRAVERSE_CLOSEST;
   plan.count = p->countStats != 0;
+  plan.moments = moments;
   // FAITHFUL on a scene whose whole node array fits into a CU's LDS: the LDS-resident-tree kernel (srt_render_kernel
   // LDSTREE), one workgroup of 1024 threads per CU, walking the threaded copy of the tree (no per-lane stack).
   const size_t ldsTreeBytes = (size_t)sc.numNodes * 32 + 16 * sizeof(int32_t);  // threaded tree: no stacks
@@ -491,7 +493,7 @@ static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p) {
     plan.form = hybrid ? 4 : 3;
     plan.block = SRT_BLOCK_TREE;
     plan.lds = wfFixed + wfPerContext * plan.wfRingCap;
-    plan.profile = !plan.count && tun.wfProfile > 0;  // a counting launch takes no profile
+    plan.profile = !plan.count && !plan.moments && tun.wfProfile > 0;  // a counting or moments launch takes no profile
     // (hybrid form: the single-root instance is worth +12 to +15 % on cache-resident trees and costs 5 % on the HBM-bound
     // soups of 4 M triangles and more, where the shorter visit only crowds the memory system: profiles/r03/hybrid.txt)
     plan.single = !plan.profile && sc.numWorld == 1 && (!hybrid || sc.numNodes <= (1 << 20));
@@ -505,9 +507,10 @@ static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p) {
   return plan;
 }
 
-// aov: srtRenderAov's per-pixel records of the ray at bounce aovDepth (counting launches only), else null
+// aov: srtRenderAov's per-pixel records of the ray at bounce aovDepth (counting launches only), else null.
+// dMoments: srtRenderTilesMoments's plane (the MOMENTS instance of the planned form), else null.
 static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr,
-                              SrtAovRecord* aov = nullptr, int32_t aovDepth = 0) {
+                              SrtAovRecord* aov = nullptr, int32_t aovDepth = 0, void* dMoments = nullptr) {
   if (!ctx || !p || !dAccumTiles) return 1;
   if (checkParams(ctx, p)) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -581,40 +584,49 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
   a.primAgainMin = std::max(1, ctx->tun.primAgainMin);
   a.keepEighths = std::min(8, ctx->tun.keepEighths >= 0 ? ctx->tun.keepEighths : (closestMode ? 6 : 4));
   a.queue = ctx->dQueue.get<int32_t>();
-  a.stats = (p->countStats || ctx->tun.wfProfile > 0) ? ctx->dStats.get<unsigned long long>() : nullptr;
+  const bool moments = dMoments != nullptr;
+  // (a moments launch neither counts nor profiles: its mout / mfix take the places of aov / stats, RenderArgs)
+  unsigned long long* const stats = !moments && (p->countStats || ctx->tun.wfProfile > 0) ? ctx->dStats.get<unsigned long long>() : nullptr;
+  a.stats = stats;
   a.aov = p->countStats ? aov : nullptr;
   a.aovDepth = aovDepth;
   const size_t tilePixels = (size_t)a.numLocalTiles * SRT_TILE_PIXELS;
   a.out = static_cast<float4*>(dAccumTiles);
   a.fix = nullptr;
+  if (moments) a.mout = static_cast<float4*>(dMoments);
   a.chunkStride = 0;
   bool scratchPath = false;
+  // a moments launch sums its moments plane exactly as the beauty, on the same path: twice the slots or accumulators,
+  // the beauty's first, the moments' behind them
+  const size_t planes = moments ? 2 : 1;
   if (a.sppChunks > 1) {
     // Chunk sums are added exactly (srt_kernels.hip "Chunk sums").  Scratch path (a float4 slot per item, summed by
     // srt_sum_chunks_kernel) while this rank's slots fit the budget, else the atomic path (32 B per pixel, 0.4-1 %
     // slower); the two give the same bits, so the choice may differ from rank to rank.
-    const size_t localSlots = tilePixels * a.sppChunks * sizeof(float4);
+    const size_t localSlots = planes * tilePixels * a.sppChunks * sizeof(float4);
     // budget: the tunable, and never more than a quarter of what the device has free right now (a smaller, shared or
     // partitioned GPU takes the atomic path -- same bits -- instead of failing)
     size_t budget = (size_t)std::max(0, ctx->tun.chunkScratchMb) * 1024 * 1024, freeB = 0, totalB = 0;
     if (ctx->chunkScratch.bytes() < localSlots && hipMemGetInfo(&freeB, &totalB) == hipSuccess) budget = std::min(budget, (freeB + ctx->chunkScratch.bytes()) / 4);
     scratchPath = localSlots <= budget;
-    const size_t need = scratchPath ? localSlots : tilePixels * sizeof(SrtFixedAccum);
+    const size_t need = scratchPath ? localSlots : planes * tilePixels * sizeof(SrtFixedAccum);
     if (ctx->chunkScratch.reserve(need) != hipSuccess) {
       (void)hipGetLastError();
       if (!scratchPath) return fail(ctx, "render: cannot allocate %zu B for the pixel sums", need);
       scratchPath = false;  // the slots do not fit after all: 32 B per pixel on the atomic path
-      HIP_OK(ctx, ctx->chunkScratch.reserve(tilePixels * sizeof(SrtFixedAccum)));
+      HIP_OK(ctx, ctx->chunkScratch.reserve(planes * tilePixels * sizeof(SrtFixedAccum)));
     }
     if (scratchPath) {
       a.out = ctx->chunkScratch.get<float4>();
       a.chunkStride = (int32_t)tilePixels;
+      if (moments) a.mout = a.out + tilePixels * a.sppChunks;
     } else {
       a.fix = ctx->chunkScratch.get<SrtFixedAccum>();
-      HIP_OK(ctx, hipMemsetAsync(a.fix, 0, tilePixels * sizeof(SrtFixedAccum), stream));
+      if (moments) a.mfix = a.fix + tilePixels;
+      HIP_OK(ctx, hipMemsetAsync(a.fix, 0, planes * tilePixels * sizeof(SrtFixedAccum), stream));
     }
   }
-  const RenderPlan plan = renderPlan(ctx, p);
+  const RenderPlan plan = renderPlan(ctx, p, moments);
   if (plan.lds > 160 * 1024) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->scene.stackDepth, plan.lds);
   const RenderKernel kernel = plan.form >= 3 ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
   if (plan.lds > 64 * 1024)
@@ -647,7 +659,7 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
     a.attScratch = ctx->attScratch.get<float>();
   }
   HIP_OK(ctx, hipMemsetAsync(a.queue, 0, sizeof(int32_t) * 16 * a.numQueues, stream));
-  if (a.stats) HIP_OK(ctx, hipMemsetAsync(a.stats, 0, 96 * sizeof(unsigned long long), stream));
+  if (stats) HIP_OK(ctx, hipMemsetAsync(stats, 0, 96 * sizeof(unsigned long long), stream));
   HIP_OK(ctx, hipEventRecord(ctx->evStart, stream));
   ctx->lastPlan = plan;
   ctx->lastGrid = grid;
@@ -658,12 +670,30 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
   ctx->timed = true;
   if (a.fix) {
     rc = srt_launch_finalize(a.fix, static_cast<float4*>(dAccumTiles), (int)tilePixels, a.spp, stream);
+    if (!rc && moments) rc = srt_launch_finalize(a.mfix, static_cast<float4*>(dMoments), (int)tilePixels, a.spp, stream);
     if (rc) return fail(ctx, "finalize launch failed: %s", hipGetErrorString((hipError_t)rc));
   } else if (scratchPath) {
     rc = srt_launch_sum_chunks(a.out, static_cast<float4*>(dAccumTiles), (int)tilePixels, a.sppChunks, a.fixLimit, stream);
+    if (!rc && moments) rc = srt_launch_sum_chunks(a.mout, static_cast<float4*>(dMoments), (int)tilePixels, a.sppChunks, a.fixLimit, stream);
     if (rc) return fail(ctx, "chunk sum launch failed: %s", hipGetErrorString((hipError_t)rc));
   }
   return 0;
+}
+
+// srtRenderTilesMoments's own checks, before anything is launched
+static int checkMoments(SrtContext* ctx, const SrtRenderParams* p, const void* dMoments) {
+  if (!ctx) return 1;
+  if (!p) return fail(ctx, "render: null parameters");
+  if (!dMoments) return fail(ctx, "render: null moments buffer");
+  if (p->countStats) return fail(ctx, "render: the moments entries have no counting variant (countStats must be 0)");
+  return 0;
+}
+
+static int srtRenderTilesMomentsImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* dMomentTiles,
+                                     void* streamPtr) {
+  if (checkMoments(ctx, p, dMomentTiles)) return 1;
+  if (!dAccumTiles) return fail(ctx, "render: null accumulator buffer");
+  return srtRenderTilesImpl(ctx, p, dAccumTiles, streamPtr, nullptr, 0, dMomentTiles);
 }
 
 int srtResolveTiles(SrtContext* ctx, const SrtRenderParams* p, const void* dGathered, void* dRgba, void* dAccumImage,
@@ -704,6 +734,34 @@ int srtRenderImage(SrtContext* ctx, const SrtRenderParams* pIn, float* hAccum, u
   if (wfCheck(ctx)) return 1;
   if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy rgba");
   if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy accum");
+  return 0;
+}
+
+// srtRenderImage with the moments plane: the same render through srtRenderTilesMoments, both planes resolved
+static int srtRenderImageMomentsImpl(SrtContext* ctx, const SrtRenderParams* pIn, float* hAccum, float* hMoments, uint8_t* hRgba) {
+  if (!ctx) return 1;
+  if (!pIn) return fail(ctx, "render: null parameters");
+  if (pIn->countStats) return fail(ctx, "render: the moments entries have no counting variant (countStats must be 0)");
+  SrtRenderParams p = *pIn;
+  p.tileFirst = 0;
+  p.tileStride = 1;
+  if (checkParams(ctx, &p)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
+  const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
+  DeviceBuffer tiles, mtiles, rgba, acc, mom;
+  if (tiles.reserve(tileBytes) != hipSuccess || mtiles.reserve(tileBytes) != hipSuccess) return fail(ctx, "hipMalloc tiles");
+  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "hipMalloc rgba");
+  if (hAccum && acc.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "hipMalloc accum");
+  if (hMoments && mom.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "hipMalloc moments");
+  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr, nullptr, 0, mtiles.get())) return 1;
+  if (srtResolveTiles(ctx, &p, tiles.get(), rgba.get(), acc.get(), nullptr)) return 1;
+  if (hMoments && srtResolveTiles(ctx, &p, mtiles.get(), nullptr, mom.get(), nullptr)) return 1;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "render kernel failed: %s", hipGetErrorString(hipGetLastError()));
+  if (wfCheck(ctx)) return 1;
+  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy rgba");
+  if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy accum");
+  if (hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy moments");
   return 0;
 }
 
@@ -796,6 +854,12 @@ int srtUploadScene(SrtContext* ctx, const SrtSceneDesc* d) { SRT_GUARDED(ctx, sr
 int srtBuildBvh(const SrtSceneDesc* d, int32_t item, SrtBvhNode* out, int32_t capacity, int32_t* count, int32_t* stackDepth) { SRT_GUARDED(nullptr, srtBuildBvhImpl(d, item, out, capacity, count, stackDepth)); }
 int srtGetBvh(SrtContext* ctx, int32_t item, SrtBvhNode* nodes, int32_t capacity, int32_t* count) { SRT_GUARDED(ctx, srtGetBvhImpl(ctx, item, nodes, capacity, count)); }
 int srtRenderTiles(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr) { SRT_GUARDED(ctx, srtRenderTilesImpl(ctx, p, dAccumTiles, streamPtr)); }
+int srtRenderTilesMoments(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* dMomentTiles, void* streamPtr) {
+  SRT_GUARDED(ctx, srtRenderTilesMomentsImpl(ctx, p, dAccumTiles, dMomentTiles, streamPtr));
+}
+int srtRenderImageMoments(SrtContext* ctx, const SrtRenderParams* p, float* hAccum, float* hMoments, uint8_t* hRgba) {
+  SRT_GUARDED(ctx, srtRenderImageMomentsImpl(ctx, p, hAccum, hMoments, hRgba));
+}
 
 /* Feature pass (srt_features.hip).  Reads the scene, the camera and the tile_block tunable; writes only the caller's planes
  * and its own tile counter, so a later render sees the context as it was. */
@@ -886,7 +950,7 @@ int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t pla
 
 /* Denoiser (srt_denoise.hip).  Reads the tunable denoise_lds_step; writes only the caller's outputs and its own scratch. */
 static int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, DenoiseArgs& a,
-                              int& iterations) {
+                              int& iterations, bool moments = false) {
   if (!d) return fail(ctx, "denoise: null parameters");
   if (width <= 0 || height <= 0) return fail(ctx, "denoise: image size %dx%d must be positive", width, height);
   if ((int64_t)width * height > 0x7fffffff) return fail(ctx, "denoise: image of %dx%d pixels is too large", width, height);
@@ -895,7 +959,8 @@ static int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_
     return fail(ctx, "denoise: iterations %d not in [1, %d] (0 = %d)", d->iterations, SRT_DENOISE_MAX_ITERATIONS,
                 SRT_DENOISE_DEFAULT_ITERATIONS);
   const float sig[3] = {d->sigmaLuminance, d->sigmaNormal, d->sigmaDepth};
-  const float dflt[3] = {SRT_DENOISE_DEFAULT_SIGMA_LUMINANCE, SRT_DENOISE_DEFAULT_SIGMA_NORMAL, SRT_DENOISE_DEFAULT_SIGMA_DEPTH};
+  const float dflt[3] = {moments ? SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE : SRT_DENOISE_DEFAULT_SIGMA_LUMINANCE,
+                         SRT_DENOISE_DEFAULT_SIGMA_NORMAL, SRT_DENOISE_DEFAULT_SIGMA_DEPTH};
   float use[3];
   for (int k = 0; k < 3; ++k) {
     if (!(sig[k] >= 0.0f && sig[k] < 1e30f)) return fail(ctx, "denoise: sigma %g must be finite and >= 0 (0 = default)", sig[k]);
@@ -910,12 +975,14 @@ static int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_
   return 0;
 }
 
+// srtDenoiseMoments (moments = true): dMoments may be null, and then this is srtDenoise bit for bit
 static int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
-                          const void* const dPlanes[4], void* dOut, void* dRgba, void* streamPtr) {
+                          const void* const dPlanes[4], void* dOut, void* dRgba, void* streamPtr, bool moments = false,
+                          const void* dMoments = nullptr) {
   if (!ctx) return 1;
   DenoiseArgs a;
   int iterations = 0;
-  if (checkDenoiseParams(ctx, d, width, height, a, iterations)) return 1;
+  if (checkDenoiseParams(ctx, d, width, height, a, iterations, moments && dMoments)) return 1;
   if (!dBeauty) return fail(ctx, "denoise: null beauty buffer");
   if (!dPlanes) return fail(ctx, "denoise: null plane array");
   if (!dPlanes[1]) return fail(ctx, "denoise: the NORMAL plane is required");
@@ -936,18 +1003,22 @@ static int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t wi
   a.grad = reinterpret_cast<float2*>(s + 48 * nPix);
   a.out = static_cast<float4*>(dOut);
   a.rgba = static_cast<uint8_t*>(dRgba);
+  a.moments = moments ? static_cast<const float4*>(dMoments) : nullptr;
   const int rc = srt_launch_denoise(&a, iterations, std::max(0, ctx->tun.denoiseLdsStep), static_cast<hipStream_t>(streamPtr));
   if (rc) return fail(ctx, "denoise launch failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
 
+// moments: srtRenderDenoisedImageMoments -- the moments render, its plane resolved (into hMoments as well) and handed to
+// the denoiser
 static int srtRenderDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtDenoiseParams* d, float* hAccum,
-                                      float* hDenoised, uint8_t* hRgba) {
+                                      float* hDenoised, uint8_t* hRgba, bool moments = false, float* hMoments = nullptr) {
   if (!ctx) return 1;
   if (!pIn) return fail(ctx, "denoise: null render parameters");
   DenoiseArgs check;
   int iterations = 0;
-  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, check, iterations)) return 1;
+  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, check, iterations, moments)) return 1;
+  if (moments && pIn->countStats) return fail(ctx, "render: the moments entries have no counting variant (countStats must be 0)");
   SrtRenderParams p = *pIn;
   p.tileFirst = 0;
   p.tileStride = 1;
@@ -957,8 +1028,9 @@ static int srtRenderDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* pI
   const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
   const int32_t planes = SRT_FEATURE_NORMAL | SRT_FEATURE_DEPTH | (d->demodulate ? SRT_FEATURE_ALBEDO : 0);
   // the beauty render and its resolve exactly as srtRenderImage does them, then the feature pass of the same parameters
-  DeviceBuffer tiles, accum, featTiles[4], featImage[4], out, rgba;
+  DeviceBuffer tiles, accum, featTiles[4], featImage[4], out, rgba, mtiles, mom;
   if (tiles.reserve(tileBytes) != hipSuccess || accum.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
+  if (moments && (mtiles.reserve(tileBytes) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess)) return fail(ctx, "denoise: hipMalloc");
   if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
   if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
   void* dTiles[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -970,19 +1042,22 @@ static int srtRenderDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* pI
     dTiles[k] = featTiles[k].get();
     dPlanes[k] = featImage[k].get();
   }
-  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr)) return 1;
+  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr, nullptr, 0, moments ? mtiles.get() : nullptr)) return 1;
   if (srtResolveTiles(ctx, &p, tiles.get(), nullptr, accum.get(), nullptr)) return 1;
+  if (moments && srtResolveTiles(ctx, &p, mtiles.get(), nullptr, mom.get(), nullptr)) return 1;
   if (srtRenderFeatureTilesImpl(ctx, &p, planes, dTiles, nullptr)) return 1;
   for (int k = 0; k < 4; ++k)
     if (dTiles[k] && srtResolveTiles(ctx, &p, dTiles[k], nullptr, featImage[k].get(), nullptr)) return 1;
   if (hDenoised || hRgba) {
-    if (srtDenoiseImpl(ctx, d, p.imageWidth, p.imageHeight, accum.get(), dPlanes, out.get(), rgba.get(), nullptr)) return 1;
+    if (srtDenoiseImpl(ctx, d, p.imageWidth, p.imageHeight, accum.get(), dPlanes, out.get(), rgba.get(), nullptr, moments, mom.get())) return 1;
   }
   if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "denoise: kernel failed: %s", hipGetErrorString(hipGetLastError()));
   if (wfCheck(ctx)) return 1;
   if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy accum");
   if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy denoised");
   if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy rgba");
+  if (moments && hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ctx, "denoise: copy moments");
   return 0;
 }
 
@@ -993,6 +1068,14 @@ int srtDenoise(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_
 int srtRenderDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
                            float* hDenoised, uint8_t* hRgba) {
   SRT_GUARDED(ctx, srtRenderDenoisedImageImpl(ctx, p, d, hAccum, hDenoised, hRgba));
+}
+int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
+                      const void* const dPlanes[4], const void* dMoments, void* dOut, void* dRgba, void* stream) {
+  SRT_GUARDED(ctx, srtDenoiseImpl(ctx, d, width, height, dBeauty, dPlanes, dOut, dRgba, stream, true, dMoments));
+}
+int srtRenderDenoisedImageMoments(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
+                                  float* hMoments, float* hDenoised, uint8_t* hRgba) {
+  SRT_GUARDED(ctx, srtRenderDenoisedImageImpl(ctx, p, d, hAccum, hDenoised, hRgba, true, hMoments));
 }
 
 /* include/srt_hip_test.h: the render kernel's own traversal, ray by ray */

@@ -89,6 +89,9 @@ __device__ __forceinline__ bool geomLog2(const float4& gp, const float4& gq, flo
   return true;
 }
 
+// MOMENTS (srtDenoiseMoments): the level-0 variance of a pixel with a usable moments record is the sample variance of its
+// mean luminance instead of the spatial estimate (header: "Sample variance")
+template <bool MOMENTS>
 __global__ __launch_bounds__(DN_THREADS) void srt_denoise_prepare(const DenoiseArgs a) {
   __shared__ float4 sG[PREP_SIDE * PREP_SIDE];
   __shared__ float4 sC[PREP_SIDE * PREP_SIDE];  // {e.rgb, l}; cells outside the image: a miss that is not valid
@@ -143,6 +146,23 @@ __global__ __launch_bounds__(DN_THREADS) void srt_denoise_prepare(const DenoiseA
     v = v > 0.0f ? v : 0.0f;
   }
   const size_t i = (size_t)y * a.width + x;
+  if constexpr (MOMENTS) {
+    // v_p = max(0, S2 - S1^2 / n) / (n (n - 1)), the subtraction in double (it cancels at high sample counts); divided by
+    // lum(a~_p)^2 when demodulating
+    const float4 m = a.moments[i];
+    const float n = m.w;
+    if (n >= 2.0f && __builtin_isfinite(m.x) && __builtin_isfinite(m.y)) {
+      const double s1 = (double)m.x, nd = (double)n;
+      double d = (double)m.y - s1 * s1 / nd;
+      d = d > 0.0 ? d : 0.0;
+      v = (float)(d / (nd * (nd - 1.0)));
+      if (a.albedo) {
+        const float4 al = a.albedo[i];
+        const float la = lum(albedoDiv(al.x, al.w), albedoDiv(al.y, al.w), albedoDiv(al.z, al.w));
+        v = v / (la * la);
+      }
+    }
+  }
   a.guide[i] = gp;
   a.grad[i] = make_float2(zx, zy);
   a.col[0][i] = make_float4(cp.x, cp.y, cp.z, v);
@@ -262,7 +282,10 @@ extern "C" {
 // The prepare pass and `iterations` levels on `stream`; levels of step <= ldsMaxStep (<= 8) stage their window in LDS.
 int srt_launch_denoise(const DenoiseArgs* a, int iterations, int ldsMaxStep, hipStream_t stream) {
   const dim3 grid((a->width + DN_TILE - 1) / DN_TILE, (a->height + DN_TILE - 1) / DN_TILE), block(DN_THREADS);
-  hipLaunchKernelGGL(srt_denoise_prepare, grid, block, 0, stream, *a);
+  if (a->moments)
+    hipLaunchKernelGGL(srt_denoise_prepare<true>, grid, block, 0, stream, *a);
+  else
+    hipLaunchKernelGGL(srt_denoise_prepare<false>, grid, block, 0, stream, *a);
   hipError_t e = hipGetLastError();
   for (int lv = 0; lv < iterations && e == hipSuccess; ++lv) {
     const int step = 1 << lv, last = lv == iterations - 1;

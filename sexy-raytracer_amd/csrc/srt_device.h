@@ -141,8 +141,16 @@ struct RenderArgs {
   int32_t chunkStride;  // scratch path: numLocalTiles * 64, else 0
   SrtFixedAccum* fix;   // atomic path: [localTile][64], items add their fixed-point partial sums here (null otherwise)
   float fixLimit;       // exact chunk sums: a partial sum of this much or more counts as infinite (toFixed36)
-  unsigned long long* stats;  // 8 counters (SrtStats order) or nullptr
-  SrtAovRecord* aov;          // counting variants only: per-pixel record of the ray at bounce aovDepth (srtRenderAov)
+  // The moments instances (srtRenderTilesMoments) neither count nor profile: their two pointers share the places of the
+  // counters and the AOV records, so that the struct -- and the code of every other instance -- stays as it was.
+  union {
+    unsigned long long* stats;  // 8 counters (SrtStats order) or nullptr
+    SrtFixedAccum* mfix;        // moments instances, atomic path: the moments' exact sums, as `fix` (null otherwise)
+  };
+  union {
+    SrtAovRecord* aov;  // counting variants only: per-pixel record of the ray at bounce aovDepth (srtRenderAov)
+    float4* mout;       // moments instances: {sum l, sum l^2, 0, count} per item, laid out as `out`
+  };
   int32_t aovDepth;
   float* attScratch;          // LDS-resident-tree variant: [3 * maxBounce + 3][grid * 1024] attenuation slots in global memory
   // work-item decomposition without divisions (restart step): groups of 64 items per unit, float reciprocals of
@@ -169,6 +177,7 @@ struct RenderArgs {
 struct RenderPlan {
   int32_t form;
   bool closest, single, count, profile;
+  bool moments;   // srtRenderTilesMoments: the MOMENTS instance of the same form (never counting or profiling)
   int32_t block;  // threads per workgroup
   size_t lds;     // dynamic LDS bytes per workgroup
   int32_t wfRingCap, wfRingShift, wfRingMul3;  // forms 3 and 4: RenderArgs::wfRingCap = (wfRingMul3 ? 3 : 1) << wfRingShift
@@ -214,6 +223,7 @@ struct DenoiseArgs {
   float4* col[2];        // {e.rgb, v}; e.x NaN: not valid
   float4* out;           // may be null: rgb = denoised mean, w = the beauty count
   uint8_t* rgba;         // may be null
+  const float4* moments; // srtDenoiseMoments: {sum l, sum l^2, 0, count} per pixel (image order), or null
 };
 
 struct ResolveArgs {

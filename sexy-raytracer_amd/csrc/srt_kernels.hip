@@ -68,10 +68,15 @@ enum { M_NODE = 0, M_PRIM = 1, M_SHADE = 2, M_EXIT = 3, M_HIT = 4 };
 // the headline scene's 16-bit stacks took are free, and a visit is two ds_read_b128 and nothing else.
 // The attenuation stack lives in global memory (three coalesced stores per bounce) unless the tree leaves room
 // (ATTLDS).  Same records, same arithmetic, same decisions as the stack walk.
-template <bool CLOSEST, bool COUNT, bool SINGLE, bool LDSTREE, bool ATTLDS>
+//
+// MOMENTS (srtRenderTilesMoments): the item also keeps the float running sums of its samples' luminance and of its square
+// next to `acc`, in the same sample order, and commits them where it commits `acc` (RenderArgs::mout / mfix).  Every use
+// is under `if constexpr`: the instances without it compile to the code they had.
+template <bool CLOSEST, bool COUNT, bool SINGLE, bool LDSTREE, bool ATTLDS, bool MOMENTS = false>
 __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT_TREE_WAVES_PER_SIMD : SRT_RENDER_WAVES_PER_SIMD) void srt_render_kernel(
     const RenderArgs a) {
   static_assert(LDSTREE || !ATTLDS, "ATTLDS qualifies the LDS-resident-tree kernel");
+  static_assert(!(MOMENTS && COUNT), "the moments instances do not count");
   static_assert(!(CLOSEST && LDSTREE), "the LDS-resident tree serves the FAITHFUL traversal");
   constexpr int BLOCK = LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK;  // threads per workgroup = stride of the [slot][thread] arrays
   // "no reference": what popping the empty stack yields.  LDSTREE: the 16-bit sentinel, sign-extended.
@@ -156,6 +161,7 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
   int px = 0, py = 0;
   uint32_t pixel = 0;
   V3 acc = mk(0.0f, 0.0f, 0.0f);
+  float mom1 = 0.0f, mom2 = 0.0f;  // MOMENTS: sum of l_s and of l_s^2 over the item's samples so far
   Ray ray;
   ray.o = ray.d = mk(0.0f, 0.0f, 0.0f);
   ray.time = 0.0f;
@@ -535,6 +541,11 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
             L = mk(0.0f + L.x * ax, 0.0f + L.y * ay, 0.0f + L.z * az);
           }
           acc = acc + L;  // main.cpp:217
+          if constexpr (MOMENTS) {
+            const float l = sampleLum(L);
+            mom1 = mom1 + l;
+            mom2 = mom2 + l * l;
+          }
           s++;
         }
         if (s >= sEnd) {
@@ -544,6 +555,12 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
               commitFixed(a.fix + outIndex, acc, a.fixLimit);
             else
               a.out[outIndex] = make_float4(acc.x, acc.y, acc.z, (float)sCount);
+            if constexpr (MOMENTS) {
+              if (a.mfix)
+                commitFixed(a.mfix + outIndex, mk(mom1, mom2, 0.0f), a.fixLimit);
+              else
+                a.mout[outIndex] = make_float4(mom1, mom2, 0.0f, (float)sCount);
+            }
           }
           const unsigned long long mF = __ballot(1);
           const int leader = __ffsll((long long)mF) - 1;
@@ -630,6 +647,7 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
             s = s0;
             sEnd = valid ? s1 : s0;
             acc = mk(0.0f, 0.0f, 0.0f);
+            if constexpr (MOMENTS) mom1 = mom2 = 0.0f;
             // slot of this item: [chunk][localTile][pixel] on the scratch path (chunkStride = numLocalTiles * 64),
             // [localTile][pixel] otherwise (chunkStride = 0)
             outIndex = localTile < a.numLocalTiles ? chunk * a.chunkStride + localTile * SRT_TILE_PIXELS + ln : -1;
@@ -819,6 +837,14 @@ extern "C" {
 
 // the srt_render_kernel instance a plan of form 0-2 names (srt_api.cpp renderPlan)
 RenderKernel srt_render_kernel_for(const RenderPlan* p) {
+  if (p->moments) {  // (never counting: srtRenderTilesMoments refuses countStats)
+    if (p->form == 2)
+      return p->single ? srt_render_kernel<false, false, true, true, true, true> : srt_render_kernel<false, false, false, true, true, true>;
+    if (p->form == 1)
+      return p->single ? srt_render_kernel<false, false, true, true, false, true> : srt_render_kernel<false, false, false, true, false, true>;
+    if (p->single) return p->closest ? srt_render_kernel<true, false, true, false, false, true> : srt_render_kernel<false, false, true, false, false, true>;
+    return p->closest ? srt_render_kernel<true, false, false, false, false, true> : srt_render_kernel<false, false, false, false, false, true>;
+  }
   if (p->form == 2)
     return p->count ? srt_render_kernel<false, true, false, true, true>
                     : p->single ? srt_render_kernel<false, false, true, true, true> : srt_render_kernel<false, false, false, true, true>;

@@ -819,6 +819,8 @@ __device__ __forceinline__ float fromFixed36(long long q, uint32_t flags, int k)
   if (ninf) return -SRT_INF;
   return (float)((double)q * 0x1p-36);
 }
+// srtRenderTilesMoments: a sample's luminance, left to right in float (the library builds with -ffp-contract=off)
+__device__ __forceinline__ float sampleLum(V3 L) { return 0.2126f * L.x + 0.7152f * L.y + 0.0722f * L.z; }
 __device__ __forceinline__ void commitFixed(SrtFixedAccum* f, V3 acc, float limit) {
   const float c[3] = {acc.x, acc.y, acc.z};
   long long* const ch = &f->r;

@@ -39,7 +39,9 @@
 #define WF_CTX_BYTES 128
 // Context line (global memory, one per context id):  +0 A = ray origin, time   +16 B = ray direction (terminal radiance
 // once the path has ended), -   +32 C = RNG state (2 words), -, depth | pend << 8   +48 D = partial pixel sum, sample
-// count of the item   +64 E = output index, next sample, end sample, px | py << 16   +80 attenuations of bounces 0..3
+// count of the item   +64 E = output index, next sample, end sample, px | py << 16   +80 attenuations of bounces 0..3.
+// The moments instances keep the item's running sum of l_s in B.w and of l_s^2 in C.z (0 in the others): every store of
+// B and C carries them, so they cost no traffic of their own.
 // Control words (LDS, behind the tree): 0..15 the waves' current work queue; 16 + 2r ring r's tail (places reserved),
 // 17 + 2r its head (places claimed) -- one 8-byte read gets both --, 28 live contexts, 29 abort.  Behind them the rings
 // (16-bit slots), then per context the t (float) and the primitive (16 bits) its last walk ended at.
@@ -75,8 +77,11 @@ __device__ __forceinline__ uint32_t bufLoad1(Rsrc r, int off) { return __builtin
 // COUNT (a countStats launch): the eight SrtStats counters with srt_render_kernel's definitions -> RenderArgs::stats[0..7],
 // and with RenderArgs::aov set the srtRenderAov record of every walk at bounce aovDepth of sample sampleFirst.  A walk
 // never leaves its lane before it ends (swapStep hands over finished walks only), so its counters stay in registers.
-template <bool SINGLE, bool PROFILE, bool HYBRID, bool COUNT>
+// MOMENTS (srtRenderTilesMoments): the item's luminance moments ride in the context line (B.w, C.z, see above) and are
+// committed with its sum to RenderArgs::mout / mfix.  Every use is under `if constexpr` or a constant select.
+template <bool SINGLE, bool PROFILE, bool HYBRID, bool COUNT, bool MOMENTS = false>
 __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const RenderArgs a) {
+  static_assert(!(MOMENTS && (COUNT || PROFILE)), "the moments instances neither count nor profile");
 
   // whole tree in LDS: 16-bit references, DONE = the 16-bit "no reference" sign-extended, a link = two of them.
   // HYBRID: 32-bit references, DONE = -2^29, a link = successor << 2 | what follows a leaf's first object (srt_device.h)
@@ -310,8 +315,8 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     w = 0;
     cur = worldRef(0);
   };
-  // the next camera ray of a context (main.cpp:204-216): A, B, C of its line
-  auto cameraRayInto = [&](int at, uint32_t pxy, int s) {
+  // the next camera ray of a context (main.cpp:204-216): A, B, C of its line (MOMENTS: with the item's moments m1, m2)
+  auto cameraRayInto = [&](int at, uint32_t pxy, int s, float m1 = 0.0f, float m2 = 0.0f) {
     const int px = (int)(pxy & 0xffffu), py = (int)(pxy >> 16);
     Pcg rng;
     rng.key(seedMixed, (uint32_t)(py * a.imageWidth + px), (uint32_t)s);
@@ -322,11 +327,11 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     cameraRay(cam, u, v, rng, r);
     if constexpr (COUNT) cnt[0]++;
     bufStore4(rsPool, at, make_float4(r.o.x, r.o.y, r.o.z, r.time));
-    bufStore4(rsPool, at + 16, make_float4(r.d.x, r.d.y, r.d.z, 0.0f));
+    bufStore4(rsPool, at + 16, make_float4(r.d.x, r.d.y, r.d.z, MOMENTS ? m1 : 0.0f));
     u32x4 Cn;
     Cn.x = (uint32_t)rng.state;
     Cn.y = (uint32_t)(rng.state >> 32);
-    Cn.z = 0;
+    Cn.z = MOMENTS ? __float_as_uint(m2) : 0u;
     Cn.w = 0;  // depth 0, in flight (a miss unless a hit step says otherwise)
     __builtin_amdgcn_raw_buffer_store_b128(Cn, rsPool, at + 32, 0, 0);
   };
@@ -618,15 +623,15 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           u32x4 Cn;
           Cn.x = (uint32_t)rng.state;
           Cn.y = (uint32_t)(rng.state >> 32);
-          Cn.z = 0;
+          Cn.z = MOMENTS ? C.z : 0u;  // (B.w and C.z: the item's moments, carried over)
           if (done) {
             // the path ends here: its terminal radiance takes the (dead) direction's place
-            bufStore4(rsPool, at + 16, make_float4(terminal.x, terminal.y, terminal.z, 0.0f));
+            bufStore4(rsPool, at + 16, make_float4(terminal.x, terminal.y, terminal.z, MOMENTS ? B.w : 0.0f));
             Cn.w = (uint32_t)depth | (WF_PEND_TERMINAL << 8);
             toRestart = true;
           } else {
             bufStore4(rsPool, at, make_float4(next.o.x, next.o.y, next.o.z, next.time));
-            bufStore4(rsPool, at + 16, make_float4(next.d.x, next.d.y, next.d.z, 0.0f));
+            bufStore4(rsPool, at + 16, make_float4(next.d.x, next.d.y, next.d.z, MOMENTS ? B.w : 0.0f));
             Cn.w = (uint32_t)depth;
             toReady = true;
           }
@@ -666,11 +671,20 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           D.x += L.x;  // main.cpp:217
           D.y += L.y;
           D.z += L.z;
+          float m1 = 0.0f, m2 = 0.0f;
+          if constexpr (MOMENTS) {
+            const float l = sampleLum(L);
+            m1 = B.w + l;
+            m2 = __uint_as_float(C.z) + l * l;
+          }
           s++;
           if (s < sEnd) {
             bufStore4(rsPool, at + 48, D);
             bufStore1(rsPool, at + 68, (uint32_t)s);
-            cameraRayInto(at, E.w, s);
+            if constexpr (MOMENTS)
+              cameraRayInto(at, E.w, s, m1, m2);
+            else
+              cameraRayInto(at, E.w, s);
             toReady = true;
           } else {
             // the item is complete: its partial sum goes out (exact chunk sums: srt_path.h)
@@ -679,6 +693,12 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
                 commitFixed(a.fix + outIndex, mk(D.x, D.y, D.z), a.fixLimit);
               else
                 a.out[outIndex] = D;
+              if constexpr (MOMENTS) {
+                if (a.mfix)
+                  commitFixed(a.mfix + outIndex, mk(m1, m2, 0.0f), a.fixLimit);
+                else
+                  a.mout[outIndex] = make_float4(m1, m2, 0.0f, D.w);
+              }
             }
             toNewItem = true;
           }
@@ -775,6 +795,9 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
             } else {
               // an item with nothing to trace (a pixel outside the image, or no bounces): its zero sum is written at once
               if (outIndex >= 0 && !a.fix) a.out[outIndex] = D;
+              if constexpr (MOMENTS) {
+                if (outIndex >= 0 && !a.mfix) a.mout[outIndex] = D;  // (0, 0, 0, count) as well
+              }
               again = true;
             }
           }
@@ -911,6 +934,10 @@ extern "C" {
 // the srt_render_wf_kernel instance a plan of form 3 or 4 names (srt_api.cpp renderPlan)
 RenderKernel srt_render_wf_kernel_for(const RenderPlan* p) {
   static_assert(WF_BLOCK == SRT_BLOCK_TREE, "srt_api.cpp launches the path-pool kernel with SRT_BLOCK_TREE threads");
+  if (p->moments) {  // (never counting or profiling: srtRenderTilesMoments refuses countStats and ignores wf_profile)
+    if (p->form == 4) return p->single ? srt_render_wf_kernel<true, false, true, false, true> : srt_render_wf_kernel<false, false, true, false, true>;
+    return p->single ? srt_render_wf_kernel<true, false, false, false, true> : srt_render_wf_kernel<false, false, false, false, true>;
+  }
   if (p->form == 4)
     return p->count     ? (p->single ? srt_render_wf_kernel<true, false, true, true> : srt_render_wf_kernel<false, false, true, true>)
            : p->profile ? srt_render_wf_kernel<false, true, true, false>

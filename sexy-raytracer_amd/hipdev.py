@@ -33,6 +33,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtUploadScene", "srtSetCamera", "srtBuildBvh", "srtGetBvh", "srtGetBvhDepth", "srtNumTiles", "srtNumLocalTiles", "srtDefaultSppChunks", "srtPlanSppChunks",
            "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtScatterRays",
+           "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -69,6 +70,13 @@ lib.srtRenderFeatureImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_i
 lib.srtDenoise.argtypes = [_vp, C.POINTER(abi.SrtDenoiseParams), C.c_int32, C.c_int32, _vp, C.POINTER(_vp), _vp, _vp, _vp]
 lib.srtRenderDenoisedImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtDenoiseParams),
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
+lib.srtRenderTilesMoments.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
+lib.srtRenderImageMoments.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
+lib.srtDenoiseMoments.argtypes = [_vp, C.POINTER(abi.SrtDenoiseParams), C.c_int32, C.c_int32, _vp, C.POINTER(_vp), _vp, _vp,
+                                  _vp, _vp]
+lib.srtRenderDenoisedImageMoments.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtDenoiseParams),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                              C.POINTER(C.c_uint8)]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -226,6 +234,17 @@ class Context:
                                        rgba.ctypes.data if want_rgba else None))
         return accum, rgba
 
+    def render_image_moments(self, params, want_accum=True, want_rgba=True):
+        """render_image with the luminance moments of the samples (srtRenderImageMoments).  Returns (accum, moments, rgba):
+        accum and rgba bit-identical to render_image's; moments (H, W, 4) float32 {sum l, sum l^2, 0, count}."""
+        W, H = params.imageWidth, params.imageHeight
+        accum = np.zeros((H, W, 4), np.float32) if want_accum else None
+        moments = np.zeros((H, W, 4), np.float32)
+        rgba = np.zeros((H, W, 4), np.uint8) if want_rgba else None
+        self._check(lib.srtRenderImageMoments(self.h, C.byref(params), accum.ctypes.data if want_accum else None,
+                                              moments.ctypes.data, rgba.ctypes.data if want_rgba else None))
+        return accum, moments, rgba
+
     def render_features(self, params, planes=abi.SRT_FEATURE_ALL):
         """Feature pass (include/srt_hip.h srtRenderFeatureImage): the first hit of the beauty render's camera rays.
         Returns {plane name: (H, W, 4) float32}, xyz = the mean over the samples that counted (0 where none did), w = their
@@ -246,12 +265,18 @@ class Context:
         arr = (_vp * 4)(*[(p if p else None) for p in list(ptrs) + [None] * (4 - len(ptrs))])
         self._check(lib.srtRenderFeatureTiles(self.h, C.byref(params), int(planes), arr, stream))
 
-    def denoise(self, dparams, width, height, d_beauty_ptr, plane_ptrs, d_out_ptr=None, d_rgba_ptr=None, stream=None):
+    def denoise(self, dparams, width, height, d_beauty_ptr, plane_ptrs, d_out_ptr=None, d_rgba_ptr=None, stream=None,
+                d_moments_ptr=None):
         """Asynchronous denoiser over DEVICE image-order buffers (include/srt_hip.h srtDenoise): d_beauty_ptr = float4[W*H]
-        sums with counts, plane_ptrs[k] = the resolved feature plane of bit 1 << k (None where not given)."""
+        sums with counts, plane_ptrs[k] = the resolved feature plane of bit 1 << k (None where not given).
+        d_moments_ptr: the resolved moments plane of srtRenderTilesMoments -> srtDenoiseMoments (the sample variance)."""
         arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
-        self._check(lib.srtDenoise(self.h, C.byref(dparams), int(width), int(height), d_beauty_ptr, arr, d_out_ptr,
-                                   d_rgba_ptr, stream))
+        if d_moments_ptr is None:
+            self._check(lib.srtDenoise(self.h, C.byref(dparams), int(width), int(height), d_beauty_ptr, arr, d_out_ptr,
+                                       d_rgba_ptr, stream))
+        else:
+            self._check(lib.srtDenoiseMoments(self.h, C.byref(dparams), int(width), int(height), d_beauty_ptr, arr,
+                                              d_moments_ptr, d_out_ptr, d_rgba_ptr, stream))
 
     def render_denoised(self, params, dparams=None):
         """Beauty render, feature pass and denoiser of one frame (srtRenderDenoisedImage).  Returns (accum, denoised, rgba):
@@ -268,8 +293,27 @@ class Context:
                                                denoised.ctypes.data_as(fp), rgba.ctypes.data_as(C.POINTER(C.c_uint8))))
         return accum, denoised, rgba
 
+    def render_denoised_moments(self, params, dparams=None):
+        """render_denoised with the sample variance (srtRenderDenoisedImageMoments).  Returns (accum, moments, denoised,
+        rgba): accum bit-identical to render_image's, moments as render_image_moments's."""
+        if dparams is None:
+            dparams = abi.default_denoise_params()
+        W, H = params.imageWidth, params.imageHeight
+        accum, moments, denoised = (np.zeros((H, W, 4), np.float32) for _ in range(3))
+        rgba = np.zeros((H, W, 4), np.uint8)
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtRenderDenoisedImageMoments(self.h, C.byref(params), C.byref(dparams), accum.ctypes.data_as(fp),
+                                                      moments.ctypes.data_as(fp), denoised.ctypes.data_as(fp),
+                                                      rgba.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return accum, moments, denoised, rgba
+
     def render_tiles(self, params, d_accum_ptr, stream=None):
         self._check(lib.srtRenderTiles(self.h, C.byref(params), d_accum_ptr, stream))
+
+    def render_tiles_moments(self, params, d_accum_ptr, d_moments_ptr, stream=None):
+        """srtRenderTilesMoments: render_tiles (bit-identical accumulators) plus the moments plane, DEVICE
+        float4[numLocalTiles*64] {sum l, sum l^2, 0, count} in the tiles' layout."""
+        self._check(lib.srtRenderTilesMoments(self.h, C.byref(params), d_accum_ptr, d_moments_ptr, stream))
 
     def resolve_tiles(self, params, d_gathered_ptr, d_rgba_ptr=None, d_accum_image_ptr=None, stream=None):
         self._check(lib.srtResolveTiles(self.h, C.byref(params), d_gathered_ptr, d_rgba_ptr, d_accum_image_ptr, stream))

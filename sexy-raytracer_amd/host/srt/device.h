@@ -103,10 +103,12 @@ class hipDevice {
 
   // rtFrame plus the denoiser (include/srt_hip.h "Denoiser"): frameData (may be null) receives the frame rtFrame would
   // write, denoisedData (may be null) the denoised frame with the same quantisation; accum / denoised (float[w*h*4], may be
-  // null) the sums with counts and the denoised means.  d = null: the library's defaults.  Single-process only.
+  // null) the sums with counts and the denoised means.  d = null: the library's defaults.  sampleVariance: the denoiser's
+  // noise estimate from the render's own samples (srtRenderDenoisedImageMoments) instead of the spatial one; the frame and
+  // the sums are the same either way.  Single-process only.
   bool rtFrameDenoised(void* frameData, void* denoisedData, int w, int h, const camera& cam, const color3f& background,
                        int numSamples, int maxBounce, uint64_t seed = 1, const SrtDenoiseParams* d = nullptr,
-                       float* accum = nullptr, float* denoised = nullptr) {
+                       float* accum = nullptr, float* denoised = nullptr, bool sampleVariance = false) {
     if (!ctx) return false;
     if (ranks > 1) {
       std::cerr << "ERROR: rtFrameDenoised renders on one GPU\n";
@@ -126,7 +128,10 @@ class hipDevice {
       sums.resize((size_t)w * h * 4);
       accum = sums.data();
     }
-    if (srtRenderDenoisedImage(ctx, &p, d ? d : &defaults, accum, denoised, static_cast<uint8_t*>(denoisedData)) != 0) return error();
+    const int rc = sampleVariance ? srtRenderDenoisedImageMoments(ctx, &p, d ? d : &defaults, accum, nullptr, denoised,
+                                                                  static_cast<uint8_t*>(denoisedData))
+                                  : srtRenderDenoisedImage(ctx, &p, d ? d : &defaults, accum, denoised, static_cast<uint8_t*>(denoisedData));
+    if (rc != 0) return error();
     (void)srtLastKernelMs(ctx, &lastKernelMs);
     if (frameData) {  // the resolve's quantisation (color.h:25-41) of the sums
       uint8_t* px = static_cast<uint8_t*>(frameData);

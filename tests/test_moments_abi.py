@@ -1,0 +1,184 @@
+"""CPU-side checks of the sample moments and the denoiser's sample variance (no GPU): the four entries' ctypes prototypes
+and EXPORTS against include/srt_hip.h, the C++ host layer (hipDevice::rtFrameDenoised's opt-in, examples/main.cpp
+--sample-variance) compiling against them, and self-checks of the NumPy reference tests/denoise_moments_ref.py."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+import denoise_moments_ref as RM
+import denoise_ref as R
+
+HEADER = os.path.join(ROOT, "include", "srt_hip.h")
+HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "g++"
+ENTRIES = ("srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments")
+
+
+def _header():
+    return open(HEADER).read()
+
+
+def _syntax_check(tmp_path, name, text):
+    src = tmp_path / name
+    src.write_text(text)
+    host = os.path.join(ROOT, "sexy-raytracer_amd", "host")
+    subprocess.check_call([HIPCC, "-std=c++17", "-fsyntax-only", "-Wall", "-I" + host, "-I" + os.path.join(ROOT, "include"),
+                           "-x", "c++", str(src)])
+
+
+def test_moments_ctypes_prototypes_match_header(dev, abi):
+    ctype = {
+        "SrtContext*": C.c_void_p,
+        "const SrtRenderParams*": C.POINTER(abi.SrtRenderParams),
+        "const SrtDenoiseParams*": C.POINTER(abi.SrtDenoiseParams),
+        "int32_t": C.c_int32,
+        "const void*": C.c_void_p,
+        "const void* const[4]": C.POINTER(C.c_void_p),
+        "void*": C.c_void_p,
+        "float*": C.POINTER(C.c_float),
+        "uint8_t*": C.POINTER(C.c_uint8),
+    }
+    for name in ENTRIES:
+        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
+        assert m, name
+        params = []
+        for arg in m.group(1).split(","):
+            arg = " ".join(arg.split())
+            arr = re.search(r"\[(\d+)\]$", arg)
+            base = re.sub(r"\s*\w+(\[\d+\])?$", "", arg)
+            params.append(base.replace(" *", "*") + ("[%s]" % arr.group(1) if arr else ""))
+        want = [ctype[p] for p in params]
+        got = getattr(dev.lib, name).argtypes
+        # pointer-to-buffer arguments may be bound as void* (device pointers) or typed (host arrays)
+        assert len(got) == len(want), name
+        for g, w, p in zip(got, want, params):
+            assert g.__name__ == w.__name__ or (w is C.c_void_p and p == "void*") or (g is C.c_void_p and p.endswith("*")), (name, p, g)
+        assert name in dev.EXPORTS and hasattr(dev.lib, name)
+    m = re.search(r"#define SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE ([0-9.]+)f", _header())
+    assert m and float(m.group(1)) == abi.SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE == RM.MOMENTS_DEFAULT_SIGMA_L
+
+
+def test_context_has_the_moments_methods(dev):
+    for name in ("render_tiles_moments", "render_image_moments", "render_denoised_moments"):
+        assert callable(getattr(dev.Context, name, None)), name
+    import inspect
+    assert inspect.signature(dev.Context.denoise).parameters["d_moments_ptr"].default is None
+
+
+def test_host_layer_compiles_with_sample_variance(tmp_path, dev):
+    """hipDevice::rtFrameDenoised's sample-variance opt-in and the example's --sample-variance build against the header."""
+    host = os.path.join(ROOT, "sexy-raytracer_amd", "host")
+    subprocess.check_call(["make", "-C", host], stdout=subprocess.DEVNULL)
+    main = open(os.path.join(ROOT, "examples", "main.cpp")).read()
+    assert '"--sample-variance"' in main
+    _syntax_check(tmp_path, "moments_call.cpp", """
+#include "srt/device.h"
+#include <type_traits>
+static_assert(std::is_same<decltype(&srtRenderTilesMoments), int (*)(SrtContext*, const SrtRenderParams*, void*, void*, void*)>::value, "tiles");
+static_assert(std::is_same<decltype(&srtRenderImageMoments), int (*)(SrtContext*, const SrtRenderParams*, float*, float*, uint8_t*)>::value, "image");
+static_assert(std::is_same<decltype(&srtDenoiseMoments), int (*)(SrtContext*, const SrtDenoiseParams*, int32_t, int32_t, const void*,
+                                                                 const void* const*, const void*, void*, void*, void*)>::value, "denoise");
+static_assert(std::is_same<decltype(&srtRenderDenoisedImageMoments), int (*)(SrtContext*, const SrtRenderParams*, const SrtDenoiseParams*,
+                                                                             float*, float*, float*, uint8_t*)>::value, "denoised image");
+bool frames(hipDevice& d, const camera& cam, std::vector<uint8_t>& noisy, std::vector<uint8_t>& clean) {
+  SrtDenoiseParams p{};
+  std::vector<float> accum(16), out(16);
+  return d.rtFrameDenoised(noisy.data(), clean.data(), 2, 2, cam, color3f(0.53f, 0.81f, 0.92f), 4, 4) &&
+         d.rtFrameDenoised(nullptr, clean.data(), 2, 2, cam, color3f(0, 0, 0), 4, 4, 7, &p, accum.data(), out.data(), true);
+}
+""")
+
+
+# ---- the NumPy reference's own properties
+
+
+def _planes(H, W, rng, hit=None, spp=8):
+    hit = np.ones((H, W), bool) if hit is None else hit
+    beauty = np.zeros((H, W, 4), np.float32)
+    beauty[..., :3] = rng.uniform(0.1, 2.0, (H, W, 3)).astype(np.float32) * spp
+    beauty[..., 3] = spp
+    n = np.zeros((H, W, 4), np.float32)
+    n[..., 2] = spp
+    n[..., 0] = rng.normal(0, 0.05, (H, W)).astype(np.float32) * spp
+    n[..., 3] = np.where(hit, spp, 0)
+    n[~hit, :3] = 0
+    depth = np.zeros((H, W, 4), np.float32)
+    depth[..., 0] = np.where(hit, np.float32(3.0 * spp), 0)
+    depth[..., 3] = np.where(hit, spp, 0)
+    albedo = np.zeros((H, W, 4), np.float32)
+    albedo[..., :3] = rng.uniform(0.2, 0.9, (H, W, 3)).astype(np.float32) * spp
+    albedo[..., 3] = spp
+    moments = np.zeros((H, W, 4), np.float32)
+    l = R.lum(beauty[..., :3] / spp)
+    moments[..., 0] = l * spp
+    moments[..., 1] = (l * l) * spp * np.float32(1.3)  # a spread of the samples around the mean
+    moments[..., 3] = spp
+    return beauty, n, depth, albedo, moments
+
+
+def test_sample_variance_formula():
+    m = np.zeros((2, 3, 4), np.float32)
+    m[..., 0], m[..., 1], m[..., 3] = 6.0, 14.0, 4.0  # samples 0, 1, 2, 3: S1 = 6, S2 = 14
+    m[0, 1, 3] = 1.0
+    m[0, 2, 0] = np.nan
+    m[1, 0, 1] = 8.0  # S2 < S1^2 / n: clamped to 0
+    v = RM.sample_variance(m)
+    assert v[1, 1] == np.float32((14 - 9) / 12.0)  # (S2 - S1^2/n) / (n (n - 1)) = the variance of the mean of 0..3
+    assert np.isnan(v[0, 1]) and np.isnan(v[0, 2]) and v[1, 0] == 0
+    alb = np.zeros((2, 3, 4), np.float32)
+    alb[...] = 0.5
+    alb[..., 3] = 1
+    assert np.isclose(RM.sample_variance(m, alb, True)[1, 1], v[1, 1] / np.float32(0.25), rtol=1e-6)
+
+
+@pytest.mark.parametrize("demodulate", [False, True])
+def test_reference_keeps_a_constant_image(demodulate):
+    rng = np.random.default_rng(1)
+    beauty, n, depth, albedo, moments = _planes(23, 37, rng)
+    col = np.float32([0.7, 0.3, 1.9])
+    beauty[..., :3] = col * np.float32(8)
+    if demodulate:
+        albedo[..., :3] = np.float32([0.5, 0.25, 0.75]) * np.float32(8)
+    out, rgba = RM.denoise(beauty, n, depth, albedo, iterations=5, demodulate=demodulate, moments=moments)
+    assert (np.abs(out[..., :3] - col) <= 2 * np.spacing(col)).all()
+    assert (out[..., 3] == 8).all() and (rgba[..., 3] == 255).all()
+
+
+def test_reference_never_mixes_hits_and_misses():
+    rng = np.random.default_rng(2)
+    H, W = 32, 40
+    hit = np.zeros((H, W), bool)
+    hit[8:24, 10:30] = True
+    beauty, n, depth, _, moments = _planes(H, W, rng, hit)
+    beauty[hit, :3] = 800.0
+    beauty[~hit, :3] = rng.uniform(0.01, 0.02, ((~hit).sum(), 3)).astype(np.float32) * 8
+    moments[..., 1] *= 1e4  # very noisy everywhere: the geometric stops alone keep the two apart
+    out, _ = RM.denoise(beauty, n, depth, iterations=8, moments=moments)
+    assert out[~hit, :3].max() < 0.02 and out[hit, :3].min() > 90
+
+
+@pytest.mark.parametrize("demodulate", [False, True])
+def test_reference_with_counts_below_two_is_the_spatial_one(demodulate):
+    rng = np.random.default_rng(3)
+    beauty, n, depth, albedo, moments = _planes(20, 31, rng)
+    moments[..., 3] = rng.integers(0, 2, moments.shape[:2]).astype(np.float32)
+    for it in (1, 5):
+        want, want_rgba = R.denoise(beauty, n, depth, albedo, iterations=it, demodulate=demodulate)
+        got, got_rgba = RM.denoise(beauty, n, depth, albedo, iterations=it, demodulate=demodulate, moments=moments,
+                                   sigma_l=R.DEFAULTS["sigma_l"])
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and np.array_equal(got_rgba, want_rgba)
+        # and without any override at all
+        got2, _ = RM.denoise(beauty, n, depth, albedo, iterations=it, demodulate=demodulate)
+        assert np.array_equal(got2.view(np.uint32), want.view(np.uint32))
+
+
+def test_reference_sample_variance_changes_the_filter():
+    rng = np.random.default_rng(4)
+    beauty, n, depth, albedo, moments = _planes(24, 24, rng)
+    a, _ = R.denoise(beauty, n, depth, iterations=3)
+    b, _ = RM.denoise(beauty, n, depth, iterations=3, moments=moments)
+    assert not np.array_equal(a, b)
