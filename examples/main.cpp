@@ -4,11 +4,14 @@
 // the pixel loop is hipDevice::rtFrame instead of the CPU loops.
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
-//                  [--denoise FILE.png [--sample-variance]]
+//                  [--denoise FILE.png [--sample-variance]] [--adaptive THRESHOLD --max-spp N]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
 //                     sample variance, srtRenderDenoisedImageMoments) instead of the spatial one
+//   --adaptive THRESHOLD --max-spp N  tile-adaptive sampling (hipDevice::rtFrameAdaptive): --spp samples everywhere, then
+//                     doubling rounds for the tiles whose display-space standard error is still >= THRESHOLD (1/256 = one
+//                     display step), up to N samples a pixel
 //   SRT_DATA_DIR selects the directory of the glTF's images (default "../data/", as the reference).
 #include <chrono>
 #include <cstdlib>
@@ -74,7 +77,8 @@ static bool writeFeaturePng(const std::string& path, const std::vector<float>& p
 }
 
 int main(int argc, char** argv) {
-  int imageHeight = 720, numSamples = 5000, maxBounce = 4, chunks = 0;
+  int imageHeight = 720, numSamples = 5000, maxBounce = 4, chunks = 0, maxSpp = 0;
+  float adaptive = -1.0f;  // < 0: a uniform frame
   std::string out = "test.png", features, denoise;
   bool sampleVariance = false;
   for (int i = 1; i < argc; i += 2) {
@@ -92,6 +96,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
     else if (!strcmp(argv[i], "--features")) features = argv[i + 1];
     else if (!strcmp(argv[i], "--denoise")) denoise = argv[i + 1];
+    else if (!strcmp(argv[i], "--adaptive")) adaptive = strtof(argv[i + 1], nullptr);
+    else if (!strcmp(argv[i], "--max-spp")) maxSpp = atoi(argv[i + 1]);
   }
   const float aspect = 16.0f / 9.0f;
   const int imageWidth = static_cast<int>(imageHeight * aspect);
@@ -108,7 +114,16 @@ int main(int argc, char** argv) {
   device.sppChunks = chunks;
   auto t0 = std::chrono::steady_clock::now();
   std::vector<uint8_t> denoised;
-  if (denoise.empty()) {
+  SrtAdaptiveStats adaptiveStats{};
+  if (adaptive >= 0.0f) {
+    if (!denoise.empty()) {
+      std::cerr << "ERROR: --adaptive does not combine with --denoise\n";
+      return 1;
+    }
+    if (!device.rtFrameAdaptive(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce,
+                                maxSpp > 0 ? maxSpp : numSamples, adaptive, 1, nullptr, &adaptiveStats))
+      return 1;
+  } else if (denoise.empty()) {
     if (!device.rtFrame(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
   } else {  // one render: the noisy frame and the denoised one
     denoised.resize((size_t)4 * imageWidth * imageHeight);
@@ -136,6 +151,10 @@ int main(int argc, char** argv) {
   free(target);
   std::cerr << imageWidth << "x" << imageHeight << " @" << numSamples << " spp: " << device.numPrims << " primitives, kernel "
             << device.lastKernelMs << " ms (" << (double)imageWidth * imageHeight * numSamples / device.lastKernelMs / 1e3
-            << " Msamples/s), wall " << sec << " s -> " << out << "\nDone.\n";
+            << " Msamples/s), wall " << sec << " s -> " << out << "\n";
+  if (adaptive >= 0.0f)
+    std::cerr << "adaptive: " << adaptiveStats.rounds << " rounds, " << (double)adaptiveStats.pixelSamples / ((double)imageWidth * imageHeight)
+              << " samples per pixel on average\n";
+  std::cerr << "Done.\n";
   return 0;
 }

@@ -425,6 +425,66 @@ int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width,
 int srtRenderDenoisedImageMoments(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
                                   float* hMoments, float* hDenoised, uint8_t* hRgba);
 
+/* Adaptive sampling: more samples where the per-pixel sample moments (srtRenderTilesMoments) say the frame is still noisy.
+ * The unit is the 8x8 tile; tiles are always rendered whole (no masking of pixels inside a tile).  n_0 = p->spp, n_r = the
+ * samples every pixel of a tile still active after launch r has.
+ *   round 0   the whole frame, p->spp = n_0 >= 2 samples from p->sampleFirst: exactly srtRenderTilesMoments + srtResolveTiles,
+ *             so beauty and moments are bit-identical to srtRenderImageMoments(p)
+ *   launch r >= 1 adds b_r = min(n_{r-1}, sppMax - n_{r-1}) samples (the count doubles: a logarithmic number of launches,
+ *             each of which pays the render's tail of slow single-pixel items), samples [sampleFirst + n_{r-1},
+ *             sampleFirst + n_r) of the active tiles, n_r = n_{r-1} + b_r, with the chunk plan of a full-frame render of that
+ *             range: sppChunks = p->sppChunks > 0 ? min(p->sppChunks, b_r) : 0.  A listed tile's outputs are therefore
+ *             bit-identical to the same tile of srtRenderTilesMoments over that range, whatever the list
+ *   accumulation: after each launch its beauty and moments are added into the image-order float4 sums, one float add per
+ *             channel, w included: ((pass0 + pass1) + pass2) + ... per pixel
+ *   convergence of an in-image pixel after round r, in DOUBLE from its accumulated float moments S1 = x, S2 = y, n = w, in
+ *             this order (no multiply-add forms):
+ *               mu = S1 / n;  d = S2 - (S1 * S1) / n;  v = max(0, d) / (n * (n - 1));  limit = 4 * (thr * thr)
+ *             converged iff S1 or S2 is not finite (more samples cannot repair it), or v < limit * max(mu, 2^-16).
+ *             v is the variance of the mean; sqrt(v) / (2 sqrt(mu)) is the standard error of sqrt(mean), the gamma-2 value
+ *             the resolve quantises: thr is a threshold in display units (1/256 = one display step), 2^-16 floors mu at one
+ *             display step.  thr = +inf stops after round 0; thr = 0 refines every tile up to sppMax
+ *   active set: a tile is active in launch r+1 iff it was active in launch r (every tile is in round 0), n_r < sppMax, and at
+ *             least one in-image pixel of it is not converged after round r.  Convergence is sticky (a tile never comes
+ *             back), so every pixel of an active tile has the same count.  The list keeps the ascending blocked-curve order of
+ *             srtNumTiles (the results do not depend on it, the coherence of the rays does).  The render stops when the list
+ *             is empty or n = sppMax
+ *   RGBA:     srtResolveTiles's quantisation with the pixel's own count: sqrtf(c * (1.0f / w)), clamp to 0.999, x256
+ *             truncated, NaN -> 0, alpha 255 (bit-identical to srtResolveTiles where every count is equal)
+ *
+ * srtRenderAdaptive       DEVICE image-order float4[W*H] sums with counts: dAccumImage (beauty) and dMomentsImage
+ *                         ({S1, S2, 0, n}, srtRenderTilesMoments's plane), both required (the decisions read them);
+ *                         dRgba = DEVICE uint8[W*H*4] or NULL.  Works on `stream`, and reads the next tile count back once
+ *                         per round: it returns only after all of its work has finished.
+ * srtRenderAdaptiveImage  blocking, HOST buffers float[W*H*4], float[W*H*4], uint8[W*H*4]; each may be NULL.
+ * stats may be NULL in both.  Errors (non-zero, message in srtLastError; no kernel launched): spp < 2, sppMax < spp,
+ * sppMax > 2^24 (counts stop being exact in float), sampleFirst + sppMax beyond int32, a negative or NaN threshold,
+ * countStats != 0, tileFirst != 0 or tileStride != 1 (one GPU), NULL device buffers, and what srtRenderTiles rejects.
+ * Neither entry changes the tunables or the host generator; srtLastKernelMs / srtGetLaunchInfo describe the last render
+ * launch, as after any render.  Device memory held by the context until srtDestroy: SRT_ADAPTIVE_SCRATCH_BYTES_PER_PIXEL
+ * bytes per pixel of the largest image (one launch's beauty and moments tiles) plus 12 bytes per tile (two tile lists and
+ * the flags), besides the moments render's chunk scratch (srtRenderTilesMoments). */
+#define SRT_ADAPTIVE_MAX_ROUNDS 32
+#define SRT_ADAPTIVE_MAX_SPP (1 << 24)
+#define SRT_ADAPTIVE_SCRATCH_BYTES_PER_PIXEL 32
+typedef struct SrtAdaptiveParams {
+  int32_t sppMax;  /* samples a pixel gets at most, >= spp */
+  float threshold; /* thr: the standard error of the displayed (gamma-2) value a pixel must get below, in [0, +inf] */
+  int32_t pad[2];
+} SrtAdaptiveParams;
+typedef struct SrtAdaptiveStats {
+  int32_t rounds;                              /* launches, round 0 included */
+  int32_t pad;
+  int64_t pixelSamples;                        /* sum of w over the in-image pixels */
+  int32_t roundSpp[SRT_ADAPTIVE_MAX_ROUNDS];   /* b_r (round 0: n_0) */
+  int32_t roundTiles[SRT_ADAPTIVE_MAX_ROUNDS]; /* tiles launch r rendered (round 0: srtNumTiles) */
+  float roundMs[SRT_ADAPTIVE_MAX_ROUNDS];      /* render kernel time of launch r (srtLastKernelMs of it) */
+} SrtAdaptiveStats;
+int srtRenderAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, void* dAccumImage,
+                      void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* stream);
+int srtRenderAdaptiveImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, float* hAccum,
+                           float* hMoments, uint8_t* hRgba, SrtAdaptiveStats* stats);
+
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the
  * ranks' equal-sized tile buffers to rank 0 over RCCL (ncclGather), after which rank 0 calls

@@ -25,6 +25,8 @@ SRT_DENOISE_DEFAULT_SIGMA_LUMINANCE, SRT_DENOISE_DEFAULT_SIGMA_NORMAL, SRT_DENOI
 SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL = 56
 # sample variance (srtDenoiseMoments / srtRenderDenoisedImageMoments): the luminance default with a moments plane
 SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE = 4.0
+# adaptive sampling (srtRenderAdaptive / srtRenderAdaptiveImage)
+SRT_ADAPTIVE_MAX_ROUNDS, SRT_ADAPTIVE_MAX_SPP, SRT_ADAPTIVE_SCRATCH_BYTES_PER_PIXEL = 32, 1 << 24, 32
 
 f32, i32, i64, u64 = C.c_float, C.c_int32, C.c_int64, C.c_uint64
 
@@ -105,6 +107,15 @@ class SrtDenoiseParams(C.Structure):
                 ("sigmaDepth", f32), ("pad", i32 * 3)]
 
 
+class SrtAdaptiveParams(C.Structure):
+    _fields_ = [("sppMax", i32), ("threshold", f32), ("pad", i32 * 2)]
+
+
+class SrtAdaptiveStats(C.Structure):
+    _fields_ = [("rounds", i32), ("pad", i32), ("pixelSamples", i64), ("roundSpp", i32 * 32), ("roundTiles", i32 * 32),
+                ("roundMs", f32 * 32)]
+
+
 class SrtStats(C.Structure):
     _fields_ = [("samples", u64), ("rays", u64), ("nodeVisits", u64), ("boxPasses", u64),
                 ("triTests", u64), ("sphereTests", u64), ("shadedTriHits", u64), ("texelFetches", u64),
@@ -149,6 +160,14 @@ def default_denoise_params(iterations=0, demodulate=0, sigma_luminance=0.0, sigm
     d.iterations, d.demodulate = iterations, demodulate
     d.sigmaLuminance, d.sigmaNormal, d.sigmaDepth = sigma_luminance, sigma_normal, sigma_depth
     return d
+
+
+def default_adaptive_params(spp_max, threshold):
+    """include/srt_hip.h SrtAdaptiveParams: at most spp_max samples per pixel; threshold = the standard error of the displayed
+    (gamma-2) value a pixel must get below, in display units (1/256 = one step; +inf: round 0 only, 0: every tile to spp_max)."""
+    a = SrtAdaptiveParams()
+    a.sppMax, a.threshold = spp_max, threshold
+    return a
 
 
 def default_camera_params(aspect=16.0 / 9.0):

@@ -32,6 +32,12 @@ int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hit
 int srt_features_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU);
 int srt_launch_features(const FeatureArgs* a, int closest, int ldsTree, int grid, size_t lds, hipStream_t stream);
 int srt_launch_denoise(const DenoiseArgs* a, int iterations, int ldsMaxStep, hipStream_t stream);
+int srt_launch_adaptive_update(const uint32_t* list, int count, const float4* beautyTiles, const float4* momentTiles,
+                               float4* accum, float4* moments, int32_t* flags, int width, int height, double limit,
+                               bool accumulate, bool decide, hipStream_t stream);
+int srt_launch_adaptive_compact(const uint32_t* list, const int32_t* flags, int count, uint32_t* out, int32_t* counts,
+                                int width, int height, hipStream_t stream);
+int srt_launch_adaptive_resolve(const float4* accum, uint8_t* rgba, int n, hipStream_t stream);
 }
 
 // Diagnostic tunables of the work distribution and the wave scheduler.  Environment variables give the
@@ -77,6 +83,9 @@ struct SrtContext {
   DeviceBuffer dFeatureCounter;  // the feature pass's tile counter (its own: a render's queues are never touched)
   DeviceBuffer denoiseScratch;   // srtDenoise: guide records, depth gradients, two colour buffers (56 B per pixel)
   DeviceBuffer tileTable;   // RenderArgs::tileXY for the image size and tile order below
+  // srtRenderAdaptive: one launch's beauty and moments tiles, two tile lists (this launch's, the next one's), the per-tile
+  // flags and the compaction's {count, pixels}
+  DeviceBuffer adaptTiles, adaptList[2], adaptFlags, adaptCounts;
   int32_t tileTableKey[3] = {0, 0, 0};
   RenderPlan lastPlan{};  // the most recent render launch (srtGetLaunchInfo)
   int32_t lastGrid = 0;
@@ -446,7 +455,8 @@ static int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
 // The render launch for these parameters: the kernel form and the instance of it, workgroup and LDS size, the path-pool
 // kernel's rings.  Every choice of kernel is made here; srtRenderTilesImpl allocates and launches what it says.
 // moments: srtRenderTilesMoments -- the same form, grid, block and LDS, its MOMENTS instance (never counting or profiling).
-static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bool moments = false) {
+// listTiles >= 0: a launch over a tile list of that length (srtRenderAdaptive) instead of the rank's share of the image.
+static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bool moments = false, int32_t listTiles = -1) {
   const DevScene& sc = ctx->scene;
   const Tunables& tun = ctx->tun;
   RenderPlan plan{};
@@ -477,7 +487,7 @@ static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bo
   const size_t wfPerContext = hybrid ? 20 : 18;  // six ring slots of 16 bits, t, the primitive (16 bits; 32 in the hybrid form)
   // ring counters are 32-bit and a 3 * 2^j ring cannot take their wrap-around: such rings only while a workgroup's
   // enqueues stay far below 2^32 (about three per sample)
-  const int numLocalTiles = srtNumLocalTiles(p->imageWidth, p->imageHeight, p->tileStride);
+  const int numLocalTiles = listTiles >= 0 ? listTiles : srtNumLocalTiles(p->imageWidth, p->imageHeight, p->tileStride);
   const double enqueuesPerGroup = 4.0 * (double)numLocalTiles * SRT_TILE_PIXELS * (double)p->spp / std::max(1, ctx->prop.multiProcessorCount);
   static const struct { int cap, shift, mul3; } kRings[] = {{4096, 12, 0}, {3072, 10, 1}, {2048, 11, 0}, {1536, 9, 1}, {1024, 10, 0}};
   for (const auto& r : kRings) {
@@ -509,14 +519,22 @@ static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bo
 
 // aov: srtRenderAov's per-pixel records of the ray at bounce aovDepth (counting launches only), else null.
 // dMoments: srtRenderTilesMoments's plane (the MOMENTS instance of the planned form), else null.
+// dList: a DEVICE table of listTiles tiles (tx | ty << 16) to render instead of the rank's share of the image
+// (srtRenderAdaptive; p->tileFirst = 0, p->tileStride = 1): the output holds list position i where it holds local tile i,
+// and the queues, the grid and the chunk scratch follow the list's length.  The render kernels see an ordinary launch
+// whose tile table is the list.
 static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr,
-                              SrtAovRecord* aov = nullptr, int32_t aovDepth = 0, void* dMoments = nullptr) {
+                              SrtAovRecord* aov = nullptr, int32_t aovDepth = 0, void* dMoments = nullptr,
+                              const uint32_t* dList = nullptr, int32_t listTiles = 0) {
   if (!ctx || !p || !dAccumTiles) return 1;
   if (checkParams(ctx, p)) return 1;
+  if (dList && (listTiles < 1 || listTiles > srtNumTiles(p->imageWidth, p->imageHeight) || p->tileStride != 1))
+    return fail(ctx, "render: bad tile list of %d tiles", listTiles);
   HIP_OK(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
   RenderArgs a;
   setImageArgs(a, ctx, p);
+  if (dList) a.numTiles = a.numLocalTiles = listTiles;
   a.maxBounce = p->maxBounce;
   a.sppChunks = p->sppChunks > 0 ? p->sppChunks : srtDefaultSppChunks(p->spp);
   {
@@ -554,7 +572,7 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
   a.unitGroups = a.unitTiles * a.sppChunks;
   a.rcpUnitGroups = 1.0f / (float)a.unitGroups;
   a.rcpChunks = 1.0f / (float)a.sppChunks;
-  if (ctx->tileTableKey[0] != p->imageWidth || ctx->tileTableKey[1] != p->imageHeight || ctx->tileTableKey[2] != a.tileBlock || !ctx->tileTable.get()) {
+  if (!dList && (ctx->tileTableKey[0] != p->imageWidth || ctx->tileTableKey[1] != p->imageHeight || ctx->tileTableKey[2] != a.tileBlock || !ctx->tileTable.get())) {
     // the tile order as a table (once per image size): the kernel's restart step looks a tile up instead of dividing
     std::vector<uint32_t> table((size_t)a.numTiles);
     for (int32_t i = 0; i < a.numTiles; ++i) {
@@ -569,7 +587,7 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
     ctx->tileTableKey[1] = p->imageHeight;
     ctx->tileTableKey[2] = a.tileBlock;
   }
-  a.tileXY = ctx->tileTable.get<const uint32_t>();
+  a.tileXY = dList ? dList : ctx->tileTable.get<const uint32_t>();
   // Scheduler defaults by traversal mode (profiles/r02/scheduler_sweep.txt).  FAITHFUL on cache-resident scenes:
   // node bursts go on while half of their lanes are still at nodes, up to 64 visits, restarts at 24 waiting lanes
   // (+6 % on the headline frame against 6/8, 32, 16).  The closest-hit traversal over the 64-byte records is bound by
@@ -626,7 +644,7 @@ static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* d
       HIP_OK(ctx, hipMemsetAsync(a.fix, 0, planes * tilePixels * sizeof(SrtFixedAccum), stream));
     }
   }
-  const RenderPlan plan = renderPlan(ctx, p, moments);
+  const RenderPlan plan = renderPlan(ctx, p, moments, dList ? listTiles : -1);
   if (plan.lds > 160 * 1024) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->scene.stackDepth, plan.lds);
   const RenderKernel kernel = plan.form >= 3 ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
   if (plan.lds > 64 * 1024)
@@ -765,6 +783,135 @@ static int srtRenderImageMomentsImpl(SrtContext* ctx, const SrtRenderParams* pIn
   return 0;
 }
 
+// ---------------------------------------------------------------- adaptive sampling (include/srt_hip.h)
+
+// The schedule: b_0 = n_0, then b_r = min(n_{r-1}, sppMax - n_{r-1}) until n = sppMax.
+static int adaptiveSchedule(int32_t n0, int32_t sppMax, int32_t* spp) {
+  int rounds = 0;
+  int32_t n = n0;
+  spp[rounds++] = n0;
+  while (n < sppMax && rounds < SRT_ADAPTIVE_MAX_ROUNDS) {
+    const int32_t b = std::min(n, sppMax - n);
+    spp[rounds++] = b;
+    n += b;
+  }
+  return rounds;
+}
+
+static int checkAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, bool device,
+                         const void* dAccum, const void* dMoments) {
+  if (!ctx) return 1;
+  if (!p || !ap) return fail(ctx, "adaptive: null parameters");
+  if (device && (!dAccum || !dMoments)) return fail(ctx, "adaptive: the beauty and moments buffers are required");
+  if (p->countStats) return fail(ctx, "adaptive: no counting variant (countStats must be 0)");
+  if (p->tileFirst != 0 || p->tileStride != 1) return fail(ctx, "adaptive: renders on one GPU (tileFirst 0, tileStride 1)");
+  if (p->spp < 2) return fail(ctx, "adaptive: spp (the first round) must be >= 2");
+  if (ap->sppMax < p->spp || ap->sppMax > SRT_ADAPTIVE_MAX_SPP) return fail(ctx, "adaptive: sppMax must be in [spp, 2^24]");
+  if (p->sampleFirst < 0 || (int64_t)p->sampleFirst + ap->sppMax > 0x7fffffff) return fail(ctx, "adaptive: bad sample range");
+  if (!(ap->threshold >= 0.0f)) return fail(ctx, "adaptive: threshold must be >= 0 (+inf allowed)");
+  if (checkParams(ctx, p)) return 1;
+  // every launch's chunk plan, before anything is launched
+  int32_t spp[SRT_ADAPTIVE_MAX_ROUNDS];
+  const int rounds = adaptiveSchedule(p->spp, ap->sppMax, spp);
+  for (int r = 0; r < rounds; ++r) {
+    const int32_t chunks = p->sppChunks > 0 ? std::min(p->sppChunks, spp[r]) : 0;
+    if (srtPlanSppChunks(p->imageWidth, p->imageHeight, spp[r], chunks) < 1)
+      return fail(ctx, "adaptive: sppChunks %d x %d tiles exceeds 2^31 work items", chunks, srtNumTiles(p->imageWidth, p->imageHeight));
+  }
+  return 0;
+}
+
+static int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap, void* dAccumImage,
+                                 void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* streamPtr) {
+  if (checkAdaptive(ctx, pIn, ap, true, dAccumImage, dMomentsImage)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+  const SrtRenderParams p0 = *pIn;
+  const int W = p0.imageWidth, H = p0.imageHeight;
+  const int32_t numTiles = srtNumTiles(W, H);
+  const size_t tilePixels = (size_t)numTiles * SRT_TILE_PIXELS;
+  HIP_OK(ctx, ctx->adaptTiles.reserve(2 * tilePixels * sizeof(float4)));
+  for (auto& l : ctx->adaptList) HIP_OK(ctx, l.reserve((size_t)numTiles * sizeof(uint32_t)));
+  HIP_OK(ctx, ctx->adaptFlags.reserve((size_t)numTiles * sizeof(int32_t)));
+  HIP_OK(ctx, ctx->adaptCounts.reserve(2 * sizeof(int32_t)));
+  float4* const beautyTiles = ctx->adaptTiles.get<float4>();
+  float4* const momentTiles = beautyTiles + tilePixels;
+  float4* const accum = static_cast<float4*>(dAccumImage);
+  float4* const moments = static_cast<float4*>(dMomentsImage);
+  const double thr = (double)ap->threshold;
+  const double limit = 4.0 * (thr * thr);
+  SrtAdaptiveStats st;
+  memset(&st, 0, sizeof st);
+  int32_t spp[SRT_ADAPTIVE_MAX_ROUNDS];
+  const int plannedRounds = adaptiveSchedule(p0.spp, ap->sppMax, spp);
+  // round 0: the whole frame, srtRenderImageMoments's launch and resolves
+  const uint32_t* list = nullptr;  // this launch's tiles (round 0: the image's own tile table)
+  int32_t listTiles = numTiles, listPixels = W * H;
+  int32_t n = 0;
+  for (int r = 0; r < plannedRounds; ++r) {
+    SrtRenderParams q = p0;
+    q.spp = spp[r];
+    q.sampleFirst = p0.sampleFirst + n;
+    q.sppChunks = p0.sppChunks > 0 ? std::min(p0.sppChunks, spp[r]) : 0;
+    if (srtRenderTilesImpl(ctx, &q, beautyTiles, stream, nullptr, 0, momentTiles, list, list ? listTiles : 0)) return 1;
+    n += spp[r];
+    st.roundSpp[r] = spp[r];
+    st.roundTiles[r] = listTiles;
+    st.pixelSamples += (int64_t)listPixels * spp[r];
+    st.rounds = r + 1;
+    int rc = 0;
+    const bool decide = n < ap->sppMax;
+    if (r == 0) {
+      if (srtResolveTiles(ctx, &q, beautyTiles, nullptr, accum, stream) || srtResolveTiles(ctx, &q, momentTiles, nullptr, moments, stream))
+        return 1;
+      list = ctx->tileTable.get<const uint32_t>();  // built for this size by the launch above
+      if (decide)
+        rc = srt_launch_adaptive_update(list, listTiles, nullptr, nullptr, accum, moments, ctx->adaptFlags.get<int32_t>(), W, H,
+                                        limit, false, true, stream);
+    } else {
+      rc = srt_launch_adaptive_update(list, listTiles, beautyTiles, momentTiles, accum, moments, ctx->adaptFlags.get<int32_t>(),
+                                      W, H, limit, true, decide, stream);
+    }
+    uint32_t* const next = ctx->adaptList[r & 1].get<uint32_t>();
+    int32_t counts[2] = {0, 0};
+    if (!rc && decide)
+      rc = srt_launch_adaptive_compact(list, ctx->adaptFlags.get<const int32_t>(), listTiles, next, ctx->adaptCounts.get<int32_t>(),
+                                       W, H, stream);
+    if (rc) return fail(ctx, "adaptive launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (decide) HIP_OK(ctx, hipMemcpyAsync(counts, ctx->adaptCounts.get(), sizeof counts, hipMemcpyDeviceToHost, stream));
+    if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "render kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    if (wfCheck(ctx)) return 1;
+    HIP_OK(ctx, hipEventElapsedTime(&st.roundMs[r], ctx->evStart, ctx->evStop));
+    if (!decide || counts[0] == 0) break;
+    list = next;
+    listTiles = counts[0];
+    listPixels = counts[1];
+  }
+  if (dRgba) {
+    const int rc = srt_launch_adaptive_resolve(accum, static_cast<uint8_t*>(dRgba), W * H, stream);
+    if (rc) return fail(ctx, "adaptive resolve launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "adaptive resolve failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  if (stats) *stats = st;
+  return 0;
+}
+
+static int srtRenderAdaptiveImageImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, float* hAccum,
+                                      float* hMoments, uint8_t* hRgba, SrtAdaptiveStats* stats) {
+  if (checkAdaptive(ctx, p, ap, false, nullptr, nullptr)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const size_t nPix = (size_t)p->imageWidth * p->imageHeight;
+  DeviceBuffer acc, mom, rgba;
+  if (acc.reserve(nPix * sizeof(float4)) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess)
+    return fail(ctx, "hipMalloc accum");
+  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "hipMalloc rgba");
+  if (srtRenderAdaptiveImpl(ctx, p, ap, acc.get(), mom.get(), rgba.get(), stats, nullptr)) return 1;
+  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy rgba");
+  if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy accum");
+  if (hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy moments");
+  return 0;
+}
+
 int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, int32_t traversal) {
   if (!ctx || !rays || !hits || n < 0) return 1;
   if (!ctx->haveScene) return fail(ctx, "trace: no scene uploaded");
@@ -859,6 +1006,14 @@ int srtRenderTilesMoments(SrtContext* ctx, const SrtRenderParams* p, void* dAccu
 }
 int srtRenderImageMoments(SrtContext* ctx, const SrtRenderParams* p, float* hAccum, float* hMoments, uint8_t* hRgba) {
   SRT_GUARDED(ctx, srtRenderImageMomentsImpl(ctx, p, hAccum, hMoments, hRgba));
+}
+int srtRenderAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, void* dAccumImage, void* dMomentsImage,
+                      void* dRgba, SrtAdaptiveStats* stats, void* stream) {
+  SRT_GUARDED(ctx, srtRenderAdaptiveImpl(ctx, p, ap, dAccumImage, dMomentsImage, dRgba, stats, stream));
+}
+int srtRenderAdaptiveImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, float* hAccum, float* hMoments,
+                           uint8_t* hRgba, SrtAdaptiveStats* stats) {
+  SRT_GUARDED(ctx, srtRenderAdaptiveImageImpl(ctx, p, ap, hAccum, hMoments, hRgba, stats));
 }
 
 /* Feature pass (srt_features.hip).  Reads the scene, the camera and the tile_block tunable; writes only the caller's planes

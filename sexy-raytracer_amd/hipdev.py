@@ -34,6 +34,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtScatterRays",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
+           "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -77,6 +78,11 @@ lib.srtDenoiseMoments.argtypes = [_vp, C.POINTER(abi.SrtDenoiseParams), C.c_int3
 lib.srtRenderDenoisedImageMoments.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtDenoiseParams),
                                               C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                               C.POINTER(C.c_uint8)]
+lib.srtRenderAdaptive.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtAdaptiveParams), _vp, _vp, _vp,
+                                  C.POINTER(abi.SrtAdaptiveStats), _vp]
+lib.srtRenderAdaptiveImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtAdaptiveParams),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8),
+                                       C.POINTER(abi.SrtAdaptiveStats)]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -244,6 +250,37 @@ class Context:
         self._check(lib.srtRenderImageMoments(self.h, C.byref(params), accum.ctypes.data if want_accum else None,
                                               moments.ctypes.data, rgba.ctypes.data if want_rgba else None))
         return accum, moments, rgba
+
+    @staticmethod
+    def _adaptive_stats(st):
+        r = st.rounds
+        return {"rounds": r, "pixelSamples": st.pixelSamples, "roundSpp": list(st.roundSpp[:r]),
+                "roundTiles": list(st.roundTiles[:r]), "roundMs": list(st.roundMs[:r])}
+
+    def render_adaptive(self, params, aparams, want_accum=True, want_moments=True, want_rgba=True):
+        """Tile-adaptive sampling (srtRenderAdaptiveImage): round 0 renders params.spp samples everywhere, later rounds double
+        the samples of the tiles whose pixels have not converged (include/srt_hip.h "Adaptive sampling").  Returns (accum,
+        moments, rgba, stats): (H, W, 4) float32 sums with per-pixel counts w, the moments {sum l, sum l^2, 0, w}, uint8 RGBA
+        (each None when not wanted), and a dict of SrtAdaptiveStats with the per-round lists cut to `rounds`."""
+        W, H = params.imageWidth, params.imageHeight
+        accum = np.zeros((H, W, 4), np.float32) if want_accum else None
+        moments = np.zeros((H, W, 4), np.float32) if want_moments else None
+        rgba = np.zeros((H, W, 4), np.uint8) if want_rgba else None
+        st = abi.SrtAdaptiveStats()
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtRenderAdaptiveImage(self.h, C.byref(params), C.byref(aparams),
+                                               accum.ctypes.data_as(fp) if want_accum else None,
+                                               moments.ctypes.data_as(fp) if want_moments else None,
+                                               rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None, C.byref(st)))
+        return accum, moments, rgba, self._adaptive_stats(st)
+
+    def render_adaptive_device(self, params, aparams, d_accum_ptr, d_moments_ptr, d_rgba_ptr=None, stream=None):
+        """srtRenderAdaptive into DEVICE image-order buffers (float4[W*H] beauty and moments, both required; uint8[W*H*4]
+        RGBA or None).  Returns the stats dict; the work has finished when it returns."""
+        st = abi.SrtAdaptiveStats()
+        self._check(lib.srtRenderAdaptive(self.h, C.byref(params), C.byref(aparams), d_accum_ptr, d_moments_ptr, d_rgba_ptr,
+                                          C.byref(st), stream))
+        return self._adaptive_stats(st)
 
     def render_features(self, params, planes=abi.SRT_FEATURE_ALL):
         """Feature pass (include/srt_hip.h srtRenderFeatureImage): the first hit of the beauty render's camera rays.

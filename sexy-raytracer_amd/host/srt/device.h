@@ -6,6 +6,8 @@
 //                                           the first hit of the camera rays rtFrame traces (a denoiser's guides)
 //   rtFrameDenoised(target, denoised, ...)  rtFrame's frame, its feature pass and the library's a-trous denoiser: the
 //                                           noisy and the denoised RGBA8 frames of one render
+//   rtFrameAdaptive(target, ..., sppMax, thr)  tile-adaptive sampling: numSamples everywhere, then more samples, doubling,
+//                                           for the tiles that have not converged (include/srt_hip.h "Adaptive sampling")
 //   terminate()
 //   uniqueId / initRanks                    multi-GPU: one process per GPU; rtFrame then renders this rank's
 //                                           tiles, the library gathers them with ONE ncclGather and rank 0's
@@ -70,6 +72,34 @@ class hipDevice {
     } else if (srtRenderImage(ctx, &p, accum, static_cast<uint8_t*>(frameData)) != 0) {
       return error();
     }
+    (void)srtLastKernelMs(ctx, &lastKernelMs);
+    return true;
+  }
+
+  // Tile-adaptive sampling (include/srt_hip.h "Adaptive sampling"): numSamples (>= 2) samples everywhere, then doubling rounds
+  // for the tiles not yet converged to the display-space standard error `threshold`, up to sppMax samples a pixel.
+  // frameData = uint8[w*h*4] (may be null), accum = float[w*h*4] sums with per-pixel counts (may be null), stats may be null.
+  // Single-process only.
+  bool rtFrameAdaptive(void* frameData, int w, int h, const camera& cam, const color3f& background, int numSamples,
+                       int maxBounce, int sppMax, float threshold, uint64_t seed = 1, float* accum = nullptr,
+                       SrtAdaptiveStats* stats = nullptr) {
+    if (!ctx) return false;
+    if (ranks > 1) {
+      std::cerr << "ERROR: rtFrameAdaptive renders on one GPU\n";
+      return false;
+    }
+    if (srtSetCamera(ctx, &cam.data()) != 0) return error();
+    SrtRenderParams p{};
+    p.imageWidth = w; p.imageHeight = h; p.spp = numSamples; p.maxBounce = maxBounce; p.seed = seed;
+    for (int i = 0; i < 3; ++i) p.background[i] = background(i);
+    p.tMin = 0.001f;  // main.cpp:39
+    p.traversal = SRT_TRAVERSE_FAITHFUL;
+    p.tileFirst = 0; p.tileStride = 1;
+    p.sppChunks = sppChunks;
+    SrtAdaptiveParams a{};
+    a.sppMax = sppMax;
+    a.threshold = threshold;
+    if (srtRenderAdaptiveImage(ctx, &p, &a, accum, nullptr, static_cast<uint8_t*>(frameData), stats) != 0) return error();
     (void)srtLastKernelMs(ctx, &lastKernelMs);
     return true;
   }
