@@ -80,10 +80,12 @@ int main(int argc, char** argv) {
   int imageHeight = 720, numSamples = 5000, maxBounce = 4, chunks = 0, maxSpp = 0;
   float adaptive = -1.0f;  // < 0: a uniform frame
   std::string out = "test.png", features, denoise;
-  bool sampleVariance = false;
+  bool sampleVariance = false, temporal = false;
+  int frames = 0;        // > 0: a sequence, NAME_%03d.png
+  float orbit = 0.0f;    // degrees the eye turns about the lookAt point's vertical axis over the sequence
   for (int i = 1; i < argc; i += 2) {
-    if (!strcmp(argv[i], "--sample-variance")) {  // the one flag without a value
-      sampleVariance = true;
+    if (!strcmp(argv[i], "--sample-variance") || !strcmp(argv[i], "--temporal")) {  // the flags without a value
+      (argv[i][2] == 't' ? temporal : sampleVariance) = true;
       --i;
       continue;
     }
@@ -98,6 +100,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--denoise")) denoise = argv[i + 1];
     else if (!strcmp(argv[i], "--adaptive")) adaptive = strtof(argv[i + 1], nullptr);
     else if (!strcmp(argv[i], "--max-spp")) maxSpp = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--frames")) frames = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--orbit")) orbit = strtof(argv[i + 1], nullptr);
   }
   const float aspect = 16.0f / 9.0f;
   const int imageWidth = static_cast<int>(imageHeight * aspect);
@@ -112,6 +116,41 @@ int main(int argc, char** argv) {
   hipDevice device;
   if (!device.init(imageWidth, imageHeight, world)) return 1;
   device.sppChunks = chunks;
+  if (frames > 0) {
+    // A camera move: frame k looks from the eye turned by orbit * k / (frames - 1) degrees about the vertical axis through
+    // the lookAt point and draws samples [k * spp, (k + 1) * spp).  --temporal accumulates each frame onto the reprojected
+    // history of the one before it (rtFrameTemporal); without it every frame is denoised from its own samples alone.
+    const vec3f eye(0.0f, 3.0f, 5.0f), lookAt(0, 2.5f, 0);
+    const float dx = eye(0) - lookAt(0), dz = eye(2) - lookAt(2);
+    const std::string stem = out.size() > 4 && out.substr(out.size() - 4) == ".png" ? out.substr(0, out.size() - 4) : out;
+    std::vector<uint8_t> frame((size_t)4 * imageWidth * imageHeight);
+    for (int k = 0; k < frames; ++k) {
+      const double angle = frames > 1 ? (double)orbit * k / (frames - 1) * (3.14159265358979323846 / 180.0) : 0.0;
+      const float c = (float)std::cos(angle), s = (float)std::sin(angle);
+      const vec3f eyeK(lookAt(0) + (c * dx + s * dz), eye(1), lookAt(2) + (c * dz - s * dx));
+      camera cam(eyeK, lookAt, vec3f(0, 1.0f, 0), 70.0f, aspect, 0.1f, 10.0f, 0, 1.0f);
+      if (temporal) {
+        if (!device.rtFrameTemporal(frame.data(), imageWidth, imageHeight, cam, background, numSamples, maxBounce, k * numSamples))
+          return 1;
+      } else {
+        device.sampleFirst = k * numSamples;
+        if (!device.rtFrameDenoised(nullptr, frame.data(), imageWidth, imageHeight, cam, background, numSamples, maxBounce, 1,
+                                    nullptr, nullptr, nullptr, true))
+          return 1;
+      }
+      char name[32];
+      snprintf(name, sizeof name, "_%03d.png", k);
+      if (!stbi_write_png((stem + name).c_str(), imageWidth, imageHeight, 4, frame.data(), 4 * imageWidth)) {
+        std::cerr << "ERROR: could not write " << stem << name << "\n";
+        return 1;
+      }
+    }
+    device.terminate();
+    free(target);
+    std::cerr << frames << " frames of " << imageWidth << "x" << imageHeight << " @" << numSamples << " spp, "
+              << (temporal ? "temporal accumulation" : "frame by frame") << " -> " << stem << "_000.png ...\nDone.\n";
+    return 0;
+  }
   auto t0 = std::chrono::steady_clock::now();
   std::vector<uint8_t> denoised;
   SrtAdaptiveStats adaptiveStats{};

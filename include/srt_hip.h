@@ -348,7 +348,8 @@ int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t pla
 
 /* Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) in the spatial form of SVGF, guided by the
  * feature planes' normals and depths, luminance-stopped by a variance estimate carried from level to level, optionally
- * demodulated by albedo.  Single frames: there is no temporal part.  fp32 throughout.
+ * demodulated by albedo.  It works on one frame; the temporal part is srtTemporalAccumulate below, which feeds it buffers in
+ * the same formats.  fp32 throughout.
  *
  * Inputs, every buffer image-order float4[W*H] as srtResolveTiles(..., dAccumImage) writes it: dBeauty = rgb sums, w = the
  * sample count; dPlanes[k] = the resolved feature plane of bit 1 << k (sums with counts).  NORMAL and DEPTH are required,
@@ -484,6 +485,111 @@ int srtRenderAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdapti
                       void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* stream);
 int srtRenderAdaptiveImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, float* hAccum,
                            float* hMoments, uint8_t* hRgba, SrtAdaptiveStats* stats);
+
+/* Temporal accumulation: the temporal half of SVGF (Schied et al. 2017) in front of the denoiser above.  The previous
+ * frame's accumulated radiance and luminance moments are reprojected onto the current camera, kept where the surface is
+ * the same, and the current frame's samples are added.  The scene is static; only the camera moves.  fp32 throughout, and
+ * only + - * / sqrt, rint, floor and comparisons: the kernel agrees with a NumPy float32 evaluation of this text in this
+ * operation order bit for bit (tests/temporal_ref.py), decisions included.
+ *
+ * Buffers, all DEVICE, image order, float4[W*H] unless said otherwise, sums with counts as srtResolveTiles(...,
+ * dAccumImage) writes them: dBeauty (rgb sums, w = n); dMoments ({S1, S2, 0, n}, may be NULL); dPlanes[k] = the resolved
+ * feature plane of bit 1 << k: NORMAL, POSITION and DEPTH required, ALBEDO only when demodulating.
+ * A history is SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL bytes per pixel, three float4 planes one after the other:
+ *   plane 0  {r, g, b, count}   accumulated radiance sums (divided by a~ when demodulating); count 0 = empty
+ *   plane 1  {nx, ny, nz, S1}   the surface normal the pixel had when it was written; nx = NaN marks a miss
+ *   plane 2  {Px, Py, Pz, S2}   the POSITION mean it had (0 for a miss)
+ * It is caller-owned and belongs to (image size, demodulate, the scene, the camera it was written with).
+ *
+ * Per pixel p = (x, y), i = y W + x, with cur = the current camera, prev = the camera of the history:
+ *   means       m(s, c) = s / c, 0 where c == 0.  p is a HIT if the NORMAL count is > 0.  n_p = the NORMAL mean divided by
+ *               its length len = sqrt(nx nx + ny ny + nz nz) when 0 < len < inf, else 0.  tbar = m(DEPTH.x, DEPTH.w).
+ *               Q_p = the POSITION mean (its own count).  a~ = max(m(ALBEDO), 1e-3) per channel and la = 0.2126 a~.r +
+ *               0.7152 a~.g + 0.0722 a~.b when demodulating (the divisor of srtDenoiseMoments), else 1.
+ *               p is USABLE if n > 0 and n, r, g, b (and S1, S2 when dMoments is given) are all finite
+ *   ray         s_c = (x + 0.5) / (W - 1), t_c = ((H - y) + 0.5) / (H - 1): the render's own pixel mapping at the mean of
+ *               its jitter.  d = ((cur.lleft + s_c cur.horizontal) + t_c cur.vertical) - cur.origin per component,
+ *               dlen = sqrt(d.d) (dot products are (x x + y y) + z z everywhere)
+ *   point       a hit: P = cur.origin + tbar d, v = P - prev.origin.  Depth is in units of d, and lens-offset rays meet
+ *               planes parallel to the focus plane at the same parameter, so P is the centre of the pixel's footprint
+ *               whatever the aperture, and it projects back onto the pixel centre when the camera has not moved (the
+ *               POSITION mean, a mean over jittered samples, does not).  A miss: v = d (the sky has no parallax)
+ *   projection  through prev's lens centre onto its focus plane: e = prev.origin - prev.lleft, f = e.w (the focus
+ *               distance), z = -(v.w) with w = prev.w; z > 0 or there is no history (behind the camera); k = f / z;
+ *               g = e + k v; s = (g.H) / (H.H), t = (g.V) / (V.V), H = prev.horizontal, V = prev.vertical;
+ *               xf = s (W - 1) - 0.5, yf = (H + 0.5) - t (H - 1).  No history unless -1 < xf < W and -1 < yf < H
+ *   snap        xr = rint(xf), yr = rint(yf) (ties to even).  If |xf - xr| <= SRT_TEMPORAL_SNAP and |yf - yr| <=
+ *               SRT_TEMPORAL_SNAP there is one tap (xr, yr) of weight 1
+ *   taps        otherwise x0 = floor(xf), fx = xf - x0 (y alike) and the taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1),
+ *               in this order, with weights (1-fx)(1-fy), fx (1-fy), (1-fx) fy, fx fy.  A tap q is ACCEPTED iff its weight
+ *               is > 0, it lies inside the image, its history count c is > 0 and finite, it is a hit iff p is, and for
+ *               hits  n_p . n_q >= normalCos  and  |(Q_q - P) . n_p| <= (planeDist tbar) dlen  (n_q, Q_q from the history).
+ *               Rejected taps are never read into a sum: a NaN in one cannot reach the output
+ *   history     wsum = the accepted weights added in tap order; each accepted tap adds (w / wsum) times its r, g, b,
+ *               count, S1, S2 to the reprojected history h, in tap order from 0.  If h.count > maxHistory: r, g, b, S1,
+ *               S2 are multiplied by maxHistory / h.count and h.count = maxHistory (an exponential moving average with
+ *               weight n / (n + maxHistory) for the new frame)
+ *   output      no accepted tap: dBeautyOut = the current pixel, dMomentsOut = {S1, S2, 0, n}, bit for bit, and the new
+ *               history is the current pixel (a disocclusion starts over).  Otherwise, for a USABLE pixel,
+ *                 dBeautyOut  = {cur.rgb + a~ h.rgb, n + h.count}      dMomentsOut = {S1 + la h.S1, S2 + (la la) h.S2, 0, that count}
+ *                 new history = {h.rgb + cur.rgb / a~, h.count + n}, S1' = h.S1 + S1 / la, S2' = h.S2 + S2 / (la la)
+ *               one float add per channel, w included -- srtRenderAdaptive's rule; the multiplications and divisions are
+ *               skipped when not demodulating, so K frames from one camera are the running sum ((f0 + f1) + f2) + ...
+ *               The current frame's own sums never pass through the division.  Demodulation keeps bilinear history taps
+ *               from blurring textures; like srtDenoiseMoments's divisor it is exact for grey noise only.
+ *               A pixel that is not USABLE (the r = 0 ground's NaN samples, overflowed chunk sums) stays what it is in
+ *               dBeautyOut and dMomentsOut, for the denoiser to fill, and its new history is h alone, or empty.
+ *               The new history's planes 1 and 2 always describe the current frame's surface.
+ *               dMoments == NULL: S1 = S2 = 0 everywhere (dMomentsOut's x and y are 0)
+ * A camera that has not moved (cur and prev agree bit for bit in origin, lleft, horizontal, vertical and w): every pixel
+ * is its own history -- the one tap (x, y) of weight 1, accepted iff its count is > 0 and finite, WITHOUT the hit, normal
+ * and plane tests.  The footprint is the same, so those tests could only reject on the sampling noise of a few-sample
+ * feature mean (a silhouette pixel that is a hit in one frame and a miss in the next), and K frames are the running sum on
+ * every pixel.
+ * dHistoryIn == NULL (the first frame): every pixel takes the "no accepted tap" branch; prev is not read.
+ *
+ * srtTemporalAccumulate   asynchronous on `stream`, one kernel.  dBeautyOut, dMomentsOut may be NULL (not both);
+ *                 dHistoryOut is required and must not be dHistoryIn; outputs must not alias inputs.
+ * srtRenderTemporalFrame  blocking, HOST buffers, each may be NULL: the moments render and the feature pass (all four
+ *                 planes) of `p` with the camera currently set, srtTemporalAccumulate against the history and camera the
+ *                 context kept from the previous call, srtDenoiseMoments (parameters d) on the accumulated buffers, then
+ *                 the context keeps the new history and the camera.  hAccum = THIS frame's sums, bit-identical to
+ *                 srtRenderImage(p); hDenoised / hRgba as srtRenderDenoisedImageMoments.  The first frame after a reset
+ *                 equals srtRenderDenoisedImageMoments bit for bit.  Callers advance p->sampleFirst by p->spp per frame.
+ *                 The history is dropped by srtTemporalReset, by srtUploadScene, and when the image size or
+ *                 t->demodulate differs from the previous call's.  Device memory held by the context until srtDestroy
+ *                 or srtTemporalReset: two histories, 2 x SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL bytes per pixel.
+ * Errors (non-zero, message in srtLastError, nothing launched, outputs untouched): a missing NORMAL, POSITION or DEPTH
+ * plane, demodulate without ALBEDO, a size <= 0 or below 2 x 2, dHistoryOut NULL or == dHistoryIn, both outputs NULL,
+ * a negative or NaN parameter, normalCos > 1.  Neither entry changes the tunables, the chunk scratch, srtLastKernelMs,
+ * srtGetLaunchInfo or the host generator beyond what the render of the blocking entry does.
+ *
+ * SRT_TEMPORAL_SNAP: the float32 round trip pixel -> P -> the same camera -> (xf, yf) of the text above, over every
+ * pixel of 1920 x 1080 for the default camera and its orbit positions at 7, 20 and 45 degrees, depths 1e-2 .. 1e4, is off
+ * by at most 3.10e-3 px (at depth 1e-2; 8.5e-4 px from depth 0.1 on): x 4 = 1.24e-2, rounded up to a power of two
+ * (tests/test_temporal_abi.py repeats the measurement). */
+#define SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL 48
+#define SRT_TEMPORAL_SNAP 0.015625f /* 2^-6 px */
+#define SRT_TEMPORAL_DEFAULT_NORMAL_COS 0.5f
+#define SRT_TEMPORAL_DEFAULT_PLANE_DIST 0.02f
+#define SRT_TEMPORAL_DEFAULT_MAX_HISTORY 64.0f
+typedef struct SrtTemporalParams { /* a field of 0 takes its default */
+  float normalCos;    /* taps need n_p . n_q >= this; in (0, 1]; default 0.5 (the sweep) */
+  float planeDist;    /* taps need |(Q_q - P) . n_p| <= this x the pixel's distance tbar |d|; default 0.02 */
+  float maxHistory;   /* samples of history kept at most, default 64; +inf = no cap (a plain running sum) */
+  int32_t demodulate; /* non-zero: the history carries radiance / albedo (needs the ALBEDO plane) */
+  int32_t pad[4];
+} SrtTemporalParams;
+typedef struct SrtTemporalStats {
+  int64_t historyPixels;   /* pixels whose output count exceeds this frame's (history accepted) */
+  double meanHistoryCount; /* mean over all pixels of the new history's count (samples behind a pixel) */
+} SrtTemporalStats;
+int srtTemporalAccumulate(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
+                          const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
+                          const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut, void* stream);
+int srtRenderTemporalFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, const SrtTemporalParams* t,
+                           float* hAccum, float* hDenoised, uint8_t* hRgba, SrtTemporalStats* stats);
+int srtTemporalReset(SrtContext* ctx);
 
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the

@@ -27,6 +27,10 @@ SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL = 56
 SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE = 4.0
 # adaptive sampling (srtRenderAdaptive / srtRenderAdaptiveImage)
 SRT_ADAPTIVE_MAX_ROUNDS, SRT_ADAPTIVE_MAX_SPP, SRT_ADAPTIVE_SCRATCH_BYTES_PER_PIXEL = 32, 1 << 24, 32
+# temporal accumulation (srtTemporalAccumulate / srtRenderTemporalFrame): history bytes per pixel (three float4 planes), the
+# snap tolerance in pixels, and the defaults a field of 0 takes
+SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL, SRT_TEMPORAL_SNAP = 48, 2.0 ** -6
+SRT_TEMPORAL_DEFAULT_NORMAL_COS, SRT_TEMPORAL_DEFAULT_PLANE_DIST, SRT_TEMPORAL_DEFAULT_MAX_HISTORY = 0.5, 0.02, 64.0
 
 f32, i32, i64, u64 = C.c_float, C.c_int32, C.c_int64, C.c_uint64
 
@@ -116,6 +120,14 @@ class SrtAdaptiveStats(C.Structure):
                 ("roundMs", f32 * 32)]
 
 
+class SrtTemporalParams(C.Structure):
+    _fields_ = [("normalCos", f32), ("planeDist", f32), ("maxHistory", f32), ("demodulate", i32), ("pad", i32 * 4)]
+
+
+class SrtTemporalStats(C.Structure):
+    _fields_ = [("historyPixels", i64), ("meanHistoryCount", C.c_double)]
+
+
 class SrtStats(C.Structure):
     _fields_ = [("samples", u64), ("rays", u64), ("nodeVisits", u64), ("boxPasses", u64),
                 ("triTests", u64), ("sphereTests", u64), ("shadedTriHits", u64), ("texelFetches", u64),
@@ -168,6 +180,13 @@ def default_adaptive_params(spp_max, threshold):
     a = SrtAdaptiveParams()
     a.sppMax, a.threshold = spp_max, threshold
     return a
+
+
+def default_temporal_params(normal_cos=0.0, plane_dist=0.0, max_history=0.0, demodulate=0):
+    """include/srt_hip.h SrtTemporalParams: a field of 0 takes the library's default; max_history = inf keeps everything."""
+    t = SrtTemporalParams()
+    t.normalCos, t.planeDist, t.maxHistory, t.demodulate = normal_cos, plane_dist, max_history, demodulate
+    return t
 
 
 def default_camera_params(aspect=16.0 / 9.0):

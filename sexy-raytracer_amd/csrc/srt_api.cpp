@@ -38,6 +38,7 @@ int srt_launch_adaptive_update(const uint32_t* list, int count, const float4* be
 int srt_launch_adaptive_compact(const uint32_t* list, const int32_t* flags, int count, uint32_t* out, int32_t* counts,
                                 int width, int height, hipStream_t stream);
 int srt_launch_adaptive_resolve(const float4* accum, uint8_t* rgba, int n, hipStream_t stream);
+int srt_launch_temporal(const TemporalArgs* a, hipStream_t stream);
 }
 
 // Diagnostic tunables of the work distribution and the wave scheduler.  Environment variables give the
@@ -86,6 +87,13 @@ struct SrtContext {
   // srtRenderAdaptive: one launch's beauty and moments tiles, two tile lists (this launch's, the next one's), the per-tile
   // flags and the compaction's {count, pixels}
   DeviceBuffer adaptTiles, adaptList[2], adaptFlags, adaptCounts;
+  // srtRenderTemporalFrame: the two histories (the one the last frame wrote, the one the next writes), what they belong to,
+  // and the camera as srtSetCamera received it (DevCamera drops w)
+  DeviceBuffer temporalHistory[2];
+  int32_t temporalCurrent = 0;  // index of the history the last frame wrote
+  bool temporalValid = false;
+  int32_t temporalKey[3] = {0, 0, 0};  // width, height, demodulate
+  SrtCamera camFull{}, temporalCam{};
   int32_t tileTableKey[3] = {0, 0, 0};
   RenderPlan lastPlan{};  // the most recent render launch (srtGetLaunchInfo)
   int32_t lastGrid = 0;
@@ -268,6 +276,7 @@ int srtSetCamera(SrtContext* ctx, const SrtCamera* c) {
   d.lensRadius = c->lensRadius;
   d.time0 = c->time0;
   d.time1 = c->time1;
+  ctx->camFull = *c;
   ctx->haveCamera = true;
   return 0;
 }
@@ -277,6 +286,7 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   HIP_OK(ctx, hipSetDevice(ctx->device));
   ctx->sceneBuffers.clear();
   ctx->haveScene = false;
+  ctx->temporalValid = false;  // a history belongs to its scene
   ctx->itemNodes.clear();
   ctx->deviceBuilds.clear();
   ctx->bvhDepth = 0;
@@ -1231,6 +1241,165 @@ int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width,
 int srtRenderDenoisedImageMoments(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
                                   float* hMoments, float* hDenoised, uint8_t* hRgba) {
   SRT_GUARDED(ctx, srtRenderDenoisedImageImpl(ctx, p, d, hAccum, hDenoised, hRgba, true, hMoments));
+}
+
+/* Temporal accumulation (srt_temporal.hip).  Reads nothing of the context but the device ordinal; the frame entry keeps
+ * the histories and the previous camera in the context. */
+static bool sameProjection(const SrtCamera& a, const SrtCamera& b) {
+  return !memcmp(a.origin, b.origin, 12) && !memcmp(a.lleft, b.lleft, 12) && !memcmp(a.horizontal, b.horizontal, 12) &&
+         !memcmp(a.vertical, b.vertical, 12) && !memcmp(a.w, b.w, 12);
+}
+
+static int checkTemporalParams(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, TemporalArgs& a) {
+  if (!t) return fail(ctx, "temporal: null parameters");
+  if (width < 2 || height < 2) return fail(ctx, "temporal: image size %dx%d must be at least 2x2", width, height);
+  if ((int64_t)width * height > 0x7fffffff / 3) return fail(ctx, "temporal: image of %dx%d pixels is too large", width, height);
+  if (!(t->normalCos >= 0.0f && t->normalCos <= 1.0f)) return fail(ctx, "temporal: normalCos %g must be in [0, 1] (0 = default)", t->normalCos);
+  if (!(t->planeDist >= 0.0f)) return fail(ctx, "temporal: planeDist %g must be >= 0 (0 = default)", t->planeDist);
+  if (!(t->maxHistory >= 0.0f)) return fail(ctx, "temporal: maxHistory %g must be >= 0 (0 = default, +inf = no cap)", t->maxHistory);
+  memset(&a, 0, sizeof a);
+  a.width = width;
+  a.height = height;
+  a.normalCos = t->normalCos == 0.0f ? SRT_TEMPORAL_DEFAULT_NORMAL_COS : t->normalCos;
+  a.planeDist = t->planeDist == 0.0f ? SRT_TEMPORAL_DEFAULT_PLANE_DIST : t->planeDist;
+  a.maxHistory = t->maxHistory == 0.0f ? SRT_TEMPORAL_DEFAULT_MAX_HISTORY : t->maxHistory;
+  return 0;
+}
+
+static int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
+                                     const void* dBeauty, const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
+                                     const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
+                                     void* dHistoryOut, void* streamPtr) {
+  if (!ctx) return 1;
+  TemporalArgs a;
+  if (checkTemporalParams(ctx, t, width, height, a)) return 1;
+  if (!dBeauty) return fail(ctx, "temporal: null beauty buffer");
+  if (!dPlanes) return fail(ctx, "temporal: null plane array");
+  if (!dPlanes[1]) return fail(ctx, "temporal: the NORMAL plane is required");
+  if (!dPlanes[2]) return fail(ctx, "temporal: the POSITION plane is required");
+  if (!dPlanes[3]) return fail(ctx, "temporal: the DEPTH plane is required");
+  if (t->demodulate && !dPlanes[0]) return fail(ctx, "temporal: demodulate needs the ALBEDO plane");
+  if (!dBeautyOut && !dMomentsOut) return fail(ctx, "temporal: no output buffer");
+  if (!dHistoryOut) return fail(ctx, "temporal: null history output");
+  if (dHistoryOut == dHistoryIn) return fail(ctx, "temporal: the history is not updated in place (dHistoryOut == dHistoryIn)");
+  if (!cam || (dHistoryIn && !prevCam)) return fail(ctx, "temporal: null camera");
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  a.beauty = static_cast<const float4*>(dBeauty);
+  a.moments = static_cast<const float4*>(dMoments);
+  a.albedo = t->demodulate ? static_cast<const float4*>(dPlanes[0]) : nullptr;
+  a.normal = static_cast<const float4*>(dPlanes[1]);
+  a.position = static_cast<const float4*>(dPlanes[2]);
+  a.depth = static_cast<const float4*>(dPlanes[3]);
+  a.historyIn = static_cast<const float4*>(dHistoryIn);
+  a.beautyOut = static_cast<float4*>(dBeautyOut);
+  a.momentsOut = static_cast<float4*>(dMomentsOut);
+  a.historyOut = static_cast<float4*>(dHistoryOut);
+  a.cam = *cam;
+  a.prev = dHistoryIn ? *prevCam : *cam;
+  a.sameCamera = sameProjection(a.cam, a.prev) ? 1 : 0;
+  const int rc = srt_launch_temporal(&a, static_cast<hipStream_t>(streamPtr));
+  if (rc) return fail(ctx, "temporal launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static int srtRenderTemporalFrameImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtDenoiseParams* d,
+                                      const SrtTemporalParams* t, float* hAccum, float* hDenoised, uint8_t* hRgba,
+                                      SrtTemporalStats* stats) {
+  if (!ctx) return 1;
+  if (!pIn) return fail(ctx, "temporal: null render parameters");
+  DenoiseArgs dcheck;
+  TemporalArgs tcheck;
+  int iterations = 0;
+  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, dcheck, iterations, true)) return 1;
+  if (checkTemporalParams(ctx, t, pIn->imageWidth, pIn->imageHeight, tcheck)) return 1;
+  if (pIn->countStats) return fail(ctx, "render: the moments entries have no counting variant (countStats must be 0)");
+  SrtRenderParams p = *pIn;
+  p.tileFirst = 0;
+  p.tileStride = 1;
+  if (checkParams(ctx, &p)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const int W = p.imageWidth, H = p.imageHeight;
+  const size_t nPix = (size_t)W * H;
+  const size_t tileBytes = (size_t)srtNumTiles(W, H) * SRT_TILE_PIXELS * sizeof(float4);
+  const int32_t key[3] = {W, H, t->demodulate ? 1 : 0};
+  if (memcmp(key, ctx->temporalKey, sizeof key) != 0) ctx->temporalValid = false;
+  const int32_t planes = SRT_FEATURE_ALL;
+  DeviceBuffer tiles, mtiles, accum, mom, accOut, momOut, featTiles[4], featImage[4], out, rgba;
+  if (tiles.reserve(tileBytes) != hipSuccess || mtiles.reserve(tileBytes) != hipSuccess || accum.reserve(nPix * sizeof(float4)) != hipSuccess ||
+      mom.reserve(nPix * sizeof(float4)) != hipSuccess || accOut.reserve(nPix * sizeof(float4)) != hipSuccess ||
+      momOut.reserve(nPix * sizeof(float4)) != hipSuccess)
+    return fail(ctx, "temporal: hipMalloc");
+  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
+  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
+  void* dTiles[4];
+  const void* dPlanes[4];
+  for (int k = 0; k < 4; ++k) {
+    if (featTiles[k].reserve(tileBytes) != hipSuccess || featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess)
+      return fail(ctx, "temporal: hipMalloc");
+    dTiles[k] = featTiles[k].get();
+    dPlanes[k] = featImage[k].get();
+  }
+  for (auto& h : ctx->temporalHistory)
+    if (h.reserve(nPix * SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL) != hipSuccess) return fail(ctx, "temporal: hipMalloc history");
+  // the frame exactly as srtRenderDenoisedImageMoments renders it, with all four planes
+  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr, nullptr, 0, mtiles.get())) return 1;
+  if (srtResolveTiles(ctx, &p, tiles.get(), nullptr, accum.get(), nullptr)) return 1;
+  if (srtResolveTiles(ctx, &p, mtiles.get(), nullptr, mom.get(), nullptr)) return 1;
+  if (srtRenderFeatureTilesImpl(ctx, &p, planes, dTiles, nullptr)) return 1;
+  for (int k = 0; k < 4; ++k)
+    if (srtResolveTiles(ctx, &p, dTiles[k], nullptr, featImage[k].get(), nullptr)) return 1;
+  const int next = ctx->temporalCurrent ^ 1;
+  const void* histIn = ctx->temporalValid ? ctx->temporalHistory[ctx->temporalCurrent].get() : nullptr;
+  void* histOut = ctx->temporalHistory[next].get();
+  ctx->temporalValid = false;  // until this frame's history is complete
+  if (srtTemporalAccumulateImpl(ctx, t, W, H, accum.get(), mom.get(), dPlanes, &ctx->camFull, &ctx->temporalCam, histIn, accOut.get(),
+                                momOut.get(), histOut, nullptr))
+    return 1;
+  if (hDenoised || hRgba) {
+    if (srtDenoiseImpl(ctx, d, W, H, accOut.get(), dPlanes, out.get(), rgba.get(), nullptr, true, momOut.get())) return 1;
+  }
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "temporal: kernel failed: %s", hipGetErrorString(hipGetLastError()));
+  if (wfCheck(ctx)) return 1;
+  ctx->temporalCurrent = next;
+  ctx->temporalCam = ctx->camFull;
+  memcpy(ctx->temporalKey, key, sizeof key);
+  ctx->temporalValid = true;
+  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy accum");
+  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy denoised");
+  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy rgba");
+  if (stats) {
+    std::vector<float> cur(nPix * 4), acc(nPix * 4), hist(nPix * 4);
+    if (hipMemcpy(cur.data(), accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(acc.data(), accOut.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(hist.data(), histOut, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(ctx, "temporal: copy stats");
+    stats->historyPixels = 0;
+    double sum = 0.0;
+    for (size_t i = 0; i < nPix; ++i) {
+      if (acc[4 * i + 3] > cur[4 * i + 3]) stats->historyPixels++;
+      sum += (double)hist[4 * i + 3];
+    }
+    stats->meanHistoryCount = sum / (double)nPix;
+  }
+  return 0;
+}
+
+int srtTemporalAccumulate(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
+                          const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
+                          const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut, void* stream) {
+  SRT_GUARDED(ctx, srtTemporalAccumulateImpl(ctx, t, width, height, dBeauty, dMoments, dPlanes, cam, prevCam, dHistoryIn, dBeautyOut,
+                                             dMomentsOut, dHistoryOut, stream));
+}
+int srtRenderTemporalFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, const SrtTemporalParams* t,
+                           float* hAccum, float* hDenoised, uint8_t* hRgba, SrtTemporalStats* stats) {
+  SRT_GUARDED(ctx, srtRenderTemporalFrameImpl(ctx, p, d, t, hAccum, hDenoised, hRgba, stats));
+}
+int srtTemporalReset(SrtContext* ctx) {
+  if (!ctx) return 1;
+  (void)hipSetDevice(ctx->device);
+  ctx->temporalValid = false;
+  for (auto& h : ctx->temporalHistory) h = DeviceBuffer();
+  return 0;
 }
 
 /* include/srt_hip_test.h: the render kernel's own traversal, ray by ray */

@@ -226,6 +226,25 @@ struct DenoiseArgs {
   const float4* moments; // srtDenoiseMoments: {sum l, sum l^2, 0, count} per pixel (image order), or null
 };
 
+// srtTemporalAccumulate (srt_temporal.hip): image-order planes in, accumulated planes and the new history out.  A
+// history is three float4 planes one after the other (include/srt_hip.h).
+struct TemporalArgs {
+  int32_t width, height;
+  const float4* beauty;
+  const float4* moments;  // may be null
+  const float4* albedo;   // null unless demodulating
+  const float4* normal;
+  const float4* position;
+  const float4* depth;
+  const float4* historyIn;  // null: the first frame
+  float4* beautyOut;        // may be null
+  float4* momentsOut;       // may be null
+  float4* historyOut;
+  SrtCamera cam, prev;
+  int32_t sameCamera;  // cam and prev agree bit for bit in what the projection reads: every pixel is its own history
+  float normalCos, planeDist, maxHistory;
+};
+
 struct ResolveArgs {
   const float4* gathered;  // [rank][localTile][64]
   int32_t imageWidth, imageHeight, tilesX;

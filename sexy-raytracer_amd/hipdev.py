@@ -35,6 +35,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtScatterRays",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
+           "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -83,6 +84,12 @@ lib.srtRenderAdaptive.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER
 lib.srtRenderAdaptiveImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtAdaptiveParams),
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8),
                                        C.POINTER(abi.SrtAdaptiveStats)]
+lib.srtTemporalAccumulate.argtypes = [_vp, C.POINTER(abi.SrtTemporalParams), C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_vp),
+                                      C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtCamera), _vp, _vp, _vp, _vp, _vp]
+lib.srtRenderTemporalFrame.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtDenoiseParams),
+                                       C.POINTER(abi.SrtTemporalParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_uint8), C.POINTER(abi.SrtTemporalStats)]
+lib.srtTemporalReset.argtypes = [_vp]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -343,6 +350,38 @@ class Context:
                                                       moments.ctypes.data_as(fp), denoised.ctypes.data_as(fp),
                                                       rgba.ctypes.data_as(C.POINTER(C.c_uint8))))
         return accum, moments, denoised, rgba
+
+    def temporal_accumulate(self, tparams, width, height, d_beauty_ptr, d_moments_ptr, plane_ptrs, cam, prev_cam, d_history_in_ptr,
+                            d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream=None):
+        """Asynchronous temporal accumulation over DEVICE image-order buffers (include/srt_hip.h srtTemporalAccumulate):
+        reprojects the history written with prev_cam (None / NULL history: the first frame) onto cam and adds the current
+        frame.  plane_ptrs[k] = the resolved feature plane of bit 1 << k; a history is
+        abi.SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL bytes per pixel."""
+        arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
+        self._check(lib.srtTemporalAccumulate(self.h, C.byref(tparams), int(width), int(height), d_beauty_ptr, d_moments_ptr, arr,
+                                              C.byref(cam), C.byref(prev_cam) if prev_cam is not None else None,
+                                              d_history_in_ptr, d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream))
+
+    def render_temporal_frame(self, params, dparams=None, tparams=None, want_stats=True):
+        """One frame of a sequence (srtRenderTemporalFrame): render with the camera currently set, accumulate onto the history
+        the context kept from the previous call, denoise.  Returns (accum, denoised, rgba, stats): accum = this frame's own
+        sums, bit-identical to render_image's; stats = {"historyPixels", "meanHistoryCount"} or None."""
+        dparams = abi.default_denoise_params() if dparams is None else dparams
+        tparams = abi.default_temporal_params() if tparams is None else tparams
+        W, H = params.imageWidth, params.imageHeight
+        accum, denoised = (np.zeros((H, W, 4), np.float32) for _ in range(2))
+        rgba = np.zeros((H, W, 4), np.uint8)
+        st = abi.SrtTemporalStats()
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtRenderTemporalFrame(self.h, C.byref(params), C.byref(dparams), C.byref(tparams), accum.ctypes.data_as(fp),
+                                               denoised.ctypes.data_as(fp), rgba.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                               C.byref(st) if want_stats else None))
+        stats = {"historyPixels": int(st.historyPixels), "meanHistoryCount": float(st.meanHistoryCount)} if want_stats else None
+        return accum, denoised, rgba, stats
+
+    def temporal_reset(self):
+        """Drops the history srtRenderTemporalFrame keeps: the next frame starts over."""
+        self._check(lib.srtTemporalReset(self.h))
 
     def render_tiles(self, params, d_accum_ptr, stream=None):
         self._check(lib.srtRenderTiles(self.h, C.byref(params), d_accum_ptr, stream))

@@ -6,6 +6,9 @@
 //                                           the first hit of the camera rays rtFrame traces (a denoiser's guides)
 //   rtFrameDenoised(target, denoised, ...)  rtFrame's frame, its feature pass and the library's a-trous denoiser: the
 //                                           noisy and the denoised RGBA8 frames of one render
+//   rtFrameTemporal(denoised, ..., sampleFirst)  one frame of a sequence: rtFrameDenoised's frame accumulated onto the
+//                                           reprojected history of the previous call before it is denoised
+//                                           (include/srt_hip.h "Temporal accumulation"); temporalReset() starts over
 //   rtFrameAdaptive(target, ..., sppMax, thr)  tile-adaptive sampling: numSamples everywhere, then more samples, doubling,
 //                                           for the tiles that have not converged (include/srt_hip.h "Adaptive sampling")
 //   terminate()
@@ -152,6 +155,7 @@ class hipDevice {
     p.traversal = SRT_TRAVERSE_FAITHFUL;
     p.tileFirst = 0; p.tileStride = 1;
     p.sppChunks = sppChunks;
+    p.sampleFirst = sampleFirst;
     const SrtDenoiseParams defaults{};
     std::vector<float> sums;
     if (!accum && frameData) {
@@ -178,6 +182,39 @@ class hipDevice {
     return true;
   }
 
+  // One frame of a camera move (include/srt_hip.h srtRenderTemporalFrame): samples [sampleFirst, sampleFirst + numSamples)
+  // with `cam`, accumulated onto the history the previous call left (reprojected from its camera), then denoised with the
+  // sample variance.  denoisedData (may be null) receives the RGBA8 frame, accum / denoised (float[w*h*4], may be null)
+  // this frame's own sums and the denoised means.  d, t = null: the library's defaults.  Callers advance sampleFirst by
+  // numSamples per frame so that every frame draws fresh samples.  Single-process only.
+  bool rtFrameTemporal(void* denoisedData, int w, int h, const camera& cam, const color3f& background, int numSamples,
+                       int maxBounce, int sampleFirst, uint64_t seed = 1, const SrtDenoiseParams* d = nullptr,
+                       const SrtTemporalParams* t = nullptr, float* accum = nullptr, float* denoised = nullptr,
+                       SrtTemporalStats* stats = nullptr) {
+    if (!ctx) return false;
+    if (ranks > 1) {
+      std::cerr << "ERROR: rtFrameTemporal renders on one GPU\n";
+      return false;
+    }
+    if (srtSetCamera(ctx, &cam.data()) != 0) return error();
+    SrtRenderParams p{};
+    p.imageWidth = w; p.imageHeight = h; p.spp = numSamples; p.maxBounce = maxBounce; p.seed = seed;
+    for (int i = 0; i < 3; ++i) p.background[i] = background(i);
+    p.tMin = 0.001f;  // main.cpp:39
+    p.traversal = SRT_TRAVERSE_FAITHFUL;
+    p.tileFirst = 0; p.tileStride = 1;
+    p.sppChunks = sppChunks;
+    p.sampleFirst = sampleFirst;
+    const SrtDenoiseParams ddefaults{};
+    const SrtTemporalParams tdefaults{};
+    if (srtRenderTemporalFrame(ctx, &p, d ? d : &ddefaults, t ? t : &tdefaults, accum, denoised, static_cast<uint8_t*>(denoisedData),
+                               stats) != 0)
+      return error();
+    (void)srtLastKernelMs(ctx, &lastKernelMs);
+    return true;
+  }
+  bool temporalReset() { return ctx && srtTemporalReset(ctx) == 0; }
+
   bool trace(const std::vector<SrtRay>& rays, std::vector<SrtHit>& hits) {
     hits.resize(rays.size());
     if (!ctx || srtTraceRays(ctx, rays.data(), (int64_t)rays.size(), hits.data(), SRT_TRAVERSE_FAITHFUL) != 0) return error();
@@ -190,6 +227,7 @@ class hipDevice {
   }
 
  public:
+  int sampleFirst = 0;  // rtFrameDenoised: the first sample index of the frame (frame k of a sequence: k * numSamples)
   int sppChunks = 0;  // 0 = library default; 1 = the reference's single running sum per pixel
   float lastKernelMs = 0;
   int numPrims = 0;
