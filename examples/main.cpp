@@ -5,6 +5,7 @@
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
 //                  [--denoise FILE.png [--sample-variance]] [--adaptive THRESHOLD --max-spp N]
+//                  [--frames N --orbit DEG [--temporal]]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
@@ -12,6 +13,12 @@
 //   --adaptive THRESHOLD --max-spp N  tile-adaptive sampling (hipDevice::rtFrameAdaptive): --spp samples everywhere, then
 //                     doubling rounds for the tiles whose display-space standard error is still >= THRESHOLD (1/256 = one
 //                     display step), up to N samples a pixel
+//   --frames N --orbit D [--temporal]  a camera move of N frames over D degrees, NAME_%03d.png; --temporal accumulates
+//                     each frame onto the reprojected history of the one before it
+//   --frames N --orbit D --temporal --adaptive THRESHOLD --max-spp M  the same with history-steered sampling
+//                     (hipDevice::rtFrameTemporalAdaptive): the adaptive rounds decide on each tile's samples pooled with
+//                     its history, so disoccluded tiles get up to M samples and settled ones stop at --spp; frame k
+//                     draws its samples from k * M
 //   SRT_DATA_DIR selects the directory of the glTF's images (default "../data/", as the reference).
 #include <chrono>
 #include <cstdlib>
@@ -120,6 +127,9 @@ int main(int argc, char** argv) {
     // A camera move: frame k looks from the eye turned by orbit * k / (frames - 1) degrees about the vertical axis through
     // the lookAt point and draws samples [k * spp, (k + 1) * spp).  --temporal accumulates each frame onto the reprojected
     // history of the one before it (rtFrameTemporal); without it every frame is denoised from its own samples alone.
+    // --temporal with --adaptive steers each frame's samples by that history (rtFrameTemporalAdaptive).
+    const bool steered = temporal && adaptive >= 0.0f;
+    const int sppMax = maxSpp > 0 ? maxSpp : numSamples;
     const vec3f eye(0.0f, 3.0f, 5.0f), lookAt(0, 2.5f, 0);
     const float dx = eye(0) - lookAt(0), dz = eye(2) - lookAt(2);
     const std::string stem = out.size() > 4 && out.substr(out.size() - 4) == ".png" ? out.substr(0, out.size() - 4) : out;
@@ -129,7 +139,14 @@ int main(int argc, char** argv) {
       const float c = (float)std::cos(angle), s = (float)std::sin(angle);
       const vec3f eyeK(lookAt(0) + (c * dx + s * dz), eye(1), lookAt(2) + (c * dz - s * dx));
       camera cam(eyeK, lookAt, vec3f(0, 1.0f, 0), 70.0f, aspect, 0.1f, 10.0f, 0, 1.0f);
-      if (temporal) {
+      if (steered) {
+        SrtTemporalAdaptiveStats st{};
+        if (!device.rtFrameTemporalAdaptive(frame.data(), imageWidth, imageHeight, cam, background, numSamples, maxBounce, sppMax,
+                                            adaptive, k * sppMax, 1, nullptr, nullptr, nullptr, nullptr, &st))
+          return 1;
+        std::cerr << "frame " << k << ": " << (double)st.adaptive.pixelSamples / ((double)imageWidth * imageHeight)
+                  << " samples per pixel in " << st.adaptive.rounds << " rounds\n";
+      } else if (temporal) {
         if (!device.rtFrameTemporal(frame.data(), imageWidth, imageHeight, cam, background, numSamples, maxBounce, k * numSamples))
           return 1;
       } else {
@@ -148,7 +165,8 @@ int main(int argc, char** argv) {
     device.terminate();
     free(target);
     std::cerr << frames << " frames of " << imageWidth << "x" << imageHeight << " @" << numSamples << " spp, "
-              << (temporal ? "temporal accumulation" : "frame by frame") << " -> " << stem << "_000.png ...\nDone.\n";
+              << (steered ? "temporal accumulation with history-steered sampling" : temporal ? "temporal accumulation" : "frame by frame")
+              << " -> " << stem << "_000.png ...\nDone.\n";
     return 0;
   }
   auto t0 = std::chrono::steady_clock::now();

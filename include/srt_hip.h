@@ -591,6 +591,71 @@ int srtRenderTemporalFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtD
                            float* hAccum, float* hDenoised, uint8_t* hRgba, SrtTemporalStats* stats);
 int srtTemporalReset(SrtContext* ctx);
 
+/* Temporal-adaptive frames: "Adaptive sampling" deciding on the TEMPORALLY ACCUMULATED moments.  A tile stops once its
+ * reprojected history and this frame's samples together are below the display-space threshold and keeps doubling while
+ * they are not -- because it has just been disoccluded (no history: the frame's own few samples decide, as in
+ * srtRenderAdaptive), or because the history disagrees with the new samples (the pooled variance grows, and buys samples).
+ *
+ * srtTemporalAccumulate is linear in the current frame's sums and its reprojected history h does not depend on them, so h
+ * is computed once per frame and every round reads it back:
+ *   reprojected history  SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL bytes per pixel, two image-order float4 planes one after
+ *             the other: plane 0 = {h.r, h.g, h.b, h.count}, plane 1 = {h.S1, h.S2, 0, has ? 1 : 0}, has = the pixel has an
+ *             accepted tap; all zeros where it has none.  h is the result of the "Temporal accumulation" rules through the
+ *             maxHistory cap -- ray, point, projection, snap, taps, acceptance, normalisation in tap order, the cap, and the
+ *             camera-not-moved rule -- in that text's operation order, bit for bit.  It reads the NORMAL and DEPTH planes, the two cameras and the
+ *             history (the POSITION mean only reaches srtTemporalAccumulate's new history); never the beauty, the moments
+ *             or the ALBEDO plane: h is in the history's (demodulated) units
+ *   round 0   exactly srtRenderAdaptive's: dAccumImage and dMomentsImage are bit-identical to srtRenderImageMoments(p)
+ *   pooled moments after launch r, per in-image pixel with the sums so far {r, g, b, n} and {S1, S2, 0, n}: what
+ *             srtTemporalAccumulate would write to dMomentsOut,
+ *               M~ = {S1 + la h.S1, S2 + (la la) h.S2, 0, n + h.count}   for a USABLE pixel with has
+ *               M~ = {S1, S2, 0, n}                                      otherwise
+ *             la = 1 and no multiplication when not demodulating; USABLE, a~ and la as in "Temporal accumulation"
+ *   convergence  srtRenderAdaptive's test in double, in its operation order, on M~ instead of the frame's own moments
+ *   active set, schedule b_r = min(n_{r-1}, sppMax - n_{r-1}), chunk plans, the per-launch float add into the image-order
+ *             sums and the end of the render are srtRenderAdaptive's, unchanged; n_r counts THIS frame's samples only, and
+ *             every pixel of an active tile still has the same current count
+ *   end       dBeautyOut, dMomentsOut and dHistoryOut are srtTemporalAccumulate of the final sums, bit for bit
+ * Consequences: threshold = +inf or sppMax == spp is srtRenderImageMoments followed by srtTemporalAccumulate; dHistoryIn ==
+ * NULL gives srtRenderAdaptive's sums bit for bit, stats->adaptive.roundTiles included.
+ * The feature planes are those of the frame's first p->spp samples: their means guide the reprojection (and, in the frame
+ * entry, the denoiser) for every tile, however many samples the tile ends with.  Extra samples get no feature pass.
+ *
+ * srtTemporalReproject    asynchronous on `stream`, one kernel.  dReprojected = DEVICE float4[2][W*H].  dHistoryIn == NULL:
+ *                 all zeros, prevCam is not read.  Plane requirements and errors are srtTemporalAccumulate's (ALBEDO is
+ *                 required when t->demodulate is set although it is not read: one rule for both entries).
+ * srtRenderTemporalAdaptive  DEVICE image-order buffers, one GPU, the camera currently set as cur.  dPlanes = the resolved
+ *                 feature planes of samples [p->sampleFirst, p->sampleFirst + p->spp).  dAccumImage and dMomentsImage
+ *                 (required) receive this frame's sums with per-pixel counts; dBeautyOut, dMomentsOut (either may be NULL,
+ *                 not both) and dHistoryOut (required, not dHistoryIn) as in srtTemporalAccumulate.  Works on `stream` and
+ *                 reads the next tile count back once per round, as srtRenderAdaptive: it returns after its work has
+ *                 finished.  stats (may be NULL): adaptive as srtRenderAdaptive's, pixelSamples included; temporal as
+ *                 srtRenderTemporalFrame's.
+ * srtRenderTemporalAdaptiveFrame  blocking, HOST buffers, each may be NULL: the feature pass of `p` (all four planes,
+ *                 p->spp samples), srtRenderTemporalAdaptive against the history and camera the context kept,
+ *                 srtDenoiseMoments (parameters d) on the accumulated buffers, then the context keeps the new history and
+ *                 the camera: srtRenderTemporalFrame's histories, ping-pong and reset rules, so frames of both kinds may
+ *                 follow one another on one context.  hAccum = THIS frame's sums with per-pixel counts; hDenoised / hRgba as
+ *                 srtRenderTemporalFrame.  Callers advance p->sampleFirst by ap->sppMax per frame.
+ * Errors (non-zero, message in srtLastError, nothing launched, outputs untouched): what srtRenderAdaptive rejects and what
+ * srtTemporalAccumulate rejects.  Tunables, the host generator, srtLastKernelMs and srtGetLaunchInfo are left as after
+ * srtRenderAdaptive.  Device memory held by the context until srtDestroy: srtRenderAdaptive's, plus
+ * SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL bytes per pixel of the largest image. */
+#define SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL 32
+typedef struct SrtTemporalAdaptiveStats {
+  SrtAdaptiveStats adaptive;
+  SrtTemporalStats temporal;
+} SrtTemporalAdaptiveStats;
+int srtTemporalReproject(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* const dPlanes[4],
+                         const SrtCamera* cam, const SrtCamera* prevCam, const void* dHistoryIn, void* dReprojected, void* stream);
+int srtRenderTemporalAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtTemporalParams* t,
+                              const void* const dPlanes[4], const SrtCamera* prevCam, const void* dHistoryIn, void* dAccumImage,
+                              void* dMomentsImage, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut,
+                              SrtTemporalAdaptiveStats* stats, void* stream);
+int srtRenderTemporalAdaptiveFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtDenoiseParams* d,
+                                   const SrtTemporalParams* t, float* hAccum, float* hDenoised, uint8_t* hRgba,
+                                   SrtTemporalAdaptiveStats* stats);
+
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the
  * ranks' equal-sized tile buffers to rank 0 over RCCL (ncclGather), after which rank 0 calls

@@ -31,6 +31,8 @@ SRT_ADAPTIVE_MAX_ROUNDS, SRT_ADAPTIVE_MAX_SPP, SRT_ADAPTIVE_SCRATCH_BYTES_PER_PI
 # snap tolerance in pixels, and the defaults a field of 0 takes
 SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL, SRT_TEMPORAL_SNAP = 48, 2.0 ** -6
 SRT_TEMPORAL_DEFAULT_NORMAL_COS, SRT_TEMPORAL_DEFAULT_PLANE_DIST, SRT_TEMPORAL_DEFAULT_MAX_HISTORY = 0.5, 0.02, 64.0
+# temporal-adaptive frames (srtTemporalReproject / srtRenderTemporalAdaptive): the reprojected history, two float4 planes
+SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL = 32
 
 f32, i32, i64, u64 = C.c_float, C.c_int32, C.c_int64, C.c_uint64
 
@@ -126,6 +128,10 @@ class SrtTemporalParams(C.Structure):
 
 class SrtTemporalStats(C.Structure):
     _fields_ = [("historyPixels", i64), ("meanHistoryCount", C.c_double)]
+
+
+class SrtTemporalAdaptiveStats(C.Structure):
+    _fields_ = [("adaptive", SrtAdaptiveStats), ("temporal", SrtTemporalStats)]
 
 
 class SrtStats(C.Structure):

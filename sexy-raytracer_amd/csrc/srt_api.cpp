@@ -39,6 +39,11 @@ int srt_launch_adaptive_compact(const uint32_t* list, const int32_t* flags, int 
                                 int width, int height, hipStream_t stream);
 int srt_launch_adaptive_resolve(const float4* accum, uint8_t* rgba, int n, hipStream_t stream);
 int srt_launch_temporal(const TemporalArgs* a, hipStream_t stream);
+int srt_launch_temporal_reproject(const TemporalArgs* a, hipStream_t stream);
+int srt_launch_temporal_adaptive_update(const uint32_t* list, int count, const float4* beautyTiles, const float4* momentTiles,
+                                        float4* accum, float4* moments, const float4* reprojected, const float4* albedo,
+                                        int32_t* flags, int width, int height, double limit, bool accumulate,
+                                        hipStream_t stream);
 }
 
 // Diagnostic tunables of the work distribution and the wave scheduler.  Environment variables give the
@@ -90,6 +95,7 @@ struct SrtContext {
   // srtRenderTemporalFrame: the two histories (the one the last frame wrote, the one the next writes), what they belong to,
   // and the camera as srtSetCamera received it (DevCamera drops w)
   DeviceBuffer temporalHistory[2];
+  DeviceBuffer temporalReprojected;  // srtRenderTemporalAdaptive: the frame's reprojected history (32 B per pixel)
   int32_t temporalCurrent = 0;  // index of the history the last frame wrote
   bool temporalValid = false;
   int32_t temporalKey[3] = {0, 0, 0};  // width, height, demodulate
@@ -831,8 +837,15 @@ static int checkAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAda
   return 0;
 }
 
+// srtRenderTemporalAdaptive: the decisions pool the frame's moments with this reprojected history (srt_temporal_adaptive.hip)
+struct AdaptivePool {
+  const float4* reprojected;  // two planes, SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL
+  const float4* albedo;       // null unless the history is demodulated
+};
+
 static int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap, void* dAccumImage,
-                                 void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* streamPtr) {
+                                 void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* streamPtr,
+                                 const AdaptivePool* pool = nullptr) {
   if (checkAdaptive(ctx, pIn, ap, true, dAccumImage, dMomentsImage)) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
@@ -875,13 +888,13 @@ static int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, co
       if (srtResolveTiles(ctx, &q, beautyTiles, nullptr, accum, stream) || srtResolveTiles(ctx, &q, momentTiles, nullptr, moments, stream))
         return 1;
       list = ctx->tileTable.get<const uint32_t>();  // built for this size by the launch above
-      if (decide)
-        rc = srt_launch_adaptive_update(list, listTiles, nullptr, nullptr, accum, moments, ctx->adaptFlags.get<int32_t>(), W, H,
-                                        limit, false, true, stream);
-    } else {
-      rc = srt_launch_adaptive_update(list, listTiles, beautyTiles, momentTiles, accum, moments, ctx->adaptFlags.get<int32_t>(),
-                                      W, H, limit, true, decide, stream);
     }
+    if (pool && decide)
+      rc = srt_launch_temporal_adaptive_update(list, listTiles, beautyTiles, momentTiles, accum, moments, pool->reprojected,
+                                               pool->albedo, ctx->adaptFlags.get<int32_t>(), W, H, limit, r > 0, stream);
+    else if (r > 0 || decide)
+      rc = srt_launch_adaptive_update(list, listTiles, beautyTiles, momentTiles, accum, moments, ctx->adaptFlags.get<int32_t>(),
+                                      W, H, limit, r > 0, decide, stream);
     uint32_t* const next = ctx->adaptList[r & 1].get<uint32_t>();
     int32_t counts[2] = {0, 0};
     if (!rc && decide)
@@ -1266,12 +1279,11 @@ static int checkTemporalParams(SrtContext* ctx, const SrtTemporalParams* t, int3
   return 0;
 }
 
-static int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
-                                     const void* dBeauty, const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
-                                     const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
-                                     void* dHistoryOut, void* streamPtr) {
+// Everything srtTemporalAccumulate checks, and the kernel's arguments: nothing is launched
+static int temporalArgs(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
+                        const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
+                        const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut, TemporalArgs& a) {
   if (!ctx) return 1;
-  TemporalArgs a;
   if (checkTemporalParams(ctx, t, width, height, a)) return 1;
   if (!dBeauty) return fail(ctx, "temporal: null beauty buffer");
   if (!dPlanes) return fail(ctx, "temporal: null plane array");
@@ -1297,8 +1309,37 @@ static int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t
   a.cam = *cam;
   a.prev = dHistoryIn ? *prevCam : *cam;
   a.sameCamera = sameProjection(a.cam, a.prev) ? 1 : 0;
+  return 0;
+}
+
+static int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
+                                     const void* dBeauty, const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
+                                     const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
+                                     void* dHistoryOut, void* streamPtr) {
+  TemporalArgs a;
+  if (temporalArgs(ctx, t, width, height, dBeauty, dMoments, dPlanes, cam, prevCam, dHistoryIn, dBeautyOut, dMomentsOut, dHistoryOut, a))
+    return 1;
   const int rc = srt_launch_temporal(&a, static_cast<hipStream_t>(streamPtr));
   if (rc) return fail(ctx, "temporal launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// SrtTemporalStats from the finished frame's DEVICE buffers: this frame's sums, an accumulated plane (its w is the
+// output count) and the new history
+static int temporalStats(SrtContext* ctx, size_t nPix, const void* dCurrent, const void* dAccumulated, const void* dHistory,
+                         SrtTemporalStats* stats) {
+  std::vector<float> cur(nPix * 4), acc(nPix * 4), hist(nPix * 4);
+  if (hipMemcpy(cur.data(), dCurrent, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(acc.data(), dAccumulated, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(hist.data(), dHistory, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ctx, "temporal: copy stats");
+  stats->historyPixels = 0;
+  double sum = 0.0;
+  for (size_t i = 0; i < nPix; ++i) {
+    if (acc[4 * i + 3] > cur[4 * i + 3]) stats->historyPixels++;
+    sum += (double)hist[4 * i + 3];
+  }
+  stats->meanHistoryCount = sum / (double)nPix;
   return 0;
 }
 
@@ -1367,20 +1408,117 @@ static int srtRenderTemporalFrameImpl(SrtContext* ctx, const SrtRenderParams* pI
   if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy accum");
   if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy denoised");
   if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy rgba");
+  if (stats && temporalStats(ctx, nPix, accum.get(), accOut.get(), histOut, stats)) return 1;
+  return 0;
+}
+
+/* Temporal-adaptive frames (srt_temporal_adaptive.hip): the reprojected history once per frame, srtRenderAdaptive's rounds
+ * deciding on the pooled moments, srtTemporalAccumulate of the final sums. */
+static int srtTemporalReprojectImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
+                                    const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
+                                    const void* dHistoryIn, void* dReprojected, void* streamPtr) {
+  if (!ctx) return 1;
+  if (!dReprojected) return fail(ctx, "temporal: null reprojected buffer");
+  TemporalArgs a;
+  // srtTemporalAccumulate's checks; the beauty and its outputs are not part of this entry (any non-null pointer passes)
+  if (temporalArgs(ctx, t, width, height, dReprojected, nullptr, dPlanes, cam, prevCam, dHistoryIn, dReprojected, nullptr, dReprojected, a))
+    return 1;
+  a.beauty = nullptr;
+  a.beautyOut = nullptr;
+  const int rc = srt_launch_temporal_reproject(&a, static_cast<hipStream_t>(streamPtr));
+  if (rc) return fail(ctx, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                         const SrtTemporalParams* t, const void* const dPlanes[4], const SrtCamera* prevCam,
+                                         const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
+                                         void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* streamPtr) {
+  // every check of both halves before the first launch
+  if (checkAdaptive(ctx, p, ap, true, dAccumImage, dMomentsImage)) return 1;
+  const int W = p->imageWidth, H = p->imageHeight;
+  const size_t nPix = (size_t)W * H;
+  TemporalArgs a;
+  if (temporalArgs(ctx, t, W, H, dAccumImage, dMomentsImage, dPlanes, &ctx->camFull, prevCam, dHistoryIn, dBeautyOut, dMomentsOut,
+                   dHistoryOut, a))
+    return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  HIP_OK(ctx, ctx->temporalReprojected.reserve(nPix * SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL));
+  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+  TemporalArgs ra = a;
+  ra.historyOut = ctx->temporalReprojected.get<float4>();
+  int rc = srt_launch_temporal_reproject(&ra, stream);
+  if (rc) return fail(ctx, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)rc));
+  const AdaptivePool pool{ctx->temporalReprojected.get<const float4>(), a.albedo};
+  SrtTemporalAdaptiveStats st;
+  memset(&st, 0, sizeof st);
+  if (srtRenderAdaptiveImpl(ctx, p, ap, dAccumImage, dMomentsImage, nullptr, &st.adaptive, streamPtr, &pool)) return 1;
+  rc = srt_launch_temporal(&a, stream);
+  if (rc) return fail(ctx, "temporal launch failed: %s", hipGetErrorString((hipError_t)rc));
+  if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "temporal: kernel failed: %s", hipGetErrorString(hipGetLastError()));
   if (stats) {
-    std::vector<float> cur(nPix * 4), acc(nPix * 4), hist(nPix * 4);
-    if (hipMemcpy(cur.data(), accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(acc.data(), accOut.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(hist.data(), histOut, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
-      return fail(ctx, "temporal: copy stats");
-    stats->historyPixels = 0;
-    double sum = 0.0;
-    for (size_t i = 0; i < nPix; ++i) {
-      if (acc[4 * i + 3] > cur[4 * i + 3]) stats->historyPixels++;
-      sum += (double)hist[4 * i + 3];
-    }
-    stats->meanHistoryCount = sum / (double)nPix;
+    if (temporalStats(ctx, nPix, dAccumImage, dBeautyOut ? dBeautyOut : dMomentsOut, dHistoryOut, &st.temporal)) return 1;
+    *stats = st;
   }
+  return 0;
+}
+
+static int srtRenderTemporalAdaptiveFrameImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap,
+                                              const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum,
+                                              float* hDenoised, uint8_t* hRgba, SrtTemporalAdaptiveStats* stats) {
+  if (!ctx) return 1;
+  if (checkAdaptive(ctx, pIn, ap, false, nullptr, nullptr)) return 1;
+  DenoiseArgs dcheck;
+  TemporalArgs tcheck;
+  int iterations = 0;
+  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, dcheck, iterations, true)) return 1;
+  if (checkTemporalParams(ctx, t, pIn->imageWidth, pIn->imageHeight, tcheck)) return 1;
+  const SrtRenderParams p = *pIn;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const int W = p.imageWidth, H = p.imageHeight;
+  const size_t nPix = (size_t)W * H;
+  const size_t tileBytes = (size_t)srtNumTiles(W, H) * SRT_TILE_PIXELS * sizeof(float4);
+  const int32_t key[3] = {W, H, t->demodulate ? 1 : 0};
+  if (memcmp(key, ctx->temporalKey, sizeof key) != 0) ctx->temporalValid = false;
+  DeviceBuffer accum, mom, accOut, momOut, featTiles[4], featImage[4], out, rgba;
+  if (accum.reserve(nPix * sizeof(float4)) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess ||
+      accOut.reserve(nPix * sizeof(float4)) != hipSuccess || momOut.reserve(nPix * sizeof(float4)) != hipSuccess)
+    return fail(ctx, "temporal: hipMalloc");
+  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
+  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
+  void* dTiles[4];
+  const void* dPlanes[4];
+  for (int k = 0; k < 4; ++k) {
+    if (featTiles[k].reserve(tileBytes) != hipSuccess || featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess)
+      return fail(ctx, "temporal: hipMalloc");
+    dTiles[k] = featTiles[k].get();
+    dPlanes[k] = featImage[k].get();
+  }
+  for (auto& h : ctx->temporalHistory)
+    if (h.reserve(nPix * SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL) != hipSuccess) return fail(ctx, "temporal: hipMalloc history");
+  // the feature planes of the first p.spp samples: the rounds' reprojection needs them before the first decision
+  if (srtRenderFeatureTilesImpl(ctx, &p, SRT_FEATURE_ALL, dTiles, nullptr)) return 1;
+  for (int k = 0; k < 4; ++k)
+    if (srtResolveTiles(ctx, &p, dTiles[k], nullptr, featImage[k].get(), nullptr)) return 1;
+  const int next = ctx->temporalCurrent ^ 1;
+  const void* histIn = ctx->temporalValid ? ctx->temporalHistory[ctx->temporalCurrent].get() : nullptr;
+  void* histOut = ctx->temporalHistory[next].get();
+  ctx->temporalValid = false;  // until this frame's history is complete
+  if (srtRenderTemporalAdaptiveImpl(ctx, &p, ap, t, dPlanes, &ctx->temporalCam, histIn, accum.get(), mom.get(), accOut.get(),
+                                    momOut.get(), histOut, stats, nullptr))
+    return 1;
+  if (hDenoised || hRgba) {
+    if (srtDenoiseImpl(ctx, d, W, H, accOut.get(), dPlanes, out.get(), rgba.get(), nullptr, true, momOut.get())) return 1;
+  }
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "temporal: kernel failed: %s", hipGetErrorString(hipGetLastError()));
+  if (wfCheck(ctx)) return 1;
+  ctx->temporalCurrent = next;
+  ctx->temporalCam = ctx->camFull;
+  memcpy(ctx->temporalKey, key, sizeof key);
+  ctx->temporalValid = true;
+  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy accum");
+  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy denoised");
+  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy rgba");
   return 0;
 }
 
@@ -1393,6 +1531,22 @@ int srtTemporalAccumulate(SrtContext* ctx, const SrtTemporalParams* t, int32_t w
 int srtRenderTemporalFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, const SrtTemporalParams* t,
                            float* hAccum, float* hDenoised, uint8_t* hRgba, SrtTemporalStats* stats) {
   SRT_GUARDED(ctx, srtRenderTemporalFrameImpl(ctx, p, d, t, hAccum, hDenoised, hRgba, stats));
+}
+int srtTemporalReproject(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* const dPlanes[4],
+                         const SrtCamera* cam, const SrtCamera* prevCam, const void* dHistoryIn, void* dReprojected, void* stream) {
+  SRT_GUARDED(ctx, srtTemporalReprojectImpl(ctx, t, width, height, dPlanes, cam, prevCam, dHistoryIn, dReprojected, stream));
+}
+int srtRenderTemporalAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtTemporalParams* t,
+                              const void* const dPlanes[4], const SrtCamera* prevCam, const void* dHistoryIn, void* dAccumImage,
+                              void* dMomentsImage, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut,
+                              SrtTemporalAdaptiveStats* stats, void* stream) {
+  SRT_GUARDED(ctx, srtRenderTemporalAdaptiveImpl(ctx, p, ap, t, dPlanes, prevCam, dHistoryIn, dAccumImage, dMomentsImage, dBeautyOut,
+                                                 dMomentsOut, dHistoryOut, stats, stream));
+}
+int srtRenderTemporalAdaptiveFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtDenoiseParams* d,
+                                   const SrtTemporalParams* t, float* hAccum, float* hDenoised, uint8_t* hRgba,
+                                   SrtTemporalAdaptiveStats* stats) {
+  SRT_GUARDED(ctx, srtRenderTemporalAdaptiveFrameImpl(ctx, p, ap, d, t, hAccum, hDenoised, hRgba, stats));
 }
 int srtTemporalReset(SrtContext* ctx) {
   if (!ctx) return 1;

@@ -36,6 +36,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
+           "srtTemporalReproject", "srtRenderTemporalAdaptive", "srtRenderTemporalAdaptiveFrame",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -90,6 +91,15 @@ lib.srtRenderTemporalFrame.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.PO
                                        C.POINTER(abi.SrtTemporalParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.POINTER(C.c_uint8), C.POINTER(abi.SrtTemporalStats)]
 lib.srtTemporalReset.argtypes = [_vp]
+lib.srtTemporalReproject.argtypes = [_vp, C.POINTER(abi.SrtTemporalParams), C.c_int32, C.c_int32, C.POINTER(_vp),
+                                     C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtCamera), _vp, _vp, _vp]
+lib.srtRenderTemporalAdaptive.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtAdaptiveParams),
+                                          C.POINTER(abi.SrtTemporalParams), C.POINTER(_vp), C.POINTER(abi.SrtCamera), _vp, _vp,
+                                          _vp, _vp, _vp, _vp, C.POINTER(abi.SrtTemporalAdaptiveStats), _vp]
+lib.srtRenderTemporalAdaptiveFrame.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtAdaptiveParams),
+                                               C.POINTER(abi.SrtDenoiseParams), C.POINTER(abi.SrtTemporalParams),
+                                               C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8),
+                                               C.POINTER(abi.SrtTemporalAdaptiveStats)]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -382,6 +392,50 @@ class Context:
     def temporal_reset(self):
         """Drops the history srtRenderTemporalFrame keeps: the next frame starts over."""
         self._check(lib.srtTemporalReset(self.h))
+
+    def temporal_reproject(self, tparams, width, height, plane_ptrs, cam, prev_cam, d_history_in_ptr, d_reprojected_ptr,
+                           stream=None):
+        """srtTemporalReproject: the reprojected history h of temporal_accumulate, written once into DEVICE float4[2][W*H]
+        ({h.r, h.g, h.b, h.count} and {h.S1, h.S2, 0, has}); None / NULL history gives zeros."""
+        arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
+        self._check(lib.srtTemporalReproject(self.h, C.byref(tparams), int(width), int(height), arr, C.byref(cam),
+                                             C.byref(prev_cam) if prev_cam is not None else None, d_history_in_ptr,
+                                             d_reprojected_ptr, stream))
+
+    @classmethod
+    def _temporal_adaptive_stats(cls, st):
+        out = cls._adaptive_stats(st.adaptive)
+        out.update(historyPixels=int(st.temporal.historyPixels), meanHistoryCount=float(st.temporal.meanHistoryCount))
+        return out
+
+    def render_temporal_adaptive_device(self, params, aparams, tparams, plane_ptrs, prev_cam, d_history_in_ptr, d_accum_ptr,
+                                        d_moments_ptr, d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream=None):
+        """srtRenderTemporalAdaptive over DEVICE image-order buffers with the camera currently set: adaptive rounds that
+        decide on the frame's moments pooled with the reprojected history, then temporal_accumulate of the final sums.
+        Returns render_adaptive's stats dict plus "historyPixels" and "meanHistoryCount"; the work has finished."""
+        arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
+        st = abi.SrtTemporalAdaptiveStats()
+        self._check(lib.srtRenderTemporalAdaptive(self.h, C.byref(params), C.byref(aparams), C.byref(tparams), arr,
+                                                  C.byref(prev_cam) if prev_cam is not None else None, d_history_in_ptr,
+                                                  d_accum_ptr, d_moments_ptr, d_beauty_out_ptr, d_moments_out_ptr,
+                                                  d_history_out_ptr, C.byref(st), stream))
+        return self._temporal_adaptive_stats(st)
+
+    def render_temporal_adaptive_frame(self, params, aparams, dparams=None, tparams=None):
+        """One frame of a sequence with history-steered sampling (srtRenderTemporalAdaptiveFrame); interleaves with
+        render_temporal_frame on one context.  Returns (accum, denoised, rgba, stats): accum = this frame's own sums with
+        per-pixel counts; stats as render_temporal_adaptive_device's.  Advance params.sampleFirst by aparams.sppMax."""
+        dparams = abi.default_denoise_params() if dparams is None else dparams
+        tparams = abi.default_temporal_params() if tparams is None else tparams
+        W, H = params.imageWidth, params.imageHeight
+        accum, denoised = (np.zeros((H, W, 4), np.float32) for _ in range(2))
+        rgba = np.zeros((H, W, 4), np.uint8)
+        st = abi.SrtTemporalAdaptiveStats()
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtRenderTemporalAdaptiveFrame(self.h, C.byref(params), C.byref(aparams), C.byref(dparams),
+                                                       C.byref(tparams), accum.ctypes.data_as(fp), denoised.ctypes.data_as(fp),
+                                                       rgba.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+        return accum, denoised, rgba, self._temporal_adaptive_stats(st)
 
     def render_tiles(self, params, d_accum_ptr, stream=None):
         self._check(lib.srtRenderTiles(self.h, C.byref(params), d_accum_ptr, stream))

@@ -9,6 +9,9 @@
 //   rtFrameTemporal(denoised, ..., sampleFirst)  one frame of a sequence: rtFrameDenoised's frame accumulated onto the
 //                                           reprojected history of the previous call before it is denoised
 //                                           (include/srt_hip.h "Temporal accumulation"); temporalReset() starts over
+//   rtFrameTemporalAdaptive(denoised, ..., sppMax, thr, sampleFirst)  rtFrameTemporal with rtFrameAdaptive's rounds deciding
+//                                           on the frame's samples pooled with the reprojected history
+//                                           (include/srt_hip.h "Temporal-adaptive frames")
 //   rtFrameAdaptive(target, ..., sppMax, thr)  tile-adaptive sampling: numSamples everywhere, then more samples, doubling,
 //                                           for the tiles that have not converged (include/srt_hip.h "Adaptive sampling")
 //   terminate()
@@ -209,6 +212,41 @@ class hipDevice {
     const SrtTemporalParams tdefaults{};
     if (srtRenderTemporalFrame(ctx, &p, d ? d : &ddefaults, t ? t : &tdefaults, accum, denoised, static_cast<uint8_t*>(denoisedData),
                                stats) != 0)
+      return error();
+    (void)srtLastKernelMs(ctx, &lastKernelMs);
+    return true;
+  }
+
+  // rtFrameTemporal with history-steered sampling (include/srt_hip.h srtRenderTemporalAdaptiveFrame): numSamples (>= 2)
+  // samples everywhere from sampleFirst, then doubling rounds, up to sppMax samples a pixel, for the tiles whose samples and
+  // reprojected history together are not yet below the display-space standard error `threshold`.  Buffers, d and t as in
+  // rtFrameTemporal; accum carries per-pixel counts.  Callers advance sampleFirst by sppMax per frame.  Frames of both
+  // kinds may follow one another.  Single-process only.
+  bool rtFrameTemporalAdaptive(void* denoisedData, int w, int h, const camera& cam, const color3f& background, int numSamples,
+                               int maxBounce, int sppMax, float threshold, int sampleFirst, uint64_t seed = 1,
+                               const SrtDenoiseParams* d = nullptr, const SrtTemporalParams* t = nullptr, float* accum = nullptr,
+                               float* denoised = nullptr, SrtTemporalAdaptiveStats* stats = nullptr) {
+    if (!ctx) return false;
+    if (ranks > 1) {
+      std::cerr << "ERROR: rtFrameTemporalAdaptive renders on one GPU\n";
+      return false;
+    }
+    if (srtSetCamera(ctx, &cam.data()) != 0) return error();
+    SrtRenderParams p{};
+    p.imageWidth = w; p.imageHeight = h; p.spp = numSamples; p.maxBounce = maxBounce; p.seed = seed;
+    for (int i = 0; i < 3; ++i) p.background[i] = background(i);
+    p.tMin = 0.001f;  // main.cpp:39
+    p.traversal = SRT_TRAVERSE_FAITHFUL;
+    p.tileFirst = 0; p.tileStride = 1;
+    p.sppChunks = sppChunks;
+    p.sampleFirst = sampleFirst;
+    SrtAdaptiveParams a{};
+    a.sppMax = sppMax;
+    a.threshold = threshold;
+    const SrtDenoiseParams ddefaults{};
+    const SrtTemporalParams tdefaults{};
+    if (srtRenderTemporalAdaptiveFrame(ctx, &p, &a, d ? d : &ddefaults, t ? t : &tdefaults, accum, denoised,
+                                       static_cast<uint8_t*>(denoisedData), stats) != 0)
       return error();
     (void)srtLastKernelMs(ctx, &lastKernelMs);
     return true;
