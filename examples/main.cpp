@@ -5,20 +5,23 @@
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
 //                  [--denoise FILE.png [--sample-variance]] [--adaptive THRESHOLD --max-spp N]
-//                  [--frames N --orbit DEG [--temporal]]
+//                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
 //                     sample variance, srtRenderDenoisedImageMoments) instead of the spatial one
 //   --adaptive THRESHOLD --max-spp N  tile-adaptive sampling (hipDevice::rtFrameAdaptive): --spp samples everywhere, then
 //                     doubling rounds for the tiles whose display-space standard error is still >= THRESHOLD (1/256 = one
-//                     display step), up to N samples a pixel
+//                     display step), up to N samples a pixel.  With --denoise FILE.png the frame also goes through the
+//                     denoiser, guided by feature planes from every sample a tile got and by the sample variance
+//                     (hipDevice::rtFrameAdaptiveDenoised)
 //   --frames N --orbit D [--temporal]  a camera move of N frames over D degrees, NAME_%03d.png; --temporal accumulates
 //                     each frame onto the reprojected history of the one before it
 //   --frames N --orbit D --temporal --adaptive THRESHOLD --max-spp M  the same with history-steered sampling
 //                     (hipDevice::rtFrameTemporalAdaptive): the adaptive rounds decide on each tile's samples pooled with
 //                     its history, so disoccluded tiles get up to M samples and settled ones stop at --spp; frame k
-//                     draws its samples from k * M
+//                     draws its samples from k * M.  --guide-all-samples: the feature planes follow the rounds, so the
+//                     accumulation, the history and the denoiser are guided by all of a tile's samples, not its first --spp
 //   SRT_DATA_DIR selects the directory of the glTF's images (default "../data/", as the reference).
 #include <chrono>
 #include <cstdlib>
@@ -87,12 +90,12 @@ int main(int argc, char** argv) {
   int imageHeight = 720, numSamples = 5000, maxBounce = 4, chunks = 0, maxSpp = 0;
   float adaptive = -1.0f;  // < 0: a uniform frame
   std::string out = "test.png", features, denoise;
-  bool sampleVariance = false, temporal = false;
+  bool sampleVariance = false, temporal = false, guideAll = false;
   int frames = 0;        // > 0: a sequence, NAME_%03d.png
   float orbit = 0.0f;    // degrees the eye turns about the lookAt point's vertical axis over the sequence
   for (int i = 1; i < argc; i += 2) {
-    if (!strcmp(argv[i], "--sample-variance") || !strcmp(argv[i], "--temporal")) {  // the flags without a value
-      (argv[i][2] == 't' ? temporal : sampleVariance) = true;
+    if (!strcmp(argv[i], "--sample-variance") || !strcmp(argv[i], "--temporal") || !strcmp(argv[i], "--guide-all-samples")) {
+      (argv[i][2] == 't' ? temporal : argv[i][2] == 'g' ? guideAll : sampleVariance) = true;  // the flags without a value
       --i;
       continue;
     }
@@ -142,7 +145,7 @@ int main(int argc, char** argv) {
       if (steered) {
         SrtTemporalAdaptiveStats st{};
         if (!device.rtFrameTemporalAdaptive(frame.data(), imageWidth, imageHeight, cam, background, numSamples, maxBounce, sppMax,
-                                            adaptive, k * sppMax, 1, nullptr, nullptr, nullptr, nullptr, &st))
+                                            adaptive, k * sppMax, 1, nullptr, nullptr, nullptr, nullptr, &st, guideAll))
           return 1;
         std::cerr << "frame " << k << ": " << (double)st.adaptive.pixelSamples / ((double)imageWidth * imageHeight)
                   << " samples per pixel in " << st.adaptive.rounds << " rounds\n";
@@ -173,13 +176,16 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> denoised;
   SrtAdaptiveStats adaptiveStats{};
   if (adaptive >= 0.0f) {
-    if (!denoise.empty()) {
-      std::cerr << "ERROR: --adaptive does not combine with --denoise\n";
+    if (!denoise.empty()) {  // one adaptive render: the noisy frame and the denoised one
+      denoised.resize((size_t)4 * imageWidth * imageHeight);
+      if (!device.rtFrameAdaptiveDenoised(target, denoised.data(), imageWidth, imageHeight, mainCamera, background, numSamples,
+                                          maxBounce, maxSpp > 0 ? maxSpp : numSamples, adaptive, 1, nullptr, nullptr, nullptr,
+                                          &adaptiveStats))
+        return 1;
+    } else if (!device.rtFrameAdaptive(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce,
+                                       maxSpp > 0 ? maxSpp : numSamples, adaptive, 1, nullptr, &adaptiveStats)) {
       return 1;
     }
-    if (!device.rtFrameAdaptive(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce,
-                                maxSpp > 0 ? maxSpp : numSamples, adaptive, 1, nullptr, &adaptiveStats))
-      return 1;
   } else if (denoise.empty()) {
     if (!device.rtFrame(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
   } else {  // one render: the noisy frame and the denoised one

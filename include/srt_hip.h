@@ -346,6 +346,26 @@ enum { SRT_FEATURE_ALBEDO = 1, SRT_FEATURE_NORMAL = 2, SRT_FEATURE_POSITION = 4,
 int srtRenderFeatureTiles(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* stream);
 int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, float* const hPlanes[4]);
 
+/* Feature pass over a tile list: the planes above for the listed tiles only, written straight into IMAGE-ORDER planes.
+ * dTileList = DEVICE uint32[numListed], entry i = tx | ty << 16, the tile whose pixels are x in [8 tx, 8 tx + 8), y in
+ * [8 ty, 8 ty + 8) (the format of the adaptive rounds' lists; any order).  dPlaneImages[k] = DEVICE float4[W*H] for every
+ * selected bit 1 << k, ignored (may be NULL) otherwise.  For every in-image pixel i = y W + x of a listed tile and every
+ * selected plane, with F = {xyz = the float running sum over the samples [sampleFirst, sampleFirst + spp) that count, in
+ * sample-index order starting from 0; w = how many counted} -- exactly the record srtRenderFeatureTiles forms for that pixel:
+ *   accumulate == 0:  plane[i] = F
+ *   accumulate != 0:  plane[i] = {plane[i].x + F.x, plane[i].y + F.y, plane[i].z + F.z, plane[i].w + F.w}, one float add per
+ *                     channel
+ * Pixels of tiles that are not listed, and the padding of edge tiles (x >= W or y >= H), are neither read nor written.  An
+ * entry with tx >= ceil(W / 8) or ty >= ceil(H / 8) is skipped whole.  A tile listed twice is a caller error (its two passes
+ * race).  The full tile table with accumulate == 0 equals srtRenderFeatureTiles + srtResolveTiles(..., dAccumImage) bit for
+ * bit.  Asynchronous on `stream`: one kernel and the memset of its counter; numListed == 0 returns 0 and launches nothing.
+ * Errors (non-zero, message in srtLastError, nothing launched): what srtRenderFeatureTiles rejects, tileFirst != 0 or
+ * tileStride != 1, numListed < 0 or > srtNumTiles, a NULL list with numListed > 0.  Side effects are the feature pass's: none
+ * on the tunables, the host generator, the chunk scratch, srtLastKernelMs or srtGetLaunchInfo.  Device memory: nothing beyond
+ * the feature pass's counter. */
+int srtRenderFeatureTileList(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList, int32_t numListed,
+                             void* const dPlaneImages[4], int32_t accumulate, void* stream);
+
 /* Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) in the spatial form of SVGF, guided by the
  * feature planes' normals and depths, luminance-stopped by a variance estimate carried from level to level, optionally
  * demodulated by albedo.  It works on one frame; the temporal part is srtTemporalAccumulate below, which feeds it buffers in
@@ -485,6 +505,29 @@ int srtRenderAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdapti
                       void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* stream);
 int srtRenderAdaptiveImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, float* hAccum,
                            float* hMoments, uint8_t* hRgba, SrtAdaptiveStats* stats);
+
+/* Adaptive sampling with guide planes from every sample: srtRenderAdaptive whose feature planes follow the rounds.  After
+ * launch r the same tile list and the same sample range [sampleFirst + n_{r-1}, sampleFirst + n_r) go through
+ * srtRenderFeatureTileList: round 0 over the whole frame with accumulate = 0, launch r >= 1 over its list with accumulate = 1.
+ *   planes    image-order sums with per-pixel counts, ((pass0 + pass1) + pass2) + ... per pixel and channel, as the beauty;
+ *             round 0 equals srtRenderFeatureTiles + srtResolveTiles of p bit for bit, so threshold = +inf or sppMax == spp
+ *             gives the plain feature sums of p.  ALBEDO's w (every sample counts) equals the beauty's w on every pixel
+ *   beauty, moments, RGBA, stats and the decisions are srtRenderAdaptive's bit for bit: the planes are never read
+ * srtRenderAdaptiveGuided         planes / dPlaneImages as srtRenderFeatureTileList (any non-empty subset), the rest as
+ *                                 srtRenderAdaptive; returns after all of its work has finished.
+ * srtRenderAdaptiveDenoisedImage  blocking, HOST buffers, each may be NULL: srtRenderAdaptiveGuided with all four planes, then
+ *                                 srtDenoiseMoments (parameters d) on its sums, moments and planes.  hAccum, hMoments as
+ *                                 srtRenderAdaptiveImage; hDenoised (rgb = the denoised mean, w = the pixel's count) and hRgba
+ *                                 (of the denoised mean) as srtRenderDenoisedImageMoments, which threshold = +inf reproduces
+ *                                 in every byte.
+ * Errors (nothing launched): what srtRenderAdaptive, srtRenderFeatureTileList and (the image entry) srtDenoiseMoments reject.
+ * Side effects as srtRenderAdaptive.  Device memory held by the context: srtRenderAdaptive's; nothing new beyond the feature
+ * pass's counter. */
+int srtRenderAdaptiveGuided(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, int32_t planes,
+                            void* const dPlaneImages[4], void* dAccumImage, void* dMomentsImage, void* dRgba,
+                            SrtAdaptiveStats* stats, void* stream);
+int srtRenderAdaptiveDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtDenoiseParams* d,
+                                   float* hAccum, float* hMoments, float* hDenoised, uint8_t* hRgba, SrtAdaptiveStats* stats);
 
 /* Temporal accumulation: the temporal half of SVGF (Schied et al. 2017) in front of the denoiser above.  The previous
  * frame's accumulated radiance and luminance moments are reprojected onto the current camera, kept where the surface is
@@ -655,6 +698,30 @@ int srtRenderTemporalAdaptive(SrtContext* ctx, const SrtRenderParams* p, const S
 int srtRenderTemporalAdaptiveFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtDenoiseParams* d,
                                    const SrtTemporalParams* t, float* hAccum, float* hDenoised, uint8_t* hRgba,
                                    SrtTemporalAdaptiveStats* stats);
+
+/* Temporal-adaptive frames with guide planes from every sample: the two entries above, except that the rounds extend the
+ * feature planes.  dPlanes is IN/OUT in the device form: in = the resolved planes of the first p->spp samples, as above.
+ *   decisions   the reprojected history h and every round's pooled decision read the planes of the first p->spp samples, as
+ *             in the unguided entries (h is computed once, before the rounds; with demodulate the decisions read a copy of
+ *             the incoming ALBEDO plane).  This frame's sums, stats->adaptive.roundTiles and pixelSamples are therefore the
+ *             unguided entry's bit for bit
+ *   planes    after launch r >= 1 its list and sample range go through srtRenderFeatureTileList with accumulate = 1 on every
+ *             non-NULL plane: out = in + pass1 + pass2 + ... in that order, per-pixel counts in w
+ *   end       dBeautyOut, dMomentsOut and dHistoryOut are srtTemporalAccumulate of the final sums with the EXTENDED planes:
+ *             the closing accumulation recomputes its reprojection and acceptance from the extended means (so a pixel's
+ *             accepted taps may differ from the ones h had), and the new history's normal and position describe all of a
+ *             tile's samples.  In the frame entry srtDenoiseMoments reads the extended planes as well
+ * threshold = +inf or sppMax == spp is the unguided entry in every byte.  Guided and unguided (and uniform) frames share the
+ * context's histories, ping-pong and reset rules, so they may follow one another.  Errors and side effects are the unguided
+ * entries'.  Device memory: nothing new is held by the context beyond the feature pass's counter; with demodulate the
+ * device entry takes 16 bytes per pixel for the ALBEDO copy and releases them before it returns. */
+int srtRenderTemporalAdaptiveGuided(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                    const SrtTemporalParams* t, void* const dPlanes[4], const SrtCamera* prevCam,
+                                    const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
+                                    void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* stream);
+int srtRenderTemporalAdaptiveGuidedFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                         const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum, float* hDenoised,
+                                         uint8_t* hRgba, SrtTemporalAdaptiveStats* stats);
 
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the

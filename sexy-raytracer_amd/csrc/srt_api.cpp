@@ -31,6 +31,9 @@ int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hit
                        hipStream_t stream);
 int srt_features_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU);
 int srt_launch_features(const FeatureArgs* a, int closest, int ldsTree, int grid, size_t lds, hipStream_t stream);
+int srt_features_list_plan(int closest, int ldsTree, int accumulate, size_t lds, int* block, int* perCU);
+int srt_launch_features_list(const FeatureListArgs* a, int closest, int ldsTree, int accumulate, int grid, size_t lds,
+                             hipStream_t stream);
 int srt_launch_denoise(const DenoiseArgs* a, int iterations, int ldsMaxStep, hipStream_t stream);
 int srt_launch_adaptive_update(const uint32_t* list, int count, const float4* beautyTiles, const float4* momentTiles,
                                float4* accum, float4* moments, int32_t* flags, int width, int height, double limit,
@@ -86,7 +89,7 @@ struct SrtContext {
   DeviceBuffer attScratch;  // LDS-resident-tree kernel: the lanes' attenuation stacks (srt_render_kernel LDSTREE)
   DeviceBuffer wfPool, wfAttHi;  // path-pool kernel: contexts and upper attenuation levels (srt_wavefront.hip)
   int32_t* dWfError = nullptr;
-  DeviceBuffer dFeatureCounter;  // the feature pass's tile counter (its own: a render's queues are never touched)
+  DeviceBuffer dFeatureCounter;  // the feature passes' tile counter (their own: a render's queues are never touched)
   DeviceBuffer denoiseScratch;   // srtDenoise: guide records, depth gradients, two colour buffers (56 B per pixel)
   DeviceBuffer tileTable;   // RenderArgs::tileXY for the image size and tile order below
   // srtRenderAdaptive: one launch's beauty and moments tiles, two tile lists (this launch's, the next one's), the per-tile
@@ -843,10 +846,23 @@ struct AdaptivePool {
   const float4* albedo;       // null unless the history is demodulated
 };
 
+// srtRenderAdaptiveGuided / srtRenderTemporalAdaptiveGuided: image-order feature planes that follow the rounds
+// (srt_features_list.hip): after launch r its list and sample range go through the list kernel
+struct AdaptiveGuides {
+  int32_t planes;       // SRT_FEATURE_* bits
+  void* const* images;  // [4], float4[W*H] for every selected bit
+  bool storeFirst;      // round 0 is stored over the whole tile table; false: the planes hold round 0 already
+};
+
+static int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* const* buffers);
+static int srtRenderFeatureTileListImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList,
+                                        int32_t numListed, void* const dPlaneImages[4], int32_t accumulate, void* streamPtr);
+
 static int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap, void* dAccumImage,
                                  void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* streamPtr,
-                                 const AdaptivePool* pool = nullptr) {
+                                 const AdaptivePool* pool = nullptr, const AdaptiveGuides* guides = nullptr) {
   if (checkAdaptive(ctx, pIn, ap, true, dAccumImage, dMomentsImage)) return 1;
+  if (guides && checkFeatureArgs(ctx, pIn, guides->planes, guides->images)) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
   const SrtRenderParams p0 = *pIn;
@@ -889,6 +905,10 @@ static int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, co
         return 1;
       list = ctx->tileTable.get<const uint32_t>();  // built for this size by the launch above
     }
+    // the guide planes of the same tiles over the same samples: stored in round 0, added from round 1 on
+    if (guides && (r > 0 || guides->storeFirst) &&
+        srtRenderFeatureTileListImpl(ctx, &q, guides->planes, list, listTiles, guides->images, r > 0, stream))
+      return 1;
     if (pool && decide)
       rc = srt_launch_temporal_adaptive_update(list, listTiles, beautyTiles, momentTiles, accum, moments, pool->reprojected,
                                                pool->albedo, ctx->adaptFlags.get<int32_t>(), W, H, limit, r > 0, stream);
@@ -1038,10 +1058,23 @@ int srtRenderAdaptiveImage(SrtContext* ctx, const SrtRenderParams* p, const SrtA
                            uint8_t* hRgba, SrtAdaptiveStats* stats) {
   SRT_GUARDED(ctx, srtRenderAdaptiveImageImpl(ctx, p, ap, hAccum, hMoments, hRgba, stats));
 }
+static int srtRenderAdaptiveGuidedImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, int32_t planes,
+                                       void* const dPlaneImages[4], void* dAccumImage, void* dMomentsImage, void* dRgba,
+                                       SrtAdaptiveStats* stats, void* stream) {
+  if (!ctx) return 1;
+  const AdaptiveGuides guides{planes, dPlaneImages, true};
+  return srtRenderAdaptiveImpl(ctx, p, ap, dAccumImage, dMomentsImage, dRgba, stats, stream, nullptr, &guides);
+}
+int srtRenderAdaptiveGuided(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, int32_t planes,
+                            void* const dPlaneImages[4], void* dAccumImage, void* dMomentsImage, void* dRgba,
+                            SrtAdaptiveStats* stats, void* stream) {
+  SRT_GUARDED(ctx, srtRenderAdaptiveGuidedImpl(ctx, p, ap, planes, dPlaneImages, dAccumImage, dMomentsImage, dRgba, stats, stream));
+}
 
 /* Feature pass (srt_features.hip).  Reads the scene, the camera and the tile_block tunable; writes only the caller's planes
  * and its own tile counter, so a later render sees the context as it was. */
 static int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* const* buffers) {
+  if (!ctx) return 1;
   if (!p) return fail(ctx, "features: null parameters");
   if (planes <= 0 || (planes & ~SRT_FEATURE_ALL) != 0) return fail(ctx, "features: bad plane mask 0x%x", (unsigned)planes);
   SrtRenderParams q = *p;  // maxBounce, sppChunks and countStats do not apply
@@ -1124,6 +1157,49 @@ int srtRenderFeatureTiles(SrtContext* ctx, const SrtRenderParams* p, int32_t pla
 }
 int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, float* const hPlanes[4]) {
   SRT_GUARDED(ctx, srtRenderFeatureImageImpl(ctx, p, planes, hPlanes));
+}
+
+/* Feature pass over a tile list (srt_features_list.hip), into image-order planes.  The feature pass's side effects: its own
+ * counter and the caller's planes. */
+static int srtRenderFeatureTileListImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList,
+                                        int32_t numListed, void* const dPlaneImages[4], int32_t accumulate, void* streamPtr) {
+  if (!ctx) return 1;
+  if (checkFeatureArgs(ctx, p, planes, dPlaneImages)) return 1;
+  if (p->tileFirst != 0 || p->tileStride != 1) return fail(ctx, "features: a tile list covers the whole image (tileFirst 0, tileStride 1)");
+  if (numListed < 0 || numListed > srtNumTiles(p->imageWidth, p->imageHeight))
+    return fail(ctx, "features: bad tile list of %d tiles", numListed);
+  if (numListed > 0 && !dTileList) return fail(ctx, "features: null tile list");
+  if (numListed == 0) return 0;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+  const DevScene& sc = ctx->scene;
+  FeatureListArgs a;
+  setImageArgs(a.f, ctx, p);
+  a.f.planes = planes;
+  for (int k = 0; k < 4; ++k) a.f.out[k] = (planes >> k & 1) ? static_cast<float4*>(dPlaneImages[k]) : nullptr;
+  a.list = static_cast<const uint32_t*>(dTileList);
+  a.numListed = numListed;
+  // the traversal form and its LDS exactly as srtRenderFeatureTiles chooses them
+  const bool closest = p->traversal == SRT_TRAVERSE_CLOSEST;
+  const size_t treeBytes = (size_t)sc.numNodes * 32;
+  const bool ldsTree = !closest && sc.nodeThread != nullptr && treeBytes <= 160 * 1024;
+  const size_t lds = ldsTree ? treeBytes : (size_t)std::max(sc.stackDepth, 1) * SRT_BLOCK * sizeof(int32_t);
+  if (lds > 160 * 1024) return fail(ctx, "features: BVH depth %d needs %zu B of LDS per workgroup", sc.stackDepth, lds);
+  int block = 0, perCU = 1;
+  int rc = srt_features_list_plan(closest, ldsTree, accumulate != 0, lds, &block, &perCU);
+  if (rc) return fail(ctx, "features: kernel setup failed: %s", hipGetErrorString((hipError_t)rc));
+  const int wavesPerGroup = block / 64;
+  const int grid = std::max(1, std::min(ctx->prop.multiProcessorCount * perCU, (numListed + wavesPerGroup - 1) / wavesPerGroup));
+  HIP_OK(ctx, ctx->dFeatureCounter.reserve(16 * sizeof(int32_t)));
+  a.f.counter = ctx->dFeatureCounter.get<int32_t>();
+  HIP_OK(ctx, hipMemsetAsync(a.f.counter, 0, sizeof(int32_t), stream));
+  rc = srt_launch_features_list(&a, closest, ldsTree, accumulate != 0, grid, lds, stream);
+  if (rc) return fail(ctx, "features launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+int srtRenderFeatureTileList(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList, int32_t numListed,
+                             void* const dPlaneImages[4], int32_t accumulate, void* stream) {
+  SRT_GUARDED(ctx, srtRenderFeatureTileListImpl(ctx, p, planes, dTileList, numListed, dPlaneImages, accumulate, stream));
 }
 
 /* Denoiser (srt_denoise.hip).  Reads the tunable denoise_lds_step; writes only the caller's outputs and its own scratch. */
@@ -1254,6 +1330,46 @@ int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width,
 int srtRenderDenoisedImageMoments(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
                                   float* hMoments, float* hDenoised, uint8_t* hRgba) {
   SRT_GUARDED(ctx, srtRenderDenoisedImageImpl(ctx, p, d, hAccum, hDenoised, hRgba, true, hMoments));
+}
+
+// srtRenderAdaptiveDenoisedImage: the guided adaptive render with all four planes, srtDenoiseMoments on its sums
+static int srtRenderAdaptiveDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                              const SrtDenoiseParams* d, float* hAccum, float* hMoments, float* hDenoised,
+                                              uint8_t* hRgba, SrtAdaptiveStats* stats) {
+  if (!ctx) return 1;
+  if (checkAdaptive(ctx, p, ap, false, nullptr, nullptr)) return 1;
+  DenoiseArgs check;
+  int iterations = 0;
+  if (checkDenoiseParams(ctx, d, p->imageWidth, p->imageHeight, check, iterations, true)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const int W = p->imageWidth, H = p->imageHeight;
+  const size_t nPix = (size_t)W * H;
+  DeviceBuffer accum, mom, featImage[4], out, rgba;
+  if (accum.reserve(nPix * sizeof(float4)) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess)
+    return fail(ctx, "denoise: hipMalloc");
+  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
+  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
+  void* dPlanes[4];
+  for (int k = 0; k < 4; ++k) {
+    if (featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
+    dPlanes[k] = featImage[k].get();
+  }
+  const AdaptiveGuides guides{SRT_FEATURE_ALL, dPlanes, true};
+  if (srtRenderAdaptiveImpl(ctx, p, ap, accum.get(), mom.get(), nullptr, stats, nullptr, nullptr, &guides)) return 1;
+  if (hDenoised || hRgba) {
+    if (srtDenoiseImpl(ctx, d, W, H, accum.get(), dPlanes, out.get(), rgba.get(), nullptr, true, mom.get())) return 1;
+  }
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "denoise: kernel failed: %s", hipGetErrorString(hipGetLastError()));
+  if (wfCheck(ctx)) return 1;
+  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy accum");
+  if (hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy moments");
+  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy denoised");
+  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy rgba");
+  return 0;
+}
+int srtRenderAdaptiveDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtDenoiseParams* d,
+                                   float* hAccum, float* hMoments, float* hDenoised, uint8_t* hRgba, SrtAdaptiveStats* stats) {
+  SRT_GUARDED(ctx, srtRenderAdaptiveDenoisedImageImpl(ctx, p, ap, d, hAccum, hMoments, hDenoised, hRgba, stats));
 }
 
 /* Temporal accumulation (srt_temporal.hip).  Reads nothing of the context but the device ordinal; the frame entry keeps
@@ -1433,8 +1549,10 @@ static int srtTemporalReprojectImpl(SrtContext* ctx, const SrtTemporalParams* t,
 static int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
                                          const SrtTemporalParams* t, const void* const dPlanes[4], const SrtCamera* prevCam,
                                          const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
-                                         void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* streamPtr) {
+                                         void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* streamPtr,
+                                         bool guided = false) {
   // every check of both halves before the first launch
+  if (!ctx) return 1;
   if (checkAdaptive(ctx, p, ap, true, dAccumImage, dMomentsImage)) return 1;
   const int W = p->imageWidth, H = p->imageHeight;
   const size_t nPix = (size_t)W * H;
@@ -1449,10 +1567,24 @@ static int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams*
   ra.historyOut = ctx->temporalReprojected.get<float4>();
   int rc = srt_launch_temporal_reproject(&ra, stream);
   if (rc) return fail(ctx, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)rc));
-  const AdaptivePool pool{ctx->temporalReprojected.get<const float4>(), a.albedo};
+  AdaptivePool pool{ctx->temporalReprojected.get<const float4>(), a.albedo};
   SrtTemporalAdaptiveStats st;
   memset(&st, 0, sizeof st);
-  if (srtRenderAdaptiveImpl(ctx, p, ap, dAccumImage, dMomentsImage, nullptr, &st.adaptive, streamPtr, &pool)) return 1;
+  // guided: the rounds from 1 on extend the caller's planes (they hold round 0).  The pooled decisions keep reading the
+  // ALBEDO means of the first p->spp samples -- h was formed beside them -- from a copy that lives as long as this call
+  AdaptiveGuides guides{0, const_cast<void* const*>(dPlanes), false};
+  DeviceBuffer albedoFirst;
+  if (guided) {
+    for (int k = 0; k < 4; ++k)
+      if (dPlanes[k]) guides.planes |= 1 << k;
+    if (a.albedo) {
+      if (albedoFirst.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
+      HIP_OK(ctx, hipMemcpyAsync(albedoFirst.get(), a.albedo, nPix * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+      pool.albedo = albedoFirst.get<const float4>();
+    }
+  }
+  if (srtRenderAdaptiveImpl(ctx, p, ap, dAccumImage, dMomentsImage, nullptr, &st.adaptive, streamPtr, &pool, guided ? &guides : nullptr))
+    return 1;
   rc = srt_launch_temporal(&a, stream);
   if (rc) return fail(ctx, "temporal launch failed: %s", hipGetErrorString((hipError_t)rc));
   if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "temporal: kernel failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1465,7 +1597,8 @@ static int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams*
 
 static int srtRenderTemporalAdaptiveFrameImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap,
                                               const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum,
-                                              float* hDenoised, uint8_t* hRgba, SrtTemporalAdaptiveStats* stats) {
+                                              float* hDenoised, uint8_t* hRgba, SrtTemporalAdaptiveStats* stats,
+                                              bool guided = false) {
   if (!ctx) return 1;
   if (checkAdaptive(ctx, pIn, ap, false, nullptr, nullptr)) return 1;
   DenoiseArgs dcheck;
@@ -1505,7 +1638,7 @@ static int srtRenderTemporalAdaptiveFrameImpl(SrtContext* ctx, const SrtRenderPa
   void* histOut = ctx->temporalHistory[next].get();
   ctx->temporalValid = false;  // until this frame's history is complete
   if (srtRenderTemporalAdaptiveImpl(ctx, &p, ap, t, dPlanes, &ctx->temporalCam, histIn, accum.get(), mom.get(), accOut.get(),
-                                    momOut.get(), histOut, stats, nullptr))
+                                    momOut.get(), histOut, stats, nullptr, guided))
     return 1;
   if (hDenoised || hRgba) {
     if (srtDenoiseImpl(ctx, d, W, H, accOut.get(), dPlanes, out.get(), rgba.get(), nullptr, true, momOut.get())) return 1;
@@ -1547,6 +1680,18 @@ int srtRenderTemporalAdaptiveFrame(SrtContext* ctx, const SrtRenderParams* p, co
                                    const SrtTemporalParams* t, float* hAccum, float* hDenoised, uint8_t* hRgba,
                                    SrtTemporalAdaptiveStats* stats) {
   SRT_GUARDED(ctx, srtRenderTemporalAdaptiveFrameImpl(ctx, p, ap, d, t, hAccum, hDenoised, hRgba, stats));
+}
+int srtRenderTemporalAdaptiveGuided(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                    const SrtTemporalParams* t, void* const dPlanes[4], const SrtCamera* prevCam,
+                                    const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
+                                    void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* stream) {
+  SRT_GUARDED(ctx, srtRenderTemporalAdaptiveImpl(ctx, p, ap, t, dPlanes, prevCam, dHistoryIn, dAccumImage, dMomentsImage, dBeautyOut,
+                                                 dMomentsOut, dHistoryOut, stats, stream, true));
+}
+int srtRenderTemporalAdaptiveGuidedFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                         const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum, float* hDenoised,
+                                         uint8_t* hRgba, SrtTemporalAdaptiveStats* stats) {
+  SRT_GUARDED(ctx, srtRenderTemporalAdaptiveFrameImpl(ctx, p, ap, d, t, hAccum, hDenoised, hRgba, stats, true));
 }
 int srtTemporalReset(SrtContext* ctx) {
   if (!ctx) return 1;

@@ -209,6 +209,14 @@ struct FeatureArgs {
   int32_t* counter;   // next local tile to take (zeroed before launch)
 };
 
+// srtRenderFeatureTileList (srt_features_list.hip): the feature pass of the listed tiles, into image-order planes.  Of f,
+// tileFirst, tileStride, numLocalTiles, numTiles and tileBlock are not read; f.out[k] = float4[W*H] in image order.
+struct FeatureListArgs {
+  FeatureArgs f;
+  const uint32_t* list;  // tx | ty << 16 per listed tile (RenderArgs::tileXY's format)
+  int32_t numListed;     // f.counter: the next list position to take (zeroed before launch)
+};
+
 // srtDenoise (srt_denoise.hip): the edge-aware a-trous filter over image-order planes.  Scratch in the context, 56 B per
 // pixel: guide, gradient and the two colour buffers.
 struct DenoiseArgs {

@@ -37,6 +37,8 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
            "srtTemporalReproject", "srtRenderTemporalAdaptive", "srtRenderTemporalAdaptiveFrame",
+           "srtRenderFeatureTileList", "srtRenderAdaptiveGuided", "srtRenderAdaptiveDenoisedImage",
+           "srtRenderTemporalAdaptiveGuided", "srtRenderTemporalAdaptiveGuidedFrame",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -100,6 +102,15 @@ lib.srtRenderTemporalAdaptiveFrame.argtypes = [_vp, C.POINTER(abi.SrtRenderParam
                                                C.POINTER(abi.SrtDenoiseParams), C.POINTER(abi.SrtTemporalParams),
                                                C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8),
                                                C.POINTER(abi.SrtTemporalAdaptiveStats)]
+lib.srtRenderFeatureTileList.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp, C.c_int32, C.POINTER(_vp), C.c_int32,
+                                         _vp]
+lib.srtRenderAdaptiveGuided.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtAdaptiveParams), C.c_int32,
+                                        C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(abi.SrtAdaptiveStats), _vp]
+lib.srtRenderAdaptiveDenoisedImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(abi.SrtAdaptiveParams),
+                                               C.POINTER(abi.SrtDenoiseParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(abi.SrtAdaptiveStats)]
+lib.srtRenderTemporalAdaptiveGuided.argtypes = lib.srtRenderTemporalAdaptive.argtypes
+lib.srtRenderTemporalAdaptiveGuidedFrame.argtypes = lib.srtRenderTemporalAdaptiveFrame.argtypes
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -299,6 +310,34 @@ class Context:
                                           C.byref(st), stream))
         return self._adaptive_stats(st)
 
+    def render_adaptive_guided_device(self, params, aparams, planes, plane_ptrs, d_accum_ptr, d_moments_ptr, d_rgba_ptr=None,
+                                      stream=None):
+        """srtRenderAdaptiveGuided: render_adaptive_device whose guide planes follow the rounds.  plane_ptrs[k] = DEVICE
+        image-order float4[W*H] for every selected bit 1 << k (None otherwise): sums over all of a pixel's samples with
+        per-pixel counts.  Returns the stats dict; the work has finished when it returns."""
+        arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
+        st = abi.SrtAdaptiveStats()
+        self._check(lib.srtRenderAdaptiveGuided(self.h, C.byref(params), C.byref(aparams), int(planes), arr, d_accum_ptr,
+                                                d_moments_ptr, d_rgba_ptr, C.byref(st), stream))
+        return self._adaptive_stats(st)
+
+    def render_adaptive_denoised(self, params, aparams, dparams=None):
+        """Adaptive render, guide planes from every sample and the moments-driven denoiser on one frame
+        (srtRenderAdaptiveDenoisedImage).  Returns (accum, moments, denoised, rgba, stats): accum, moments and stats as
+        render_adaptive's, denoised and rgba as render_denoised_moments's."""
+        if dparams is None:
+            dparams = abi.default_denoise_params()
+        W, H = params.imageWidth, params.imageHeight
+        accum, moments, denoised = (np.zeros((H, W, 4), np.float32) for _ in range(3))
+        rgba = np.zeros((H, W, 4), np.uint8)
+        st = abi.SrtAdaptiveStats()
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtRenderAdaptiveDenoisedImage(self.h, C.byref(params), C.byref(aparams), C.byref(dparams),
+                                                       accum.ctypes.data_as(fp), moments.ctypes.data_as(fp),
+                                                       denoised.ctypes.data_as(fp), rgba.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       C.byref(st)))
+        return accum, moments, denoised, rgba, self._adaptive_stats(st)
+
     def render_features(self, params, planes=abi.SRT_FEATURE_ALL):
         """Feature pass (include/srt_hip.h srtRenderFeatureImage): the first hit of the beauty render's camera rays.
         Returns {plane name: (H, W, 4) float32}, xyz = the mean over the samples that counted (0 where none did), w = their
@@ -318,6 +357,14 @@ class Context:
         1 << k (None otherwise)."""
         arr = (_vp * 4)(*[(p if p else None) for p in list(ptrs) + [None] * (4 - len(ptrs))])
         self._check(lib.srtRenderFeatureTiles(self.h, C.byref(params), int(planes), arr, stream))
+
+    def render_feature_tile_list(self, params, planes, d_list_ptr, num_listed, plane_ptrs, accumulate=False, stream=None):
+        """Asynchronous feature pass over a DEVICE tile list (srtRenderFeatureTileList): d_list_ptr = uint32[num_listed],
+        tx | ty << 16 per tile; plane_ptrs[k] = DEVICE image-order float4[W*H] for every selected bit 1 << k (None
+        otherwise), stored, or added to when `accumulate` is set."""
+        arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
+        self._check(lib.srtRenderFeatureTileList(self.h, C.byref(params), int(planes), d_list_ptr, int(num_listed), arr,
+                                                 1 if accumulate else 0, stream))
 
     def denoise(self, dparams, width, height, d_beauty_ptr, plane_ptrs, d_out_ptr=None, d_rgba_ptr=None, stream=None,
                 d_moments_ptr=None):
@@ -409,22 +456,32 @@ class Context:
         return out
 
     def render_temporal_adaptive_device(self, params, aparams, tparams, plane_ptrs, prev_cam, d_history_in_ptr, d_accum_ptr,
-                                        d_moments_ptr, d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream=None):
+                                        d_moments_ptr, d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream=None,
+                                        entry=None):
         """srtRenderTemporalAdaptive over DEVICE image-order buffers with the camera currently set: adaptive rounds that
         decide on the frame's moments pooled with the reprojected history, then temporal_accumulate of the final sums.
         Returns render_adaptive's stats dict plus "historyPixels" and "meanHistoryCount"; the work has finished."""
         arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
         st = abi.SrtTemporalAdaptiveStats()
-        self._check(lib.srtRenderTemporalAdaptive(self.h, C.byref(params), C.byref(aparams), C.byref(tparams), arr,
-                                                  C.byref(prev_cam) if prev_cam is not None else None, d_history_in_ptr,
-                                                  d_accum_ptr, d_moments_ptr, d_beauty_out_ptr, d_moments_out_ptr,
-                                                  d_history_out_ptr, C.byref(st), stream))
+        entry = lib.srtRenderTemporalAdaptive if entry is None else entry
+        self._check(entry(self.h, C.byref(params), C.byref(aparams), C.byref(tparams), arr,
+                          C.byref(prev_cam) if prev_cam is not None else None, d_history_in_ptr, d_accum_ptr, d_moments_ptr,
+                          d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, C.byref(st), stream))
         return self._temporal_adaptive_stats(st)
 
-    def render_temporal_adaptive_frame(self, params, aparams, dparams=None, tparams=None):
+    def render_temporal_adaptive_guided_device(self, params, aparams, tparams, plane_ptrs, prev_cam, d_history_in_ptr, d_accum_ptr,
+                                               d_moments_ptr, d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream=None):
+        """srtRenderTemporalAdaptiveGuided: render_temporal_adaptive_device whose rounds extend the planes in plane_ptrs (in:
+        the first params.spp samples; out: all of a pixel's samples); the closing accumulation reads the extended planes."""
+        return self.render_temporal_adaptive_device(params, aparams, tparams, plane_ptrs, prev_cam, d_history_in_ptr, d_accum_ptr,
+                                                    d_moments_ptr, d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream,
+                                                    entry=lib.srtRenderTemporalAdaptiveGuided)
+
+    def render_temporal_adaptive_frame(self, params, aparams, dparams=None, tparams=None, guided=False):
         """One frame of a sequence with history-steered sampling (srtRenderTemporalAdaptiveFrame); interleaves with
         render_temporal_frame on one context.  Returns (accum, denoised, rgba, stats): accum = this frame's own sums with
-        per-pixel counts; stats as render_temporal_adaptive_device's.  Advance params.sampleFirst by aparams.sppMax."""
+        per-pixel counts; stats as render_temporal_adaptive_device's.  Advance params.sampleFirst by aparams.sppMax.
+        guided: srtRenderTemporalAdaptiveGuidedFrame, the guide planes follow the rounds."""
         dparams = abi.default_denoise_params() if dparams is None else dparams
         tparams = abi.default_temporal_params() if tparams is None else tparams
         W, H = params.imageWidth, params.imageHeight
@@ -432,9 +489,9 @@ class Context:
         rgba = np.zeros((H, W, 4), np.uint8)
         st = abi.SrtTemporalAdaptiveStats()
         fp = C.POINTER(C.c_float)
-        self._check(lib.srtRenderTemporalAdaptiveFrame(self.h, C.byref(params), C.byref(aparams), C.byref(dparams),
-                                                       C.byref(tparams), accum.ctypes.data_as(fp), denoised.ctypes.data_as(fp),
-                                                       rgba.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+        entry = lib.srtRenderTemporalAdaptiveGuidedFrame if guided else lib.srtRenderTemporalAdaptiveFrame
+        self._check(entry(self.h, C.byref(params), C.byref(aparams), C.byref(dparams), C.byref(tparams), accum.ctypes.data_as(fp),
+                          denoised.ctypes.data_as(fp), rgba.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
         return accum, denoised, rgba, self._temporal_adaptive_stats(st)
 
     def render_tiles(self, params, d_accum_ptr, stream=None):

@@ -14,6 +14,9 @@
 //                                           (include/srt_hip.h "Temporal-adaptive frames")
 //   rtFrameAdaptive(target, ..., sppMax, thr)  tile-adaptive sampling: numSamples everywhere, then more samples, doubling,
 //                                           for the tiles that have not converged (include/srt_hip.h "Adaptive sampling")
+//   rtFrameAdaptiveDenoised(target, denoised, ..., sppMax, thr)  rtFrameAdaptive's frame, guide planes from every one of its
+//                                           samples and the denoiser with the sample variance
+//                                           (include/srt_hip.h srtRenderAdaptiveDenoisedImage)
 //   terminate()
 //   uniqueId / initRanks                    multi-GPU: one process per GPU; rtFrame then renders this rank's
 //                                           tiles, the library gathers them with ONE ncclGather and rank 0's
@@ -107,6 +110,56 @@ class hipDevice {
     a.threshold = threshold;
     if (srtRenderAdaptiveImage(ctx, &p, &a, accum, nullptr, static_cast<uint8_t*>(frameData), stats) != 0) return error();
     (void)srtLastKernelMs(ctx, &lastKernelMs);
+    return true;
+  }
+
+  // rtFrameAdaptive plus the denoiser (include/srt_hip.h srtRenderAdaptiveDenoisedImage): the adaptive render, feature planes
+  // that follow its rounds (every sample of a tile guides the filter) and srtDenoiseMoments on the sums.  frameData (may be
+  // null) receives the frame rtFrameAdaptive would write, denoisedData (may be null) the denoised one; accum / denoised
+  // (float[w*h*4], may be null) the sums with per-pixel counts and the denoised means.  d = null: the library's defaults.
+  // Single-process only.
+  bool rtFrameAdaptiveDenoised(void* frameData, void* denoisedData, int w, int h, const camera& cam, const color3f& background,
+                               int numSamples, int maxBounce, int sppMax, float threshold, uint64_t seed = 1,
+                               const SrtDenoiseParams* d = nullptr, float* accum = nullptr, float* denoised = nullptr,
+                               SrtAdaptiveStats* stats = nullptr) {
+    if (!ctx) return false;
+    if (ranks > 1) {
+      std::cerr << "ERROR: rtFrameAdaptiveDenoised renders on one GPU\n";
+      return false;
+    }
+    if (srtSetCamera(ctx, &cam.data()) != 0) return error();
+    SrtRenderParams p{};
+    p.imageWidth = w; p.imageHeight = h; p.spp = numSamples; p.maxBounce = maxBounce; p.seed = seed;
+    for (int i = 0; i < 3; ++i) p.background[i] = background(i);
+    p.tMin = 0.001f;  // main.cpp:39
+    p.traversal = SRT_TRAVERSE_FAITHFUL;
+    p.tileFirst = 0; p.tileStride = 1;
+    p.sppChunks = sppChunks;
+    SrtAdaptiveParams a{};
+    a.sppMax = sppMax;
+    a.threshold = threshold;
+    const SrtDenoiseParams defaults{};
+    std::vector<float> sums;
+    if (!accum && frameData) {
+      sums.resize((size_t)w * h * 4);
+      accum = sums.data();
+    }
+    if (srtRenderAdaptiveDenoisedImage(ctx, &p, &a, d ? d : &defaults, accum, nullptr, denoised, static_cast<uint8_t*>(denoisedData),
+                                       stats) != 0)
+      return error();
+    (void)srtLastKernelMs(ctx, &lastKernelMs);
+    if (frameData) {  // srtRenderAdaptive's quantisation of the sums, each pixel with its own count
+      uint8_t* px = static_cast<uint8_t*>(frameData);
+      for (size_t i = 0; i < (size_t)w * h; ++i) {
+        const float scale = 1.0f / accum[4 * i + 3];
+        for (int c = 0; c < 3; ++c) {
+          const float g = std::sqrt(accum[4 * i + c] * scale);
+          const float q = 256.0f * (g < 0.0f ? 0.0f : (g > 0.999f ? 0.999f : g));
+          px[4 * i + c] = (q == q) ? (uint8_t)q : (uint8_t)0;  // NaN -> 0
+        }
+        px[4 * i + 3] = 255;
+      }
+    }
     return true;
   }
 
@@ -221,11 +274,12 @@ class hipDevice {
   // samples everywhere from sampleFirst, then doubling rounds, up to sppMax samples a pixel, for the tiles whose samples and
   // reprojected history together are not yet below the display-space standard error `threshold`.  Buffers, d and t as in
   // rtFrameTemporal; accum carries per-pixel counts.  Callers advance sampleFirst by sppMax per frame.  Frames of both
-  // kinds may follow one another.  Single-process only.
+  // kinds may follow one another.  guided: the feature planes follow the rounds (srtRenderTemporalAdaptiveGuidedFrame), so
+  // the closing accumulation, the new history and the denoiser see guides from all of a tile's samples.  Single-process only.
   bool rtFrameTemporalAdaptive(void* denoisedData, int w, int h, const camera& cam, const color3f& background, int numSamples,
                                int maxBounce, int sppMax, float threshold, int sampleFirst, uint64_t seed = 1,
                                const SrtDenoiseParams* d = nullptr, const SrtTemporalParams* t = nullptr, float* accum = nullptr,
-                               float* denoised = nullptr, SrtTemporalAdaptiveStats* stats = nullptr) {
+                               float* denoised = nullptr, SrtTemporalAdaptiveStats* stats = nullptr, bool guided = false) {
     if (!ctx) return false;
     if (ranks > 1) {
       std::cerr << "ERROR: rtFrameTemporalAdaptive renders on one GPU\n";
@@ -245,8 +299,8 @@ class hipDevice {
     a.threshold = threshold;
     const SrtDenoiseParams ddefaults{};
     const SrtTemporalParams tdefaults{};
-    if (srtRenderTemporalAdaptiveFrame(ctx, &p, &a, d ? d : &ddefaults, t ? t : &tdefaults, accum, denoised,
-                                       static_cast<uint8_t*>(denoisedData), stats) != 0)
+    const auto entry = guided ? srtRenderTemporalAdaptiveGuidedFrame : srtRenderTemporalAdaptiveFrame;
+    if (entry(ctx, &p, &a, d ? d : &ddefaults, t ? t : &tdefaults, accum, denoised, static_cast<uint8_t*>(denoisedData), stats) != 0)
       return error();
     (void)srtLastKernelMs(ctx, &lastKernelMs);
     return true;
