@@ -59,6 +59,14 @@ int srtTestThreadLinks16(const float* nodes8, int32_t numNodes, const int32_t* w
 int srtTestHybridRecords(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, int32_t numTriangles, int32_t numSpheres,
                          int32_t cap, float* outNodes8, int32_t* outWorld, int32_t* outSecond);
 
+/* Reads back what the near-child-first traversal walks for world item `item` (host-built and device-built trees alike), as
+ * it lies in device memory: the item's slice of DevScene::nodeAxis -> outAxis[count] (the split axis of each node, 3 = none)
+ * and of DevScene::nodes2 -> outPairs16[count x 16] (the 64-byte records of csrc/srt_lbvh.hip pairNodes: left child's box
+ * min / max in floats 0-2 / 4-6, the right child's in 8-10 / 12-14, the left / right reference as int bits in floats 3 / 7:
+ * a node's record offset (scene-wide index * 64) or a device primitive reference ~(index << 1 | sphere)).  Either output
+ * may be NULL; with both NULL only *count is written.  Fails for an item that is not a tree, or when capacity < count. */
+int srtTestGetTreeAux(SrtContext* ctx, int32_t item, uint8_t* outAxis, float* outPairs16, int32_t capacity, int32_t* count);
+
 /* The most recent render-kernel launch: out4 = { 0 node records through the L1, 1 the step-scheduler kernel over the
  * LDS-resident threaded tree (FAITHFUL, node array small enough for a CU's LDS; tunable "lds_tree" = 0 switches it
  * off), 2 the same with the attenuation stacks in LDS as well, 3 the path-pool kernel over the same tree (tunable

@@ -1768,6 +1768,26 @@ int srtTestHybridRecords(const float* nodes8, int32_t numNodes, const int32_t* w
   return resident;
 }
 
+/* include/srt_hip_test.h: world item `item`'s slice of DevScene::nodeAxis and DevScene::nodes2, read back as they are */
+int srtTestGetTreeAux(SrtContext* ctx, int32_t item, uint8_t* outAxis, float* outPairs16, int32_t capacity, int32_t* count) {
+  if (!ctx || !count) return 1;
+  if (!ctx->haveScene) return fail(ctx, "srtTestGetTreeAux: no scene uploaded");
+  if (item < 0 || item >= (int32_t)ctx->itemNodes.size()) return fail(ctx, "srtTestGetTreeAux: item %d out of range", item);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  int32_t ref = 0;
+  HIP_OK(ctx, hipMemcpy(&ref, ctx->scene.world + item, sizeof ref, hipMemcpyDeviceToHost));
+  if (ref < 0) return fail(ctx, "srtTestGetTreeAux: item %d is not a tree", item);
+  const auto dt = std::find_if(ctx->deviceBuilds.begin(), ctx->deviceBuilds.end(), [&](const DeviceBuild& b) { return b.item == item; });
+  const int32_t base = SRT_NODE_INDEX(ref), n = dt != ctx->deviceBuilds.end() ? dt->count : (int32_t)ctx->itemNodes[item].size();
+  if (base + n > ctx->scene.numNodes) return fail(ctx, "srtTestGetTreeAux: item %d lies outside the node array", item);
+  *count = n;
+  if (!outAxis && !outPairs16) return 0;
+  if (capacity < n) return fail(ctx, "srtTestGetTreeAux: capacity %d < %d", capacity, n);
+  if (outAxis) HIP_OK(ctx, hipMemcpy(outAxis, ctx->scene.nodeAxis + base, (size_t)n, hipMemcpyDeviceToHost));
+  if (outPairs16) HIP_OK(ctx, hipMemcpy(outPairs16, ctx->scene.nodes2 + 4 * (size_t)base, (size_t)n * 64, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int srtGetShadeProfile(SrtContext* ctx, uint64_t* out10) {
   if (!ctx || !out10) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));

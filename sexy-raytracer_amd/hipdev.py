@@ -43,7 +43,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
-                "srtTestThreadLinks16", "srtTestHybridRecords"]
+                "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -126,6 +126,7 @@ lib.srtGetLaunchInfo.argtypes = [_vp, _vp]
 lib.srtTestThreadLinks16.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]
 lib.srtTestHybridRecords.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]
 lib.srtTestThreadLinks16.restype = lib.srtTestHybridRecords.restype = C.c_int32
+lib.srtTestGetTreeAux.argtypes = [_vp, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]
 lib.srtRenderAov.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
 lib.srtLastKernelMs.argtypes = [_vp, C.POINTER(C.c_float)]
 lib.srtGetStats.argtypes = [_vp, C.POINTER(abi.SrtStats)]
@@ -259,6 +260,17 @@ class Context:
         d = C.c_int32(0)
         self._check(lib.srtGetBvhDepth(self.h, C.byref(d)))
         return d.value
+
+    def tree_aux(self, item=0):
+        """What the near-child-first traversal reads beside the node array (include/srt_hip_test.h srtTestGetTreeAux):
+        returns (axis, pairs) of world item `item`, uint8 (n,) and float32 (n, 16), n = the item's node count."""
+        n = C.c_int32(0)
+        self._check(lib.srtTestGetTreeAux(self.h, item, None, None, 0, C.byref(n)))
+        axis = np.zeros(n.value, np.uint8)
+        pairs = np.zeros((n.value, 16), np.float32)
+        self._check(lib.srtTestGetTreeAux(self.h, item, axis.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          pairs.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
+        return axis, pairs
 
     def render_image(self, params, want_accum=True, want_rgba=True):
         W, H = params.imageWidth, params.imageHeight

@@ -429,11 +429,17 @@ def test_device_lbvh_build_and_closest_hit(ctx, oracle, abi, srt, camera, builde
     ctx.set_camera(camera)
     nodes = ctx.bvh(0)
     assert _tree_checks(nodes, n + 1)
-    # boxes: parents enclose children exactly (union), checked top-down on the node array
+    # boxes: every parent's box is exactly the union of its children's -- the bitwise min / max of the two boxes, a leaf's
+    # being its primitive's box (tests/tree_build_ref.py prim_boxes) over the item's time range
+    import tree_build_ref
+    leaf_mn, leaf_mx = tree_build_ref.prim_boxes(sb, np.arange(n + 1), 0.0, 1.0)
+    kids = []
     for child in ("left", "right"):
         c = nodes[child]
-        m = c >= 0
-        assert (nodes["bmin"][m] <= nodes["bmin"][c[m]]).all() and (nodes["bmax"][m] >= nodes["bmax"][c[m]]).all()
+        inner, node, prim = (c >= 0)[:, None], np.maximum(c, 0), np.maximum(~c, 0)
+        kids.append((np.where(inner, nodes["bmin"][node], leaf_mn[prim]), np.where(inner, nodes["bmax"][node], leaf_mx[prim])))
+    assert np.array_equal(nodes["bmin"].view(np.uint32), np.minimum(kids[0][0], kids[1][0]).view(np.uint32))
+    assert np.array_equal(nodes["bmax"].view(np.uint32), np.maximum(kids[0][1], kids[1][1]).view(np.uint32))
     assert 15 <= ctx.bvh_depth() <= 64
     if builder == abi.SRT_BUILDER_PLOC:
         # children are numbered after their parents (creation order reversed)

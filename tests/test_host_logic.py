@@ -194,5 +194,23 @@ def test_python_binding_covers_every_entry_point(dev):
     for method in ("upload_scene", "set_camera", "bvh", "bvh_depth", "render_image", "render_tiles", "resolve_tiles",
                    "comm_init", "gather_tiles", "render_image_ranks", "comm_destroy", "trace", "scatter_test",
                    "set_tunable", "get_tunable", "render_aov", "shade_profile", "last_kernel_ms", "stats",
-                   "device_info", "fingerprint", "close"):
+                   "device_info", "fingerprint", "close", "tree_aux"):
         assert callable(getattr(dev.Context, method, None)), method
+
+
+def test_tree_aux_prototype_matches_header(dev):
+    """srtTestGetTreeAux (include/srt_hip_test.h): the ctypes prototype against the declaration; a test hook, not an
+    export of the drop-in boundary; without a context it fails instead of reading anything."""
+    header = open(os.path.join(ROOT, "include", "srt_hip_test.h")).read()
+    m = re.search(r"\bint\s+srtTestGetTreeAux\s*\(([^)]*)\)\s*;", header)
+    assert m
+    ctype = {"SrtContext*": C.c_void_p, "int32_t": C.c_int32, "uint8_t*": C.POINTER(C.c_uint8), "float*": C.POINTER(C.c_float),
+             "int32_t*": C.POINTER(C.c_int32)}
+    params = [re.sub(r"\s*\w+$", "", " ".join(a.split())).replace(" *", "*") for a in m.group(1).split(",")]
+    got = dev.lib.srtTestGetTreeAux.argtypes
+    assert len(got) == len(params) == 6
+    for g, p in zip(got, params):
+        assert g.__name__ == ctype[p].__name__, (p, g)
+    assert "srtTestGetTreeAux" in dev.TEST_EXPORTS and "srtTestGetTreeAux" not in dev.EXPORTS
+    n = C.c_int32(-7)
+    assert dev.lib.srtTestGetTreeAux(None, 0, None, None, 0, C.byref(n)) != 0 and n.value == -7
