@@ -6,27 +6,11 @@
 //
 // All of them are HBM-bound and tiny next to a render: one wave per listed tile (64 lanes, 64 pixels) for the update,
 // one 1024-thread workgroup for the compaction (a few bytes per tile), one thread per pixel for the resolve.
-#include <hip/hip_runtime.h>
-
-#include "srt_device.h"
+#include "srt_adaptive_common.h"
 
 namespace {
 
-constexpr int AD_WAVES = 4;           // tiles (waves) per workgroup of the update kernel
 constexpr int AD_COMPACT_THREADS = 1024;
-
-// The convergence test of include/srt_hip.h, in double and in the header's operation order (the library builds with
-// -ffp-contract=off: no multiply-add forms).  limit = 4 thr^2, computed on the host.
-__device__ inline bool adaptiveConverged(const float4 m, double limit) {
-  const double s1 = (double)m.x, s2 = (double)m.y, n = (double)m.w;
-  if (!isfinite(s1) || !isfinite(s2)) return true;  // more samples cannot repair a NaN or an infinity
-  const double mu = s1 / n;
-  const double sq = s1 * s1;
-  const double d = s2 - sq / n;
-  const double v = (d > 0.0 ? d : 0.0) / (n * (n - 1.0));
-  const double floorMu = mu > 0x1p-16 ? mu : 0x1p-16;
-  return v < limit * floorMu;
-}
 
 // One wave per listed tile.  ACCUM: adds tile i's beauty and moments (the render's tile-major outputs, list position i)
 // into the image-order sums, one float add per channel.  DECIDE: flags[i] = 1 iff an in-image pixel of the tile is not
@@ -40,11 +24,8 @@ __global__ __launch_bounds__(64 * AD_WAVES) void srt_adaptive_update_kernel(cons
   const int i = blockIdx.x * AD_WAVES + (int)(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (i >= count) return;  // whole waves
-  const uint32_t txy = list[i];
-  const int px = (int)(txy & 0xffffu) * SRT_TILE_W + (lane & (SRT_TILE_W - 1));
-  const int py = (int)(txy >> 16) * SRT_TILE_H + (lane >> 3);
-  const bool inImage = px < width && py < height;  // edge tiles: the padding lanes are skipped
-  const size_t idx = (size_t)py * width + px;
+  size_t idx;
+  const bool inImage = listedTilePixel(list[i], lane, width, height, idx);
   float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (inImage) {
     if constexpr (ACCUM) {

@@ -1088,16 +1088,12 @@ static int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t p
   return 0;
 }
 
-static int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* streamPtr) {
-  if (!ctx) return 1;
-  if (checkFeatureArgs(ctx, p, planes, dPlanes)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+/* What the two feature passes do alike once their arguments are set: the traversal form and its LDS, the kernel's plan, a
+ * grid of at most `work` waves, the tile counter reset, the launch.  plan and launch are the pass's own kernel's. */
+extern "C++" template <typename Plan, typename Launch>
+static int launchFeaturePass(SrtContext* ctx, const SrtRenderParams* p, FeatureArgs& a, int work, hipStream_t stream, Plan plan,
+                             Launch launch) {
   const DevScene& sc = ctx->scene;
-  FeatureArgs a;
-  setImageArgs(a, ctx, p);
-  a.planes = planes;
-  for (int k = 0; k < 4; ++k) a.out[k] = (planes >> k & 1) ? static_cast<float4*>(dPlanes[k]) : nullptr;
   // FAITHFUL over a threaded tree that fits a CU's LDS: the stackless walk out of LDS; otherwise the stack walk over
   // scene.nodes (stacks in LDS), which CLOSEST always takes
   const bool closest = p->traversal == SRT_TRAVERSE_CLOSEST;
@@ -1106,16 +1102,30 @@ static int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, 
   const size_t lds = ldsTree ? treeBytes : (size_t)std::max(sc.stackDepth, 1) * SRT_BLOCK * sizeof(int32_t);
   if (lds > 160 * 1024) return fail(ctx, "features: BVH depth %d needs %zu B of LDS per workgroup", sc.stackDepth, lds);
   int block = 0, perCU = 1;
-  int rc = srt_features_plan(closest, ldsTree, lds, &block, &perCU);
+  int rc = plan(closest, ldsTree, lds, &block, &perCU);
   if (rc) return fail(ctx, "features: kernel setup failed: %s", hipGetErrorString((hipError_t)rc));
   const int wavesPerGroup = block / 64;
-  const int grid = std::max(1, std::min(ctx->prop.multiProcessorCount * perCU, (a.numLocalTiles + wavesPerGroup - 1) / wavesPerGroup));
+  const int grid = std::max(1, std::min(ctx->prop.multiProcessorCount * perCU, (work + wavesPerGroup - 1) / wavesPerGroup));
   HIP_OK(ctx, ctx->dFeatureCounter.reserve(16 * sizeof(int32_t)));
   a.counter = ctx->dFeatureCounter.get<int32_t>();
   HIP_OK(ctx, hipMemsetAsync(a.counter, 0, sizeof(int32_t), stream));
-  rc = srt_launch_features(&a, closest, ldsTree, grid, lds, stream);
+  rc = launch(closest, ldsTree, grid, lds);
   if (rc) return fail(ctx, "features launch failed: %s", hipGetErrorString((hipError_t)rc));
   return 0;
+}
+
+static int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* streamPtr) {
+  if (!ctx) return 1;
+  if (checkFeatureArgs(ctx, p, planes, dPlanes)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+  FeatureArgs a;
+  setImageArgs(a, ctx, p);
+  a.planes = planes;
+  for (int k = 0; k < 4; ++k) a.out[k] = (planes >> k & 1) ? static_cast<float4*>(dPlanes[k]) : nullptr;
+  return launchFeaturePass(ctx, p, a, a.numLocalTiles, stream, [&](bool closest, bool ldsTree, size_t lds, int* block, int* perCU) {
+    return srt_features_plan(closest, ldsTree, lds, block, perCU);
+  }, [&](bool closest, bool ldsTree, int grid, size_t lds) { return srt_launch_features(&a, closest, ldsTree, grid, lds, stream); });
 }
 
 static int srtRenderFeatureImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, int32_t planes, float* const hPlanes[4]) {
@@ -1172,30 +1182,17 @@ static int srtRenderFeatureTileListImpl(SrtContext* ctx, const SrtRenderParams* 
   if (numListed == 0) return 0;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-  const DevScene& sc = ctx->scene;
   FeatureListArgs a;
   setImageArgs(a.f, ctx, p);
   a.f.planes = planes;
   for (int k = 0; k < 4; ++k) a.f.out[k] = (planes >> k & 1) ? static_cast<float4*>(dPlaneImages[k]) : nullptr;
   a.list = static_cast<const uint32_t*>(dTileList);
   a.numListed = numListed;
-  // the traversal form and its LDS exactly as srtRenderFeatureTiles chooses them
-  const bool closest = p->traversal == SRT_TRAVERSE_CLOSEST;
-  const size_t treeBytes = (size_t)sc.numNodes * 32;
-  const bool ldsTree = !closest && sc.nodeThread != nullptr && treeBytes <= 160 * 1024;
-  const size_t lds = ldsTree ? treeBytes : (size_t)std::max(sc.stackDepth, 1) * SRT_BLOCK * sizeof(int32_t);
-  if (lds > 160 * 1024) return fail(ctx, "features: BVH depth %d needs %zu B of LDS per workgroup", sc.stackDepth, lds);
-  int block = 0, perCU = 1;
-  int rc = srt_features_list_plan(closest, ldsTree, accumulate != 0, lds, &block, &perCU);
-  if (rc) return fail(ctx, "features: kernel setup failed: %s", hipGetErrorString((hipError_t)rc));
-  const int wavesPerGroup = block / 64;
-  const int grid = std::max(1, std::min(ctx->prop.multiProcessorCount * perCU, (numListed + wavesPerGroup - 1) / wavesPerGroup));
-  HIP_OK(ctx, ctx->dFeatureCounter.reserve(16 * sizeof(int32_t)));
-  a.f.counter = ctx->dFeatureCounter.get<int32_t>();
-  HIP_OK(ctx, hipMemsetAsync(a.f.counter, 0, sizeof(int32_t), stream));
-  rc = srt_launch_features_list(&a, closest, ldsTree, accumulate != 0, grid, lds, stream);
-  if (rc) return fail(ctx, "features launch failed: %s", hipGetErrorString((hipError_t)rc));
-  return 0;
+  return launchFeaturePass(ctx, p, a.f, numListed, stream, [&](bool closest, bool ldsTree, size_t lds, int* block, int* perCU) {
+    return srt_features_list_plan(closest, ldsTree, accumulate != 0, lds, block, perCU);
+  }, [&](bool closest, bool ldsTree, int grid, size_t lds) {
+    return srt_launch_features_list(&a, closest, ldsTree, accumulate != 0, grid, lds, stream);
+  });
 }
 int srtRenderFeatureTileList(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList, int32_t numListed,
                              void* const dPlaneImages[4], int32_t accumulate, void* stream) {

@@ -8,7 +8,15 @@
 Every kernel of the old listing must be in the new one under its name with `Lb0E` (a defaulted trailing `false`
 template argument, such as MOMENTS) appended to its template arguments, or under its old name; its instructions and its
 descriptor (registers, scratch, LDS, argument size) must be identical once label numbers and the kernel's own name are
-normalised.  Kernels only in the new listing are listed with their register counts and scratch size."""
+normalised.  Kernels only in the new listing are listed with their register counts and scratch size.
+
+The whole check, every kernel source against the parent commit (FLAGS, KFLAGS: the values in csrc/Makefile):
+
+    git archive HEAD sexy-raytracer_amd/csrc include | tar -x -C old          (a checkout of the parent)
+    for d in old .; do mkdir -p $d/asm; for f in $d/sexy-raytracer_amd/csrc/*.hip; do
+      (cd $d/sexy-raytracer_amd/csrc && hipcc $FLAGS $KFLAGS --cuda-device-only -S -o - $(basename $f)) \
+        > $d/asm/$(basename $f .hip).s; done; done
+    for s in old/asm/*.s; do echo "== $(basename $s .s)"; python tools/isa_compare.py $s asm/$(basename $s); done"""
 import re
 import sys
 
