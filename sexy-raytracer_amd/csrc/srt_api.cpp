@@ -1,5 +1,6 @@
-// srt_api.cpp -- host side of the C ABI (include/srt_hip.h): context, device memory, the upload of a flattened scene
-// (srt_scene.cpp) and the device BVH builds, launches and timing.
+// srt_api.cpp -- host side of the C ABI (include/srt_hip.h): context (srt_context.h), device memory, the upload of a
+// flattened scene (srt_scene.cpp) and the device BVH builds, launches and timing.  The entries that render a whole frame
+// into host buffers compose these launches in srt_frames.cpp.
 
 #include <hip/hip_runtime.h>
 
@@ -8,13 +9,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <string>
 #include <vector>
 
-#include "srt_buffer.h"
-#include "srt_device.h"
-#include "srt_scene.h"
+#include "srt_context.h"
 #include "srt_thread.h"
 
 extern "C" {
@@ -49,69 +47,6 @@ int srt_launch_temporal_adaptive_update(const uint32_t* list, int count, const f
                                         hipStream_t stream);
 }
 
-// Diagnostic tunables of the work distribution and the wave scheduler.  Environment variables give the
-// defaults ONCE, at srtCreate; srtSetTunable (include/srt_hip_test.h) changes them per context.  -1 = the
-// library's own rule.
-struct Tunables {
-  int tileBlock, unitTiles, queues;
-  int shadeMin, primMin, hitMin, fuseMin, nodeBurst;
-  int plocRadius, fastDiv;
-  int chunkScratchMb;
-  int primAgainMin;
-  int keepEighths;
-  int ldsTree;
-  int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
-  int wfHybrid, wfResidentMax, wfFarRounds;
-  int denoiseLdsStep;
-};
-
-struct SrtContext {
-  int device = 0;
-  std::string error;
-  Tunables tun{};
-  hipDeviceProp_t prop;
-  // device scene
-  std::vector<DeviceBuffer> sceneBuffers;
-  DevScene scene{};
-  DevCamera cam{};
-  bool haveScene = false, haveCamera = false;
-  // host copies for srtGetBvh
-  std::vector<std::vector<SrtBvhNode>> itemNodes;
-  std::vector<DeviceBuild> deviceBuilds;  // where the device-built trees live in scene.nodes (without their refs)
-  std::vector<int32_t> hostTriPrimId, hostSphPrimId;
-  int bvhDepth = 0;
-  // work areas
-  DeviceBuffer dQueue;
-  DeviceBuffer dStats;
-  void* comm = nullptr;          // ncclComm_t (srt_comm.cpp)
-  int commRanks[2] = {1, 0};     // number of ranks, this rank
-  DeviceBuffer chunkScratch;
-  DeviceBuffer attScratch;  // LDS-resident-tree kernel: the lanes' attenuation stacks (srt_render_kernel LDSTREE)
-  DeviceBuffer wfPool, wfAttHi;  // path-pool kernel: contexts and upper attenuation levels (srt_wavefront.hip)
-  int32_t* dWfError = nullptr;
-  DeviceBuffer dFeatureCounter;  // the feature passes' tile counter (their own: a render's queues are never touched)
-  DeviceBuffer denoiseScratch;   // srtDenoise: guide records, depth gradients, two colour buffers (56 B per pixel)
-  DeviceBuffer tileTable;   // RenderArgs::tileXY for the image size and tile order below
-  // srtRenderAdaptive: one launch's beauty and moments tiles, two tile lists (this launch's, the next one's), the per-tile
-  // flags and the compaction's {count, pixels}
-  DeviceBuffer adaptTiles, adaptList[2], adaptFlags, adaptCounts;
-  // srtRenderTemporalFrame: the two histories (the one the last frame wrote, the one the next writes), what they belong to,
-  // and the camera as srtSetCamera received it (DevCamera drops w)
-  DeviceBuffer temporalHistory[2];
-  DeviceBuffer temporalReprojected;  // srtRenderTemporalAdaptive: the frame's reprojected history (32 B per pixel)
-  int32_t temporalCurrent = 0;  // index of the history the last frame wrote
-  bool temporalValid = false;
-  int32_t temporalKey[3] = {0, 0, 0};  // width, height, demodulate
-  SrtCamera camFull{}, temporalCam{};
-  int32_t tileTableKey[3] = {0, 0, 0};
-  RenderPlan lastPlan{};  // the most recent render launch (srtGetLaunchInfo)
-  int32_t lastGrid = 0;
-  hipEvent_t evStart = nullptr, evStop = nullptr;
-  bool timed = false;
-};
-
-namespace {
-
 int fail(SrtContext* ctx, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -123,8 +58,6 @@ int fail(SrtContext* ctx, const char* fmt, ...) {
   return 1;
 }
 
-// A path-pool launch that gave up (a ring wait exceeded its bound, srt_wavefront.hip) has added to the context's error
-// word: the frame is incomplete.  Checked wherever the host has waited for the device anyway.
 int wfCheck(SrtContext* ctx) {
   if (ctx->dWfError && *(volatile int32_t*)ctx->dWfError != 0) {
     const int n = *(volatile int32_t*)ctx->dWfError;
@@ -134,11 +67,7 @@ int wfCheck(SrtContext* ctx) {
   return 0;
 }
 
-#define HIP_OK(ctx, call)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) return fail(ctx, "%s -> %s", #call, hipGetErrorString(e_));       \
-  } while (0)
+namespace {
 
 template <typename T>
 int uploadVec(SrtContext* ctx, const std::vector<T>& v, const T** out, size_t padBytes = 0) {
@@ -256,13 +185,6 @@ int srtCreate(int deviceOrdinal, SrtContext** out) {
   *out = ctx;
   return 0;
 }
-
-// srt_comm.cpp's view of the context
-int srtCtxFail(SrtContext* ctx, const char* text) { return fail(ctx, "%s", text); }
-int srtCtxDevice(const SrtContext* ctx) { return ctx->device; }
-void** srtCtxCommSlot(SrtContext* ctx) { return &ctx->comm; }
-int* srtCtxCommRanks(SrtContext* ctx) { return ctx->commRanks; }
-int srtCommDestroy(SrtContext* ctx);
 
 int srtDestroy(SrtContext* ctx) {
   if (!ctx) return 0;
@@ -458,7 +380,7 @@ int32_t srtPlanSppChunks(int32_t imageWidth, int32_t imageHeight, int32_t spp, i
   return (int32_t)std::min<int64_t>(srtDefaultSppChunks(spp), maxChunks);
 }
 
-static int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
+extern "C++" int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
   if (!ctx->haveScene) return fail(ctx, "render: no scene uploaded");
   if (!ctx->haveCamera) return fail(ctx, "render: no camera set");
   if (p->imageWidth < 2 || p->imageHeight < 2) return fail(ctx, "render: image must be at least 2x2 (u,v divide by W-1,H-1)");
@@ -542,9 +464,8 @@ static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bo
 // (srtRenderAdaptive; p->tileFirst = 0, p->tileStride = 1): the output holds list position i where it holds local tile i,
 // and the queues, the grid and the chunk scratch follow the list's length.  The render kernels see an ordinary launch
 // whose tile table is the list.
-static int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr,
-                              SrtAovRecord* aov = nullptr, int32_t aovDepth = 0, void* dMoments = nullptr,
-                              const uint32_t* dList = nullptr, int32_t listTiles = 0) {
+extern "C++" int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr, SrtAovRecord* aov,
+                                    int32_t aovDepth, void* dMoments, const uint32_t* dList, int32_t listTiles) {
   if (!ctx || !p || !dAccumTiles) return 1;
   if (checkParams(ctx, p)) return 1;
   if (dList && (listTiles < 1 || listTiles > srtNumTiles(p->imageWidth, p->imageHeight) || p->tileStride != 1))
@@ -753,55 +674,6 @@ int srtResolveTiles(SrtContext* ctx, const SrtRenderParams* p, const void* dGath
   return 0;
 }
 
-int srtRenderImage(SrtContext* ctx, const SrtRenderParams* pIn, float* hAccum, uint8_t* hRgba) {
-  if (!ctx || !pIn) return 1;
-  SrtRenderParams p = *pIn;
-  p.tileFirst = 0;
-  p.tileStride = 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
-  const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
-  DeviceBuffer tiles, rgba, acc;
-  if (tiles.reserve(tileBytes) != hipSuccess) return fail(ctx, "hipMalloc tiles");
-  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "hipMalloc rgba");
-  if (hAccum && acc.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "hipMalloc accum");
-  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr)) return 1;
-  if (srtResolveTiles(ctx, &p, tiles.get(), rgba.get(), acc.get(), nullptr)) return 1;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "render kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  if (wfCheck(ctx)) return 1;
-  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy rgba");
-  if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy accum");
-  return 0;
-}
-
-// srtRenderImage with the moments plane: the same render through srtRenderTilesMoments, both planes resolved
-static int srtRenderImageMomentsImpl(SrtContext* ctx, const SrtRenderParams* pIn, float* hAccum, float* hMoments, uint8_t* hRgba) {
-  if (!ctx) return 1;
-  if (!pIn) return fail(ctx, "render: null parameters");
-  if (pIn->countStats) return fail(ctx, "render: the moments entries have no counting variant (countStats must be 0)");
-  SrtRenderParams p = *pIn;
-  p.tileFirst = 0;
-  p.tileStride = 1;
-  if (checkParams(ctx, &p)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
-  const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
-  DeviceBuffer tiles, mtiles, rgba, acc, mom;
-  if (tiles.reserve(tileBytes) != hipSuccess || mtiles.reserve(tileBytes) != hipSuccess) return fail(ctx, "hipMalloc tiles");
-  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "hipMalloc rgba");
-  if (hAccum && acc.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "hipMalloc accum");
-  if (hMoments && mom.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "hipMalloc moments");
-  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr, nullptr, 0, mtiles.get())) return 1;
-  if (srtResolveTiles(ctx, &p, tiles.get(), rgba.get(), acc.get(), nullptr)) return 1;
-  if (hMoments && srtResolveTiles(ctx, &p, mtiles.get(), nullptr, mom.get(), nullptr)) return 1;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "render kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  if (wfCheck(ctx)) return 1;
-  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy rgba");
-  if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy accum");
-  if (hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy moments");
-  return 0;
-}
-
 // ---------------------------------------------------------------- adaptive sampling (include/srt_hip.h)
 
 // The schedule: b_0 = n_0, then b_r = min(n_{r-1}, sppMax - n_{r-1}) until n = sppMax.
@@ -817,8 +689,8 @@ static int adaptiveSchedule(int32_t n0, int32_t sppMax, int32_t* spp) {
   return rounds;
 }
 
-static int checkAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, bool device,
-                         const void* dAccum, const void* dMoments) {
+extern "C++" int checkAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, bool device,
+                               const void* dAccum, const void* dMoments) {
   if (!ctx) return 1;
   if (!p || !ap) return fail(ctx, "adaptive: null parameters");
   if (device && (!dAccum || !dMoments)) return fail(ctx, "adaptive: the beauty and moments buffers are required");
@@ -840,27 +712,12 @@ static int checkAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAda
   return 0;
 }
 
-// srtRenderTemporalAdaptive: the decisions pool the frame's moments with this reprojected history (srt_temporal_adaptive.hip)
-struct AdaptivePool {
-  const float4* reprojected;  // two planes, SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL
-  const float4* albedo;       // null unless the history is demodulated
-};
-
-// srtRenderAdaptiveGuided / srtRenderTemporalAdaptiveGuided: image-order feature planes that follow the rounds
-// (srt_features_list.hip): after launch r its list and sample range go through the list kernel
-struct AdaptiveGuides {
-  int32_t planes;       // SRT_FEATURE_* bits
-  void* const* images;  // [4], float4[W*H] for every selected bit
-  bool storeFirst;      // round 0 is stored over the whole tile table; false: the planes hold round 0 already
-};
-
-static int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* const* buffers);
 static int srtRenderFeatureTileListImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList,
                                         int32_t numListed, void* const dPlaneImages[4], int32_t accumulate, void* streamPtr);
 
-static int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap, void* dAccumImage,
-                                 void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* streamPtr,
-                                 const AdaptivePool* pool = nullptr, const AdaptiveGuides* guides = nullptr) {
+extern "C++" int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap, void* dAccumImage,
+                                       void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* streamPtr,
+                                       const AdaptivePool* pool, const AdaptiveGuides* guides) {
   if (checkAdaptive(ctx, pIn, ap, true, dAccumImage, dMomentsImage)) return 1;
   if (guides && checkFeatureArgs(ctx, pIn, guides->planes, guides->images)) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -936,22 +793,6 @@ static int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, co
     if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "adaptive resolve failed: %s", hipGetErrorString(hipGetLastError()));
   }
   if (stats) *stats = st;
-  return 0;
-}
-
-static int srtRenderAdaptiveImageImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, float* hAccum,
-                                      float* hMoments, uint8_t* hRgba, SrtAdaptiveStats* stats) {
-  if (checkAdaptive(ctx, p, ap, false, nullptr, nullptr)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const size_t nPix = (size_t)p->imageWidth * p->imageHeight;
-  DeviceBuffer acc, mom, rgba;
-  if (acc.reserve(nPix * sizeof(float4)) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess)
-    return fail(ctx, "hipMalloc accum");
-  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "hipMalloc rgba");
-  if (srtRenderAdaptiveImpl(ctx, p, ap, acc.get(), mom.get(), rgba.get(), stats, nullptr)) return 1;
-  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy rgba");
-  if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy accum");
-  if (hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "copy moments");
   return 0;
 }
 
@@ -1031,15 +872,6 @@ int srtDeviceInfo(SrtContext* ctx, char* name, int32_t nameCap, int32_t* numCUs,
   return 0;
 }
 
-// No exception crosses the C boundary (std::vector / std::string allocations above may throw).
-#define SRT_GUARDED(ctx, call)                                                  \
-  try {                                                                         \
-    return (call);                                                              \
-  } catch (const std::exception& e) {                                           \
-    return fail(ctx, "%s: %s", __func__, e.what());                             \
-  } catch (...) {                                                               \
-    return fail(ctx, "%s: unknown exception", __func__);                        \
-  }
 int srtUploadScene(SrtContext* ctx, const SrtSceneDesc* d) { SRT_GUARDED(ctx, srtUploadSceneImpl(ctx, d)); }
 int srtBuildBvh(const SrtSceneDesc* d, int32_t item, SrtBvhNode* out, int32_t capacity, int32_t* count, int32_t* stackDepth) { SRT_GUARDED(nullptr, srtBuildBvhImpl(d, item, out, capacity, count, stackDepth)); }
 int srtGetBvh(SrtContext* ctx, int32_t item, SrtBvhNode* nodes, int32_t capacity, int32_t* count) { SRT_GUARDED(ctx, srtGetBvhImpl(ctx, item, nodes, capacity, count)); }
@@ -1047,16 +879,9 @@ int srtRenderTiles(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles,
 int srtRenderTilesMoments(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* dMomentTiles, void* streamPtr) {
   SRT_GUARDED(ctx, srtRenderTilesMomentsImpl(ctx, p, dAccumTiles, dMomentTiles, streamPtr));
 }
-int srtRenderImageMoments(SrtContext* ctx, const SrtRenderParams* p, float* hAccum, float* hMoments, uint8_t* hRgba) {
-  SRT_GUARDED(ctx, srtRenderImageMomentsImpl(ctx, p, hAccum, hMoments, hRgba));
-}
 int srtRenderAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, void* dAccumImage, void* dMomentsImage,
                       void* dRgba, SrtAdaptiveStats* stats, void* stream) {
   SRT_GUARDED(ctx, srtRenderAdaptiveImpl(ctx, p, ap, dAccumImage, dMomentsImage, dRgba, stats, stream));
-}
-int srtRenderAdaptiveImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, float* hAccum, float* hMoments,
-                           uint8_t* hRgba, SrtAdaptiveStats* stats) {
-  SRT_GUARDED(ctx, srtRenderAdaptiveImageImpl(ctx, p, ap, hAccum, hMoments, hRgba, stats));
 }
 static int srtRenderAdaptiveGuidedImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, int32_t planes,
                                        void* const dPlaneImages[4], void* dAccumImage, void* dMomentsImage, void* dRgba,
@@ -1073,7 +898,7 @@ int srtRenderAdaptiveGuided(SrtContext* ctx, const SrtRenderParams* p, const Srt
 
 /* Feature pass (srt_features.hip).  Reads the scene, the camera and the tile_block tunable; writes only the caller's planes
  * and its own tile counter, so a later render sees the context as it was. */
-static int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* const* buffers) {
+extern "C++" int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* const* buffers) {
   if (!ctx) return 1;
   if (!p) return fail(ctx, "features: null parameters");
   if (planes <= 0 || (planes & ~SRT_FEATURE_ALL) != 0) return fail(ctx, "features: bad plane mask 0x%x", (unsigned)planes);
@@ -1114,7 +939,7 @@ static int launchFeaturePass(SrtContext* ctx, const SrtRenderParams* p, FeatureA
   return 0;
 }
 
-static int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* streamPtr) {
+extern "C++" int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* streamPtr) {
   if (!ctx) return 1;
   if (checkFeatureArgs(ctx, p, planes, dPlanes)) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -1128,45 +953,8 @@ static int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, 
   }, [&](bool closest, bool ldsTree, int grid, size_t lds) { return srt_launch_features(&a, closest, ldsTree, grid, lds, stream); });
 }
 
-static int srtRenderFeatureImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, int32_t planes, float* const hPlanes[4]) {
-  if (!ctx) return 1;
-  if (checkFeatureArgs(ctx, pIn, planes, reinterpret_cast<const void* const*>(hPlanes))) return 1;
-  SrtRenderParams p = *pIn;
-  p.tileFirst = 0;
-  p.tileStride = 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
-  const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
-  DeviceBuffer tiles[4], image;
-  void* dTiles[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < 4; ++k) {
-    if (!(planes >> k & 1)) continue;
-    if (tiles[k].reserve(tileBytes) != hipSuccess) return fail(ctx, "features: hipMalloc");
-    dTiles[k] = tiles[k].get();
-  }
-  if (image.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "features: hipMalloc");
-  if (srtRenderFeatureTilesImpl(ctx, &p, planes, dTiles, nullptr)) return 1;
-  for (int k = 0; k < 4; ++k) {
-    if (!(planes >> k & 1)) continue;
-    if (srtResolveTiles(ctx, &p, dTiles[k], nullptr, image.get(), nullptr)) return 1;
-    if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "features kernel failed: %s", hipGetErrorString(hipGetLastError()));
-    float* h = hPlanes[k];
-    if (hipMemcpy(h, image.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "features: copy out");
-    // the mean over the samples that counted (a float division, as the caller would do it), w stays the count
-    for (size_t i = 0; i < nPix; ++i) {
-      float* v = h + 4 * i;
-      const float w = v[3];
-      for (int c = 0; c < 3; ++c) v[c] = w != 0.0f ? v[c] / w : 0.0f;
-    }
-  }
-  return 0;
-}
-
 int srtRenderFeatureTiles(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* stream) {
   SRT_GUARDED(ctx, srtRenderFeatureTilesImpl(ctx, p, planes, dPlanes, stream));
-}
-int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, float* const hPlanes[4]) {
-  SRT_GUARDED(ctx, srtRenderFeatureImageImpl(ctx, p, planes, hPlanes));
 }
 
 /* Feature pass over a tile list (srt_features_list.hip), into image-order planes.  The feature pass's side effects: its own
@@ -1200,8 +988,8 @@ int srtRenderFeatureTileList(SrtContext* ctx, const SrtRenderParams* p, int32_t 
 }
 
 /* Denoiser (srt_denoise.hip).  Reads the tunable denoise_lds_step; writes only the caller's outputs and its own scratch. */
-static int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, DenoiseArgs& a,
-                              int& iterations, bool moments = false) {
+extern "C++" int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, DenoiseArgs& a,
+                                    int& iterations, bool moments) {
   if (!d) return fail(ctx, "denoise: null parameters");
   if (width <= 0 || height <= 0) return fail(ctx, "denoise: image size %dx%d must be positive", width, height);
   if ((int64_t)width * height > 0x7fffffff) return fail(ctx, "denoise: image of %dx%d pixels is too large", width, height);
@@ -1227,9 +1015,9 @@ static int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_
 }
 
 // srtDenoiseMoments (moments = true): dMoments may be null, and then this is srtDenoise bit for bit
-static int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
-                          const void* const dPlanes[4], void* dOut, void* dRgba, void* streamPtr, bool moments = false,
-                          const void* dMoments = nullptr) {
+extern "C++" int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
+                                const void* const dPlanes[4], void* dOut, void* dRgba, void* streamPtr, bool moments,
+                                const void* dMoments) {
   if (!ctx) return 1;
   DenoiseArgs a;
   int iterations = 0;
@@ -1260,113 +1048,13 @@ static int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t wi
   return 0;
 }
 
-// moments: srtRenderDenoisedImageMoments -- the moments render, its plane resolved (into hMoments as well) and handed to
-// the denoiser
-static int srtRenderDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtDenoiseParams* d, float* hAccum,
-                                      float* hDenoised, uint8_t* hRgba, bool moments = false, float* hMoments = nullptr) {
-  if (!ctx) return 1;
-  if (!pIn) return fail(ctx, "denoise: null render parameters");
-  DenoiseArgs check;
-  int iterations = 0;
-  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, check, iterations, moments)) return 1;
-  if (moments && pIn->countStats) return fail(ctx, "render: the moments entries have no counting variant (countStats must be 0)");
-  SrtRenderParams p = *pIn;
-  p.tileFirst = 0;
-  p.tileStride = 1;
-  if (checkParams(ctx, &p)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
-  const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
-  const int32_t planes = SRT_FEATURE_NORMAL | SRT_FEATURE_DEPTH | (d->demodulate ? SRT_FEATURE_ALBEDO : 0);
-  // the beauty render and its resolve exactly as srtRenderImage does them, then the feature pass of the same parameters
-  DeviceBuffer tiles, accum, featTiles[4], featImage[4], out, rgba, mtiles, mom;
-  if (tiles.reserve(tileBytes) != hipSuccess || accum.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
-  if (moments && (mtiles.reserve(tileBytes) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess)) return fail(ctx, "denoise: hipMalloc");
-  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
-  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
-  void* dTiles[4] = {nullptr, nullptr, nullptr, nullptr};
-  const void* dPlanes[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < 4; ++k) {
-    if (!(planes >> k & 1)) continue;
-    if (featTiles[k].reserve(tileBytes) != hipSuccess || featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess)
-      return fail(ctx, "denoise: hipMalloc");
-    dTiles[k] = featTiles[k].get();
-    dPlanes[k] = featImage[k].get();
-  }
-  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr, nullptr, 0, moments ? mtiles.get() : nullptr)) return 1;
-  if (srtResolveTiles(ctx, &p, tiles.get(), nullptr, accum.get(), nullptr)) return 1;
-  if (moments && srtResolveTiles(ctx, &p, mtiles.get(), nullptr, mom.get(), nullptr)) return 1;
-  if (srtRenderFeatureTilesImpl(ctx, &p, planes, dTiles, nullptr)) return 1;
-  for (int k = 0; k < 4; ++k)
-    if (dTiles[k] && srtResolveTiles(ctx, &p, dTiles[k], nullptr, featImage[k].get(), nullptr)) return 1;
-  if (hDenoised || hRgba) {
-    if (srtDenoiseImpl(ctx, d, p.imageWidth, p.imageHeight, accum.get(), dPlanes, out.get(), rgba.get(), nullptr, moments, mom.get())) return 1;
-  }
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "denoise: kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  if (wfCheck(ctx)) return 1;
-  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy accum");
-  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy denoised");
-  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy rgba");
-  if (moments && hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ctx, "denoise: copy moments");
-  return 0;
-}
-
 int srtDenoise(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
                const void* const dPlanes[4], void* dOut, void* dRgba, void* stream) {
   SRT_GUARDED(ctx, srtDenoiseImpl(ctx, d, width, height, dBeauty, dPlanes, dOut, dRgba, stream));
 }
-int srtRenderDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
-                           float* hDenoised, uint8_t* hRgba) {
-  SRT_GUARDED(ctx, srtRenderDenoisedImageImpl(ctx, p, d, hAccum, hDenoised, hRgba));
-}
 int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
                       const void* const dPlanes[4], const void* dMoments, void* dOut, void* dRgba, void* stream) {
   SRT_GUARDED(ctx, srtDenoiseImpl(ctx, d, width, height, dBeauty, dPlanes, dOut, dRgba, stream, true, dMoments));
-}
-int srtRenderDenoisedImageMoments(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
-                                  float* hMoments, float* hDenoised, uint8_t* hRgba) {
-  SRT_GUARDED(ctx, srtRenderDenoisedImageImpl(ctx, p, d, hAccum, hDenoised, hRgba, true, hMoments));
-}
-
-// srtRenderAdaptiveDenoisedImage: the guided adaptive render with all four planes, srtDenoiseMoments on its sums
-static int srtRenderAdaptiveDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
-                                              const SrtDenoiseParams* d, float* hAccum, float* hMoments, float* hDenoised,
-                                              uint8_t* hRgba, SrtAdaptiveStats* stats) {
-  if (!ctx) return 1;
-  if (checkAdaptive(ctx, p, ap, false, nullptr, nullptr)) return 1;
-  DenoiseArgs check;
-  int iterations = 0;
-  if (checkDenoiseParams(ctx, d, p->imageWidth, p->imageHeight, check, iterations, true)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const int W = p->imageWidth, H = p->imageHeight;
-  const size_t nPix = (size_t)W * H;
-  DeviceBuffer accum, mom, featImage[4], out, rgba;
-  if (accum.reserve(nPix * sizeof(float4)) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess)
-    return fail(ctx, "denoise: hipMalloc");
-  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
-  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
-  void* dPlanes[4];
-  for (int k = 0; k < 4; ++k) {
-    if (featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "denoise: hipMalloc");
-    dPlanes[k] = featImage[k].get();
-  }
-  const AdaptiveGuides guides{SRT_FEATURE_ALL, dPlanes, true};
-  if (srtRenderAdaptiveImpl(ctx, p, ap, accum.get(), mom.get(), nullptr, stats, nullptr, nullptr, &guides)) return 1;
-  if (hDenoised || hRgba) {
-    if (srtDenoiseImpl(ctx, d, W, H, accum.get(), dPlanes, out.get(), rgba.get(), nullptr, true, mom.get())) return 1;
-  }
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "denoise: kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  if (wfCheck(ctx)) return 1;
-  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy accum");
-  if (hMoments && hipMemcpy(hMoments, mom.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy moments");
-  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy denoised");
-  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "denoise: copy rgba");
-  return 0;
-}
-int srtRenderAdaptiveDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtDenoiseParams* d,
-                                   float* hAccum, float* hMoments, float* hDenoised, uint8_t* hRgba, SrtAdaptiveStats* stats) {
-  SRT_GUARDED(ctx, srtRenderAdaptiveDenoisedImageImpl(ctx, p, ap, d, hAccum, hMoments, hDenoised, hRgba, stats));
 }
 
 /* Temporal accumulation (srt_temporal.hip).  Reads nothing of the context but the device ordinal; the frame entry keeps
@@ -1376,7 +1064,7 @@ static bool sameProjection(const SrtCamera& a, const SrtCamera& b) {
          !memcmp(a.vertical, b.vertical, 12) && !memcmp(a.w, b.w, 12);
 }
 
-static int checkTemporalParams(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, TemporalArgs& a) {
+extern "C++" int checkTemporalParams(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, TemporalArgs& a) {
   if (!t) return fail(ctx, "temporal: null parameters");
   if (width < 2 || height < 2) return fail(ctx, "temporal: image size %dx%d must be at least 2x2", width, height);
   if ((int64_t)width * height > 0x7fffffff / 3) return fail(ctx, "temporal: image of %dx%d pixels is too large", width, height);
@@ -1425,10 +1113,10 @@ static int temporalArgs(SrtContext* ctx, const SrtTemporalParams* t, int32_t wid
   return 0;
 }
 
-static int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
-                                     const void* dBeauty, const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
-                                     const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
-                                     void* dHistoryOut, void* streamPtr) {
+extern "C++" int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
+                                           const void* dBeauty, const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
+                                           const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
+                                           void* dHistoryOut, void* streamPtr) {
   TemporalArgs a;
   if (temporalArgs(ctx, t, width, height, dBeauty, dMoments, dPlanes, cam, prevCam, dHistoryIn, dBeautyOut, dMomentsOut, dHistoryOut, a))
     return 1;
@@ -1439,8 +1127,8 @@ static int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t
 
 // SrtTemporalStats from the finished frame's DEVICE buffers: this frame's sums, an accumulated plane (its w is the
 // output count) and the new history
-static int temporalStats(SrtContext* ctx, size_t nPix, const void* dCurrent, const void* dAccumulated, const void* dHistory,
-                         SrtTemporalStats* stats) {
+extern "C++" int temporalStats(SrtContext* ctx, size_t nPix, const void* dCurrent, const void* dAccumulated, const void* dHistory,
+                               SrtTemporalStats* stats) {
   std::vector<float> cur(nPix * 4), acc(nPix * 4), hist(nPix * 4);
   if (hipMemcpy(cur.data(), dCurrent, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(acc.data(), dAccumulated, nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
@@ -1453,75 +1141,6 @@ static int temporalStats(SrtContext* ctx, size_t nPix, const void* dCurrent, con
     sum += (double)hist[4 * i + 3];
   }
   stats->meanHistoryCount = sum / (double)nPix;
-  return 0;
-}
-
-static int srtRenderTemporalFrameImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtDenoiseParams* d,
-                                      const SrtTemporalParams* t, float* hAccum, float* hDenoised, uint8_t* hRgba,
-                                      SrtTemporalStats* stats) {
-  if (!ctx) return 1;
-  if (!pIn) return fail(ctx, "temporal: null render parameters");
-  DenoiseArgs dcheck;
-  TemporalArgs tcheck;
-  int iterations = 0;
-  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, dcheck, iterations, true)) return 1;
-  if (checkTemporalParams(ctx, t, pIn->imageWidth, pIn->imageHeight, tcheck)) return 1;
-  if (pIn->countStats) return fail(ctx, "render: the moments entries have no counting variant (countStats must be 0)");
-  SrtRenderParams p = *pIn;
-  p.tileFirst = 0;
-  p.tileStride = 1;
-  if (checkParams(ctx, &p)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const int W = p.imageWidth, H = p.imageHeight;
-  const size_t nPix = (size_t)W * H;
-  const size_t tileBytes = (size_t)srtNumTiles(W, H) * SRT_TILE_PIXELS * sizeof(float4);
-  const int32_t key[3] = {W, H, t->demodulate ? 1 : 0};
-  if (memcmp(key, ctx->temporalKey, sizeof key) != 0) ctx->temporalValid = false;
-  const int32_t planes = SRT_FEATURE_ALL;
-  DeviceBuffer tiles, mtiles, accum, mom, accOut, momOut, featTiles[4], featImage[4], out, rgba;
-  if (tiles.reserve(tileBytes) != hipSuccess || mtiles.reserve(tileBytes) != hipSuccess || accum.reserve(nPix * sizeof(float4)) != hipSuccess ||
-      mom.reserve(nPix * sizeof(float4)) != hipSuccess || accOut.reserve(nPix * sizeof(float4)) != hipSuccess ||
-      momOut.reserve(nPix * sizeof(float4)) != hipSuccess)
-    return fail(ctx, "temporal: hipMalloc");
-  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
-  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
-  void* dTiles[4];
-  const void* dPlanes[4];
-  for (int k = 0; k < 4; ++k) {
-    if (featTiles[k].reserve(tileBytes) != hipSuccess || featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess)
-      return fail(ctx, "temporal: hipMalloc");
-    dTiles[k] = featTiles[k].get();
-    dPlanes[k] = featImage[k].get();
-  }
-  for (auto& h : ctx->temporalHistory)
-    if (h.reserve(nPix * SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL) != hipSuccess) return fail(ctx, "temporal: hipMalloc history");
-  // the frame exactly as srtRenderDenoisedImageMoments renders it, with all four planes
-  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr, nullptr, 0, mtiles.get())) return 1;
-  if (srtResolveTiles(ctx, &p, tiles.get(), nullptr, accum.get(), nullptr)) return 1;
-  if (srtResolveTiles(ctx, &p, mtiles.get(), nullptr, mom.get(), nullptr)) return 1;
-  if (srtRenderFeatureTilesImpl(ctx, &p, planes, dTiles, nullptr)) return 1;
-  for (int k = 0; k < 4; ++k)
-    if (srtResolveTiles(ctx, &p, dTiles[k], nullptr, featImage[k].get(), nullptr)) return 1;
-  const int next = ctx->temporalCurrent ^ 1;
-  const void* histIn = ctx->temporalValid ? ctx->temporalHistory[ctx->temporalCurrent].get() : nullptr;
-  void* histOut = ctx->temporalHistory[next].get();
-  ctx->temporalValid = false;  // until this frame's history is complete
-  if (srtTemporalAccumulateImpl(ctx, t, W, H, accum.get(), mom.get(), dPlanes, &ctx->camFull, &ctx->temporalCam, histIn, accOut.get(),
-                                momOut.get(), histOut, nullptr))
-    return 1;
-  if (hDenoised || hRgba) {
-    if (srtDenoiseImpl(ctx, d, W, H, accOut.get(), dPlanes, out.get(), rgba.get(), nullptr, true, momOut.get())) return 1;
-  }
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "temporal: kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  if (wfCheck(ctx)) return 1;
-  ctx->temporalCurrent = next;
-  ctx->temporalCam = ctx->camFull;
-  memcpy(ctx->temporalKey, key, sizeof key);
-  ctx->temporalValid = true;
-  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy accum");
-  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy denoised");
-  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy rgba");
-  if (stats && temporalStats(ctx, nPix, accum.get(), accOut.get(), histOut, stats)) return 1;
   return 0;
 }
 
@@ -1543,11 +1162,11 @@ static int srtTemporalReprojectImpl(SrtContext* ctx, const SrtTemporalParams* t,
   return 0;
 }
 
-static int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
-                                         const SrtTemporalParams* t, const void* const dPlanes[4], const SrtCamera* prevCam,
-                                         const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
-                                         void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* streamPtr,
-                                         bool guided = false) {
+extern "C++" int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                               const SrtTemporalParams* t, const void* const dPlanes[4], const SrtCamera* prevCam,
+                                               const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
+                                               void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* streamPtr,
+                                               bool guided) {
   // every check of both halves before the first launch
   if (!ctx) return 1;
   if (checkAdaptive(ctx, p, ap, true, dAccumImage, dMomentsImage)) return 1;
@@ -1592,75 +1211,11 @@ static int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams*
   return 0;
 }
 
-static int srtRenderTemporalAdaptiveFrameImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap,
-                                              const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum,
-                                              float* hDenoised, uint8_t* hRgba, SrtTemporalAdaptiveStats* stats,
-                                              bool guided = false) {
-  if (!ctx) return 1;
-  if (checkAdaptive(ctx, pIn, ap, false, nullptr, nullptr)) return 1;
-  DenoiseArgs dcheck;
-  TemporalArgs tcheck;
-  int iterations = 0;
-  if (checkDenoiseParams(ctx, d, pIn->imageWidth, pIn->imageHeight, dcheck, iterations, true)) return 1;
-  if (checkTemporalParams(ctx, t, pIn->imageWidth, pIn->imageHeight, tcheck)) return 1;
-  const SrtRenderParams p = *pIn;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const int W = p.imageWidth, H = p.imageHeight;
-  const size_t nPix = (size_t)W * H;
-  const size_t tileBytes = (size_t)srtNumTiles(W, H) * SRT_TILE_PIXELS * sizeof(float4);
-  const int32_t key[3] = {W, H, t->demodulate ? 1 : 0};
-  if (memcmp(key, ctx->temporalKey, sizeof key) != 0) ctx->temporalValid = false;
-  DeviceBuffer accum, mom, accOut, momOut, featTiles[4], featImage[4], out, rgba;
-  if (accum.reserve(nPix * sizeof(float4)) != hipSuccess || mom.reserve(nPix * sizeof(float4)) != hipSuccess ||
-      accOut.reserve(nPix * sizeof(float4)) != hipSuccess || momOut.reserve(nPix * sizeof(float4)) != hipSuccess)
-    return fail(ctx, "temporal: hipMalloc");
-  if (hDenoised && out.reserve(nPix * sizeof(float4)) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
-  if (hRgba && rgba.reserve(nPix * 4) != hipSuccess) return fail(ctx, "temporal: hipMalloc");
-  void* dTiles[4];
-  const void* dPlanes[4];
-  for (int k = 0; k < 4; ++k) {
-    if (featTiles[k].reserve(tileBytes) != hipSuccess || featImage[k].reserve(nPix * sizeof(float4)) != hipSuccess)
-      return fail(ctx, "temporal: hipMalloc");
-    dTiles[k] = featTiles[k].get();
-    dPlanes[k] = featImage[k].get();
-  }
-  for (auto& h : ctx->temporalHistory)
-    if (h.reserve(nPix * SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL) != hipSuccess) return fail(ctx, "temporal: hipMalloc history");
-  // the feature planes of the first p.spp samples: the rounds' reprojection needs them before the first decision
-  if (srtRenderFeatureTilesImpl(ctx, &p, SRT_FEATURE_ALL, dTiles, nullptr)) return 1;
-  for (int k = 0; k < 4; ++k)
-    if (srtResolveTiles(ctx, &p, dTiles[k], nullptr, featImage[k].get(), nullptr)) return 1;
-  const int next = ctx->temporalCurrent ^ 1;
-  const void* histIn = ctx->temporalValid ? ctx->temporalHistory[ctx->temporalCurrent].get() : nullptr;
-  void* histOut = ctx->temporalHistory[next].get();
-  ctx->temporalValid = false;  // until this frame's history is complete
-  if (srtRenderTemporalAdaptiveImpl(ctx, &p, ap, t, dPlanes, &ctx->temporalCam, histIn, accum.get(), mom.get(), accOut.get(),
-                                    momOut.get(), histOut, stats, nullptr, guided))
-    return 1;
-  if (hDenoised || hRgba) {
-    if (srtDenoiseImpl(ctx, d, W, H, accOut.get(), dPlanes, out.get(), rgba.get(), nullptr, true, momOut.get())) return 1;
-  }
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "temporal: kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  if (wfCheck(ctx)) return 1;
-  ctx->temporalCurrent = next;
-  ctx->temporalCam = ctx->camFull;
-  memcpy(ctx->temporalKey, key, sizeof key);
-  ctx->temporalValid = true;
-  if (hAccum && hipMemcpy(hAccum, accum.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy accum");
-  if (hDenoised && hipMemcpy(hDenoised, out.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy denoised");
-  if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "temporal: copy rgba");
-  return 0;
-}
-
 int srtTemporalAccumulate(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
                           const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
                           const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut, void* stream) {
   SRT_GUARDED(ctx, srtTemporalAccumulateImpl(ctx, t, width, height, dBeauty, dMoments, dPlanes, cam, prevCam, dHistoryIn, dBeautyOut,
                                              dMomentsOut, dHistoryOut, stream));
-}
-int srtRenderTemporalFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, const SrtTemporalParams* t,
-                           float* hAccum, float* hDenoised, uint8_t* hRgba, SrtTemporalStats* stats) {
-  SRT_GUARDED(ctx, srtRenderTemporalFrameImpl(ctx, p, d, t, hAccum, hDenoised, hRgba, stats));
 }
 int srtTemporalReproject(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* const dPlanes[4],
                          const SrtCamera* cam, const SrtCamera* prevCam, const void* dHistoryIn, void* dReprojected, void* stream) {
@@ -1673,22 +1228,12 @@ int srtRenderTemporalAdaptive(SrtContext* ctx, const SrtRenderParams* p, const S
   SRT_GUARDED(ctx, srtRenderTemporalAdaptiveImpl(ctx, p, ap, t, dPlanes, prevCam, dHistoryIn, dAccumImage, dMomentsImage, dBeautyOut,
                                                  dMomentsOut, dHistoryOut, stats, stream));
 }
-int srtRenderTemporalAdaptiveFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtDenoiseParams* d,
-                                   const SrtTemporalParams* t, float* hAccum, float* hDenoised, uint8_t* hRgba,
-                                   SrtTemporalAdaptiveStats* stats) {
-  SRT_GUARDED(ctx, srtRenderTemporalAdaptiveFrameImpl(ctx, p, ap, d, t, hAccum, hDenoised, hRgba, stats));
-}
 int srtRenderTemporalAdaptiveGuided(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
                                     const SrtTemporalParams* t, void* const dPlanes[4], const SrtCamera* prevCam,
                                     const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
                                     void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* stream) {
   SRT_GUARDED(ctx, srtRenderTemporalAdaptiveImpl(ctx, p, ap, t, dPlanes, prevCam, dHistoryIn, dAccumImage, dMomentsImage, dBeautyOut,
                                                  dMomentsOut, dHistoryOut, stats, stream, true));
-}
-int srtRenderTemporalAdaptiveGuidedFrame(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
-                                         const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum, float* hDenoised,
-                                         uint8_t* hRgba, SrtTemporalAdaptiveStats* stats) {
-  SRT_GUARDED(ctx, srtRenderTemporalAdaptiveFrameImpl(ctx, p, ap, d, t, hAccum, hDenoised, hRgba, stats, true));
 }
 int srtTemporalReset(SrtContext* ctx) {
   if (!ctx) return 1;
@@ -1697,29 +1242,6 @@ int srtTemporalReset(SrtContext* ctx) {
   for (auto& h : ctx->temporalHistory) h = DeviceBuffer();
   return 0;
 }
-
-/* include/srt_hip_test.h: the render kernel's own traversal, ray by ray */
-static int srtRenderAovImpl(SrtContext* ctx, const SrtRenderParams* pIn, int32_t depth, SrtAovRecord* hOut) {
-  if (!ctx || !pIn || !hOut || depth < 0) return 1;
-  SrtRenderParams p = *pIn;
-  p.spp = 1;
-  p.sppChunks = 1;
-  p.countStats = 1;
-  p.tileFirst = 0;
-  p.tileStride = 1;
-  if (checkParams(ctx, &p)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
-  const size_t tileBytes = (size_t)srtNumTiles(p.imageWidth, p.imageHeight) * SRT_TILE_PIXELS * sizeof(float4);
-  DeviceBuffer tiles, aov;
-  if (tiles.reserve(tileBytes) != hipSuccess || aov.reserve(nPix * sizeof(SrtAovRecord)) != hipSuccess) return fail(ctx, "aov: hipMalloc");
-  if (hipMemset(aov.get(), 0, nPix * sizeof(SrtAovRecord)) != hipSuccess) return fail(ctx, "aov: memset");
-  if (srtRenderTilesImpl(ctx, &p, tiles.get(), nullptr, aov.get<SrtAovRecord>(), depth)) return 1;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "aov: render kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  if (hipMemcpy(hOut, aov.get(), nPix * sizeof(SrtAovRecord), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "aov: copy out");
-  return 0;
-}
-int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAovRecord* hOut) { SRT_GUARDED(ctx, srtRenderAovImpl(ctx, p, depth, hOut)); }
 
 /* include/srt_hip_test.h: the most recent render-kernel launch */
 int srtGetLaunchInfo(SrtContext* ctx, int32_t* out4) {

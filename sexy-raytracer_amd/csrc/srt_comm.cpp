@@ -14,15 +14,9 @@
 #include <cstdio>
 #include <cstring>
 
-#include "srt_buffer.h"
-#include "srt_device.h"
+#include "srt_context.h"
 
 extern "C" {
-// implemented in srt_api.cpp
-int srtCtxFail(SrtContext* ctx, const char* text);
-int srtCtxDevice(const SrtContext* ctx);
-void** srtCtxCommSlot(SrtContext* ctx);  // where the context keeps its ncclComm_t (opaque there)
-int* srtCtxCommRanks(SrtContext* ctx);   // [0] = number of ranks, [1] = this rank
 
 int srtCommGetUniqueId(void* id128) {
   if (!id128) return 1;
@@ -39,34 +33,30 @@ int srtCommGetUniqueId(void* id128) {
 
 int srtCommInit(SrtContext* ctx, const void* id128, int32_t numRanks, int32_t rank) {
   if (!ctx || !id128) return 1;
-  if (numRanks < 1 || rank < 0 || rank >= numRanks) return srtCtxFail(ctx, "srtCommInit: rank out of range");
-  if (*srtCtxCommSlot(ctx)) return srtCtxFail(ctx, "srtCommInit: this context already has a communicator");
-  if (hipSetDevice(srtCtxDevice(ctx)) != hipSuccess) return srtCtxFail(ctx, "srtCommInit: hipSetDevice failed");
+  if (numRanks < 1 || rank < 0 || rank >= numRanks) return fail(ctx, "srtCommInit: rank out of range");
+  if (ctx->comm) return fail(ctx, "srtCommInit: this context already has a communicator");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, "srtCommInit: hipSetDevice failed");
   ncclUniqueId id;
   memcpy(&id, id128, sizeof id);
   ncclComm_t comm = nullptr;
   ncclResult_t r = ncclCommInitRank(&comm, numRanks, id, rank);
-  if (r != ncclSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "srtCommInit: ncclCommInitRank(%d of %d) -> %s", rank, numRanks, ncclGetErrorString(r));
-    return srtCtxFail(ctx, buf);
-  }
-  *srtCtxCommSlot(ctx) = comm;
-  srtCtxCommRanks(ctx)[0] = numRanks;
-  srtCtxCommRanks(ctx)[1] = rank;
+  if (r != ncclSuccess)
+    return fail(ctx, "srtCommInit: ncclCommInitRank(%d of %d) -> %s", rank, numRanks, ncclGetErrorString(r));
+  ctx->comm = comm;
+  ctx->commRanks[0] = numRanks;
+  ctx->commRanks[1] = rank;
   return 0;
 }
 
 int srtCommDestroy(SrtContext* ctx) {
   if (!ctx) return 0;
-  void** slot = srtCtxCommSlot(ctx);
-  if (*slot) {
-    (void)hipSetDevice(srtCtxDevice(ctx));
-    (void)ncclCommDestroy(static_cast<ncclComm_t>(*slot));
-    *slot = nullptr;
+  if (ctx->comm) {
+    (void)hipSetDevice(ctx->device);
+    (void)ncclCommDestroy(static_cast<ncclComm_t>(ctx->comm));
+    ctx->comm = nullptr;
   }
-  srtCtxCommRanks(ctx)[0] = 1;
-  srtCtxCommRanks(ctx)[1] = 0;
+  ctx->commRanks[0] = 1;
+  ctx->commRanks[1] = 0;
   return 0;
 }
 
@@ -75,27 +65,23 @@ int srtCommDestroy(SrtContext* ctx) {
 // srtResolveTiles un-permutes.  Asynchronous on `stream`.
 int srtGatherTiles(SrtContext* ctx, const SrtRenderParams* p, const void* dLocalTiles, void* dGathered, void* streamPtr) {
   if (!ctx || !p || !dLocalTiles) return 1;
-  const int numRanks = srtCtxCommRanks(ctx)[0], rank = srtCtxCommRanks(ctx)[1];
+  const int numRanks = ctx->commRanks[0], rank = ctx->commRanks[1];
   if (p->tileStride != numRanks || p->tileFirst != rank)
-    return srtCtxFail(ctx, "srtGatherTiles: the tile split of the render parameters is not this communicator's (tileStride = ranks, tileFirst = rank)");
+    return fail(ctx, "srtGatherTiles: the tile split of the render parameters is not this communicator's (tileStride = ranks, tileFirst = rank)");
   const size_t count = (size_t)srtNumLocalTiles(p->imageWidth, p->imageHeight, p->tileStride) * SRT_TILE_PIXELS * 4;  // floats
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-  if (hipSetDevice(srtCtxDevice(ctx)) != hipSuccess) return srtCtxFail(ctx, "srtGatherTiles: hipSetDevice failed");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, "srtGatherTiles: hipSetDevice failed");
   if (numRanks == 1) {  // nothing to exchange: the gathered buffer is the local one
     if (dGathered && dGathered != dLocalTiles &&
         hipMemcpyAsync(dGathered, dLocalTiles, count * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
-      return srtCtxFail(ctx, "srtGatherTiles: copy failed");
+      return fail(ctx, "srtGatherTiles: copy failed");
     return 0;
   }
-  ncclComm_t comm = static_cast<ncclComm_t>(*srtCtxCommSlot(ctx));
-  if (!comm) return srtCtxFail(ctx, "srtGatherTiles: no communicator (srtCommInit)");
-  if (rank == 0 && !dGathered) return srtCtxFail(ctx, "srtGatherTiles: rank 0 needs the gathered buffer");
+  ncclComm_t comm = static_cast<ncclComm_t>(ctx->comm);
+  if (!comm) return fail(ctx, "srtGatherTiles: no communicator (srtCommInit)");
+  if (rank == 0 && !dGathered) return fail(ctx, "srtGatherTiles: rank 0 needs the gathered buffer");
   ncclResult_t r = ncclGather(dLocalTiles, dGathered, count, ncclFloat32, 0, comm, stream);
-  if (r != ncclSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "srtGatherTiles: ncclGather -> %s", ncclGetErrorString(r));
-    return srtCtxFail(ctx, buf);
-  }
+  if (r != ncclSuccess) return fail(ctx, "srtGatherTiles: ncclGather -> %s", ncclGetErrorString(r));
   return 0;
 }
 
@@ -104,11 +90,11 @@ int srtGatherTiles(SrtContext* ctx, const SrtRenderParams* p, const void* dLocal
 // HOST buffers (hAccum float[W*H*4], hRgba uint8[W*H*4]; either may be NULL, both are ignored on other ranks).
 int srtRenderImageRanks(SrtContext* ctx, const SrtRenderParams* pIn, float* hAccum, uint8_t* hRgba) {
   if (!ctx || !pIn) return 1;
-  const int numRanks = srtCtxCommRanks(ctx)[0], rank = srtCtxCommRanks(ctx)[1];
+  const int numRanks = ctx->commRanks[0], rank = ctx->commRanks[1];
   SrtRenderParams p = *pIn;
   p.tileFirst = rank;
   p.tileStride = numRanks;
-  if (hipSetDevice(srtCtxDevice(ctx)) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: hipSetDevice failed");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, "srtRenderImageRanks: hipSetDevice failed");
   const size_t nPix = (size_t)p.imageWidth * p.imageHeight;
   const size_t localBytes = (size_t)srtNumLocalTiles(p.imageWidth, p.imageHeight, numRanks) * SRT_TILE_PIXELS * sizeof(float4);
   DeviceBuffer local, gathered, rgba, acc, agree;
@@ -116,34 +102,34 @@ int srtRenderImageRanks(SrtContext* ctx, const SrtRenderParams* pIn, float* hAcc
   // returned here while the others entered ncclGather would leave them waiting for ever.  The agreement is a
   // 4-byte all-reduce (minimum of the ranks' status); only a rank that cannot even allocate those 4 bytes leaves
   // without taking part -- its peers then need ncclCommAbort (srtCommDestroy), as after any lost rank.
-  if (numRanks > 1 && agree.reserve(sizeof(int32_t)) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc (4 bytes)");
+  if (numRanks > 1 && agree.reserve(sizeof(int32_t)) != hipSuccess) return fail(ctx, "srtRenderImageRanks: hipMalloc (4 bytes)");
   int32_t ok = 1;
-  if (local.reserve(localBytes) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+  if (local.reserve(localBytes) != hipSuccess) { fail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
   if (ok && rank == 0) {
-    if (gathered.reserve(localBytes * numRanks) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
-    if (ok && hRgba && rgba.reserve(nPix * 4) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
-    if (ok && hAccum && acc.reserve(nPix * sizeof(float4)) != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+    if (gathered.reserve(localBytes * numRanks) != hipSuccess) { fail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+    if (ok && hRgba && rgba.reserve(nPix * 4) != hipSuccess) { fail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
+    if (ok && hAccum && acc.reserve(nPix * sizeof(float4)) != hipSuccess) { fail(ctx, "srtRenderImageRanks: hipMalloc"); ok = 0; }
   }
   if (ok && srtRenderTiles(ctx, &p, local.get(), nullptr)) ok = 0;
-  if (ok && hipDeviceSynchronize() != hipSuccess) { srtCtxFail(ctx, "srtRenderImageRanks: render kernel failed"); ok = 0; }
+  if (ok && hipDeviceSynchronize() != hipSuccess) { fail(ctx, "srtRenderImageRanks: render kernel failed"); ok = 0; }
   if (numRanks > 1) {
-    ncclComm_t comm = static_cast<ncclComm_t>(*srtCtxCommSlot(ctx));
+    ncclComm_t comm = static_cast<ncclComm_t>(ctx->comm);
     int32_t agreed = 0;
-    if (!comm) return srtCtxFail(ctx, "srtRenderImageRanks: no communicator (srtCommInit)");
+    if (!comm) return fail(ctx, "srtRenderImageRanks: no communicator (srtCommInit)");
     if (hipMemcpy(agree.get(), &ok, sizeof ok, hipMemcpyHostToDevice) != hipSuccess ||
         ncclAllReduce(agree.get(), agree.get(), 1, ncclInt32, ncclMin, comm, nullptr) != ncclSuccess ||
         hipMemcpy(&agreed, agree.get(), sizeof agreed, hipMemcpyDeviceToHost) != hipSuccess)
-      return srtCtxFail(ctx, "srtRenderImageRanks: the ranks could not agree on the render's status");
-    if (!agreed) return ok ? srtCtxFail(ctx, "srtRenderImageRanks: another rank failed before the gather") : 1;
+      return fail(ctx, "srtRenderImageRanks: the ranks could not agree on the render's status");
+    if (!agreed) return ok ? fail(ctx, "srtRenderImageRanks: another rank failed before the gather") : 1;
   } else if (!ok) {
     return 1;
   }
   if (srtGatherTiles(ctx, &p, local.get(), gathered.get(), nullptr)) return 1;
   if (rank == 0 && srtResolveTiles(ctx, &p, gathered.get(), rgba.get(), acc.get(), nullptr)) return 1;
-  if (hipDeviceSynchronize() != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: gather or resolve failed");
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "srtRenderImageRanks: gather or resolve failed");
   if (rank == 0) {
-    if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: copy rgba");
-    if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return srtCtxFail(ctx, "srtRenderImageRanks: copy accum");
+    if (hRgba && hipMemcpy(hRgba, rgba.get(), nPix * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "srtRenderImageRanks: copy rgba");
+    if (hAccum && hipMemcpy(hAccum, acc.get(), nPix * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "srtRenderImageRanks: copy accum");
   }
   return 0;
 }

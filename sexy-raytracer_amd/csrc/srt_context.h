@@ -1,0 +1,141 @@
+// srt_context.h -- the context behind the C ABI's SrtContext* and what the host translation units share around it: error
+// reporting, and the device-level entries (srt_api.cpp) that the whole-frame entries (srt_frames.cpp) compose.  Internal:
+// none of this is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "srt_buffer.h"
+#include "srt_device.h"
+#include "srt_scene.h"
+
+// Diagnostic tunables of the work distribution and the wave scheduler.  Environment variables give the
+// defaults ONCE, at srtCreate; srtSetTunable (include/srt_hip_test.h) changes them per context.  -1 = the
+// library's own rule.
+struct Tunables {
+  int tileBlock, unitTiles, queues;
+  int shadeMin, primMin, hitMin, fuseMin, nodeBurst;
+  int plocRadius, fastDiv;
+  int chunkScratchMb;
+  int primAgainMin;
+  int keepEighths;
+  int ldsTree;
+  int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
+  int wfHybrid, wfResidentMax, wfFarRounds;
+  int denoiseLdsStep;
+};
+
+struct SrtContext {
+  int device = 0;
+  std::string error;
+  Tunables tun{};
+  hipDeviceProp_t prop;
+  // device scene
+  std::vector<DeviceBuffer> sceneBuffers;
+  DevScene scene{};
+  DevCamera cam{};
+  bool haveScene = false, haveCamera = false;
+  // host copies for srtGetBvh
+  std::vector<std::vector<SrtBvhNode>> itemNodes;
+  std::vector<DeviceBuild> deviceBuilds;  // where the device-built trees live in scene.nodes (without their refs)
+  std::vector<int32_t> hostTriPrimId, hostSphPrimId;
+  int bvhDepth = 0;
+  // work areas
+  DeviceBuffer dQueue;
+  DeviceBuffer dStats;
+  void* comm = nullptr;          // ncclComm_t (srt_comm.cpp)
+  int commRanks[2] = {1, 0};     // number of ranks, this rank
+  DeviceBuffer chunkScratch;
+  DeviceBuffer attScratch;  // LDS-resident-tree kernel: the lanes' attenuation stacks (srt_render_kernel LDSTREE)
+  DeviceBuffer wfPool, wfAttHi;  // path-pool kernel: contexts and upper attenuation levels (srt_wavefront.hip)
+  int32_t* dWfError = nullptr;
+  DeviceBuffer dFeatureCounter;  // the feature passes' tile counter (their own: a render's queues are never touched)
+  DeviceBuffer denoiseScratch;   // srtDenoise: guide records, depth gradients, two colour buffers (56 B per pixel)
+  DeviceBuffer tileTable;   // RenderArgs::tileXY for the image size and tile order below
+  // srtRenderAdaptive: one launch's beauty and moments tiles, two tile lists (this launch's, the next one's), the per-tile
+  // flags and the compaction's {count, pixels}
+  DeviceBuffer adaptTiles, adaptList[2], adaptFlags, adaptCounts;
+  // srtRenderTemporalFrame: the two histories (the one the last frame wrote, the one the next writes), what they belong to,
+  // and the camera as srtSetCamera received it (DevCamera drops w)
+  DeviceBuffer temporalHistory[2];
+  DeviceBuffer temporalReprojected;  // srtRenderTemporalAdaptive: the frame's reprojected history (32 B per pixel)
+  int32_t temporalCurrent = 0;  // index of the history the last frame wrote
+  bool temporalValid = false;
+  int32_t temporalKey[3] = {0, 0, 0};  // width, height, demodulate
+  SrtCamera camFull{}, temporalCam{};
+  int32_t tileTableKey[3] = {0, 0, 0};
+  RenderPlan lastPlan{};  // the most recent render launch (srtGetLaunchInfo)
+  int32_t lastGrid = 0;
+  hipEvent_t evStart = nullptr, evStop = nullptr;
+  bool timed = false;
+};
+
+// Records the text in the context (srtLastError), reports it on stderr and returns 1
+int fail(SrtContext* ctx, const char* fmt, ...);
+
+// A path-pool launch that gave up (a ring wait exceeded its bound, srt_wavefront.hip) has added to the context's error
+// word: the frame is incomplete.  Checked wherever the host has waited for the device anyway.
+int wfCheck(SrtContext* ctx);
+
+#define HIP_OK(ctx, call)                                                                   \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess) return fail(ctx, "%s -> %s", #call, hipGetErrorString(e_));       \
+  } while (0)
+
+// No exception crosses the C boundary (std::vector / std::string allocations may throw).
+#define SRT_GUARDED(ctx, call)                                                  \
+  try {                                                                         \
+    return (call);                                                              \
+  } catch (const std::exception& e) {                                           \
+    return fail(ctx, "%s: %s", __func__, e.what());                             \
+  } catch (...) {                                                               \
+    return fail(ctx, "%s: unknown exception", __func__);                        \
+  }
+
+// srtRenderTemporalAdaptive: the decisions pool the frame's moments with this reprojected history (srt_temporal_adaptive.hip)
+struct AdaptivePool {
+  const float4* reprojected;  // two planes, SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL
+  const float4* albedo;       // null unless the history is demodulated
+};
+
+// srtRenderAdaptiveGuided / srtRenderTemporalAdaptiveGuided: image-order feature planes that follow the rounds
+// (srt_features_list.hip): after launch r its list and sample range go through the list kernel
+struct AdaptiveGuides {
+  int32_t planes;       // SRT_FEATURE_* bits
+  void* const* images;  // [4], float4[W*H] for every selected bit
+  bool storeFirst;      // round 0 is stored over the whole tile table; false: the planes hold round 0 already
+};
+
+// The device-level entries behind the exported ones and their argument checks (srt_api.cpp, where each is described)
+int checkParams(SrtContext* ctx, const SrtRenderParams* p);
+int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr,
+                       SrtAovRecord* aov = nullptr, int32_t aovDepth = 0, void* dMoments = nullptr,
+                       const uint32_t* dList = nullptr, int32_t listTiles = 0);
+int checkAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, bool device, const void* dAccum,
+                  const void* dMoments);
+int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtAdaptiveParams* ap, void* dAccumImage,
+                          void* dMomentsImage, void* dRgba, SrtAdaptiveStats* stats, void* streamPtr,
+                          const AdaptivePool* pool = nullptr, const AdaptiveGuides* guides = nullptr);
+int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* const* buffers);
+int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* streamPtr);
+int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, DenoiseArgs& a,
+                       int& iterations, bool moments = false);
+int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
+                   const void* const dPlanes[4], void* dOut, void* dRgba, void* streamPtr, bool moments = false,
+                   const void* dMoments = nullptr);
+int checkTemporalParams(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, TemporalArgs& a);
+int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
+                              const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
+                              const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
+                              void* dHistoryOut, void* streamPtr);
+int temporalStats(SrtContext* ctx, size_t nPix, const void* dCurrent, const void* dAccumulated, const void* dHistory,
+                  SrtTemporalStats* stats);
+int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap,
+                                  const SrtTemporalParams* t, const void* const dPlanes[4], const SrtCamera* prevCam,
+                                  const void* dHistoryIn, void* dAccumImage, void* dMomentsImage, void* dBeautyOut,
+                                  void* dMomentsOut, void* dHistoryOut, SrtTemporalAdaptiveStats* stats, void* streamPtr,
+                                  bool guided = false);

@@ -168,6 +168,8 @@ def test_errors_launch_nothing_and_leave_no_trace(ctx, dev, abi, srt, camera):
     bad(accum=False)
     bad(moments=False)
     bad(sppChunks=5)  # more chunks than the first round's samples
+    with pytest.raises(dev.SrtError, match="sppMax"):  # the blocking entry: the same checks before it allocates or launches
+        ctx.render_adaptive(abi.default_render_params(97, 61, 4, 4, seed=4, spp_chunks=0), abi.default_adaptive_params(3, 0.01))
     torch.cuda.synchronize()
     assert (d[0] == 7.0).all() and (d[1] == 7.0).all()
     assert ctx.launch_info() == info and ctx.last_kernel_ms() == ms  # nothing launched

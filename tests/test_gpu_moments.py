@@ -258,6 +258,11 @@ def test_launch_info_and_errors(ctx, dev, abi, srt, camera):
         assert ctx.launch_info() == info and ctx.last_kernel_ms() == ms, msg
     with pytest.raises(dev.SrtError, match="countStats"):
         ctx.render_image_moments(abi.default_render_params(W, H, 8, 4, count_stats=1))
+    with pytest.raises(dev.SrtError, match="countStats"):
+        ctx.render_denoised_moments(abi.default_render_params(97, 61, 8, 4, count_stats=1))
+    with pytest.raises(dev.SrtError, match="maxBounce"):
+        ctx.render_aov(abi.default_render_params(97, 61, 8, 99))
+    assert ctx.launch_info() == info and ctx.last_kernel_ms() == ms  # the blocking entries launched nothing either
     assert {k: ctx.get_tunable(k) for k in tun} == tun
     # wf_profile is ignored by a moments launch: the same bits and launch as without it
     want = _tiles(ctx, dev, abi, p)[1]
