@@ -5,7 +5,7 @@
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
 //                  [--denoise FILE.png [--sample-variance]] [--adaptive THRESHOLD --max-spp N]
-//                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]]
+//                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]] [--frames N --spin DEG]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
@@ -22,6 +22,10 @@
 //                     its history, so disoccluded tiles get up to M samples and settled ones stop at --spp; frame k
 //                     draws its samples from k * M.  --guide-all-samples: the feature planes follow the rounds, so the
 //                     accumulation, the history and the denoiser are guided by all of a tile's samples, not its first --spp
+//   --frames N --spin D  moving geometry: before frame k >= 1 the model's triangles, as loaded, are turned by k * D degrees
+//                     about the vertical axis on the host and go to the device with hipDevice::updateTriangles + refit (no
+//                     second upload: the trees keep their shape and get new boxes); every frame is rendered on its own
+//                     (rtFrame, samples from 0) to NAME_%03d.png.  Not with --temporal: the reprojection assumes a static scene
 //   SRT_DATA_DIR selects the directory of the glTF's images (default "../data/", as the reference).
 #include <chrono>
 #include <cstdlib>
@@ -93,6 +97,8 @@ int main(int argc, char** argv) {
   bool sampleVariance = false, temporal = false, guideAll = false;
   int frames = 0;        // > 0: a sequence, NAME_%03d.png
   float orbit = 0.0f;    // degrees the eye turns about the lookAt point's vertical axis over the sequence
+  float spin = 0.0f;     // degrees per frame the model's triangles turn about the vertical axis
+  bool spinning = false;
   for (int i = 1; i < argc; i += 2) {
     if (!strcmp(argv[i], "--sample-variance") || !strcmp(argv[i], "--temporal") || !strcmp(argv[i], "--guide-all-samples")) {
       (argv[i][2] == 't' ? temporal : argv[i][2] == 'g' ? guideAll : sampleVariance) = true;  // the flags without a value
@@ -112,6 +118,18 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--max-spp")) maxSpp = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--frames")) frames = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--orbit")) orbit = strtof(argv[i + 1], nullptr);
+    else if (!strcmp(argv[i], "--spin")) {
+      spin = strtof(argv[i + 1], nullptr);
+      spinning = true;
+    }
+  }
+  if (spinning && temporal) {
+    std::cerr << "ERROR: --spin moves the geometry and --temporal reprojects a static scene: use one of them\n";
+    return 1;
+  }
+  if (spinning && frames < 1) {
+    std::cerr << "ERROR: --spin needs --frames N\n";
+    return 1;
   }
   const float aspect = 16.0f / 9.0f;
   const int imageWidth = static_cast<int>(imageHeight * aspect);
@@ -138,6 +156,29 @@ int main(int argc, char** argv) {
     const std::string stem = out.size() > 4 && out.substr(out.size() - 4) == ".png" ? out.substr(0, out.size() - 4) : out;
     std::vector<uint8_t> frame((size_t)4 * imageWidth * imageHeight);
     for (int k = 0; k < frames; ++k) {
+      if (spinning) {
+        // frame k: every triangle of the scene as loaded, turned by k * spin degrees about the vertical axis; update + refit
+        if (k > 0) {
+          const double a = (double)spin * k * (3.14159265358979323846 / 180.0);
+          const float c = (float)std::cos(a), s = (float)std::sin(a);
+          std::vector<SrtTriangleIn> moved = device.triangles;
+          for (SrtTriangleIn& t : moved)
+            for (int v = 0; v < 3; ++v) {
+              const float x = t.p[v][0], z = t.p[v][2];
+              t.p[v][0] = c * x + s * z;
+              t.p[v][2] = c * z - s * x;
+            }
+          if (!device.updateTriangles(0, moved) || !device.refit()) return 1;
+        }
+        if (!device.rtFrame(frame.data(), imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
+        char name[32];
+        snprintf(name, sizeof name, "_%03d.png", k);
+        if (!stbi_write_png((stem + name).c_str(), imageWidth, imageHeight, 4, frame.data(), 4 * imageWidth)) {
+          std::cerr << "ERROR: could not write " << stem << name << "\n";
+          return 1;
+        }
+        continue;
+      }
       const double angle = frames > 1 ? (double)orbit * k / (frames - 1) * (3.14159265358979323846 / 180.0) : 0.0;
       const float c = (float)std::cos(angle), s = (float)std::sin(angle);
       const vec3f eyeK(lookAt(0) + (c * dx + s * dz), eye(1), lookAt(2) + (c * dz - s * dx));
@@ -168,7 +209,8 @@ int main(int argc, char** argv) {
     device.terminate();
     free(target);
     std::cerr << frames << " frames of " << imageWidth << "x" << imageHeight << " @" << numSamples << " spp, "
-              << (steered ? "temporal accumulation with history-steered sampling" : temporal ? "temporal accumulation" : "frame by frame")
+              << (spinning ? "geometry updated and refitted between frames"
+                  : steered ? "temporal accumulation with history-steered sampling" : temporal ? "temporal accumulation" : "frame by frame")
               << " -> " << stem << "_000.png ...\nDone.\n";
     return 0;
   }

@@ -723,6 +723,54 @@ int srtRenderTemporalAdaptiveGuidedFrame(SrtContext* ctx, const SrtRenderParams*
                                          const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum, float* hDenoised,
                                          uint8_t* hRgba, SrtTemporalAdaptiveStats* stats);
 
+/* Moving geometry: the primitive records of the uploaded scene rewritten in place, then every tree refitted on the
+ * device.  Topology never changes: the trees, nodeAxis, the world list, the thread links, the stack depth, srtGetBvhDepth,
+ * the triangles' device order, the material tables and every primitive's material stay as srtUploadScene left them.
+ *
+ * srtUpdateTriangles / srtUpdateSpheres   HOST records; `first`, `count` index the uploaded SrtSceneDesc's triangles[] /
+ *             spheres[].  The records are staged in device memory the context keeps and handed to the device forms on the
+ *             NULL stream; the host memory may be reused when the call returns.
+ * srtUpdateTrianglesDevice / srtUpdateSpheresDevice   the same records in DEVICE memory (SrtTriangleIn aligned to 16 bytes,
+ *             SrtSphereIn to 4), asynchronous on `stream`: dIn must stay untouched until the stream has passed the call.
+ *   taken     a triangle's positions and uvs; a sphere's centres, times and radius.  From them the device computes what
+ *             srtUploadScene computes on the host, in the same operations (the geometric normal, its unit vector, the tangent
+ *             basis with its f == 0 -> f += epsilon rule; the sphere's "moving" bit from center0 != center1): the records
+ *             are, bit for bit, those of an upload of the same data.
+ *   ignored   the `material` field.  A primitive keeps its material, so the per-material tables stay valid.
+ *   errors    no scene uploaded; first < 0, count < 0 or first + count beyond the scene's count; a NULL or misaligned
+ *             pointer with count > 0.  Nothing is launched or changed then.  count == 0 (in range) is a no-op.
+ *   after     any update that launched: every render / feature / trace / scatter entry returns an error ("geometry was
+ *             updated; call srtRefitScene ...") WITHOUT launching anything until srtRefitScene has run -- the node boxes no
+ *             longer contain their primitives.  Updates may follow one another freely (ranges may overlap: stream order).
+ *
+ * srtRefitScene   recomputes every node box of every SRT_WORLD_BVH item -- host-built, caller-supplied, LBVH and PLOC trees
+ *             alike -- from the current primitive records: a primitive's box by the reference's boundingBox rules with its
+ *             item's (time0, time1), a node's box the min / max union of its children's (bottom-up, one kernel per item, no
+ *             waiting; the result does not depend on the order of arrival).  Then everything derived from boxes: the
+ *             closest-hit pair records, the box halves of the path-pool kernel's hybrid records (the resident set chosen at
+ *             upload stays: it decides only where a record is read from), the fast-division certificate (recomputed on the
+ *             device over the node boxes and the device-built items' primitive boxes: the scene is certified exactly when an
+ *             upload of the moved scene would have certified it), and what srtGetBvh returns (the refit boxes, read back
+ *             when asked for).  Work is issued on `stream` -- the stream the updates went to, or one ordered behind them --
+ *             and has FINISHED when the call returns: it reads the certificate's flag word back.
+ *   FAITHFUL  after a refit FAITHFUL traversal means: bvh.h:97-105 on the UPLOADED topology with the new boxes -- what the
+ *             reference's bvhNode::hit does on a tree whose boxes were recomputed -- not what a freshly constructed bvhNode
+ *             over the moved primitives would do (its median splits would sort differently).  CLOSEST results do not
+ *             depend on the tree; its speed does, see DESIGN.md 5.13 on when to upload again instead.
+ *   history   srtRefitScene drops the context's temporal history exactly as srtUploadScene does (the next
+ *             srtRenderTemporalFrame is a first frame): the reprojection assumes static surfaces.
+ *   untouched the host generator, the tunables (fast_div as read at the upload), srtGetStats, and srtLastKernelMs / srtGetLaunchInfo,
+ *             which keep describing the last render.
+ *   errors    no scene uploaded; a failed launch.  A scene without trees (bare primitives only) just becomes renderable.
+ * Device memory held by the context from the first call on, until the next srtUploadScene or srtDestroy: 4 bytes per
+ * triangle (scene index -> device index, when the upload reordered), 8 bytes per node (parent links, arrival counters), 4
+ * more per node with hybrid records, and the host forms' staging (the largest update's records). */
+int srtUpdateTriangles(SrtContext* ctx, int32_t first, int32_t count, const SrtTriangleIn* hTriangles);
+int srtUpdateSpheres(SrtContext* ctx, int32_t first, int32_t count, const SrtSphereIn* hSpheres);
+int srtUpdateTrianglesDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dTriangles, void* stream);
+int srtUpdateSpheresDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dSpheres, void* stream);
+int srtRefitScene(SrtContext* ctx, void* stream);
+
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the
  * ranks' equal-sized tile buffers to rank 0 over RCCL (ncclGather), after which rank 0 calls

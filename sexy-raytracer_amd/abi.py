@@ -150,11 +150,16 @@ HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("normal",
 AOV_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("time", "<f4"), ("valid", "<i4"), ("prim", "<i4"), ("t", "<f4"),
                       ("nodeVisits", "<i4"), ("boxPasses", "<i4"), ("triTests", "<i4"), ("sphereTests", "<i4"), ("pad", "<i4", 2)])
 assert AOV_DTYPE.itemsize == 64
+# SrtTriangleIn / SrtSphereIn as arrays: what SceneBuilder keeps and Context.update_triangles / update_spheres take
+TRIANGLE_DTYPE = np.dtype([("p", "<f4", (3, 3)), ("uv", "<f4", (3, 2)), ("material", "<i4")])
+SPHERE_DTYPE = np.dtype([("center0", "<f4", 3), ("center1", "<f4", 3), ("time0", "<f4"), ("time1", "<f4"),
+                         ("radius", "<f4"), ("material", "<i4")])
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("left", "<i4"), ("bmax", "<f4", 3), ("right", "<i4")])
 assert RAY_DTYPE.itemsize == C.sizeof(SrtRay)
 assert HIT_DTYPE.itemsize == C.sizeof(SrtHit)
 assert NODE_DTYPE.itemsize == C.sizeof(SrtBvhNode) == 32
-assert C.sizeof(SrtTriangleIn) == 64
+assert C.sizeof(SrtTriangleIn) == TRIANGLE_DTYPE.itemsize == 64
+assert C.sizeof(SrtSphereIn) == SPHERE_DTYPE.itemsize == 40
 
 
 def default_render_params(width, height, spp, max_bounce, seed=1, background=(0.53, 0.81, 0.92),

@@ -25,6 +25,7 @@ int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0,
 int srt_ploc_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
                    uint8_t* outAxis, int base, int radius, int* depthOut);
 int srt_pair_nodes(const DevScene* sc, float time0, float time1, float4* out);
+int srt_pair_nodes_async(const DevScene* sc, float time0, float time1, float4* out, hipStream_t stream);
 int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint64_t seed, int n,
                        hipStream_t stream);
 int srt_features_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU);
@@ -221,6 +222,13 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   ctx->itemNodes.clear();
   ctx->deviceBuilds.clear();
   ctx->bvhDepth = 0;
+  ctx->trees.clear();
+  ctx->geometryDirty = false;
+  ctx->refitTables = false;
+  ctx->triDevIndex = DeviceBuffer();
+  ctx->wfIndex = DeviceBuffer();
+  ctx->refitUp = DeviceBuffer();
+  ctx->refitArrived = DeviceBuffer();
   std::string err = validateScene(d);
   HostScene h;
   if (err.empty()) err = flattenScene(d, SceneOptions{ctx->tun.wfHybrid, ctx->tun.wfResidentMax, ctx->tun.fastDiv}, h);
@@ -279,6 +287,15 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   if (rc) return fail(ctx, "pairing the node records failed: %s", hipGetErrorString((hipError_t)rc));
   ctx->itemNodes = std::move(h.itemNodes);
   ctx->deviceBuilds = std::move(h.deviceBuilds);
+  // what an update and a refit need of this upload (srt_refit_host.cpp)
+  for (const HostTree& t : h.hostTrees) ctx->trees.push_back(SrtContext::Tree{t.item, t.base, t.count, t.time0, t.time1, false});
+  for (const DeviceBuild& b : ctx->deviceBuilds) ctx->trees.push_back(SrtContext::Tree{b.item, b.base, b.count, b.time0, b.time1, true});
+  ctx->hostTriDevIndex = std::move(h.triDevIndex);
+  ctx->hostWfIndex = std::move(h.wfIndex);
+  ctx->itemBoxesStale.assign(ctx->itemNodes.size(), 0);
+  ctx->pairTime0 = t0;
+  ctx->pairTime1 = t1;
+  ctx->fastDivOption = ctx->tun.fastDiv;
   ctx->hostTriPrimId = std::move(h.triPrimId);
   ctx->hostSphPrimId = std::move(h.sphPrimId);
   ctx->haveScene = true;
@@ -306,6 +323,23 @@ static int srtGetBvhImpl(SrtContext* ctx, int32_t item, SrtBvhNode* nodes, int32
   if (!ctx || !count) return 1;
   if (item < 0 || item >= (int32_t)ctx->itemNodes.size()) return fail(ctx, "srtGetBvh: item %d out of range", item);
   const auto dt = std::find_if(ctx->deviceBuilds.begin(), ctx->deviceBuilds.end(), [&](const DeviceBuild& b) { return b.item == item; });
+  if (ctx->itemBoxesStale[item]) {
+    // srtRefitScene has moved the boxes since this copy was made: a device-built tree is read back again (below), a
+    // host-built one gets the device's boxes (its children stay in the host convention)
+    ctx->itemBoxesStale[item] = 0;
+    auto& out = ctx->itemNodes[item];
+    const auto tr = std::find_if(ctx->trees.begin(), ctx->trees.end(), [&](const SrtContext::Tree& t) { return t.item == item; });
+    if (dt != ctx->deviceBuilds.end()) {
+      out.clear();
+    } else if (tr != ctx->trees.end() && !out.empty()) {
+      std::vector<float4> raw((size_t)tr->count * 2);
+      HIP_OK(ctx, hipMemcpy(raw.data(), ctx->scene.nodes + 2 * (size_t)tr->base, raw.size() * sizeof(float4), hipMemcpyDeviceToHost));
+      for (int i = 0; i < tr->count; ++i) {
+        out[i].bmin[0] = raw[2 * i].x; out[i].bmin[1] = raw[2 * i].y; out[i].bmin[2] = raw[2 * i].z;
+        out[i].bmax[0] = raw[2 * i + 1].x; out[i].bmax[1] = raw[2 * i + 1].y; out[i].bmax[2] = raw[2 * i + 1].z;
+      }
+    }
+  }
   if (dt != ctx->deviceBuilds.end() && ctx->itemNodes[item].empty()) {
     // device-built tree: read it back once, converting child refs to the host convention
     std::vector<float4> raw((size_t)dt->count * 2);
@@ -380,8 +414,14 @@ int32_t srtPlanSppChunks(int32_t imageWidth, int32_t imageHeight, int32_t spp, i
   return (int32_t)std::min<int64_t>(srtDefaultSppChunks(spp), maxChunks);
 }
 
+extern "C++" int checkSceneReady(SrtContext* ctx, const char* what) {
+  if (!ctx->haveScene) return fail(ctx, "%s: no scene uploaded", what);
+  if (ctx->geometryDirty) return fail(ctx, "%s: geometry was updated; call srtRefitScene before anything traverses the scene", what);
+  return 0;
+}
+
 extern "C++" int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
-  if (!ctx->haveScene) return fail(ctx, "render: no scene uploaded");
+  if (checkSceneReady(ctx, "render")) return 1;
   if (!ctx->haveCamera) return fail(ctx, "render: no camera set");
   if (p->imageWidth < 2 || p->imageHeight < 2) return fail(ctx, "render: image must be at least 2x2 (u,v divide by W-1,H-1)");
   if (p->imageWidth > 65535 * SRT_TILE_W || p->imageHeight > 65535 * SRT_TILE_H) return fail(ctx, "render: image larger than 65535 tiles a side");
@@ -798,7 +838,7 @@ extern "C++" int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* p
 
 int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, int32_t traversal) {
   if (!ctx || !rays || !hits || n < 0) return 1;
-  if (!ctx->haveScene) return fail(ctx, "trace: no scene uploaded");
+  if (checkSceneReady(ctx, "trace")) return 1;
   if (n == 0) return 0;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   DeviceBuffer dRays, dHits;
@@ -822,7 +862,7 @@ int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, i
 
 int srtScatterRays(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, float* out13) {
   if (!ctx || !rays || !hits || !out13 || n < 1) return 1;
-  if (!ctx->haveScene) return fail(ctx, "scatter: no scene uploaded");
+  if (checkSceneReady(ctx, "scatter")) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   for (int i = 0; i < n; ++i)
     if (hits[i].material < 0) return fail(ctx, "scatter: hit %d has no material", i);

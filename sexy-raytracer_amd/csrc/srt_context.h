@@ -43,6 +43,22 @@ struct SrtContext {
   std::vector<DeviceBuild> deviceBuilds;  // where the device-built trees live in scene.nodes (without their refs)
   std::vector<int32_t> hostTriPrimId, hostSphPrimId;
   int bvhDepth = 0;
+  // srtUpdateTriangles / srtUpdateSpheres / srtRefitScene (srt_refit_host.cpp).  Every tree of the world list with its node
+  // slots and times, the host tables the upload left (moved to the device by the first call that needs them), and the
+  // refit's own device state: parent links, arrival counters, the certificate's flag word, the host entries' staging.
+  struct Tree {
+    int32_t item, base, count;
+    float time0, time1;
+    bool deviceBuilt;
+  };
+  std::vector<Tree> trees;
+  std::vector<int32_t> hostTriDevIndex, hostWfIndex;  // HostScene::triDevIndex, wfIndex
+  std::vector<uint8_t> itemBoxesStale;                // per world item: itemNodes holds boxes from before a refit
+  DeviceBuffer triDevIndex, wfIndex, refitUp, refitArrived, refitFlag, refitStage;
+  bool refitTables = false;         // refitUp (and wfIndex) hold this scene's tables
+  bool geometryDirty = false;       // an update since the last refit: nothing renders
+  float pairTime0 = 0, pairTime1 = 0;  // the times the closest-hit pair records were made for
+  int32_t fastDivOption = 0;        // SceneOptions::fastDiv of the upload: what fastDivScene is while the certificate holds
   // work areas
   DeviceBuffer dQueue;
   DeviceBuffer dStats;
@@ -112,6 +128,8 @@ struct AdaptiveGuides {
 
 // The device-level entries behind the exported ones and their argument checks (srt_api.cpp, where each is described)
 int checkParams(SrtContext* ctx, const SrtRenderParams* p);
+// "no scene uploaded", or an update that srtRefitScene has not followed: `what` names the entry.  Launches nothing.
+int checkSceneReady(SrtContext* ctx, const char* what);
 int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr,
                        SrtAovRecord* aov = nullptr, int32_t aovDepth = 0, void* dMoments = nullptr,
                        const uint32_t* dList = nullptr, int32_t listTiles = 0);

@@ -1,0 +1,228 @@
+// srt_refit.hip -- geometry updates in place (include/srt_hip.h srtUpdateTriangles / srtUpdateSpheres / srtRefitScene):
+// the primitive records rewritten from caller data, every node box refitted bottom-up over the uploaded topology, and
+// what is derived from boxes refreshed.  Topology (the reference words of every record, nodeAxis, the thread links) is
+// never written.
+//
+// The record kernels restate flattenScene's arithmetic (srt_scene.cpp) operation for operation; this file is built with
+// -ffp-contract=off and IEEE division / sqrt like the rest, so a record carries the bits an upload of the same data gives.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "srt_device.h"
+#include "srt_prim_box.h"
+
+namespace {
+
+struct V3 {
+  float x, y, z;
+};
+__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ V3 unit(V3 v) {  // vec3.h:54-60
+  const float len = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
+  if (len != 0) return V3{v.x / len, v.y / len, v.z / len};
+  return v;
+}
+
+// One lane per updated triangle: SrtTriangleIn (64 B, four 16-byte loads) -> triTest and triShade at the triangle's DEVICE
+// index.  The material word (index, type and flag bits) stays.  devIndex: scene triangle index -> device index, null =
+// identity.
+__global__ void refitTriRecords(const float4* in, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float4 a = in[4 * (size_t)i], b = in[4 * (size_t)i + 1], c = in[4 * (size_t)i + 2], d = in[4 * (size_t)i + 3];
+  const V3 v0{a.x, a.y, a.z}, v1{a.w, b.x, b.y}, v2{b.z, b.w, c.x};
+  const float uv[3][2] = {{c.y, c.z}, {c.w, d.x}, {d.y, d.z}};
+  const size_t j = (size_t)(devIndex ? devIndex[first + i] : first + i);
+  const V3 n = cross(sub(v1, v0), sub(v2, v0));  // getNormal, model.h:276-283
+  triTest[3 * j + 0] = make_float4(v0.x, v0.y, v0.z, n.x);
+  triTest[3 * j + 1] = make_float4(v1.x, v1.y, v1.z, n.y);
+  triTest[3 * j + 2] = make_float4(v2.x, v2.y, v2.z, n.z);
+  const V3 nu = unit(n);  // model.h:172
+  // calcTangentBasis, model.h:214-235
+  const V3 e0 = sub(v1, v0), e1 = sub(v2, v0);
+  const float du0 = uv[1][0] - uv[0][0], dv0 = uv[1][1] - uv[0][1];
+  const float du1 = uv[2][0] - uv[0][0], dv1 = uv[2][1] - uv[0][1];
+  float f = (du0 * dv1 - du1 * dv0);
+  if (f == 0) f += 1.1920928955078125e-7f;  // std::numeric_limits<float>::epsilon()
+  f = 1.0f / f;
+  const V3 tg = unit(V3{f * (dv1 * e0.x - dv0 * e1.x), f * (dv1 * e0.y - dv0 * e1.y), f * (dv1 * e0.z - dv0 * e1.z)});
+  const V3 bt = unit(V3{f * (-du1 * e0.x + du0 * e1.x), f * (-du1 * e0.y + du0 * e1.y), f * (-du1 * e0.z + du0 * e1.z)});
+  const float material = triShade[4 * j + 3].w;
+  triShade[4 * j + 0] = make_float4(nu.x, nu.y, nu.z, uv[0][0]);
+  triShade[4 * j + 1] = make_float4(tg.x, tg.y, tg.z, uv[0][1]);
+  triShade[4 * j + 2] = make_float4(bt.x, bt.y, bt.z, uv[1][0]);
+  triShade[4 * j + 3] = make_float4(uv[1][1], uv[2][0], uv[2][1], material);
+}
+
+// One lane per updated sphere: SrtSphereIn (ten words) -> the sphere's three records.  The material word keeps everything
+// but the "moving" bit, which follows center0 != center1.
+__global__ void refitSphereRecords(const float* in, int first, int count, float4* spheres) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float* s = in + 10 * (size_t)i;
+  const float c0[3] = {s[0], s[1], s[2]}, c1[3] = {s[3], s[4], s[5]};
+  const float time0 = s[6], time1 = s[7], radius = s[8];
+  const size_t j = (size_t)(first + i);
+  const bool moving = c0[0] != c1[0] || c0[1] != c1[1] || c0[2] != c1[2];
+  const int32_t bits = (__float_as_int(spheres[3 * j + 1].w) & ~(1 << 30)) | (moving ? (1 << 30) : 0);
+  spheres[3 * j + 0] = make_float4(c0[0], c0[1], c0[2], radius);
+  spheres[3 * j + 1] = make_float4(c1[0], c1[1], c1[2], __int_as_float(bits));
+  spheres[3 * j + 2] = make_float4(time0, time1, 0.0f, 0.0f);
+}
+
+// ---------------------------------------------------------------------------------------------------- refit
+// up[node] = parent index | (the parent's number of node children) << 28, -1 for a root: the topology the refit climbs.
+// Built once per uploaded scene from the node array's reference words (pure topology: a refit never changes it).
+#define REFIT_NEED_SHIFT 28
+#define REFIT_PARENT_MASK ((1 << REFIT_NEED_SHIFT) - 1) /* SRT_MAX_NODES = 2^25 */
+
+__device__ __forceinline__ bool isNode(int32_t ref) { return ref >= 0; }
+
+__global__ void refitLinks(const float4* nodes, int numNodes, int32_t* up) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= numNodes) return;
+  const int32_t l = __float_as_int(nodes[2 * (size_t)i].w), r = __float_as_int(nodes[2 * (size_t)i + 1].w);
+  const int need = (isNode(l) ? 1 : 0) + (isNode(r) && r != l ? 1 : 0);
+  const int32_t word = i | need << REFIT_NEED_SHIFT;
+  if (isNode(l)) up[SRT_NODE_INDEX(l)] = word;
+  if (isNode(r)) up[SRT_NODE_INDEX(r)] = word;
+}
+
+// fastDiv's operand certificate (srt_scene.cpp fastDivOperand): 0 or 2^-77 <= |c| <= 2^30
+__device__ __forceinline__ bool fastDivOperand(float c) {
+  const float ac = fabsf(c);
+  return c == 0.0f || (ac >= 0x1p-77f && ac <= 0x1p30f);
+}
+
+struct RefitArgs {
+  DevScene scene;
+  int32_t base, count;  // the item's node slots
+  float time0, time1;   // the item's (bvh.h:15-16)
+  const int32_t* up;
+  int32_t* arrived;     // one counter per node, zero before the launch
+  int32_t* flag;        // bit 0: a primitive box of a device-built item fails the fast-division certificate
+  int32_t checkPrims;   // the item is device-built
+};
+
+// Bottom-up over one world item's tree, in the manner of lbvhFit (srt_lbvh.hip): one lane per node; the lanes of the nodes
+// without node children start, fit their node and climb; at a parent the lane that completes its node children's count
+// goes on, every other one stops.  Nobody waits.  A child's box is published by a release fence before the arrival is
+// counted and read behind an acquire fence after it (agent scope: the compute dies have private L2s).  Unions are
+// min / max, so the boxes do not depend on who arrives when.  The reference words of the records are written back as read.
+__global__ void refitNodes(RefitArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.count) return;
+  float4* const nodes = const_cast<float4*>(a.scene.nodes);
+  int node = a.base + i;
+  {
+    const int32_t l = __float_as_int(nodes[2 * (size_t)node].w), r = __float_as_int(nodes[2 * (size_t)node + 1].w);
+    if (isNode(l) || isNode(r)) return;
+  }
+  bool bad = false;
+  for (;;) {
+    const float4 n0 = nodes[2 * (size_t)node], n1 = nodes[2 * (size_t)node + 1];
+    const int32_t link = a.up[node];  // read before the stores: nothing but the fence stands between them and the arrival
+    const int32_t refs[2] = {__float_as_int(n0.w), __float_as_int(n1.w)};
+    const float inf = __int_as_float(0x7f800000);
+    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    bool any = false;
+    for (int c = 0; c < 2; ++c) {
+      const int32_t ref = refs[c];
+      if (ref == SRT_REF_DONE || (c == 1 && ref == refs[0])) continue;  // an unused slot; a single-object leaf
+      float cmn[3], cmx[3];
+      if (isNode(ref)) {
+        const size_t j = (size_t)SRT_NODE_INDEX(ref);
+        const float4 c0 = nodes[2 * j], c1 = nodes[2 * j + 1];
+        cmn[0] = c0.x; cmn[1] = c0.y; cmn[2] = c0.z;
+        cmx[0] = c1.x; cmx[1] = c1.y; cmx[2] = c1.z;
+      } else {
+        primBox(a.scene, ref, a.time0, a.time1, cmn, cmx);
+        if (a.checkPrims)
+          for (int k = 0; k < 3; ++k) bad = bad || !fastDivOperand(cmn[k]) || !fastDivOperand(cmx[k]);
+      }
+      for (int k = 0; k < 3; ++k) {  // aabb.h:33-43
+        mn[k] = fminf(mn[k], cmn[k]);
+        mx[k] = fmaxf(mx[k], cmx[k]);
+      }
+      any = true;
+    }
+    if (any) {
+      nodes[2 * (size_t)node] = make_float4(mn[0], mn[1], mn[2], n0.w);
+      nodes[2 * (size_t)node + 1] = make_float4(mx[0], mx[1], mx[2], n1.w);
+    }
+    if (link < 0) break;  // a root
+    const int parent = link & REFIT_PARENT_MASK, need = link >> REFIT_NEED_SHIFT;
+    __threadfence();
+    if (atomicAdd(&a.arrived[parent], 1) + 1 < need) break;  // a sibling subtree is not finished: its last lane goes on
+    __threadfence();
+    node = parent;
+  }
+  if (bad) atomicOr(a.flag, 1);
+}
+
+// After the refit, one lane per node: the node boxes' share of the certificate (flag bit 1), and the box halves of the
+// hybrid records (DevScene::nodesWf) through the renumbering of srtHybridRecords; their reference and link words stay.
+__global__ void refitDerived(const float4* nodes, int numNodes, const int32_t* wfIndex, float4* nodesWf, int32_t* flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= numNodes) return;
+  const float4 lo = nodes[2 * (size_t)i], hi = nodes[2 * (size_t)i + 1];
+  if (!(fastDivOperand(lo.x) && fastDivOperand(lo.y) && fastDivOperand(lo.z) && fastDivOperand(hi.x) && fastDivOperand(hi.y) &&
+        fastDivOperand(hi.z)))
+    atomicOr(flag, 2);
+  if (wfIndex) {
+    const size_t j = (size_t)wfIndex[i];
+    nodesWf[2 * j] = make_float4(lo.x, lo.y, lo.z, nodesWf[2 * j].w);
+    nodesWf[2 * j + 1] = make_float4(hi.x, hi.y, hi.z, nodesWf[2 * j + 1].w);
+  }
+}
+
+inline dim3 gridFor(int n) { return dim3((unsigned)((n + 255) / 256)); }
+
+}  // namespace
+
+extern "C" {
+
+int srt_launch_refit_triangles(const void* dIn, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(refitTriRecords, gridFor(count), dim3(256), 0, stream, static_cast<const float4*>(dIn), first, count, devIndex,
+                     triTest, triShade);
+  return (int)hipGetLastError();
+}
+
+int srt_launch_refit_spheres(const void* dIn, int first, int count, float4* spheres, hipStream_t stream) {
+  hipLaunchKernelGGL(refitSphereRecords, gridFor(count), dim3(256), 0, stream, static_cast<const float*>(dIn), first, count, spheres);
+  return (int)hipGetLastError();
+}
+
+int srt_launch_refit_links(const float4* nodes, int numNodes, int32_t* up, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(up, 0xff, (size_t)numNodes * sizeof(int32_t), stream);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(refitLinks, gridFor(numNodes), dim3(256), 0, stream, nodes, numNodes, up);
+  return (int)hipGetLastError();
+}
+
+// One world item's tree.  arrived must be zero over the item's nodes.
+int srt_launch_refit_nodes(const DevScene* sc, int base, int count, float time0, float time1, const int32_t* up, int32_t* arrived,
+                           int32_t* flag, int checkPrims, hipStream_t stream) {
+  RefitArgs a;
+  a.scene = *sc;
+  a.base = base;
+  a.count = count;
+  a.time0 = time0;
+  a.time1 = time1;
+  a.up = up;
+  a.arrived = arrived;
+  a.flag = flag;
+  a.checkPrims = checkPrims;
+  hipLaunchKernelGGL(refitNodes, gridFor(count), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+int srt_launch_refit_derived(const DevScene* sc, const int32_t* wfIndex, int32_t* flag, hipStream_t stream) {
+  hipLaunchKernelGGL(refitDerived, gridFor(sc->numNodes), dim3(256), 0, stream, sc->nodes, sc->numNodes, wfIndex,
+                     const_cast<float4*>(sc->nodesWf), flag);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

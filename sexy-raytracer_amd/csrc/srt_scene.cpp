@@ -360,6 +360,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
       h.nodeAxis.push_back(n.axis);
     }
     h.world.push_back(SRT_NODE_REF(base));
+    h.hostTrees.push_back(HostTree{w, base, (int32_t)b.nodes.size(), it.time0, it.time1});
     h.stackDepth = std::max(h.stackDepth, b.maxPending);
     // tree depth for reporting: longest root->node chain
     std::vector<int> depth(b.nodes.size(), 1);
@@ -557,7 +558,8 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
       const size_t fitsWhole = (160 * 1024 - 64 * sizeof(int32_t) - 18 * 1024) / 32;  // the whole-tree form's smallest pool
       const size_t cap = o.wfResidentMax > 0 ? std::min<size_t>(fits, (size_t)o.wfResidentMax) : fits;
       if (n > (o.wfResidentMax > 0 ? cap : fitsWhole))
-        h.wfResident = srtHybridRecords(h.nodes, h.world, d->numTriangles, d->numSpheres, cap, h.nodesWf, h.worldWf, h.primSecond);
+        h.wfResident = srtHybridRecords(h.nodes, h.world, d->numTriangles, d->numSpheres, cap, h.nodesWf, h.worldWf, h.primSecond, &h.wfIndex);
+      if (h.nodesWf.empty()) h.wfIndex.clear();
     }
   }
   // ---- material class per primitive reference (DevScene::primClass)
@@ -570,6 +572,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     // four lookups) would make every hit step of the plain spheres (the ground) run that code too: it goes with "the rest"
     return flags ? 2 : 1;
   };
+  h.triDevIndex.swap(triDevIndex);
   h.primClass.assign((size_t)2 * std::max(d->numTriangles, d->numSpheres) + 2, 2);
   for (int i = 0; i < d->numTriangles; ++i) h.primClass[(size_t)i << 1] = classOf(h.triShade[4 * (size_t)i + 3].w, false);
   for (int i = 0; i < d->numSpheres; ++i) h.primClass[((size_t)i << 1) | 1] = classOf(h.spheres[3 * (size_t)i + 1].w, true);

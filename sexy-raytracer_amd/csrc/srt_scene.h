@@ -57,6 +57,14 @@ struct DeviceBuild {
   std::vector<int32_t> refs;  // the item's primitives as device references
 };
 
+// A world item whose tree the host built or adopted: where it lies in the node array, and the times its boxes are made
+// for (srtRefitScene fits them again; DeviceBuild carries the same for the device-built ones).
+struct HostTree {
+  int32_t item;
+  int32_t base, count;
+  float time0, time1;
+};
+
 // Every array srtUploadScene uploads, in its final order and layout (DevScene's fields of the same names).
 struct HostScene {
   std::vector<float4> nodes;  // device-built items' slots are zero until their build
@@ -75,6 +83,9 @@ struct HostScene {
   int32_t wfResident = 0;
   std::vector<std::vector<SrtBvhNode>> itemNodes;  // per world item: its host-built tree (srtGetBvh)
   std::vector<DeviceBuild> deviceBuilds;
+  std::vector<HostTree> hostTrees;
+  std::vector<int32_t> triDevIndex;  // scene triangle index -> device index (the inverse of the reordering); empty: identity
+  std::vector<int32_t> wfIndex;      // node index -> its record in nodesWf (srtHybridRecords' renumbering); empty with nodesWf
   int stackDepth = 0, bvhDepth = 0;  // over the host-built trees
   int32_t fastDivScene = 0;          // over the host-built nodes and the device-built items' primitive boxes
 };

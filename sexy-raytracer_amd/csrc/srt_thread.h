@@ -76,9 +76,11 @@ inline void srtThreadLinks16(const std::vector<float4>& nodes, const std::vector
 // roots come first (greedy expansion; a child's box lies inside its parent's, so the set is closed upward: a walk leaves
 // it once per excursion and comes back through a successor), both groups in the trees' pre-order (a node's first child
 // is the next record of its group where both are on the same side).  Returns the number of resident nodes, 0 when the
-// world is not a forest of two-node / two-primitive trees (outputs empty then).
+// world is not a forest of two-node / two-primitive trees (outputs empty then).  newIndexOut: the renumbering, old node index ->
+// record.
 inline int32_t srtHybridRecords(const std::vector<float4>& nodes, const std::vector<int32_t>& world, int64_t numTriangles, int64_t numSpheres, size_t cap,
-                                std::vector<float4>& nodesWf, std::vector<int32_t>& worldWf, std::vector<int32_t>& primSecond) {
+                                std::vector<float4>& nodesWf, std::vector<int32_t>& worldWf, std::vector<int32_t>& primSecond,
+                                std::vector<int32_t>* newIndexOut = nullptr) {
   using namespace srt_thread_detail;
   nodesWf.clear();
   worldWf.clear();
@@ -163,5 +165,6 @@ inline int32_t srtHybridRecords(const std::vector<float4>& nodes, const std::vec
     nodesWf[2 * (size_t)newIndex[i] + 1] = hi;
   }
   for (int32_t wr : world) worldWf.push_back(wr >= 0 ? newIndex[SRT_NODE_INDEX(wr)] : wr);
+  if (newIndexOut) newIndexOut->swap(newIndex);  // srtRefitScene rewrites the box halves through it
   return (int32_t)k;
 }

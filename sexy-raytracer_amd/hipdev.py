@@ -39,6 +39,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtTemporalReproject", "srtRenderTemporalAdaptive", "srtRenderTemporalAdaptiveFrame",
            "srtRenderFeatureTileList", "srtRenderAdaptiveGuided", "srtRenderAdaptiveDenoisedImage",
            "srtRenderTemporalAdaptiveGuided", "srtRenderTemporalAdaptiveGuidedFrame",
+           "srtUpdateTriangles", "srtUpdateSpheres", "srtUpdateTrianglesDevice", "srtUpdateSpheresDevice", "srtRefitScene",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -111,6 +112,9 @@ lib.srtRenderAdaptiveDenoisedImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParam
                                                C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(abi.SrtAdaptiveStats)]
 lib.srtRenderTemporalAdaptiveGuided.argtypes = lib.srtRenderTemporalAdaptive.argtypes
 lib.srtRenderTemporalAdaptiveGuidedFrame.argtypes = lib.srtRenderTemporalAdaptiveFrame.argtypes
+lib.srtUpdateTriangles.argtypes = lib.srtUpdateSpheres.argtypes = [_vp, C.c_int32, C.c_int32, _vp]
+lib.srtUpdateTrianglesDevice.argtypes = lib.srtUpdateSpheresDevice.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
+lib.srtRefitScene.argtypes = [_vp, _vp]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -535,6 +539,40 @@ class Context:
 
     def comm_destroy(self):
         self._check(lib.srtCommDestroy(self.h))
+
+    def _update(self, host_entry, device_entry, dtype, first, records, stream):
+        size = dtype.itemsize
+        if hasattr(records, "data_ptr"):  # a torch tensor: DEVICE memory, handed over as it is
+            if not records.is_cuda or not records.is_contiguous():
+                raise ValueError("a tensor of records must be contiguous and live on the GPU")
+            nbytes = records.numel() * records.element_size()
+            if nbytes % size:
+                raise ValueError("the tensor holds %d bytes, not a whole number of %d-byte records" % (nbytes, size))
+            self._check(device_entry(self.h, int(first), nbytes // size, records.data_ptr() if nbytes else None, stream))
+            return
+        a = np.ascontiguousarray(records)
+        if a.dtype != dtype:
+            if a.nbytes % size:
+                raise ValueError("the array holds %d bytes, not a whole number of %d-byte records" % (a.nbytes, size))
+            a = a.reshape(-1).view(np.uint8).view(dtype)
+        self._check(host_entry(self.h, int(first), a.size, a.ctypes.data if a.size else None))
+
+    def update_triangles(self, first, triangles, stream=None):
+        """srtUpdateTriangles / srtUpdateTrianglesDevice: new positions and uvs for triangles [first, first + n) of the
+        uploaded scene (its own triangle order; `material` is ignored).  triangles: a NumPy array of abi.TRIANGLE_DTYPE
+        (or any array of n * 64 bytes laid out like SrtTriangleIn), or a contiguous torch tensor on the GPU with the same
+        bytes, which is read asynchronously on `stream`.  Nothing renders until refit() has run."""
+        self._update(lib.srtUpdateTriangles, lib.srtUpdateTrianglesDevice, abi.TRIANGLE_DTYPE, first, triangles, stream)
+
+    def update_spheres(self, first, spheres, stream=None):
+        """srtUpdateSpheres / srtUpdateSpheresDevice: new centres, times and radius for spheres [first, first + n); records
+        of abi.SPHERE_DTYPE (40 bytes, SrtSphereIn), NumPy or a torch tensor on the GPU as in update_triangles."""
+        self._update(lib.srtUpdateSpheres, lib.srtUpdateSpheresDevice, abi.SPHERE_DTYPE, first, spheres, stream)
+
+    def refit(self, stream=None):
+        """srtRefitScene: every node box from the current primitive records, and what is derived from boxes; the topology
+        stays.  Blocking.  Drops the temporal history."""
+        self._check(lib.srtRefitScene(self.h, stream))
 
     def trace(self, rays, traversal=abi.SRT_TRAVERSE_FAITHFUL):
         rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)

@@ -17,6 +17,10 @@
 //   rtFrameAdaptiveDenoised(target, denoised, ..., sppMax, thr)  rtFrameAdaptive's frame, guide planes from every one of its
 //                                           samples and the denoiser with the sample variance
 //                                           (include/srt_hip.h srtRenderAdaptiveDenoisedImage)
+//   updateTriangles(first, tris) / updateSpheres(first, spheres) / refit()  moving geometry: new positions for
+//                                           primitives of the uploaded scene (`triangles` keeps what init uploaded, in the
+//                                           scene's order), then every tree's boxes refitted on the device
+//                                           (include/srt_hip.h "Moving geometry"); nothing renders between the two
 //   terminate()
 //   uniqueId / initRanks                    multi-GPU: one process per GPU; rtFrame then renders this rank's
 //                                           tiles, the library gathers them with ONE ncclGather and rank 0's
@@ -51,7 +55,22 @@ class hipDevice {
     SrtSceneDesc d = f.desc();
     if (srtUploadScene(ctx, &d) != 0) return error();
     numPrims = (int)f.prims.size();
+    triangles = f.triangles;
     return true;
+  }
+
+  // Moving geometry (include/srt_hip.h srtUpdateTriangles / srtUpdateSpheres / srtRefitScene)
+  bool updateTriangles(int first, const std::vector<SrtTriangleIn>& tris) {
+    if (!ctx) return false;
+    return srtUpdateTriangles(ctx, first, (int32_t)tris.size(), tris.data()) == 0 || error();
+  }
+  bool updateSpheres(int first, const std::vector<SrtSphereIn>& s) {
+    if (!ctx) return false;
+    return srtUpdateSpheres(ctx, first, (int32_t)s.size(), s.data()) == 0 || error();
+  }
+  bool refit() {
+    if (!ctx) return false;
+    return srtRefitScene(ctx, nullptr) == 0 || error();
   }
 
   // Multi-GPU.  Rank 0 obtains an id (128 bytes) and hands it to the other processes by its own means;
@@ -323,6 +342,7 @@ class hipDevice {
   int sppChunks = 0;  // 0 = library default; 1 = the reference's single running sum per pixel
   float lastKernelMs = 0;
   int numPrims = 0;
+  std::vector<SrtTriangleIn> triangles;  // the uploaded scene's triangles, in its own order (updateTriangles' indices)
 
  private:
   bool error() {
