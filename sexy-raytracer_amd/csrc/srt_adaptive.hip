@@ -2,11 +2,12 @@
 // sampling"): the accumulate-scatter of a launch's tile outputs into the image-order sums, the convergence test with its
 // per-tile reduction, the order-preserving compaction of the active tiles into the next launch's tile table, and the
 // resolve with the per-pixel sample count.  The render kernels are not touched: a launch over a tile list is the plain
-// render with RenderArgs::tileXY pointing at the list (srt_api.cpp srtRenderTilesImpl).
+// render with RenderArgs::tileXY pointing at the list (srt_render.cpp srtRenderTilesImpl).
 //
 // All of them are HBM-bound and tiny next to a render: one wave per listed tile (64 lanes, 64 pixels) for the update,
 // one 1024-thread workgroup for the compaction (a few bytes per tile), one thread per pixel for the resolve.
 #include "srt_adaptive_common.h"
+#include "srt_launch.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // srt_buffer.h -- device memory that frees itself: the context's cached work areas, the scene's arrays and the
-// temporaries of the entry points (srt_api.cpp, srt_frames.cpp, srt_comm.cpp).
+// temporaries of the entry points (srt_api.cpp and the other host files).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,9 +1,11 @@
 // srt_context.h -- the context behind the C ABI's SrtContext* and what the host translation units share around it: error
-// reporting, and the device-level entries (srt_api.cpp) that the whole-frame entries (srt_frames.cpp) compose.  Internal:
-// none of this is exported.
+// reporting, and the device-level entries (srt_api.cpp, srt_render.cpp, srt_passes.cpp) that each other and the whole-frame
+// entries (srt_frames.cpp) compose.  Internal: none of this is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstring>
 #include <exception>
 #include <string>
 #include <vector>
@@ -28,16 +30,13 @@ struct Tunables {
   int denoiseLdsStep;
 };
 
-struct SrtContext {
-  int device = 0;
-  std::string error;
-  Tunables tun{};
-  hipDeviceProp_t prop;
-  // device scene
+// What belongs to the uploaded scene and is invalid for the next one.  srtUploadScene starts by assigning a fresh Upload,
+// which also frees the previous scene's device memory; a member added here can therefore not survive into the next scene.
+// (Work areas sized by need, the camera, the temporal history and the tunables are the context's, below.)
+struct Upload {
   std::vector<DeviceBuffer> sceneBuffers;
   DevScene scene{};
-  DevCamera cam{};
-  bool haveScene = false, haveCamera = false;
+  bool haveScene = false;
   // host copies for srtGetBvh
   std::vector<std::vector<SrtBvhNode>> itemNodes;
   std::vector<DeviceBuild> deviceBuilds;  // where the device-built trees live in scene.nodes (without their refs)
@@ -45,7 +44,7 @@ struct SrtContext {
   int bvhDepth = 0;
   // srtUpdateTriangles / srtUpdateSpheres / srtRefitScene (srt_refit_host.cpp).  Every tree of the world list with its node
   // slots and times, the host tables the upload left (moved to the device by the first call that needs them), and the
-  // refit's own device state: parent links, arrival counters, the certificate's flag word, the host entries' staging.
+  // refit's per-scene device tables: parent links, arrival counters, the hybrid records' renumbering.
   struct Tree {
     int32_t item, base, count;
     float time0, time1;
@@ -54,12 +53,23 @@ struct SrtContext {
   std::vector<Tree> trees;
   std::vector<int32_t> hostTriDevIndex, hostWfIndex;  // HostScene::triDevIndex, wfIndex
   std::vector<uint8_t> itemBoxesStale;                // per world item: itemNodes holds boxes from before a refit
-  DeviceBuffer triDevIndex, wfIndex, refitUp, refitArrived, refitFlag, refitStage;
+  DeviceBuffer triDevIndex, wfIndex, refitUp, refitArrived;
   bool refitTables = false;         // refitUp (and wfIndex) hold this scene's tables
   bool geometryDirty = false;       // an update since the last refit: nothing renders
   float pairTime0 = 0, pairTime1 = 0;  // the times the closest-hit pair records were made for
   int32_t fastDivOption = 0;        // SceneOptions::fastDiv of the upload: what fastDivScene is while the certificate holds
+};
+
+struct SrtContext {
+  int device = 0;
+  std::string error;
+  Tunables tun{};
+  hipDeviceProp_t prop;
+  Upload upload;  // the uploaded scene
+  DevCamera cam{};
+  bool haveCamera = false;
   // work areas
+  DeviceBuffer refitFlag, refitStage;  // srtRefitScene's certificate flag word, the host update entries' staging
   DeviceBuffer dQueue;
   DeviceBuffer dStats;
   void* comm = nullptr;          // ncclComm_t (srt_comm.cpp)
@@ -126,7 +136,31 @@ struct AdaptiveGuides {
   bool storeFirst;      // round 0 is stored over the whole tile table; false: the planes hold round 0 already
 };
 
-// The device-level entries behind the exported ones and their argument checks (srt_api.cpp, where each is described)
+// The fields a launch over the image shares (RenderArgs, FeatureArgs): the scene, the camera, the image, its samples and
+// the tile split; everything else zero.
+template <typename Args>
+void setImageArgs(Args& a, const SrtContext* ctx, const SrtRenderParams* p) {
+  memset(&a, 0, sizeof a);
+  a.scene = ctx->upload.scene;
+  a.cam = ctx->cam;
+  a.imageWidth = p->imageWidth;
+  a.imageHeight = p->imageHeight;
+  a.tilesX = (p->imageWidth + SRT_TILE_W - 1) / SRT_TILE_W;
+  a.tilesY = (p->imageHeight + SRT_TILE_H - 1) / SRT_TILE_H;
+  a.tileBlock = std::max(1, ctx->tun.tileBlock);  // the tile order every render and srtResolveTiles use
+  a.numTiles = srtNumTiles(p->imageWidth, p->imageHeight);
+  a.spp = p->spp;
+  a.sampleFirst = p->sampleFirst;
+  a.seed = p->seed;
+  memcpy(a.background, p->background, 12);
+  a.tMin = p->tMin;
+  a.tileFirst = p->tileFirst;
+  a.tileStride = p->tileStride;
+  a.numLocalTiles = srtNumLocalTiles(p->imageWidth, p->imageHeight, p->tileStride);
+}
+
+// The device-level entries behind the exported ones and their argument checks (srt_api.cpp, srt_render.cpp, srt_passes.cpp,
+// where each is described)
 int checkParams(SrtContext* ctx, const SrtRenderParams* p);
 // "no scene uploaded", or an update that srtRefitScene has not followed: `what` names the entry.  Launches nothing.
 int checkSceneReady(SrtContext* ctx, const char* what);
@@ -140,6 +174,8 @@ int srtRenderAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* pIn, const Srt
                           const AdaptivePool* pool = nullptr, const AdaptiveGuides* guides = nullptr);
 int checkFeatureArgs(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* const* buffers);
 int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, void* const dPlanes[4], void* streamPtr);
+int srtRenderFeatureTileListImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList,
+                                 int32_t numListed, void* const dPlaneImages[4], int32_t accumulate, void* streamPtr);
 int checkDenoiseParams(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, DenoiseArgs& a,
                        int& iterations, bool moments = false);
 int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,

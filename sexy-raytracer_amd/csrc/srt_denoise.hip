@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "srt_device.h"
+#include "srt_launch.h"
 
 namespace {
 

@@ -170,10 +170,10 @@ struct RenderArgs {
   int32_t* wfError;
 };
 
-// One render launch, decided by srt_api.cpp renderPlan.  form: srtGetLaunchInfo's codes -- 0 srt_render_kernel over node
+// One render launch, decided by srt_render.cpp renderPlan.  form: srtGetLaunchInfo's codes -- 0 srt_render_kernel over node
 // records read through the L1, 1 / 2 srt_render_kernel over the LDS-resident tree with the attenuation stacks in global
 // memory / in LDS, 3 srt_render_wf_kernel over the LDS-resident tree, 4 its hybrid form.  closest, single, count and
-// profile are the template arguments of the instance that runs (srt_render_kernel_for, srt_render_wf_kernel_for).
+// profile are the template arguments of the instance that runs (srt_launch.h srt_render_kernel_for, srt_render_wf_kernel_for).
 struct RenderPlan {
   int32_t form;
   bool closest, single, count, profile;
@@ -183,8 +183,6 @@ struct RenderPlan {
   int32_t wfRingCap, wfRingShift, wfRingMul3;  // forms 3 and 4: RenderArgs::wfRingCap = (wfRingMul3 ? 3 : 1) << wfRingShift
 };
 typedef void (*RenderKernel)(const RenderArgs);
-extern "C" RenderKernel srt_render_kernel_for(const RenderPlan* p);     // srt_kernels.hip, forms 0-2
-extern "C" RenderKernel srt_render_wf_kernel_for(const RenderPlan* p);  // srt_wavefront.hip, forms 3 and 4
 
 struct TraceArgs {
   DevScene scene;

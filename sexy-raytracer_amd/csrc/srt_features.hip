@@ -16,6 +16,7 @@
 //            trees included) -- 256-thread workgroups (the stack's [slot][thread] stride is SRT_BLOCK)
 // Nothing of the render kernels is shared beyond srt_path.h's device functions: their code objects do not change.
 #include "srt_features_body.h"
+#include "srt_launch.h"
 
 template <bool CLOSEST, bool LDSTREE>
 __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK) void srt_features_kernel(const FeatureArgs a) {
@@ -107,7 +108,7 @@ static void (*const featuresKernels[3])(const FeatureArgs) = {srt_features_kerne
                                                               srt_features_kernel<false, false>};
 
 extern "C" {
-// srt_api.cpp srtRenderFeatureTiles: ldsTree = the FAITHFUL walk of the LDS-resident threaded tree
+// srt_passes.cpp srtRenderFeatureTiles: ldsTree = the FAITHFUL walk of the LDS-resident threaded tree
 int srt_features_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU) {
   return featurePlan(reinterpret_cast<const void*>(featuresKernels[featureForm(closest, ldsTree)]), ldsTree, lds, block, perCU);
 }

@@ -13,6 +13,7 @@
 // threadedTraverse and surfaceFeatures are srt_features_body.h's, the one copy both kernels inline.  The LDS fill and the
 // sample loop are stated here as in srt_features.hip: change one, change the other.
 #include "srt_features_body.h"
+#include "srt_launch.h"
 
 template <bool CLOSEST, bool LDSTREE, bool ACCUM>
 __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK) void srt_features_list_kernel(const FeatureListArgs args) {
@@ -117,7 +118,7 @@ static void (*const featuresListKernels[2][3])(const FeatureListArgs) = {
      srt_features_list_kernel<false, false, true>}};
 
 extern "C" {
-// srt_api.cpp srtRenderFeatureTileList, as srt_features_plan
+// srt_passes.cpp srtRenderFeatureTileList, as srt_features_plan
 int srt_features_list_plan(int closest, int ldsTree, int accumulate, size_t lds, int* block, int* perCU) {
   const void* k = reinterpret_cast<const void*>(featuresListKernels[accumulate != 0][featureForm(closest, ldsTree)]);
   return featurePlan(k, ldsTree, lds, block, perCU);

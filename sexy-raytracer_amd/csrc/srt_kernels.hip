@@ -34,6 +34,7 @@
 // No MFMA: there is no dense contraction on this path.
 
 #include "srt_path.h"
+#include "srt_launch.h"
 
 
 // =================================================================== render
@@ -835,7 +836,7 @@ __global__ void srt_scatter_kernel(const ScatterArgs a) {
 // =================================================================== launch wrappers (host)
 extern "C" {
 
-// the srt_render_kernel instance a plan of form 0-2 names (srt_api.cpp renderPlan)
+// the srt_render_kernel instance a plan of form 0-2 names (srt_render.cpp renderPlan)
 RenderKernel srt_render_kernel_for(const RenderPlan* p) {
   if (p->moments) {  // (never counting: srtRenderTilesMoments refuses countStats)
     if (p->form == 2)

@@ -1,0 +1,67 @@
+// srt_launch.h -- every C-linkage function a kernel file (.hip) defines and a host file (.cpp) calls, declared once.  The
+// defining file and every caller include this header: C linkage does not mangle the parameter types into the symbol, so a
+// definition that disagrees with a caller's idea of it would link and pass garbage; seen by both, it is "conflicting
+// types" at compile time.  Each returns a hipError_t as int (0 = launched) unless it says otherwise.  Internal.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "srt_device.h"
+
+extern "C" {
+
+// srt_kernels.hip / srt_wavefront.hip: the instance of the render kernel a plan names (forms 0-2 / forms 3 and 4)
+RenderKernel srt_render_kernel_for(const RenderPlan* p);
+RenderKernel srt_render_wf_kernel_for(const RenderPlan* p);
+
+// srt_kernels.hip
+int srt_launch_finalize(const SrtFixedAccum* fix, float4* out, int n, int samples, hipStream_t stream);
+int srt_launch_sum_chunks(const float4* buf, float4* out, int n, int chunks, float limit, hipStream_t stream);
+int srt_launch_resolve(const ResolveArgs* a, hipStream_t stream);
+int srt_launch_trace(const TraceArgs* a, int traversal, int grid, size_t ldsBytes, hipStream_t stream);
+int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint64_t seed, int n,
+                       hipStream_t stream);
+
+// srt_lbvh.hip: the device tree builders (blocking) and the closest-hit traversal's pair records
+int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
+                   uint8_t* outAxis, int base, int* depthOut);
+int srt_ploc_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
+                   uint8_t* outAxis, int base, int radius, int* depthOut);
+int srt_pair_nodes(const DevScene* sc, float time0, float time1, float4* out);
+int srt_pair_nodes_async(const DevScene* sc, float time0, float time1, float4* out, hipStream_t stream);
+
+// srt_refit.hip
+int srt_launch_refit_triangles(const void* dIn, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade,
+                               hipStream_t stream);
+int srt_launch_refit_spheres(const void* dIn, int first, int count, float4* spheres, hipStream_t stream);
+int srt_launch_refit_links(const float4* nodes, int numNodes, int32_t* up, hipStream_t stream);
+int srt_launch_refit_nodes(const DevScene* sc, int base, int count, float time0, float time1, const int32_t* up, int32_t* arrived,
+                           int32_t* flag, int checkPrims, hipStream_t stream);
+int srt_launch_refit_derived(const DevScene* sc, const int32_t* wfIndex, int32_t* flag, hipStream_t stream);
+
+// srt_features.hip, srt_features_list.hip: the kernel's workgroup size and workgroups per CU, then its launch
+int srt_features_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU);
+int srt_launch_features(const FeatureArgs* a, int closest, int ldsTree, int grid, size_t lds, hipStream_t stream);
+int srt_features_list_plan(int closest, int ldsTree, int accumulate, size_t lds, int* block, int* perCU);
+int srt_launch_features_list(const FeatureListArgs* a, int closest, int ldsTree, int accumulate, int grid, size_t lds,
+                             hipStream_t stream);
+
+// srt_denoise.hip
+int srt_launch_denoise(const DenoiseArgs* a, int iterations, int ldsMaxStep, hipStream_t stream);
+
+// srt_adaptive.hip
+int srt_launch_adaptive_update(const uint32_t* list, int count, const float4* beautyTiles, const float4* momentTiles,
+                               float4* accum, float4* moments, int32_t* flags, int width, int height, double limit,
+                               bool accumulate, bool decide, hipStream_t stream);
+int srt_launch_adaptive_compact(const uint32_t* list, const int32_t* flags, int count, uint32_t* out, int32_t* counts,
+                                int width, int height, hipStream_t stream);
+int srt_launch_adaptive_resolve(const float4* accum, uint8_t* rgba, int n, hipStream_t stream);
+
+// srt_temporal.hip, srt_temporal_adaptive.hip
+int srt_launch_temporal(const TemporalArgs* a, hipStream_t stream);
+int srt_launch_temporal_reproject(const TemporalArgs* a, hipStream_t stream);
+int srt_launch_temporal_adaptive_update(const uint32_t* list, int count, const float4* beautyTiles, const float4* momentTiles,
+                                        float4* accum, float4* moments, const float4* reprojected, const float4* albedo,
+                                        int32_t* flags, int width, int height, double limit, bool accumulate,
+                                        hipStream_t stream);
+
+}  // extern "C"

@@ -19,6 +19,7 @@
 
 #include "srt_device.h"
 #include "srt_prim_box.h"
+#include "srt_launch.h"
 
 namespace {
 

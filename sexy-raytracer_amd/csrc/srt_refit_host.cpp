@@ -9,23 +9,13 @@
 #include <cstring>
 
 #include "srt_context.h"
-
-extern "C" {
-int srt_launch_refit_triangles(const void* dIn, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade,
-                               hipStream_t stream);
-int srt_launch_refit_spheres(const void* dIn, int first, int count, float4* spheres, hipStream_t stream);
-int srt_launch_refit_links(const float4* nodes, int numNodes, int32_t* up, hipStream_t stream);
-int srt_launch_refit_nodes(const DevScene* sc, int base, int count, float time0, float time1, const int32_t* up, int32_t* arrived,
-                           int32_t* flag, int checkPrims, hipStream_t stream);
-int srt_launch_refit_derived(const DevScene* sc, const int32_t* wfIndex, int32_t* flag, hipStream_t stream);
-int srt_pair_nodes_async(const DevScene* sc, float time0, float time1, float4* out, hipStream_t stream);
-}
+#include "srt_launch.h"
 
 namespace {
 
 // Everything an update entry checks before it touches the device.  Returns 0 to go on, 1 for an error, 2 for the no-op.
 int checkUpdate(SrtContext* ctx, const char* what, int32_t first, int32_t count, int32_t have, const void* in, size_t align) {
-  if (!ctx->haveScene) return fail(ctx, "%s: no scene uploaded", what);
+  if (!ctx->upload.haveScene) return fail(ctx, "%s: no scene uploaded", what);
   if (first < 0 || count < 0 || (int64_t)first + count > have)
     return fail(ctx, "%s: range [%d, %d + %d) lies outside the scene's %d records", what, first, first, count, have);
   if (count == 0) return 2;
@@ -37,36 +27,36 @@ int checkUpdate(SrtContext* ctx, const char* what, int32_t first, int32_t count,
 // The scene-to-device triangle table, on the device (identity when the upload did not reorder: null)
 int triangleTable(SrtContext* ctx, const int32_t** out) {
   *out = nullptr;
-  if (ctx->hostTriDevIndex.empty()) return 0;
-  if (!ctx->triDevIndex.get()) {  // (srtUploadScene drops the previous scene's)
-    HIP_OK(ctx, ctx->triDevIndex.reserve(ctx->hostTriDevIndex.size() * sizeof(int32_t)));
-    HIP_OK(ctx, hipMemcpy(ctx->triDevIndex.get(), ctx->hostTriDevIndex.data(), ctx->hostTriDevIndex.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (ctx->upload.hostTriDevIndex.empty()) return 0;
+  if (!ctx->upload.triDevIndex.get()) {  // (srtUploadScene drops the previous scene's)
+    HIP_OK(ctx, ctx->upload.triDevIndex.reserve(ctx->upload.hostTriDevIndex.size() * sizeof(int32_t)));
+    HIP_OK(ctx, hipMemcpy(ctx->upload.triDevIndex.get(), ctx->upload.hostTriDevIndex.data(), ctx->upload.hostTriDevIndex.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  *out = ctx->triDevIndex.get<const int32_t>();
+  *out = ctx->upload.triDevIndex.get<const int32_t>();
   return 0;
 }
 
 int updateTrianglesDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dIn, void* stream) {
   if (!ctx) return 1;
-  const int rc = checkUpdate(ctx, "srtUpdateTriangles", first, count, ctx->haveScene ? ctx->scene.numTris : 0, dIn, 16);
+  const int rc = checkUpdate(ctx, "srtUpdateTriangles", first, count, ctx->upload.haveScene ? ctx->upload.scene.numTris : 0, dIn, 16);
   if (rc) return rc == 2 ? 0 : 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   const int32_t* table = nullptr;
   if (triangleTable(ctx, &table)) return 1;
-  ctx->geometryDirty = true;
-  const int e = srt_launch_refit_triangles(dIn, first, count, table, const_cast<float4*>(ctx->scene.triTest),
-                                           const_cast<float4*>(ctx->scene.triShade), static_cast<hipStream_t>(stream));
+  ctx->upload.geometryDirty = true;
+  const int e = srt_launch_refit_triangles(dIn, first, count, table, const_cast<float4*>(ctx->upload.scene.triTest),
+                                           const_cast<float4*>(ctx->upload.scene.triShade), static_cast<hipStream_t>(stream));
   if (e) return fail(ctx, "srtUpdateTriangles: launch failed: %s", hipGetErrorString((hipError_t)e));
   return 0;
 }
 
 int updateSpheresDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dIn, void* stream) {
   if (!ctx) return 1;
-  const int rc = checkUpdate(ctx, "srtUpdateSpheres", first, count, ctx->haveScene ? ctx->scene.numSpheres : 0, dIn, 4);
+  const int rc = checkUpdate(ctx, "srtUpdateSpheres", first, count, ctx->upload.haveScene ? ctx->upload.scene.numSpheres : 0, dIn, 4);
   if (rc) return rc == 2 ? 0 : 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
-  ctx->geometryDirty = true;
-  const int e = srt_launch_refit_spheres(dIn, first, count, const_cast<float4*>(ctx->scene.spheres), static_cast<hipStream_t>(stream));
+  ctx->upload.geometryDirty = true;
+  const int e = srt_launch_refit_spheres(dIn, first, count, const_cast<float4*>(ctx->upload.scene.spheres), static_cast<hipStream_t>(stream));
   if (e) return fail(ctx, "srtUpdateSpheres: launch failed: %s", hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -76,7 +66,7 @@ int updateSpheresDevice(SrtContext* ctx, int32_t first, int32_t count, const voi
 template <typename Device>
 int updateHost(SrtContext* ctx, const char* what, int32_t first, int32_t count, int32_t have, const void* hIn, size_t recordBytes, Device device) {
   if (!ctx) return 1;
-  const int rc = checkUpdate(ctx, what, first, count, ctx->haveScene ? have : 0, hIn, 1);
+  const int rc = checkUpdate(ctx, what, first, count, ctx->upload.haveScene ? have : 0, hIn, 1);
   if (rc) return rc == 2 ? 0 : 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   HIP_OK(ctx, ctx->refitStage.reserve((size_t)count * recordBytes));
@@ -86,46 +76,46 @@ int updateHost(SrtContext* ctx, const char* what, int32_t first, int32_t count, 
 
 int refitScene(SrtContext* ctx, void* streamPtr) {
   if (!ctx) return 1;
-  if (!ctx->haveScene) return fail(ctx, "srtRefitScene: no scene uploaded");
+  if (!ctx->upload.haveScene) return fail(ctx, "srtRefitScene: no scene uploaded");
   HIP_OK(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-  const DevScene& s = ctx->scene;
+  const DevScene& s = ctx->upload.scene;
   const int n = s.numNodes;
   int32_t flag = 0;
   if (n > 0) {
-    if (!ctx->refitTables) {
+    if (!ctx->upload.refitTables) {
       // once per upload: the parent links, and the hybrid records' renumbering
-      HIP_OK(ctx, ctx->refitUp.reserve((size_t)n * sizeof(int32_t)));
-      HIP_OK(ctx, ctx->refitArrived.reserve((size_t)n * sizeof(int32_t)));
+      HIP_OK(ctx, ctx->upload.refitUp.reserve((size_t)n * sizeof(int32_t)));
+      HIP_OK(ctx, ctx->upload.refitArrived.reserve((size_t)n * sizeof(int32_t)));
       HIP_OK(ctx, ctx->refitFlag.reserve(16));
       if (s.nodesWf) {
-        if (ctx->hostWfIndex.size() != (size_t)n) return fail(ctx, "srtRefitScene: the hybrid records have no renumbering");
-        HIP_OK(ctx, ctx->wfIndex.reserve((size_t)n * sizeof(int32_t)));
-        HIP_OK(ctx, hipMemcpy(ctx->wfIndex.get(), ctx->hostWfIndex.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (ctx->upload.hostWfIndex.size() != (size_t)n) return fail(ctx, "srtRefitScene: the hybrid records have no renumbering");
+        HIP_OK(ctx, ctx->upload.wfIndex.reserve((size_t)n * sizeof(int32_t)));
+        HIP_OK(ctx, hipMemcpy(ctx->upload.wfIndex.get(), ctx->upload.hostWfIndex.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
       }
-      const int e = srt_launch_refit_links(s.nodes, n, ctx->refitUp.get<int32_t>(), stream);
+      const int e = srt_launch_refit_links(s.nodes, n, ctx->upload.refitUp.get<int32_t>(), stream);
       if (e) return fail(ctx, "srtRefitScene: launch failed: %s", hipGetErrorString((hipError_t)e));
-      ctx->refitTables = true;
+      ctx->upload.refitTables = true;
     }
-    HIP_OK(ctx, hipMemsetAsync(ctx->refitArrived.get(), 0, (size_t)n * sizeof(int32_t), stream));
+    HIP_OK(ctx, hipMemsetAsync(ctx->upload.refitArrived.get(), 0, (size_t)n * sizeof(int32_t), stream));
     HIP_OK(ctx, hipMemsetAsync(ctx->refitFlag.get(), 0, 16, stream));
     int e = 0;
-    for (const SrtContext::Tree& t : ctx->trees) {
+    for (const Upload::Tree& t : ctx->upload.trees) {
       if (t.base < 0 || t.count < 1 || t.base + t.count > n) return fail(ctx, "srtRefitScene: world item %d lies outside the node array", t.item);
-      e = srt_launch_refit_nodes(&s, t.base, t.count, t.time0, t.time1, ctx->refitUp.get<const int32_t>(), ctx->refitArrived.get<int32_t>(),
+      e = srt_launch_refit_nodes(&s, t.base, t.count, t.time0, t.time1, ctx->upload.refitUp.get<const int32_t>(), ctx->upload.refitArrived.get<int32_t>(),
                                  ctx->refitFlag.get<int32_t>(), t.deviceBuilt ? 1 : 0, stream);
       if (e) break;
     }
-    if (!e) e = srt_launch_refit_derived(&s, s.nodesWf ? ctx->wfIndex.get<const int32_t>() : nullptr, ctx->refitFlag.get<int32_t>(), stream);
-    if (!e) e = srt_pair_nodes_async(&s, ctx->pairTime0, ctx->pairTime1, const_cast<float4*>(s.nodes2), stream);
+    if (!e) e = srt_launch_refit_derived(&s, s.nodesWf ? ctx->upload.wfIndex.get<const int32_t>() : nullptr, ctx->refitFlag.get<int32_t>(), stream);
+    if (!e) e = srt_pair_nodes_async(&s, ctx->upload.pairTime0, ctx->upload.pairTime1, const_cast<float4*>(s.nodes2), stream);
     if (e) return fail(ctx, "srtRefitScene: launch failed: %s", hipGetErrorString((hipError_t)e));
     HIP_OK(ctx, hipMemcpyAsync(&flag, ctx->refitFlag.get(), sizeof flag, hipMemcpyDeviceToHost, stream));
   }
   if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "srtRefitScene: kernel failed: %s", hipGetErrorString(hipGetLastError()));
-  ctx->scene.fastDivScene = flag == 0 ? ctx->fastDivOption : 0;
+  ctx->upload.scene.fastDivScene = flag == 0 ? ctx->upload.fastDivOption : 0;
   ctx->temporalValid = false;  // as srtUploadScene: the reprojection assumes the surfaces of the history's frame
-  std::fill(ctx->itemBoxesStale.begin(), ctx->itemBoxesStale.end(), (uint8_t)1);
-  ctx->geometryDirty = false;
+  std::fill(ctx->upload.itemBoxesStale.begin(), ctx->upload.itemBoxesStale.end(), (uint8_t)1);
+  ctx->upload.geometryDirty = false;
   return 0;
 }
 
@@ -140,10 +130,10 @@ int srtUpdateSpheresDevice(SrtContext* ctx, int32_t first, int32_t count, const 
   SRT_GUARDED(ctx, updateSpheresDevice(ctx, first, count, dIn, stream));
 }
 int srtUpdateTriangles(SrtContext* ctx, int32_t first, int32_t count, const SrtTriangleIn* hTris) {
-  SRT_GUARDED(ctx, updateHost(ctx, "srtUpdateTriangles", first, count, ctx ? ctx->scene.numTris : 0, hTris, sizeof(SrtTriangleIn), updateTrianglesDevice));
+  SRT_GUARDED(ctx, updateHost(ctx, "srtUpdateTriangles", first, count, ctx ? ctx->upload.scene.numTris : 0, hTris, sizeof(SrtTriangleIn), updateTrianglesDevice));
 }
 int srtUpdateSpheres(SrtContext* ctx, int32_t first, int32_t count, const SrtSphereIn* hSpheres) {
-  SRT_GUARDED(ctx, updateHost(ctx, "srtUpdateSpheres", first, count, ctx ? ctx->scene.numSpheres : 0, hSpheres, sizeof(SrtSphereIn), updateSpheresDevice));
+  SRT_GUARDED(ctx, updateHost(ctx, "srtUpdateSpheres", first, count, ctx ? ctx->upload.scene.numSpheres : 0, hSpheres, sizeof(SrtSphereIn), updateSpheresDevice));
 }
 int srtRefitScene(SrtContext* ctx, void* stream) { SRT_GUARDED(ctx, refitScene(ctx, stream)); }
 

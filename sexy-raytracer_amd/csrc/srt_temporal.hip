@@ -8,6 +8,7 @@
 // history records: neighbouring pixels gather neighbouring records, so they go through the vector L1.  No LDS, no scratch
 // memory, no atomics.  The reprojection itself is srt_reproject.h's reprojectHistory, shared with srt_temporal_adaptive.hip.
 #include "srt_reproject.h"
+#include "srt_launch.h"
 
 namespace {
 

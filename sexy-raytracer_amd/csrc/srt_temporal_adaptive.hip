@@ -13,6 +13,7 @@
 // memory, no atomics.
 #include "srt_adaptive_common.h"
 #include "srt_reproject.h"
+#include "srt_launch.h"
 
 namespace {
 

@@ -27,6 +27,7 @@
 // every wave leaves at its next scheduling decision and the host reports the error (RenderArgs::wfError).  The
 // grid drains when every context has found the work queues empty (live == 0).
 #include "srt_path.h"
+#include "srt_launch.h"
 
 #define WF_BLOCK 1024
 #define WF_CLASSES 3
@@ -931,9 +932,9 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
 }
 
 extern "C" {
-// the srt_render_wf_kernel instance a plan of form 3 or 4 names (srt_api.cpp renderPlan)
+// the srt_render_wf_kernel instance a plan of form 3 or 4 names (srt_render.cpp renderPlan)
 RenderKernel srt_render_wf_kernel_for(const RenderPlan* p) {
-  static_assert(WF_BLOCK == SRT_BLOCK_TREE, "srt_api.cpp launches the path-pool kernel with SRT_BLOCK_TREE threads");
+  static_assert(WF_BLOCK == SRT_BLOCK_TREE, "srt_render.cpp launches the path-pool kernel with SRT_BLOCK_TREE threads");
   if (p->moments) {  // (never counting or profiling: srtRenderTilesMoments refuses countStats and ignores wf_profile)
     if (p->form == 4) return p->single ? srt_render_wf_kernel<true, false, true, false, true> : srt_render_wf_kernel<false, false, true, false, true>;
     return p->single ? srt_render_wf_kernel<true, false, false, false, true> : srt_render_wf_kernel<false, false, false, false, true>;

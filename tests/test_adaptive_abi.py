@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 
 from conftest import ROOT
+import abi_header
 import adaptive_ref as A
 
 HEADER = os.path.join(ROOT, "include", "srt_hip.h")
@@ -26,24 +27,8 @@ def _define(name):
 
 
 def test_adaptive_ctypes_prototypes_match_header(dev, abi):
-    ctype = {
-        "SrtContext*": C.c_void_p,
-        "const SrtRenderParams*": C.POINTER(abi.SrtRenderParams),
-        "const SrtAdaptiveParams*": C.POINTER(abi.SrtAdaptiveParams),
-        "SrtAdaptiveStats*": C.POINTER(abi.SrtAdaptiveStats),
-        "void*": C.c_void_p,
-        "float*": C.POINTER(C.c_float),
-        "uint8_t*": C.POINTER(C.c_uint8),
-    }
     for name in ("srtRenderAdaptive", "srtRenderAdaptiveImage"):
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
-        assert m, name
-        params = [re.sub(r"\s*\w+$", "", " ".join(a.split())).replace(" *", "*") for a in m.group(1).split(",")]
-        got = getattr(dev.lib, name).argtypes
-        assert len(got) == len(params), name
-        for g, p in zip(got, params):
-            w = ctype[p]
-            assert g.__name__ == w.__name__, (name, p, g)
+        abi_header.assert_prototype(dev, abi, name)
         assert name in dev.EXPORTS and hasattr(dev.lib, name)
 
 

@@ -5,13 +5,13 @@ them, and the NumPy emulation tests/adaptive_guides_ref.py on synthetic count ma
 in tests/test_gpu_adaptive_guides.py."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+import abi_header
 import adaptive_guides_ref as G
 import adaptive_ref as A
 
@@ -37,34 +37,8 @@ def _syntax_check(tmp_path, name, text):
 
 
 def test_ctypes_prototypes_match_header(dev, abi):
-    ctype = {
-        "SrtContext*": C.c_void_p,
-        "const SrtRenderParams*": C.POINTER(abi.SrtRenderParams),
-        "const SrtAdaptiveParams*": C.POINTER(abi.SrtAdaptiveParams),
-        "const SrtDenoiseParams*": C.POINTER(abi.SrtDenoiseParams),
-        "const SrtTemporalParams*": C.POINTER(abi.SrtTemporalParams),
-        "const SrtCamera*": C.POINTER(abi.SrtCamera),
-        "SrtAdaptiveStats*": C.POINTER(abi.SrtAdaptiveStats),
-        "SrtTemporalAdaptiveStats*": C.POINTER(abi.SrtTemporalAdaptiveStats),
-        "int32_t": C.c_int32,
-        "const void*": C.c_void_p,
-        "void* const[4]": C.POINTER(C.c_void_p),
-        "void*": C.c_void_p,
-        "float*": C.POINTER(C.c_float),
-        "uint8_t*": C.POINTER(C.c_uint8),
-    }
     for name in ENTRIES:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
-        assert m, name
-        params = []
-        for arg in m.group(1).split(","):
-            arg = " ".join(arg.split())
-            arr = re.search(r"\[(\d+)\]$", arg)
-            base = re.sub(r"\s*\w+(\[\d+\])?$", "", arg)  # drop the parameter name
-            params.append(base.replace(" *", "*") + ("[%s]" % arr.group(1) if arr else ""))
-        want = [ctype[p] for p in params]
-        got = getattr(dev.lib, name).argtypes
-        assert [g.__name__ for g in got] == [w.__name__ for w in want], (name, params)
+        abi_header.assert_prototype(dev, abi, name)
         assert name in dev.EXPORTS
     for method in METHODS:
         assert callable(getattr(dev.Context, method))

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import abi_header
 import denoise_ref as R
 
 HEADER = os.path.join(ROOT, "include", "srt_hip.h")
@@ -47,29 +48,8 @@ def test_denoise_params_layout_matches_header(tmp_path, abi):
 
 
 def test_denoise_ctypes_prototypes_match_header(dev, abi):
-    ctype = {
-        "SrtContext*": C.c_void_p,
-        "const SrtRenderParams*": C.POINTER(abi.SrtRenderParams),
-        "const SrtDenoiseParams*": C.POINTER(abi.SrtDenoiseParams),
-        "int32_t": C.c_int32,
-        "const void*": C.c_void_p,
-        "const void* const[4]": C.POINTER(C.c_void_p),
-        "void*": C.c_void_p,
-        "float*": C.POINTER(C.c_float),
-        "uint8_t*": C.POINTER(C.c_uint8),
-    }
     for name in ("srtDenoise", "srtRenderDenoisedImage"):
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
-        assert m, name
-        params = []
-        for arg in m.group(1).split(","):
-            arg = " ".join(arg.split())
-            arr = re.search(r"\[(\d+)\]$", arg)
-            base = re.sub(r"\s*\w+(\[\d+\])?$", "", arg)  # drop the parameter name
-            params.append(base.replace(" *", "*") + ("[%s]" % arr.group(1) if arr else ""))
-        want = [ctype[p] for p in params]
-        got = getattr(dev.lib, name).argtypes
-        assert [g.__name__ for g in got] == [w.__name__ for w in want], (name, params)
+        abi_header.assert_prototype(dev, abi, name)
         assert name in dev.EXPORTS
 
 

@@ -1,12 +1,12 @@
 """CPU-side checks of the feature pass's boundary (no GPU): the plane-mask constants, the ctypes prototypes against
 include/srt_hip.h, and the C++ host layer (srt/device.h hipDevice::rtFeatures, examples/main.cpp --features) compiling
 against the new entry."""
-import ctypes as C
 import os
 import re
 import subprocess
 
 from conftest import ROOT
+import abi_header
 
 HEADER = os.path.join(ROOT, "include", "srt_hip.h")
 
@@ -27,26 +27,8 @@ def test_feature_plane_constants(abi):
 
 
 def test_feature_ctypes_prototypes_match_header(dev, abi):
-    ctype = {
-        "SrtContext*": C.c_void_p,
-        "const SrtRenderParams*": C.POINTER(abi.SrtRenderParams),
-        "int32_t": C.c_int32,
-        "void* const[4]": C.POINTER(C.c_void_p),
-        "float* const[4]": C.POINTER(C.POINTER(C.c_float)),
-        "void*": C.c_void_p,
-    }
     for name in ("srtRenderFeatureTiles", "srtRenderFeatureImage"):
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
-        assert m, name
-        params = []
-        for arg in m.group(1).split(","):
-            arg = " ".join(arg.split())
-            arr = re.search(r"\[(\d+)\]$", arg)
-            base = re.sub(r"\s*\w+(\[\d+\])?$", "", arg)  # drop the parameter name
-            params.append(base.replace(" *", "*") + ("[%s]" % arr.group(1) if arr else ""))
-        want = [ctype[p] for p in params]
-        got = getattr(dev.lib, name).argtypes
-        assert [g.__name__ if hasattr(g, "__name__") else g for g in got] == [w.__name__ for w in want], (name, params)
+        abi_header.assert_prototype(dev, abi, name)
         assert name in dev.EXPORTS
 
 

@@ -238,7 +238,7 @@ FULL_SIZE_CONFIGS = {  # BASELINE.json configs[1..4] at their own size (SURVEY 8
 
 def _oracle_rows_in_chunks(oracle, osc, abi, camera, W, H, spp, mb, seed, chunks, y0, y1, threads):
     """The oracle's render of rows [y0, y1) with the kernel's chunk plan: chunk c holds samples
-    [c * base + min(c, rem), ...) (base = spp // chunks, rem = spp % chunks: srt_api.cpp), each chunk a float running sum
+    [c * base + min(c, rem), ...) (base = spp // chunks, rem = spp % chunks: srt_render.cpp), each chunk a float running sum
     in sample order (main.cpp:217), the chunk sums added exactly (float64 holds the sum of a few hundred float32 chunk
     sums of this size without rounding) and rounded to float32 once -- what the exact chunk sums of the kernel compute."""
     base, rem = spp // chunks, spp % chunks

@@ -367,6 +367,57 @@ def test_contract(ctx, dev, srt, abi, camera):
     assert a2[3] == a0[3] and all(x.tobytes() == y.tobytes() for x, y in zip(a0[:3], a2[:3]))
 
 
+# ------------------------------------------------------------------------------------------------ a scene after another
+def _upload_and_record(c, dev, abi, camera, sb):
+    """What a scene could inherit from the one before it: the tree as srtGetBvh reads it back, its depth, the axis and pair
+    records, the render kernel's form and the image -- and all of them again after an identity update and a refit, which
+    make the refit's per-scene tables; the render between the two is refused."""
+    c.upload_scene(sb)
+    c.set_camera(camera)
+    p = _params(abi)
+
+    def record():
+        tree, depth, (axis, pairs) = c.bvh(0), c.bvh_depth(), c.tree_aux(0)
+        image = c.render_image(p)[0]
+        return tree.tobytes(), depth, axis.tobytes(), pairs.tobytes(), c.launch_info()["lds_tree_mode"], image.tobytes()
+
+    before = record()
+    c.update_spheres(0, _sphere_array(abi, sb))
+    with pytest.raises(dev.SrtError, match="geometry was updated"):
+        c.render_image(p)
+    c.refit()
+    return before, record()
+
+
+@pytest.mark.parametrize("order", ["soup_then_spheres", "spheres_then_soup"])
+@pytest.mark.parametrize("builder", [0, 2])
+def test_scene_after_another_behaves_as_on_a_fresh_context(ctx, dev, srt, abi, camera, builder, order):
+    """The first scene is rendered, displaced and refitted on the hybrid form, so that its triangle table, hybrid
+    renumbering, parent links and stale-box flags all exist; the scene uploaded after it must be served by none of them.
+    The render kernels are deterministic from run to run: byte equality, no tolerance."""
+    tunables = {"wavefront": 1, "lds_tree": 1, "wf_resident_max": 24}
+    saved = {k: ctx.get_tunable(k) for k in tunables}
+    scenes = [_soup(srt, builder), _spheres_one_moving(srt)]
+    first, second = scenes if order == "soup_then_spheres" else scenes[::-1]
+    fresh = dev.Context(0)
+    try:
+        for k, v in tunables.items():
+            ctx.set_tunable(k, v)
+            fresh.set_tunable(k, v)
+        ctx.upload_scene(first)
+        ctx.set_camera(camera)
+        ctx.render_image(_params(abi))
+        _update_all(ctx, *_displaced(abi, first, 0.05)[2:])
+        got = _upload_and_record(ctx, dev, abi, camera, second)
+        want = _upload_and_record(fresh, dev, abi, camera, second)
+        assert got[0] == want[0]
+        assert got[1] == want[1]
+    finally:
+        fresh.close()
+        for k, v in saved.items():
+            ctx.set_tunable(k, v)
+
+
 # ------------------------------------------------------------------------------------------------ example
 def _example_data(tmp_path, srt):
     from PIL import Image

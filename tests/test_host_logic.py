@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import abi_header
 
 
 def test_abi_exports_every_declared_symbol(dev):
@@ -148,7 +149,7 @@ def test_no_gpu_is_an_error_not_a_fallback(dev):
 
 def test_default_chunk_plan(dev):
     """srtDefaultSppChunks: ~8 samples per item, at least 128 items per pixel when there are that many
-    samples, never more chunks than samples, at most 640 (srt_api.cpp); a function of the sample count alone."""
+    samples, never more chunks than samples, at most 640 (srt_render.cpp); a function of the sample count alone."""
     want = {1: 1, 2: 2, 16: 16, 64: 64, 100: 100, 128: 128, 333: 128, 1000: 128, 1024: 128, 4096: 512, 5000: 625, 8192: 640, 10 ** 6: 640}
     for spp, chunks in want.items():
         assert dev.default_spp_chunks(spp) == chunks, spp
@@ -198,19 +199,28 @@ def test_python_binding_covers_every_entry_point(dev):
         assert callable(getattr(dev.Context, method, None)), method
 
 
-def test_tree_aux_prototype_matches_header(dev):
+def test_every_ctypes_prototype_matches_its_declaration(dev, abi):
+    """Every function include/srt_hip.h and include/srt_hip_test.h declare against hipdev.py's hand-copied table: the number
+    of parameters, every scalar exactly, every pointer the table's typed pointer or c_void_p (the older wrappers and the
+    tests pass ndarray.ctypes.data integers), and the return type."""
+    seen = []
+    for h in abi_header.HEADERS:
+        for name, (ret, params) in abi_header.declarations(h).items():
+            fn = getattr(dev.lib, name)
+            if not params:
+                assert not fn.argtypes, name
+            abi_header.assert_prototype(dev, abi, name, untyped=lambda p: p[-1] in "*]")
+            assert fn.restype is abi_header.RETURNS[ret], (name, ret, fn.restype)
+            seen.append(name)
+    assert sorted(seen) == sorted(dev.EXPORTS + dev.TEST_EXPORTS)
+    assert [n for n in seen if not abi_header.prototype(n)[1]] == ["srtHostRandomFloat", "srtHostRandomReset"]
+
+
+def test_tree_aux_prototype_matches_header(dev, abi):
     """srtTestGetTreeAux (include/srt_hip_test.h): the ctypes prototype against the declaration; a test hook, not an
     export of the drop-in boundary; without a context it fails instead of reading anything."""
-    header = open(os.path.join(ROOT, "include", "srt_hip_test.h")).read()
-    m = re.search(r"\bint\s+srtTestGetTreeAux\s*\(([^)]*)\)\s*;", header)
-    assert m
-    ctype = {"SrtContext*": C.c_void_p, "int32_t": C.c_int32, "uint8_t*": C.POINTER(C.c_uint8), "float*": C.POINTER(C.c_float),
-             "int32_t*": C.POINTER(C.c_int32)}
-    params = [re.sub(r"\s*\w+$", "", " ".join(a.split())).replace(" *", "*") for a in m.group(1).split(",")]
-    got = dev.lib.srtTestGetTreeAux.argtypes
-    assert len(got) == len(params) == 6
-    for g, p in zip(got, params):
-        assert g.__name__ == ctype[p].__name__, (p, g)
+    assert "srtTestGetTreeAux" in abi_header.declarations("srt_hip_test.h")
+    assert len(abi_header.assert_prototype(dev, abi, "srtTestGetTreeAux")) == 6
     assert "srtTestGetTreeAux" in dev.TEST_EXPORTS and "srtTestGetTreeAux" not in dev.EXPORTS
     n = C.c_int32(-7)
     assert dev.lib.srtTestGetTreeAux(None, 0, None, None, 0, C.byref(n)) != 0 and n.value == -7

@@ -1,7 +1,6 @@
 """CPU-side checks of the sample moments and the denoiser's sample variance (no GPU): the four entries' ctypes prototypes
 and EXPORTS against include/srt_hip.h, the C++ host layer (hipDevice::rtFrameDenoised's opt-in, examples/main.cpp
 --sample-variance) compiling against them, and self-checks of the NumPy reference tests/denoise_moments_ref.py."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -10,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import abi_header
 import denoise_moments_ref as RM
 import denoise_ref as R
 
@@ -31,32 +31,9 @@ def _syntax_check(tmp_path, name, text):
 
 
 def test_moments_ctypes_prototypes_match_header(dev, abi):
-    ctype = {
-        "SrtContext*": C.c_void_p,
-        "const SrtRenderParams*": C.POINTER(abi.SrtRenderParams),
-        "const SrtDenoiseParams*": C.POINTER(abi.SrtDenoiseParams),
-        "int32_t": C.c_int32,
-        "const void*": C.c_void_p,
-        "const void* const[4]": C.POINTER(C.c_void_p),
-        "void*": C.c_void_p,
-        "float*": C.POINTER(C.c_float),
-        "uint8_t*": C.POINTER(C.c_uint8),
-    }
     for name in ENTRIES:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
-        assert m, name
-        params = []
-        for arg in m.group(1).split(","):
-            arg = " ".join(arg.split())
-            arr = re.search(r"\[(\d+)\]$", arg)
-            base = re.sub(r"\s*\w+(\[\d+\])?$", "", arg)
-            params.append(base.replace(" *", "*") + ("[%s]" % arr.group(1) if arr else ""))
-        want = [ctype[p] for p in params]
-        got = getattr(dev.lib, name).argtypes
         # pointer-to-buffer arguments may be bound as void* (device pointers) or typed (host arrays)
-        assert len(got) == len(want), name
-        for g, w, p in zip(got, want, params):
-            assert g.__name__ == w.__name__ or (w is C.c_void_p and p == "void*") or (g is C.c_void_p and p.endswith("*")), (name, p, g)
+        abi_header.assert_prototype(dev, abi, name, untyped=lambda p: p.endswith("*"))
         assert name in dev.EXPORTS and hasattr(dev.lib, name)
     m = re.search(r"#define SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE ([0-9.]+)f", _header())
     assert m and float(m.group(1)) == abi.SRT_DENOISE_MOMENTS_DEFAULT_SIGMA_LUMINANCE == RM.MOMENTS_DEFAULT_SIGMA_L

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 
 from conftest import ROOT
+import abi_header
 import adaptive_ref as A
 import temporal_adaptive_ref as TA
 import temporal_ref as R
@@ -56,33 +57,8 @@ static_assert(SRT_TEMPORAL_REPROJECTED_BYTES_PER_PIXEL == %d, "reprojected");
 
 
 def test_ctypes_prototypes_match_header(dev, abi):
-    ctype = {
-        "SrtContext*": C.c_void_p,
-        "const SrtRenderParams*": C.POINTER(abi.SrtRenderParams),
-        "const SrtAdaptiveParams*": C.POINTER(abi.SrtAdaptiveParams),
-        "const SrtDenoiseParams*": C.POINTER(abi.SrtDenoiseParams),
-        "const SrtTemporalParams*": C.POINTER(abi.SrtTemporalParams),
-        "const SrtCamera*": C.POINTER(abi.SrtCamera),
-        "SrtTemporalAdaptiveStats*": C.POINTER(abi.SrtTemporalAdaptiveStats),
-        "int32_t": C.c_int32,
-        "const void*": C.c_void_p,
-        "const void* const[4]": C.POINTER(C.c_void_p),
-        "void*": C.c_void_p,
-        "float*": C.POINTER(C.c_float),
-        "uint8_t*": C.POINTER(C.c_uint8),
-    }
     for name in ENTRIES:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header())
-        assert m, name
-        params = []
-        for arg in m.group(1).split(","):
-            arg = " ".join(arg.split())
-            arr = re.search(r"\[(\d+)\]$", arg)
-            base = re.sub(r"\s*\w+(\[\d+\])?$", "", arg)  # drop the parameter name
-            params.append(base.replace(" *", "*") + ("[%s]" % arr.group(1) if arr else ""))
-        want = [ctype[p] for p in params]
-        got = getattr(dev.lib, name).argtypes
-        assert [g.__name__ for g in got] == [w.__name__ for w in want], (name, params)
+        abi_header.assert_prototype(dev, abi, name)
         assert name in dev.EXPORTS
     for method in ("temporal_reproject", "render_temporal_adaptive_device", "render_temporal_adaptive_frame"):
         assert callable(getattr(dev.Context, method))
