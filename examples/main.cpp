@@ -5,7 +5,7 @@
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
 //                  [--denoise FILE.png [--sample-variance]] [--adaptive THRESHOLD --max-spp N]
-//                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]] [--frames N --spin DEG]
+//                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]] [--frames N --spin DEG [--temporal --motion [PREFIX]]]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
@@ -25,7 +25,12 @@
 //   --frames N --spin D  moving geometry: before frame k >= 1 the model's triangles, as loaded, are turned by k * D degrees
 //                     about the vertical axis on the host and go to the device with hipDevice::updateTriangles + refit (no
 //                     second upload: the trees keep their shape and get new boxes); every frame is rendered on its own
-//                     (rtFrame, samples from 0) to NAME_%03d.png.  Not with --temporal: the reprojection assumes a static scene
+//                     (rtFrame, samples from 0) to NAME_%03d.png.  Not with --temporal alone: the reprojection assumes a
+//                     static scene
+//   --frames N --spin D --temporal --motion [PREFIX]  motion tracking (hipDevice::setMotionTracking): the previous frame's
+//                     geometry stays on the device and every frame is a temporal frame (rtFrameTemporal, samples from k *
+//                     spp) whose reprojection follows the turning model; reports the pixels that accepted history.
+//                     PREFIX also writes each frame's motion plane as PREFIX_%03d.png (displacement * 0.5 + 0.5)
 //   SRT_DATA_DIR selects the directory of the glTF's images (default "../data/", as the reference).
 #include <chrono>
 #include <cstdlib>
@@ -98,11 +103,18 @@ int main(int argc, char** argv) {
   int frames = 0;        // > 0: a sequence, NAME_%03d.png
   float orbit = 0.0f;    // degrees the eye turns about the lookAt point's vertical axis over the sequence
   float spin = 0.0f;     // degrees per frame the model's triangles turn about the vertical axis
-  bool spinning = false;
+  bool spinning = false, motion = false;
+  std::string motionPrefix;
   for (int i = 1; i < argc; i += 2) {
     if (!strcmp(argv[i], "--sample-variance") || !strcmp(argv[i], "--temporal") || !strcmp(argv[i], "--guide-all-samples")) {
       (argv[i][2] == 't' ? temporal : argv[i][2] == 'g' ? guideAll : sampleVariance) = true;  // the flags without a value
       --i;
+      continue;
+    }
+    if (!strcmp(argv[i], "--motion")) {  // its value is optional
+      motion = true;
+      if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) motionPrefix = argv[i + 1];
+      else --i;
       continue;
     }
     if (i + 1 >= argc) break;
@@ -123,8 +135,12 @@ int main(int argc, char** argv) {
       spinning = true;
     }
   }
-  if (spinning && temporal) {
+  if (spinning && temporal && !motion) {
     std::cerr << "ERROR: --spin moves the geometry and --temporal reprojects a static scene: use one of them\n";
+    return 1;
+  }
+  if (motion && !(spinning && temporal)) {
+    std::cerr << "ERROR: --motion goes with --spin and --temporal\n";
     return 1;
   }
   if (spinning && frames < 1) {
@@ -144,6 +160,7 @@ int main(int argc, char** argv) {
   hipDevice device;
   if (!device.init(imageWidth, imageHeight, world)) return 1;
   device.sppChunks = chunks;
+  if (motion && !device.setMotionTracking(true)) return 1;
   if (frames > 0) {
     // A camera move: frame k looks from the eye turned by orbit * k / (frames - 1) degrees about the vertical axis through
     // the lookAt point and draws samples [k * spp, (k + 1) * spp).  --temporal accumulates each frame onto the reprojected
@@ -170,7 +187,26 @@ int main(int argc, char** argv) {
             }
           if (!device.updateTriangles(0, moved) || !device.refit()) return 1;
         }
-        if (!device.rtFrame(frame.data(), imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
+        if (motion) {
+          SrtTemporalStats st{};
+          if (!device.rtFrameTemporal(frame.data(), imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce,
+                                      k * numSamples, 1, nullptr, nullptr, nullptr, nullptr, &st))
+            return 1;
+          std::cerr << "frame " << k << ": history accepted on " << st.historyPixels << " pixels, " << st.meanHistoryCount
+                    << " samples behind a pixel on average\n";
+          if (!motionPrefix.empty()) {
+            std::vector<float> plane;
+            char mname[32];
+            snprintf(mname, sizeof mname, "_%03d.png", k);
+            if (!device.rtMotion(mainCamera, background, numSamples, 1, k * numSamples, plane) ||
+                !writeFeaturePng(motionPrefix + mname, plane, imageWidth, imageHeight, true)) {
+              std::cerr << "ERROR: could not write " << motionPrefix << mname << "\n";
+              return 1;
+            }
+          }
+        } else if (!device.rtFrame(frame.data(), imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) {
+          return 1;
+        }
         char name[32];
         snprintf(name, sizeof name, "_%03d.png", k);
         if (!stbi_write_png((stem + name).c_str(), imageWidth, imageHeight, 4, frame.data(), 4 * imageWidth)) {
@@ -209,7 +245,8 @@ int main(int argc, char** argv) {
     device.terminate();
     free(target);
     std::cerr << frames << " frames of " << imageWidth << "x" << imageHeight << " @" << numSamples << " spp, "
-              << (spinning ? "geometry updated and refitted between frames"
+              << (motion ? "geometry updated and refitted between frames, temporal accumulation with motion tracking"
+                  : spinning ? "geometry updated and refitted between frames"
                   : steered ? "temporal accumulation with history-steered sampling" : temporal ? "temporal accumulation" : "frame by frame")
               << " -> " << stem << "_000.png ...\nDone.\n";
     return 0;

@@ -758,7 +758,8 @@ int srtRenderTemporalAdaptiveGuidedFrame(SrtContext* ctx, const SrtRenderParams*
  *             over the moved primitives would do (its median splits would sort differently).  CLOSEST results do not
  *             depend on the tree; its speed does, see DESIGN.md 5.13 on when to upload again instead.
  *   history   srtRefitScene drops the context's temporal history exactly as srtUploadScene does (the next
- *             srtRenderTemporalFrame is a first frame): the reprojection assumes static surfaces.
+ *             srtRenderTemporalFrame is a first frame): the reprojection assumes static surfaces.  (srtSetMotionTracking,
+ *             below, keeps it.)
  *   untouched the host generator, the tunables (fast_div as read at the upload), srtGetStats, and srtLastKernelMs / srtGetLaunchInfo,
  *             which keep describing the last render.
  *   errors    no scene uploaded; a failed launch.  A scene without trees (bare primitives only) just becomes renderable.
@@ -770,6 +771,75 @@ int srtUpdateSpheres(SrtContext* ctx, int32_t first, int32_t count, const SrtSph
 int srtUpdateTrianglesDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dTriangles, void* stream);
 int srtUpdateSpheresDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dSpheres, void* stream);
 int srtRefitScene(SrtContext* ctx, void* stream);
+
+/* Motion: the temporal history kept across a refit.  Opt-in; with tracking off (the default) every entry above behaves as
+ * written there, srtRefitScene dropping the history included.
+ *
+ * srtSetMotionTracking   a flag of the context that, like the tunables, survives srtUploadScene.  An error while the
+ *             geometry is updated but not yet refitted.  Disabling releases the snapshot (and drops a history that was
+ *             being kept across a refit).  While it is on:
+ *   snapshot  the first srtUpdate* call that launches after an upload or a refit first copies the scene's triangle test
+ *             records (48 B per triangle, device order) and sphere records (48 B per sphere) into buffers the context keeps
+ *             for the scene: device to device, on that call's stream, ahead of its own kernel.  Later updates of the same
+ *             epoch do not copy again (issue them on that stream or on one ordered behind it: the copy reads both tables
+ *             whole), and a srtRefitScene that no update preceded copies too.  So "previous" is always
+ *             the geometry as of the previous srtRefitScene, or as of the upload; before any snapshot exists it is the
+ *             current geometry (all displacements are exact zeros).
+ *   history   srtRefitScene keeps the context's temporal history and counts the refits since the last temporal frame.
+ *   memory    48 B per triangle and 48 B per sphere from the first update (or refit) on, until the next srtUploadScene or
+ *             until tracking is disabled.
+ *
+ * srtRenderMotionTiles   asynchronous on `stream`; the parameters, tile layout, split, checks and side effects of
+ *             srtRenderFeatureTiles (none on the tunables, the host generator, the chunk scratch, srtLastKernelMs or
+ *             srtGetLaunchInfo), one plane; srtGatherTiles / srtResolveTiles work on dMotionTiles unchanged.
+ * srtRenderMotionImage   blocking, into HOST float[W*H*4]: xyz = sum / w (0 where w == 0), w = count, as
+ *             srtRenderFeatureImage returns its planes.
+ *   Per sample, in sample-index order from 0, the pass traces the beauty render's camera ray (same RNG key, same draws)
+ *   with the traversal `p` asks for.  A miss does not count.  A hit at p = o + t d adds the displacement m to a float
+ *   running sum and 1 to the count w (the plane's w equals the NORMAL plane's).  Only + - * / in float32, no contraction,
+ *   IEEE division; dot(a, b) = a.x b.x + (a.y b.y + a.z b.z), cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z,
+ *   a.x b.y - a.y b.x): tests/motion_ref.py evaluates this text in NumPy float32 bit for bit.
+ *   triangle  v0, v1, v2 and n = (v1 - v0) x (v2 - v0) from the current record, v0', v1', v2' from the snapshot's:
+ *             d_i = v_i' - v_i;  e0 = dot(n, cross(v1 - v0, p - v0)), e1 = dot(n, cross(v2 - v1, p - v1)),
+ *             e2 = dot(n, cross(v0 - v2, p - v2)) (the hit test's edge values; they weigh v2, v0 and v1);
+ *             s = (e0 + e1) + e2;  b0 = e1 / s, b1 = e2 / s, b2 = e0 / s;  m = (b0 d0 + b1 d1) + b2 d2 per component;
+ *             m = d0 unless s > 0.
+ *   sphere    c, c' = the current and the snapshot record's centre at the ray's time (the moving sphere's interpolation,
+ *             each with its own times), r, r' the radii:  m = (c' - c) + ((r' / r) - 1) (p - c) per component.  A
+ *             sphere's rotation is not observable and gives no motion.
+ *   An unmoved primitive gives m = 0 exactly: a scene in which nothing moved has an all-zero plane.
+ *   errors    (nothing launched, outputs untouched) tracking off; anything srtRenderFeatureTiles rejects; a NULL output.
+ *
+ * srtTemporalAccumulateMotion / srtTemporalReprojectMotion   srtTemporalAccumulate / srtTemporalReproject with dMotion,
+ *             the resolved motion plane in image order (DEVICE float4[W*H], sums with counts).  dMotion == NULL is the
+ *             plain entry in every byte (the plain entries call these with NULL).  With dMotion the text of "Temporal
+ *             accumulation" changes in exactly three places:
+ *   mean      mbar = m(MOTION.xyz, MOTION.w) per component, 0 where the count is 0
+ *   point     a hit: P = cur.origin + tbar d as before, P' = P + mbar per component, v = P' - prev.origin, and a tap's
+ *             plane test is |(Q_q - P') . n_p| <= (planeDist tbar) dlen.  A miss: v = d, unchanged
+ *   no camera-not-moved rule   every pixel goes through projection, snap, taps and acceptance even when the cameras agree
+ *             bit for bit: a static pixel still snaps onto itself, and a pixel an object has just uncovered is rejected
+ *             by the plane test instead of inheriting the object's radiance
+ *             Everything else is as written there; a zero plane with two different cameras is srtTemporalAccumulate bit
+ *             for bit.  A mean of affine images is the affine image of the mean: where all of a pixel's samples hit one
+ *             rigidly or affinely moving body, mbar is that body's displacement at the POSITION mean up to rounding.
+ *             Normals are not counter-rotated: the history's n_q is compared with the current n_p as it is, and the
+ *             default normalCos 0.5 tolerates a rotation of 60 degrees per frame.
+ *
+ * srtRenderTemporalFrame with tracking on: after exactly one srtRefitScene since its last frame it also runs the motion
+ * pass over `p`, resolves it and accumulates with srtTemporalAccumulateMotion against the kept history and camera.  No
+ * refit: the frame as described above, byte for byte.  More than one refit: the snapshot spans only the last epoch, so the
+ * history is dropped.  The temporal-adaptive frame entries drop the history after any refit, whatever the flag says. */
+int srtSetMotionTracking(SrtContext* ctx, int32_t enable);
+int srtRenderMotionTiles(SrtContext* ctx, const SrtRenderParams* p, void* dMotionTiles, void* stream);
+int srtRenderMotionImage(SrtContext* ctx, const SrtRenderParams* p, float* hMotion);
+int srtTemporalAccumulateMotion(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
+                                const void* dMoments, const void* const dPlanes[4], const void* dMotion, const SrtCamera* cam,
+                                const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
+                                void* dHistoryOut, void* stream);
+int srtTemporalReprojectMotion(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
+                               const void* const dPlanes[4], const void* dMotion, const SrtCamera* cam, const SrtCamera* prevCam,
+                               const void* dHistoryIn, void* dReprojected, void* stream);
 
 /* Multi-GPU: one process per GPU, the scene replicated, rank r of N renders tile positions
  * r, r+N, ... (SrtRenderParams.tileFirst / tileStride), and the path's only collective is ONE gather of the

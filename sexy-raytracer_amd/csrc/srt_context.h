@@ -58,6 +58,11 @@ struct Upload {
   bool geometryDirty = false;       // an update since the last refit: nothing renders
   float pairTime0 = 0, pairTime1 = 0;  // the times the closest-hit pair records were made for
   int32_t fastDivOption = 0;        // SceneOptions::fastDiv of the upload: what fastDivScene is while the certificate holds
+  // srtSetMotionTracking: triTest and spheres as of the previous srtRefitScene (or the upload), copied by the first update
+  // of an epoch before its kernel, or by a refit that no update preceded.  48 B per triangle and per sphere.
+  DeviceBuffer prevTriTest, prevSpheres;
+  bool haveSnapshot = false;   // the two buffers hold a snapshot (until then "previous" is the current tables)
+  bool epochSnapshot = false;  // ... taken since the last refit: later updates of the epoch leave it alone
 };
 
 struct SrtContext {
@@ -92,6 +97,8 @@ struct SrtContext {
   bool temporalValid = false;
   int32_t temporalKey[3] = {0, 0, 0};  // width, height, demodulate
   SrtCamera camFull{}, temporalCam{};
+  bool motionTracking = false;     // srtSetMotionTracking: the context's, like the tunables
+  int32_t temporalRefits = 0;      // srtRefitScene calls with tracking on since the last committed temporal frame
   int32_t tileTableKey[3] = {0, 0, 0};
   RenderPlan lastPlan{};  // the most recent render launch (srtGetLaunchInfo)
   int32_t lastGrid = 0;
@@ -182,8 +189,10 @@ int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, in
                    const void* const dPlanes[4], void* dOut, void* dRgba, void* streamPtr, bool moments = false,
                    const void* dMoments = nullptr);
 int checkTemporalParams(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, TemporalArgs& a);
+int srtRenderMotionTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dMotionTiles, void* streamPtr);
+// dMotion: the resolved motion plane (srtTemporalAccumulateMotion), or null for srtTemporalAccumulate
 int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
-                              const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
+                              const void* dMoments, const void* const dPlanes[4], const void* dMotion, const SrtCamera* cam,
                               const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
                               void* dHistoryOut, void* streamPtr);
 int temporalStats(SrtContext* ctx, size_t nPix, const void* dCurrent, const void* dAccumulated, const void* dHistory,

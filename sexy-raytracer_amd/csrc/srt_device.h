@@ -209,6 +209,14 @@ struct FeatureArgs {
 
 // srtRenderFeatureTileList (srt_features_list.hip): the feature pass of the listed tiles, into image-order planes.  Of f,
 // tileFirst, tileStride, numLocalTiles, numTiles and tileBlock are not read; f.out[k] = float4[W*H] in image order.
+// srtRenderMotionTiles (srt_motion.hip): the feature pass's launch (f.out[0] = the motion plane, f.planes is not read) with
+// the primitive records of the previous srtRefitScene, laid out as scene.triTest and scene.spheres
+struct MotionArgs {
+  FeatureArgs f;
+  const float4* prevTriTest;
+  const float4* prevSpheres;
+};
+
 struct FeatureListArgs {
   FeatureArgs f;
   const uint32_t* list;  // tx | ty << 16 per listed tile (RenderArgs::tileXY's format)
@@ -249,6 +257,7 @@ struct TemporalArgs {
   SrtCamera cam, prev;
   int32_t sameCamera;  // cam and prev agree bit for bit in what the projection reads: every pixel is its own history
   float normalCos, planeDist, maxHistory;
+  const float4* motion;  // srtTemporalAccumulateMotion: the resolved motion plane (sums with counts), else null
 };
 
 struct ResolveArgs {

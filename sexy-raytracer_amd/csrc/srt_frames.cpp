@@ -19,6 +19,7 @@ struct FrameStage {
   size_t nPix = 0, imageBytes = 0, tileBytes = 0;  // pixels, a float4 image, a float4 tile buffer of the whole image
   DeviceBuffer tiles, mtiles, featTiles[4];        // tile order: beauty, moments, feature planes
   DeviceBuffer accum, mom, rgba, featImage[4];     // image order: what render() and features() resolve into
+  DeviceBuffer motionTiles, motionImage;           // the motion plane (a fifth one: the frame after a tracked refit)
   DeviceBuffer accOut, momOut, out, outRgba;       // image order: the temporal step's and the denoiser's outputs
   void* dTiles[4] = {nullptr, nullptr, nullptr, nullptr};
   void* dPlanes[4] = {nullptr, nullptr, nullptr, nullptr};  // featImage as the denoiser and the temporal step take it
@@ -65,6 +66,11 @@ struct FrameStage {
       if (dTiles[k] && srtResolveTiles(ctx, &p, dTiles[k], nullptr, dPlanes[k], nullptr)) return 1;
     return 0;
   }
+  // The motion pass of the same parameters, resolved into motionImage
+  int motion() {
+    if (srtRenderMotionTilesImpl(ctx, &p, motionTiles.get(), nullptr)) return 1;
+    return srtResolveTiles(ctx, &p, motionTiles.get(), nullptr, motionImage.get(), nullptr);
+  }
   // The denoiser (moments: srtDenoiseMoments with that plane) into the outputs reserveDenoised reserved, if any
   int denoise(const SrtDenoiseParams* d, const DeviceBuffer& beauty, bool moments, const DeviceBuffer& dMoments) {
     if (!out.get() && !outRgba.get()) return 0;
@@ -83,10 +89,16 @@ struct FrameStage {
 // The history ping-pong of the temporal frame entries (SrtContext::temporalHistory).  begin, before the frame's first
 // launch: a history of another size or demodulation is forgotten (first: the reservation may reallocate), both histories
 // are reserved, the frame reads the one the last frame wrote (null: none) and writes the other, and no history is valid
-// until commit, after the frame is complete.
-int beginTemporalFrame(SrtContext* ctx, int32_t W, int32_t H, bool demodulate, const void** histIn, void** histOut) {
+// until commit, after the frame is complete.  Refits with motion tracking on leave the history valid and are counted: a
+// motionAware frame (srtRenderTemporalFrame) keeps it across exactly one -- the snapshot spans one epoch -- and *useMotion
+// tells it to reproject with the motion plane; any other frame, or more refits, drop it as a refit without tracking does.
+int beginTemporalFrame(SrtContext* ctx, int32_t W, int32_t H, bool demodulate, bool motionAware, const void** histIn, void** histOut,
+                       bool* useMotion = nullptr) {
   const int32_t key[3] = {W, H, demodulate ? 1 : 0};
   if (memcmp(key, ctx->temporalKey, sizeof key) != 0) ctx->temporalValid = false;
+  const bool across = motionAware && ctx->motionTracking && ctx->temporalRefits == 1;
+  if (ctx->temporalRefits > 0 && !across) ctx->temporalValid = false;
+  if (useMotion) *useMotion = across && ctx->temporalValid;
   for (auto& h : ctx->temporalHistory)
     if (h.reserve((size_t)W * H * SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL) != hipSuccess) return fail(ctx, "temporal: hipMalloc history");
   *histIn = ctx->temporalValid ? ctx->temporalHistory[ctx->temporalCurrent].get() : nullptr;
@@ -101,6 +113,7 @@ void commitTemporalFrame(SrtContext* ctx, int32_t W, int32_t H, bool demodulate)
   ctx->temporalCam = ctx->camFull;
   memcpy(ctx->temporalKey, key, sizeof key);
   ctx->temporalValid = true;
+  ctx->temporalRefits = 0;
 }
 
 // srtRenderImage, and srtRenderImageMoments (moments): the same render through srtRenderTilesMoments, both planes resolved
@@ -160,6 +173,23 @@ int srtRenderFeatureImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, int32
   return 0;
 }
 
+// srtRenderMotionImage: the motion pass resolved, the division by the count the host's as above
+int srtRenderMotionImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, float* hMotion) {
+  if (!ctx) return 1;
+  if (!ctx->motionTracking) return fail(ctx, "motion: motion tracking is off (srtSetMotionTracking)");
+  const void* const outs[4] = {hMotion, nullptr, nullptr, nullptr};
+  if (checkFeatureArgs(ctx, pIn, 1, outs)) return 1;
+  FrameStage f(ctx, "motion", pIn);
+  if (f.begin() || f.reserve(f.motionTiles, f.tileBytes) || f.reserve(f.motionImage, f.imageBytes)) return 1;
+  if (f.motion() || f.finish() || f.copyOut(hMotion, f.motionImage, f.imageBytes, "out")) return 1;
+  for (size_t i = 0; i < f.nPix; ++i) {
+    float* v = hMotion + 4 * i;
+    const float w = v[3];
+    for (int c = 0; c < 3; ++c) v[c] = w != 0.0f ? v[c] / w : 0.0f;
+  }
+  return 0;
+}
+
 // srtRenderDenoisedImage: the beauty render and its resolve exactly as srtRenderImage does them, the feature pass of the
 // same parameters, the denoiser.  moments: srtRenderDenoisedImageMoments -- the moments render, its plane resolved (into
 // hMoments as well) and handed to the denoiser
@@ -202,7 +232,8 @@ int srtRenderAdaptiveDenoisedImageImpl(SrtContext* ctx, const SrtRenderParams* p
 }
 
 // srtRenderTemporalFrame: the frame exactly as srtRenderDenoisedImageMoments renders it, with all four planes, accumulated
-// onto the context's history, the denoiser on the accumulated sums
+// onto the context's history, the denoiser on the accumulated sums.  The one frame after a refit with motion tracking on
+// also runs the motion pass and accumulates with srtTemporalAccumulateMotion (include/srt_hip.h "Motion")
 int srtRenderTemporalFrameImpl(SrtContext* ctx, const SrtRenderParams* pIn, const SrtDenoiseParams* d, const SrtTemporalParams* t,
                                float* hAccum, float* hDenoised, uint8_t* hRgba, SrtTemporalStats* stats) {
   if (!ctx) return 1;
@@ -222,9 +253,11 @@ int srtRenderTemporalFrameImpl(SrtContext* ctx, const SrtRenderParams* pIn, cons
   if (f.reserveDenoised(hDenoised, hRgba) || f.reserveFeatures(SRT_FEATURE_ALL)) return 1;
   const void* histIn;
   void* histOut;
-  if (beginTemporalFrame(ctx, W, H, t->demodulate != 0, &histIn, &histOut)) return 1;
-  if (f.render() || f.features(SRT_FEATURE_ALL)) return 1;
-  if (srtTemporalAccumulateImpl(ctx, t, W, H, f.accum.get(), f.mom.get(), f.dPlanes, &ctx->camFull, &ctx->temporalCam, histIn,
+  bool useMotion;
+  if (beginTemporalFrame(ctx, W, H, t->demodulate != 0, true, &histIn, &histOut, &useMotion)) return 1;
+  if (useMotion && (f.reserve(f.motionTiles, f.tileBytes) || f.reserve(f.motionImage, f.imageBytes))) return 1;
+  if (f.render() || f.features(SRT_FEATURE_ALL) || (useMotion && f.motion())) return 1;
+  if (srtTemporalAccumulateImpl(ctx, t, W, H, f.accum.get(), f.mom.get(), f.dPlanes, f.motionImage.get(), &ctx->camFull, &ctx->temporalCam, histIn,
                                 f.accOut.get(), f.momOut.get(), histOut, nullptr))
     return 1;
   if (f.denoise(d, f.accOut, true, f.momOut) || f.finish()) return 1;
@@ -256,7 +289,7 @@ int srtRenderTemporalAdaptiveFrameImpl(SrtContext* ctx, const SrtRenderParams* p
   if (f.reserveDenoised(hDenoised, hRgba) || f.reserveFeatures(SRT_FEATURE_ALL)) return 1;
   const void* histIn;
   void* histOut;
-  if (beginTemporalFrame(ctx, W, H, t->demodulate != 0, &histIn, &histOut)) return 1;
+  if (beginTemporalFrame(ctx, W, H, t->demodulate != 0, false, &histIn, &histOut)) return 1;
   if (f.features(SRT_FEATURE_ALL)) return 1;
   if (srtRenderTemporalAdaptiveImpl(ctx, &f.p, ap, t, f.dPlanes, &ctx->temporalCam, histIn, f.accum.get(), f.mom.get(), f.accOut.get(),
                                     f.momOut.get(), histOut, stats, nullptr, guided))
@@ -300,6 +333,9 @@ int srtRenderAdaptiveImage(SrtContext* ctx, const SrtRenderParams* p, const SrtA
 }
 int srtRenderFeatureImage(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, float* const hPlanes[4]) {
   SRT_GUARDED(ctx, srtRenderFeatureImageImpl(ctx, p, planes, hPlanes));
+}
+int srtRenderMotionImage(SrtContext* ctx, const SrtRenderParams* p, float* hMotion) {
+  SRT_GUARDED(ctx, srtRenderMotionImageImpl(ctx, p, hMotion));
 }
 int srtRenderDenoisedImage(SrtContext* ctx, const SrtRenderParams* p, const SrtDenoiseParams* d, float* hAccum,
                            float* hDenoised, uint8_t* hRgba) {

@@ -45,6 +45,10 @@ int srt_features_list_plan(int closest, int ldsTree, int accumulate, size_t lds,
 int srt_launch_features_list(const FeatureListArgs* a, int closest, int ldsTree, int accumulate, int grid, size_t lds,
                              hipStream_t stream);
 
+// srt_motion.hip: as srt_features.hip's pair
+int srt_motion_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU);
+int srt_launch_motion(const MotionArgs* a, int closest, int ldsTree, int grid, size_t lds, hipStream_t stream);
+
 // srt_denoise.hip
 int srt_launch_denoise(const DenoiseArgs* a, int iterations, int ldsMaxStep, hipStream_t stream);
 

@@ -68,6 +68,26 @@ int srtRenderFeatureTilesImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t
   }, [&](bool closest, bool ldsTree, int grid, size_t lds) { return srt_launch_features(&a, closest, ldsTree, grid, lds, stream); });
 }
 
+/* Motion pass (srt_motion.hip): the feature pass's checks, launch shape and side effects.  "Previous" is the snapshot
+ * srt_refit_host.cpp keeps while tracking is on, or the current tables before there is one (exact zeros). */
+int srtRenderMotionTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dMotionTiles, void* streamPtr) {
+  if (!ctx) return 1;
+  if (!ctx->motionTracking) return fail(ctx, "motion: motion tracking is off (srtSetMotionTracking)");
+  void* const planes[4] = {dMotionTiles, nullptr, nullptr, nullptr};
+  if (checkFeatureArgs(ctx, p, 1, planes)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+  MotionArgs a;
+  setImageArgs(a.f, ctx, p);
+  a.f.out[0] = static_cast<float4*>(dMotionTiles);
+  const Upload& up = ctx->upload;
+  a.prevTriTest = up.haveSnapshot ? up.prevTriTest.get<const float4>() : up.scene.triTest;
+  a.prevSpheres = up.haveSnapshot ? up.prevSpheres.get<const float4>() : up.scene.spheres;
+  return launchFeaturePass(ctx, p, a.f, a.f.numLocalTiles, stream, [&](bool closest, bool ldsTree, size_t lds, int* block, int* perCU) {
+    return srt_motion_plan(closest, ldsTree, lds, block, perCU);
+  }, [&](bool closest, bool ldsTree, int grid, size_t lds) { return srt_launch_motion(&a, closest, ldsTree, grid, lds, stream); });
+}
+
 /* Feature pass over a tile list (srt_features_list.hip), into image-order planes.  The feature pass's side effects: its own
  * counter and the caller's planes. */
 int srtRenderFeatureTileListImpl(SrtContext* ctx, const SrtRenderParams* p, int32_t planes, const void* dTileList,
@@ -156,7 +176,8 @@ int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, in
 }
 
 /* Temporal accumulation (srt_temporal.hip).  Reads nothing of the context but the device ordinal; the frame entry keeps
- * the histories and the previous camera in the context. */
+ * the histories and the previous camera in the context.  dMotion (the Motion entries) selects the motion-aware kernels;
+ * null is the plain entry in every byte. */
 static bool sameProjection(const SrtCamera& a, const SrtCamera& b) {
   return !memcmp(a.origin, b.origin, 12) && !memcmp(a.lleft, b.lleft, 12) && !memcmp(a.horizontal, b.horizontal, 12) &&
          !memcmp(a.vertical, b.vertical, 12) && !memcmp(a.w, b.w, 12);
@@ -180,8 +201,9 @@ int checkTemporalParams(SrtContext* ctx, const SrtTemporalParams* t, int32_t wid
 
 // Everything srtTemporalAccumulate checks, and the kernel's arguments: nothing is launched
 static int temporalArgs(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
-                        const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
-                        const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut, TemporalArgs& a) {
+                        const void* dMoments, const void* const dPlanes[4], const void* dMotion, const SrtCamera* cam,
+                        const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut,
+                        TemporalArgs& a) {
   if (!ctx) return 1;
   if (checkTemporalParams(ctx, t, width, height, a)) return 1;
   if (!dBeauty) return fail(ctx, "temporal: null beauty buffer");
@@ -208,15 +230,16 @@ static int temporalArgs(SrtContext* ctx, const SrtTemporalParams* t, int32_t wid
   a.cam = *cam;
   a.prev = dHistoryIn ? *prevCam : *cam;
   a.sameCamera = sameProjection(a.cam, a.prev) ? 1 : 0;
+  a.motion = static_cast<const float4*>(dMotion);  // set: the Motion forms, which do not read sameCamera
   return 0;
 }
 
 int srtTemporalAccumulateImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
-                                           const void* dBeauty, const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam,
-                                           const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
-                                           void* dHistoryOut, void* streamPtr) {
+                                           const void* dBeauty, const void* dMoments, const void* const dPlanes[4], const void* dMotion,
+                                           const SrtCamera* cam, const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut,
+                                           void* dMomentsOut, void* dHistoryOut, void* streamPtr) {
   TemporalArgs a;
-  if (temporalArgs(ctx, t, width, height, dBeauty, dMoments, dPlanes, cam, prevCam, dHistoryIn, dBeautyOut, dMomentsOut, dHistoryOut, a))
+  if (temporalArgs(ctx, t, width, height, dBeauty, dMoments, dPlanes, dMotion, cam, prevCam, dHistoryIn, dBeautyOut, dMomentsOut, dHistoryOut, a))
     return 1;
   const int rc = srt_launch_temporal(&a, static_cast<hipStream_t>(streamPtr));
   if (rc) return fail(ctx, "temporal launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -245,13 +268,13 @@ int temporalStats(SrtContext* ctx, size_t nPix, const void* dCurrent, const void
 /* Temporal-adaptive frames (srt_temporal_adaptive.hip): the reprojected history once per frame, srtRenderAdaptive's rounds
  * deciding on the pooled moments, srtTemporalAccumulate of the final sums. */
 static int srtTemporalReprojectImpl(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
-                                    const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
-                                    const void* dHistoryIn, void* dReprojected, void* streamPtr) {
+                                    const void* const dPlanes[4], const void* dMotion, const SrtCamera* cam,
+                                    const SrtCamera* prevCam, const void* dHistoryIn, void* dReprojected, void* streamPtr) {
   if (!ctx) return 1;
   if (!dReprojected) return fail(ctx, "temporal: null reprojected buffer");
   TemporalArgs a;
   // srtTemporalAccumulate's checks; the beauty and its outputs are not part of this entry (any non-null pointer passes)
-  if (temporalArgs(ctx, t, width, height, dReprojected, nullptr, dPlanes, cam, prevCam, dHistoryIn, dReprojected, nullptr, dReprojected, a))
+  if (temporalArgs(ctx, t, width, height, dReprojected, nullptr, dPlanes, dMotion, cam, prevCam, dHistoryIn, dReprojected, nullptr, dReprojected, a))
     return 1;
   a.beauty = nullptr;
   a.beautyOut = nullptr;
@@ -271,7 +294,7 @@ int srtRenderTemporalAdaptiveImpl(SrtContext* ctx, const SrtRenderParams* p, con
   const int W = p->imageWidth, H = p->imageHeight;
   const size_t nPix = (size_t)W * H;
   TemporalArgs a;
-  if (temporalArgs(ctx, t, W, H, dAccumImage, dMomentsImage, dPlanes, &ctx->camFull, prevCam, dHistoryIn, dBeautyOut, dMomentsOut,
+  if (temporalArgs(ctx, t, W, H, dAccumImage, dMomentsImage, dPlanes, nullptr, &ctx->camFull, prevCam, dHistoryIn, dBeautyOut, dMomentsOut,
                    dHistoryOut, a))
     return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -329,12 +352,27 @@ int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width,
 int srtTemporalAccumulate(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
                           const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,
                           const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut, void* dHistoryOut, void* stream) {
-  SRT_GUARDED(ctx, srtTemporalAccumulateImpl(ctx, t, width, height, dBeauty, dMoments, dPlanes, cam, prevCam, dHistoryIn, dBeautyOut,
-                                             dMomentsOut, dHistoryOut, stream));
+  return srtTemporalAccumulateMotion(ctx, t, width, height, dBeauty, dMoments, dPlanes, nullptr, cam, prevCam, dHistoryIn, dBeautyOut,
+                                     dMomentsOut, dHistoryOut, stream);
+}
+int srtTemporalAccumulateMotion(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
+                                const void* dMoments, const void* const dPlanes[4], const void* dMotion, const SrtCamera* cam,
+                                const SrtCamera* prevCam, const void* dHistoryIn, void* dBeautyOut, void* dMomentsOut,
+                                void* dHistoryOut, void* stream) {
+  SRT_GUARDED(ctx, srtTemporalAccumulateImpl(ctx, t, width, height, dBeauty, dMoments, dPlanes, dMotion, cam, prevCam, dHistoryIn,
+                                             dBeautyOut, dMomentsOut, dHistoryOut, stream));
+}
+int srtRenderMotionTiles(SrtContext* ctx, const SrtRenderParams* p, void* dMotionTiles, void* stream) {
+  SRT_GUARDED(ctx, srtRenderMotionTilesImpl(ctx, p, dMotionTiles, stream));
 }
 int srtTemporalReproject(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* const dPlanes[4],
                          const SrtCamera* cam, const SrtCamera* prevCam, const void* dHistoryIn, void* dReprojected, void* stream) {
-  SRT_GUARDED(ctx, srtTemporalReprojectImpl(ctx, t, width, height, dPlanes, cam, prevCam, dHistoryIn, dReprojected, stream));
+  return srtTemporalReprojectMotion(ctx, t, width, height, dPlanes, nullptr, cam, prevCam, dHistoryIn, dReprojected, stream);
+}
+int srtTemporalReprojectMotion(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height,
+                               const void* const dPlanes[4], const void* dMotion, const SrtCamera* cam, const SrtCamera* prevCam,
+                               const void* dHistoryIn, void* dReprojected, void* stream) {
+  SRT_GUARDED(ctx, srtTemporalReprojectImpl(ctx, t, width, height, dPlanes, dMotion, cam, prevCam, dHistoryIn, dReprojected, stream));
 }
 int srtRenderTemporalAdaptive(SrtContext* ctx, const SrtRenderParams* p, const SrtAdaptiveParams* ap, const SrtTemporalParams* t,
                               const void* const dPlanes[4], const SrtCamera* prevCam, const void* dHistoryIn, void* dAccumImage,
@@ -354,6 +392,7 @@ int srtTemporalReset(SrtContext* ctx) {
   if (!ctx) return 1;
   (void)hipSetDevice(ctx->device);
   ctx->temporalValid = false;
+  ctx->temporalRefits = 0;
   for (auto& h : ctx->temporalHistory) h = DeviceBuffer();
   return 0;
 }

@@ -1,6 +1,7 @@
 // srt_refit_host.cpp -- host side of the geometry updates (include/srt_hip.h srtUpdateTriangles / srtUpdateSpheres /
 // srtRefitScene): argument checks, the device tables an uploaded scene needs for them (made by the first call that uses
-// them, so an upload that is never updated pays nothing), and the launches of srt_refit.hip.
+// them, so an upload that is never updated pays nothing), and the launches of srt_refit.hip.  Also srtSetMotionTracking
+// and the snapshot of the previous epoch's records that the motion pass reads (include/srt_hip.h "Motion").
 
 #include <hip/hip_runtime.h>
 
@@ -36,6 +37,35 @@ int triangleTable(SrtContext* ctx, const int32_t** out) {
   return 0;
 }
 
+// srtSetMotionTracking's snapshot: triTest and spheres as they are now, into the buffers the upload owns, on `stream`.
+// Taken once per epoch -- by its first update, ahead of that update's kernel, or by a refit that no update preceded.
+int snapshotGeometry(SrtContext* ctx, hipStream_t stream) {
+  Upload& up = ctx->upload;
+  if (!ctx->motionTracking || up.epochSnapshot) return 0;
+  const size_t triBytes = (size_t)up.scene.numTris * 48, sphBytes = (size_t)up.scene.numSpheres * 48;
+  HIP_OK(ctx, up.prevTriTest.reserve(triBytes));
+  HIP_OK(ctx, up.prevSpheres.reserve(sphBytes));
+  if (triBytes) HIP_OK(ctx, hipMemcpyAsync(up.prevTriTest.get(), up.scene.triTest, triBytes, hipMemcpyDeviceToDevice, stream));
+  if (sphBytes) HIP_OK(ctx, hipMemcpyAsync(up.prevSpheres.get(), up.scene.spheres, sphBytes, hipMemcpyDeviceToDevice, stream));
+  up.haveSnapshot = up.epochSnapshot = true;
+  return 0;
+}
+
+int setMotionTracking(SrtContext* ctx, int32_t enable) {
+  if (!ctx) return 1;
+  if (ctx->upload.geometryDirty) return fail(ctx, "srtSetMotionTracking: geometry was updated; call srtRefitScene first");
+  ctx->motionTracking = enable != 0;
+  if (!ctx->motionTracking) {
+    (void)hipSetDevice(ctx->device);
+    ctx->upload.prevTriTest = DeviceBuffer();
+    ctx->upload.prevSpheres = DeviceBuffer();
+    ctx->upload.haveSnapshot = ctx->upload.epochSnapshot = false;
+    if (ctx->temporalRefits) ctx->temporalValid = false;  // a history kept across a refit is of no use without its motion
+    ctx->temporalRefits = 0;
+  }
+  return 0;
+}
+
 int updateTrianglesDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dIn, void* stream) {
   if (!ctx) return 1;
   const int rc = checkUpdate(ctx, "srtUpdateTriangles", first, count, ctx->upload.haveScene ? ctx->upload.scene.numTris : 0, dIn, 16);
@@ -43,6 +73,7 @@ int updateTrianglesDevice(SrtContext* ctx, int32_t first, int32_t count, const v
   HIP_OK(ctx, hipSetDevice(ctx->device));
   const int32_t* table = nullptr;
   if (triangleTable(ctx, &table)) return 1;
+  if (snapshotGeometry(ctx, static_cast<hipStream_t>(stream))) return 1;
   ctx->upload.geometryDirty = true;
   const int e = srt_launch_refit_triangles(dIn, first, count, table, const_cast<float4*>(ctx->upload.scene.triTest),
                                            const_cast<float4*>(ctx->upload.scene.triShade), static_cast<hipStream_t>(stream));
@@ -55,6 +86,7 @@ int updateSpheresDevice(SrtContext* ctx, int32_t first, int32_t count, const voi
   const int rc = checkUpdate(ctx, "srtUpdateSpheres", first, count, ctx->upload.haveScene ? ctx->upload.scene.numSpheres : 0, dIn, 4);
   if (rc) return rc == 2 ? 0 : 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
+  if (snapshotGeometry(ctx, static_cast<hipStream_t>(stream))) return 1;
   ctx->upload.geometryDirty = true;
   const int e = srt_launch_refit_spheres(dIn, first, count, const_cast<float4*>(ctx->upload.scene.spheres), static_cast<hipStream_t>(stream));
   if (e) return fail(ctx, "srtUpdateSpheres: launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -82,6 +114,7 @@ int refitScene(SrtContext* ctx, void* streamPtr) {
   const DevScene& s = ctx->upload.scene;
   const int n = s.numNodes;
   int32_t flag = 0;
+  if (snapshotGeometry(ctx, stream)) return 1;  // tracking on and no update since the last refit: motion is zero
   if (n > 0) {
     if (!ctx->upload.refitTables) {
       // once per upload: the parent links, and the hybrid records' renumbering
@@ -113,7 +146,14 @@ int refitScene(SrtContext* ctx, void* streamPtr) {
   }
   if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "srtRefitScene: kernel failed: %s", hipGetErrorString(hipGetLastError()));
   ctx->upload.scene.fastDivScene = flag == 0 ? ctx->upload.fastDivOption : 0;
-  ctx->temporalValid = false;  // as srtUploadScene: the reprojection assumes the surfaces of the history's frame
+  // Without tracking, as srtUploadScene: the reprojection assumes the surfaces of the history's frame.  With it, the history
+  // stays and srtRenderTemporalFrame decides by the count of refits since its last frame (srt_frames.cpp)
+  if (ctx->motionTracking) {
+    if (ctx->temporalRefits < 2) ctx->temporalRefits++;
+    ctx->upload.epochSnapshot = false;
+  } else {
+    ctx->temporalValid = false;
+  }
   std::fill(ctx->upload.itemBoxesStale.begin(), ctx->upload.itemBoxesStale.end(), (uint8_t)1);
   ctx->upload.geometryDirty = false;
   return 0;
@@ -136,5 +176,6 @@ int srtUpdateSpheres(SrtContext* ctx, int32_t first, int32_t count, const SrtSph
   SRT_GUARDED(ctx, updateHost(ctx, "srtUpdateSpheres", first, count, ctx ? ctx->upload.scene.numSpheres : 0, hSpheres, sizeof(SrtSphereIn), updateSpheresDevice));
 }
 int srtRefitScene(SrtContext* ctx, void* stream) { SRT_GUARDED(ctx, refitScene(ctx, stream)); }
+int srtSetMotionTracking(SrtContext* ctx, int32_t enable) { SRT_GUARDED(ctx, setMotionTracking(ctx, enable)); }
 
 }  // extern "C"

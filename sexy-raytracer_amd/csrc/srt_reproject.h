@@ -67,6 +67,9 @@ __device__ __forceinline__ AlbedoTerms albedoTerms(const float4 al) {
 // choose the taps, test them, blend the accepted ones, cap the count.  h = r, g, b, count, S1, S2 and has come in as zeros
 // and false and stay so without history or an accepted tap.  The tap loop keeps the form DESIGN.md 5.9 asks for: loads
 // under nested conditions, taps in a plain float[4][6].
+// MOTION (include/srt_hip.h "Motion"): a.motion is the resolved motion plane.  The hit point moves by the pixel's mean
+// displacement before it is projected and before the taps' plane test, and the camera-not-moved rule does not apply.
+template <bool MOTION = false>
 __device__ __forceinline__ void reprojectHistory(const TemporalArgs& a, int x, int y, bool hit, const V3f np, float tbar,
                                                  float (&h)[6], bool& has) {
   const int W = a.width, H = a.height;
@@ -80,7 +83,8 @@ __device__ __forceinline__ void reprojectHistory(const TemporalArgs& a, int x, i
     bool ok = true;
     V3f P{0.0f, 0.0f, 0.0f};
     float dlen = 0.0f;
-    if (!a.sameCamera) {
+    const bool sameCamera = !MOTION && a.sameCamera;
+    if (!sameCamera) {
       const float sc = ((float)x + 0.5f) / (float)(W - 1);
       const float tc = ((float)(H - y) + 0.5f) / (float)(H - 1);
       const V3f o = ld(a.cam.origin), ll = ld(a.cam.lleft), hz = ld(a.cam.horizontal), vt = ld(a.cam.vertical);
@@ -88,6 +92,10 @@ __device__ __forceinline__ void reprojectHistory(const TemporalArgs& a, int x, i
                   ((ll.z + sc * hz.z) + tc * vt.z) - o.z};
       dlen = sqrtf(dot3(d, d));
       P = V3f{o.x + tbar * d.x, o.y + tbar * d.y, o.z + tbar * d.z};
+      if constexpr (MOTION) {  // P' = P + mbar: where the pixel's surface was in the history's frame
+        const float4 mv = a.motion[(size_t)y * W + x];
+        P = V3f{P.x + meanOf(mv.x, mv.w), P.y + meanOf(mv.y, mv.w), P.z + meanOf(mv.z, mv.w)};
+      }
       const V3f po = ld(a.prev.origin), pl = ld(a.prev.lleft), pw = ld(a.prev.w), pH = ld(a.prev.horizontal),
                 pV = ld(a.prev.vertical);
       const V3f v = hit ? V3f{P.x - po.x, P.y - po.y, P.z - po.z} : d;
@@ -135,7 +143,7 @@ __device__ __forceinline__ void reprojectHistory(const TemporalArgs& a, int x, i
           if (c0.w > 0.0f && c0.w < __builtin_inff()) {
             c1 = h1[q];
             c2 = h2[q];
-            take = a.sameCamera || tapMatches(hit, np, P, planeLimit, a.normalCos, c1, c2);
+            take = sameCamera || tapMatches(hit, np, P, planeLimit, a.normalCos, c1, c2);
           }
         }
         acc[k] = take;

@@ -7,12 +7,13 @@
 // loads of records it uses half of, the depth and moments planes).  The taps are a data-dependent gather of
 // history records: neighbouring pixels gather neighbouring records, so they go through the vector L1.  No LDS, no scratch
 // memory, no atomics.  The reprojection itself is srt_reproject.h's reprojectHistory, shared with srt_temporal_adaptive.hip.
+// MOTION: srtTemporalAccumulateMotion's instances (a.motion set), the motion-aware form of the reprojection.
 #include "srt_reproject.h"
 #include "srt_launch.h"
 
 namespace {
 
-template <bool DEMOD>
+template <bool DEMOD, bool MOTION = false>
 __global__ __launch_bounds__(TP_TILE* TP_TILE) void srt_temporal_kernel(const TemporalArgs a) {
   const int x = (int)blockIdx.x * TP_TILE + (int)(threadIdx.x % TP_TILE);
   const int y = (int)blockIdx.y * TP_TILE + (int)(threadIdx.x / TP_TILE);
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(TP_TILE* TP_TILE) void srt_temporal_kernel(const Te
   // ---- the reprojected history h
   float h[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // r, g, b, count, S1, S2
   bool has = false;
-  reprojectHistory(a, x, y, hit, np, tbar, h, has);
+  reprojectHistory<MOTION>(a, x, y, hit, np, tbar, h, has);
 
   // ---- outputs
   const bool add = has && usable;
@@ -87,7 +88,11 @@ __global__ __launch_bounds__(TP_TILE* TP_TILE) void srt_temporal_kernel(const Te
 
 extern "C" int srt_launch_temporal(const TemporalArgs* a, hipStream_t stream) {
   const dim3 grid((a->width + TP_TILE - 1) / TP_TILE, (a->height + TP_TILE - 1) / TP_TILE), block(TP_TILE * TP_TILE);
-  if (a->albedo)
+  if (a->motion && a->albedo)
+    hipLaunchKernelGGL((srt_temporal_kernel<true, true>), grid, block, 0, stream, *a);
+  else if (a->motion)
+    hipLaunchKernelGGL((srt_temporal_kernel<false, true>), grid, block, 0, stream, *a);
+  else if (a->albedo)
     hipLaunchKernelGGL(srt_temporal_kernel<true>, grid, block, 0, stream, *a);
   else
     hipLaunchKernelGGL(srt_temporal_kernel<false>, grid, block, 0, stream, *a);

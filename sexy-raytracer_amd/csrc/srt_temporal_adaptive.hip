@@ -41,6 +41,31 @@ __global__ __launch_bounds__(TP_TILE* TP_TILE) void srt_temporal_reproject_kerne
   o0[nPix + i] = make_float4(h[4], h[5], 0.0f, has ? 1.0f : 0.0f);
 }
 
+// srtTemporalReprojectMotion (a.motion set): the kernel above with the motion-aware reprojection.  Stated a second time:
+// as a template, or with the pixel's code in a shared inlined function, the kernel above lost its name or its instruction
+// order against the build before this one (tools/isa_compare.py)
+__global__ __launch_bounds__(TP_TILE* TP_TILE) void srt_temporal_reproject_motion_kernel(const TemporalArgs a) {
+  const int x = (int)blockIdx.x * TP_TILE + (int)(threadIdx.x % TP_TILE);
+  const int y = (int)blockIdx.y * TP_TILE + (int)(threadIdx.x / TP_TILE);
+  const int W = a.width, H = a.height;
+  if (x >= W || y >= H) return;
+  const size_t nPix = (size_t)W * H;
+  const size_t i = (size_t)y * W + x;
+
+  float h[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool has = false;
+  if (a.historyIn) {
+    bool hit;
+    V3f np;
+    float tbar;
+    pixelSurface(a.normal[i], a.depth[i], hit, np, tbar);
+    reprojectHistory<true>(a, x, y, hit, np, tbar, h, has);
+  }
+  float4* const o0 = a.historyOut;
+  o0[i] = make_float4(h[0], h[1], h[2], h[3]);
+  o0[nPix + i] = make_float4(h[4], h[5], 0.0f, has ? 1.0f : 0.0f);
+}
+
 // One wave per listed tile.  ACCUM: adds tile i's beauty and moments (list position i of the launch's tile-major outputs)
 // into the image-order sums, as srt_adaptive_update_kernel does.  Then the pooled moments M~ of the sums so far --
 // srt_temporal_kernel's dMomentsOut, from the pixel's reprojected record instead of the gather -- go through the
@@ -99,7 +124,10 @@ extern "C" {
 // a->historyOut receives the two reprojected planes; a->historyIn == nullptr writes zeros
 int srt_launch_temporal_reproject(const TemporalArgs* a, hipStream_t stream) {
   const dim3 grid((a->width + TP_TILE - 1) / TP_TILE, (a->height + TP_TILE - 1) / TP_TILE), block(TP_TILE * TP_TILE);
-  hipLaunchKernelGGL(srt_temporal_reproject_kernel, grid, block, 0, stream, *a);
+  if (a->motion)
+    hipLaunchKernelGGL(srt_temporal_reproject_motion_kernel, grid, block, 0, stream, *a);
+  else
+    hipLaunchKernelGGL(srt_temporal_reproject_kernel, grid, block, 0, stream, *a);
   return (int)hipGetLastError();
 }
 

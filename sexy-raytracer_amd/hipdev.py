@@ -40,6 +40,8 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderFeatureTileList", "srtRenderAdaptiveGuided", "srtRenderAdaptiveDenoisedImage",
            "srtRenderTemporalAdaptiveGuided", "srtRenderTemporalAdaptiveGuidedFrame",
            "srtUpdateTriangles", "srtUpdateSpheres", "srtUpdateTrianglesDevice", "srtUpdateSpheresDevice", "srtRefitScene",
+           "srtSetMotionTracking", "srtRenderMotionTiles", "srtRenderMotionImage", "srtTemporalAccumulateMotion",
+           "srtTemporalReprojectMotion",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
@@ -115,6 +117,13 @@ lib.srtRenderTemporalAdaptiveGuidedFrame.argtypes = lib.srtRenderTemporalAdaptiv
 lib.srtUpdateTriangles.argtypes = lib.srtUpdateSpheres.argtypes = [_vp, C.c_int32, C.c_int32, _vp]
 lib.srtUpdateTrianglesDevice.argtypes = lib.srtUpdateSpheresDevice.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
 lib.srtRefitScene.argtypes = [_vp, _vp]
+lib.srtSetMotionTracking.argtypes = [_vp, C.c_int32]
+lib.srtRenderMotionTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp]
+lib.srtRenderMotionImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(C.c_float)]
+lib.srtTemporalAccumulateMotion.argtypes = [_vp, C.POINTER(abi.SrtTemporalParams), C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_vp),
+                                            _vp, C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtCamera), _vp, _vp, _vp, _vp, _vp]
+lib.srtTemporalReprojectMotion.argtypes = [_vp, C.POINTER(abi.SrtTemporalParams), C.c_int32, C.c_int32, C.POINTER(_vp), _vp,
+                                           C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtCamera), _vp, _vp, _vp]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -425,15 +434,22 @@ class Context:
         return accum, moments, denoised, rgba
 
     def temporal_accumulate(self, tparams, width, height, d_beauty_ptr, d_moments_ptr, plane_ptrs, cam, prev_cam, d_history_in_ptr,
-                            d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream=None):
+                            d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream=None, motion_ptr=None):
         """Asynchronous temporal accumulation over DEVICE image-order buffers (include/srt_hip.h srtTemporalAccumulate):
         reprojects the history written with prev_cam (None / NULL history: the first frame) onto cam and adds the current
         frame.  plane_ptrs[k] = the resolved feature plane of bit 1 << k; a history is
-        abi.SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL bytes per pixel."""
+        abi.SRT_TEMPORAL_HISTORY_BYTES_PER_PIXEL bytes per pixel.  motion_ptr: the resolved motion plane of
+        render_motion_tiles (DEVICE float4[W*H]) -> srtTemporalAccumulateMotion, the motion-aware reprojection."""
         arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
-        self._check(lib.srtTemporalAccumulate(self.h, C.byref(tparams), int(width), int(height), d_beauty_ptr, d_moments_ptr, arr,
-                                              C.byref(cam), C.byref(prev_cam) if prev_cam is not None else None,
-                                              d_history_in_ptr, d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream))
+        prev = C.byref(prev_cam) if prev_cam is not None else None
+        if motion_ptr is None:
+            self._check(lib.srtTemporalAccumulate(self.h, C.byref(tparams), int(width), int(height), d_beauty_ptr, d_moments_ptr,
+                                                  arr, C.byref(cam), prev, d_history_in_ptr, d_beauty_out_ptr,
+                                                  d_moments_out_ptr, d_history_out_ptr, stream))
+        else:
+            self._check(lib.srtTemporalAccumulateMotion(self.h, C.byref(tparams), int(width), int(height), d_beauty_ptr,
+                                                        d_moments_ptr, arr, motion_ptr, C.byref(cam), prev, d_history_in_ptr,
+                                                        d_beauty_out_ptr, d_moments_out_ptr, d_history_out_ptr, stream))
 
     def render_temporal_frame(self, params, dparams=None, tparams=None, want_stats=True):
         """One frame of a sequence (srtRenderTemporalFrame): render with the camera currently set, accumulate onto the history
@@ -457,13 +473,18 @@ class Context:
         self._check(lib.srtTemporalReset(self.h))
 
     def temporal_reproject(self, tparams, width, height, plane_ptrs, cam, prev_cam, d_history_in_ptr, d_reprojected_ptr,
-                           stream=None):
+                           stream=None, motion_ptr=None):
         """srtTemporalReproject: the reprojected history h of temporal_accumulate, written once into DEVICE float4[2][W*H]
-        ({h.r, h.g, h.b, h.count} and {h.S1, h.S2, 0, has}); None / NULL history gives zeros."""
+        ({h.r, h.g, h.b, h.count} and {h.S1, h.S2, 0, has}); None / NULL history gives zeros.  motion_ptr as
+        temporal_accumulate's -> srtTemporalReprojectMotion."""
         arr = (_vp * 4)(*[(p if p else None) for p in list(plane_ptrs) + [None] * (4 - len(plane_ptrs))])
-        self._check(lib.srtTemporalReproject(self.h, C.byref(tparams), int(width), int(height), arr, C.byref(cam),
-                                             C.byref(prev_cam) if prev_cam is not None else None, d_history_in_ptr,
-                                             d_reprojected_ptr, stream))
+        prev = C.byref(prev_cam) if prev_cam is not None else None
+        if motion_ptr is None:
+            self._check(lib.srtTemporalReproject(self.h, C.byref(tparams), int(width), int(height), arr, C.byref(cam), prev,
+                                                 d_history_in_ptr, d_reprojected_ptr, stream))
+        else:
+            self._check(lib.srtTemporalReprojectMotion(self.h, C.byref(tparams), int(width), int(height), arr, motion_ptr,
+                                                       C.byref(cam), prev, d_history_in_ptr, d_reprojected_ptr, stream))
 
     @classmethod
     def _temporal_adaptive_stats(cls, st):
@@ -571,8 +592,27 @@ class Context:
 
     def refit(self, stream=None):
         """srtRefitScene: every node box from the current primitive records, and what is derived from boxes; the topology
-        stays.  Blocking.  Drops the temporal history."""
+        stays.  Blocking.  Drops the temporal history unless motion tracking is on."""
         self._check(lib.srtRefitScene(self.h, stream))
+
+    def set_motion_tracking(self, enable=True):
+        """srtSetMotionTracking: keep the geometry of the previous refit (48 B per triangle and per sphere) so that
+        render_motion has a displacement to report and render_temporal_frame keeps its history across one update + refit.
+        Call order: enable, upload, then per frame update_*, refit, render_temporal_frame."""
+        self._check(lib.srtSetMotionTracking(self.h, 1 if enable else 0))
+
+    def render_motion(self, params):
+        """Motion pass (srtRenderMotionImage): (H, W, 4) float32, xyz = the mean displacement from the first hit of the
+        pixel's camera rays to where that surface point was at the previous refit (0 where nothing was hit), w = the
+        hit count."""
+        out = np.zeros((params.imageHeight, params.imageWidth, 4), np.float32)
+        self._check(lib.srtRenderMotionImage(self.h, C.byref(params), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_motion_tiles(self, params, d_motion_ptr, stream=None):
+        """Asynchronous motion pass into a DEVICE tile buffer float4[numLocalTiles*64] (sums with counts), laid out as
+        render_feature_tiles's planes: resolve_tiles / gather_tiles take it unchanged."""
+        self._check(lib.srtRenderMotionTiles(self.h, C.byref(params), d_motion_ptr, stream))
 
     def trace(self, rays, traversal=abi.SRT_TRAVERSE_FAITHFUL):
         rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)

@@ -73,6 +73,30 @@ class hipDevice {
     return srtRefitScene(ctx, nullptr) == 0 || error();
   }
 
+  // Motion tracking (include/srt_hip.h "Motion"): the geometry of the previous refit stays on the device, so that
+  // rtFrameTemporal keeps its history across one update + refit and rtMotion has a displacement to report.  Call order:
+  // init, setMotionTracking(true), then per frame updateTriangles / updateSpheres, refit, rtFrameTemporal.
+  bool setMotionTracking(bool enable) {
+    if (!ctx) return false;
+    return srtSetMotionTracking(ctx, enable ? 1 : 0) == 0 || error();
+  }
+  // The motion plane of the frame rtFrameTemporal renders with the same numSamples, seed and sampleFirst: float[w*h*4] in
+  // image order, xyz = the mean displacement back to the previous refit's geometry, w = the hit count.  Renders the size
+  // init was given.
+  bool rtMotion(const camera& cam, const color3f& background, int numSamples, uint64_t seed, int firstSample, std::vector<float>& motion) {
+    if (!ctx) return false;
+    if (srtSetCamera(ctx, &cam.data()) != 0) return error();
+    SrtRenderParams p{};
+    p.imageWidth = width; p.imageHeight = height; p.spp = numSamples; p.seed = seed;
+    for (int i = 0; i < 3; ++i) p.background[i] = background(i);
+    p.tMin = 0.001f;  // main.cpp:39
+    p.traversal = SRT_TRAVERSE_FAITHFUL;
+    p.tileFirst = 0; p.tileStride = 1;
+    p.sampleFirst = firstSample;
+    motion.assign((size_t)width * height * 4, 0.0f);
+    return srtRenderMotionImage(ctx, &p, motion.data()) == 0 || error();
+  }
+
   // Multi-GPU.  Rank 0 obtains an id (128 bytes) and hands it to the other processes by its own means;
   // every process then calls initRanks after init.  Single-process programs never call these.
   static bool uniqueId(void* id128) { return srtCommGetUniqueId(id128) == 0; }

@@ -64,7 +64,7 @@ def meta(path):
 
 
 def new_name(old):
-    m = re.match(r"(.*I(?:Lb[01]E)+)(Ev.*)", old)
+    m = re.match(r"(.*I(?:Lb[01]E)+)(EE?v.*)", old)  # EEv: a kernel in a namespace (a nested name)
     return m.group(1) + "Lb0E" + m.group(2) if m else old
 
 
