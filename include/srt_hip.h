@@ -876,7 +876,8 @@ int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, i
  * the uploaded scene's materials; p, normal, tangent, bitangent, uv, t, frontFace are read as the reference's hitRecord
  * fields.  Random draws come from the counter RNG keyed (seed, i, 0) -- the reference draws from its process-global
  * generator.  out13 per entry: attenuation[3], scattered direction[3], scattered origin[3], scatter's bool (0 / 1),
- * emitted[3].  HOST pointers; blocking. */
+ * emitted[3]; a light's scatter makes no scattered ray (material.h:144-146), and what the entry reports as one is not
+ * specified.  A hit whose material is not one of the scene's is refused.  HOST pointers; blocking. */
 int srtScatterRays(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, float* out13);
 
 /* Duration of the most recent srtRenderTiles kernel, from HIP events recorded

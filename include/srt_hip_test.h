@@ -32,6 +32,14 @@ typedef struct SrtAovRecord {
 } SrtAovRecord;
 int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAovRecord* hOut);
 
+/* What srtScatterRays does (include/srt_hip.h), through any instance of the kernels' shading function: bit 0 of `form` selects the
+ * WIDE instance (all four texel loads of a pbr hit in flight at once: the path-pool kernel and the kernels over the
+ * LDS-resident tree), bit 1 the COUNT instance (the counting launches).  Form 0 is srtScatterRays itself.  Entry i is keyed
+ * (seed, i, 0).  outFetches: one uint32 per entry, the texel-fetch counter of the call (lookups of loaded images; stays 0
+ * in a form without COUNT), or NULL.  Both entries refuse a hit whose material is not one of the scene's. */
+int srtScatterRaysForm(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, int32_t form, float* out13,
+                       uint32_t* outFetches);
+
 /* Sub-step profile of the most recent countStats launch of the step-scheduler kernel (shader clocks summed over waves,
  * diagnostics only; zero after one of the path-pool kernel, which a counting launch runs where the production launch would):
  * out10 = { hit step: hit record, textures, direction draw, BRDF + bookkeeping; restart step;

@@ -229,10 +229,10 @@ struct checker : texture {  // texture.h:34-52
 };
 struct imagePNG : texture {  // texture.h:109-153 (image3bpp :54-107 is the bpp=3 case)
   const uint8_t* data;
-  const uint8_t* dataEnd;  // end of the owning texel buffer: defines the 1-bpp overrun
+  const uint8_t* dataEnd;  // end of this image's own texels: defines the 1-bpp overrun
   int width, height, bpp, bytesPerScanline;
-  imagePNG(const uint8_t* d, const uint8_t* end, int w, int h, int b)
-      : data(d), dataEnd(end), width(w), height(h), bpp(b), bytesPerScanline(b * w) {}
+  imagePNG(const uint8_t* d, int w, int h, int b)
+      : data(d), dataEnd(d ? d + (int64_t)w * h * b : nullptr), width(w), height(h), bpp(b), bytesPerScanline(b * w) {}
   vec3 value(float u, float v, const vec3&) const override {
     if (data == nullptr) return vec3(1.0f, 0, 1.0f);
     COUNT(texelFetches);
@@ -245,8 +245,8 @@ struct imagePNG : texture {  // texture.h:109-153 (image3bpp :54-107 is the bpp=
     if (i >= width) i = width - 1;
     if (j >= height) j = height - 1;
     const uint8_t* pixel = data + (int64_t)j * bytesPerScanline + (int64_t)i * bpp;
-    // bpp==1 reads pixel[1], pixel[2] from the next texels (texture.h:147); past the
-    // end of the buffer the reference reads heap garbage -- defined as 0 here.
+    // bpp==1 reads pixel[1], pixel[2] from the next texels (texture.h:147); past the end of the
+    // image (its own allocation in the reference) that is heap garbage -- defined as 0 here.
     float c[3];
     for (int k = 0; k < 3; k++) c[k] = (pixel + k < dataEnd) ? (float)pixel[k] : 0.0f;
     return vec3(c[0], c[1], c[2]);
@@ -688,7 +688,6 @@ static Scene* buildScene(const SrtSceneDesc* d, uint64_t preDraws) {
   auto s = std::make_unique<Scene>();
   s->texels.assign(d->texels, d->texels + d->numTexelBytes);
   const uint8_t* tbase = s->texels.data();
-  const uint8_t* tend = tbase + s->texels.size();
   s->textures.resize(d->numTextures);
   // two passes: checkers reference other textures
   for (int i = 0; i < d->numTextures; i++) {
@@ -696,7 +695,7 @@ static Scene* buildScene(const SrtSceneDesc* d, uint64_t preDraws) {
     if (t.kind == SRT_TEX_SOLID)
       s->textures[i].reset(new solidColor(vec3(t.color[0], t.color[1], t.color[2])));
     else if (t.kind == SRT_TEX_IMAGE)
-      s->textures[i].reset(new imagePNG(t.width > 0 ? tbase + t.texelOffset : nullptr, tend, t.width, t.height, t.bpp));
+      s->textures[i].reset(new imagePNG(t.width > 0 ? tbase + t.texelOffset : nullptr, t.width, t.height, t.bpp));
   }
   for (int i = 0; i < d->numTextures; i++) {
     const SrtTextureIn& t = d->textures[i];
@@ -932,6 +931,18 @@ void orc_scatter(void* h, const SrtRay* rIn, const SrtHit* hit, uint64_t seed, u
   bool ok = rec.matPtr->scatter(r, rec, att, sc, rng);
   for (int k = 0; k < 3; k++) { out13[k] = att(k); out13[3 + k] = sc.dir(k); out13[6 + k] = sc.o(k); out13[10 + k] = em(k); }
   out13[9] = ok ? 1.0f : 0.0f;
+}
+
+// orc_scatter on n (ray, hit record) pairs, entry i keyed (seed, i, 0) as srtScatterRays keys it.  out13: 13 floats per
+// entry; outFetches (may be null): the loaded-image lookups entry i made.
+void orc_scatter_many(void* h, const SrtRay* rIn, const SrtHit* hit, int64_t n, uint64_t seed, float* out13, uint32_t* outFetches) {
+  for (int64_t i = 0; i < n; ++i) {
+    Counters c;
+    tlsCounters = &c;
+    orc_scatter(h, rIn + i, hit + i, seed, (uint32_t)i, 0u, out13 + 13 * i);
+    tlsCounters = nullptr;
+    if (outFetches) outFetches[i] = (uint32_t)c.texelFetches;
+  }
 }
 
 // main.cpp:200-227.  accum: float[W*H*4] image order (rgb sum, a = spp); rgba: uint8[W*H*4].

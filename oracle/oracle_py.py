@@ -58,6 +58,7 @@ def lib():
         L.orc_bvh_flatten.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.orc_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
         L.orc_scatter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.orc_scatter_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p]
         L.orc_render.argtypes = [C.c_void_p, C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtRenderParams), C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(OrcStats)]
         L.orc_resolve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -120,6 +121,16 @@ class OracleScene:
         out = np.zeros(13, np.float32)
         lib().orc_scatter(self.h, ray.ctypes.data, hit.ctypes.data, seed, pixel, sample, out.ctypes.data)
         return out
+
+    def scatter_many(self, rays, hits, seed):
+        """scatter() on every (ray, hit) pair, entry i keyed (seed, i, 0): (out13 of shape (n, 13), texel fetches per entry)."""
+        rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)
+        hits = np.ascontiguousarray(hits, abi.HIT_DTYPE)
+        assert len(rays) == len(hits)
+        out = np.zeros((len(rays), 13), np.float32)
+        fetches = np.zeros(len(rays), np.uint32)
+        lib().orc_scatter_many(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), seed, out.ctypes.data, fetches.ctypes.data)
+        return out, fetches
 
     def render(self, cam, params, rng_mode=RNG_COUNTER, threads=8, rows=None, want_rgba=True, want_stats=True):
         W, H = params.imageWidth, params.imageHeight

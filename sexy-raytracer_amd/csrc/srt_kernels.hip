@@ -795,16 +795,19 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_trace_kernel(const TraceArgs a)
   }
 }
 
-// material scatter known-answer kernel: one shade() per entry (tests only drive it
-// through srtScatterTest; same device function the render kernel uses)
+// material scatter known-answer kernel: one shade() per entry (tests only drive it through srtScatterRays /
+// srtScatterRaysForm; same device function the render kernels use).  WIDE, COUNT: the instance of shade() -- the
+// step-scheduler kernels run <COUNT, false>, the path-pool kernel and the LDS-tree kernels <COUNT, true>.
 struct ScatterArgs {
   DevScene scene;
   const SrtRay* rays;
   const SrtHit* hits;
-  float* out;  // 13 floats per entry
+  float* out;         // 13 floats per entry
+  uint32_t* fetches;  // shade()'s texel-fetch counter per entry (only a COUNT instance counts), or null
   uint64_t seed;
   int n;
 };
+template <bool WIDE, bool COUNT>
 __global__ void srt_scatter_kernel(const ScatterArgs a) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
@@ -824,7 +827,8 @@ __global__ void srt_scatter_kernel(const ScatterArgs a) {
   Ray out;
   out.d = mk(0, 0, 0);
   uint32_t fetches = 0;
-  bool ok = shade<false>(a.scene, makeRsrc(a.scene.texels, a.scene.texelBytes), r, rec, rng, att, out, em, fetches);
+  bool ok = shade<COUNT, WIDE>(a.scene, makeRsrc(a.scene.texels, a.scene.texelBytes), r, rec, rng, att, out, em, fetches);
+  if (a.fetches) a.fetches[i] = fetches;
   float* o = a.out + 13 * i;
   o[0] = att.x; o[1] = att.y; o[2] = att.z;
   o[3] = out.d.x; o[4] = out.d.y; o[5] = out.d.z;
@@ -881,10 +885,16 @@ int srt_launch_trace(const TraceArgs* a, int traversal, int grid, size_t ldsByte
   return (int)hipGetLastError();
 }
 
-int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint64_t seed, int n,
-                       hipStream_t stream) {
-  ScatterArgs a{*sc, rays, hits, out, seed, n};
-  hipLaunchKernelGGL(srt_scatter_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, a);
+int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint32_t* fetches, uint64_t seed,
+                       int n, int form, hipStream_t stream) {
+  ScatterArgs a{*sc, rays, hits, out, fetches, seed, n};
+  const dim3 grid((n + 63) / 64), block(64);
+  switch (form & 3) {  // bit 0: WIDE, bit 1: COUNT
+    case 0: hipLaunchKernelGGL((srt_scatter_kernel<false, false>), grid, block, 0, stream, a); break;
+    case 1: hipLaunchKernelGGL((srt_scatter_kernel<true, false>), grid, block, 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((srt_scatter_kernel<false, true>), grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL((srt_scatter_kernel<true, true>), grid, block, 0, stream, a); break;
+  }
   return (int)hipGetLastError();
 }
 

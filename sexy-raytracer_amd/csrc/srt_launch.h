@@ -18,8 +18,8 @@ int srt_launch_finalize(const SrtFixedAccum* fix, float4* out, int n, int sample
 int srt_launch_sum_chunks(const float4* buf, float4* out, int n, int chunks, float limit, hipStream_t stream);
 int srt_launch_resolve(const ResolveArgs* a, hipStream_t stream);
 int srt_launch_trace(const TraceArgs* a, int traversal, int grid, size_t ldsBytes, hipStream_t stream);
-int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint64_t seed, int n,
-                       hipStream_t stream);
+int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint32_t* fetches, uint64_t seed,
+                       int n, int form, hipStream_t stream);
 
 // srt_lbvh.hip: the device tree builders (blocking) and the closest-hit traversal's pair records
 int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,

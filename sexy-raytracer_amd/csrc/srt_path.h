@@ -472,8 +472,8 @@ __device__ __forceinline__ void triRecord(const DevScene& sc, int idx, const Ray
 // Texel storage (srt_api.cpp): images of 3 or 4 bytes per pixel are kept as one aligned dword per texel
 // (RGB padded to RGBA8), fetched with ONE buffer_load_dword; 1- and 2-byte images keep the reference's
 // byte rows, because texture.h:147 reads pixel[1] and pixel[2] of a 1-bpp image from the NEXT texels (and
-// past the end of the buffer at the last texel: reads as 0 here and in the oracle -- raw buffer loads
-// return 0 out of range).  DevTexture::offset is a byte offset into the texel buffer (< 2^31).
+// past the end of the image at its last texels: reads as 0 here and in the oracle -- the upload puts two zero
+// bytes behind every such image, srt_scene.cpp).  DevTexture::offset is a byte offset into the texel buffer (< 2^31).
 typedef __amdgpu_buffer_rsrc_t Rsrc;
 template <bool COUNT>
 __device__ __forceinline__ V3 texLeaf(const DevScene& sc, Rsrc rsTexels, int id, float u, float v, uint32_t& fetches) {

@@ -508,26 +508,40 @@ int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, i
   return 0;
 }
 
-// test entry: material::scatter known answers through the kernel's own shade()
+// test entries: material::scatter known answers through the kernels' own shade(), in the instance `form` selects
+// (bit 0 WIDE, bit 1 COUNT: include/srt_hip_test.h)
 
-int srtScatterRays(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, float* out13) {
+int srtScatterRaysForm(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, int32_t form, float* out13,
+                       uint32_t* outFetches) {
   if (!ctx || !rays || !hits || !out13 || n < 1) return 1;
+  if (form < 0 || form > 3) return fail(ctx, "scatter: form %d is not one of 0-3", form);
   if (checkSceneReady(ctx, "scatter")) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
-  for (int i = 0; i < n; ++i)
+  // the kernel indexes the shading records with the hit's material through a plain pointer
+  const int32_t numMaterials = ctx->upload.scene.numMaterials;
+  for (int i = 0; i < n; ++i) {
     if (hits[i].material < 0) return fail(ctx, "scatter: hit %d has no material", i);
-  DeviceBuffer dRays, dHits, dOut;
+    if (hits[i].material >= numMaterials) return fail(ctx, "scatter: hit %d names material %d of %d", i, hits[i].material, numMaterials);
+  }
+  DeviceBuffer dRays, dHits, dOut, dFetches;
   if (dRays.reserve(n * sizeof(SrtRay)) != hipSuccess || dHits.reserve(n * sizeof(SrtHit)) != hipSuccess ||
-      dOut.reserve((size_t)n * 13 * 4) != hipSuccess)
+      dOut.reserve((size_t)n * 13 * 4) != hipSuccess || (outFetches && dFetches.reserve((size_t)n * 4) != hipSuccess))
     return fail(ctx, "scatter: hipMalloc");
   if (hipMemcpy(dRays.get(), rays, n * sizeof(SrtRay), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(dHits.get(), hits, n * sizeof(SrtHit), hipMemcpyHostToDevice) != hipSuccess)
     return fail(ctx, "scatter: copy in");
-  int e = srt_launch_scatter(&ctx->upload.scene, dRays.get<const SrtRay>(), dHits.get<const SrtHit>(), dOut.get<float>(), seed, n, nullptr);
+  int e = srt_launch_scatter(&ctx->upload.scene, dRays.get<const SrtRay>(), dHits.get<const SrtHit>(), dOut.get<float>(),
+                             outFetches ? dFetches.get<uint32_t>() : nullptr, seed, n, form, nullptr);
   if (e) return fail(ctx, "scatter launch failed");
   if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "scatter kernel failed");
   if (hipMemcpy(out13, dOut.get(), (size_t)n * 13 * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "scatter: copy out");
+  if (outFetches && hipMemcpy(outFetches, dFetches.get(), (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ctx, "scatter: copy out");
   return 0;
+}
+
+int srtScatterRays(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, float* out13) {
+  return srtScatterRaysForm(ctx, rays, hits, n, seed, 0, out13, nullptr);
 }
 
 int srtRenderTiles(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr) { SRT_GUARDED(ctx, srtRenderTilesImpl(ctx, p, dAccumTiles, streamPtr)); }

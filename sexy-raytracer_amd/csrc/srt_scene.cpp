@@ -403,7 +403,8 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
   }
   // textures: 3-byte images are padded to one aligned dword per texel, so a lookup is one
   // buffer_load_dword; 1- and 2-byte images keep their byte rows (the 1-bpp quirk of texture.h:147 reads the
-  // neighbouring texels)
+  // neighbouring texels), followed by two zero bytes: that read reaches up to two bytes past the image's last texel,
+  // which are 0 by definition whatever texture comes next in this buffer
   h.textures.resize(d->numTextures);
   for (int i = 0; i < d->numTextures; ++i) {
     const SrtTextureIn& t = d->textures[i];
@@ -428,6 +429,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
       }
     } else {
       h.texels.insert(h.texels.end(), src, src + n * t.bpp);
+      if (t.bpp < 3) h.texels.insert(h.texels.end(), 2, (uint8_t)0);
     }
     if (h.texels.size() > (size_t)0x7fffff00) return "scene: more than 2 GiB of texels";
   }

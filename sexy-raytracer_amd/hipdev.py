@@ -46,7 +46,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
-                "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux"]
+                "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -131,6 +131,7 @@ lib.srtGatherTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _v
 lib.srtRenderImageRanks.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp]
 lib.srtCommDestroy.argtypes = [_vp]
 lib.srtScatterRays.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp]
+lib.srtScatterRaysForm.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, C.c_int32, _vp, _vp]
 lib.srtSetTunable.argtypes = [_vp, C.c_char_p, C.c_int32]
 lib.srtGetTunable.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_int32)]
 lib.srtGetShadeProfile.argtypes = [_vp, _vp]
@@ -626,6 +627,17 @@ class Context:
         out = np.zeros((len(rays), 13), np.float32)
         self._check(lib.srtScatterRays(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), seed, out.ctypes.data))
         return out
+
+    def scatter_test_form(self, rays, hits, seed, form):
+        """scatter_test through the instance of the shading function `form` selects (bit 0 WIDE, bit 1 COUNT;
+        include/srt_hip_test.h): (out13, fetches), fetches = the texel-fetch counter per entry."""
+        rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)
+        hits = np.ascontiguousarray(hits, abi.HIT_DTYPE)
+        out = np.zeros((len(rays), 13), np.float32)
+        fetches = np.zeros(len(rays), np.uint32)
+        self._check(lib.srtScatterRaysForm(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), seed, form, out.ctypes.data,
+                                           fetches.ctypes.data))
+        return out, fetches
 
     def set_tunable(self, name, value):
         """Diagnostic knobs of the work distribution / wave scheduler (include/srt_hip_test.h)."""
