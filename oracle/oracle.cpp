@@ -4,20 +4,23 @@
 // include/) links, loads or calls this file; only tests/, __graft_entry__.smoke()
 // and bench.py's cpu_baseline leg do, as the checker / reported CPU baseline.
 //
-// PARITY PIN STATUS: the reference (swishersnaaake/sexy-raytracer) cannot be
-// built in this image: vec3.h:7, camera.h:6 need Eigen, texture.h:6-7 need stb,
-// model.h:4 needs cgltf, gl.h:9-10 need glad+glfw, all of which are empty,
-// un-pinned git submodules (.gitmodules:1-15) and absent from the container.
-// The reference has no tests, golden vectors or fixtures (CMakeLists.txt:13-14
-// is empty CTest boilerplate).  This restatement is therefore pinned only by
-//   (1) libstdc++'s mt19937/uniform_real_distribution<float> known answers
-//       (the RNG the reference uses, globals.h:30-35),
-//   (2) the BVH statistics of the main.cpp scene recorded in SURVEY.md A.5
-//       (3046 prims -> 4043 nodes, 998 single / 1024 double leaves, depth 11),
-//   (3) region means of the two published renders images/test-*.png
-//       (statistical, tests/test_oracle_published.py).
-// Eigen's reduction order in dot()/Matrix3f*vec (a0b0 + (a1b1 + a2b2)) is taken
-// from Eigen's unrolled redux and is "parity unpinned" (no Eigen checkout).
+// PARITY PIN STATUS: the reference (swishersnaaake/sexy-raytracer) as shipped cannot be built (Eigen, stb, cgltf, glad
+// and glfw are empty, un-pinned git submodules, .gitmodules:1-15) and has no tests or golden vectors, but its hot-path
+// headers compile unmodified against the stand-ins of oracle/refshim/.  oracle/ref_harness.cpp is that program, and
+// tests/test_reference_pin.py holds this file against it ON BITS, with no tolerance:
+//   (a) the generator: 200 000 draws, randomVec3f's draw order             test_generator
+//   (b) the tree: every node's children and box bits, depth, draws         test_tree_build
+//   (c) hit records: every field and the four counters, fixed + edge rays  test_hit_records
+//   (d) checker / imagePNG / solidColor through diffuseLight::emitted      test_textures_and_emitted
+//   (e) scatter of every material on one stream, and the next draw         test_scatter
+//   (f) whole frames: sums, RGBA8, the generator's position                test_whole_frames, test_cameras
+// and against the harness's recorded results tests/golden/ref_<scene>.npz, which every machine has
+// (test_oracle_reproduces_recorded_reference).  The statistical pins that came first stay (test_oracle_anchors.py:
+// libstdc++ known answers, BVH statistics of SURVEY.md A.5, the two published PNGs).
+// What stays ASSUMED: Eigen's reduction order in dot() / Matrix3f * vec (a0b0 + (a1b1 + a2b2), Eigen's unrolled redux;
+// no Eigen checkout exists; the stand-in and this file share the assumption, written once in refshim/Eigen/Core), and
+// stb's PNG decode (the harness reads PIL's bytes).  Where the reference's behaviour is undefined (NaN cast to int, the
+// 1-bpp overrun, uninitialised pbr fields) this file defines it; those inputs are left out of the pin by name.
 //
 // Every function cites the reference file:line it restates.  Arithmetic is
 // IEEE binary32 with no FMA contraction (build with -ffp-contract=off, no
@@ -913,14 +916,9 @@ void orc_trace(void* h, const SrtRay* rays, int64_t n, SrtHit* hits, int travers
   }
 }
 
-// material scatter known-answer entry: one scatter() call on a given hit record with the
-// counter RNG keyed (seed, pixel, sample).  out: attenuation[3], dir[3], origin[3], ok, emitted[3]
-void orc_scatter(void* h, const SrtRay* rIn, const SrtHit* hit, uint64_t seed, uint32_t pixel, uint32_t sample,
-                 float* out13) {
-  Scene* s = static_cast<Scene*>(h);
-  Rng rng;
-  rng.mode = RNG_COUNTER;
-  rng.key(seed, pixel, sample);
+// one scatter() call (and emitted(), evaluated first as main.cpp:44-46 does) on a given hit record.
+// out: attenuation[3], dir[3], origin[3], ok, emitted[3]; outTime (may be null): the scattered ray's time
+static void scatterOne(Scene* s, const SrtRay* rIn, const SrtHit* hit, Rng& rng, float* out13, float* outTime) {
   hitRecord rec;
   rec.p = v3(hit->p); rec.normal = v3(hit->normal); rec.tangent = v3(hit->tangent); rec.bitangent = v3(hit->bitangent);
   rec.uv[0] = hit->uv[0]; rec.uv[1] = hit->uv[1]; rec.t = hit->t; rec.frontFace = hit->frontFace != 0;
@@ -931,6 +929,32 @@ void orc_scatter(void* h, const SrtRay* rIn, const SrtHit* hit, uint64_t seed, u
   bool ok = rec.matPtr->scatter(r, rec, att, sc, rng);
   for (int k = 0; k < 3; k++) { out13[k] = att(k); out13[3 + k] = sc.dir(k); out13[6 + k] = sc.o(k); out13[10 + k] = em(k); }
   out13[9] = ok ? 1.0f : 0.0f;
+  if (outTime) *outTime = sc.time;
+}
+
+// material scatter known-answer entry: one scatter() call on a given hit record with the
+// counter RNG keyed (seed, pixel, sample).  out: attenuation[3], dir[3], origin[3], ok, emitted[3]
+void orc_scatter(void* h, const SrtRay* rIn, const SrtHit* hit, uint64_t seed, uint32_t pixel, uint32_t sample,
+                 float* out13) {
+  Rng rng;
+  rng.mode = RNG_COUNTER;
+  rng.key(seed, pixel, sample);
+  scatterOne(static_cast<Scene*>(h), rIn, hit, rng, out13, nullptr);
+}
+
+// The same in MT mode: the n pairs in order on ONE stream, a fresh default-seeded generator (globals.h:30-35) after
+// preDraws draws -- what a process of the reference does that scatters these records one after the other (the scene
+// handle's own generator, which the tree build advanced, is not used).  outTime: the scattered ray's time per pair;
+// nextDraw: the randomFloat() after the last pair, which shows how many draws the pairs consumed.
+void orc_scatter_many_mt(void* h, const SrtRay* rIn, const SrtHit* hit, int64_t n, uint64_t preDraws, float* out13,
+                         float* outTime, float* nextDraw) {
+  std::mt19937 mt;
+  mt.discard(preDraws);
+  Rng rng;
+  rng.mode = RNG_MT;
+  rng.mt = &mt;
+  for (int64_t i = 0; i < n; ++i) scatterOne(static_cast<Scene*>(h), rIn + i, hit + i, rng, out13 + 13 * i, outTime + i);
+  *nextDraw = rng.randomFloat();
 }
 
 // orc_scatter on n (ray, hit record) pairs, entry i keyed (seed, i, 0) as srtScatterRays keys it.  out13: 13 floats per

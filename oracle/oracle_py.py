@@ -59,6 +59,7 @@ def lib():
         L.orc_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
         L.orc_scatter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
         L.orc_scatter_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.orc_scatter_many_mt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_render.argtypes = [C.c_void_p, C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtRenderParams), C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(OrcStats)]
         L.orc_resolve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -131,6 +132,19 @@ class OracleScene:
         fetches = np.zeros(len(rays), np.uint32)
         lib().orc_scatter_many(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), seed, out.ctypes.data, fetches.ctypes.data)
         return out, fetches
+
+    def scatter_many_mt(self, rays, hits, pre_draws=0):
+        """scatter() on every (ray, hit) pair in order on one MT stream, a fresh default-seeded generator after pre_draws
+        draws: (out13 of shape (n, 13), the scattered rays' times, the next draw after the last pair)."""
+        rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)
+        hits = np.ascontiguousarray(hits, abi.HIT_DTYPE)
+        assert len(rays) == len(hits)
+        out = np.zeros((len(rays), 13), np.float32)
+        times = np.zeros(len(rays), np.float32)
+        nxt = np.zeros(1, np.float32)
+        lib().orc_scatter_many_mt(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), int(pre_draws), out.ctypes.data,
+                                  times.ctypes.data, nxt.ctypes.data)
+        return out, times, nxt[0]
 
     def render(self, cam, params, rng_mode=RNG_COUNTER, threads=8, rows=None, want_rgba=True, want_stats=True):
         W, H = params.imageWidth, params.imageHeight

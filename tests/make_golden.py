@@ -13,6 +13,10 @@
   bvh_topology.json       pre-order node arrays of the config scenes (count, depth, sha1, first nodes).
   render_<scene>.npz      tiny full renders by the oracle in COUNTER and MT mode
                           (float accumulators + RGBA8).
+  ref_<scene>.npz         RECORDED RESULTS OF THE REFERENCE ITSELF (oracle/ref_harness.cpp: its own headers as g++
+                          compiles them): the edge set of tests/ref_cases.py and every second ray of trace_<scene>.npz
+                          -> hit records and counters, the closest hit (over the tree and by brute force), and the pre-order tree; also for the edge scene (ref_edges.npz).
+                          accum_mt / rgba_mt of render_<scene>.npz are asserted to be what the harness renders.
   reference_models.tar.xz the model files of the reference's data/ directory that test_host_cpp.py loads, packed
                           small (pack_reference_models: data: URIs decoded, the assets/ images they embed cut out,
                           sha256 of every file as shipped); the textures they name are not included.
@@ -135,6 +139,42 @@ def pack_reference_models(data_dir):
             t.addfile(info, io.BytesIO(blobs[name]))
 
 
+def reference_fixtures():
+    """ref_<scene>.npz from the harness (needs oracle/_ref/ref_harness, i.e. the reference's sources at build time)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_cases
+    import ref_harness as H
+    assert H.available(), "oracle/_ref/ref_harness is not built"
+    for name in ("spheres", "iron", "masterchief", "edges"):
+        sb = ref_cases.edge_scene(abi) if name == "edges" else srt.scenes.SCENES[name]()
+        gltf = name == "masterchief"  # its triangles go through model::create(...)->init() (model.h:301-460)
+        rays, names = ref_cases.edge_rays(abi, sb)
+        if name != "edges":  # thinned to keep the file below the largest fixture; the edge set stays whole
+            rays = np.concatenate([rays, np.load(os.path.join(GOLD, "trace_%s.npz" % name))["rays"][::2]])
+        hits = H.trace(sb, rays, gltf)
+        near = H.closest(sb, rays, gltf)
+        items, position = H.tree(sb, gltf)
+        (nodes, depth), = items
+        np.savez_compressed(os.path.join(GOLD, "ref_%s.npz" % name), rays=rays, names=np.array(names), hits=hits, nodes=nodes,
+                            depth=depth, build_draws=position, closest_prim=near["prim"], closest_t=near["t"],
+                            closest_ties=near["ties"], brute_prim=near["brute_prim"], brute_t=near["brute_t"])
+        print("ref_%s.npz: %d rays (%d edge), %d hits, %d nodes, %d bytes" % (
+            name, len(rays), len(names), int((hits["prim"] >= 0).sum()), len(nodes), os.path.getsize(os.path.join(GOLD, "ref_%s.npz" % name))))
+
+
+def assert_harness_renders(name, sb, p, acc_m, rgba_m):
+    """The MT-mode golden frame is the reference's own: the harness's pixel loop gives the same sums and bytes."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_harness as H
+    if not H.available():
+        return
+    acc, rgba, _ = H.render(sb, abi.default_camera_params(), p, gltf=(name == "masterchief"))
+    nan = np.isnan(acc_m)
+    assert np.array_equal(np.isnan(acc), nan) and np.array_equal(acc.view(np.uint32)[~nan], acc_m.view(np.uint32)[~nan]), name
+    defined = ~nan[..., :3].any(axis=-1)
+    assert np.array_equal(rgba[defined], rgba_m[defined]), name
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     from PIL import Image
@@ -190,6 +230,7 @@ def main():
         acc_c, rgba_c, st_c = osc.render(cam, p, O.RNG_COUNTER, threads=4)
         osc2 = O.OracleScene(sb)  # fresh generator: BVH build then render, like a new process
         acc_m, rgba_m, st_m = osc2.render(cam, p, O.RNG_MT, threads=1)
+        assert_harness_renders(name, sb, p, acc_m, rgba_m)
         np.savez_compressed(os.path.join(GOLD, "render_%s.npz" % name), width=W, height=H, spp=spp, max_bounce=mb,
                             seed=7, accum_counter=acc_c, rgba_counter=rgba_c, accum_mt=acc_m, rgba_mt=rgba_m,
                             stats_counter=json.dumps(st_c), stats_mt=json.dumps(st_m))
@@ -204,5 +245,12 @@ def main():
               "faithful!=closest", int((hits["prim"] != closest["prim"]).sum() + ((hits["prim"] == closest["prim"]) & (hits["t"] != closest["t"])).sum()))
 
 
+    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ref_harness")):
+        reference_fixtures()
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref"]:  # only the recorded reference results
+        reference_fixtures()
+    else:
+        main()
