@@ -40,6 +40,14 @@ int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAo
 int srtScatterRaysForm(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, int32_t form, float* out13,
                        uint32_t* outFetches);
 
+/* The exact chunk sum on caller-made partial sums.  hChunks: chunks x n float4, slot [c][i] (rgb partial sums, w the slot's
+ * sample count).  path 0: srt_sum_chunks_kernel over the uploaded slots.  path 1: the atomic path -- one thread per slot
+ * calls commitFixed on a zeroed SrtFixedAccum[n], then srt_finalize_kernel(samples).  The limit is the one a render of
+ * `chunks` chunks uses.  hOut4: n float4 (w: path 0 the float sum of the slot counts in slot order, path 1 (float)samples).
+ * Host pointers; needs no scene.  Refuses, with an error text, n outside [1, 2^20], chunks < 1 or above the largest count
+ * srtPlanSppChunks allows any image (30 812), a path other than 0 or 1, and null pointers. */
+int srtTestChunkSum(SrtContext* ctx, const float* hChunks, int32_t n, int32_t chunks, int32_t path, int32_t samples, float* hOut4);
+
 /* Sub-step profile of the most recent countStats launch of the step-scheduler kernel (shader clocks summed over waves,
  * diagnostics only; zero after one of the path-pool kernel, which a counting launch runs where the production launch would):
  * out10 = { hit step: hit record, textures, direction draw, BRDF + bookkeeping; restart step;

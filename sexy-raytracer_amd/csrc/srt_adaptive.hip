@@ -103,14 +103,7 @@ __global__ void srt_adaptive_resolve_kernel(const float4* accum, uchar4* rgba, i
   if (idx >= n) return;
   const float4 v = accum[idx];
   const float scale = 1.0f / v.w;
-  const float c[3] = {v.x, v.y, v.z};
-  uint8_t o[3];
-  for (int k = 0; k < 3; ++k) {
-    const float g = sqrtf(c[k] * scale);
-    const float q = 256.0f * (g < 0.0f ? 0.0f : (g > 0.999f ? 0.999f : g));  // clampf (srt_path.h)
-    o[k] = (q == q) ? (uint8_t)q : (uint8_t)0;
-  }
-  rgba[idx] = make_uchar4(o[0], o[1], o[2], 255);
+  rgba[idx] = make_uchar4(srtQuantise8(v.x * scale), srtQuantise8(v.y * scale), srtQuantise8(v.z * scale), 255);
 }
 
 }  // namespace

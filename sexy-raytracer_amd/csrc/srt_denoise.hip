@@ -265,14 +265,8 @@ __global__ __launch_bounds__(DN_THREADS) void srt_denoise_level(const DenoiseArg
   }
   if (a.out) a.out[i] = make_float4(m[0], m[1], m[2], a.beauty[i].w);
   if (a.rgba) {
-    uint8_t o[4];
-    for (int k = 0; k < 3; ++k) {  // srt_resolve_kernel's quantisation of a mean
-      const float g = sqrtf(m[k]);
-      const float qv = 256.0f * fminf(fmaxf(g, 0.0f), 0.999f);
-      o[k] = (qv == qv) ? (uint8_t)qv : (uint8_t)0;
-    }
-    o[3] = 255;
-    reinterpret_cast<uchar4*>(a.rgba)[i] = make_uchar4(o[0], o[1], o[2], o[3]);
+    // srt_resolve_kernel's quantisation of a mean
+    reinterpret_cast<uchar4*>(a.rgba)[i] = make_uchar4(srtQuantise8(m[0]), srtQuantise8(m[1]), srtQuantise8(m[2]), 255);
   }
 }
 

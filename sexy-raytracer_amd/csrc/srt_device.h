@@ -299,4 +299,19 @@ SRT_HD inline int srtOrderFromTile(int tx, int ty, int tilesX, int tilesY, int B
   return by * B * tilesX + bx * B * bh + iy * bw + (ix + iy) % bw;
 }
 
+// ---- the 8-bit quantisation of one channel's mean (color.h:25-41), the device's one copy: srt_resolve_kernel,
+// srt_adaptive_resolve_kernel and the last denoise level call it, each with its own scale (1 / spp, 1 / w, none).
+// sqrtf is the correctly rounded square root here (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt; the
+// intrinsic __fsqrt_rn is NOT: without OCML_BASIC_ROUNDED_OPERATIONS it is the native approximation).  The clamp is
+// globals.h:17-24: a NaN passes both compares and the cast's undefined result is pinned to 0 (what x86 yields); a
+// negative mean has a NaN root, -0.0 has the root -0.0 and gives 0; +inf clamps to 0.999 -> 255.
+// tests/test_gpu_quantise.py pins every level boundary byte for byte against an integer square root.
+#if defined(__HIPCC__)
+__device__ __forceinline__ uint8_t srtQuantise8(float mean) {
+  const float g = sqrtf(mean);
+  const float q = 256.0f * (g < 0.0f ? 0.0f : (g > 0.999f ? 0.999f : g));
+  return (q == q) ? (uint8_t)q : (uint8_t)0;
+}
+#endif
+
 #endif

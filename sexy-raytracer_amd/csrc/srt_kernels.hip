@@ -723,6 +723,15 @@ __global__ void srt_sum_chunks_kernel(const float4* buf, float4* out, int n, int
   out[i] = make_float4(fromFixed36(sum[0], flags, 0), fromFixed36(sum[1], flags, 1), fromFixed36(sum[2], flags, 2), count);
 }
 
+// srtTestChunkSum, atomic path: the commit an item of a render makes, on caller-made slots buf[c][i] -- one thread per slot,
+// so the atomics of a pixel arrive in whatever order the waves run
+__global__ void srt_test_commit_kernel(const float4* buf, SrtFixedAccum* fix, int n, int chunks, float limit) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)n * chunks) return;
+  const float4 v = buf[t];
+  commitFixed(fix + (int)(t % n), mk(v.x, v.y, v.z), limit);
+}
+
 // =================================================================== resolve (color.h:25-41)
 __global__ void srt_resolve_kernel(const ResolveArgs a) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -735,15 +744,7 @@ __global__ void srt_resolve_kernel(const ResolveArgs a) {
   if (a.accumImage) a.accumImage[idx] = v;
   if (a.rgba) {
     float scale = 1.0f / (float)a.spp;
-    float c[3] = {v.x, v.y, v.z};
-    uint8_t o[4];
-    for (int k = 0; k < 3; ++k) {
-      float g = sqrtf(c[k] * scale);
-      float q = 256.0f * clampf(g, 0.0f, 0.999f);
-      o[k] = (q == q) ? (uint8_t)q : (uint8_t)0;  // NaN -> 0 (what the reference's UB cast yields on x86)
-    }
-    o[3] = 255;
-    reinterpret_cast<uchar4*>(a.rgba)[idx] = make_uchar4(o[0], o[1], o[2], o[3]);
+    reinterpret_cast<uchar4*>(a.rgba)[idx] = make_uchar4(srtQuantise8(v.x * scale), srtQuantise8(v.y * scale), srtQuantise8(v.z * scale), 255);
   }
 }
 
@@ -868,6 +869,12 @@ int srt_launch_finalize(const SrtFixedAccum* fix, float4* out, int n, int sample
 
 int srt_launch_sum_chunks(const float4* buf, float4* out, int n, int chunks, float limit, hipStream_t stream) {
   hipLaunchKernelGGL(srt_sum_chunks_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, buf, out, n, chunks, limit);
+  return (int)hipGetLastError();
+}
+
+int srt_launch_test_commit(const float4* buf, SrtFixedAccum* fix, int n, int chunks, float limit, hipStream_t stream) {
+  const int64_t slots = (int64_t)n * chunks;
+  hipLaunchKernelGGL(srt_test_commit_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, buf, fix, n, chunks, limit);
   return (int)hipGetLastError();
 }
 

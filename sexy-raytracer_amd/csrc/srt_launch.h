@@ -16,6 +16,7 @@ RenderKernel srt_render_wf_kernel_for(const RenderPlan* p);
 // srt_kernels.hip
 int srt_launch_finalize(const SrtFixedAccum* fix, float4* out, int n, int samples, hipStream_t stream);
 int srt_launch_sum_chunks(const float4* buf, float4* out, int n, int chunks, float limit, hipStream_t stream);
+int srt_launch_test_commit(const float4* buf, SrtFixedAccum* fix, int n, int chunks, float limit, hipStream_t stream);
 int srt_launch_resolve(const ResolveArgs* a, hipStream_t stream);
 int srt_launch_trace(const TraceArgs* a, int traversal, int grid, size_t ldsBytes, hipStream_t stream);
 int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint32_t* fetches, uint64_t seed,

@@ -817,7 +817,11 @@ __device__ __forceinline__ float fromFixed36(long long q, uint32_t flags, int k)
   if (nan || (pinf && ninf)) return __builtin_nanf("");
   if (pinf) return SRT_INF;
   if (ninf) return -SRT_INF;
-  return (float)((double)q * 0x1p-36);
+  // ONE rounding: the integer-to-float conversion rounds to nearest, ties to even, and the scaling by 2^-36 is exact (a
+  // nonzero |q| >= 1 stays a normal float).  Through double -- (float)((double)q * 0x1p-36) -- a sum of 2^17 or more
+  // (q >= 2^53) was rounded twice: 65536 + 2^-7, 65536 and 2^-36 gave 131072 where the sum rounded once is 131072.015625.
+  // A sum of zero is +0.0, also where every partial sum was -0.0.  (tests/test_gpu_chunk_sum.py)
+  return (float)q * 0x1p-36f;
 }
 // srtRenderTilesMoments: a sample's luminance, left to right in float (the library builds with -ffp-contract=off)
 __device__ __forceinline__ float sampleLum(V3 L) { return 0.2126f * L.x + 0.7152f * L.y + 0.0722f * L.z; }

@@ -18,6 +18,14 @@ size_t ldsBytesFor(const SrtContext* ctx, int maxBounce, int stackDepth) {
   return (size_t)(stackDepth + 2 + 3 * maxBounce + 3) * SRT_BLOCK * sizeof(int32_t) + 4 * sizeof(int32_t);
 }
 
+// RenderArgs::fixLimit of a render of `chunks` chunks (srt_path.h toFixed36): exact chunk sums cannot wrap, partial sums of
+// 2^26 / (chunk count rounded up to a power of two) or more count as infinite.  The render and srtTestChunkSum both ask here.
+float chunkFixLimit(int32_t chunks) {
+  int pow2 = 1;
+  while (pow2 < chunks) pow2 *= 2;
+  return 0x1p26f / (float)pow2;
+}
+
 }  // namespace
 
 extern "C" {
@@ -182,12 +190,7 @@ int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTi
     if (planned < 1) return fail(ctx, "render: sppChunks %d x %d tiles exceeds 2^31 work items", p->sppChunks, a.numTiles);
     a.sppChunks = planned;
   }
-  {
-    // exact chunk sums cannot wrap: partial sums of 2^26 / (chunk count rounded up to a power of two) or more count as infinite
-    int pow2 = 1;
-    while (pow2 < a.sppChunks) pow2 *= 2;
-    a.fixLimit = 0x1p26f / (float)pow2;
-  }
+  a.fixLimit = chunkFixLimit(a.sppChunks);
   a.numWork = a.numLocalTiles * a.sppChunks * SRT_TILE_PIXELS;
   a.sppBase = a.spp / a.sppChunks;
   a.sppRem = a.spp % a.sppChunks;
@@ -542,6 +545,39 @@ int srtScatterRaysForm(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, 
 
 int srtScatterRays(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, float* out13) {
   return srtScatterRaysForm(ctx, rays, hits, n, seed, 0, out13, nullptr);
+}
+
+// test entry: the exact chunk sum on caller-made partial sums, through the kernels and the limit a render uses
+// (include/srt_hip_test.h).  Needs no scene.
+int srtTestChunkSum(SrtContext* ctx, const float* hChunks, int32_t n, int32_t chunks, int32_t path, int32_t samples, float* hOut4) {
+  if (!ctx) return 1;
+  if (!hChunks) return fail(ctx, "chunk sum: null slots");
+  if (!hOut4) return fail(ctx, "chunk sum: null output");
+  if (n <= 0 || n > (1 << 20)) return fail(ctx, "chunk sum: n = %d is not in [1, 2^20]", n);
+  if (chunks < 1) return fail(ctx, "chunk sum: chunks = %d, must be at least 1", chunks);
+  // the largest count the planner lets any render use (the smallest image's; srtPlanSppChunks)
+  if (srtPlanSppChunks(1, 1, chunks, chunks) < 1) return fail(ctx, "chunk sum: %d chunks are more than any render's plan allows", chunks);
+  if (path != 0 && path != 1) return fail(ctx, "chunk sum: path %d is neither 0 (chunk slots) nor 1 (atomics)", path);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const size_t slotBytes = (size_t)n * chunks * sizeof(float4), outBytes = (size_t)n * sizeof(float4);
+  DeviceBuffer dSlots, dOut, dFix;
+  if (dSlots.reserve(slotBytes) != hipSuccess || dOut.reserve(outBytes) != hipSuccess ||
+      (path == 1 && dFix.reserve((size_t)n * sizeof(SrtFixedAccum)) != hipSuccess))
+    return fail(ctx, "chunk sum: hipMalloc");
+  if (hipMemcpy(dSlots.get(), hChunks, slotBytes, hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, "chunk sum: copy in");
+  const float limit = chunkFixLimit(chunks);
+  int e;
+  if (path == 0) {
+    e = srt_launch_sum_chunks(dSlots.get<const float4>(), dOut.get<float4>(), n, chunks, limit, nullptr);
+  } else {
+    if (hipMemset(dFix.get(), 0, (size_t)n * sizeof(SrtFixedAccum)) != hipSuccess) return fail(ctx, "chunk sum: memset");
+    e = srt_launch_test_commit(dSlots.get<const float4>(), dFix.get<SrtFixedAccum>(), n, chunks, limit, nullptr);
+    if (!e) e = srt_launch_finalize(dFix.get<const SrtFixedAccum>(), dOut.get<float4>(), n, samples, nullptr);
+  }
+  if (e) return fail(ctx, "chunk sum launch failed: %s", hipGetErrorString((hipError_t)e));
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "chunk sum kernel failed");
+  if (hipMemcpy(hOut4, dOut.get(), outBytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "chunk sum: copy out");
+  return 0;
 }
 
 int srtRenderTiles(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr) { SRT_GUARDED(ctx, srtRenderTilesImpl(ctx, p, dAccumTiles, streamPtr)); }

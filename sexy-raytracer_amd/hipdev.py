@@ -46,7 +46,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
-                "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux"]
+                "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -132,6 +132,7 @@ lib.srtRenderImageRanks.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _v
 lib.srtCommDestroy.argtypes = [_vp]
 lib.srtScatterRays.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp]
 lib.srtScatterRaysForm.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, C.c_int32, _vp, _vp]
+lib.srtTestChunkSum.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
 lib.srtSetTunable.argtypes = [_vp, C.c_char_p, C.c_int32]
 lib.srtGetTunable.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_int32)]
 lib.srtGetShadeProfile.argtypes = [_vp, _vp]
@@ -638,6 +639,17 @@ class Context:
         self._check(lib.srtScatterRaysForm(self.h, rays.ctypes.data, hits.ctypes.data, len(rays), seed, form, out.ctypes.data,
                                            fetches.ctypes.data))
         return out, fetches
+
+    def chunk_sum_test(self, slots, path, samples=0):
+        """srtTestChunkSum (include/srt_hip_test.h): the exact chunk sum of caller-made partial sums.  slots: (chunks, n, 4)
+        float32, rgb partial sums and the slot's sample count; path 0 the chunk-slot kernel, 1 the atomic path with one
+        commit per slot.  Returns (n, 4) float32."""
+        slots = np.ascontiguousarray(slots, np.float32)
+        if slots.ndim != 3 or slots.shape[2] != 4:
+            raise ValueError("slots must be (chunks, n, 4)")
+        out = np.zeros((slots.shape[1], 4), np.float32)
+        self._check(lib.srtTestChunkSum(self.h, slots.ctypes.data, slots.shape[1], slots.shape[0], path, samples, out.ctypes.data))
+        return out
 
     def set_tunable(self, name, value):
         """Diagnostic knobs of the work distribution / wave scheduler (include/srt_hip_test.h)."""
