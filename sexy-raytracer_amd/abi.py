@@ -300,7 +300,7 @@ class SceneBuilder:
         texcoords = np.asarray(texcoords, np.float32)
         indices = np.asarray(indices).reshape(-1, 3)
         n = len(indices)
-        arr = np.zeros(n, dtype=np.dtype([("p", "<f4", (3, 3)), ("uv", "<f4", (3, 2)), ("material", "<i4")]))
+        arr = np.zeros(n, dtype=TRIANGLE_DTYPE)
         arr["p"] = positions[indices]
         arr["uv"] = texcoords[indices]
         arr["material"] = material
@@ -334,7 +334,7 @@ class SceneBuilder:
             return a
 
         tri_np = (np.concatenate(self.triangles) if self.triangles
-                  else np.zeros(0, dtype=np.dtype([("p", "<f4", (3, 3)), ("uv", "<f4", (3, 2)), ("material", "<i4")])))
+                  else np.zeros(0, dtype=TRIANGLE_DTYPE))
         tri_np = np.ascontiguousarray(tri_np)
         assert tri_np.dtype.itemsize == 64
         sph = arr(SrtSphereIn, self.spheres)

@@ -18,7 +18,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "srt_device.h"
-#include "srt_prim_box.h"
+#include "srt_records.h"
 #include "srt_launch.h"
 
 namespace {

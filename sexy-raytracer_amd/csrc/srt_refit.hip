@@ -1,29 +1,16 @@
 // srt_refit.hip -- geometry updates in place (include/srt_hip.h srtUpdateTriangles / srtUpdateSpheres / srtRefitScene):
 // the primitive records rewritten from caller data, every node box refitted bottom-up over the uploaded topology, and
 // what is derived from boxes refreshed.  Topology (the reference words of every record, nodeAxis, the thread links) is
-// never written.
-//
-// The record kernels restate flattenScene's arithmetic (srt_scene.cpp) operation for operation; this file is built with
-// -ffp-contract=off and IEEE division / sqrt like the rest, so a record carries the bits an upload of the same data gives.
+// never written.  Records, boxes, unions and the certificate are srt_records.h's, the ones flattenScene (srt_scene.cpp)
+// calls, so a record or box carries the bits an upload of the same data gives.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "srt_device.h"
-#include "srt_prim_box.h"
+#include "srt_records.h"
 #include "srt_launch.h"
 
 namespace {
-
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 unit(V3 v) {  // vec3.h:54-60
-  const float len = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
-  if (len != 0) return V3{v.x / len, v.y / len, v.z / len};
-  return v;
-}
 
 // One lane per updated triangle: SrtTriangleIn (64 B, four 16-byte loads) -> triTest and triShade at the triangle's DEVICE
 // index.  The material word (index, type and flag bits) stays.  devIndex: scene triangle index -> device index, null =
@@ -32,44 +19,24 @@ __global__ void refitTriRecords(const float4* in, int first, int count, const in
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const float4 a = in[4 * (size_t)i], b = in[4 * (size_t)i + 1], c = in[4 * (size_t)i + 2], d = in[4 * (size_t)i + 3];
-  const V3 v0{a.x, a.y, a.z}, v1{a.w, b.x, b.y}, v2{b.z, b.w, c.x};
-  const float uv[3][2] = {{c.y, c.z}, {c.w, d.x}, {d.y, d.z}};
+  const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x}, uv[6] = {c.y, c.z, c.w, d.x, d.y, d.z};
   const size_t j = (size_t)(devIndex ? devIndex[first + i] : first + i);
-  const V3 n = cross(sub(v1, v0), sub(v2, v0));  // getNormal, model.h:276-283
-  triTest[3 * j + 0] = make_float4(v0.x, v0.y, v0.z, n.x);
-  triTest[3 * j + 1] = make_float4(v1.x, v1.y, v1.z, n.y);
-  triTest[3 * j + 2] = make_float4(v2.x, v2.y, v2.z, n.z);
-  const V3 nu = unit(n);  // model.h:172
-  // calcTangentBasis, model.h:214-235
-  const V3 e0 = sub(v1, v0), e1 = sub(v2, v0);
-  const float du0 = uv[1][0] - uv[0][0], dv0 = uv[1][1] - uv[0][1];
-  const float du1 = uv[2][0] - uv[0][0], dv1 = uv[2][1] - uv[0][1];
-  float f = (du0 * dv1 - du1 * dv0);
-  if (f == 0) f += 1.1920928955078125e-7f;  // std::numeric_limits<float>::epsilon()
-  f = 1.0f / f;
-  const V3 tg = unit(V3{f * (dv1 * e0.x - dv0 * e1.x), f * (dv1 * e0.y - dv0 * e1.y), f * (dv1 * e0.z - dv0 * e1.z)});
-  const V3 bt = unit(V3{f * (-du1 * e0.x + du0 * e1.x), f * (-du1 * e0.y + du0 * e1.y), f * (-du1 * e0.z + du0 * e1.z)});
-  const float material = triShade[4 * j + 3].w;
-  triShade[4 * j + 0] = make_float4(nu.x, nu.y, nu.z, uv[0][0]);
-  triShade[4 * j + 1] = make_float4(tg.x, tg.y, tg.z, uv[0][1]);
-  triShade[4 * j + 2] = make_float4(bt.x, bt.y, bt.z, uv[1][0]);
-  triShade[4 * j + 3] = make_float4(uv[1][1], uv[2][0], uv[2][1], material);
+  float4 test[3], shade[4];
+  triangleRecords(p, uv, triShade[4 * j + 3].w, test, shade);
+  for (int k = 0; k < 3; ++k) triTest[3 * j + k] = test[k];
+  for (int k = 0; k < 4; ++k) triShade[4 * j + k] = shade[k];
 }
 
 // One lane per updated sphere: SrtSphereIn (ten words) -> the sphere's three records.  The material word keeps everything
-// but the "moving" bit, which follows center0 != center1.
+// but the "moving" bit.
 __global__ void refitSphereRecords(const float* in, int first, int count, float4* spheres) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const float* s = in + 10 * (size_t)i;
-  const float c0[3] = {s[0], s[1], s[2]}, c1[3] = {s[3], s[4], s[5]};
-  const float time0 = s[6], time1 = s[7], radius = s[8];
   const size_t j = (size_t)(first + i);
-  const bool moving = c0[0] != c1[0] || c0[1] != c1[1] || c0[2] != c1[2];
-  const int32_t bits = (__float_as_int(spheres[3 * j + 1].w) & ~(1 << 30)) | (moving ? (1 << 30) : 0);
-  spheres[3 * j + 0] = make_float4(c0[0], c0[1], c0[2], radius);
-  spheres[3 * j + 1] = make_float4(c1[0], c1[1], c1[2], __int_as_float(bits));
-  spheres[3 * j + 2] = make_float4(time0, time1, 0.0f, 0.0f);
+  float4 rec[3];
+  sphereRecords(vec3(s), vec3(s + 3), s[6], s[7], s[8], __float_as_int(spheres[3 * j + 1].w), rec);
+  for (int k = 0; k < 3; ++k) spheres[3 * j + k] = rec[k];
 }
 
 // ---------------------------------------------------------------------------------------------------- refit
@@ -88,12 +55,6 @@ __global__ void refitLinks(const float4* nodes, int numNodes, int32_t* up) {
   const int32_t word = i | need << REFIT_NEED_SHIFT;
   if (isNode(l)) up[SRT_NODE_INDEX(l)] = word;
   if (isNode(r)) up[SRT_NODE_INDEX(r)] = word;
-}
-
-// fastDiv's operand certificate (srt_scene.cpp fastDivOperand): 0 or 2^-77 <= |c| <= 2^30
-__device__ __forceinline__ bool fastDivOperand(float c) {
-  const float ac = fabsf(c);
-  return c == 0.0f || (ac >= 0x1p-77f && ac <= 0x1p30f);
 }
 
 struct RefitArgs {
@@ -125,32 +86,26 @@ __global__ void refitNodes(RefitArgs a) {
     const float4 n0 = nodes[2 * (size_t)node], n1 = nodes[2 * (size_t)node + 1];
     const int32_t link = a.up[node];  // read before the stores: nothing but the fence stands between them and the arrival
     const int32_t refs[2] = {__float_as_int(n0.w), __float_as_int(n1.w)};
-    const float inf = __int_as_float(0x7f800000);
-    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    Box box = {};
     bool any = false;
     for (int c = 0; c < 2; ++c) {
       const int32_t ref = refs[c];
       if (ref == SRT_REF_DONE || (c == 1 && ref == refs[0])) continue;  // an unused slot; a single-object leaf
-      float cmn[3], cmx[3];
+      Box child;
       if (isNode(ref)) {
         const size_t j = (size_t)SRT_NODE_INDEX(ref);
         const float4 c0 = nodes[2 * j], c1 = nodes[2 * j + 1];
-        cmn[0] = c0.x; cmn[1] = c0.y; cmn[2] = c0.z;
-        cmx[0] = c1.x; cmx[1] = c1.y; cmx[2] = c1.z;
+        child = Box{{c0.x, c0.y, c0.z}, {c1.x, c1.y, c1.z}};
       } else {
-        primBox(a.scene, ref, a.time0, a.time1, cmn, cmx);
-        if (a.checkPrims)
-          for (int k = 0; k < 3; ++k) bad = bad || !fastDivOperand(cmn[k]) || !fastDivOperand(cmx[k]);
+        primBox(a.scene, ref, a.time0, a.time1, child.mn, child.mx);
+        if (a.checkPrims) bad = bad || !fastDivOperands(child);
       }
-      for (int k = 0; k < 3; ++k) {  // aabb.h:33-43
-        mn[k] = fminf(mn[k], cmn[k]);
-        mx[k] = fmaxf(mx[k], cmx[k]);
-      }
+      box = any ? surrounding(box, child) : child;
       any = true;
     }
     if (any) {
-      nodes[2 * (size_t)node] = make_float4(mn[0], mn[1], mn[2], n0.w);
-      nodes[2 * (size_t)node + 1] = make_float4(mx[0], mx[1], mx[2], n1.w);
+      nodes[2 * (size_t)node] = make_float4(box.mn[0], box.mn[1], box.mn[2], n0.w);
+      nodes[2 * (size_t)node + 1] = make_float4(box.mx[0], box.mx[1], box.mx[2], n1.w);
     }
     if (link < 0) break;  // a root
     const int parent = link & REFIT_PARENT_MASK, need = link >> REFIT_NEED_SHIFT;
@@ -168,9 +123,7 @@ __global__ void refitDerived(const float4* nodes, int numNodes, const int32_t* w
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= numNodes) return;
   const float4 lo = nodes[2 * (size_t)i], hi = nodes[2 * (size_t)i + 1];
-  if (!(fastDivOperand(lo.x) && fastDivOperand(lo.y) && fastDivOperand(lo.z) && fastDivOperand(hi.x) && fastDivOperand(hi.y) &&
-        fastDivOperand(hi.z)))
-    atomicOr(flag, 2);
+  if (!fastDivOperands(Box{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}})) atomicOr(flag, 2);
   if (wfIndex) {
     const size_t j = (size_t)wfIndex[i];
     nodesWf[2 * j] = make_float4(lo.x, lo.y, lo.z, nodesWf[2 * j].w);

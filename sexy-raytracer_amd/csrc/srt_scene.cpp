@@ -20,32 +20,6 @@
 
 namespace {
 
-// ------------------------------------------------------------------ host vector math
-struct H3 {
-  float x, y, z;
-};
-inline H3 h3(const float* p) { return H3{p[0], p[1], p[2]}; }
-inline H3 operator+(H3 a, H3 b) { return H3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-inline H3 operator-(H3 a, H3 b) { return H3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline H3 operator*(float s, H3 a) { return H3{s * a.x, s * a.y, s * a.z}; }
-inline H3 operator/(H3 a, float s) { return H3{a.x / s, a.y / s, a.z / s}; }
-inline H3 crossH(H3 a, H3 b) { return H3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-inline float lenSqH(H3 v) { return v.x * v.x + v.y * v.y + v.z * v.z; }  // vec3.h:29-31
-inline H3 unitH(H3 v) {                                                    // vec3.h:54-60
-  float len = sqrtf(lenSqH(v));
-  if (len != 0) return H3{v.x / len, v.y / len, v.z / len};
-  return v;
-}
-
-inline Box surrounding(const Box& a, const Box& b) {  // aabb.h:33-43
-  Box r;
-  for (int k = 0; k < 3; ++k) {
-    r.mn[k] = fminf(a.mn[k], b.mn[k]);
-    r.mx[k] = fmaxf(a.mx[k], b.mx[k]);
-  }
-  return r;
-}
-
 // ------------------------------------------------------------------ the global generator
 // globals.h:30-35: function-local static default-seeded mt19937 + uniform_real_distribution<float>(0,1)
 std::mt19937& hostGenerator() {
@@ -61,47 +35,16 @@ int hostRandomInt(int lo, int hi) {  // globals.h:37-43
   return static_cast<int>(a + (b - a) * hostRandomFloat());
 }
 
-// ------------------------------------------------------------------ primitives on the host
-Box sphereBoxAt(const SrtSphereIn& s, float time) {  // sphere.h:47-52, 86-89
-  H3 c0 = h3(s.center0), c1 = h3(s.center1);
-  H3 c = c0;
-  if (c0.x != c1.x || c0.y != c1.y || c0.z != c1.z) c = c0 + ((time - s.time0) / (s.time1 - s.time0)) * (c1 - c0);
-  Box b;
-  b.mn[0] = c.x - s.radius; b.mn[1] = c.y - s.radius; b.mn[2] = c.z - s.radius;
-  b.mx[0] = c.x + s.radius; b.mx[1] = c.y + s.radius; b.mx[2] = c.z + s.radius;
-  return b;
-}
-Box sphereBox(const SrtSphereIn& s, float t0, float t1) {  // sphere.h:85-94
-  return surrounding(sphereBoxAt(s, t0), sphereBoxAt(s, t1));
-}
-Box triangleBox(const SrtTriangleIn& t) {  // model.h:183-212
-  const float inf = std::numeric_limits<float>::infinity();
-  Box b;
-  for (int a = 0; a < 3; ++a) {
-    b.mn[a] = inf;
-    b.mx[a] = -inf;
-  }
-  for (int k = 0; k < 3; ++k)
-    for (int a = 0; a < 3; ++a) {
-      b.mn[a] = std::min(b.mn[a], t.p[k][a]);
-      b.mx[a] = std::max(b.mx[a], t.p[k][a]);
-    }
-  for (int a = 0; a < 3; ++a)
-    if (b.mn[a] == b.mx[a]) {
-      b.mn[a] -= 0.0001f;
-      b.mx[a] += 0.0001f;
-    }
-  return surrounding(b, b);
-}
+// ------------------------------------------------------------------ primitives on the host (srt_records.h)
 Box primBox(const SrtSceneDesc* d, int32_t prim, float t0, float t1) {
   const SrtPrimRef& pr = d->prims[prim];
-  return pr.type == SRT_PRIM_SPHERE ? sphereBox(d->spheres[pr.index], t0, t1) : triangleBox(d->triangles[pr.index]);
-}
-
-// fastDiv's operand certificate for the box coordinates (srt_kernels.hip): 0 or 2^-77 <= |c| <= 2^30
-bool fastDivOperand(float c) {
-  const float ac = fabsf(c);
-  return c == 0.0f || (ac >= 0x1p-77f && ac <= 0x1p30f);
+  if (pr.type == SRT_PRIM_SPHERE) {
+    const SrtSphereIn& s = d->spheres[pr.index];
+    const Vec3 c0 = vec3(s.center0), c1 = vec3(s.center1);
+    return sphereBox(c0, c1, c0 != c1, s.time0, s.time1, s.radius, t0, t1);
+  }
+  const SrtTriangleIn& t = d->triangles[pr.index];
+  return triangleBox(vec3(t.p[0]), vec3(t.p[1]), vec3(t.p[2]));
 }
 
 std::string format(const char* fmt, ...) {
@@ -286,37 +229,14 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
   }
   h.triTest.resize((size_t)d->numTriangles * 3);
   h.triShade.resize((size_t)d->numTriangles * 4);
-  const float eps = std::numeric_limits<float>::epsilon();
   for (int i = 0; i < d->numTriangles; ++i) {
     const SrtTriangleIn& t = d->triangles[i];
-    H3 v0 = h3(t.p[0]), v1 = h3(t.p[1]), v2 = h3(t.p[2]);
-    H3 n = crossH(v1 - v0, v2 - v0);  // getNormal, model.h:276-283
-    h.triTest[3 * i + 0] = make_float4(v0.x, v0.y, v0.z, n.x);
-    h.triTest[3 * i + 1] = make_float4(v1.x, v1.y, v1.z, n.y);
-    h.triTest[3 * i + 2] = make_float4(v2.x, v2.y, v2.z, n.z);
-    H3 nu = unitH(n);  // model.h:172
-    // calcTangentBasis, model.h:214-235
-    H3 e0 = v1 - v0, e1 = v2 - v0;
-    float du0 = t.uv[1][0] - t.uv[0][0], dv0 = t.uv[1][1] - t.uv[0][1];
-    float du1 = t.uv[2][0] - t.uv[0][0], dv1 = t.uv[2][1] - t.uv[0][1];
-    float f = (du0 * dv1 - du1 * dv0);
-    if (f == 0) f += eps;
-    f = 1.0f / f;
-    H3 tg = unitH(H3{f * (dv1 * e0.x - dv0 * e1.x), f * (dv1 * e0.y - dv0 * e1.y), f * (dv1 * e0.z - dv0 * e1.z)});
-    H3 bt = unitH(H3{f * (-du1 * e0.x + du0 * e1.x), f * (-du1 * e0.y + du0 * e1.y), f * (-du1 * e0.z + du0 * e1.z)});
-    h.triShade[4 * i + 0] = make_float4(nu.x, nu.y, nu.z, t.uv[0][0]);
-    h.triShade[4 * i + 1] = make_float4(tg.x, tg.y, tg.z, t.uv[0][1]);
-    h.triShade[4 * i + 2] = make_float4(bt.x, bt.y, bt.z, t.uv[1][0]);
-    h.triShade[4 * i + 3] = make_float4(t.uv[1][1], t.uv[2][0], t.uv[2][1], bitsAs<float>(&t.material));
+    triangleRecords(&t.p[0][0], &t.uv[0][0], bitsAs<float>(&t.material), &h.triTest[3 * (size_t)i], &h.triShade[4 * (size_t)i]);
   }
   h.spheres.resize((size_t)d->numSpheres * 3);
   for (int i = 0; i < d->numSpheres; ++i) {
     const SrtSphereIn& s = d->spheres[i];
-    bool moving = s.center0[0] != s.center1[0] || s.center0[1] != s.center1[1] || s.center0[2] != s.center1[2];
-    int32_t bits = s.material | (moving ? (1 << 30) : 0);
-    h.spheres[3 * i + 0] = make_float4(s.center0[0], s.center0[1], s.center0[2], s.radius);
-    h.spheres[3 * i + 1] = make_float4(s.center1[0], s.center1[1], s.center1[2], bitsAs<float>(&bits));
-    h.spheres[3 * i + 2] = make_float4(s.time0, s.time1, 0.0f, 0.0f);
+    sphereRecords(vec3(s.center0), vec3(s.center1), s.time0, s.time1, s.radius, s.material, &h.spheres[3 * (size_t)i]);
   }
   // device index of a triangle: identity until the trees are built, then the order in which the host-built
   // trees' leaves reference the triangles (below), so that a leaf's records and its neighbours' sit together
@@ -545,8 +465,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     db.refs.resize(it.count);
     for (int i = 0; i < it.count; ++i) {
       db.refs[i] = devRef(~(it.first + i));
-      const Box bx = primBox(d, it.first + i, it.time0, it.time1);
-      for (int k = 0; k < 3; ++k) certified = certified && fastDivOperand(bx.mn[k]) && fastDivOperand(bx.mx[k]);
+      certified = certified && fastDivOperands(primBox(d, it.first + i, it.time0, it.time1));
     }
   }
   h.fastDivScene = certified ? o.fastDiv : 0;
@@ -590,18 +509,18 @@ void srtHostRandomReset(void) { hostGenerator().seed(std::mt19937::default_seed)
 int srtMakeCamera(const SrtCameraParams* in, SrtCamera* out) {
   if (!in || !out) return 1;
   const float pi = 3.1415926535897932385f;
-  H3 eye = h3(in->eye), lookAt = h3(in->lookAt), up = h3(in->up);
+  Vec3 eye = vec3(in->eye), lookAt = vec3(in->lookAt), up = vec3(in->up);
   float theta = in->vfovDegrees * pi / 180.0f;  // deg2rad, globals.h:26-28
   double h = tan((double)(theta / 2.0f));       // camera.h:20: tan(float) is the double overload
   double vpHeight = 2.0f * h;
   double vpWidth = in->aspect * vpHeight;
-  H3 w = unitH(eye - lookAt);
-  H3 hor = unitH(crossH(up, w));
-  H3 vert = unitH(crossH(w, hor));
-  H3 horizontal = (float)(in->focusDist * vpWidth) * hor;  // Eigen casts the double scalar to float
-  H3 vertical = (float)(in->focusDist * vpHeight) * vert;
-  H3 lleft = eye - horizontal / 2.0f - vertical / 2.0f - in->focusDist * w;
-  const H3* src[] = {&eye, &lleft, &horizontal, &vertical, &w, &hor, &vert};
+  Vec3 w = unit(eye - lookAt);
+  Vec3 hor = unit(cross(up, w));
+  Vec3 vert = unit(cross(w, hor));
+  Vec3 horizontal = (float)(in->focusDist * vpWidth) * hor;  // Eigen casts the double scalar to float
+  Vec3 vertical = (float)(in->focusDist * vpHeight) * vert;
+  Vec3 lleft = eye - horizontal / 2.0f - vertical / 2.0f - in->focusDist * w;
+  const Vec3* src[] = {&eye, &lleft, &horizontal, &vertical, &w, &hor, &vert};
   float* dst[] = {out->origin, out->lleft, out->horizontal, out->vertical, out->w, out->hor, out->vert};
   for (int i = 0; i < 7; ++i) {
     dst[i][0] = src[i]->x;

@@ -9,10 +9,7 @@
 #include <vector>
 
 #include "srt_device.h"
-
-struct Box {
-  float mn[3], mx[3];
-};
+#include "srt_records.h"
 
 // ------------------------------------------------------------------ bvh.h:55-95
 struct BuildNode {

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import records_cases as RC
 import refit_ref as RF
 import tree_build_ref as R
 import tree_build_scenes as S
@@ -182,6 +183,53 @@ def test_updated_records_trace_like_the_oracle_on_the_moved_scene(ctx, oracle, s
         (_bits(got["uv"][on_tri]) != _bits(want["uv"][on_tri])).sum(), (_bits(got["uv"][on_sph]) != _bits(want["uv"][on_sph])).sum()))
     assert np.array_equal(_bits(got["uv"][on_tri]), _bits(want["uv"][on_tri]))
     assert np.abs(got["uv"][on_sph].astype(np.float64) - want["uv"][on_sph]).max() <= 1e-6
+
+
+# ------------------------------------------------------------------------------------------------ edge cases
+EDGE_HIT_FIELDS = HIT_FIELDS + ("uv", "material")
+
+
+@pytest.mark.parametrize("builder", ["host", "lbvh", "ploc"])
+def test_edge_case_records_and_boxes_are_an_uploads(ctx, dev, abi, builder):
+    """tests/records_cases.py as one world item: uploaded scaled by exactly 2 with every zero made +0 (same topology: every
+    box minimum and centroid doubles, but no record, box or zero sign is the one wanted), updated to the edge cases and
+    refitted, against a fresh context that uploads the edge cases.  Trees, pair records (they hold the primitives' own
+    boxes) and the closest hits of one ray per primitive on bits, the signs of zeros included."""
+    tri, sph = RC.geometry(abi)
+    which = {"host": abi.SRT_BUILDER_REFERENCE, "lbvh": abi.SRT_BUILDER_LBVH, "ploc": abi.SRT_BUILDER_PLOC}[builder]
+    far_tri, far_sph = tri.copy(), sph.copy()
+    far_tri["p"] = far_tri["p"] * F(2) + F(0)
+    for f in ("center0", "center1", "radius"):
+        far_sph[f] = far_sph[f] * F(2) + F(0)
+    neg_zero = lambda v: ((v == 0) & np.signbit(v)).any()
+    assert not neg_zero(far_tri["p"]) and neg_zero(tri["p"])
+    edge = RC.scene(abi, tri, sph, which)
+    ctx.upload_scene(RC.scene(abi, far_tri, far_sph, which))
+    stale = ctx.bvh(0)
+    sent_tri, sent_sph = tri.copy(), sph.copy()
+    sent_tri["material"], sent_sph["material"] = 12345, -7  # ignored
+    _update_all(ctx, sent_tri, sent_sph)
+    rays = RC.rays(abi, tri, sph)
+    got_nodes, (got_axis, got_pairs), got = ctx.bvh(0), ctx.tree_aux(0), ctx.trace(rays, abi.SRT_TRAVERSE_CLOSEST)
+    fresh = dev.Context(0)
+    try:
+        fresh.upload_scene(edge)
+        want_nodes, (want_axis, want_pairs), want = fresh.bvh(0), fresh.tree_aux(0), fresh.trace(rays, abi.SRT_TRAVERSE_CLOSEST)
+    finally:
+        fresh.close()
+    assert stale.tobytes() != want_nodes.tobytes()
+    assert got_nodes.tobytes() == want_nodes.tobytes()
+    assert got_axis.tobytes() == want_axis.tobytes() and got_pairs.tobytes() == want_pairs.tobytes()
+    # every primitive with an area is met by its own ray (list order: the triangles, then the spheres)
+    no_area = [4, 5]
+    assert [int(p) for p in want["prim"]] == [-1 if i in no_area else i for i in range(len(rays))]
+    for f in EDGE_HIT_FIELDS:
+        assert np.array_equal(_bits(got[f]), _bits(want[f])), f
+    # the zero rule reached the device: the root's minimum is +0 on x (triangle 2 alone) and -0 on y (triangle 3 alone)
+    assert _bits(got_nodes["bmin"][0, :2]).tolist() == [0x00000000, 0x80000000]
+    if builder == "host":
+        built = dev.build_bvh_host(edge)[0]
+        assert got_nodes.tobytes() == built.tobytes()
 
 
 # ------------------------------------------------------------------------------------------------ FAITHFUL renders

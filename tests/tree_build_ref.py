@@ -68,7 +68,12 @@ def prim_boxes(scene, refs, time0, time1):
     t = kind == PRIM_TRIANGLE
     if t.any():
         v = sc.tri[index[t]]
-        lo, hi = v.min(axis=1), v.max(axis=1)
+        # model.h:191-197: std::min / std::max folded over the vertices in order from +-infinity, so of two zeros of
+        # opposite sign the first one seen stays (NumPy's min / max leave that open)
+        lo, hi = np.full(v[:, 0].shape, np.inf, F), np.full(v[:, 0].shape, -np.inf, F)
+        for k in range(3):
+            lo = np.where(v[:, k] < lo, v[:, k], lo)
+            hi = np.where(hi < v[:, k], v[:, k], hi)
         flat = lo == hi
         mn[t] = np.where(flat, lo - PAD, lo)
         mx[t] = np.where(flat, hi + PAD, hi)
