@@ -28,6 +28,7 @@
 // grid drains when every context has found the work queues empty (live == 0).
 #include "srt_path.h"
 #include "srt_launch.h"
+#include "srt_wf_links.h"
 
 #define WF_BLOCK 1024
 #define WF_CLASSES 3
@@ -64,6 +65,8 @@ __device__ __forceinline__ void bufStore4(Rsrc r, int off, float4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(u, r, off, 0, 0);
 }
 __device__ __forceinline__ void bufStore1(Rsrc r, int off, uint32_t v) { __builtin_amdgcn_raw_buffer_store_b32(v, r, off, 0, 0); }
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) const f32x4 LdsVec4;  // a 16-byte slot addressed by its LDS byte offset
 __device__ __forceinline__ uint32_t bufLoad1(Rsrc r, int off) { return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0); }
 }  // namespace
 
@@ -84,15 +87,15 @@ template <bool SINGLE, bool PROFILE, bool HYBRID, bool COUNT, bool MOMENTS = fal
 __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const RenderArgs a) {
   static_assert(!(MOMENTS && (COUNT || PROFILE)), "the moments instances neither count nor profile");
 
-  // whole tree in LDS: 16-bit references, DONE = the 16-bit "no reference" sign-extended, a link = two of them.
+  // whole tree in LDS: the words of srt_wf_links.h -- a node is its record's LDS byte offset, a leaf one word that holds
+  // both objects, a link the successor alone; hitRef and hitPrim[] hold 16-bit primitive references, sign-extended.
   // HYBRID: 32-bit references, DONE = -2^29, a link = successor << 2 | what follows a leaf's first object (srt_device.h)
-  constexpr int32_t DONE = HYBRID ? -(1 << 29) : (int32_t)0xFFFF8000;
-  constexpr int32_t DONE_PAIR = HYBRID ? (int32_t)0x80000000 : (int32_t)0x80008000;  // "nothing follows, then done"
-  constexpr int LINK_SHIFT = HYBRID ? 2 : 16;
+  constexpr int32_t DONE = HYBRID ? -(1 << 29) : SRT_WF_DONE;
+  constexpr int32_t DONE_PAIR = HYBRID ? (int32_t)0x80000000 : SRT_WF_DONE;  // "nothing follows, then done"
   typedef typename std::conditional<HYBRID, int32_t, uint16_t>::type PrimSlot;
   extern __shared__ int32_t lds[];
   const DevScene& sc = a.scene;
-  char* const ldsTree = reinterpret_cast<char*>(lds);
+  char* const ldsTree = reinterpret_cast<char*>(lds);  // LDS offset 0 (the kernel has no other LDS): a node's offset is its address
   const int resident = HYBRID ? sc.wfResident : sc.numNodes;  // nodes [0, resident) are in LDS
   const int treeBytes = resident * 32;
   int32_t* const ctl = reinterpret_cast<int32_t*>(ldsTree + treeBytes);
@@ -118,8 +121,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   const bool singleRoot = SINGLE || sc.numWorld == 1;
   auto worldRef = [&](int k) {
     if (HYBRID) return sc.worldWf[k];
-    const int r = sc.world[k];
-    return r >= 0 ? r >> 5 : r;
+    return srtWfRootWord(sc.world[k]);
   };
   // place of counter value c in a ring: c mod RCAP, RCAP = 2^j or 3 * 2^j (the pool size rounded up to such a number)
   const int ringShift = a.wfRingShift;
@@ -131,17 +133,15 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     return (int)((c & ((1u << ringShift) - 1u)) | (x3 << ringShift));
   };
 
-  // ---- set-up: the threaded tree into LDS (as srt_render_kernel LDSTREE), empty rings, every context waits for an item
+  // ---- set-up: the threaded tree into LDS, at offset 0, its two link words per node re-encoded for this kernel's walk
+  // (srt_wf_links.h; the hybrid form's records are stored ready-made), empty rings, every context waits for an item
   {
     float4* dst = reinterpret_cast<float4*>(ldsTree);
     for (int i = threadIdx.x; i < resident * 2; i += WF_BLOCK) {
       float4 v = bufLoad4(rsNodes, 16 * i);
       if (!HYBRID) {  // nodesWf holds the threaded records already
-        const int r = __float_as_int(v.w);
-        if (i & 1)
-          v.w = __int_as_float(sc.nodeThread[i >> 1]);
-        else if (r >= 0)
-          v.w = __int_as_float(r >> 5);
+        const int32_t thread = sc.nodeThread[i >> 1];
+        v.w = __int_as_float((i & 1) ? srtWfMissWord(thread) : srtWfHitWord(__float_as_int(v.w), thread));
       }
       dst[i] = v;
     }
@@ -291,8 +291,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
       if (follows == 2) next = (int)__builtin_amdgcn_raw_buffer_load_b32(rsSecond, (~cur) << 2, 0, 0);  // any other pair (rare)
       link &= ~3;
     } else {
-      next = (int32_t)(int16_t)link;
-      link >>= 16;
+      next = srtWfLeafHasSecond(cur) ? srtWfLeafRest(cur) : link;
     }
     if (!SINGLE && !singleRoot && next == DONE && ++w < sc.numWorld) {
       next = worldRef(w);
@@ -366,7 +365,8 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           pLanes[1] += __popcll(__ballot(atPrim()));
         }
         if (atPrim()) {
-          const int pr = ~cur;
+          const int ref = HYBRID ? cur : srtWfLeafFirst(cur);  // the object this lane stands on
+          const int pr = ~ref;
           float t;
           bool ok;
           if (pr & 1) {
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           }
           if (ok) {
             closest = t;
-            hitRef = cur;
+            hitRef = ref;
           }
           popNext();
         }
@@ -417,7 +417,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           if (hitBox) cnt[3]++;
         }
         link = __float_as_int(n1.w);
-        cur = hitBox ? __float_as_int(n0.w) : (link >> LINK_SHIFT);
+        cur = hitBox ? __float_as_int(n0.w) : (HYBRID ? link >> 2 : link);
         if (!SINGLE && !singleRoot && cur == DONE && ++w < sc.numWorld) {
           cur = worldRef(w);
           link = DONE_PAIR;
@@ -430,8 +430,15 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           pLanes[0] += __popcll(__ballot(here));
         }
         if (here) {
-          const char* rec = ldsTree + (cur << 5);
-          visit(*reinterpret_cast<const float4*>(rec), *reinterpret_cast<const float4*>(rec + 16));
+          if constexpr (HYBRID) {
+            const char* rec = ldsTree + (cur << 5);
+            visit(*reinterpret_cast<const float4*>(rec), *reinterpret_cast<const float4*>(rec + 16));
+          } else {
+            // the tree sits at LDS offset 0: `cur` IS the record's LDS address (no base to add, not even a zero one)
+            const LdsVec4* rec = (const LdsVec4*)(uintptr_t)(uint32_t)cur;
+            const f32x4 n0 = rec[0], n1 = rec[1];
+            visit(make_float4(n0.x, n0.y, n0.z, n0.w), make_float4(n1.x, n1.y, n1.z, n1.w));
+          }
         }
       };
       do {
