@@ -17,6 +17,8 @@
 // and against the harness's recorded results tests/golden/ref_<scene>.npz, which every machine has
 // (test_oracle_reproduces_recorded_reference).  The statistical pins that came first stay (test_oracle_anchors.py:
 // libstdc++ known answers, BVH statistics of SURVEY.md A.5, the two published PNGs).
+// orc_sample_path retraces ONE sample of orc_render bounce by bounce (ray, hit, attenuation, emitted): what
+// tests/test_gpu_exact_frames.py's explain_pixel holds srtRenderAov's records against when a zero-tolerance frame differs.
 // What stays ASSUMED: Eigen's reduction order in dot() / Matrix3f * vec (a0b0 + (a1b1 + a2b2), Eigen's unrolled redux;
 // no Eigen checkout exists; the stand-in and this file share the assumption, written once in refshim/Eigen/Core), and
 // stb's PNG decode (the harness reads PIL's bytes).  Where the reference's behaviour is undefined (NaN cast to int, the
@@ -188,6 +190,17 @@ struct Counters {
 };
 static thread_local Counters* tlsCounters = nullptr;
 #define COUNT(field) do { if (tlsCounters) tlsCounters->field++; } while (0)
+
+// orc_sample_path: what rayColor did at every bounce of ONE sample -- the ray it traced, what that ray hit, and what
+// scatter() / emitted() returned there.  Recorded only while tlsPath is set; a render never sets it.
+struct PathStep {
+  float o[3], d[3], time;
+  int32_t prim;  // SRT_NO_HIT: the path ended on the background
+  float t;
+  int32_t material, scattered;  // scattered 0: scatter() was false (a light), the path ended on `emitted`
+  float attenuation[3], emitted[3];
+};
+static thread_local std::vector<PathStep>* tlsPath = nullptr;
 
 // ---------------------------------------------------------------- aabb.h
 struct aabb {
@@ -662,12 +675,32 @@ static vec3 rayColor(const ray& r, const vec3& background, const hittable& world
   hitRecord rec;
   if (maxBounce <= 0) return vec3(0, 0, 0);
   COUNT(rays);
+  size_t step = 0;
+  if (tlsPath) {
+    step = tlsPath->size();
+    PathStep ps;
+    memset(&ps, 0, sizeof ps);
+    for (int k = 0; k < 3; k++) { ps.o[k] = r.o(k); ps.d[k] = r.dir(k); }
+    ps.time = r.time;
+    ps.prim = SRT_NO_HIT;
+    ps.material = -1;
+    tlsPath->push_back(ps);
+  }
   if (!world.hit(r, tMin, infinity, rec)) return background;
   ray scattered;
   vec3 attenuation;
   vec3 emitted = rec.matPtr->emitted(rec.uv[0], rec.uv[1], rec.p);
   if (rec.isTri) COUNT(shadedTriHits);
-  if (!rec.matPtr->scatter(r, rec, attenuation, scattered, rng)) return emitted;
+  const bool goesOn = rec.matPtr->scatter(r, rec, attenuation, scattered, rng);
+  if (tlsPath) {
+    PathStep& ps = (*tlsPath)[step];
+    ps.prim = rec.prim;
+    ps.t = rec.t;
+    ps.material = rec.matPtr->id;
+    ps.scattered = goesOn ? 1 : 0;
+    for (int k = 0; k < 3; k++) { ps.attenuation[k] = goesOn ? attenuation(k) : 0.0f; ps.emitted[k] = emitted(k); }
+  }
+  if (!goesOn) return emitted;
   vec3 newColor = rayColor(scattered, background, world, maxBounce - 1, tMin, rng);
   newColor = vec3(newColor(0) * attenuation(0), newColor(1) * attenuation(1), newColor(2) * attenuation(2));
   return emitted + newColor;
@@ -1023,6 +1056,29 @@ int orc_render(void* h, const SrtCamera* cam, const SrtRenderParams* p, int rngM
     stats->texelFetches = total.texelFetches; stats->rngDraws = draws;
   }
   return 0;
+}
+
+// One sample of orc_render in COUNTER mode -- pixel (x, y), sample index `sample`, the same key and the same draws -- with
+// rayColor's steps recorded: steps[capacity] (PathStep: 17 words each), *count = the number of rays the sample traced
+// (also when it exceeds capacity), color3 = the sample's value, the term orc_render adds to the pixel sum.
+void orc_sample_path(void* h, const SrtCamera* cam, const SrtRenderParams* p, int x, int y, int sample, void* steps,
+                     int capacity, int* count, float* color3) {
+  Scene* s = static_cast<Scene*>(h);
+  const int W = p->imageWidth, H = p->imageHeight;
+  std::vector<PathStep> path;
+  Rng rng;
+  rng.mode = RNG_COUNTER;
+  rng.mt = &s->mt;
+  rng.key(p->seed, (uint32_t)(y * W + x), (uint32_t)sample);
+  float u = (float)(x + rng.randomFloat()) / (W - 1);
+  float v = (float)((H - y) + rng.randomFloat()) / (H - 1);
+  ray r = getRay(*cam, u, v, rng);
+  tlsPath = &path;
+  vec3 c = rayColor(r, vec3(p->background[0], p->background[1], p->background[2]), s->world, p->maxBounce, p->tMin, rng);
+  tlsPath = nullptr;
+  *count = (int)path.size();
+  if (steps) memcpy(steps, path.data(), sizeof(PathStep) * (size_t)std::min<int>(capacity, (int)path.size()));
+  for (int k = 0; k < 3; k++) color3[k] = c(k);
 }
 
 // color.h:25-41 on an accumulator image

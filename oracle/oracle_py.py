@@ -15,6 +15,10 @@ if _ROOT not in sys.path:
 abi = importlib.import_module("sexy-raytracer_amd.abi")
 
 RNG_MT, RNG_COUNTER = 0, 1
+# orc_sample_path's record per bounce (oracle.cpp PathStep)
+PATH_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("time", "<f4"), ("prim", "<i4"), ("t", "<f4"), ("material", "<i4"),
+                       ("scattered", "<i4"), ("attenuation", "<f4", 3), ("emitted", "<f4", 3)])
+assert PATH_DTYPE.itemsize == 68
 
 
 class OrcStats(C.Structure):
@@ -62,6 +66,8 @@ def lib():
         L.orc_scatter_many_mt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_render.argtypes = [C.c_void_p, C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtRenderParams), C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(OrcStats)]
+        L.orc_sample_path.argtypes = [C.c_void_p, C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtRenderParams), C.c_int, C.c_int,
+                                      C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
         L.orc_resolve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
@@ -155,6 +161,16 @@ class OracleScene:
         lib().orc_render(self.h, C.byref(cam), C.byref(params), rng_mode, threads, r0, r1, accum.ctypes.data,
                          rgba.ctypes.data if rgba is not None else None, C.byref(st) if want_stats else None)
         return accum, rgba, st.as_dict()
+
+    def sample_path(self, cam, params, x, y, sample):
+        """What render(RNG_COUNTER) did for sample index `sample` of pixel (x, y): (steps, colour) -- one PATH_DTYPE record
+        per ray the sample traced (the ray, its hit, scatter()'s attenuation and emitted()), and the sample's value."""
+        steps = np.zeros(params.maxBounce + 1, PATH_DTYPE)
+        n, colour = C.c_int(0), np.zeros(3, np.float32)
+        lib().orc_sample_path(self.h, C.byref(cam), C.byref(params), int(x), int(y), int(sample), steps.ctypes.data, len(steps),
+                              C.byref(n), colour.ctypes.data)
+        assert n.value <= params.maxBounce
+        return steps[:n.value], colour
 
 
 def resolve(accum, spp):

@@ -1,5 +1,5 @@
 """Inputs of the reference pin (tests/test_reference_pin.py, tests/make_golden.py, tests/test_gpu_reference_pin.py): the
-edge rays, the edge scene and the scatter records.  Everything here is made from the scene's own numbers in float32 and
+edge rays, the edge scene, the cameras and the scatter records.  Everything here is made from the scene's own numbers in float32 and
 from seeded generators: nothing calls the oracle, the harness or the device library."""
 import numpy as np
 
@@ -166,6 +166,26 @@ def edge_scene(abi):
     sb.add_sphere((-4.0, 1.0, 2.0), 1.0, mat)
     sb.world_bvh(0, None, 0.0, 1.0)
     return sb
+
+
+# ---------------------------------------------------------------------------------------------------- cameras
+# camera.h:10-38 at other settings than main.cpp's: aperture 0, time0 == time1, vfov 20 to 151 degrees, another eye, a tilted up
+# vector (tests/test_reference_pin.py test_cameras on the CPU, tests/test_gpu_exact_frames.py on the GPU)
+CAMERAS = [  # eye, lookAt, up, vfov, aspect, aperture, focus distance, time0, time1
+    ((0, 3, 5), (0, 2.5, 0), (0, 1, 0), vfov, aspect, aperture, focus, t0, t1)
+    for vfov, aspect, aperture, focus, t0, t1 in (
+        (20.0, 16 / 9, 0.1, 10.0, 0.0, 1.0), (33.3, 1.5, 0.0, 1.0, 0.0, 0.0), (45.0, 1.0, 2.0, 5.5, 0.25, 0.75),
+        (59.9, 2.35, 0.3, 7.3, 0.0, 1.0), (89.0, 4 / 3, 0.05, 3.1, 0.0, 2.0), (101.7, 16 / 9, 0.7, 12.9, 1.0, 3.0),
+        (120.0, 0.75, 1.1, 0.37, 0.0, 1.0), (151.3, 2.0, 0.01, 25.0, 0.0, 1.0))
+] + [((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, 1.5, 0.1, 10.0, 0.0, 1.0), ((-2, 7, 1), (1, 0.5, -3), (0.2, 1, -0.1), 64.2, 1.25, 0.4, 6.6, 0.0, 1.0)]
+
+
+def camera_params(abi, k):
+    """CAMERAS[k] as an SrtCameraParams."""
+    cp = abi.SrtCameraParams()
+    cp.eye[:], cp.lookAt[:], cp.up[:] = CAMERAS[k][:3]
+    cp.vfovDegrees, cp.aspect, cp.aperture, cp.focusDist, cp.time0, cp.time1 = CAMERAS[k][3:]
+    return cp
 
 
 # ---------------------------------------------------------------------------------------------------- scatter records

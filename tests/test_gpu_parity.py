@@ -13,6 +13,15 @@ Bars:
     lookup); all other arithmetic keeps the reference's operation order without FMA contraction.
   * traversal/shading counters (rays, node visits, box passes, primitive tests, texel fetches)
     equal the oracle's exactly.
+
+The render bars above accept their residual whatever its cause: one wrong sample in a few thousand passes them.  The
+EXACT tier (tests/test_gpu_exact_frames.py on the scenes of tests/exact_scenes.py) closes that: on scenes whose shading
+calls no single-precision libm (metal, dielectric, solid-colour lights, the background; pbr with constant factors or
+solid-colour textures, whose one libm call is a double exp2) whole frames are compared with NO tolerance -- every kernel
+form, chunk plan, camera, ring capacity of the path pool and scheduling tunable.  It proves that the sample keys, the
+bounce bookkeeping, the attenuation levels, the chunk sums and the work distribution are the oracle's, bit for bit.  It
+cannot see what needs sinf / acosf / atan2f or a texel: checker and image textures, normal and metallic / roughness
+maps stay with the residual bars of this file.
 """
 import json
 import os

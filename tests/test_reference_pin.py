@@ -15,6 +15,7 @@ import os
 import numpy as np
 import pytest
 
+import exact_scenes
 import ref_cases
 import ref_harness as H
 import shade_ref
@@ -107,6 +108,9 @@ def scene(srt, abi, name):
             sb = ref_cases.edge_scene(abi)
         elif name == "dielectric":
             sb = dielectric_scene(abi)
+        elif name.startswith("exact_"):  # "exact_room_A", "exact_random_B": tests/exact_scenes.py
+            _, kind, tier = name.split("_")
+            sb = exact_scenes.room(abi, tier) if kind == "room" else exact_scenes.random(abi, EXACT_RANDOM_SEED, tier)
         else:
             sb = _variants(abi)[name]
         _scene_cache[name] = sb
@@ -264,7 +268,11 @@ def test_scatter(abi, oracle, pre_draws):
 FRAMES = {  # scene: width, height, samples, bounces
     "spheres": (64, 36, 4, 8), "iron": (64, 36, 4, 4), "masterchief": (64, 36, 4, 4),  # those of render_<scene>.npz
     "sphere_field": (64, 36, 4, 4), "moving": (32, 18, 2, 6), "textures": (32, 18, 2, 6), "dielectric": (48, 27, 4, 8),
+    # the scenes the GPU's zero-tolerance frames use (tests/exact_scenes.py), so that the reference's own headers pin the
+    # oracle on exactly these: the closed room with deep paths, and one random scene (a single tree) per tier
+    "exact_room_A": (48, 27, 2, 12), "exact_room_B": (48, 27, 2, 12), "exact_random_A": (48, 27, 3, 6), "exact_random_B": (48, 27, 3, 6),
 }
+EXACT_RANDOM_SEED = 3
 
 
 @pytest.mark.parametrize("name", list(FRAMES))
@@ -291,13 +299,7 @@ def test_whole_frames(srt, abi, oracle, name):
         assert np.array_equal(want_rgba[defined], g["rgba_mt"][defined])
 
 
-CAMERAS = [  # eye, lookAt, up, vfov, aspect, aperture, focus distance, time0, time1
-    ((0, 3, 5), (0, 2.5, 0), (0, 1, 0), vfov, aspect, aperture, focus, t0, t1)
-    for vfov, aspect, aperture, focus, t0, t1 in (
-        (20.0, 16 / 9, 0.1, 10.0, 0.0, 1.0), (33.3, 1.5, 0.0, 1.0, 0.0, 0.0), (45.0, 1.0, 2.0, 5.5, 0.25, 0.75),
-        (59.9, 2.35, 0.3, 7.3, 0.0, 1.0), (89.0, 4 / 3, 0.05, 3.1, 0.0, 2.0), (101.7, 16 / 9, 0.7, 12.9, 1.0, 3.0),
-        (120.0, 0.75, 1.1, 0.37, 0.0, 1.0), (151.3, 2.0, 0.01, 25.0, 0.0, 1.0))
-] + [((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, 1.5, 0.1, 10.0, 0.0, 1.0), ((-2, 7, 1), (1, 0.5, -3), (0.2, 1, -0.1), 64.2, 1.25, 0.4, 6.6, 0.0, 1.0)]
+CAMERAS = ref_cases.CAMERAS
 
 
 @pytest.mark.parametrize("k", range(len(CAMERAS)))
