@@ -397,6 +397,13 @@ int srtRenderFeatureTileList(SrtContext* ctx, const SrtRenderParams* p, int32_t 
  * same math, but a constant neighbourhood comes back exactly.
  * The kernel computes the exponentials as one v_exp_f32 and the normal power as one v_log_f32 per tap: it agrees with a
  * libm evaluation of these formulas within a few 1e-6 relative (measured: DESIGN.md 5.6).
+ * Underflow: a tap's exponential (w_n exp(-a_z) in the level-0 variance, exp(sigmaN ln(n_p.n_q) - a_z - a_l) in a level)
+ * below 2^-126, the smallest normal float, counts as 0; the products with h keep denormals.  A valid pixel never meets this
+ * (its own tap has exponent 0), but a pixel that is not valid is filled only by taps whose exponentials reach 2^-126, and
+ * "sum w = 0" above includes the sum of nothing but such zeros: the pixel stays invalid.  Whether an invalid pixel gets
+ * filled is therefore ill-conditioned where every neighbour's weight lies near that threshold -- sigmas far from the
+ * defaults, such as sigmaLuminance 1e-3 with sigmaNormal 1000: there a float and a double evaluation of these formulas
+ * may fill different pixels.
  *
  * srtDenoise      DEVICE buffers, asynchronous on `stream`.  dOut (may be NULL) = float4[W*H]: rgb = the denoised mean
  *                 radiance, w = the beauty count; dRgba (may be NULL, not both) = uchar4[W*H], srtResolveTiles's

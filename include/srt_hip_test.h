@@ -48,6 +48,17 @@ int srtScatterRaysForm(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, 
  * srtPlanSppChunks allows any image (30 812), a path other than 0 or 1, and null pointers. */
 int srtTestChunkSum(SrtContext* ctx, const float* hChunks, int32_t n, int32_t chunks, int32_t path, int32_t samples, float* hOut4);
 
+/* Reads back the denoiser's scratch (csrc/srt_denoise.hip) as the most recent srtDenoise / srtDenoiseMoments of a
+ * width x height image on this context left it: synchronises the device, then copies the four regions to HOST buffers, any
+ * of which may be NULL.  hGuide4: W*H x {n.xyz, z}, z = NaN for a miss.  hGrad2: W*H x {zx, zy}.  hCol0_4, hCol1_4: the two
+ * ping-pong colour buffers, W*H x {e.rgb, v}; a pixel that is not valid has e.r = NaN (the prepare pass: all of e NaN; a
+ * level: {NaN, 0, 0, 0}).  The prepare pass writes col[0] = {e, v} after 0 levels, level i reads col[i & 1] and writes
+ * col[(i + 1) & 1], and the last level writes the caller's outputs instead.  So after a run of k + 1 levels col[k & 1] holds
+ * {e, v} after k levels (col[0] after 0 levels when k = 0) and the other buffer the state after k - 1 levels, or what an
+ * earlier call left when k = 0.  Launches nothing and changes nothing.  Fails, with an error text, for a size <= 0 and
+ * when the context's scratch is smaller than width * height * SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL bytes. */
+int srtTestDenoiseScratch(SrtContext* ctx, int32_t width, int32_t height, float* hGuide4, float* hCol0_4, float* hCol1_4, float* hGrad2);
+
 /* Sub-step profile of the most recent countStats launch of the step-scheduler kernel (shader clocks summed over waves,
  * diagnostics only; zero after one of the path-pool kernel, which a counting launch runs where the production launch would):
  * out10 = { hit step: hit record, textures, direction draw, BRDF + bookkeeping; restart step;

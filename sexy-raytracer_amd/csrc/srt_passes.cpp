@@ -175,6 +175,27 @@ int srtDenoiseImpl(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, in
   return 0;
 }
 
+// test entry (include/srt_hip_test.h): the four regions of the denoise scratch as srtDenoiseImpl lays them out for a
+// width x height image, copied to the host.  Launches nothing, changes nothing.
+static int srtTestDenoiseScratchImpl(SrtContext* ctx, int32_t width, int32_t height, float* hGuide4, float* hCol0_4,
+                                     float* hCol1_4, float* hGrad2) {
+  if (!ctx) return 1;
+  if (width <= 0 || height <= 0) return fail(ctx, "denoise scratch: image size %dx%d must be positive", width, height);
+  if ((int64_t)width * height > 0x7fffffff) return fail(ctx, "denoise scratch: image of %dx%d pixels is too large", width, height);
+  const size_t nPix = (size_t)width * height;
+  if (ctx->denoiseScratch.bytes() < nPix * SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL)
+    return fail(ctx, "denoise scratch: the scratch holds %zu bytes, a %dx%d image needs %zu (no srtDenoise of that size yet)",
+                ctx->denoiseScratch.bytes(), width, height, nPix * SRT_DENOISE_SCRATCH_BYTES_PER_PIXEL);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  HIP_OK(ctx, hipDeviceSynchronize());
+  const char* s = ctx->denoiseScratch.get<char>();
+  float* const dst[4] = {hGuide4, hCol0_4, hCol1_4, hGrad2};
+  const size_t off[4] = {0, 16 * nPix, 32 * nPix, 48 * nPix}, len[4] = {16 * nPix, 16 * nPix, 16 * nPix, 8 * nPix};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) HIP_OK(ctx, hipMemcpy(dst[k], s + off[k], len[k], hipMemcpyDeviceToHost));
+  return 0;
+}
+
 /* Temporal accumulation (srt_temporal.hip).  Reads nothing of the context but the device ordinal; the frame entry keeps
  * the histories and the previous camera in the context.  dMotion (the Motion entries) selects the motion-aware kernels;
  * null is the plain entry in every byte. */
@@ -348,6 +369,10 @@ int srtDenoise(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_
 int srtDenoiseMoments(SrtContext* ctx, const SrtDenoiseParams* d, int32_t width, int32_t height, const void* dBeauty,
                       const void* const dPlanes[4], const void* dMoments, void* dOut, void* dRgba, void* stream) {
   SRT_GUARDED(ctx, srtDenoiseImpl(ctx, d, width, height, dBeauty, dPlanes, dOut, dRgba, stream, true, dMoments));
+}
+int srtTestDenoiseScratch(SrtContext* ctx, int32_t width, int32_t height, float* hGuide4, float* hCol0_4, float* hCol1_4,
+                          float* hGrad2) {
+  SRT_GUARDED(ctx, srtTestDenoiseScratchImpl(ctx, width, height, hGuide4, hCol0_4, hCol1_4, hGrad2));
 }
 int srtTemporalAccumulate(SrtContext* ctx, const SrtTemporalParams* t, int32_t width, int32_t height, const void* dBeauty,
                           const void* dMoments, const void* const dPlanes[4], const SrtCamera* cam, const SrtCamera* prevCam,

@@ -46,7 +46,8 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtLastKernelMs", "srtGetStats", "srtDeviceInfo"]
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
-                "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum"]
+                "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
+                "srtTestDenoiseScratch"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -133,6 +134,7 @@ lib.srtCommDestroy.argtypes = [_vp]
 lib.srtScatterRays.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp]
 lib.srtScatterRaysForm.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_uint64, C.c_int32, _vp, _vp]
 lib.srtTestChunkSum.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
+lib.srtTestDenoiseScratch.argtypes = [_vp, C.c_int32, C.c_int32] + [C.POINTER(C.c_float)] * 4
 lib.srtSetTunable.argtypes = [_vp, C.c_char_p, C.c_int32]
 lib.srtGetTunable.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_int32)]
 lib.srtGetShadeProfile.argtypes = [_vp, _vp]
@@ -405,6 +407,17 @@ class Context:
         else:
             self._check(lib.srtDenoiseMoments(self.h, C.byref(dparams), int(width), int(height), d_beauty_ptr, arr,
                                               d_moments_ptr, d_out_ptr, d_rgba_ptr, stream))
+
+    def denoise_scratch(self, width, height):
+        """srtTestDenoiseScratch (include/srt_hip_test.h): what the last denoise of a width x height image left in the
+        context's scratch.  Returns (guide, col0, col1, grad): (H, W, 4) {n.xyz, z}, two (H, W, 4) {e.rgb, v}, (H, W, 2)
+        float32; after k + 1 levels col[k & 1] holds {e, v} after k levels."""
+        guide, col0, col1 = (np.zeros((height, width, 4), np.float32) for _ in range(3))
+        grad = np.zeros((height, width, 2), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtTestDenoiseScratch(self.h, int(width), int(height), guide.ctypes.data_as(fp), col0.ctypes.data_as(fp),
+                                              col1.ctypes.data_as(fp), grad.ctypes.data_as(fp)))
+        return guide, col0, col1, grad
 
     def render_denoised(self, params, dparams=None):
         """Beauty render, feature pass and denoiser of one frame (srtRenderDenoisedImage).  Returns (accum, denoised, rgba):

@@ -2,7 +2,11 @@
 
 It follows the header's math operation by operation and sums the taps in the kernel's order (rows outer, columns inner);
 the kernel differs only where it evaluates exp and the normal power with the hardware's v_exp_f32 / v_log_f32 and
-divides by a reciprocal."""
+divides by a reciprocal.  The header's underflow rule is `_exp`: an exponential below 2^-126 counts as 0.
+
+tests/denoise_f64.py states the same formulas in float64, written from the header alone; tests/test_denoise_ref.py holds
+this file to it.  `denoise(..., intermediates={})` fills the dict with what the kernel keeps between its passes (the scratch
+srtTestDenoiseScratch reads back): hit, n, z, grad and levels[k] = (valid, e, v) after k levels, k = 0 .. iterations."""
 import numpy as np
 
 F = np.float32
@@ -10,6 +14,15 @@ H5 = np.array([1, 4, 6, 4, 1], F) / F(16)
 K3 = np.array([0.25, 0.5, 0.25], F)
 ALBEDO_MIN, DEPTH_EPS, LUM_EPS = F(1e-3), F(1e-3), F(1e-10)
 DEFAULTS = dict(iterations=5, sigma_l=4.0, sigma_n=16.0, sigma_z=1.0)
+
+
+TINY = np.finfo(F).tiny  # 2^-126
+
+
+def _exp(t):
+    """exp(t) in float32, 0 where the result is below the normal range (the hardware exponential returns no denormals)."""
+    x = np.exp(t)
+    return np.where(x < TINY, F(0), x).astype(F)
 
 
 def mean(plane):
@@ -67,8 +80,11 @@ class _Guide:
         return ok, t.astype(F)
 
 
-def denoise(beauty, normal, depth, albedo=None, iterations=0, demodulate=False, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0):
+def denoise(beauty, normal, depth, albedo=None, iterations=0, demodulate=False, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0,
+            v0=None, intermediates=None):
     """beauty, normal, depth, albedo: (H, W, 4) float32 image-order sums with counts.  A parameter of 0 takes its default.
+    v0: a per-pixel override of the level-0 variance, NaN where the spatial estimate stays (denoise_moments_ref).
+    intermediates: a dict to fill (see above).
     Returns (out, rgba): (H, W, 4) float32, rgb = the denoised mean, w = the beauty count; (H, W, 4) uint8."""
     iterations = iterations or DEFAULTS["iterations"]
     sigma_l, sigma_n, sigma_z = (F(s or DEFAULTS[k]) for s, k in ((sigma_l, "sigma_l"), (sigma_n, "sigma_n"), (sigma_z, "sigma_z")))
@@ -90,12 +106,17 @@ def denoise(beauty, normal, depth, albedo=None, iterations=0, demodulate=False, 
                 ok, t = g.log_weight(dx, dy, sigma_n, sigma_z)
                 lq, _ = _shift(el, dx, dy, F(0))
                 vq, _ = _shift(valid, dx, dy, False)
-                w = np.where(ok & vq, np.exp(t), F(0))
+                w = np.where(ok & vq, _exp(t), F(0))
                 dl = lq - l0
                 sw, s1, s2 = sw + w, s1 + w * dl, s2 + w * (dl * dl)
         m1, m2 = s1 / np.where(sw > 0, sw, F(1)), s2 / np.where(sw > 0, sw, F(1))
         v = np.where(sw > 0, m2 - m1 * m1, F(0))
         v = np.where(v > 0, v, F(0)).astype(F)
+        if v0 is not None:
+            v0 = np.asarray(v0, F)
+            v = np.where(np.isnan(v0), v, v0).astype(F)
+        if intermediates is not None:
+            intermediates.update(hit=g.hit, n=g.n, z=g.z, grad=np.stack(g.grad, -1), levels=[(valid, e, v)])
         for lv in range(iterations):
             s = 1 << lv
             gs, ks = np.zeros_like(v), np.zeros_like(v)
@@ -117,12 +138,14 @@ def denoise(beauty, normal, depth, albedo=None, iterations=0, demodulate=False, 
                     vq, _ = _shift(v, dx * s, dy * s, F(0))
                     qv, _ = _shift(valid, dx * s, dy * s, False)
                     al = np.where(valid, np.abs(lp - lum(eq)) / den, F(0))
-                    w = np.where(ok & qv, (H5[dx + 2] * H5[dy + 2]) * np.exp(t - al), F(0)).astype(F)
+                    w = np.where(ok & qv, (H5[dx + 2] * H5[dy + 2]) * _exp(t - al), F(0)).astype(F)
                     sw, se, sv = sw + w, se + w[..., None] * (eq - ep), sv + (w * w) * vq
             valid = sw > 0
             d = np.where(valid, sw, F(1))
             e = np.where(valid[..., None], ep + se / d[..., None], F(0)).astype(F)
             v = np.where(valid, sv / d / d, F(0)).astype(F)
+            if intermediates is not None:
+                intermediates["levels"].append((valid, e, v))
         rgb = np.where(valid[..., None], e * at, F(0)).astype(F)
         out = np.concatenate([rgb, cnt[..., None]], axis=-1).astype(F)
         q = F(256) * np.clip(np.sqrt(rgb), F(0), F(0.999))

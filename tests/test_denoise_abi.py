@@ -53,6 +53,18 @@ def test_denoise_ctypes_prototypes_match_header(dev, abi):
         assert name in dev.EXPORTS
 
 
+def test_denoise_scratch_hook_is_a_test_entry(dev, abi):
+    """srtTestDenoiseScratch (include/srt_hip_test.h): the ctypes prototype against the declaration; not an export of the
+    drop-in boundary; without a context it fails instead of reading anything."""
+    assert "srtTestDenoiseScratch" in abi_header.declarations("srt_hip_test.h")
+    assert len(abi_header.assert_prototype(dev, abi, "srtTestDenoiseScratch")) == 7
+    assert "srtTestDenoiseScratch" in dev.TEST_EXPORTS and "srtTestDenoiseScratch" not in dev.EXPORTS
+    buf = np.full(16, 7.0, np.float32)
+    assert dev.lib.srtTestDenoiseScratch(None, 2, 2, buf.ctypes.data_as(C.POINTER(C.c_float)), None, None, None) != 0
+    assert (buf == 7.0).all()
+    assert callable(getattr(dev.Context, "denoise_scratch", None))
+
+
 def test_host_layer_compiles_with_denoise_call(tmp_path, dev):
     """srt/device.h's rtFrameDenoised and the example's --denoise path build against the header and the library."""
     host = os.path.join(ROOT, "sexy-raytracer_amd", "host")
