@@ -5,7 +5,7 @@
 //
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
 //                  [--denoise FILE.png [--sample-variance]] [--adaptive THRESHOLD --max-spp N]
-//                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]] [--frames N --spin DEG [--temporal --motion [PREFIX]]]
+//                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]] [--frames N --spin DEG [--tree-cost] [--temporal --motion [PREFIX]]]
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
@@ -27,6 +27,9 @@
 //                     second upload: the trees keep their shape and get new boxes); every frame is rendered on its own
 //                     (rtFrame, samples from 0) to NAME_%03d.png.  Not with --temporal alone: the reprojection assumes a
 //                     static scene
+//   --frames N --spin D --tree-cost  also reports, after each frame's refit (for frame 0: after the upload), the surface-area
+//                     cost of the first world item's tree (hipDevice::treeCost) as "frame K tree cost X" on stderr: how
+//                     far the motion has inflated the boxes, which is what a caller decides on a rebuild by
 //   --frames N --spin D --temporal --motion [PREFIX]  motion tracking (hipDevice::setMotionTracking): the previous frame's
 //                     geometry stays on the device and every frame is a temporal frame (rtFrameTemporal, samples from k *
 //                     spp) whose reprojection follows the turning model; reports the pixels that accepted history.
@@ -103,11 +106,16 @@ int main(int argc, char** argv) {
   int frames = 0;        // > 0: a sequence, NAME_%03d.png
   float orbit = 0.0f;    // degrees the eye turns about the lookAt point's vertical axis over the sequence
   float spin = 0.0f;     // degrees per frame the model's triangles turn about the vertical axis
-  bool spinning = false, motion = false;
+  bool spinning = false, motion = false, treeCost = false;
   std::string motionPrefix;
   for (int i = 1; i < argc; i += 2) {
     if (!strcmp(argv[i], "--sample-variance") || !strcmp(argv[i], "--temporal") || !strcmp(argv[i], "--guide-all-samples")) {
       (argv[i][2] == 't' ? temporal : argv[i][2] == 'g' ? guideAll : sampleVariance) = true;  // the flags without a value
+      --i;
+      continue;
+    }
+    if (!strcmp(argv[i], "--tree-cost")) {
+      treeCost = true;
       --i;
       continue;
     }
@@ -145,6 +153,10 @@ int main(int argc, char** argv) {
   }
   if (spinning && frames < 1) {
     std::cerr << "ERROR: --spin needs --frames N\n";
+    return 1;
+  }
+  if (treeCost && !spinning) {
+    std::cerr << "ERROR: --tree-cost goes with --spin\n";
     return 1;
   }
   const float aspect = 16.0f / 9.0f;
@@ -186,6 +198,11 @@ int main(int argc, char** argv) {
               t.p[v][2] = c * z - s * x;
             }
           if (!device.updateTriangles(0, moved) || !device.refit()) return 1;
+        }
+        if (treeCost) {
+          double cost = 0.0;
+          if (!device.treeCost(0, cost)) return 1;
+          std::cerr << "frame " << k << " tree cost " << cost << "\n";
         }
         if (motion) {
           SrtTemporalStats st{};

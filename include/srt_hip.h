@@ -763,7 +763,7 @@ int srtRenderTemporalAdaptiveGuidedFrame(SrtContext* ctx, const SrtRenderParams*
  *   FAITHFUL  after a refit FAITHFUL traversal means: bvh.h:97-105 on the UPLOADED topology with the new boxes -- what the
  *             reference's bvhNode::hit does on a tree whose boxes were recomputed -- not what a freshly constructed bvhNode
  *             over the moved primitives would do (its median splits would sort differently).  CLOSEST results do not
- *             depend on the tree; its speed does, see DESIGN.md 5.13 on when to upload again instead.
+ *             depend on the tree; its speed does, see srtRebuildScene / srtGetTreeCost below and DESIGN.md 5.16.
  *   history   srtRefitScene drops the context's temporal history exactly as srtUploadScene does (the next
  *             srtRenderTemporalFrame is a first frame): the reprojection assumes static surfaces.  (srtSetMotionTracking,
  *             below, keeps it.)
@@ -778,6 +778,53 @@ int srtUpdateSpheres(SrtContext* ctx, int32_t first, int32_t count, const SrtSph
 int srtUpdateTrianglesDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dTriangles, void* stream);
 int srtUpdateSpheresDevice(SrtContext* ctx, int32_t first, int32_t count, const void* dSpheres, void* stream);
 int srtRefitScene(SrtContext* ctx, void* stream);
+
+/* Rebuilding: srtRefitScene, except that every world item whose tree srtUploadScene built on the device (SRT_BUILDER_LBVH
+ * or SRT_BUILDER_PLOC without caller-supplied nodes) gets its tree built ANEW from the current primitive records, by the
+ * same builder, into the same node slots (a device-built item has max(count - 1, 1) nodes whatever its topology).  So a
+ * scene can move indefinitely without leaving the device, and srtGetTreeCost tells when a rebuild is due.
+ *
+ * srtRebuildScene   host-built and caller-supplied trees are refitted exactly as srtRefitScene refits them (constructing
+ *             the reference's tree needs the host generator and std::sort, and stays an upload).
+ *   result    after the call the node records of every device-built item (boxes and reference words), nodeAxis, the pair
+ *             records, srtGetBvhDepth, the stack depth the kernels size their stacks by and the fast-division certificate
+ *             equal, bit for bit, what srtUploadScene of a scene description holding the current geometry leaves: updated
+ *             records are an upload's bit for bit, the builders read nothing but records and the item's primitive list,
+ *             and their sort keys are unique.  The depths are the maxima over the host-built trees, as the upload had
+ *             them before its device builds, and the new trees': they can grow as well as shrink.
+ *   radius    PLOC's search radius is the ploc_radius tunable AS READ AT THE UPLOAD (like fast_div), not its current value.
+ *   derived   as after srtRefitScene, and on the new topology: the refit's parent links are made again, the pair records
+ *             and the certificate are recomputed over the whole node array, srtGetBvh reads the new trees back.
+ *   ordering  the work is ordered behind `stream` -- the stream the updates went to -- and has FINISHED when the call
+ *             returns.  (The builders are blocking and work on the NULL stream: the call waits for `stream` first.)
+ *   history   a rebuild counts exactly as a refit: it takes srtSetMotionTracking's snapshot if no update preceded it, with
+ *             tracking on it keeps the temporal history and counts as one refit, with tracking off it drops the history.
+ *             The motion pass reads records, not trees, so a history survives one rebuild as it survives one refit.
+ *   no device-built item   srtRefitScene, in every byte of device state.
+ *   no update since the last refit   the call still rebuilds; the result is the same (idempotent).
+ *   untouched what srtRefitScene leaves, the ploc_radius tunable included; the primitive records and their device order.
+ *   errors    no scene uploaded; a failed build or launch, after which the scene counts as updated: render entries refuse
+ *             until a rebuild has succeeded.
+ * Device memory: the upload keeps every device-built item's primitive list (4 bytes per primitive of those items) until
+ * the next srtUploadScene or srtDestroy, whether or not a rebuild ever follows; a build's own work area is allocated and
+ * freed inside the call, as at the upload.
+ *
+ * srtGetTreeCost   the surface-area cost of world item `item`'s tree as it stands (after the upload, a refit or a rebuild):
+ *             the sum of its node boxes' areas over the root's.  A tree whose boxes a refit has inflated costs more than
+ *             the tree a rebuild gives; the ratio of the two is what a caller decides by.  Blocking; a streaming reduction
+ *             over the item's node records on the device (32 B per node).  Defined exactly (tests/tree_cost_ref.py
+ *             evaluates this text in NumPy float64 bit for bit):
+ *   node i    of the item, in node order, its float32 box widened to double: dx = (double)max.x - (double)min.x, dy, dz
+ *             likewise; a_i = (dx dy + dy dz) + dz dx, IEEE double, no contraction.
+ *   sum       S = the pairwise sum of a_0 .. a_(n-1) padded with +0.0 to the next power of two: level by level element k
+ *             becomes x[2k] + x[2k+1].  No floating-point atomics: S does not depend on any order of arrival.
+ *   result    *cost = S / a_0 (node 0 is the item's root for every builder), an IEEE double division.  A root of zero
+ *             area gives what the division gives (inf or NaN), not an error.  An item of one node costs 1.
+ *   errors    (*cost untouched) no scene uploaded; geometry updated and not yet refitted or rebuilt; `item` out of range
+ *             or not SRT_WORLD_BVH; a NULL cost.
+ *   side effects   none, beyond a work area of the context's (16 bytes per 256 nodes of the largest item asked about). */
+int srtRebuildScene(SrtContext* ctx, void* stream);
+int srtGetTreeCost(SrtContext* ctx, int32_t item, double* cost);
 
 /* Motion: the temporal history kept across a refit.  Opt-in; with tracking off (the default) every entry above behaves as
  * written there, srtRefitScene dropping the history included.

@@ -108,6 +108,32 @@ int checkSceneReady(SrtContext* ctx, const char* what) {
   return 0;
 }
 
+// Every device-built item's tree from the current primitive records into its node slots, and the scene's depths: the
+// maxima over the host-built trees' and these.  Blocking (the builders work on the null stream and read their depth
+// back).  srtUploadScene's builds and srtRebuildScene's are this one function.
+int buildDeviceTrees(SrtContext* ctx) {
+  Upload& up = ctx->upload;
+  DevScene& s = up.scene;
+  int stackDepth = up.hostStackDepth, bvhDepth = up.hostBvhDepth;
+  for (size_t k = 0; k < up.deviceBuilds.size(); ++k) {
+    const DeviceBuild& b = up.deviceBuilds[k];
+    const int32_t* refs = up.buildRefs[k].get<int32_t>();
+    const int n = (int)(up.buildRefs[k].bytes() / sizeof(int32_t));
+    int depth = 0;
+    const int rc = b.builder == SRT_BUILDER_PLOC
+                       ? srt_ploc_build(&s, refs, n, b.time0, b.time1, const_cast<float4*>(s.nodes), const_cast<uint8_t*>(s.nodeAxis),
+                                        b.base, up.plocRadius, &depth)
+                       : srt_lbvh_build(&s, refs, n, b.time0, b.time1, const_cast<float4*>(s.nodes), const_cast<uint8_t*>(s.nodeAxis),
+                                        b.base, &depth);
+    if (rc) return fail(ctx, "device BVH build of world item %d failed: %s", b.item, hipGetErrorString((hipError_t)rc));
+    stackDepth = std::max(stackDepth, depth);
+    bvhDepth = std::max(bvhDepth, depth);
+  }
+  s.stackDepth = stackDepth;
+  up.bvhDepth = bvhDepth;
+  return 0;
+}
+
 static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   if (!ctx || !d) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -140,23 +166,20 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   s.texelBytes = (int32_t)h.texels.size();
   s.fastDivScene = h.fastDivScene;
   ctx->upload.bvhDepth = h.bvhDepth;
-  // device-built trees (srt_lbvh.hip) into the node slots the flattening reserved
+  // device-built trees (srt_lbvh.hip) into the node slots the flattening reserved.  Their refs stay on the device for
+  // srtRebuildScene (buildDeviceTrees)
+  ctx->upload.hostStackDepth = h.stackDepth;
+  ctx->upload.hostBvhDepth = h.bvhDepth;
+  ctx->upload.plocRadius = ctx->tun.plocRadius;
   for (DeviceBuild& b : h.deviceBuilds) {
     DeviceBuffer refs;
     HIP_OK(ctx, refs.reserve(b.refs.size() * sizeof(int32_t)));
-    int rc = (int)hipMemcpy(refs.get(), b.refs.data(), b.refs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    int depth = 0;
-    if (rc == hipSuccess)
-      rc = b.builder == SRT_BUILDER_PLOC
-               ? srt_ploc_build(&s, refs.get<int32_t>(), (int)b.refs.size(), b.time0, b.time1, const_cast<float4*>(s.nodes),
-                                const_cast<uint8_t*>(s.nodeAxis), b.base, ctx->tun.plocRadius, &depth)
-               : srt_lbvh_build(&s, refs.get<int32_t>(), (int)b.refs.size(), b.time0, b.time1, const_cast<float4*>(s.nodes),
-                                const_cast<uint8_t*>(s.nodeAxis), b.base, &depth);
-    if (rc) return fail(ctx, "device BVH build of world item %d failed: %s", b.item, hipGetErrorString((hipError_t)rc));
-    s.stackDepth = std::max(s.stackDepth, depth);
-    ctx->upload.bvhDepth = std::max(ctx->upload.bvhDepth, depth);
+    HIP_OK(ctx, hipMemcpy(refs.get(), b.refs.data(), b.refs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    ctx->upload.buildRefs.push_back(std::move(refs));
     b.refs = std::vector<int32_t>();
   }
+  ctx->upload.deviceBuilds = std::move(h.deviceBuilds);
+  if (buildDeviceTrees(ctx)) return 1;
   // the closest-hit traversal's records: both children's boxes per node (srt_lbvh.hip pairNodes), built on the device
   // from the finished node array (host-built and device-built trees alike)
   float t0 = d->world[0].time0, t1 = d->world[0].time1;
@@ -171,7 +194,6 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   const int rc = srt_pair_nodes(&s, t0, t1, const_cast<float4*>(s.nodes2));
   if (rc) return fail(ctx, "pairing the node records failed: %s", hipGetErrorString((hipError_t)rc));
   ctx->upload.itemNodes = std::move(h.itemNodes);
-  ctx->upload.deviceBuilds = std::move(h.deviceBuilds);
   // what an update and a refit need of this upload (srt_refit_host.cpp)
   for (const HostTree& t : h.hostTrees) ctx->upload.trees.push_back(Upload::Tree{t.item, t.base, t.count, t.time0, t.time1, false});
   for (const DeviceBuild& b : ctx->upload.deviceBuilds) ctx->upload.trees.push_back(Upload::Tree{b.item, b.base, b.count, b.time0, b.time1, true});

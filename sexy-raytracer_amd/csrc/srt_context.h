@@ -39,7 +39,12 @@ struct Upload {
   bool haveScene = false;
   // host copies for srtGetBvh
   std::vector<std::vector<SrtBvhNode>> itemNodes;
-  std::vector<DeviceBuild> deviceBuilds;  // where the device-built trees live in scene.nodes (without their refs)
+  std::vector<DeviceBuild> deviceBuilds;  // where the device-built trees live in scene.nodes (without their host refs)
+  // srtRebuildScene builds them again as the upload did: each build's refs on the device (4 B per primitive), the PLOC
+  // radius the upload read, and the depths over the host-built trees alone, to take the maxima again
+  std::vector<DeviceBuffer> buildRefs;    // [k] belongs to deviceBuilds[k]
+  int plocRadius = 0;
+  int hostStackDepth = 0, hostBvhDepth = 0;
   std::vector<int32_t> hostTriPrimId, hostSphPrimId;
   int bvhDepth = 0;
   // srtUpdateTriangles / srtUpdateSpheres / srtRefitScene (srt_refit_host.cpp).  Every tree of the world list with its node
@@ -54,7 +59,8 @@ struct Upload {
   std::vector<int32_t> hostTriDevIndex, hostWfIndex;  // HostScene::triDevIndex, wfIndex
   std::vector<uint8_t> itemBoxesStale;                // per world item: itemNodes holds boxes from before a refit
   DeviceBuffer triDevIndex, wfIndex, refitUp, refitArrived;
-  bool refitTables = false;         // refitUp (and wfIndex) hold this scene's tables
+  bool refitTables = false;         // refitUp, refitArrived (and wfIndex) exist for this scene
+  bool refitLinksStale = false;     // refitUp is not of the current topology: srtRebuildScene has built trees since
   bool geometryDirty = false;       // an update since the last refit: nothing renders
   float pairTime0 = 0, pairTime1 = 0;  // the times the closest-hit pair records were made for
   int32_t fastDivOption = 0;        // SceneOptions::fastDiv of the upload: what fastDivScene is while the certificate holds
@@ -75,6 +81,7 @@ struct SrtContext {
   bool haveCamera = false;
   // work areas
   DeviceBuffer refitFlag, refitStage;  // srtRefitScene's certificate flag word, the host update entries' staging
+  DeviceBuffer costScratch;            // srtGetTreeCost: the partial sums of its levels
   DeviceBuffer dQueue;
   DeviceBuffer dStats;
   void* comm = nullptr;          // ncclComm_t (srt_comm.cpp)
@@ -171,6 +178,8 @@ void setImageArgs(Args& a, const SrtContext* ctx, const SrtRenderParams* p) {
 int checkParams(SrtContext* ctx, const SrtRenderParams* p);
 // "no scene uploaded", or an update that srtRefitScene has not followed: `what` names the entry.  Launches nothing.
 int checkSceneReady(SrtContext* ctx, const char* what);
+// The trees of the device-built items from the current records, and the scene's depths (srt_api.cpp).  Blocking.
+int buildDeviceTrees(SrtContext* ctx);
 int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr,
                        SrtAovRecord* aov = nullptr, int32_t aovDepth = 0, void* dMoments = nullptr,
                        const uint32_t* dList = nullptr, int32_t listTiles = 0);

@@ -38,6 +38,10 @@ int srt_launch_refit_links(const float4* nodes, int numNodes, int32_t* up, hipSt
 int srt_launch_refit_nodes(const DevScene* sc, int base, int count, float time0, float time1, const int32_t* up, int32_t* arrived,
                            int32_t* flag, int checkPrims, hipStream_t stream);
 int srt_launch_refit_derived(const DevScene* sc, const int32_t* wfIndex, int32_t* flag, hipStream_t stream);
+// srtGetTreeCost: one level of the pairwise sum each, SRT_COST_BLOCK values per workgroup (a power of two)
+#define SRT_COST_BLOCK 256
+int srt_launch_tree_cost_nodes(const float4* itemNodes, int count, double* out, hipStream_t stream);
+int srt_launch_tree_cost_partials(const double* in, int count, double* out, hipStream_t stream);
 
 // srt_features.hip, srt_features_list.hip: the kernel's workgroup size and workgroups per CU, then its launch
 int srt_features_plan(int closest, int ldsTree, size_t lds, int* block, int* perCU);

@@ -2,7 +2,8 @@
 // the primitive records rewritten from caller data, every node box refitted bottom-up over the uploaded topology, and
 // what is derived from boxes refreshed.  Topology (the reference words of every record, nodeAxis, the thread links) is
 // never written.  Records, boxes, unions and the certificate are srt_records.h's, the ones flattenScene (srt_scene.cpp)
-// calls, so a record or box carries the bits an upload of the same data gives.
+// calls, so a record or box carries the bits an upload of the same data gives.  Also srtGetTreeCost's reduction over the
+// node boxes (at the end).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -131,6 +132,48 @@ __global__ void refitDerived(const float4* nodes, int numNodes, const int32_t* w
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- tree cost
+// srtGetTreeCost (include/srt_hip.h): the pairwise sum of the node boxes' half areas.  Every workgroup owns COST_BLOCK
+// consecutive values (an aligned power-of-two range of the zero-padded array) and leaves their pairwise sum: lane 0 of a
+// wave after __shfl_down by 1, 2, .. 32 holds ((x0 + x1) + (x2 + x3)) + .., element k of a level being x[2k] + x[2k+1];
+// the waves' four partials take the same two steps through LDS.  Values past `count` are +0.0, which changes no sum (no
+// term and no partial is -0.0: x + (-x) rounds to +0.0, and of a box's three products at most two can be negative zeros).
+// No atomics: nothing depends on who arrives when.
+#define COST_BLOCK SRT_COST_BLOCK
+
+__device__ __forceinline__ double pairwiseBlockSum(double v, double* waveSums) {
+  for (int step = 1; step < 64; step <<= 1) v += __shfl_down(v, step);
+  if ((threadIdx.x & 63) == 0) waveSums[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = threadIdx.x < COST_BLOCK / 64 ? waveSums[threadIdx.x] : 0.0;
+  for (int step = 1; step < COST_BLOCK / 64; step <<= 1) v += __shfl_down(v, step);
+  return v;  // thread 0's
+}
+
+// One lane per node of the item (32 B: two 16-byte loads): a_i = (dx dy + dy dz) + dz dx in double, the float box widened
+// first.  out[block] = the block's sum; out[gridDim.x] = a_0, the root's.
+__global__ __launch_bounds__(COST_BLOCK) void treeCostNodes(const float4* nodes, int count, double* out) {
+  __shared__ double waveSums[COST_BLOCK / 64];
+  const int i = blockIdx.x * COST_BLOCK + threadIdx.x;
+  double a = 0.0;
+  if (i < count) {
+    const float4 lo = nodes[2 * (size_t)i], hi = nodes[2 * (size_t)i + 1];
+    const double dx = (double)hi.x - (double)lo.x, dy = (double)hi.y - (double)lo.y, dz = (double)hi.z - (double)lo.z;
+    a = (dx * dy + dy * dz) + dz * dx;
+    if (i == 0) out[gridDim.x] = a;
+  }
+  const double sum = pairwiseBlockSum(a, waveSums);
+  if (threadIdx.x == 0) out[blockIdx.x] = sum;
+}
+
+// The next levels: COST_BLOCK partials per workgroup
+__global__ __launch_bounds__(COST_BLOCK) void treeCostPartials(const double* in, int count, double* out) {
+  __shared__ double waveSums[COST_BLOCK / 64];
+  const int i = blockIdx.x * COST_BLOCK + threadIdx.x;
+  const double sum = pairwiseBlockSum(i < count ? in[i] : 0.0, waveSums);
+  if (threadIdx.x == 0) out[blockIdx.x] = sum;
+}
+
 inline dim3 gridFor(int n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
@@ -176,6 +219,18 @@ int srt_launch_refit_nodes(const DevScene* sc, int base, int count, float time0,
 int srt_launch_refit_derived(const DevScene* sc, const int32_t* wfIndex, int32_t* flag, hipStream_t stream) {
   hipLaunchKernelGGL(refitDerived, gridFor(sc->numNodes), dim3(256), 0, stream, sc->nodes, sc->numNodes, wfIndex,
                      const_cast<float4*>(sc->nodesWf), flag);
+  return (int)hipGetLastError();
+}
+
+// srtGetTreeCost's levels.  out: SRT_COST_BLOCK-th as many sums as values (rounded up); the node level adds the root's
+// term behind them.
+int srt_launch_tree_cost_nodes(const float4* itemNodes, int count, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(treeCostNodes, dim3((unsigned)((count + COST_BLOCK - 1) / COST_BLOCK)), dim3(COST_BLOCK), 0, stream, itemNodes, count, out);
+  return (int)hipGetLastError();
+}
+
+int srt_launch_tree_cost_partials(const double* in, int count, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(treeCostPartials, dim3((unsigned)((count + COST_BLOCK - 1) / COST_BLOCK)), dim3(COST_BLOCK), 0, stream, in, count, out);
   return (int)hipGetLastError();
 }
 

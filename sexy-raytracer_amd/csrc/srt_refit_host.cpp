@@ -1,13 +1,15 @@
 // srt_refit_host.cpp -- host side of the geometry updates (include/srt_hip.h srtUpdateTriangles / srtUpdateSpheres /
 // srtRefitScene): argument checks, the device tables an uploaded scene needs for them (made by the first call that uses
 // them, so an upload that is never updated pays nothing), and the launches of srt_refit.hip.  Also srtSetMotionTracking
-// and the snapshot of the previous epoch's records that the motion pass reads (include/srt_hip.h "Motion").
+// and the snapshot of the previous epoch's records that the motion pass reads (include/srt_hip.h "Motion"), srtRebuildScene
+// (a refit behind new device builds) and srtGetTreeCost.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "srt_context.h"
 #include "srt_launch.h"
@@ -106,45 +108,60 @@ int updateHost(SrtContext* ctx, const char* what, int32_t first, int32_t count, 
   return device(ctx, first, count, ctx->refitStage.get(), nullptr);
 }
 
-int refitScene(SrtContext* ctx, void* streamPtr) {
+// srtRefitScene, and srtRebuildScene (`rebuild`): the same, behind new trees for the device-built items
+int refitScene(SrtContext* ctx, void* streamPtr, bool rebuild) {
   if (!ctx) return 1;
-  if (!ctx->upload.haveScene) return fail(ctx, "srtRefitScene: no scene uploaded");
+  const char* const what = rebuild ? "srtRebuildScene" : "srtRefitScene";
+  if (!ctx->upload.haveScene) return fail(ctx, "%s: no scene uploaded", what);
   HIP_OK(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-  const DevScene& s = ctx->upload.scene;
-  const int n = s.numNodes;
+  const int n = ctx->upload.scene.numNodes;
   int32_t flag = 0;
   if (snapshotGeometry(ctx, stream)) return 1;  // tracking on and no update since the last refit: motion is zero
+  if (rebuild && !ctx->upload.deviceBuilds.empty()) {
+    // The builders read the records on the null stream and block: the updates' stream has to have passed them first.  A
+    // failed build leaves trees that are neither the old nor the new ones: nothing renders until a rebuild succeeds.
+    ctx->upload.geometryDirty = true;
+    HIP_OK(ctx, hipStreamSynchronize(stream));
+    if (buildDeviceTrees(ctx)) return 1;
+    ctx->upload.refitLinksStale = true;
+  }
+  const DevScene& s = ctx->upload.scene;  // (read after the builds: they set its stack depth)
   if (n > 0) {
     if (!ctx->upload.refitTables) {
-      // once per upload: the parent links, and the hybrid records' renumbering
+      // once per upload: the parent links' and counters' memory, and the hybrid records' renumbering
       HIP_OK(ctx, ctx->upload.refitUp.reserve((size_t)n * sizeof(int32_t)));
       HIP_OK(ctx, ctx->upload.refitArrived.reserve((size_t)n * sizeof(int32_t)));
       HIP_OK(ctx, ctx->refitFlag.reserve(16));
       if (s.nodesWf) {
-        if (ctx->upload.hostWfIndex.size() != (size_t)n) return fail(ctx, "srtRefitScene: the hybrid records have no renumbering");
+        if (ctx->upload.hostWfIndex.size() != (size_t)n) return fail(ctx, "%s: the hybrid records have no renumbering", what);
         HIP_OK(ctx, ctx->upload.wfIndex.reserve((size_t)n * sizeof(int32_t)));
         HIP_OK(ctx, hipMemcpy(ctx->upload.wfIndex.get(), ctx->upload.hostWfIndex.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
       }
+      ctx->upload.refitTables = ctx->upload.refitLinksStale = true;
+    }
+    if (ctx->upload.refitLinksStale) {
+      // the parent links: once per topology, that is per upload and per rebuild (over the whole array: one pass over the
+      // reference words, next to a build's dozens)
       const int e = srt_launch_refit_links(s.nodes, n, ctx->upload.refitUp.get<int32_t>(), stream);
-      if (e) return fail(ctx, "srtRefitScene: launch failed: %s", hipGetErrorString((hipError_t)e));
-      ctx->upload.refitTables = true;
+      if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+      ctx->upload.refitLinksStale = false;
     }
     HIP_OK(ctx, hipMemsetAsync(ctx->upload.refitArrived.get(), 0, (size_t)n * sizeof(int32_t), stream));
     HIP_OK(ctx, hipMemsetAsync(ctx->refitFlag.get(), 0, 16, stream));
     int e = 0;
     for (const Upload::Tree& t : ctx->upload.trees) {
-      if (t.base < 0 || t.count < 1 || t.base + t.count > n) return fail(ctx, "srtRefitScene: world item %d lies outside the node array", t.item);
+      if (t.base < 0 || t.count < 1 || t.base + t.count > n) return fail(ctx, "%s: world item %d lies outside the node array", what, t.item);
       e = srt_launch_refit_nodes(&s, t.base, t.count, t.time0, t.time1, ctx->upload.refitUp.get<const int32_t>(), ctx->upload.refitArrived.get<int32_t>(),
                                  ctx->refitFlag.get<int32_t>(), t.deviceBuilt ? 1 : 0, stream);
       if (e) break;
     }
     if (!e) e = srt_launch_refit_derived(&s, s.nodesWf ? ctx->upload.wfIndex.get<const int32_t>() : nullptr, ctx->refitFlag.get<int32_t>(), stream);
     if (!e) e = srt_pair_nodes_async(&s, ctx->upload.pairTime0, ctx->upload.pairTime1, const_cast<float4*>(s.nodes2), stream);
-    if (e) return fail(ctx, "srtRefitScene: launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
     HIP_OK(ctx, hipMemcpyAsync(&flag, ctx->refitFlag.get(), sizeof flag, hipMemcpyDeviceToHost, stream));
   }
-  if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "srtRefitScene: kernel failed: %s", hipGetErrorString(hipGetLastError()));
+  if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "%s: kernel failed: %s", what, hipGetErrorString(hipGetLastError()));
   ctx->upload.scene.fastDivScene = flag == 0 ? ctx->upload.fastDivOption : 0;
   // Without tracking, as srtUploadScene: the reprojection assumes the surfaces of the history's frame.  With it, the history
   // stays and srtRenderTemporalFrame decides by the count of refits since its last frame (srt_frames.cpp)
@@ -156,6 +173,43 @@ int refitScene(SrtContext* ctx, void* streamPtr) {
   }
   std::fill(ctx->upload.itemBoxesStale.begin(), ctx->upload.itemBoxesStale.end(), (uint8_t)1);
   ctx->upload.geometryDirty = false;
+  return 0;
+}
+
+// srtGetTreeCost.  The device takes the pairwise sum down to at most SRT_COST_BLOCK partials, level by level between two
+// halves of the scratch; the host finishes over the copied partials in the same order and divides by the root's term.
+int treeCost(SrtContext* ctx, int32_t item, double* cost) {
+  if (!ctx) return 1;
+  if (checkSceneReady(ctx, "srtGetTreeCost")) return 1;
+  if (!cost) return fail(ctx, "srtGetTreeCost: null cost");
+  if (item < 0 || item >= ctx->upload.scene.numWorld) return fail(ctx, "srtGetTreeCost: item %d out of range", item);
+  const auto t = std::find_if(ctx->upload.trees.begin(), ctx->upload.trees.end(), [&](const Upload::Tree& x) { return x.item == item; });
+  if (t == ctx->upload.trees.end()) return fail(ctx, "srtGetTreeCost: item %d is not a bvh", item);
+  if (t->base < 0 || t->count < 1 || t->base + t->count > ctx->upload.scene.numNodes) return fail(ctx, "srtGetTreeCost: world item %d lies outside the node array", item);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  auto blocks = [](int values) { return (values + SRT_COST_BLOCK - 1) / SRT_COST_BLOCK; };
+  int have = blocks(t->count);
+  const size_t half = (size_t)have + 1;  // the first level's sums and the root's term behind them
+  HIP_OK(ctx, ctx->costScratch.reserve(2 * half * sizeof(double)));
+  double* cur = ctx->costScratch.get<double>();
+  double* other = cur + half;
+  const double* const rootTerm = cur + have;
+  int e = srt_launch_tree_cost_nodes(ctx->upload.scene.nodes + 2 * (size_t)t->base, t->count, cur, nullptr);
+  while (!e && have > SRT_COST_BLOCK) {
+    e = srt_launch_tree_cost_partials(cur, have, other, nullptr);  // (never reaches the root's term: blocks(have) < have)
+    have = blocks(have);
+    std::swap(cur, other);
+  }
+  if (e) return fail(ctx, "srtGetTreeCost: launch failed: %s", hipGetErrorString((hipError_t)e));
+  size_t width = 1;
+  while (width < (size_t)have) width *= 2;
+  std::vector<double> x(width, 0.0);
+  double root = 0.0;
+  HIP_OK(ctx, hipMemcpy(x.data(), cur, (size_t)have * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_OK(ctx, hipMemcpy(&root, rootTerm, sizeof root, hipMemcpyDeviceToHost));
+  for (; width > 1; width /= 2)
+    for (size_t k = 0; k < width / 2; ++k) x[k] = x[2 * k] + x[2 * k + 1];
+  *cost = x[0] / root;
   return 0;
 }
 
@@ -175,7 +229,9 @@ int srtUpdateTriangles(SrtContext* ctx, int32_t first, int32_t count, const SrtT
 int srtUpdateSpheres(SrtContext* ctx, int32_t first, int32_t count, const SrtSphereIn* hSpheres) {
   SRT_GUARDED(ctx, updateHost(ctx, "srtUpdateSpheres", first, count, ctx ? ctx->upload.scene.numSpheres : 0, hSpheres, sizeof(SrtSphereIn), updateSpheresDevice));
 }
-int srtRefitScene(SrtContext* ctx, void* stream) { SRT_GUARDED(ctx, refitScene(ctx, stream)); }
+int srtRefitScene(SrtContext* ctx, void* stream) { SRT_GUARDED(ctx, refitScene(ctx, stream, false)); }
+int srtRebuildScene(SrtContext* ctx, void* stream) { SRT_GUARDED(ctx, refitScene(ctx, stream, true)); }
+int srtGetTreeCost(SrtContext* ctx, int32_t item, double* cost) { SRT_GUARDED(ctx, treeCost(ctx, item, cost)); }
 int srtSetMotionTracking(SrtContext* ctx, int32_t enable) { SRT_GUARDED(ctx, setMotionTracking(ctx, enable)); }
 
 }  // extern "C"

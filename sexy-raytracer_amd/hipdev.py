@@ -40,6 +40,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderFeatureTileList", "srtRenderAdaptiveGuided", "srtRenderAdaptiveDenoisedImage",
            "srtRenderTemporalAdaptiveGuided", "srtRenderTemporalAdaptiveGuidedFrame",
            "srtUpdateTriangles", "srtUpdateSpheres", "srtUpdateTrianglesDevice", "srtUpdateSpheresDevice", "srtRefitScene",
+           "srtRebuildScene", "srtGetTreeCost",
            "srtSetMotionTracking", "srtRenderMotionTiles", "srtRenderMotionImage", "srtTemporalAccumulateMotion",
            "srtTemporalReprojectMotion",
            "srtCommGetUniqueId", "srtCommInit", "srtGatherTiles", "srtRenderImageRanks", "srtCommDestroy",
@@ -118,6 +119,8 @@ lib.srtRenderTemporalAdaptiveGuidedFrame.argtypes = lib.srtRenderTemporalAdaptiv
 lib.srtUpdateTriangles.argtypes = lib.srtUpdateSpheres.argtypes = [_vp, C.c_int32, C.c_int32, _vp]
 lib.srtUpdateTrianglesDevice.argtypes = lib.srtUpdateSpheresDevice.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
 lib.srtRefitScene.argtypes = [_vp, _vp]
+lib.srtRebuildScene.argtypes = [_vp, _vp]
+lib.srtGetTreeCost.argtypes = [_vp, C.c_int32, _vp]  # double* cost (an address, like the other untyped outputs)
 lib.srtSetMotionTracking.argtypes = [_vp, C.c_int32]
 lib.srtRenderMotionTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp]
 lib.srtRenderMotionImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.POINTER(C.c_float)]
@@ -609,6 +612,19 @@ class Context:
         """srtRefitScene: every node box from the current primitive records, and what is derived from boxes; the topology
         stays.  Blocking.  Drops the temporal history unless motion tracking is on."""
         self._check(lib.srtRefitScene(self.h, stream))
+
+    def rebuild(self, stream=None):
+        """srtRebuildScene: refit(), except that every tree the upload built on the device (LBVH, PLOC) is built anew from
+        the current primitive records, as an upload of the moved scene would build it; PLOC's radius is the upload's.
+        Blocking; ordered behind `stream`.  Counts as a refit for the temporal history."""
+        self._check(lib.srtRebuildScene(self.h, stream))
+
+    def tree_cost(self, item=0):
+        """srtGetTreeCost: the sum of world item `item`'s node box areas over its root's, a float64 defined bit for bit
+        (include/srt_hip.h).  Compare the value after a refit with the value at the build to decide on a rebuild()."""
+        cost = C.c_double(0.0)
+        self._check(lib.srtGetTreeCost(self.h, int(item), C.byref(cost)))
+        return cost.value
 
     def set_motion_tracking(self, enable=True):
         """srtSetMotionTracking: keep the geometry of the previous refit (48 B per triangle and per sphere) so that

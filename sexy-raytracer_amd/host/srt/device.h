@@ -21,6 +21,9 @@
 //                                           primitives of the uploaded scene (`triangles` keeps what init uploaded, in the
 //                                           scene's order), then every tree's boxes refitted on the device
 //                                           (include/srt_hip.h "Moving geometry"); nothing renders between the two
+//   rebuild() / treeCost(item, cost)        srtRebuildScene / srtGetTreeCost.  This layer builds reference trees only (on
+//                                           the host), and those a rebuild refits: here rebuild() IS refit().  treeCost
+//                                           tells how far the motion has inflated an item's boxes
 //   terminate()
 //   uniqueId / initRanks                    multi-GPU: one process per GPU; rtFrame then renders this rank's
 //                                           tiles, the library gathers them with ONE ncclGather and rank 0's
@@ -71,6 +74,17 @@ class hipDevice {
   bool refit() {
     if (!ctx) return false;
     return srtRefitScene(ctx, nullptr) == 0 || error();
+  }
+  // srtRebuildScene builds the device-built trees anew; init() uploads none (every item is a reference tree built on the
+  // host), so this is a refit.  It is here for callers written against the library's moving-geometry loop.
+  bool rebuild() {
+    if (!ctx) return false;
+    return srtRebuildScene(ctx, nullptr) == 0 || error();
+  }
+  // The sum of world item `item`'s node box areas over its root's (include/srt_hip.h srtGetTreeCost), after init or refit
+  bool treeCost(int item, double& cost) {
+    if (!ctx) return false;
+    return srtGetTreeCost(ctx, item, &cost) == 0 || error();
   }
 
   // Motion tracking (include/srt_hip.h "Motion"): the geometry of the previous refit stays on the device, so that

@@ -10,10 +10,24 @@ and reported beside them the bytes the device path must move (bytes_moved: what 
 scene's counts, below) over update_refit_ms as a share of the 8 TB/s HBM peak.
 Tree quality after a refit: on soup_1m every triangle is moved rigidly by a random vector of up to a tenth of the soup's
 extent; CLOSEST Msamples/s (720p, 16 spp, srtRenderTiles kernel time) on the refit PLOC tree against a fresh PLOC build of
-the moved scene.  Prints one JSON line.
+the moved scene.
+Rebuilding (--rebuild-cases, PLOC soups): every triangle is moved rigidly by a random vector, uniform in a ball whose
+radius sweeps from a hundredth of the soup's extent to the whole extent (--displacements); per amount, on the same moved scene,
+  update_refit_ms / update_rebuild_ms / upload_ms   device records + srtRefitScene, the same + srtRebuildScene, and
+                        srtUploadScene of the moved scene, clocked as above
+  cost_*                srtGetTreeCost at the upload of the unmoved scene, after the refit, after the rebuild and after the
+                        fresh upload (the last two are equal bit for bit)
+  msamples_* / frame_ms_*   CLOSEST 720p 16 spp (srtRenderTiles kernel time) on the refitted, the rebuilt and the freshly
+                        uploaded tree
+and `rebuild_pays_from_cost_ratio`: the smallest cost_refit / cost_at_build of the sweep at which update + rebuild + one
+frame takes less than update + refit + one frame (null if at none).  A refitted tree whose frame takes longer than
+--frame-budget-ms is rendered once, and not at all for the larger displacements (null; the rebuild pays there a fortiori).
+Prints one JSON line.
 
 usage: python tools/refit_bench.py [--steps 10] [--warmup 2] [--upload-steps 2] [--cases soup_200k,soup_1m,soup_4m,masterchief]
-                                   [--no-quality]"""
+                                   [--no-quality] [--rebuild-cases soup_200k,soup_1m,soup_4m]
+                                   [--displacements 0.01,0.03,0.1,0.3,1.0] [--rebuild-steps 3]
+                                   [--frame-budget-ms 2000]"""
 import argparse
 import copy
 import importlib
@@ -144,6 +158,71 @@ def quality(ctx, W=1280, H=720, spp=16):
             "images_equal_bits": bool(torch.equal(img_refit.view(torch.int32), img_fresh.view(torch.int32)))}
 
 
+SOUP_EXTENT = 12.0  # scene(): centres over 2 * extent on x and z
+
+
+def displaced(tri, fraction, seed=1):
+    """Every triangle moved rigidly by a random vector, uniform in a ball of radius fraction * SOUP_EXTENT."""
+    rng = np.random.default_rng(seed)
+    v = rng.normal(size=(len(tri), 1, 3))
+    v *= (rng.random((len(tri), 1, 1)) ** (1 / 3)) * fraction * SOUP_EXTENT / np.linalg.norm(v, axis=-1, keepdims=True)
+    moved = tri.copy()
+    moved["p"] += v.astype(F)
+    return moved
+
+
+def rebuild_sweep(ctx, case, fractions, steps, upload_steps, budget_ms, W=1280, H=720, spp=16):
+    sb = scene(case)
+    tri = np.concatenate(sb.triangles)
+    cam = dev.make_camera(abi.default_camera_params())
+    p = abi.default_render_params(W, H, spp, 4, seed=3, traversal=abi.SRT_TRAVERSE_CLOSEST, spp_chunks=0)
+    tiles = torch.zeros((dev.num_local_tiles(W, H, 1), 64, 4), dtype=torch.float32, device="cuda")
+
+    def frame():
+        """(Msamples/s, kernel ms, the tree's cost): the best of three frames after a warm-up -- or the first frame alone
+        when it took longer than --frame-budget-ms (a tree a refit has ruined renders for seconds)"""
+        ctx.set_camera(cam)
+        ms = []
+        for _ in range(4):
+            ctx.render_tiles(p, tiles.data_ptr(), None)
+            torch.cuda.synchronize()
+            ms.append(ctx.last_kernel_ms())
+            if ms[0] > budget_ms:
+                break
+        best = min(ms[1:]) if len(ms) > 1 else ms[0]
+        return W * H * spp / (best * 1e3), best, ctx.tree_cost(0)
+
+    def moving(d_records, then):
+        def fn():
+            ctx.update_triangles(0, d_records)
+            then()
+        return fn
+
+    out = {"triangles": len(tri), "sweep": []}
+    over_budget = False
+    for f in sorted(fractions):
+        moved = displaced(tri, f)
+        d_moved = torch.from_numpy(moved.view(np.uint8).reshape(-1, 64)).cuda()
+        ctx.upload_scene(sb)  # the unmoved scene's tree: what the refit keeps
+        row = {"displacement_over_extent": f, "cost_at_build": ctx.tree_cost(0)}
+        for name, then in (("refit", ctx.refit), ("rebuild", ctx.rebuild)):
+            row["update_%s_ms" % name] = wall(moving(d_moved, then), steps, 1)
+            if name == "refit" and over_budget:  # a smaller displacement's refit tree was over the budget already
+                row["msamples_refit"], row["frame_ms_refit"], row["cost_refit"] = None, None, ctx.tree_cost(0)
+                continue
+            row["msamples_" + name], row["frame_ms_" + name], row["cost_" + name] = frame()
+        row["upload_ms"] = wall(lambda: ctx.upload_scene(with_triangles(sb, moved)), upload_steps, 0)
+        row["msamples_upload"], row["frame_ms_upload"], row["cost_upload"] = frame()
+        row["cost_ratio"] = row["cost_refit"] / row["cost_at_build"]
+        row["rebuild_pays"] = over_budget or row["update_rebuild_ms"] + row["frame_ms_rebuild"] < row["update_refit_ms"] + row["frame_ms_refit"]
+        over_budget = over_budget or row["frame_ms_refit"] > budget_ms
+        out["sweep"].append(row)
+        del d_moved
+    pays = [r["cost_ratio"] for r in out["sweep"] if r["rebuild_pays"]]
+    out["rebuild_pays_from_cost_ratio"] = min(pays) if pays else None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -151,6 +230,10 @@ def main():
     ap.add_argument("--upload-steps", type=int, default=2)
     ap.add_argument("--cases", default="soup_200k,soup_1m,soup_4m,masterchief")
     ap.add_argument("--no-quality", action="store_true")
+    ap.add_argument("--rebuild-cases", default="soup_200k,soup_1m,soup_4m")
+    ap.add_argument("--displacements", default="0.01,0.03,0.1,0.3,1.0")
+    ap.add_argument("--rebuild-steps", type=int, default=3)
+    ap.add_argument("--frame-budget-ms", type=float, default=2000.0)
     a = ap.parse_args()
     ctx = dev.Context(0)
     res = {"device": ctx.device_info()["name"], "cases": {}}
@@ -158,6 +241,9 @@ def main():
         res["cases"][case] = case_times(ctx, case, a.steps, a.warmup, a.upload_steps)
     if not a.no_quality:
         res["quality_soup_1m"] = quality(ctx)
+    fractions = [float(x) for x in a.displacements.split(",") if x]
+    res["rebuild"] = {case: rebuild_sweep(ctx, case, fractions, a.rebuild_steps, a.upload_steps, a.frame_budget_ms)
+                      for case in a.rebuild_cases.split(",") if case}
     ctx.close()
     print(json.dumps(res))
 
