@@ -925,6 +925,51 @@ int srtRenderImage(SrtContext* ctx, const SrtRenderParams* p, float* hAccum, uin
 /* Fixed-ray-set parity entry: world.hit(r, tMin, tMax, rec) for n rays. HOST pointers. */
 int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, int32_t traversal);
 
+/* Ray queries: rays that sit in DEVICE memory -- written by a kernel or a torch op -- answered in DEVICE memory against
+ * the uploaded scene, on the caller's stream.  (srtTraceRays above stays the parity entry: host pointers, a device round
+ * trip per call, traversal counters.)
+ *
+ * srtTraceRaysDevice   the closest (or the reference's) hit of every ray.
+ * srtOccludedDevice    whether anything at all is hit ("any hit"): shadow, visibility and ambient-occlusion rays.
+ *   buffers   all DEVICE pointers.  dRays = SrtRay[n], aligned to 4 bytes (36 bytes each: a contiguous (n, 9) float32
+ *             tensor).  dHits = SrtRayHit[n], aligned to 16 bytes, may be NULL.  dRecords = SrtHit[n], aligned to 4 bytes,
+ *             may be NULL (not both): the full record as srtTraceRays fills it, its four counter fields written as 0.
+ *             dOccluded = uint8_t[n], 0 / 1.  Output elements at index >= n are never written.
+ *   async     both are asynchronous on `stream`, allocate nothing, do not synchronise and touch no scratch of the
+ *             context's: one kernel.  The buffers must stay untouched until the stream has passed the call.  They read
+ *             the trees as they stand: after the upload, a refit or a rebuild.
+ *   untouched the tunables, the host generator, the chunk scratch, srtLastKernelMs, srtGetLaunchInfo, srtGetStats, the
+ *             temporal history.
+ *   n == 0    returns 0 and launches nothing.
+ *   FAITHFUL  traversal == SRT_TRAVERSE_FAITHFUL: world.hit(r, tMin, tMax, rec) in the reference's order, exactly what
+ *             srtTraceRays returns for FAITHFUL -- every field bit for bit, except the counters, which are 0.
+ *   CLOSEST   traversal == SRT_TRAVERSE_CLOSEST: the tree-independent closest hit.  Every primitive has a CANDIDATE t for
+ *             the ray's (tMin, tMax): a triangle's t when the triangle test accepts it (model.h:104-154, and t <= tMax,
+ *             which the reference does not ask); a sphere's root as sphere.h:54-73 chooses it.  The result is the
+ *             candidate of smallest t (float <); among equal t the primitive with the LARGEST prims[] index wins.  That
+ *             is what a loop over prims[] in list order that keeps `t <= closest` returns, so the answer does not depend
+ *             on the builder, on a refit or on a rebuild.  A hit with t == tMax is a hit.
+ *   occluded  occluded[i] = 1 iff at least one primitive has a candidate for (tMin, tMax) in the CLOSEST sense: the
+ *             CLOSEST query's prim != SRT_NO_HIT, whatever order the tree is walked in.
+ *   one-sided triangles are hit from their front only, as in every render of this library (model.h:119-123): a ray that
+ *             meets a triangle's back passes through, for the closest hit and for occlusion alike.
+ *   condition the ray's `time` lies inside [time0, time1] of every world item (a box bounds a moving sphere only over its
+ *             item's range: the reference's own contract); o is finite, d is finite and non-zero.  Otherwise the result
+ *             is unspecified, but the call still terminates and writes element i only.
+ *   errors    (non-zero, message in srtLastError, NOTHING launched, outputs untouched; all decided on the host) no scene
+ *             uploaded; geometry updated and not yet refitted; n < 0; with n > 0 a NULL dRays, no output buffer or a
+ *             misaligned pointer; a traversal that is neither value; a tree so deep that the per-lane stacks of a
+ *             workgroup exceed 160 KB of LDS (1 KB per pending reference: a depth beyond 158). */
+typedef struct SrtRayHit { /* 16 bytes per ray, one dwordx4 store */
+  int32_t prim;            /* index into prims[], SRT_NO_HIT on a miss */
+  float t;                 /* 0 on a miss */
+  int32_t material;        /* -1 on a miss */
+  int32_t frontFace;       /* 0 / 1; 0 on a miss */
+} SrtRayHit;
+int srtTraceRaysDevice(SrtContext* ctx, const void* dRays, int64_t n, int32_t traversal, void* dHits, void* dRecords,
+                       void* stream);
+int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccluded, void* stream);
+
 /* material::scatter + material::emitted (material.h:15-21; texture::value through a light's emitted, texture.h:13-16) for
  * n (incoming ray, hit record) pairs, evaluated by the render kernels' own shading function.  hits[i].material indexes
  * the uploaded scene's materials; p, normal, tangent, bitangent, uv, t, frontFace are read as the reference's hitRecord

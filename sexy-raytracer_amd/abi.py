@@ -101,6 +101,10 @@ class SrtHit(C.Structure):
                 ("nodeVisits", i32), ("boxPasses", i32), ("triTests", i32), ("sphereTests", i32)]
 
 
+class SrtRayHit(C.Structure):  # srtTraceRaysDevice: 16 bytes per ray
+    _fields_ = [("prim", i32), ("t", f32), ("material", i32), ("frontFace", i32)]
+
+
 class SrtRenderParams(C.Structure):
     _fields_ = [("imageWidth", i32), ("imageHeight", i32), ("spp", i32), ("maxBounce", i32),
                 ("seed", u64), ("background", f32 * 3), ("tMin", f32), ("traversal", i32),
@@ -147,6 +151,7 @@ HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("normal",
                       ("tangent", "<f4", 3), ("bitangent", "<f4", 3), ("uv", "<f4", 2),
                       ("frontFace", "<i4"), ("material", "<i4"), ("nodeVisits", "<i4"),
                       ("boxPasses", "<i4"), ("triTests", "<i4"), ("sphereTests", "<i4")])
+RAY_HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("material", "<i4"), ("frontFace", "<i4")])
 AOV_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("time", "<f4"), ("valid", "<i4"), ("prim", "<i4"), ("t", "<f4"),
                       ("nodeVisits", "<i4"), ("boxPasses", "<i4"), ("triTests", "<i4"), ("sphereTests", "<i4"), ("pad", "<i4", 2)])
 assert AOV_DTYPE.itemsize == 64
@@ -157,6 +162,7 @@ SPHERE_DTYPE = np.dtype([("center0", "<f4", 3), ("center1", "<f4", 3), ("time0",
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("left", "<i4"), ("bmax", "<f4", 3), ("right", "<i4")])
 assert RAY_DTYPE.itemsize == C.sizeof(SrtRay)
 assert HIT_DTYPE.itemsize == C.sizeof(SrtHit)
+assert RAY_HIT_DTYPE.itemsize == C.sizeof(SrtRayHit) == 16
 assert NODE_DTYPE.itemsize == C.sizeof(SrtBvhNode) == 32
 assert C.sizeof(SrtTriangleIn) == TRIANGLE_DTYPE.itemsize == 64
 assert C.sizeof(SrtSphereIn) == SPHERE_DTYPE.itemsize == 40

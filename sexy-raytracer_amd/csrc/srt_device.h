@@ -191,6 +191,16 @@ struct TraceArgs {
   int64_t n;
 };
 
+// srtTraceRaysDevice / srtOccludedDevice (srt_query.hip): every pointer is the caller's DEVICE memory
+struct QueryArgs {
+  DevScene scene;
+  const float* rays;   // SrtRay[n] as nine floats each (4-byte aligned)
+  int4* hits;          // SrtRayHit[n], or null
+  SrtHit* records;     // SrtHit[n] with zero counters, or null
+  uint8_t* occluded;   // the any-hit form's one output
+  int64_t n;
+};
+
 // srtRenderFeatureTiles (srt_features.hip): the first hit of every camera ray the beauty render traces, as feature planes
 // in the beauty tiles' layout
 struct FeatureArgs {

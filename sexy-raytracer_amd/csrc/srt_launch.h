@@ -22,6 +22,9 @@ int srt_launch_trace(const TraceArgs* a, int traversal, int grid, size_t ldsByte
 int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hits, float* out, uint32_t* fetches, uint64_t seed,
                        int n, int form, hipStream_t stream);
 
+// srt_query.hip: mode = SRT_TRAVERSE_FAITHFUL, SRT_TRAVERSE_CLOSEST or 2 (any hit, into a->occluded)
+int srt_launch_query(const QueryArgs* a, int mode, int grid, size_t ldsBytes, hipStream_t stream);
+
 // srt_lbvh.hip: the device tree builders (blocking) and the closest-hit traversal's pair records
 int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
                    uint8_t* outAxis, int base, int* depthOut);

@@ -511,6 +511,49 @@ int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, i
   return 0;
 }
 
+// srtTraceRaysDevice / srtOccludedDevice (include/srt_hip.h "Ray queries"): every check on the host, then one launch of
+// srt_query.hip on the caller's stream.  Nothing of the context changes: no work area, no event, no plan.
+// anyHit: srtOccludedDevice (dOccluded); otherwise `traversal` selects the walk (dHits, dRecords).
+static int queryDevice(SrtContext* ctx, const char* what, const void* dRays, int64_t n, bool anyHit, int32_t traversal, void* dHits,
+                       void* dRecords, void* dOccluded, void* streamPtr) {
+  if (!ctx) return 1;
+  if (checkSceneReady(ctx, what)) return 1;
+  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
+  if (!anyHit && traversal != SRT_TRAVERSE_FAITHFUL && traversal != SRT_TRAVERSE_CLOSEST)
+    return fail(ctx, "%s: traversal %d is neither SRT_TRAVERSE_FAITHFUL nor SRT_TRAVERSE_CLOSEST", what, traversal);
+  const int mode = anyHit ? 2 : traversal;  // srt_launch_query's modes
+  if (n == 0) return 0;
+  if (!dRays) return fail(ctx, "%s: null rays", what);
+  if (anyHit ? !dOccluded : (!dHits && !dRecords)) return fail(ctx, "%s: no output buffer", what);
+  if ((uintptr_t)dRays % 4) return fail(ctx, "%s: the rays are not aligned to 4 bytes", what);
+  if ((uintptr_t)dHits % 16) return fail(ctx, "%s: the hits are not aligned to 16 bytes", what);
+  if ((uintptr_t)dRecords % 4) return fail(ctx, "%s: the records are not aligned to 4 bytes", what);
+  const DevScene& sc = ctx->upload.scene;
+  // slot 0 holds the walk's sentinel, the last slot is the spare of its unconditional store (srt_query.hip)
+  const size_t lds = (size_t)(std::max(sc.stackDepth, 1) + 2) * SRT_BLOCK * sizeof(int32_t);
+  if (lds > 160 * 1024) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  QueryArgs a;
+  a.scene = sc;
+  a.rays = static_cast<const float*>(dRays);
+  a.hits = static_cast<int4*>(dHits);
+  a.records = static_cast<SrtHit*>(dRecords);
+  a.occluded = static_cast<uint8_t*>(dOccluded);
+  a.n = n;
+  const int grid = (int)std::min<int64_t>((n + SRT_BLOCK - 1) / SRT_BLOCK, (int64_t)ctx->prop.multiProcessorCount * 8);
+  const int e = srt_launch_query(&a, mode, grid, lds, static_cast<hipStream_t>(streamPtr));
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+int srtTraceRaysDevice(SrtContext* ctx, const void* dRays, int64_t n, int32_t traversal, void* dHits, void* dRecords, void* stream) {
+  SRT_GUARDED(ctx, queryDevice(ctx, "srtTraceRaysDevice", dRays, n, false, traversal, dHits, dRecords, nullptr, stream));
+}
+
+int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccluded, void* stream) {
+  SRT_GUARDED(ctx, queryDevice(ctx, "srtOccludedDevice", dRays, n, true, 0, nullptr, nullptr, dOccluded, stream));
+}
+
 // test entries: material::scatter known answers through the kernels' own shade(), in the instance `form` selects
 // (bit 0 WIDE, bit 1 COUNT: include/srt_hip_test.h)
 

@@ -32,7 +32,7 @@ lib = C.CDLL(LIB_PATH)
 EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostRandomFloat", "srtHostRandomReset",
            "srtUploadScene", "srtSetCamera", "srtBuildBvh", "srtGetBvh", "srtGetBvhDepth", "srtNumTiles", "srtNumLocalTiles", "srtDefaultSppChunks", "srtPlanSppChunks",
            "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
-           "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtScatterRays",
+           "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtTraceRaysDevice", "srtOccludedDevice", "srtScatterRays",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
@@ -129,6 +129,8 @@ lib.srtTemporalAccumulateMotion.argtypes = [_vp, C.POINTER(abi.SrtTemporalParams
 lib.srtTemporalReprojectMotion.argtypes = [_vp, C.POINTER(abi.SrtTemporalParams), C.c_int32, C.c_int32, C.POINTER(_vp), _vp,
                                            C.POINTER(abi.SrtCamera), C.POINTER(abi.SrtCamera), _vp, _vp, _vp]
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
+lib.srtTraceRaysDevice.argtypes = [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]
+lib.srtOccludedDevice.argtypes = [_vp, _vp, C.c_int64, _vp, _vp]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
 lib.srtGatherTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
@@ -650,6 +652,55 @@ class Context:
         hits = np.zeros(len(rays), abi.HIT_DTYPE)
         self._check(lib.srtTraceRays(self.h, rays.ctypes.data, len(rays), hits.ctypes.data, traversal))
         return hits
+
+    @staticmethod
+    def _device_rays(rays):
+        """The rays of a device query: a contiguous float32 torch tensor (n, 9) on the GPU, laid out as SrtRay."""
+        if not hasattr(rays, "data_ptr") or not hasattr(rays, "is_cuda"):
+            raise ValueError("rays must be a torch tensor on the GPU (for host arrays there is trace())")
+        if str(rays.dtype) != "torch.float32":
+            raise ValueError("rays must be float32, not %s" % rays.dtype)
+        if rays.dim() != 2 or rays.shape[1] != 9:
+            raise ValueError("rays must have shape (n, 9) (o, d, time, tMin, tMax), not %s" % (tuple(rays.shape),))
+        if not rays.is_contiguous():
+            raise ValueError("rays must be contiguous")
+        if not rays.is_cuda:
+            raise ValueError("rays must live on the GPU, not on %s" % rays.device)
+        return rays
+
+    @staticmethod
+    def _stream_handle(stream):
+        """None (the NULL stream), a raw hipStream_t as an integer, or a torch stream."""
+        return getattr(stream, "cuda_stream", stream)
+
+    def trace_device(self, rays, traversal=abi.SRT_TRAVERSE_CLOSEST, records=False, stream=None):
+        """srtTraceRaysDevice: the hit of every ray of a DEVICE tensor, asynchronous on `stream`.  rays: contiguous float32
+        (n, 9) on the GPU, one SrtRay per row.  Returns an int32 tensor (n, 4) laid out as SrtRayHit {prim, t's bits,
+        material, frontFace} (column 1 viewed as float32 is t); with records=True also an int32 tensor (n, 22) laid out as
+        SrtHit, its counters 0.  The outputs are allocated with torch on the rays' device: call this inside
+        `with torch.cuda.stream(s)` when `stream` is s, so that the allocator knows the stream that uses them.
+        CLOSEST is the tree-independent closest hit, ties to the largest prims[] index; triangles are one-sided; a ray's
+        time must lie inside every world item's range (include/srt_hip.h "Ray queries")."""
+        import torch
+        rays = self._device_rays(rays)
+        n = rays.shape[0]
+        hits = torch.empty((n, 4), dtype=torch.int32, device=rays.device)
+        recs = torch.empty((n, C.sizeof(abi.SrtHit) // 4), dtype=torch.int32, device=rays.device) if records else None
+        self._check(lib.srtTraceRaysDevice(self.h, rays.data_ptr() if n else None, n, int(traversal),
+                                           hits.data_ptr() if n else None, recs.data_ptr() if records and n else None,
+                                           self._stream_handle(stream)))
+        return (hits, recs) if records else hits
+
+    def occluded_device(self, rays, stream=None):
+        """srtOccludedDevice: a torch.uint8 tensor (n,), 1 where anything lies in a ray's (tMin, tMax); rays and stream as
+        trace_device's.  The any-hit walk leaves at the first primitive in the way."""
+        import torch
+        rays = self._device_rays(rays)
+        n = rays.shape[0]
+        out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        self._check(lib.srtOccludedDevice(self.h, rays.data_ptr() if n else None, n, out.data_ptr() if n else None,
+                                          self._stream_handle(stream)))
+        return out
 
     def scatter_test(self, rays, hits, seed):
         rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)

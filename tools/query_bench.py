@@ -1,0 +1,164 @@
+"""Device ray queries (srtTraceRaysDevice, srtOccludedDevice): Mrays/s on ray sets that never leave the GPU.
+
+Ray sets, per scene:
+  primary  the 720p lens-centre primary rays of the default camera, one per pixel, tMax = inf
+  ao       ambient-occlusion rays built with torch ops on the device from the feature pass's planes: from the POSITION
+           mean of every pixel that hit something, pushed off the surface along the NORMAL mean, --ao-rays cosine-
+           distributed directions about that normal, tMax = --ao-radius times the scene's extent
+Scenes: masterchief (the reference's tree) and bench.py's soups of 200 k and 1 M triangles with PLOC trees.
+Per scene and ray set: FAITHFUL (reference tree only), CLOSEST and ANY (occlusion), timed with events on a stream around
+the calls (mean of --steps back-to-back calls after --warmup), and beside them `host_trace_ms`: srtTraceRays on the same rays copied to the
+host, wall clock.  NOTE that the latter includes what the host entry does on every call -- two device allocations, 36 B
+per ray in, 88 B per ray out, a device synchronisation -- and its kernel keeps traversal counters: it is the cost of asking
+through the only entry there was, not a kernel comparison.
+--ao-png FILE writes the AO image 1 - mean(occluded) of the first scene.  Prints one JSON line.
+
+usage: python tools/query_bench.py [--steps 200] [--warmup 5] [--host-steps 3] [--cases masterchief,soup_200k,soup_1m] [--ao-rays 4]
+                                   [--ao-radius 0.1] [--ao-png FILE] [--width 1280] [--height 720]"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+srt = importlib.import_module("sexy-raytracer_amd")
+abi, dev = srt.abi, srt.device()
+F = np.float32
+
+
+def scene(case):
+    if case.startswith("soup_"):
+        n = {"200k": 200000, "1m": 1000000, "4m": 4000000}[case[5:]]
+        # bench.py's soups
+        return srt.scenes.scene_soup(n, seed=7, extent=6.0, size=max(0.01, 0.08 * (100000.0 / n) ** (1.0 / 3.0)), builder=abi.SRT_BUILDER_PLOC)
+    return srt.scenes.SCENES[case]()
+
+
+def primary_rays(cam, W, H):
+    """(W*H, 9) float32 on the GPU: camera.h:40-46 with a zero lens offset, pixel centres, time 0.5 of the shutter."""
+    ys, xs = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32), indexing="ij")
+    u = ((xs + 0.5) / (W - 1)).reshape(-1, 1)
+    v = ((H - ys - 0.5) / (H - 1)).reshape(-1, 1)
+    o, ll, hz, vt = (torch.tensor(list(a), device="cuda", dtype=torch.float32) for a in (cam.origin, cam.lleft, cam.horizontal, cam.vertical))
+    rays = torch.empty((W * H, 9), device="cuda", dtype=torch.float32)
+    rays[:, 0:3] = o
+    rays[:, 3:6] = ll + u * hz + v * vt - o
+    rays[:, 6] = 0.5 * (cam.time0 + cam.time1)
+    rays[:, 7] = 0.001
+    rays[:, 8] = float("inf")
+    return rays
+
+
+def ao_rays(planes, count, radius, time, seed=1):
+    """Cosine-distributed directions about the NORMAL mean from the POSITION mean of every pixel with a hit, torch ops on the
+    device.  Returns (rays (pixels * count, 9), pixel index of every ray's pixel)."""
+    pos = torch.from_numpy(planes["position"].reshape(-1, 4)).cuda()
+    nrm = torch.from_numpy(planes["normal"].reshape(-1, 4)).cuda()
+    pix = torch.nonzero(nrm[:, 3] > 0).reshape(-1)
+    n = torch.nn.functional.normalize(nrm[pix, :3], dim=1)
+    p = pos[pix, :3]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    # a unit vector uniform on the sphere added to the unit normal: cosine-distributed about it
+    s = torch.nn.functional.normalize(torch.randn((len(pix), count, 3), device="cuda", generator=g), dim=2)
+    d = torch.nn.functional.normalize(n[:, None, :] + 0.999 * s, dim=2)
+    rays = torch.empty((len(pix), count, 9), device="cuda", dtype=torch.float32)
+    rays[:, :, 0:3] = (p + 5e-3 * radius * n)[:, None, :]
+    rays[:, :, 3:6] = d
+    rays[:, :, 6] = time
+    rays[:, :, 7] = 5e-3 * radius
+    rays[:, :, 8] = radius
+    return rays.reshape(-1, 9).contiguous(), pix
+
+
+def event_ms(stream, fn, steps, warmup):
+    with torch.cuda.stream(stream):
+        for _ in range(warmup):
+            fn()
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record(stream)
+        for _ in range(steps):
+            fn()
+        stop.record(stream)
+    stop.synchronize()
+    return start.elapsed_time(stop) / steps
+
+
+def measure(ctx, rays, faithful, steps, warmup, host_steps):
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    n = rays.shape[0]
+    out = {"rays": n}
+    modes = [("closest", lambda: ctx.trace_device(rays, abi.SRT_TRAVERSE_CLOSEST, stream=stream)),
+             ("any", lambda: ctx.occluded_device(rays, stream=stream))]
+    if faithful:
+        modes.insert(0, ("faithful", lambda: ctx.trace_device(rays, abi.SRT_TRAVERSE_FAITHFUL, stream=stream)))
+    for name, fn in modes:
+        ms = event_ms(stream, fn, steps, warmup)
+        out[name + "_ms"] = ms
+        out[name + "_mrays_s"] = n / ms * 1e-3
+    with torch.cuda.stream(stream):
+        hits = ctx.trace_device(rays, abi.SRT_TRAVERSE_CLOSEST, stream=stream)
+        occ = ctx.occluded_device(rays, stream=stream)
+    stream.synchronize()
+    out["hit_share"] = float((hits[:, 0] >= 0).float().mean())
+    assert bool(((hits[:, 0] >= 0) == (occ != 0)).all()), "occlusion disagrees with the closest hit"
+    # the host entry on the same rays: allocation, both transfers and a device synchronisation are inside the clock
+    host = rays.cpu().numpy().view(abi.RAY_DTYPE).reshape(-1)
+    ctx.trace(host[:1024], abi.SRT_TRAVERSE_CLOSEST)
+    t = time.perf_counter()
+    for _ in range(host_steps):
+        ctx.trace(host, abi.SRT_TRAVERSE_CLOSEST)
+    out["host_trace_ms"] = (time.perf_counter() - t) * 1e3 / host_steps
+    out["host_trace_mrays_s"] = n / out["host_trace_ms"] * 1e-3
+    return out, occ
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200, help="timed device calls per figure (a call is 0.2 - 3 ms)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--host-steps", type=int, default=3, help="timed srtTraceRays calls (10 - 70 ms each)")
+    ap.add_argument("--cases", default="masterchief,soup_200k,soup_1m")
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--height", type=int, default=720)
+    ap.add_argument("--ao-rays", type=int, default=4)
+    ap.add_argument("--ao-radius", type=float, default=0.1, help="AO tMax as a share of the scene's extent (6 units)")
+    ap.add_argument("--ao-png", default=None)
+    a = ap.parse_args()
+    ctx = dev.Context(0)
+    cam = dev.make_camera(abi.default_camera_params())
+    W, H = a.width, a.height
+    result = {"device": ctx.device_info()["name"], "steps": a.steps, "host_steps": a.host_steps, "width": W, "height": H, "ao_rays_per_pixel": a.ao_rays,
+              "note": "host_trace_* is srtTraceRays end to end on the same rays: it includes allocation and transfers", "cases": {}}
+    for k, case in enumerate(a.cases.split(",")):
+        sb = scene(case)
+        ctx.upload_scene(sb)
+        ctx.set_camera(cam)
+        faithful = all(it.builder == abi.SRT_BUILDER_REFERENCE for it in sb.world)
+        out = {"tree": "reference" if faithful else "ploc", "bvh_depth": ctx.bvh_depth()}
+        out["primary"], _ = measure(ctx, primary_rays(cam, W, H), faithful, a.steps, a.warmup, a.host_steps)
+        p = abi.default_render_params(W, H, 1, 1, seed=1, traversal=abi.SRT_TRAVERSE_FAITHFUL if faithful else abi.SRT_TRAVERSE_CLOSEST)
+        planes = ctx.render_features(p, abi.SRT_FEATURE_NORMAL | abi.SRT_FEATURE_POSITION)
+        rays, pix = ao_rays(planes, a.ao_rays, a.ao_radius * 6.0, 0.5 * (cam.time0 + cam.time1))
+        out["ao"], occ = measure(ctx, rays, faithful, a.steps, a.warmup, a.host_steps)
+        out["ao"]["occluded_share"] = float((occ != 0).float().mean())
+        if a.ao_png and k == 0:
+            from PIL import Image
+            img = torch.ones(W * H, device="cuda")
+            img[pix] = 1.0 - (occ != 0).float().reshape(-1, a.ao_rays).mean(dim=1)
+            Image.fromarray((img.reshape(H, W).clamp(0, 1) * 255).byte().cpu().numpy(), "L").save(a.ao_png)
+        result["cases"][case] = out
+    ctx.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
