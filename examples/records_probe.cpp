@@ -25,10 +25,10 @@ int main(int argc, char** argv) {
   FILE* out = fopen(argv[2], "wb");
   if (!out) return 1;
   for (const SrtTriangleIn& t : tris) {
-    float4 test[3], shade[4];
+    float4 test[3], shade[4], fast[SRT_TRI_FAST_SLOTS];  // (triFast: examples/tri_cert_probe.cpp writes those out)
     float material;
     memcpy(&material, &t.material, 4);
-    triangleRecords(&t.p[0][0], &t.uv[0][0], material, test, shade);
+    triangleRecords(&t.p[0][0], &t.uv[0][0], material, test, shade, fast);
     const Box b = triangleBox(vec3(t.p[0]), vec3(t.p[1]), vec3(t.p[2]));
     fwrite(test, sizeof test, 1, out);
     fwrite(shade, sizeof shade, 1, out);

@@ -68,7 +68,9 @@ int srtGetShadeProfile(SrtContext* ctx, uint64_t* out10);
 /* Step profile of the most recent launch of the path-pool kernel's profiling variant (tunable "wf_profile" = 1;
  * csrc/srt_wavefront.hip): out46 = { clocks[12], executions[12], lanes[12] } for the step kinds node visit, primitive
  * test, swap, hit step of class 0 / 1 / 2, restart, idle, lost claim, item pull, visit of a node outside LDS (hybrid form:
- * the clocks are the wait for the records plus the visit), unused; scheduling clocks, total wave clocks; then what the
+ * the clocks are the wait for the records plus the visit), and an eleventh slot whose clocks word counts the primitive-step
+ * executions that ran the exact triangle test and whose executions word counts the lanes the triangle certificate left
+ * undecided (its lanes word: the hybrid form's near lanes); scheduling clocks, total wave clocks; then what the
  * scheduling decisions that looked at the rings saw, summed: decisions, lanes at nodes / at primitives / finished / idle,
  * READY fill, fill of the fullest served ring, RESTART fill. */
 int srtGetWfProfile(SrtContext* ctx, uint64_t* out46);
@@ -93,6 +95,20 @@ int srtTestHybridRecords(const float* nodes8, int32_t numNodes, const int32_t* w
  * a node's record offset (scene-wide index * 64) or a device primitive reference ~(index << 1 | sphere)).  Either output
  * may be NULL; with both NULL only *count is written.  Fails for an item that is not a tree, or when capacity < count. */
 int srtTestGetTreeAux(SrtContext* ctx, int32_t item, uint8_t* outAxis, float* outPairs16, int32_t capacity, int32_t* count);
+
+/* The certified triangle test of the FAITHFUL render and trace kernels (csrc/srt_tri_hit.h; tunable "tri_cert", default 1, 0 = every
+ * triangle test is the exact one): the render kernels over an LDS-resident tree and srtTraceRays run it; the path-pool
+ * kernel's hybrid form and the 256-thread kernel (trees beyond LDS) keep the exact test alone.
+ * srtTestGetTriUndecided: how many triangle tests of the most recent srtTraceRays call on this context the certificate left
+ * to the exact test (0 after a CLOSEST call; where "tri_cert" has the certificate off, every triangle test).
+ * srtTestGetTriFast: the uploaded scene's triFast records as they lie in device memory now (after srtUpdateTriangles as
+ * well), 16 floats per triangle, in the SCENE's triangle order -> out16[count x 16]; out16 NULL: only *count.
+ * srtTestTriFastRecord (host only, no device): the record srtUploadScene makes of one triangle, p9 = its three vertices:
+ * (v0.xyz, d) (n.xyz, k) (m0.xyz, kappa) (m1.xyz, kappa E + floor); kappa = +inf marks a triangle outside the certified
+ * ranges. */
+int srtTestGetTriUndecided(SrtContext* ctx, uint64_t* out);
+int srtTestGetTriFast(SrtContext* ctx, float* out16, int32_t capacity, int32_t* count);
+int srtTestTriFastRecord(const float* p9, float* out16);
 
 /* The most recent render-kernel launch: out4 = { 0 node records through the L1, 1 the step-scheduler kernel over the
  * LDS-resident threaded tree (FAITHFUL, node array small enough for a CU's LDS; tunable "lds_tree" = 0 switches it

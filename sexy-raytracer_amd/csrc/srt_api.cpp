@@ -98,7 +98,14 @@ const TunableName kTunables[] = {
     // srtDenoise: a-trous levels of step <= this stage their (16 + 4 step)^2 window in LDS, larger steps read through the
     // caches (srt_denoise.hip; 8 at most, 0 = never) -- profiles/r05/denoise_bench.json
     {"denoise_lds_step", "SRT_DENOISE_LDS_STEP", &Tunables::denoiseLdsStep, 4},
+    // FAITHFUL render and trace kernels: the triangle test's edge signs from the certified one-FMA forms over the triFast
+    // records, the exact test for the lanes they cannot decide (srt_tri_hit.h): the kernels over an LDS-resident tree and
+    // srtTraceRays.  0 = every test is the exact one.  The image, t and every counter are the same either way.
+    {"tri_cert", "SRT_TRI_CERT", &Tunables::triCert, 1},
 };
+
+// DevScene::triWMax for the tunable "tri_cert": the certificate's overflow guard, or 0 = nothing is certified
+float triWMaxFor(const SrtContext* ctx) { return ctx->tun.triCert ? SRT_TRI_W_MAX : 0.0f; }
 
 }  // namespace
 
@@ -150,7 +157,7 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   if (!h.nodeThread.empty() && uploadVec(ctx, h.nodeThread, &s.nodeThread)) return 1;
   if (!h.nodesWf.empty() && (uploadVec(ctx, h.nodesWf, &s.nodesWf) || uploadVec(ctx, h.worldWf, &s.worldWf) || uploadVec(ctx, h.primSecond, &s.primSecond))) return 1;
   if (uploadVec(ctx, h.primClass, &s.primClass, 16) || uploadVec(ctx, h.nodeAxis, &s.nodeAxis, 64) || uploadVec(ctx, h.nodes, &s.nodes) ||
-      uploadVec(ctx, h.triTest, &s.triTest) || uploadVec(ctx, h.triShade, &s.triShade) || uploadVec(ctx, h.spheres, &s.spheres) ||
+      uploadVec(ctx, h.triTest, &s.triTest) || uploadVec(ctx, h.triFast, &s.triFast) || uploadVec(ctx, h.triShade, &s.triShade) || uploadVec(ctx, h.spheres, &s.spheres) ||
       uploadVec(ctx, h.triPrimId, &s.triPrimId) || uploadVec(ctx, h.sphPrimId, &s.sphPrimId) || uploadVec(ctx, h.world, &s.world) ||
       uploadVec(ctx, h.materials, &s.materials) || uploadVec(ctx, h.shadeRecs, &s.shadeRecs) || uploadVec(ctx, h.textures, &s.textures) ||
       uploadVec(ctx, h.texels, &s.texels, 64))
@@ -165,6 +172,7 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   s.numMaterials = d->numMaterials;
   s.texelBytes = (int32_t)h.texels.size();
   s.fastDivScene = h.fastDivScene;
+  s.triWMax = triWMaxFor(ctx);
   ctx->upload.bvhDepth = h.bvhDepth;
   // device-built trees (srt_lbvh.hip) into the node slots the flattening reserved.  Their refs stay on the device for
   // srtRebuildScene (buildDeviceTrees)
@@ -436,6 +444,40 @@ int srtTestGetTreeAux(SrtContext* ctx, int32_t item, uint8_t* outAxis, float* ou
   return 0;
 }
 
+/* include/srt_hip_test.h: the certified triangle test's read-outs */
+int srtTestGetTriUndecided(SrtContext* ctx, uint64_t* out) {
+  if (!ctx || !out) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  HIP_OK(ctx, hipDeviceSynchronize());
+  HIP_OK(ctx, hipMemcpy(out, ctx->dStats.get<unsigned long long>() + SRT_STATS_TRI_UNDECIDED, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+int srtTestGetTriFast(SrtContext* ctx, float* out16, int32_t capacity, int32_t* count) {
+  if (!ctx || !count) return 1;
+  if (!ctx->upload.haveScene) return fail(ctx, "srtTestGetTriFast: no scene uploaded");
+  const int32_t n = ctx->upload.scene.numTris;
+  *count = n;
+  if (!out16) return 0;
+  if (capacity < n) return fail(ctx, "srtTestGetTriFast: capacity %d < %d", capacity, n);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  HIP_OK(ctx, hipDeviceSynchronize());
+  const std::vector<int32_t>& dev = ctx->upload.hostTriDevIndex;  // scene index -> device index, empty = identity
+  std::vector<float4> raw((size_t)n * SRT_TRI_FAST_SLOTS);
+  if (n) HIP_OK(ctx, hipMemcpy(raw.data(), ctx->upload.scene.triFast, raw.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  for (int32_t i = 0; i < n; ++i)
+    memcpy(out16 + 16 * (size_t)i, &raw[SRT_TRI_FAST_SLOTS * (size_t)(dev.empty() ? i : dev[i])], 64);
+  return 0;
+}
+/* host-only: the triFast record of one triangle as srtUploadScene makes it */
+int srtTestTriFastRecord(const float* p9, float* out16) {
+  if (!p9 || !out16) return 1;
+  const float uv[6] = {0, 0, 0, 0, 0, 0};
+  float4 test[3], shade[4], fast[SRT_TRI_FAST_SLOTS];
+  triangleRecords(p9, uv, 0.0f, test, shade, fast);
+  memcpy(out16, fast, 64);
+  return 0;
+}
+
 int srtGetShadeProfile(SrtContext* ctx, uint64_t* out10) {
   if (!ctx || !out10) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -450,6 +492,7 @@ int srtSetTunable(SrtContext* ctx, const char* name, int32_t value) {
   for (const TunableName& t : kTunables)
     if (!strcmp(t.name, name)) {
       ctx->tun.*(t.field) = value;
+      ctx->upload.scene.triWMax = triWMaxFor(ctx);  // (the uploaded scene follows "tri_cert" at once)
       return 0;
     }
   return fail(ctx, "srtSetTunable: unknown tunable '%s'", name);

@@ -28,6 +28,7 @@ struct Tunables {
   int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
   int wfHybrid, wfResidentMax, wfFarRounds;
   int denoiseLdsStep;
+  int triCert;
 };
 
 // What belongs to the uploaded scene and is invalid for the next one.  srtUploadScene starts by assigning a fresh Upload,

@@ -53,6 +53,13 @@ struct DevScene {
   const float4* nodes;
   // 3 x float4 per triangle: (v0.xyz, n.x) (v1.xyz, n.y) (v2.xyz, n.z), n = (v1-v0)x(v2-v0)  -- 48 B / test
   const float4* triTest;
+  // 4 x float4 per triangle, one aligned 64-byte line: (v0.xyz, d) (n.xyz, k) (m0.xyz, kappa) (m1.xyz, kappa E + floor) --
+  // what the certified triangle test of the FAITHFUL render and trace kernels reads (srt_tri_hit.h); triTest is read only
+  // by the lanes it cannot decide.  -- 64 B / test
+  const float4* triFast;
+  // the certified test decides only where |p - v0|_1 is below this: SRT_TRI_W_MAX, or 0 while the tunable "tri_cert" is 0
+  // (nothing is below 0: every lane that passes the plane conditions takes the exact test)
+  float triWMax;
   // 4 x float4 per triangle, read once per shaded hit:
   // (N^.xyz, uv0.u) (T.xyz, uv0.v) (B.xyz, uv1.u) (uv1.v, uv2.u, uv2.v, material)
   const float4* triShade;
@@ -184,11 +191,14 @@ struct RenderPlan {
 };
 typedef void (*RenderKernel)(const RenderArgs);
 
+// the context's statistics area (96 words): 0-17 SrtStats, 18-27 the shade profile, 32-77 the path-pool profile, and
+#define SRT_STATS_TRI_UNDECIDED 80 /* srtTraceRays: triangle tests of the last call that the certificate left undecided */
 struct TraceArgs {
   DevScene scene;
   const SrtRay* rays;
   SrtHit* hits;
   int64_t n;
+  unsigned long long* triUndecided;  // the launch's triangle tests the certificate left to the exact test are added here
 };
 
 // srtTraceRaysDevice / srtOccludedDevice (srt_query.hip): every pointer is the caller's DEVICE memory

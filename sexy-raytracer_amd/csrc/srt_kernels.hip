@@ -108,6 +108,7 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
   const __amdgpu_buffer_rsrc_t rsNodes = makeRsrc(sc.nodes, sc.numNodes * 32);
   const __amdgpu_buffer_rsrc_t rsNodes2 = makeRsrc(sc.nodes2, CLOSEST ? sc.numNodes * 64 : 0);
   const __amdgpu_buffer_rsrc_t rsTris = makeRsrc(sc.triTest, sc.numTris * 48);
+  const __amdgpu_buffer_rsrc_t rsFast = makeRsrc(sc.triFast, !CLOSEST && LDSTREE ? sc.numTris * 64 : 0);  // FAITHFUL over the LDS-resident tree: the certified test first (srt_tri_hit.h)
   const __amdgpu_buffer_rsrc_t rsSpheres = makeRsrc(sc.spheres, sc.numSpheres * 48);
   const __amdgpu_buffer_rsrc_t rsTexels = makeRsrc(sc.texels, sc.texelBytes);
   const bool singleRoot = SINGLE || sc.numWorld == 1;
@@ -314,9 +315,24 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
             ok = sphereHitV(center, s0.w, ray, rayA, a.tMin, closest, t);
           } else {
             if (COUNT) cTri++;
-            const int off = (pr >> 1) * 48;
-            ok = triHitV<CLOSEST>(bufLoad4(rsTris, off), bufLoad4(rsTris, off + 16), bufLoad4(rsTris, off + 32), ray,
-                                  a.tMin, closest, t);
+            if constexpr (!CLOSEST && LDSTREE) {
+              // FAITHFUL over the LDS-resident tree: the certified test on the 64-byte triFast line, the exact test for the
+              // lanes it cannot decide (srt_tri_hit.h; the path-pool kernel's primitive step)
+              bool unsure;
+              const int off = (pr >> 1) * 64;
+              ok = srtTriHitCert(bufLoad4(rsFast, off), bufLoad4(rsFast, off + 16), bufLoad4(rsFast, off + 32), bufLoad4(rsFast, off + 48),
+                                 triRay(ray), a.tMin, sc.triWMax, t, unsure);
+              if (__ballot(unsure) != 0) {
+                if (unsure) {
+                  const int at = (pr >> 1) * 48;
+                  ok = triHitV<false>(bufLoad4(rsTris, at), bufLoad4(rsTris, at + 16), bufLoad4(rsTris, at + 32), ray, a.tMin, closest, t);
+                }
+              }
+            } else {  // the 256-thread kernel serves the trees beyond LDS (cache- and HBM-bound) and the CLOSEST walks: the exact test alone
+              const int off = (pr >> 1) * 48;
+              ok = triHitV<CLOSEST>(bufLoad4(rsTris, off), bufLoad4(rsTris, off + 16), bufLoad4(rsTris, off + 32), ray,
+                                    a.tMin, closest, t);
+            }
           }
           if (ok) {
             closest = t;
@@ -759,9 +775,10 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_trace_kernel(const TraceArgs a)
     r.o = ld3(in.o);
     r.d = ld3(in.d);
     r.time = in.time;
-    Counters cnt = {0, 0, 0, 0};
+    Counters cnt = {0, 0, 0, 0, 0};
     float tHit;
-    int ref = traverse<CLOSEST, true>(a.scene, r, in.tMin, in.tMax, stack, tHit, cnt);
+    int ref = traverse<CLOSEST, true, !CLOSEST>(a.scene, r, in.tMin, in.tMax, stack, tHit, cnt);
+    if (cnt.triUndecided) atomicAdd(a.triUndecided, (unsigned long long)cnt.triUndecided);
     SrtHit h;
     h.prim = SRT_NO_HIT;
     h.t = 0;

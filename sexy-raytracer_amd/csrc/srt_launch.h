@@ -35,7 +35,7 @@ int srt_pair_nodes_async(const DevScene* sc, float time0, float time1, float4* o
 
 // srt_refit.hip
 int srt_launch_refit_triangles(const void* dIn, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade,
-                               hipStream_t stream);
+                               float4* triFast, hipStream_t stream);
 int srt_launch_refit_spheres(const void* dIn, int first, int count, float4* spheres, hipStream_t stream);
 int srt_launch_refit_links(const float4* nodes, int numNodes, int32_t* up, hipStream_t stream);
 int srt_launch_refit_nodes(const DevScene* sc, int base, int count, float time0, float time1, const int32_t* up, int32_t* arrived,

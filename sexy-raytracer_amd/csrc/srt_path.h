@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "srt_device.h"
+#include "srt_tri_hit.h"
 
 #define SRT_TREE_WAVES_PER_SIMD 4
 #ifndef SRT_NODE_UNROLL
@@ -151,6 +152,7 @@ struct Ray {
 
 struct Counters {
   uint32_t nodeVisits, boxPasses, triTests, sphereTests;
+  uint32_t triUndecided;  // traverse<.., TRICERT = true>: triangle tests the certificate left to the exact test
 };
 
 // ------------------------------------------------------------------ geometry tests
@@ -283,27 +285,16 @@ __device__ __forceinline__ bool sphereHit(const float4* sp, const Ray& r, float 
   return sphereHitV(sphereCenter(sp, s0, s1, r.time), s0.w, r, a, tMin, tMax, tOut);
 }
 
-// model.h:104-154.  n is precomputed on the host with the same operation order as
-// getNormal (model.h:276-283).  CLOSEST adds the t > tMax rejection the reference lacks.
+// model.h:104-154: srt_tri_hit.h holds the one statement of the exact test, and the certified form of its edge signs.
+__device__ __forceinline__ SrtTriRay triRay(const Ray& r) { return SrtTriRay{r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z}; }
 template <bool CLOSEST>
 __device__ __forceinline__ bool triHitV(float4 q0, float4 q1, float4 q2, const Ray& r, float tMin, float tMax,
                                         float& tOut) {
-  V3 v0 = mk(q0.x, q0.y, q0.z), v1 = mk(q1.x, q1.y, q1.z), v2 = mk(q2.x, q2.y, q2.z);
-  V3 n = mk(q0.w, q1.w, q2.w);
-  float NdotDir = dot3(n, r.d);
-  // model.h:119-123: parallel, then back-face (dot(dir, n) has the same bits as dot(n, dir))
-  bool ok = !(fabsf(NdotDir) < SRT_EPS) && !(NdotDir > 0);
-  float d = -dot3(n, v0);
-  float t = -(dot3(n, r.o) + d) / NdotDir;
-  ok = ok && !(t < tMin);
-  if (CLOSEST) ok = ok && !(t > tMax);
-  V3 p = r.o + t * r.d;
-  // the three inside-edge tests (model.h:135-154); a NaN passes, as in the reference
-  ok = ok && !(dot3(n, cross3(v1 - v0, p - v0)) < 0);
-  ok = ok && !(dot3(n, cross3(v2 - v1, p - v1)) < 0);
-  ok = ok && !(dot3(n, cross3(v0 - v2, p - v2)) < 0);
-  tOut = t;
-  return ok;
+  return srtTriHitExact<CLOSEST>(q0, q1, q2, triRay(r), tMin, tMax, tOut);
+}
+// the FAITHFUL test on the triFast record; `undecided` as srtTriHitCert raises it
+__device__ __forceinline__ bool triHitCert(const float4* fast, const Ray& r, float tMin, float wMax, float& tOut, bool& undecided) {
+  return srtTriHitCert(fast[0], fast[1], fast[2], fast[3], triRay(r), tMin, wMax, tOut, undecided);
 }
 template <bool CLOSEST>
 __device__ __forceinline__ bool triHit(const float4* tr, const Ray& r, float tMin, float tMax, float& tOut) {
@@ -316,7 +307,8 @@ __device__ __forceinline__ bool triHit(const float4* tr, const Ray& r, float tMi
 // tMax" (by induction over bvh.h:102-103), i.e. one running value `closest`.
 // A single-object leaf (left == right, bvh.h:67-69) tests its object twice with
 // identical outcome; it is tested once here.
-template <bool CLOSEST, bool COUNT>
+// TRICERT (FAITHFUL only; srt_trace_kernel): triangles take the certified test first.
+template <bool CLOSEST, bool COUNT, bool TRICERT = false>
 __device__ __forceinline__ int traverse(const DevScene& sc, const Ray& r, float tMin, float tMax, int32_t* stack,
                                         float& tHit, Counters& cnt) {
   const float a = lenSq(r.d);  // sphere.h:56, per ray
@@ -375,7 +367,19 @@ __device__ __forceinline__ int traverse(const DevScene& sc, const Ray& r, float 
         ok = sphereHit(sc.spheres + 3 * (pr >> 1), r, a, tMin, closest, t);
       } else {
         if (COUNT) cnt.triTests++;
-        ok = triHit<CLOSEST>(sc.triTest + 3 * (pr >> 1), r, tMin, closest, t);
+        if (TRICERT && !CLOSEST && sc.triWMax > 0.0f) {
+          bool unsure;
+          ok = triHitCert(sc.triFast + SRT_TRI_FAST_SLOTS * (pr >> 1), r, tMin, sc.triWMax, t, unsure);
+          if (unsure) {
+            if (COUNT) cnt.triUndecided++;
+            ok = triHit<false>(sc.triTest + 3 * (pr >> 1), r, tMin, closest, t);
+          }
+        } else if (TRICERT && !CLOSEST) {  // the certificate is off: the exact test, counted as one the certificate did not decide
+          if (COUNT) cnt.triUndecided++;
+          ok = triHit<false>(sc.triTest + 3 * (pr >> 1), r, tMin, closest, t);
+        } else {
+          ok = triHit<CLOSEST>(sc.triTest + 3 * (pr >> 1), r, tMin, closest, t);
+        }
       }
       if (ok) {
         closest = t;

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "srt_device.h"
+#include "srt_tri_hit.h"
 
 struct Vec3 {
   float x, y, z;
@@ -54,13 +55,16 @@ SRT_HD inline bool fastDivOperands(const Box& b) {
 
 // ------------------------------------------------------------------ triangles
 // p: the nine position floats, uv: the six texture coordinates (SrtTriangleIn's order) -> triTest (vertices, the
-// geometric normal in the w words) and triShade (unit normal, tangent, bitangent, the uvs, the caller's material word).
-SRT_HD inline void triangleRecords(const float* p, const float* uv, float material, float4* test, float4* shade) {
+// geometric normal in the w words), triShade (unit normal, tangent, bitangent, the uvs, the caller's material word) and
+// triFast (the certified test's 64-byte record, srt_tri_hit.h).
+SRT_HD inline void triangleRecords(const float* p, const float* uv, float material, float4* test, float4* shade, float4* fast) {
   const Vec3 v0 = vec3(p), v1 = vec3(p + 3), v2 = vec3(p + 6);
   const Vec3 n = cross(v1 - v0, v2 - v0);  // getNormal, model.h:276-283
   test[0] = make_float4(v0.x, v0.y, v0.z, n.x);
   test[1] = make_float4(v1.x, v1.y, v1.z, n.y);
   test[2] = make_float4(v2.x, v2.y, v2.z, n.z);
+  const float nf[3] = {n.x, n.y, n.z};
+  srtTriFastRecord(p, p + 3, p + 6, nf, fast);
   const Vec3 nu = unit(n);  // model.h:172
   // calcTangentBasis, model.h:214-235
   const Vec3 e0 = v1 - v0, e1 = v2 - v0;

@@ -13,18 +13,19 @@
 
 namespace {
 
-// One lane per updated triangle: SrtTriangleIn (64 B, four 16-byte loads) -> triTest and triShade at the triangle's DEVICE
+// One lane per updated triangle: SrtTriangleIn (64 B, four 16-byte loads) -> triTest, triShade and triFast at the triangle's DEVICE
 // index.  The material word (index, type and flag bits) stays.  devIndex: scene triangle index -> device index, null =
 // identity.
-__global__ void refitTriRecords(const float4* in, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade) {
+__global__ void refitTriRecords(const float4* in, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade, float4* triFast) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const float4 a = in[4 * (size_t)i], b = in[4 * (size_t)i + 1], c = in[4 * (size_t)i + 2], d = in[4 * (size_t)i + 3];
   const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x}, uv[6] = {c.y, c.z, c.w, d.x, d.y, d.z};
   const size_t j = (size_t)(devIndex ? devIndex[first + i] : first + i);
-  float4 test[3], shade[4];
-  triangleRecords(p, uv, triShade[4 * j + 3].w, test, shade);
+  float4 test[3], shade[4], fast[SRT_TRI_FAST_SLOTS];
+  triangleRecords(p, uv, triShade[4 * j + 3].w, test, shade, fast);
   for (int k = 0; k < 3; ++k) triTest[3 * j + k] = test[k];
+  for (int k = 0; k < SRT_TRI_FAST_SLOTS; ++k) triFast[SRT_TRI_FAST_SLOTS * j + k] = fast[k];
   for (int k = 0; k < 4; ++k) triShade[4 * j + k] = shade[k];
 }
 
@@ -181,9 +182,9 @@ inline dim3 gridFor(int n) { return dim3((unsigned)((n + 255) / 256)); }
 extern "C" {
 
 int srt_launch_refit_triangles(const void* dIn, int first, int count, const int32_t* devIndex, float4* triTest, float4* triShade,
-                               hipStream_t stream) {
+                               float4* triFast, hipStream_t stream) {
   hipLaunchKernelGGL(refitTriRecords, gridFor(count), dim3(256), 0, stream, static_cast<const float4*>(dIn), first, count, devIndex,
-                     triTest, triShade);
+                     triTest, triShade, triFast);
   return (int)hipGetLastError();
 }
 

@@ -78,7 +78,8 @@ int updateTrianglesDevice(SrtContext* ctx, int32_t first, int32_t count, const v
   if (snapshotGeometry(ctx, static_cast<hipStream_t>(stream))) return 1;
   ctx->upload.geometryDirty = true;
   const int e = srt_launch_refit_triangles(dIn, first, count, table, const_cast<float4*>(ctx->upload.scene.triTest),
-                                           const_cast<float4*>(ctx->upload.scene.triShade), static_cast<hipStream_t>(stream));
+                                           const_cast<float4*>(ctx->upload.scene.triShade), const_cast<float4*>(ctx->upload.scene.triFast),
+                                           static_cast<hipStream_t>(stream));
   if (e) return fail(ctx, "srtUpdateTriangles: launch failed: %s", hipGetErrorString((hipError_t)e));
   return 0;
 }

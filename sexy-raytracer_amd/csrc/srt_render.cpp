@@ -502,6 +502,9 @@ int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, i
   a.rays = dRays.get<const SrtRay>();
   a.hits = dHits.get<SrtHit>();
   a.n = n;
+  // srtTestGetTriUndecided's count of this call: a word of the statistics area that no render launch writes
+  a.triUndecided = ctx->dStats.get<unsigned long long>() + SRT_STATS_TRI_UNDECIDED;
+  if (hipMemset(a.triUndecided, 0, sizeof(unsigned long long)) != hipSuccess) return fail(ctx, "trace: clearing the undecided count");
   size_t lds = (size_t)std::max(ctx->upload.scene.stackDepth, 1) * 256 * sizeof(int32_t);
   int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->prop.multiProcessorCount * 8);
   int e = srt_launch_trace(&a, traversal, grid, lds, nullptr);

@@ -229,9 +229,11 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
   }
   h.triTest.resize((size_t)d->numTriangles * 3);
   h.triShade.resize((size_t)d->numTriangles * 4);
+  h.triFast.resize((size_t)d->numTriangles * SRT_TRI_FAST_SLOTS);
   for (int i = 0; i < d->numTriangles; ++i) {
     const SrtTriangleIn& t = d->triangles[i];
-    triangleRecords(&t.p[0][0], &t.uv[0][0], bitsAs<float>(&t.material), &h.triTest[3 * (size_t)i], &h.triShade[4 * (size_t)i]);
+    triangleRecords(&t.p[0][0], &t.uv[0][0], bitsAs<float>(&t.material), &h.triTest[3 * (size_t)i], &h.triShade[4 * (size_t)i],
+                    &h.triFast[SRT_TRI_FAST_SLOTS * (size_t)i]);
   }
   h.spheres.resize((size_t)d->numSpheres * 3);
   for (int i = 0; i < d->numSpheres; ++i) {
@@ -442,16 +444,18 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
         v.w = bitsAs<float>(&r);
       }
       for (int32_t& wr : h.world) wr = remap(wr);
-      std::vector<float4> tt(h.triTest.size()), ts(h.triShade.size());
+      std::vector<float4> tt(h.triTest.size()), ts(h.triShade.size()), tf(h.triFast.size());
       std::vector<int32_t> tp(h.triPrimId.size());
       for (int32_t i = 0; i < d->numTriangles; ++i) {
         const int32_t j = order[i];
         for (int k = 0; k < 3; ++k) tt[3 * (size_t)j + k] = h.triTest[3 * (size_t)i + k];
         for (int k = 0; k < 4; ++k) ts[4 * (size_t)j + k] = h.triShade[4 * (size_t)i + k];
+        for (int k = 0; k < SRT_TRI_FAST_SLOTS; ++k) tf[SRT_TRI_FAST_SLOTS * (size_t)j + k] = h.triFast[SRT_TRI_FAST_SLOTS * (size_t)i + k];
         tp[j] = h.triPrimId[i];
       }
       h.triTest.swap(tt);
       h.triShade.swap(ts);
+      h.triFast.swap(tf);
       h.triPrimId.swap(tp);
       triDevIndex.swap(order);  // devRef of the device-built trees below
     }

@@ -67,7 +67,7 @@ struct HostScene {
   std::vector<float4> nodes;  // device-built items' slots are zero until their build
   std::vector<uint8_t> nodeAxis;
   std::vector<int32_t> world;
-  std::vector<float4> triTest, triShade, spheres;
+  std::vector<float4> triTest, triShade, triFast, spheres;
   std::vector<int32_t> triPrimId, sphPrimId;  // device index -> primitive list index
   std::vector<DevMaterial> materials;
   std::vector<DevTexture> textures;

@@ -108,7 +108,8 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   const uint64_t seedMixed = mix64(a.seed);
   const V3 background = ld3(a.background);
   const Rsrc rsNodes = makeRsrc(HYBRID ? sc.nodesWf : sc.nodes, sc.numNodes * 32);
-  const Rsrc rsTris = makeRsrc(sc.triTest, sc.numTris * 48);
+  const Rsrc rsTris = makeRsrc(sc.triTest, HYBRID ? sc.numTris * 48 : 0);  // (the whole-tree instances: where an undecided lane needs it)
+  const Rsrc rsFast = makeRsrc(sc.triFast, HYBRID ? 0 : sc.numTris * 64);
   const Rsrc rsSpheres = makeRsrc(sc.spheres, sc.numSpheres * 48);
   const Rsrc rsTexels = makeRsrc(sc.texels, sc.texelBytes);
   const Rsrc rsClass = makeRsrc(sc.primClass, sc.numPrimClass);
@@ -381,8 +382,31 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
             ok = sphereHitV(center, s0.w, ray, rayA, a.tMin, closest, t);
           } else {
             if constexpr (COUNT) cnt[4]++;
-            const int off = (pr >> 1) * 48;
-            ok = triHitV<false>(bufLoad4(rsTris, off), bufLoad4(rsTris, off + 16), bufLoad4(rsTris, off + 32), ray, a.tMin, closest, t);
+            if constexpr (HYBRID) {
+              // The hybrid form's walks wait for the caches or HBM, where the 64-byte record costs more than the arithmetic
+              // saves: its instances keep the exact test, and their code.
+              const int off = (pr >> 1) * 48;
+              ok = triHitV<false>(bufLoad4(rsTris, off), bufLoad4(rsTris, off + 16), bufLoad4(rsTris, off + 32), ray, a.tMin, closest, t);
+            } else {
+              // the certified test on the triangle's one 64-byte line (srt_tri_hit.h); the exact test, on its triTest record,
+              // for the lanes whose edge signs are not certain -- a block the wave enters only when some lane needs it
+              bool unsure;
+              const int off = (pr >> 1) * 64;
+              ok = srtTriHitCert(bufLoad4(rsFast, off), bufLoad4(rsFast, off + 16), bufLoad4(rsFast, off + 32), bufLoad4(rsFast, off + 48),
+                                 triRay(ray), a.tMin, sc.triWMax, t, unsure);
+              const unsigned long long mu = __ballot(unsure);
+              if (PROFILE) {  // lanes the certificate left undecided, and primitive-step executions that ran the exact test
+                pRuns[11] += __popcll(mu);
+                pCyc[11] += mu != 0 ? 1 : 0;
+              }
+              if (mu != 0) {
+                if (unsure) {
+                  const Rsrc rsExact = makeRsrc(sc.triTest, sc.numTris * 48);
+                  const int at = (pr >> 1) * 48;
+                  ok = triHitV<false>(bufLoad4(rsExact, at), bufLoad4(rsExact, at + 16), bufLoad4(rsExact, at + 32), ray, a.tMin, closest, t);
+                }
+              }
+            }
           }
           if (ok) {
             closest = t;

@@ -48,7 +48,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
                 "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
-                "srtTestDenoiseScratch"]
+                "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -149,6 +149,10 @@ lib.srtTestThreadLinks16.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int32, 
 lib.srtTestHybridRecords.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]
 lib.srtTestThreadLinks16.restype = lib.srtTestHybridRecords.restype = C.c_int32
 lib.srtTestGetTreeAux.argtypes = [_vp, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]
+if hasattr(lib, "srtTestGetTriUndecided"):  # (an SRT_HIP_LIB build from before the certified triangle test lacks the three)
+    lib.srtTestGetTriUndecided.argtypes = [_vp, C.POINTER(C.c_uint64)]
+    lib.srtTestGetTriFast.argtypes = [_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.srtTestTriFastRecord.argtypes = [_vp, _vp]
 lib.srtRenderAov.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
 lib.srtLastKernelMs.argtypes = [_vp, C.POINTER(C.c_float)]
 lib.srtGetStats.argtypes = [_vp, C.POINTER(abi.SrtStats)]
@@ -731,6 +735,22 @@ class Context:
         self._check(lib.srtTestChunkSum(self.h, slots.ctypes.data, slots.shape[1], slots.shape[0], path, samples, out.ctypes.data))
         return out
 
+    def tri_undecided(self):
+        """Triangle tests of the last trace() call that the certified test left to the exact one (include/srt_hip_test.h)."""
+        out = C.c_uint64(0)
+        self._check(lib.srtTestGetTriUndecided(self.h, C.byref(out)))
+        return int(out.value)
+
+    def tri_fast_records(self):
+        """The uploaded scene's triFast records as they lie in device memory, (numTriangles, 16) float32 in the scene's
+        triangle order (include/srt_hip_test.h)."""
+        n = C.c_int32(0)
+        self._check(lib.srtTestGetTriFast(self.h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 16), np.float32)
+        if n.value:
+            self._check(lib.srtTestGetTriFast(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     def set_tunable(self, name, value):
         """Diagnostic knobs of the work distribution / wave scheduler (include/srt_hip_test.h)."""
         self._check(lib.srtSetTunable(self.h, name.encode(), int(value)))
@@ -756,7 +776,7 @@ class Context:
         """Step profile of the last path-pool launch with tunable wf_profile = 1 (include/srt_hip_test.h)."""
         out = np.zeros(46, np.uint64)
         self._check(lib.srtGetWfProfile(self.h, out.ctypes.data))
-        kinds = ["node", "prim", "swap", "hit0", "hit1", "hit2", "restart", "idle", "lost_claim", "new_item", "far_node", "unused"]
+        kinds = ["node", "prim", "swap", "hit0", "hit1", "hit2", "restart", "idle", "lost_claim", "new_item", "far_node", "unused"]  # "unused": clocks = primitive steps that ran the exact triangle test, runs = undecided lanes
         K = len(kinds)
         prof = {k: {"clocks": int(out[i]), "runs": int(out[K + i]), "lanes": int(out[2 * K + i])} for i, k in enumerate(kinds)}
         prof["sched_clocks"], prof["total_clocks"] = int(out[3 * K]), int(out[3 * K + 1])
@@ -789,3 +809,12 @@ class Context:
         cus, mhz = C.c_int32(0), C.c_int32(0)
         self._check(lib.srtDeviceInfo(self.h, name, 256, C.byref(cus), C.byref(mhz)))
         return {"name": name.value.decode(), "cus": cus.value, "clock_mhz": mhz.value}
+
+
+def tri_fast_record(p9):
+    """Host only: the triFast record srtUploadScene makes of one triangle (nine floats), 16 float32 (include/srt_hip_test.h)."""
+    p9 = np.ascontiguousarray(p9, np.float32).reshape(9)
+    out = np.zeros(16, np.float32)
+    if lib.srtTestTriFastRecord(p9.ctypes.data, out.ctypes.data):
+        raise RuntimeError("srtTestTriFastRecord failed")
+    return out

@@ -36,6 +36,8 @@ if pr["far_node"]["runs"]:
         pr["far_node"]["lanes"] / pr["far_node"]["runs"], pr["unused"]["lanes"] / pr["far_node"]["runs"]))
 print("slab certificate: %.4f%% of lane visits undecided, %.2f%% of wave visits ran the IEEE test" % (
     100.0 * pr["lost_claim"]["lanes"] / max(1, pr["node"]["lanes"]), 100.0 * pr["idle"]["lanes"] / max(1, pr["node"]["runs"])))
+print("triangle certificate: %.4f%% of the lanes at a primitive step undecided, %.3f%% of primitive-step executions ran the exact test" % (
+    100.0 * pr["unused"]["runs"] / max(1, pr["prim"]["lanes"]), 100.0 * pr["unused"]["clocks"] / max(1, pr["prim"]["runs"])))
 print("%-10s %5.1f%% of wave time, %d decisions (%.2f per sample)" % ("scheduling", 100.0 * pr["sched_clocks"] / tot, pr["decisions"], pr["decisions"] / samples))
 sw = max(1, pr["swap"]["runs"])
 ms_ = pr["mean_seen"]
