@@ -29,15 +29,10 @@
 #include "srt_path.h"
 #include "srt_launch.h"
 #include "srt_wf_links.h"
+#include "srt_wf_rings.h"  // the rings, their control words, enqueue and claim
 
 #define WF_BLOCK 1024
-#define WF_CLASSES 3
-#define WF_RING_READY 0
-#define WF_RING_RESTART 1
-#define WF_RING_HIT 2                   // + material class
-#define WF_RING_NEWITEM (2 + WF_CLASSES)
-#define WF_RINGS (3 + WF_CLASSES)
-#define WF_SPIN_LIMIT (1 << 24)
+#define WF_SET_OF(mask) std::integral_constant<uint32_t, (mask)>()  // the rings an enqueue site can produce
 #define WF_CTX_BYTES 128
 // Context line (global memory, one per context id):  +0 A = ray origin, time   +16 B = ray direction (terminal radiance
 // once the path has ended), -   +32 C = RNG state (2 words), -, depth | pend << 8   +48 D = partial pixel sum, sample
@@ -47,14 +42,11 @@
 // Control words (LDS, behind the tree): 0..15 the waves' current work queue; 16 + 2r ring r's tail (places reserved),
 // 17 + 2r its head (places claimed) -- one 8-byte read gets both --, 28 live contexts, 29 abort.  Behind them the rings
 // (16-bit slots), then per context the t (float) and the primitive (16 bits) its last walk ended at.
-#define WF_CTL_TAIL(r) (16 + 2 * (r))
-#define WF_CTL_HEAD(r) (17 + 2 * (r))
 #define WF_CTL_LIVE 28
 #define WF_CTL_ABORT 29
 #define WF_CTL_WORDS 64
 #define WF_PEND_MISS 0      // context meta word: depth | pend << 8
 #define WF_PEND_TERMINAL 2
-#define WF_WG __HIP_MEMORY_SCOPE_WORKGROUP
 
 namespace {
 enum { W_NODE = 0, W_PRIM = 1, W_SWAP = 2, W_SERVE = 3 };
@@ -104,7 +96,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   float* const hitT = reinterpret_cast<float*>(ringSlots + WF_RINGS * RCAP);
   PrimSlot* const hitPrim = reinterpret_cast<PrimSlot*>(hitT + POOL);
   const int lane = threadIdx.x & 63;
-  const unsigned long long laneBelow = (1ull << lane) - 1ull;
+  const unsigned long long laneBelow = (1ull << lane) - 1ull;  // (the hybrid instances' ring operations; unused in the others)
   const uint64_t seedMixed = mix64(a.seed);
   const V3 background = ld3(a.background);
   const Rsrc rsNodes = makeRsrc(HYBRID ? sc.nodesWf : sc.nodes, sc.numNodes * 32);
@@ -124,15 +116,8 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     if (HYBRID) return sc.worldWf[k];
     return srtWfRootWord(sc.world[k]);
   };
-  // place of counter value c in a ring: c mod RCAP, RCAP = 2^j or 3 * 2^j (the pool size rounded up to such a number)
-  const int ringShift = a.wfRingShift;
-  const bool ringMul3 = a.wfRingMul3 != 0;
-  auto ringPos = [&](uint32_t c) -> int {
-    if (!ringMul3) return (int)(c & (uint32_t)(RCAP - 1));
-    const uint32_t x = c >> ringShift;
-    const uint32_t x3 = x - 3u * (uint32_t)(((unsigned long long)x * 0xAAAAAAABull) >> 33);
-    return (int)((c & ((1u << ringShift) - 1u)) | (x3 << ringShift));
-  };
+  // the rings' capacity RCAP = 2^j or 3 * 2^j (the pool size rounded up to such a number): srtWfRingPos
+  const SrtWfRingGeom ringGeom = {a.wfRingCap, a.wfRingShift, a.wfRingMul3};
 
   // ---- set-up: the threaded tree into LDS, at offset 0, its two link words per node re-encoded for this kernel's walk
   // (srt_wf_links.h; the hybrid form's records are stored ready-made), empty rings, every context waits for an item
@@ -170,100 +155,14 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   // cycles a reserved place may still be unwritten.  Slots are re-used only after their consumer emptied them.
   // What a producer wrote for the context BEFORE (global stores: the caller fences; LDS: one wave's LDS operations
   // execute in order) is visible to the consumer that finds the id.
-  // `ring` < 0: this lane enqueues nothing.  All rings of one call are served together: one atomic per ring, issued side
-  // by side by the first lanes of the wave, then one look at the slots: two LDS round trips whatever the number of rings.
-  auto enqueue = [&](int ring, int id) {
-    int n = 0;  // lane r < WF_RINGS: how many lanes of this wave enqueue to ring r
-#pragma unroll
-    for (int r = 0; r < WF_RINGS; ++r) {
-      const int c = __popcll(__ballot(ring == r));
-      n = lane == r ? c : n;
-    }
-    int base = 0;
-    if (lane < WF_RINGS && n > 0) base = __hip_atomic_fetch_add(&ctl[WF_CTL_TAIL(lane)], n, __ATOMIC_RELAXED, WF_WG);
-    int myBase = 0;
-    unsigned long long mine = 0;
-#pragma unroll
-    for (int r = 0; r < WF_RINGS; ++r) {
-      const int b = __builtin_amdgcn_readlane(base, r);
-      const unsigned long long m = __ballot(ring == r);
-      if (ring == r) {
-        myBase = b;
-        mine = m;
-      }
-    }
-    if (ring >= 0) {
-      uint16_t* const s = ringSlots + ring * RCAP + ringPos((uint32_t)(myBase + __popcll(mine & laneBelow)));
-      // (first look outside the loop: a loop header makes the compiler wait for every load the caller has in flight)
-      if (__hip_atomic_load(s, __ATOMIC_RELAXED, WF_WG) != 0) {
-        int spins = 0;
-        while (__hip_atomic_load(s, __ATOMIC_RELAXED, WF_WG) != 0) {
-          if (++spins > WF_SPIN_LIMIT) {
-            raiseAbort();
-            break;
-          }
-        }
-      }
-      __hip_atomic_store(s, (uint16_t)(id + 1), __ATOMIC_RELAXED, WF_WG);
-    }
-  };
-  // claims up to `want` entries (none unless at least `atLeast` are there) for the lanes of `takers` in lane order;
-  // returns how many, and the id for the lanes that got one (-1 otherwise).  Wave-uniform call.
-  auto claim = [&](int r, unsigned long long takers, int want, int atLeast, int& id) -> int {
-    int h = 0, k = 0;
-    if (lane == 0) {
-      const unsigned long long th = __hip_atomic_load(reinterpret_cast<unsigned long long*>(&ctl[WF_CTL_TAIL(r)]), __ATOMIC_RELAXED, WF_WG);
-      int t = (int)th;
-      h = (int)(th >> 32);
-      // first attempt outside the loop (as in enqueue: no loop header on the common path)
-      bool again = false;
-      {
-        const int avail = (int)((uint32_t)t - (uint32_t)h);
-        k = avail < want ? avail : want;
-        if (k < atLeast || k <= 0) {
-          k = 0;
-        } else {
-          int expected = h;
-          if (!__hip_atomic_compare_exchange_strong(&ctl[WF_CTL_HEAD(r)], &expected, h + k, __ATOMIC_RELAXED, __ATOMIC_RELAXED, WF_WG)) {
-            h = expected;  // another wave claimed meanwhile: the tail can only have grown
-            again = true;
-          }
-        }
-      }
-      while (again) {
-        t = __hip_atomic_load(&ctl[WF_CTL_TAIL(r)], __ATOMIC_RELAXED, WF_WG);
-        const int avail = (int)((uint32_t)t - (uint32_t)h);
-        k = avail < want ? avail : want;
-        if (k < atLeast || k <= 0) {
-          k = 0;
-          break;
-        }
-        int expected = h;
-        if (__hip_atomic_compare_exchange_strong(&ctl[WF_CTL_HEAD(r)], &expected, h + k, __ATOMIC_RELAXED, __ATOMIC_RELAXED, WF_WG)) break;
-        h = expected;
-      }
-    }
-    h = __builtin_amdgcn_readfirstlane(h);
-    k = __builtin_amdgcn_readfirstlane(k);
-    id = -1;
-    const int rank = __popcll(takers & laneBelow);
-    if (((takers >> lane) & 1ull) && rank < k) {
-      uint16_t* const s = ringSlots + r * RCAP + ringPos((uint32_t)(h + rank));
-      int v = __hip_atomic_load(s, __ATOMIC_RELAXED, WF_WG);
-      if (v == 0) {
-        int spins = 0;
-        while ((v = __hip_atomic_load(s, __ATOMIC_RELAXED, WF_WG)) == 0) {
-          if (++spins > WF_SPIN_LIMIT) {
-            raiseAbort();
-            break;
-          }
-        }
-      }
-      __hip_atomic_store(s, (uint16_t)0, __ATOMIC_RELAXED, WF_WG);
-      id = v - 1;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    return k;
+  // The two operations are srt_wf_rings.h's; a call site names the rings it can produce (`ring` < 0: this lane enqueues nothing).
+  // The instances over an LDS-resident tree, bound by vector-ALU issue, take the forms specialised per call site; the hybrid
+  // instances keep the generic ones.
+  auto enqueue = [&](auto set, int ring, int id) {
+    if constexpr (HYBRID)
+      srtWfEnqueueGeneric(ctl, ringSlots, ringGeom, lane, laneBelow, ring, id, raiseAbort);
+    else
+      srtWfEnqueue<decltype(set)::value>(ctl, ringSlots, ringGeom, lane, ring, id, raiseAbort);
   };
 
   // ---- lane state: a traversal engine
@@ -514,13 +413,19 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
       // asked for first and arrive while the finished walks are handed over (LDS traffic only).
       const bool fin = cur == DONE && path >= 0;
       const bool hit = fin && hitRef != DONE;
-      const unsigned long long mNeed = __ballot(path < 0 || fin);
+      const bool need = path < 0 || fin;
+      const unsigned long long mNeed = __ballot(need);
       int id = -1;
       // the class of the hit primitive's material picks the ring: asked for first, it is there when the claim is done
       int cls = 0;
       if (hit) cls = (int)__builtin_amdgcn_raw_buffer_load_b8(rsClass, ~hitRef, 0, 0);
       const unsigned long long q0 = PROFILE ? clock64() : 0;
-      if (mNeed != 0) claim(WF_RING_READY, mNeed, __popcll(mNeed), 1, id);
+      if (mNeed != 0) {
+        if constexpr (HYBRID)
+          srtWfClaimGeneric(ctl, ringSlots, ringGeom, lane, laneBelow, WF_RING_READY, mNeed, __popcll(mNeed), 1, id, raiseAbort);
+        else
+          srtWfClaim(ctl, ringSlots, ringGeom, lane, WF_RING_READY, need, mNeed, __popcll(mNeed), 1, id, raiseAbort);
+      }
       const unsigned long long q1 = PROFILE ? clock64() : 0;
       float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A;
       if (id >= 0) {
@@ -534,7 +439,8 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
         __hip_atomic_store(&hitPrim[path], (PrimSlot)hitRef, __ATOMIC_RELAXED, WF_WG);
       }
       asm volatile("" ::: "memory");  // the ring slot is written after them (one wave's LDS operations execute in order)
-      enqueue(!fin ? -1 : (hit ? WF_RING_HIT + cls : WF_RING_RESTART), path);
+      enqueue(WF_SET_OF(WF_SET(WF_RING_RESTART) | WF_SET(WF_RING_HIT) | WF_SET(WF_RING_HIT + 1) | WF_SET(WF_RING_HIT + 2)),
+              !fin ? -1 : (hit ? WF_RING_HIT + cls : WF_RING_RESTART), path);
       if constexpr (COUNT) {
         if (fin && aovPixel >= 0) {  // as srt_render_kernel's writeAov: the finished walk's ray, hit and counters
           SrtAovRecord r;
@@ -592,7 +498,11 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
       // ------------------------------------------------ serve a ring: 64 contexts in the same state
       int id;
       const unsigned long long h0 = PROFILE ? clock64() : 0;
-      const int k = claim(bestRing, ~0ull, 64, serveAtLeast, id);
+      int k;
+      if constexpr (HYBRID)
+        k = srtWfClaimGeneric(ctl, ringSlots, ringGeom, lane, laneBelow, bestRing, ~0ull, 64, serveAtLeast, id, raiseAbort);
+      else
+        k = srtWfClaimAll(ctl, ringSlots, ringGeom, lane, bestRing, 64, serveAtLeast, id, raiseAbort);
       if (k == 0) {  // another wave took them
         prof(8, 0);
         return 0;
@@ -670,7 +580,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           __builtin_amdgcn_raw_buffer_store_b128(Cn, rsPool, at + 32, 0, 0);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        enqueue(toReady ? WF_RING_READY : (toRestart ? WF_RING_RESTART : -1), id);
+        enqueue(WF_SET_OF(WF_SET(WF_RING_READY) | WF_SET(WF_RING_RESTART)), toReady ? WF_RING_READY : (toRestart ? WF_RING_RESTART : -1), id);
         prof(3 + bestRing - WF_RING_HIT, k);
       } else if (bestRing == WF_RING_RESTART) {
         // ---------------------------- a sample is in: miss / path end (main.cpp:39-40,49-51), pixel sum (main.cpp:217),
@@ -736,7 +646,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        enqueue(toReady ? WF_RING_READY : (toNewItem ? WF_RING_NEWITEM : -1), id);
+        enqueue(WF_SET_OF(WF_SET(WF_RING_READY) | WF_SET(WF_RING_NEWITEM)), toReady ? WF_RING_READY : (toNewItem ? WF_RING_NEWITEM : -1), id);
         prof(6, k);
       } else {
         // ---------------------------- the next work item for every context here, with one atomic for the wave
@@ -750,7 +660,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           int base = 0;
           if (lane == 0) base = atomicAdd(a.queue + 16 * q, __popcll(mF2));
           base = __builtin_amdgcn_readfirstlane(base);
-          idx = base + __popcll(mF2 & laneBelow);
+          idx = HYBRID ? base + __popcll(mF2 & laneBelow) : (int)srtWfReservePlace((uint32_t)base, mF2, lane);
           const int qEnd = queueEnd(q);
           gotItem = need && idx < qEnd;
           if (base + __popcll(mF2) > qEnd) {
@@ -835,7 +745,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        enqueue(toReady ? WF_RING_READY : (again ? WF_RING_NEWITEM : -1), id);
+        enqueue(WF_SET_OF(WF_SET(WF_RING_READY) | WF_SET(WF_RING_NEWITEM)), toReady ? WF_RING_READY : (again ? WF_RING_NEWITEM : -1), id);
         const unsigned long long mR = __ballot(retired);
         if (mR != 0 && lane == __ffsll((long long)mR) - 1) __hip_atomic_fetch_sub(&ctl[WF_CTL_LIVE], __popcll(mR), __ATOMIC_RELAXED, WF_WG);
         prof(9, k);
