@@ -970,6 +970,89 @@ int srtTraceRaysDevice(SrtContext* ctx, const void* dRays, int64_t n, int32_t tr
                        void* stream);
 int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccluded, void* stream);
 
+/* Path steps on device buffers: the pieces of the render's per-sample loop on the caller's DEVICE buffers and stream --
+ * the camera ray of a (pixel, sample), the shading of a hit record, and the two halves of a bounce fused into one kernel
+ * -- with the counter RNG's state as a value the caller carries.  A loop over them in user land (below) is the library's
+ * path tracer, and reproduces srtRenderImage bit for bit.
+ *
+ * srtRngKey             (host only) the state a render gives (pixel, sample) before its first draw:
+ *                       mix64(mix64(seed) ^ (pixel << 32 | sample)), mix64 = the splitmix64 finaliser.  pixel and sample
+ *                       are the renders' 32-bit indices; they are passed as uint64_t and only their low 32 bits are
+ *                       used.  Callers seed streams of their own with it.
+ * srtCameraRaysDevice   the camera ray of every (pixel, sample) entry, and the state after its draws.
+ * srtScatterRaysDevice  material::scatter + material::emitted on every hit record (what srtScatterRays evaluates).
+ * srtPathStepDevice     srtTraceRaysDevice followed by srtScatterRaysDevice in ONE kernel: the form a loop should call (a
+ *                       path does not write an 88-byte SrtHit to memory and read it back between the two halves).
+ *   buffers   all DEVICE pointers.  dRays, dRaysOut = SrtRay[n], aligned to 4 bytes.  dRng = uint64_t[n], aligned to 8:
+ *             entry i is the generator state of path i (a PCG32 state: one 64-bit LCG step and an XSH-RR output per 32-bit
+ *             draw; a float draw is float(u32) * 2^-32, clamped below 1).  Each entry reads it, advances it by exactly the
+ *             draws its work makes, and writes it back.  dOut = SrtPathOut[n], aligned to 16.  dRecords = SrtHit[n],
+ *             aligned to 4, as srtTraceRaysDevice(..., dRecords) writes it (the counters are ignored).  dHits =
+ *             SrtRayHit[n], aligned to 16, may be NULL.  dActive = uint8_t[n], may be NULL.  dPixelSample = int32_t[n][2],
+ *             aligned to 4, may be NULL.  Elements at index >= n are never written.
+ *   async     all three are asynchronous on `stream`, allocate nothing, do not synchronise and touch no scratch of the
+ *             context's: one kernel each.  The buffers must stay untouched until the stream has passed the call.
+ *   untouched the tunables, the host generator, the chunk scratch, srtLastKernelMs, srtGetLaunchInfo, srtGetStats, the
+ *             temporal history.
+ *   n == 0    returns 0 and launches nothing.
+ *   camera    dPixelSample[i] = {pixel index y * W + x, absolute sample index}.  With NULL, n must be W * H * p->spp and
+ *             entry i is pixel i / spp, sample p->sampleFirst + i % spp.  Per entry, in this order: the state is keyed
+ *             srtRngKey(p->seed, pixel, sample); r1 is drawn, u = (x + r1) / (W - 1); r2 is drawn,
+ *             v = ((H - y) + r2) / (H - 1) (main.cpp:210-211); camera::getRay(u, v) (camera.h:40-46) of the camera set with
+ *             srtSetCamera draws the lens disk (y, then x, repeated while x*x + y*y >= 1) and then the time.  Written:
+ *             dRays[i] = {o, d, time, tMin = p->tMin, tMax = +inf} and dRng[i] = the state after those draws.  That is the
+ *             ray the beauty render, the feature pass and the motion pass trace for that sample, bit for bit.  An entry
+ *             whose pixel index lies outside [0, W * H) is left unwritten.  Of p only imageWidth, imageHeight, seed, tMin,
+ *             spp and sampleFirst are read (the last two only without a list).
+ *   scatter   per entry, from dRecords[i]:
+ *               prim == SRT_NO_HIT         dOut[i] = {attenuation 0, SRT_PATH_MISS, emitted 0, prim SRT_NO_HIT}; dRng[i] and
+ *                                          dRaysOut[i] are untouched, dRays[i] is not read.
+ *               material outside [0, numMaterials)
+ *                                          dOut[i] = {0, SRT_PATH_INVALID, 0, the record's prim}; nothing else is read or
+ *                                          written (the kernel bounds the index itself: no record can make it read out of
+ *                                          bounds).
+ *               otherwise                  material::scatter on (dRays[i], the record) with the draws from dRng[i];
+ *                                          emitted = material::emitted, always written; prim = the record's.
+ *                 scatter returned false   status SRT_PATH_ENDED, attenuation 0; dRaysOut[i] untouched; dRng[i] advanced by
+ *                                          what scatter drew before it gave up (a metal's fuzz sphere; nothing for a light).
+ *                 scatter returned true    status SRT_PATH_SCATTERED, the attenuation, and dRaysOut[i] = {o = the hit point,
+ *                                          d = the scattered direction, time = the incoming ray's, tMin and tMax copied
+ *                                          from the incoming ray}.
+ *             dRaysOut may equal dRays: an entry reads its ray before it writes it.  With dRng[i] = srtRngKey(seed, i, 0)
+ *             the attenuation, the scattered ray, the flag and the emitted colour equal srtScatterRays' out13 bit for bit (a
+ *             light's unspecified "scattered ray" excepted).
+ *   step      for every entry with dActive == NULL or dActive[i] != 0: what srtTraceRaysDevice(traversal, dHits, records)
+ *             of dRays[i] followed by srtScatterRaysDevice on its record leave in dOut[i], dRng[i], dRaysOut[i] and, where
+ *             dHits is not NULL, dHits[i] -- byte for byte.  An inactive entry reads nothing but its byte and writes nothing.
+ *             FAITHFUL and CLOSEST have the meanings, the tie rule and the conditions of "Ray queries" above.
+ *   the loop  one sample of the render is at most maxBounce steps from its camera ray (active = the entries that
+ *             SCATTERED in the step before).  Its terminal radiance is `background` after a MISS, `emitted` after ENDED and
+ *             0 when maxBounce steps all scattered (or maxBounce is 0); its radiance is the terminal one unwound through
+ *             the attenuations of its scattered steps, L = 0.0f + L * attenuation_j per channel (a separate multiply and
+ *             add, no contraction) for j from the last scattered step down to 0 (main.cpp:49-51).  A pixel is the float
+ *             running sum of its samples' L in sample-index order, with w their count (main.cpp:217).  With FAITHFUL
+ *             steps that is srtRenderImage's accumulation buffer bit for bit (sppChunks = 1; more chunks add the same
+ *             samples in the exact chunk sum's order).
+ *   errors    (non-zero, message in srtLastError, NOTHING launched, outputs untouched; all decided on the host) scatter and
+ *             step: no scene uploaded; geometry updated and not yet refitted.  All: n < 0; with n > 0 a NULL or misaligned
+ *             required pointer (every buffer not called optional above).  Step: a traversal that is neither value; a tree
+ *             too deep for the per-lane LDS stacks, as srtTraceRaysDevice refuses it.  Camera: no camera set; an image
+ *             smaller than 2 x 2; without a list, spp < 1 or n != W * H * spp. */
+enum { SRT_PATH_INVALID = -1, SRT_PATH_MISS = 0, SRT_PATH_ENDED = 1, SRT_PATH_SCATTERED = 2 };
+typedef struct SrtPathOut { /* 32 bytes, aligned to 16: two dwordx4 stores */
+  float attenuation[3];
+  int32_t status;           /* SRT_PATH_* */
+  float emitted[3];
+  int32_t prim;             /* index into prims[], SRT_NO_HIT on a miss */
+} SrtPathOut;
+uint64_t srtRngKey(uint64_t seed, uint64_t pixel, uint64_t sample); /* pixel and sample are 32-bit values: their low 32 bits */
+int srtCameraRaysDevice(SrtContext* ctx, const SrtRenderParams* p, const void* dPixelSample, int64_t n, void* dRays, void* dRng,
+                        void* stream);
+int srtScatterRaysDevice(SrtContext* ctx, const void* dRays, const void* dRecords, int64_t n, void* dRng, void* dOut,
+                         void* dRaysOut, void* stream);
+int srtPathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays, int64_t n, const void* dActive, void* dRng,
+                      void* dOut, void* dRaysOut, void* dHits, void* stream);
+
 /* material::scatter + material::emitted (material.h:15-21; texture::value through a light's emitted, texture.h:13-16) for
  * n (incoming ray, hit record) pairs, evaluated by the render kernels' own shading function.  hits[i].material indexes
  * the uploaded scene's materials; p, normal, tangent, bitangent, uv, t, frontFace are read as the reference's hitRecord

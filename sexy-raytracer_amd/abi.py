@@ -15,6 +15,8 @@ SRT_BUILDER_REFERENCE, SRT_BUILDER_LBVH, SRT_BUILDER_PLOC = 0, 1, 2
 SRT_TILE_W = SRT_TILE_H = 8
 SRT_TILE_PIXELS = 64
 SRT_NO_HIT = -1
+# path steps on device buffers (srtScatterRaysDevice / srtPathStepDevice): SrtPathOut.status
+SRT_PATH_INVALID, SRT_PATH_MISS, SRT_PATH_ENDED, SRT_PATH_SCATTERED = -1, 0, 1, 2
 # feature planes (srtRenderFeatureTiles / srtRenderFeatureImage): bit 1 << k selects plane k
 SRT_FEATURE_ALBEDO, SRT_FEATURE_NORMAL, SRT_FEATURE_POSITION, SRT_FEATURE_DEPTH = 1, 2, 4, 8
 SRT_FEATURE_ALL = 15
@@ -105,6 +107,10 @@ class SrtRayHit(C.Structure):  # srtTraceRaysDevice: 16 bytes per ray
     _fields_ = [("prim", i32), ("t", f32), ("material", i32), ("frontFace", i32)]
 
 
+class SrtPathOut(C.Structure):  # srtScatterRaysDevice / srtPathStepDevice: 32 bytes per entry
+    _fields_ = [("attenuation", f32 * 3), ("status", i32), ("emitted", f32 * 3), ("prim", i32)]
+
+
 class SrtRenderParams(C.Structure):
     _fields_ = [("imageWidth", i32), ("imageHeight", i32), ("spp", i32), ("maxBounce", i32),
                 ("seed", u64), ("background", f32 * 3), ("tMin", f32), ("traversal", i32),
@@ -152,6 +158,8 @@ HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("normal",
                       ("frontFace", "<i4"), ("material", "<i4"), ("nodeVisits", "<i4"),
                       ("boxPasses", "<i4"), ("triTests", "<i4"), ("sphereTests", "<i4")])
 RAY_HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("material", "<i4"), ("frontFace", "<i4")])
+PATH_OUT_DTYPE = np.dtype([("attenuation", "<f4", 3), ("status", "<i4"), ("emitted", "<f4", 3), ("prim", "<i4")])
+assert PATH_OUT_DTYPE.itemsize == C.sizeof(SrtPathOut) == 32
 AOV_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("time", "<f4"), ("valid", "<i4"), ("prim", "<i4"), ("t", "<f4"),
                       ("nodeVisits", "<i4"), ("boxPasses", "<i4"), ("triTests", "<i4"), ("sphereTests", "<i4"), ("pad", "<i4", 2)])
 assert AOV_DTYPE.itemsize == 64

@@ -211,6 +211,38 @@ struct QueryArgs {
   int64_t n;
 };
 
+// srtCameraRaysDevice / srtScatterRaysDevice / srtPathStepDevice (srt_pathstep.hip): every pointer is the caller's DEVICE
+// memory; rays as nine floats each, rng = Pcg::state per entry, out = SrtPathOut as two int4 per entry
+struct CameraRaysArgs {
+  DevCamera cam;
+  int32_t imageWidth, imageHeight, spp, sampleFirst;
+  uint64_t seed;
+  float tMin;
+  const int32_t* pixelSample;  // {pixel index, absolute sample index} per entry, or null: entry i = (i / spp, sampleFirst + i % spp)
+  float* rays;
+  uint64_t* rng;
+  int64_t n;
+};
+struct ScatterDeviceArgs {
+  DevScene scene;
+  const float* rays;
+  const SrtHit* records;
+  uint64_t* rng;
+  int4* out;
+  float* raysOut;  // may be `rays`
+  int64_t n;
+};
+struct PathStepArgs {
+  DevScene scene;
+  const float* rays;
+  const uint8_t* active;  // or null: every entry
+  uint64_t* rng;
+  int4* out;
+  float* raysOut;  // may be `rays`
+  int4* hits;      // SrtRayHit[n], or null
+  int64_t n;
+};
+
 // srtRenderFeatureTiles (srt_features.hip): the first hit of every camera ray the beauty render traces, as feature planes
 // in the beauty tiles' layout
 struct FeatureArgs {

@@ -25,6 +25,11 @@ int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hit
 // srt_query.hip: mode = SRT_TRAVERSE_FAITHFUL, SRT_TRAVERSE_CLOSEST or 2 (any hit, into a->occluded)
 int srt_launch_query(const QueryArgs* a, int mode, int grid, size_t ldsBytes, hipStream_t stream);
 
+// srt_pathstep.hip: one kernel each; traversal = SRT_TRAVERSE_FAITHFUL or SRT_TRAVERSE_CLOSEST, ldsBytes as srt_launch_query's
+int srt_launch_camera_rays(const CameraRaysArgs* a, int grid, hipStream_t stream);
+int srt_launch_scatter_device(const ScatterDeviceArgs* a, int grid, hipStream_t stream);
+int srt_launch_path_step(const PathStepArgs* a, int traversal, int grid, size_t ldsBytes, hipStream_t stream);
+
 // srt_lbvh.hip: the device tree builders (blocking) and the closest-hit traversal's pair records
 int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
                    uint8_t* outAxis, int base, int* depthOut);

@@ -557,6 +557,139 @@ int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccl
   SRT_GUARDED(ctx, queryDevice(ctx, "srtOccludedDevice", dRays, n, true, 0, nullptr, nullptr, dOccluded, stream));
 }
 
+// srtCameraRaysDevice / srtScatterRaysDevice / srtPathStepDevice (include/srt_hip.h "Path steps on device buffers"):
+// as queryDevice -- every check on the host, then one launch of srt_pathstep.hip on the caller's stream, and nothing of
+// the context changes.
+
+// srt_path.h mix64 on the host (the kernels' copy is device code); tests/test_pathstep_abi.py pins srtRngKey to the oracle
+static uint64_t hostMix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+uint64_t srtRngKey(uint64_t seed, uint64_t pixel, uint64_t sample) {  // the low 32 bits of pixel and of sample
+  return hostMix64(hostMix64(seed) ^ ((pixel << 32) | (sample & 0xffffffffull)));
+}
+
+static int pathGrid(const SrtContext* ctx, int64_t n) {
+  return (int)std::min<int64_t>((n + SRT_BLOCK - 1) / SRT_BLOCK, (int64_t)ctx->prop.multiProcessorCount * 8);
+}
+
+// a required device pointer of `what`: non-null and aligned
+static int checkPointer(SrtContext* ctx, const char* what, const char* name, const void* p, int align) {
+  if (!p) return fail(ctx, "%s: null %s", what, name);
+  if ((uintptr_t)p % align) return fail(ctx, "%s: the %s are not aligned to %d bytes", what, name, align);
+  return 0;
+}
+
+static int cameraRaysDevice(SrtContext* ctx, const SrtRenderParams* p, const void* dPixelSample, int64_t n, void* dRays, void* dRng,
+                            void* streamPtr) {
+  const char* what = "srtCameraRaysDevice";
+  if (!ctx) return 1;
+  if (!p) return fail(ctx, "%s: null parameters", what);
+  if (!ctx->haveCamera) return fail(ctx, "%s: no camera set", what);
+  if (p->imageWidth < 2 || p->imageHeight < 2) return fail(ctx, "%s: image must be at least 2x2 (u,v divide by W-1,H-1)", what);
+  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
+  if (!dPixelSample) {
+    if (p->spp < 1) return fail(ctx, "%s: spp must be >= 1 without a list", what);
+    const int64_t all = (int64_t)p->imageWidth * p->imageHeight * p->spp;
+    if (n != all) return fail(ctx, "%s: n = %lld without a list, the frame has %lld samples", what, (long long)n, (long long)all);
+  }
+  if (n == 0) return 0;
+  if ((uintptr_t)dPixelSample % 4) return fail(ctx, "%s: the list is not aligned to 4 bytes", what);
+  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "rng states", dRng, 8)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  CameraRaysArgs a;
+  a.cam = ctx->cam;
+  a.imageWidth = p->imageWidth;
+  a.imageHeight = p->imageHeight;
+  a.spp = std::max(p->spp, 1);
+  a.sampleFirst = p->sampleFirst;
+  a.seed = p->seed;
+  a.tMin = p->tMin;
+  a.pixelSample = static_cast<const int32_t*>(dPixelSample);
+  a.rays = static_cast<float*>(dRays);
+  a.rng = static_cast<uint64_t*>(dRng);
+  a.n = n;
+  const int e = srt_launch_camera_rays(&a, pathGrid(ctx, n), static_cast<hipStream_t>(streamPtr));
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+static int scatterDevice(SrtContext* ctx, const void* dRays, const void* dRecords, int64_t n, void* dRng, void* dOut, void* dRaysOut,
+                         void* streamPtr) {
+  const char* what = "srtScatterRaysDevice";
+  if (!ctx) return 1;
+  if (checkSceneReady(ctx, what)) return 1;
+  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
+  if (n == 0) return 0;
+  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "records", dRecords, 4) ||
+      checkPointer(ctx, what, "rng states", dRng, 8) || checkPointer(ctx, what, "outputs", dOut, 16) ||
+      checkPointer(ctx, what, "scattered rays", dRaysOut, 4))
+    return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  ScatterDeviceArgs a;
+  a.scene = ctx->upload.scene;
+  a.rays = static_cast<const float*>(dRays);
+  a.records = static_cast<const SrtHit*>(dRecords);
+  a.rng = static_cast<uint64_t*>(dRng);
+  a.out = static_cast<int4*>(dOut);
+  a.raysOut = static_cast<float*>(dRaysOut);
+  a.n = n;
+  const int e = srt_launch_scatter_device(&a, pathGrid(ctx, n), static_cast<hipStream_t>(streamPtr));
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+static int pathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays, int64_t n, const void* dActive, void* dRng, void* dOut,
+                          void* dRaysOut, void* dHits, void* streamPtr) {
+  const char* what = "srtPathStepDevice";
+  if (!ctx) return 1;
+  if (checkSceneReady(ctx, what)) return 1;
+  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
+  if (traversal != SRT_TRAVERSE_FAITHFUL && traversal != SRT_TRAVERSE_CLOSEST)
+    return fail(ctx, "%s: traversal %d is neither SRT_TRAVERSE_FAITHFUL nor SRT_TRAVERSE_CLOSEST", what, traversal);
+  if (n == 0) return 0;
+  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "rng states", dRng, 8) ||
+      checkPointer(ctx, what, "outputs", dOut, 16) || checkPointer(ctx, what, "scattered rays", dRaysOut, 4))
+    return 1;
+  if ((uintptr_t)dHits % 16) return fail(ctx, "%s: the hits are not aligned to 16 bytes", what);
+  const DevScene& sc = ctx->upload.scene;
+  // the walk's stacks, as queryDevice sizes and bounds them
+  const size_t lds = (size_t)(std::max(sc.stackDepth, 1) + 2) * SRT_BLOCK * sizeof(int32_t);
+  if (lds > 160 * 1024) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  PathStepArgs a;
+  a.scene = sc;
+  a.rays = static_cast<const float*>(dRays);
+  a.active = static_cast<const uint8_t*>(dActive);
+  a.rng = static_cast<uint64_t*>(dRng);
+  a.out = static_cast<int4*>(dOut);
+  a.raysOut = static_cast<float*>(dRaysOut);
+  a.hits = static_cast<int4*>(dHits);
+  a.n = n;
+  const int e = srt_launch_path_step(&a, traversal, pathGrid(ctx, n), lds, static_cast<hipStream_t>(streamPtr));
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+int srtCameraRaysDevice(SrtContext* ctx, const SrtRenderParams* p, const void* dPixelSample, int64_t n, void* dRays, void* dRng,
+                        void* stream) {
+  SRT_GUARDED(ctx, cameraRaysDevice(ctx, p, dPixelSample, n, dRays, dRng, stream));
+}
+
+int srtScatterRaysDevice(SrtContext* ctx, const void* dRays, const void* dRecords, int64_t n, void* dRng, void* dOut, void* dRaysOut,
+                         void* stream) {
+  SRT_GUARDED(ctx, scatterDevice(ctx, dRays, dRecords, n, dRng, dOut, dRaysOut, stream));
+}
+
+int srtPathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays, int64_t n, const void* dActive, void* dRng, void* dOut,
+                      void* dRaysOut, void* dHits, void* stream) {
+  SRT_GUARDED(ctx, pathStepDevice(ctx, traversal, dRays, n, dActive, dRng, dOut, dRaysOut, dHits, stream));
+}
+
 // test entries: material::scatter known answers through the kernels' own shade(), in the instance `form` selects
 // (bit 0 WIDE, bit 1 COUNT: include/srt_hip_test.h)
 

@@ -33,6 +33,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtUploadScene", "srtSetCamera", "srtBuildBvh", "srtGetBvh", "srtGetBvhDepth", "srtNumTiles", "srtNumLocalTiles", "srtDefaultSppChunks", "srtPlanSppChunks",
            "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtTraceRaysDevice", "srtOccludedDevice", "srtScatterRays",
+           "srtRngKey", "srtCameraRaysDevice", "srtScatterRaysDevice", "srtPathStepDevice",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
@@ -131,6 +132,11 @@ lib.srtTemporalReprojectMotion.argtypes = [_vp, C.POINTER(abi.SrtTemporalParams)
 lib.srtTraceRays.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
 lib.srtTraceRaysDevice.argtypes = [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]
 lib.srtOccludedDevice.argtypes = [_vp, _vp, C.c_int64, _vp, _vp]
+lib.srtRngKey.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+lib.srtRngKey.restype = C.c_uint64
+lib.srtCameraRaysDevice.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, C.c_int64, _vp, _vp, _vp]
+lib.srtScatterRaysDevice.argtypes = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]
+lib.srtPathStepDevice.argtypes = [_vp, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
 lib.srtGatherTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
@@ -169,6 +175,12 @@ def make_camera(params):
     if lib.srtMakeCamera(C.byref(params), C.byref(cam)):
         raise SrtError("srtMakeCamera failed")
     return cam
+
+
+def rng_key(seed, pixel, sample):
+    """srtRngKey: the generator state a render gives (pixel, sample) before its first draw, as a Python int in [0, 2^64).
+    (A torch int64 tensor of states holds the same bits: subtract 2^64 from a value of 2^63 or more.)"""
+    return int(lib.srtRngKey(int(seed) & (2 ** 64 - 1), int(pixel) & 0xffffffff, int(sample) & 0xffffffff))
 
 
 def host_random_reset():
@@ -705,6 +717,84 @@ class Context:
         self._check(lib.srtOccludedDevice(self.h, rays.data_ptr() if n else None, n, out.data_ptr() if n else None,
                                           self._stream_handle(stream)))
         return out
+
+    @staticmethod
+    def _device_tensor(t, what, dtype, shape, like=None):
+        """A buffer of a path step: a contiguous torch tensor on the GPU of this dtype and shape (-1: any); `like`: on the same
+        device as that tensor."""
+        if not hasattr(t, "data_ptr") or not hasattr(t, "is_cuda"):
+            raise ValueError("%s must be a torch tensor on the GPU" % what)
+        if str(t.dtype) != "torch." + dtype:
+            raise ValueError("%s must be %s, not %s" % (what, dtype, t.dtype))
+        if t.dim() != len(shape) or any(want >= 0 and got != want for got, want in zip(t.shape, shape)):
+            raise ValueError("%s must have shape %s, not %s" % (what, tuple("n" if s < 0 else s for s in shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % what)
+        if not t.is_cuda:
+            raise ValueError("%s must live on the GPU, not on %s" % (what, t.device))
+        if like is not None and t.device != like.device:
+            raise ValueError("%s must live on the GPU of the rays (%s), not on %s" % (what, like.device, t.device))
+        return t
+
+    def camera_rays_device(self, params, pixel_sample=None, device=None, stream=None):
+        """srtCameraRaysDevice: the camera ray the renders trace for every (pixel, sample) entry, and the generator state
+        after its draws, asynchronous on `stream`.  pixel_sample: a contiguous int32 tensor (n, 2) on the GPU holding
+        {pixel index y * W + x, absolute sample index}, or None for every sample of the frame (entry i = pixel i // spp,
+        sample sampleFirst + i % spp; `device` then names the GPU, default the current one).  Returns (rays, rng): float32
+        (n, 9) laid out as SrtRay with tMin = params.tMin and tMax = +inf, and int64 (n,) holding the 64-bit states.  An
+        entry whose pixel lies outside the image is left as torch.empty made it."""
+        import torch
+        if pixel_sample is None:
+            n = params.imageWidth * params.imageHeight * params.spp
+            device = torch.device("cuda" if device is None else device)
+        else:
+            pixel_sample = self._device_tensor(pixel_sample, "pixel_sample", "int32", (-1, 2))
+            n, device = pixel_sample.shape[0], pixel_sample.device
+        rays = torch.empty((n, 9), dtype=torch.float32, device=device)
+        rng = torch.empty((n,), dtype=torch.int64, device=device)
+        self._check(lib.srtCameraRaysDevice(self.h, C.byref(params), pixel_sample.data_ptr() if pixel_sample is not None and n else None,
+                                            n, rays.data_ptr() if n else None, rng.data_ptr() if n else None,
+                                            self._stream_handle(stream)))
+        return rays, rng
+
+    def scatter_device(self, rays, records, rng, rays_out=None, stream=None):
+        """srtScatterRaysDevice: material::scatter and material::emitted on every (ray, hit record) pair, asynchronous on
+        `stream`.  rays: float32 (n, 9); records: int32 (n, 22) as trace_device(records=True) returns them; rng: int64 (n,),
+        the generator states, advanced IN PLACE by the draws made; rays_out: float32 (n, 9) that receives the scattered
+        rays (may be `rays` itself; allocated when None -- rows that did not scatter then hold whatever torch.empty left).
+        Returns (out, rays_out): out int32 (n, 8) laid out as SrtPathOut {attenuation's bits[3], status, emitted's
+        bits[3], prim} (out.view(torch.float32) for the colours; status is one of abi.SRT_PATH_*)."""
+        import torch
+        rays = self._device_rays(rays)
+        n = rays.shape[0]
+        records = self._device_tensor(records, "records", "int32", (n, C.sizeof(abi.SrtHit) // 4), rays)
+        rng = self._device_tensor(rng, "rng", "int64", (n,), rays)
+        rays_out = torch.empty_like(rays) if rays_out is None else self._device_tensor(rays_out, "rays_out", "float32", (n, 9), rays)
+        out = torch.empty((n, 8), dtype=torch.int32, device=rays.device)
+        ptr = (lambda t: t.data_ptr()) if n else (lambda t: None)
+        self._check(lib.srtScatterRaysDevice(self.h, ptr(rays), ptr(records), n, ptr(rng), ptr(out), ptr(rays_out),
+                                             self._stream_handle(stream)))
+        return out, rays_out
+
+    def path_step_device(self, rays, rng, traversal=abi.SRT_TRAVERSE_CLOSEST, active=None, rays_out=None, hits=False, stream=None):
+        """srtPathStepDevice: one bounce in one kernel -- trace_device followed by scatter_device on its records, byte for
+        byte, without the records' round trip through memory.  rays, rng, rays_out and the returned out as scatter_device's;
+        active: uint8 (n,), entries with a 0 are neither read nor written (None: all).  Returns (out, rays_out), with
+        hits=True (out, rays_out, hits), hits as trace_device returns them.  Rows of inactive entries in a tensor allocated
+        here hold whatever torch.empty left."""
+        import torch
+        rays = self._device_rays(rays)
+        n = rays.shape[0]
+        rng = self._device_tensor(rng, "rng", "int64", (n,), rays)
+        if active is not None:
+            active = self._device_tensor(active, "active", "uint8", (n,), rays)
+        rays_out = torch.empty_like(rays) if rays_out is None else self._device_tensor(rays_out, "rays_out", "float32", (n, 9), rays)
+        out = torch.empty((n, 8), dtype=torch.int32, device=rays.device)
+        d_hits = torch.empty((n, 4), dtype=torch.int32, device=rays.device) if hits else None
+        ptr = (lambda t: t.data_ptr() if t is not None else None) if n else (lambda t: None)
+        self._check(lib.srtPathStepDevice(self.h, int(traversal), ptr(rays), n, ptr(active), ptr(rng), ptr(out), ptr(rays_out),
+                                          ptr(d_hits), self._stream_handle(stream)))
+        return (out, rays_out, d_hits) if hits else (out, rays_out)
 
     def scatter_test(self, rays, hits, seed):
         rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)

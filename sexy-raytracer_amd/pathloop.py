@@ -1,0 +1,76 @@
+"""The library's path tracer as a user-land loop over its device path steps (include/srt_hip.h "Path steps on device
+buffers"): camera rays, then one step per bounce, then the unwinding, all on torch tensors that never leave the GPU.
+
+With FAITHFUL steps render() reproduces Context.render_image's accumulation buffer bit for bit (sppChunks = 1); it is the
+worked example for integrators of one's own (ambient occlusion with materials, direct-light passes, path-length AOVs):
+everything between two steps is an ordinary torch op on `out`, `rays` and `active`.
+
+Plumbing only: no arithmetic of the hot path lives here beyond the loop's stated multiply, add and running sum."""
+from . import abi
+
+_DEAD = -2  # a status no step writes: an entry that was not active in this step
+
+
+def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_FAITHFUL, fused=True, stream=None,
+                    active_counts=None):
+    """The radiance of one path per ray: at most max_bounce steps, then the unwinding.  rays (n, 9) float32 and rng (n,)
+    int64 as Context.camera_rays_device returns them; both are overwritten.  fused: one path_step_device per bounce;
+    otherwise trace_device(records=True) + scatter_device, which compute the same bytes through an 88-byte record per ray.
+    active_counts: a list that receives, per bounce, the number of entries still on their way (a 0-dim tensor: reading it
+    synchronises, so read it after the loop).  Returns (n, 3) float32."""
+    import torch
+    n = rays.shape[0]
+    bg = torch.tensor([float(c) for c in background], dtype=torch.float32, device=rays.device)
+    terminal = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)  # maxBounce steps all scattered: black
+    active = torch.ones((n,), dtype=torch.uint8, device=rays.device)
+    steps = []  # per step: (attenuation (n, 3), scattered (n,) bool)
+    for _ in range(max_bounce):
+        if active_counts is not None:
+            active_counts.append(active.sum(dtype=torch.int64))
+        if fused:
+            out, _ = ctx.path_step_device(rays, rng, traversal, active=active, rays_out=rays, stream=stream)
+        else:
+            # the queries have no mask: a finished entry's ray is given an empty interval, so that its walk ends at the root
+            rays[:, 8].masked_fill_(active == 0, 0.0)
+            _, records = ctx.trace_device(rays, traversal, records=True, stream=stream)
+            out, _ = ctx.scatter_device(rays, records, rng, rays_out=rays, stream=stream)
+        status = torch.where(active != 0, out[:, 3], torch.full_like(out[:, 3], _DEAD))
+        colours = out.view(torch.float32)
+        scattered = status == abi.SRT_PATH_SCATTERED
+        terminal = torch.where((status == abi.SRT_PATH_MISS)[:, None], bg, terminal)
+        terminal = torch.where((status == abi.SRT_PATH_ENDED)[:, None], colours[:, 4:7], terminal)
+        steps.append((colours[:, 0:3], scattered))
+        active = scattered.to(torch.uint8)
+    # emitted + newColor * attenuation with emitted = 0, innermost first (main.cpp:49-51): a multiply, then an add
+    radiance = terminal
+    for attenuation, scattered in reversed(steps):
+        radiance = torch.where(scattered[:, None], radiance * attenuation + 0.0, radiance)
+    return radiance
+
+
+def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples_per_batch=None, device=None, active_counts=None):
+    """params.spp samples of every pixel from params.sampleFirst on, through the device path steps: the (H, W, 4) float32
+    torch tensor of per-pixel radiance sums (the float running sum in sample-index order) with the sample count in w --
+    Context.render_image's accumulation buffer.  samples_per_batch: how many sample indices of the whole frame go through
+    the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  Runs on torch's current stream."""
+    import torch
+    device = torch.device("cuda" if device is None else device)
+    W, H, spp = params.imageWidth, params.imageHeight, params.spp
+    pixels = W * H
+    batch = spp if not samples_per_batch else max(1, min(int(samples_per_batch), spp))
+    image = torch.zeros((pixels, 4), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device)
+        pixel = torch.arange(pixels, dtype=torch.int32, device=device)
+        for first in range(0, spp, batch):
+            count = min(batch, spp - first)
+            # sample-major entries: the samples of one index are one contiguous slice of the batch
+            pixel_sample = torch.stack((pixel.repeat(count),
+                                        torch.arange(params.sampleFirst + first, params.sampleFirst + first + count, dtype=torch.int32,
+                                                     device=device).repeat_interleave(pixels)), dim=1).contiguous()
+            rays, rng = ctx.camera_rays_device(params, pixel_sample, stream=stream)
+            radiance = sample_radiance(ctx, rays, rng, params.maxBounce, params.background, traversal, fused, stream, active_counts)
+            for k in range(count):
+                image[:, 0:3] += radiance[k * pixels:(k + 1) * pixels]
+        image[:, 3] = float(spp)
+    return image.view(H, W, 4)

@@ -13,8 +13,13 @@ per ray in, 88 B per ray out, a device synchronisation -- and its kernel keeps t
 through the only entry there was, not a kernel comparison.
 --ao-png FILE writes the AO image 1 - mean(occluded) of the first scene.  Prints one JSON line.
 
+--path-loop measures the device path steps instead (path_loop below): pathloop.render fused and unfused against
+srtRenderTiles on masterchief (reference tree FAITHFUL, PLOC tree CLOSEST) and soup_200k (PLOC, CLOSEST), 4 and 16 spp,
+4 bounces, with the active share of the entries per bounce.
+
 usage: python tools/query_bench.py [--steps 200] [--warmup 5] [--host-steps 3] [--cases masterchief,soup_200k,soup_1m] [--ao-rays 4]
-                                   [--ao-radius 0.1] [--ao-png FILE] [--width 1280] [--height 720]"""
+                                   [--ao-radius 0.1] [--ao-png FILE] [--width 1280] [--height 720]
+       python tools/query_bench.py --path-loop [--loop-reps 5] [--warmup-loops 1] [--cases masterchief,soup_200k]"""
 import argparse
 import importlib
 import json
@@ -121,8 +126,66 @@ def measure(ctx, rays, faithful, steps, warmup, host_steps):
     return out, occ
 
 
+def path_loop(a):
+    """--path-loop: the user-land path tracer (pathloop.render over srtCameraRaysDevice + srtPathStepDevice, fused, and
+    over srtTraceRaysDevice(records) + srtScatterRaysDevice, unfused) against srtRenderTiles of the same samples.
+    Events around whole loops after a warm-up; the three alternate within one session, --loop-reps times, and every
+    figure is the median with the spread (min, max) beside it."""
+    pathloop = importlib.import_module("sexy-raytracer_amd.pathloop")
+    ctx = dev.Context(0)
+    cam = dev.make_camera(abi.default_camera_params())
+    W, H, bounces = a.width, a.height, 4
+    result = {"device": ctx.device_info()["name"], "width": W, "height": H, "max_bounce": bounces, "reps": a.loop_reps,
+              "note": "msamples_s = W * H * spp / median ms; spread = (min ms, max ms) over the alternating repetitions", "cases": {}}
+    cases = [("masterchief_reference_faithful", "masterchief", None, abi.SRT_TRAVERSE_FAITHFUL),
+             ("masterchief_ploc_closest", "masterchief", abi.SRT_BUILDER_PLOC, abi.SRT_TRAVERSE_CLOSEST),
+             ("soup_200k_ploc_closest", "soup_200k", None, abi.SRT_TRAVERSE_CLOSEST)]
+    stream = torch.cuda.current_stream()
+    for label, case, builder, traversal in cases:
+        if case not in a.cases.split(","):
+            continue
+        sb = scene(case)
+        if builder is not None:
+            for it in sb.world:
+                if it.kind == abi.SRT_WORLD_BVH:
+                    it.builder = builder
+        ctx.upload_scene(sb)
+        ctx.set_camera(cam)
+        tiles = torch.empty((dev.lib.srtNumLocalTiles(W, H, 1) * 64, 4), dtype=torch.float32, device="cuda")
+        out = {"bvh_depth": ctx.bvh_depth()}
+        for spp in (4, 16):
+            p = abi.default_render_params(W, H, spp, bounces, seed=1, traversal=traversal)
+            variants = {"fused": lambda: pathloop.render(ctx, p, fused=True, traversal=traversal),
+                        "unfused": lambda: pathloop.render(ctx, p, fused=False, traversal=traversal),
+                        "render_tiles": lambda: ctx.render_tiles(p, tiles.data_ptr(), stream.cuda_stream)}
+            ms = {k: [] for k in variants}
+            for rep in range(a.warmup_loops + a.loop_reps):
+                for name, fn in variants.items():
+                    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    start.record(stream)
+                    fn()
+                    stop.record(stream)
+                    stop.synchronize()
+                    if rep >= a.warmup_loops:
+                        ms[name].append(start.elapsed_time(stop))
+            counts = []
+            pathloop.render(ctx, p, fused=True, traversal=traversal, active_counts=counts)
+            torch.cuda.synchronize()
+            entry = {"active_share_per_bounce": [int(c) / float(W * H * spp) for c in counts]}
+            for name, v in ms.items():
+                med = float(np.median(v))
+                entry[name] = {"ms": med, "spread_ms": [min(v), max(v)], "msamples_s": W * H * spp / med * 1e-3}
+            out["spp_%d" % spp] = entry
+        result["cases"][label] = out
+    ctx.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--path-loop", action="store_true", help="measure pathloop.render (fused / unfused) against srtRenderTiles instead")
+    ap.add_argument("--loop-reps", type=int, default=5, help="--path-loop: timed repetitions of every variant, alternating")
+    ap.add_argument("--warmup-loops", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed device calls per figure (a call is 0.2 - 3 ms)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--host-steps", type=int, default=3, help="timed srtTraceRays calls (10 - 70 ms each)")
@@ -133,6 +196,8 @@ def main():
     ap.add_argument("--ao-radius", type=float, default=0.1, help="AO tMax as a share of the scene's extent (6 units)")
     ap.add_argument("--ao-png", default=None)
     a = ap.parse_args()
+    if a.path_loop:
+        return path_loop(a)
     ctx = dev.Context(0)
     cam = dev.make_camera(abi.default_camera_params())
     W, H = a.width, a.height
