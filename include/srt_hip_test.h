@@ -110,6 +110,13 @@ int srtTestGetTriUndecided(SrtContext* ctx, uint64_t* out);
 int srtTestGetTriFast(SrtContext* ctx, float* out16, int32_t capacity, int32_t* count);
 int srtTestTriFastRecord(const float* p9, float* out16);
 
+/* The two scene conditions of the certified slab test (csrc/srt_slab.h) as the kernels read them now, after srtUploadScene,
+ * srtRefitScene or srtRebuildScene: out2 = { the fast-division word (the "fast_div" tunable as read at the upload while every
+ * box coordinate is 0 or in [2^-77, 2^30], else 0), 1 while every node box is ordered (min <= max on every axis, all finite) else
+ * 0 }.  The path-pool kernel over a whole LDS-resident tree picks a box's near and far planes by the ray's sign and certifies
+ * a ray only where both hold; every other kernel orders the two quotients itself and asks for the first alone. */
+int srtTestGetSlabScene(SrtContext* ctx, int32_t* out2);
+
 /* The most recent render-kernel launch: out4 = { 0 node records through the L1, 1 the step-scheduler kernel over the
  * LDS-resident threaded tree (FAITHFUL, node array small enough for a CU's LDS; tunable "lds_tree" = 0 switches it
  * off), 2 the same with the attenuation stacks in LDS as well, 3 the path-pool kernel over the same tree (tunable

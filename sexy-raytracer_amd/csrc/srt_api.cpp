@@ -172,6 +172,7 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   s.numMaterials = d->numMaterials;
   s.texelBytes = (int32_t)h.texels.size();
   s.fastDivScene = h.fastDivScene;
+  s.boxOrderedScene = h.boxOrderedScene;
   s.triWMax = triWMaxFor(ctx);
   ctx->upload.bvhDepth = h.bvhDepth;
   // device-built trees (srt_lbvh.hip) into the node slots the flattening reserved.  Their refs stay on the device for
@@ -441,6 +442,15 @@ int srtTestGetTreeAux(SrtContext* ctx, int32_t item, uint8_t* outAxis, float* ou
   if (capacity < n) return fail(ctx, "srtTestGetTreeAux: capacity %d < %d", capacity, n);
   if (outAxis) HIP_OK(ctx, hipMemcpy(outAxis, ctx->upload.scene.nodeAxis + base, (size_t)n, hipMemcpyDeviceToHost));
   if (outPairs16) HIP_OK(ctx, hipMemcpy(outPairs16, ctx->upload.scene.nodes2 + 4 * (size_t)base, (size_t)n * 64, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+/* include/srt_hip_test.h: the certified slab test's scene conditions */
+int srtTestGetSlabScene(SrtContext* ctx, int32_t* out2) {
+  if (!ctx || !out2) return 1;
+  if (!ctx->upload.haveScene) return fail(ctx, "srtTestGetSlabScene: no scene uploaded");
+  out2[0] = ctx->upload.scene.fastDivScene;
+  out2[1] = ctx->upload.scene.boxOrderedScene;
   return 0;
 }
 

@@ -60,6 +60,10 @@ struct DevScene {
   // the certified test decides only where |p - v0|_1 is below this: SRT_TRI_W_MAX, or 0 while the tunable "tri_cert" is 0
   // (nothing is below 0: every lane that passes the plane conditions takes the exact test)
   float triWMax;
+  // 1: every node box is ordered (min <= max on every axis, all finite).  The kernels whose slab test picks the near and
+  // far planes by the ray's sign (srt_slab.h) certify a ray only with this AND fastDivScene (below); the min/max form does
+  // not ask.  (Here, in the four bytes in front of the next pointer: no other field moves.)
+  int32_t boxOrderedScene;
   // 4 x float4 per triangle, read once per shaded hit:
   // (N^.xyz, uv0.u) (T.xyz, uv0.v) (B.xyz, uv1.u) (uv1.v, uv2.u, uv2.v, material)
   const float4* triShade;

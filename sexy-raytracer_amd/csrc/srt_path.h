@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "srt_device.h"
+#include "srt_slab.h"
 #include "srt_tri_hit.h"
 
 #define SRT_TREE_WAVES_PER_SIMD 4
@@ -138,11 +139,7 @@ __device__ __forceinline__ float refinedRcp(float d) {  // within 1.5 ulp of 1/d
   return __builtin_fmaf(e0, r0, r0);
 }
 // direction components in [2^-20, 2^20]; origin components 0 or in [2^-77, 2^30]
-__device__ __forceinline__ bool fastDivOperandOk(float o, float d) {
-  float ad = fabsf(d), ao = fabsf(o);
-  // bitwise: no short-circuit branches (each would cost the wave scalar exec-mask bookkeeping)
-  return (ad >= 0x1p-20f) & (ad <= 0x1p20f) & ((o == 0.0f) | ((ao >= 0x1p-77f) & (ao <= 0x1p30f)));
-}
+__device__ __forceinline__ bool fastDivOperandOk(float o, float d) { return srtSlabOperandOk(o, d); }
 
 // ------------------------------------------------------------------ rays, hits
 struct Ray {
@@ -175,81 +172,39 @@ __device__ __forceinline__ bool boxHit(float4 n0, float4 n1, const Ray& r, float
   return !(tMax <= tMin);
 }
 
-// Slab test decided from one-FMA quotients with an error certificate.
-// The reference computes a = fl(fl(n - o) / d) per plane (aabb.h:14-17).  With r = refinedRcp(d) (within
-// 3u of 1/d, u = 2^-24) and m = fl(-o * r), both per ray, A = fma(n, r, m) satisfies
-//   |A - a| <= 6.2u |A| + 1.03u |o/d|            (one rounding each in r, m, the fma and the reference's
-//                                                  subtraction and division; operands certified normal)
-// i.e. a relative part and an absolute part K <= 2^-23 M, M = max_k |m_k|.  x -> x +- (eps|x| + K) is
-// monotone, so min/max carry the bound through: the approximate interval ends tMinA, tMaxA are within
-// eps|t| + K of the reference's (tMin and the running closest t are exact), and the reference's decision
-// (tMax <= tMin -> miss) is certain whenever |tMaxA - tMinA| > eps (|tMaxA| + |tMinA|) + 2K with
-// eps = 2^-21 (1.3x the bound).  tolAbs = 2K = 2^-22 M per ray, or +inf for a ray outside fastDiv's
-// operand ranges (every visit of such a ray is "undecided" and takes the IEEE divisions).
+// Slab test decided from one-FMA quotients with an error certificate: srt_slab.h holds the one statement of it, in its
+// two forms (per-axis min/max of the two quotients; near and far planes picked by the sign of the ray's reciprocal).
+__device__ __forceinline__ SrtSlab3 slab3(V3 v) { return SrtSlab3{v.x, v.y, v.z}; }
 // Returns the approximate verdict and whether it is uncertain (the caller then runs the exact test).
-// The min/max chain is written with the hardware instructions directly: fminf/fmaxf make the compiler
-// quiet possible signalling NaNs first (a `v_max_f32 x, x` per live-in operand per visit), which buys
-// nothing here -- v_min/v_max already return the other operand when one is a NaN, and the result only
-// feeds the two comparisons of the certificate.
-__device__ __forceinline__ float hwMin(float a, float b) {
-  float r;
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float hwMax(float a, float b) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float hwMin3(float a, float b, float c) {
-  float r;
-  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ float hwMax3(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-// b: wave-uniform (a kernel argument), read from its scalar register
-__device__ __forceinline__ float hwMaxUniform(float a, float b) {
-  float r;
-  asm("v_max_f32 %0, %2, %1" : "=v"(r) : "v"(a), "s"(b));
-  return r;
-}
 // UNIFORM_TMIN: tMin is wave-uniform (a kernel argument) and is read from its scalar register
 template <bool UNIFORM_TMIN>
 __device__ __forceinline__ bool boxHitApprox(float4 n0, float4 n1, V3 r1, V3 m, float tolAbs, float tMin, float tMax,
                                              bool& undecided) {
-  const float ax = __builtin_fmaf(n0.x, r1.x, m.x), bx = __builtin_fmaf(n1.x, r1.x, m.x);
-  const float ay = __builtin_fmaf(n0.y, r1.y, m.y), by = __builtin_fmaf(n1.y, r1.y, m.y);
-  const float az = __builtin_fmaf(n0.z, r1.z, m.z), bz = __builtin_fmaf(n1.z, r1.z, m.z);
-  const float lo = hwMax3(hwMin(ax, bx), hwMin(ay, by), hwMin(az, bz));
-  tMin = UNIFORM_TMIN ? hwMaxUniform(lo, tMin) : hwMax(lo, tMin);
-  tMax = hwMin(hwMin3(hwMax(ax, bx), hwMax(ay, by), hwMax(az, bz)), tMax);
-  const float diff = tMax - tMin;
-  const float tol = __builtin_fmaf(0x1p-21f, fabsf(tMax) + fabsf(tMin), tolAbs);
-  undecided = !(fabsf(diff) > tol);  // also when a NaN got in, and always when tolAbs = +inf
-  return diff > tol;
+  return srtSlabVerdict<UNIFORM_TMIN, false>(srtSlabEndsMinMax(n0, n1, slab3(r1), slab3(m)), tolAbs, tMin, tMax, undecided);
 }
-// Closest-hit traversal: the same one-FMA intervals used CONSERVATIVELY -- a box is entered unless it is certainly
-// missed (tMaxA - tMinA < -tol), so no exact fallback is needed: a box entered needlessly costs time, never a hit.
-// Returns the approximate entry distance for near-first ordering.
+// the sign form (a scene of ordered boxes: DevScene::boxOrderedScene): the same values from twelve FMAs, no min/max pairs
+template <bool UNIFORM_TMIN>
+__device__ __forceinline__ bool boxHitSign(float4 n0, float4 n1, V3 rp, V3 rq, V3 m, float tolAbs, float tMin, float tMax,
+                                           bool& undecided) {
+  return srtSlabVerdict<UNIFORM_TMIN, true>(srtSlabEndsSign(n0, n1, slab3(rp), slab3(rq), slab3(m)), tolAbs, tMin, tMax, undecided);
+}
+// Closest-hit traversal: the conservative use of the same intervals (srtSlabMaybe)
 __device__ __forceinline__ bool boxMaybeHit(float4 lo, float4 hi, V3 r1, V3 m, float tolAbs, float tMin, float tMax, float& tEnter) {
-  const float ax = __builtin_fmaf(lo.x, r1.x, m.x), bx = __builtin_fmaf(hi.x, r1.x, m.x);
-  const float ay = __builtin_fmaf(lo.y, r1.y, m.y), by = __builtin_fmaf(hi.y, r1.y, m.y);
-  const float az = __builtin_fmaf(lo.z, r1.z, m.z), bz = __builtin_fmaf(hi.z, r1.z, m.z);
-  const float t0 = hwMax(hwMax3(hwMin(ax, bx), hwMin(ay, by), hwMin(az, bz)), tMin);
-  const float t1 = hwMin(hwMin3(hwMax(ax, bx), hwMax(ay, by), hwMax(az, bz)), tMax);
-  const float tol = __builtin_fmaf(0x1p-21f, fabsf(t1) + fabsf(t0), tolAbs);
-  tEnter = t0;
-  return !(t1 - t0 < -tol);  // NaN or tolAbs = +inf (uncertified ray): enter
+  return srtSlabMaybe<false>(srtSlabEndsMinMax(lo, hi, slab3(r1), slab3(m)), tolAbs, tMin, tMax, tEnter);
 }
 // per ray: m = fl(-o * r) and the absolute part of the certificate's tolerance
 __device__ __forceinline__ void slabSetup(const V3& o, const V3& r1, bool certified, V3& m, float& tolAbs) {
-  m = mk(-(o.x * r1.x), -(o.y * r1.y), -(o.z * r1.z));
-  const float M = fmaxf(fmaxf(fabsf(m.x), fabsf(m.y)), fabsf(m.z));
-  tolAbs = certified ? 0x1p-22f * M : SRT_INF;
+  SrtSlab3 mm;
+  srtSlabSetup(slab3(o), slab3(r1), certified, mm, tolAbs);
+  m = mk(mm.x, mm.y, mm.z);
+}
+// ... and the sign form's: rp = max(r, 0), rq = min(r, 0) in place of the reciprocal
+__device__ __forceinline__ void slabSetupSign(const V3& o, const V3& r1, bool certified, V3& rp, V3& rq, V3& m, float& tolAbs) {
+  SrtSlab3 p, q, mm;
+  srtSlabSignSetup(slab3(o), slab3(r1), certified, p, q, mm, tolAbs);
+  rp = mk(p.x, p.y, p.z);
+  rq = mk(q.x, q.y, q.z);
+  m = mk(mm.x, mm.y, mm.z);
 }
 
 // sphere.h:47-52

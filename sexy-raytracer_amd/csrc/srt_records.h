@@ -52,6 +52,12 @@ SRT_HD inline bool fastDivOperands(const Box& b) {
   for (int k = 0; k < 3; ++k) ok = ok && fastDivOperand(b.mn[k]) && fastDivOperand(b.mx[k]);
   return ok;
 }
+// the sign form of the slab test (srt_slab.h) takes the near plane of an axis from the ray's sign: min <= max, both finite
+SRT_HD inline bool srtBoxOrdered(const Box& b) {
+  bool ok = true;
+  for (int k = 0; k < 3; ++k) ok = ok && b.mn[k] <= b.mx[k] && fabsf(b.mn[k]) < INFINITY && fabsf(b.mx[k]) < INFINITY;
+  return ok;
+}
 
 // ------------------------------------------------------------------ triangles
 // p: the nine position floats, uv: the six texture coordinates (SrtTriangleIn's order) -> triTest (vertices, the

@@ -119,13 +119,16 @@ __global__ void refitNodes(RefitArgs a) {
   if (bad) atomicOr(a.flag, 1);
 }
 
-// After the refit, one lane per node: the node boxes' share of the certificate (flag bit 1), and the box halves of the
+// After the refit, one lane per node: the node boxes' share of the certificate (flag bit 1), whether they are ordered (flag
+// bit 2 is raised by one that is not: the sign form of the slab test, srt_slab.h), and the box halves of the
 // hybrid records (DevScene::nodesWf) through the renumbering of srtHybridRecords; their reference and link words stay.
 __global__ void refitDerived(const float4* nodes, int numNodes, const int32_t* wfIndex, float4* nodesWf, int32_t* flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= numNodes) return;
   const float4 lo = nodes[2 * (size_t)i], hi = nodes[2 * (size_t)i + 1];
-  if (!fastDivOperands(Box{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}})) atomicOr(flag, 2);
+  const Box box = {{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+  if (!fastDivOperands(box)) atomicOr(flag, 2);
+  if (!srtBoxOrdered(box)) atomicOr(flag, 4);  // (DevScene::boxOrderedScene)
   if (wfIndex) {
     const size_t j = (size_t)wfIndex[i];
     nodesWf[2 * j] = make_float4(lo.x, lo.y, lo.z, nodesWf[2 * j].w);

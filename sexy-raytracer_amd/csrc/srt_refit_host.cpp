@@ -163,7 +163,8 @@ int refitScene(SrtContext* ctx, void* streamPtr, bool rebuild) {
     HIP_OK(ctx, hipMemcpyAsync(&flag, ctx->refitFlag.get(), sizeof flag, hipMemcpyDeviceToHost, stream));
   }
   if (hipStreamSynchronize(stream) != hipSuccess) return fail(ctx, "%s: kernel failed: %s", what, hipGetErrorString(hipGetLastError()));
-  ctx->upload.scene.fastDivScene = flag == 0 ? ctx->upload.fastDivOption : 0;
+  ctx->upload.scene.fastDivScene = (flag & 3) == 0 ? ctx->upload.fastDivOption : 0;
+  ctx->upload.scene.boxOrderedScene = (flag & 4) == 0 ? 1 : 0;
   // Without tracking, as srtUploadScene: the reprojection assumes the surfaces of the history's frame.  With it, the history
   // stays and srtRenderTemporalFrame decides by the count of refits since its last frame (srt_frames.cpp)
   if (ctx->motionTracking) {

@@ -462,17 +462,24 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
   }
   // ---- device-built trees: their primitives as device references.  Their node boxes are unions of primitive boxes, so
   // fastDiv's certificate covers those as well as the host-built nodes.
-  bool certified = true;
+  // The sign form of the slab test asks for ordered boxes as well (a union of ordered boxes is ordered); the slots of the
+  // device-built items are zero here.
+  bool certified = true, ordered = true;
   for (const float4& v : h.nodes) certified = certified && fastDivOperand(v.x) && fastDivOperand(v.y) && fastDivOperand(v.z);
+  for (size_t i = 0; i + 1 < h.nodes.size(); i += 2)
+    ordered = ordered && srtBoxOrdered(Box{{h.nodes[i].x, h.nodes[i].y, h.nodes[i].z}, {h.nodes[i + 1].x, h.nodes[i + 1].y, h.nodes[i + 1].z}});
   for (DeviceBuild& db : h.deviceBuilds) {
     const SrtWorldItem& it = d->world[db.item];
     db.refs.resize(it.count);
     for (int i = 0; i < it.count; ++i) {
       db.refs[i] = devRef(~(it.first + i));
-      certified = certified && fastDivOperands(primBox(d, it.first + i, it.time0, it.time1));
+      const Box pb = primBox(d, it.first + i, it.time0, it.time1);
+      certified = certified && fastDivOperands(pb);
+      ordered = ordered && srtBoxOrdered(pb);
     }
   }
   h.fastDivScene = certified ? o.fastDiv : 0;
+  h.boxOrderedScene = ordered ? 1 : 0;
   // ---- thread links (srt_thread.h): the 16-bit form the LDS-resident-tree kernels walk (DevScene::nodeThread), and for a
   // tree that does not fit into LDS the path-pool kernel's hybrid records (32-bit references, resident nodes first)
   if (h.deviceBuilds.empty() && !h.nodes.empty()) {

@@ -85,6 +85,7 @@ struct HostScene {
   std::vector<int32_t> wfIndex;      // node index -> its record in nodesWf (srtHybridRecords' renumbering); empty with nodesWf
   int stackDepth = 0, bvhDepth = 0;  // over the host-built trees
   int32_t fastDivScene = 0;          // over the host-built nodes and the device-built items' primitive boxes
+  int32_t boxOrderedScene = 0;       // (DevScene::boxOrderedScene) over the same boxes
 };
 
 // Flattens a scene that passed validateScene.  Returns the error text, empty on success.

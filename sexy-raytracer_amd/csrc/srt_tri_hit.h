@@ -95,7 +95,7 @@ SRT_HD inline bool srtTriHitExact(float4 q0, float4 q1, float4 q2, const SrtTriR
 
 SRT_HD inline float srtTriMin3(float a, float b, float c) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  float r;  // (fminf makes the compiler quiet its operands first; see hwMin in srt_path.h)
+  float r;  // (fminf makes the compiler quiet its operands first; see srt_slab.h)
   asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 #else

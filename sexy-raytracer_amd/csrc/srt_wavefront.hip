@@ -173,7 +173,11 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   ray.o = ray.d = mk(0.0f, 0.0f, 0.0f);
   ray.time = 0.0f;
   float closest = SRT_INF, rayA = 0.0f, slabTol = SRT_INF;
-  V3 rcpD = mk(0.0f, 0.0f, 0.0f), negOR = mk(0.0f, 0.0f, 0.0f);
+  // The slab test's per-ray values.  The whole-tree instances, bound by vector-ALU issue, take the sign form (srt_slab.h:
+  // twelve FMAs per visit and no min/max pairs) and keep the reciprocal split by its sign, rp = max(r, 0) and
+  // rq = min(r, 0); the hybrid instances keep the min/max form, and the reciprocal itself in rp.
+  constexpr bool SIGNFORM = !HYBRID;
+  V3 rp = mk(0.0f, 0.0f, 0.0f), rq = mk(0.0f, 0.0f, 0.0f), negOR = mk(0.0f, 0.0f, 0.0f);
   auto atNode = [&]() { return cur >= 0; };
   auto atPrim = [&]() { return (uint32_t)cur > (uint32_t)DONE; };
   // COUNT: samples, rays, node visits, box passes, triangle / sphere tests, shaded triangle hits, texel fetches (SrtStats
@@ -207,8 +211,14 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
     rayA = lenSq(ray.d);
     const bool certified = (sc.fastDivScene != 0) & fastDivOperandOk(ray.o.x, ray.d.x) & fastDivOperandOk(ray.o.y, ray.d.y) &
                            fastDivOperandOk(ray.o.z, ray.d.z);
-    rcpD = mk(refinedRcp(ray.d.x), refinedRcp(ray.d.y), refinedRcp(ray.d.z));
-    slabSetup(ray.o, rcpD, certified, negOR, slabTol);
+    const V3 rcp = mk(refinedRcp(ray.d.x), refinedRcp(ray.d.y), refinedRcp(ray.d.z));
+    if constexpr (SIGNFORM) {
+      // a scene with a box that is not ordered: no ray is certified, every visit takes the exact test
+      slabSetupSign(ray.o, rcp, certified & (sc.boxOrderedScene != 0), rp, rq, negOR, slabTol);
+    } else {
+      rp = rcp;
+      slabSetup(ray.o, rp, certified, negOR, slabTol);
+    }
     closest = SRT_INF;
     hitRef = DONE;
     link = DONE_PAIR;
@@ -328,7 +338,8 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
       int budget = a.nodeBurst, left;
       auto visit = [&](const float4 n0, const float4 n1) {  // aabb::hit (certified slab test, IEEE when undecided), then on
         bool undecided;
-        bool hitBox = boxHitApprox<true>(n0, n1, rcpD, negOR, slabTol, a.tMin, closest, undecided);
+        bool hitBox = SIGNFORM ? boxHitSign<true>(n0, n1, rp, rq, negOR, slabTol, a.tMin, closest, undecided)
+                               : boxHitApprox<true>(n0, n1, rp, negOR, slabTol, a.tMin, closest, undecided);
         if (PROFILE) {  // how often the certificate cannot decide: lanes (-> lanes[8]) and wave visits that run the IEEE test (-> lanes[7])
           const unsigned long long mu = __ballot(undecided);
           pLanes[8] += __popcll(mu);

@@ -49,7 +49,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
                 "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
-                "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord"]
+                "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord", "srtTestGetSlabScene"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -159,6 +159,8 @@ if hasattr(lib, "srtTestGetTriUndecided"):  # (an SRT_HIP_LIB build from before 
     lib.srtTestGetTriUndecided.argtypes = [_vp, C.POINTER(C.c_uint64)]
     lib.srtTestGetTriFast.argtypes = [_vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.srtTestTriFastRecord.argtypes = [_vp, _vp]
+if hasattr(lib, "srtTestGetSlabScene"):  # (likewise: an SRT_HIP_LIB build from before the ordered-box condition)
+    lib.srtTestGetSlabScene.argtypes = [_vp, C.POINTER(C.c_int32)]
 lib.srtRenderAov.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
 lib.srtLastKernelMs.argtypes = [_vp, C.POINTER(C.c_float)]
 lib.srtGetStats.argtypes = [_vp, C.POINTER(abi.SrtStats)]
@@ -840,6 +842,12 @@ class Context:
         if n.value:
             self._check(lib.srtTestGetTriFast(self.h, out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    def slab_scene(self):
+        """(fast-division word, ordered-box word) of the uploaded scene as the kernels read them now (include/srt_hip_test.h)."""
+        out = (C.c_int32 * 2)()
+        self._check(lib.srtTestGetSlabScene(self.h, out))
+        return int(out[0]), int(out[1])
 
     def set_tunable(self, name, value):
         """Diagnostic knobs of the work distribution / wave scheduler (include/srt_hip_test.h)."""
