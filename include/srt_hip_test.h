@@ -117,6 +117,26 @@ int srtTestTriFastRecord(const float* p9, float* out16);
  * a ray only where both hold; every other kernel orders the two quotients itself and asks for the first alone. */
 int srtTestGetSlabScene(SrtContext* ctx, int32_t* out2);
 
+/* The certified slab test as the device compiles it, outside any walk (csrc/srt_slabtest.hip: two kernels of their own that call
+ * the per-ray and per-visit functions of csrc/srt_path.h and csrc/srt_query_walk.h; tests/test_gpu_slab_cert.py).  Neither needs a
+ * scene; host pointers.
+ * The first hook: r = refinedRcp(d) for the `count` float bit patterns firstBits, firstBits + 1, ... and e = |r d - 1| evaluated in
+ * double (two floats' product is exact there): out2 = { the bits of the largest e as a double (+inf where r d is a NaN: d = 0),
+ * the pattern of the d that gave it (the lowest such pattern) }.  The certificate assumes e <= 3 * 2^-24 for every direction
+ * component it certifies (2^-20 <= |d| <= 2^20).  Refuses, with an error text, a range that is not made of 32-bit patterns of one
+ * sign or that reaches an infinity or a NaN, count < 1 and a null output.
+ * The second hook: n <= 2^20 cases of 13 floats -- box min[3], box max[3], ray origin[3], ray direction[3], tMax -- and one tMin for
+ * the launch, which the kernel takes as an argument: the UNIFORM_TMIN forms read it from its scalar register, as in the render
+ * kernels.  Per case, what a kernel does per ray -- certified = certifiedScene != 0 and fastDivOperandOk on the three axes, the
+ * three refined reciprocals, slabSetup and slabSetupSign -- and per visit.  hOut: 8 words per case,
+ *   floats 0-2  the reciprocals;  float 3  tolAbs of slabSetup;  float 4  tolAbs of slabSetupSign;
+ *   word 5      flags as int32 bits: bit 0 certified; 1 / 2 verdict / undecided of boxHitApprox<false>; 3 / 4 of boxHitApprox<true>;
+ *               5 / 6 of boxHitSign<true>; 7 boxMaybeHit; 8 boxHit (the reference's divisions); 9 boxHitLoose;
+ *   float 6     tEnter of boxMaybeHit;  float 7  tEnter of boxHitLoose.
+ * Refuses n outside [1, 2^20] and null pointers. */
+int srtTestRefinedRcp(SrtContext* ctx, int64_t firstBits, int64_t count, uint64_t* out2);
+int srtTestSlabVisit(SrtContext* ctx, const float* hCases, int32_t n, float tMin, int32_t certifiedScene, float* hOut);
+
 /* The most recent render-kernel launch: out4 = { 0 node records through the L1, 1 the step-scheduler kernel over the
  * LDS-resident threaded tree (FAITHFUL, node array small enough for a CU's LDS; tunable "lds_tree" = 0 switches it
  * off), 2 the same with the attenuation stacks in LDS as well, 3 the path-pool kernel over the same tree (tunable

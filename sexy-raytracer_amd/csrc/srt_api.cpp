@@ -454,6 +454,59 @@ int srtTestGetSlabScene(SrtContext* ctx, int32_t* out2) {
   return 0;
 }
 
+/* include/srt_hip_test.h: the refined reciprocal over a range of bit patterns (csrc/srt_slabtest.hip).  Needs no scene. */
+int srtTestRefinedRcp(SrtContext* ctx, int64_t firstBits, int64_t count, uint64_t* out2) {
+  if (!ctx) return 1;
+  if (!out2) return fail(ctx, "srtTestRefinedRcp: null output");
+  if (firstBits < 0 || firstBits > 0xffffffffll || count < 1 || count > (1ll << 32) || firstBits + count - 1 > 0xffffffffll)
+    return fail(ctx, "srtTestRefinedRcp: patterns %lld .. + %lld are not 32-bit patterns", (long long)firstBits, (long long)count);
+  const int64_t last = firstBits + count - 1;
+  // one sign, and the largest magnitude still finite: neither an infinity nor a NaN in the range
+  if ((firstBits >> 31) != (last >> 31) || (last & 0x7fffffffll) > 0x7f7fffffll)
+    return fail(ctx, "srtTestRefinedRcp: patterns %lld .. %lld leave the finite floats of one sign", (long long)firstBits, (long long)last);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer dPartial;
+  std::vector<unsigned long long> partial(2 * SRT_SLABTEST_RCP_WAVES);
+  HIP_OK(ctx, dPartial.reserve(partial.size() * sizeof(unsigned long long)));
+  const int e = srt_launch_slabtest_rcp((uint32_t)firstBits, count, dPartial.get<unsigned long long>(), nullptr);
+  if (e) return fail(ctx, "srtTestRefinedRcp: launch failed: %s", hipGetErrorString((hipError_t)e));
+  HIP_OK(ctx, hipDeviceSynchronize());
+  HIP_OK(ctx, hipMemcpy(partial.data(), dPartial.get(), partial.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  double best = -1.0;
+  uint64_t bestBits = 0;
+  for (int w = 0; w < SRT_SLABTEST_RCP_WAVES; ++w) {
+    double err;
+    memcpy(&err, &partial[2 * w], sizeof err);
+    if (err > best || (err == best && err >= 0.0 && partial[2 * w + 1] < bestBits)) {
+      best = err;
+      bestBits = partial[2 * w + 1];
+    }
+  }
+  if (best < 0.0) return fail(ctx, "srtTestRefinedRcp: no wave reported");
+  memcpy(&out2[0], &best, sizeof best);
+  out2[1] = bestBits;
+  return 0;
+}
+
+/* include/srt_hip_test.h: caller-made (box, ray) cases through the device compile of the certified slab test */
+int srtTestSlabVisit(SrtContext* ctx, const float* hCases, int32_t n, float tMin, int32_t certifiedScene, float* hOut) {
+  if (!ctx) return 1;
+  if (!hCases) return fail(ctx, "srtTestSlabVisit: null cases");
+  if (!hOut) return fail(ctx, "srtTestSlabVisit: null output");
+  if (n < 1 || n > (1 << 20)) return fail(ctx, "srtTestSlabVisit: n = %d is not in [1, 2^20]", n);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  const size_t inBytes = (size_t)n * 13 * sizeof(float), outBytes = (size_t)n * 8 * sizeof(float);
+  DeviceBuffer dIn, dOut;
+  HIP_OK(ctx, dIn.reserve(inBytes));
+  HIP_OK(ctx, dOut.reserve(outBytes));
+  HIP_OK(ctx, hipMemcpy(dIn.get(), hCases, inBytes, hipMemcpyHostToDevice));
+  const int e = srt_launch_slabtest_visit(dIn.get<const float>(), n, tMin, certifiedScene, dOut.get<float>(), nullptr);
+  if (e) return fail(ctx, "srtTestSlabVisit: launch failed: %s", hipGetErrorString((hipError_t)e));
+  HIP_OK(ctx, hipDeviceSynchronize());
+  HIP_OK(ctx, hipMemcpy(hOut, dOut.get(), outBytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 /* include/srt_hip_test.h: the certified triangle test's read-outs */
 int srtTestGetTriUndecided(SrtContext* ctx, uint64_t* out) {
   if (!ctx || !out) return 1;

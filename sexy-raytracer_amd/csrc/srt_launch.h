@@ -25,6 +25,12 @@ int srt_launch_scatter(const DevScene* sc, const SrtRay* rays, const SrtHit* hit
 // srt_query.hip: mode = SRT_TRAVERSE_FAITHFUL, SRT_TRAVERSE_CLOSEST or 2 (any hit, into a->occluded)
 int srt_launch_query(const QueryArgs* a, int mode, int grid, size_t ldsBytes, hipStream_t stream);
 
+// srt_slabtest.hip: the test hooks on the certified slab test (include/srt_hip_test.h srtTestRefinedRcp, srtTestSlabVisit).
+// partial: 2 * SRT_SLABTEST_RCP_WAVES words, per wave {the bits of its largest |r d - 1| as a double, -1 for none; the pattern}
+#define SRT_SLABTEST_RCP_WAVES 4096
+int srt_launch_slabtest_rcp(uint32_t firstBits, int64_t count, unsigned long long* partial, hipStream_t stream);
+int srt_launch_slabtest_visit(const float* cases, int n, float tMin, int certifiedScene, float* out, hipStream_t stream);
+
 // srt_pathstep.hip: one kernel each; traversal = SRT_TRAVERSE_FAITHFUL or SRT_TRAVERSE_CLOSEST, ldsBytes as srt_launch_query's
 int srt_launch_camera_rays(const CameraRaysArgs* a, int grid, hipStream_t stream);
 int srt_launch_scatter_device(const ScatterDeviceArgs* a, int grid, hipStream_t stream);

@@ -29,20 +29,20 @@ enum { Q_FAITHFUL = 0, Q_CLOSEST = 1, Q_ANY = 2 };
 // aabb.h:14-17's quotients, entered unless the interval is empty by more than 2^-21 relative: the box test of a ray
 // whose reciprocals are not certified.  boxHit itself rejects an interval that only touches (tMax <= tMin), which would
 // cut a candidate with t == closest out of reach; the magnitudes are clamped so that an infinite end (a zero direction
-// component) still decides.
+// component) still decides.  A NaN quotient is 0 / 0 -- a zero direction component and the origin IN that plane of the box, so
+// the ray lies in the (closed) slab -- or comes from a NaN or infinite operand: the axis then constrains nothing.  (fminf /
+// fmaxf alone would keep the other plane's infinite quotient for both ends and cut off every primitive that touches the
+// box's upper face: tests/test_gpu_slab_cert.py, rays lying in face planes.)
+__device__ __forceinline__ void looseAxis(float a, float b, float& t0, float& t1) {
+  const bool open = (a != a) | (b != b);
+  t0 = fmaxf(open ? -SRT_INF : fminf(a, b), t0);
+  t1 = fminf(open ? SRT_INF : fmaxf(a, b), t1);
+}
 __device__ __forceinline__ bool boxHitLoose(float4 lo, float4 hi, const Ray& r, float tMin, float tMax, float& tEnter) {
-  float a, b;
-  a = (lo.x - r.o.x) / r.d.x;
-  b = (hi.x - r.o.x) / r.d.x;
-  float t0 = fmaxf(fminf(a, b), tMin), t1 = fminf(fmaxf(a, b), tMax);
-  a = (lo.y - r.o.y) / r.d.y;
-  b = (hi.y - r.o.y) / r.d.y;
-  t0 = fmaxf(fminf(a, b), t0);
-  t1 = fminf(fmaxf(a, b), t1);
-  a = (lo.z - r.o.z) / r.d.z;
-  b = (hi.z - r.o.z) / r.d.z;
-  t0 = fmaxf(fminf(a, b), t0);
-  t1 = fminf(fmaxf(a, b), t1);
+  float t0 = tMin, t1 = tMax;
+  looseAxis((lo.x - r.o.x) / r.d.x, (hi.x - r.o.x) / r.d.x, t0, t1);
+  looseAxis((lo.y - r.o.y) / r.d.y, (hi.y - r.o.y) / r.d.y, t0, t1);
+  looseAxis((lo.z - r.o.z) / r.d.z, (hi.z - r.o.z) / r.d.z, t0, t1);
   const float big = 0x1p100f;
   const float tol = 0x1p-21f * (fminf(fabsf(t1), big) + fminf(fabsf(t0), big));
   tEnter = t0;

@@ -49,7 +49,8 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
 # include/srt_hip_test.h: test hooks and diagnostics, not part of the drop-in boundary
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
                 "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
-                "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord", "srtTestGetSlabScene"]
+                "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord", "srtTestGetSlabScene",
+                "srtTestRefinedRcp", "srtTestSlabVisit"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -161,6 +162,9 @@ if hasattr(lib, "srtTestGetTriUndecided"):  # (an SRT_HIP_LIB build from before 
     lib.srtTestTriFastRecord.argtypes = [_vp, _vp]
 if hasattr(lib, "srtTestGetSlabScene"):  # (likewise: an SRT_HIP_LIB build from before the ordered-box condition)
     lib.srtTestGetSlabScene.argtypes = [_vp, C.POINTER(C.c_int32)]
+if hasattr(lib, "srtTestRefinedRcp"):  # (likewise: an SRT_HIP_LIB build from before the slab-test hooks)
+    lib.srtTestRefinedRcp.argtypes = [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]
+    lib.srtTestSlabVisit.argtypes = [_vp, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float)]
 lib.srtRenderAov.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
 lib.srtLastKernelMs.argtypes = [_vp, C.POINTER(C.c_float)]
 lib.srtGetStats.argtypes = [_vp, C.POINTER(abi.SrtStats)]
@@ -848,6 +852,25 @@ class Context:
         out = (C.c_int32 * 2)()
         self._check(lib.srtTestGetSlabScene(self.h, out))
         return int(out[0]), int(out[1])
+
+    def refined_rcp_test(self, first_bits, count):
+        """srtTestRefinedRcp (include/srt_hip_test.h): the largest |refinedRcp(d) d - 1| (in double) over the float bit patterns
+        first_bits .. first_bits + count - 1, and the d that gives it.  Returns (error, d as np.float32)."""
+        out = (C.c_uint64 * 2)()
+        self._check(lib.srtTestRefinedRcp(self.h, int(first_bits), int(count), out))
+        return float(np.array([out[0]], np.uint64).view(np.float64)[0]), np.array([out[1]], np.uint32).view(np.float32)[0]
+
+    def slab_visit_test(self, cases, t_min, certified_scene=1):
+        """srtTestSlabVisit (include/srt_hip_test.h): cases (n, 13) float32 -- box min, box max, origin, direction, tMax --
+        through the device compile of the certified slab test at one tMin.  Returns (n, 8) float32; column 5 holds the flag
+        bits (view it as int32)."""
+        cases = np.ascontiguousarray(cases, np.float32)
+        if cases.ndim != 2 or cases.shape[1] != 13:
+            raise ValueError("cases must be (n, 13)")
+        out = np.zeros((len(cases), 8), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(lib.srtTestSlabVisit(self.h, cases.ctypes.data_as(fp), len(cases), float(t_min), int(certified_scene), out.ctypes.data_as(fp)))
+        return out
 
     def set_tunable(self, name, value):
         """Diagnostic knobs of the work distribution / wave scheduler (include/srt_hip_test.h)."""

@@ -2,21 +2,36 @@
 test -- near and far planes of an ordered box picked by the sign of the ray's reciprocal, two FMAs each -- gives the float
 values of min / max of the two one-FMA quotients, and the same verdict and `undecided` as the min/max form, over more than
 10^7 seeded axis cases and the listed edges; a ray outside the certified operand ranges is undecided in both forms; and
-the ordered-box condition (csrc/srt_records.h srtBoxOrdered) on an ordered, a flat, an inverted and two non-finite boxes."""
+the ordered-box condition (csrc/srt_records.h srtBoxOrdered) on an ordered, a flat, an inverted and two non-finite boxes.
+
+And the certificate itself against the reference's divisions (aabb.h:14-22 restated in the probe), case by case, with the
+reciprocal anywhere in the band the header's proof assumes (|r d - 1| <= 3 * 2^-24): no decided verdict differs from the
+reference's, the conservative form never rejects a box whose reference interval is non-empty or touching, and the observed
+error of the clamped ends stays inside the proven bound (at most 1 x the verdict's tolerance; 0.71 observed) -- in every class
+the reference both enters and misses at least a tenth of the boxes, except the flat class (never entered: a zero-thickness slab
+gives tMax <= tMin) and the uncertified one.  The same program under the address and undefined-behaviour sanitizers, and its
+replay mode on a handful of cases."""
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
+import slab_cases
 
 PROBE = os.path.join(ROOT, "examples", "srt_slab_probe")
-PER_CLASS = 500_000  # boxes; x 3 axes x 8 seeded classes
-FIELDS = ("boxes", "axes", "certified", "undecided", "end_diff", "verdict_diff", "undecided_diff", "decided_uncertified")
+PER_CLASS = 500_000  # boxes; x 3 axes x 12 seeded classes
+FIELDS = ("boxes", "axes", "certified", "undecided", "end_diff", "verdict_diff", "undecided_diff", "decided_uncertified",
+          "in_band", "entered", "wrong", "maybe_wrong", "max_ratio")
 # random boxes; plane coordinates 0 and -0 and the ends of the certified range; n0 == n1; the ground's +-1000 / -2000;
 # |d| at 2^-20 and 2^20; o = 0 and |o| = 2^30; rays aimed at box corners; d = 0, infinite and NaN reciprocals, origins out of
-# range; and every combination of the listed planes, origins and directions on one axis
-CLASSES = {"random", "zeros", "flat", "ground", "d_edges", "o_edges", "aimed", "uncertified", "edges"}
+# range; every combination of the listed planes, origins and directions on one axis; |o| from 2^10 to 2^30 with the box near
+# zero; tMax and tMin within 4 ulps of the box's own quotients; tMin = 0 and tMin large; and the random class's cases with the
+# reciprocal moved by -2 .. 2 ulps instead of drawn from the band
+CLASSES = {"random", "zeros", "flat", "ground", "d_edges", "o_edges", "aimed", "uncertified", "edges", "far", "touch", "tmin_zero",
+           "ulp2"}
+ULP_CLASSES = {"edges", "ulp2"}  # reciprocals up to 2 ulps off fl(1 / d): partly outside the band
 
 
 @pytest.fixture(scope="module")
@@ -25,16 +40,20 @@ def probe():
     return PROBE
 
 
-@pytest.fixture(scope="module")
-def sweep(probe):
+def parse(text):
     out = {}
-    for line in subprocess.check_output([probe, "sweep", "1", str(PER_CLASS)], text=True).splitlines():
+    for line in text.splitlines():
         w = line.split()
         assert w[0] == "class" and len(w) == 2 + 2 * len(FIELDS), line
-        out[w[1]] = {w[k]: int(w[k + 1]) for k in range(2, len(w), 2)}
+        out[w[1]] = {w[k]: float(w[k + 1]) if w[k] == "max_ratio" else int(w[k + 1]) for k in range(2, len(w), 2)}
         assert tuple(out[w[1]]) == FIELDS, line
         print(line)
     return out
+
+
+@pytest.fixture(scope="module")
+def sweep(probe):
+    return parse(subprocess.check_output([probe, "sweep", "1", str(PER_CLASS)], text=True))
 
 
 def test_sign_form_equals_min_max_form(sweep):
@@ -54,6 +73,134 @@ def test_classes_are_what_they_say(sweep):
             assert c["undecided"] < c["boxes"], (name, c)  # the certificate does decide
     assert sweep["random"]["undecided"] <= 0.01 * sweep["random"]["boxes"], sweep["random"]
     assert sweep["aimed"]["undecided"] > 0.1 * sweep["aimed"]["boxes"], sweep["aimed"]  # and the exact test is reached
+
+
+def test_decided_verdicts_are_the_reference_verdicts(sweep):
+    """wrong: a certified ray with its reciprocals in the band, a form decided, the verdict not the reference's.  maybe_wrong:
+    the conservative form (both instances) rejects a box whose reference interval is not strictly empty -- a CLOSEST walk
+    would lose a hit or a tie."""
+    for name, c in sweep.items():
+        assert c["wrong"] == 0 and c["maybe_wrong"] == 0, (name, c)
+        if name == "uncertified":
+            continue
+        if name in ULP_CLASSES:
+            assert 0.5 * c["boxes"] < c["in_band"] < c["boxes"], (name, c)
+        else:
+            assert c["in_band"] == c["boxes"], (name, c)
+
+
+def test_observed_error_is_inside_the_proven_bound(sweep):
+    """(|tMinA - tMin| + |tMaxA - tMax|) / tol <= 1 is what the header's derivation gives for the clamped ends; the sweep reaches
+    0.71 (the zeros class).  0 would mean nothing was measured."""
+    for name, c in sweep.items():
+        if name != "uncertified":
+            assert 0.0 < c["max_ratio"] <= 1.0, (name, c)
+    assert max(c["max_ratio"] for c in sweep.values()) > 0.5  # and the sweep gets near the bound
+
+
+def test_reference_enters_and_misses_in_every_class(sweep):
+    for name, c in sweep.items():
+        if name == "flat":
+            assert c["entered"] == 0, c  # tMax <= tMin on the flat axis
+        elif name != "uncertified":
+            assert 0.1 * c["boxes"] <= c["entered"] <= 0.9 * c["boxes"], (name, c)
+    assert sweep["touch"]["undecided"] > 0.1 * sweep["touch"]["boxes"], sweep["touch"]
+    assert sweep["far"]["undecided"] > 0.1 * sweep["far"]["boxes"], sweep["far"]
+
+
+REPLAY_CASES = [  # lo, hi, o, d, tMin, tMax -> the reference's verdict
+    ((-1, -1, -1), (1, 1, 1), (0.25, 0.25, -4), (0.125, 0.125, 1), 0.001, np.inf, 1),    # through the box
+    ((-1, -1, -1), (1, 1, 1), (0.25, 0.25, -4), (0.125, 0.125, 1), 0.001, 2.5, 0),       # ... which lies beyond tMax
+    ((-1, -1, -1), (1, 1, 1), (3, 0.25, -4), (0.125, 0.125, 1), 0.001, np.inf, 0),      # past it
+    ((-1, 0.5, -1), (1, 0.5, 1), (0, -2, 0.5), (0.25, 1, 0.125), 0.0, np.inf, 0),      # a flat box: never entered
+    ((-1, -1, -1), (1, 1, 1), (0.25, 0.25, -4), (0.0, 0.125, 1), 0.001, np.inf, 1),      # d.x = 0: uncertified, the divisions decide
+]
+
+
+def replay(exe, tmp_path, env=None):
+    rec = np.zeros((len(REPLAY_CASES), 18), np.float32)
+    for row, (lo, hi, o, d, t0, t1, _) in zip(rec, REPLAY_CASES):
+        row[0:3], row[3:6], row[6:9], row[9:12], row[15], row[16] = lo, hi, o, d, t0, t1
+        with np.errstate(divide="ignore"):
+            row[12:15] = np.float32(1) / row[9:12]
+    rec[:, 17:].view(np.int32)[:] = 1
+    rec.tofile(tmp_path / "in.bin")
+    r = subprocess.run([exe, "replay", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "runtime error" not in r.stdout and "Sanitizer" not in r.stdout, r.stdout[-2000:]
+    out = np.fromfile(tmp_path / "out.bin", np.float32).reshape(-1, 8)
+    assert len(out) == len(rec) and np.array_equal(out[:, :3].view(np.uint32), rec[:, 12:15].view(np.uint32))
+    flags = out[:, 5].view(np.int32)
+    want = np.array([c[-1] for c in REPLAY_CASES])
+    assert np.array_equal(flags >> 8 & 1, want), flags
+    assert np.array_equal(flags & 1, [1, 1, 1, 1, 0]), flags
+    for k, f in enumerate(flags):
+        verdicts, undecided = (f >> 1 & 1, f >> 3 & 1, f >> 5 & 1), (f >> 2 & 1, f >> 4 & 1, f >> 6 & 1)
+        assert len(set(verdicts)) == 1 and len(set(undecided)) == 1, (k, f)
+        assert undecided[0] or verdicts[0] == want[k], (k, f)
+        assert f >> 7 & 1 or not want[k], (k, f)
+    assert flags[4] >> 2 & 1 and np.isinf(out[4, 3]) and np.isinf(out[4, 4])  # the uncertified ray: tolAbs = +inf, undecided
+    assert not flags[0] >> 2 & 1 and not flags[2] >> 2 & 1                     # the two clear cases are decided
+
+
+def test_replay_mode(probe, tmp_path):
+    replay(probe, tmp_path)
+
+
+def replay_cases(exe, d, cases, rcp, t_min, certified_scene=1):
+    """The probe's replay of slab_cases cases with the given reciprocals -> (n, 8) float32 (tests/test_gpu_slab_cert.py feeds the
+    device's own reciprocals through this)."""
+    rec = np.zeros((len(cases), 18), np.float32)
+    rec[:, 0:12], rec[:, 12:15], rec[:, 15], rec[:, 16] = cases[:, 0:12], rcp, t_min, cases[:, 12]
+    rec[:, 17:].view(np.int32)[:] = certified_scene
+    rec.tofile(d / "cases.bin")
+    subprocess.check_call([exe, "replay", str(d / "cases.bin"), str(d / "out.bin")])
+    out = np.fromfile(d / "out.bin", np.float32).reshape(-1, 8)
+    assert len(out) == len(cases)
+    return out
+
+
+@pytest.mark.parametrize("name", slab_cases.CLASSES)
+def test_numpy_cases_and_reference_agree_with_the_probe(probe, tmp_path, name):
+    """tests/slab_cases.py, which the device tests use: its NumPy statement of aabb.h:14-22 and of the operand ranges give the
+    probe's own on every case (zero, infinite and NaN components included), the host compile decides nothing against it with
+    fl(1 / d) as the reciprocal, and the reference both enters and misses a tenth of each class (flat: never enters)."""
+    for t_min in slab_cases.T_MINS:
+        cases = slab_cases.cases(name, 20_000, t_min)
+        with np.errstate(all="ignore"):
+            rcp = np.float32(1) / cases[:, 9:12]
+        out = replay_cases(probe, tmp_path, cases, rcp, t_min)
+        flags = out[:, 5].view(np.int32)
+        entered, t0, t1 = slab_cases.reference(cases, t_min)
+        assert np.array_equal(flags >> 8 & 1, entered.astype(np.int32)), (name, t_min)
+        assert np.array_equal(flags & 1, slab_cases.certified(cases).astype(np.int32)), (name, t_min)
+        assert (flags & 1).all() == (name != "uncertified") and (flags & 1).any() == (name != "uncertified")
+        decided = (flags >> 2 & 1) == 0
+        assert np.array_equal((flags >> 1 & 1)[decided], entered[decided].astype(np.int32)), (name, t_min)
+        with np.errstate(invalid="ignore"):
+            assert (flags >> 7 & 1)[~(t1 < t0)].all(), (name, t_min)
+        share = entered.mean()
+        print(name, t_min, "entered %.3f undecided %.3f" % (share, 1 - decided.mean()))
+        if name == "flat":
+            assert share == 0
+        elif name != "uncertified":
+            assert 0.1 <= share <= 0.9, (name, t_min, share)
+
+
+def test_probe_under_sanitizers(tmp_path):
+    """The header's host code and the probe under -fsanitize=address,undefined: a second stand-alone binary, a small sweep (the
+    same assertions hold at any size) and the replay mode."""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "sexy-raytracer_amd", "csrc"), "../../examples/srt_slab_probe_san"])
+    exe = PROBE + "_san"
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe, "sweep", "7", "20000"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0 and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-2000:]
+    small = parse(r.stdout)
+    assert set(small) == CLASSES
+    for name, c in small.items():
+        assert c["wrong"] == 0 and c["maybe_wrong"] == 0 and c["end_diff"] == 0 and c["verdict_diff"] == 0, (name, c)
+        assert c["max_ratio"] <= 1.0, (name, c)
+    replay(exe, tmp_path, env)
 
 
 def test_ordered_box_condition(probe):
