@@ -983,6 +983,7 @@ int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccl
  * srtScatterRaysDevice  material::scatter + material::emitted on every hit record (what srtScatterRays evaluates).
  * srtPathStepDevice     srtTraceRaysDevice followed by srtScatterRaysDevice in ONE kernel: the form a loop should call (a
  *                       path does not write an 88-byte SrtHit to memory and read it back between the two halves).
+ * srtCompactPathsDevice the entries that scattered, moved to the front between two steps (its own block below).
  *   buffers   all DEVICE pointers.  dRays, dRaysOut = SrtRay[n], aligned to 4 bytes.  dRng = uint64_t[n], aligned to 8:
  *             entry i is the generator state of path i (a PCG32 state: one 64-bit LCG step and an XSH-RR output per 32-bit
  *             draw; a float draw is float(u32) * 2^-32, clamped below 1).  Each entry reads it, advances it by exactly the
@@ -1052,6 +1053,51 @@ int srtScatterRaysDevice(SrtContext* ctx, const void* dRays, const void* dRecord
                          void* dRaysOut, void* stream);
 int srtPathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays, int64_t n, const void* dActive, void* dRng,
                       void* dOut, void* dRaysOut, void* dHits, void* stream);
+
+/* srtCompactPathsDevice   stable compaction of the live paths between two steps: the entries that go on move, in their
+ *                         order, to the front of fresh ray, state and slot buffers, so that the next step runs on full
+ *                         waves instead of on the few live lanes of nearly every wave.  Compaction moves bytes: nothing
+ *                         is computed, and a loop that compacts between its steps renders the same bits.
+ *   keep      keep[i] = (dActive == NULL || dActive[i] != 0) && (dOut == NULL || dOut[i].status == SRT_PATH_SCATTERED).
+ *             dOut = SrtPathOut[n], aligned to 16, of which only the status dword is read; dActive = uint8_t[n].  Not both
+ *             NULL.  An inactive entry's dOut[i] is stale by srtPathStepDevice's contract, which is why the mask of the
+ *             step that wrote dOut takes part.  With dOut == NULL the mask alone is the caller's own predicate (Russian
+ *             roulette, a path-length cut).
+ *   order     stable.  With count = the number kept and rank(i) = the number of kept j < i, for every kept i:
+ *             dRaysOut[rank(i)] = dRays[i] (36 bytes), dRngOut[rank(i)] = dRng[i] (8 bytes) and
+ *             dSlotOut[rank(i)] = dSlot ? dSlot[i] : (int32_t)i.
+ *   payloads  dRays / dRaysOut = SrtRay[n] aligned to 4, dRng / dRngOut = uint64_t[n] aligned to 8, dSlot / dSlotOut =
+ *             int32_t[n] aligned to 4.  Each of the three is optional: an output whose input is NULL is refused -- except
+ *             dSlotOut, which with dSlot == NULL receives the identity (the index an entry had before) -- and an input
+ *             whose output is NULL is ignored.  Carrying dSlotOut from one compaction into the next as dSlot keeps the
+ *             index every survivor had in the first buffer.
+ *   dCount    int64_t[1] on the device, aligned to 8, required: receives count.
+ *   dActiveOut  uint8_t[n] or NULL: dActiveOut[i] = (i < count) for every i < n.  The next step can be launched with the
+ *             old n and this mask without reading dCount: the live entries are dense in the leading waves, and the whole
+ *             waves behind them leave after one byte.  dActiveOut may be exactly dActive: each entry reads its byte
+ *             before that byte is written.
+ *   never written  elements at index >= count of dRaysOut, dRngOut and dSlotOut; elements at index >= n of dActiveOut;
+ *             anything outside the documented scratch size.
+ *   overlap   no output (dRaysOut, dRngOut, dSlotOut, dActiveOut, dCount, dScratch) may overlap any input that is read, or
+ *             any other output, each taken at its full length of n elements (compaction in place races across
+ *             workgroups); dActiveOut == dActive is the one exception.  Refused on the host by range comparison.
+ *   scratch   dScratch, aligned to 8, is the caller's: srtCompactPathsScratchBytes(n) = 8 * ceil(n / SRT_COMPACT_TILE)
+ *             bytes (one 64-bit word per tile of SRT_COMPACT_TILE entries: its kept count, then its offset), 0 for
+ *             n <= 0.  Host only, needs no context.  Its contents afterwards are unspecified.
+ *   async     on `stream`: three kernels (count per tile, a one-workgroup scan, scatter), none of which waits for another
+ *             workgroup.  Allocates nothing, does not synchronise, touches no scratch of the context's, and leaves the
+ *             tunables, the host generator, the chunk scratch, srtLastKernelMs, srtGetLaunchInfo, srtGetStats and the
+ *             temporal history as they were.  Needs no uploaded scene.
+ *   n == 0    returns 0 and launches nothing; dCount is NOT written.
+ *   errors    (non-zero, message in srtLastError, NOTHING launched, outputs untouched; all decided on the host) n < 0;
+ *             dOut and dActive both NULL; a NULL dCount; with n > 0 a NULL dScratch; dRaysOut without dRays or dRngOut
+ *             without dRng; a misaligned pointer (rays and slots 4 bytes, rng states, dCount and dScratch 8, dOut 16);
+ *             n > 2^31 - 1 with dSlotOut; an overlap as above. */
+enum { SRT_COMPACT_TILE = 1024 }; /* entries a workgroup handles per trip */
+int64_t srtCompactPathsScratchBytes(int64_t n);
+int srtCompactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const void* dActive, const void* dRays, const void* dRng,
+                          const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut, void* dActiveOut, void* dCount,
+                          void* dScratch, void* stream);
 
 /* material::scatter + material::emitted (material.h:15-21; texture::value through a light's emitted, texture.h:13-16) for
  * n (incoming ray, hit record) pairs, evaluated by the render kernels' own shading function.  hits[i].material indexes

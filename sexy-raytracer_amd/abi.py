@@ -17,6 +17,7 @@ SRT_TILE_PIXELS = 64
 SRT_NO_HIT = -1
 # path steps on device buffers (srtScatterRaysDevice / srtPathStepDevice): SrtPathOut.status
 SRT_PATH_INVALID, SRT_PATH_MISS, SRT_PATH_ENDED, SRT_PATH_SCATTERED = -1, 0, 1, 2
+SRT_COMPACT_TILE = 1024  # entries per tile of srtCompactPathsDevice: its scratch is one 64-bit word per tile
 # feature planes (srtRenderFeatureTiles / srtRenderFeatureImage): bit 1 << k selects plane k
 SRT_FEATURE_ALBEDO, SRT_FEATURE_NORMAL, SRT_FEATURE_POSITION, SRT_FEATURE_DEPTH = 1, 2, 4, 8
 SRT_FEATURE_ALL = 15

@@ -36,6 +36,25 @@ int srt_launch_camera_rays(const CameraRaysArgs* a, int grid, hipStream_t stream
 int srt_launch_scatter_device(const ScatterDeviceArgs* a, int grid, hipStream_t stream);
 int srt_launch_path_step(const PathStepArgs* a, int traversal, int grid, size_t ldsBytes, hipStream_t stream);
 
+// srt_compact.hip (srtCompactPathsDevice): count, scan and scatter, three kernels on the stream; grid = the workgroups of
+// the first and the last.  The scan is one workgroup of SRT_COMPACT_SCAN_BLOCK threads, a tile count each per trip.
+#define SRT_COMPACT_SCAN_BLOCK 1024
+struct CompactArgs {
+  const int32_t* out;     // SrtPathOut[n] as dwords (the status is dword 3 of 8), or null
+  const uint8_t* active;  // or null; not both
+  const uint32_t* rays;   // payloads in: read only where the output beside them is not null
+  const uint64_t* rng;
+  const int32_t* slot;    // null with slotOut: the identity
+  uint32_t* raysOut;      // payloads out, each or null
+  uint64_t* rngOut;
+  int32_t* slotOut;
+  uint8_t* activeOut;     // or null; may be `active`
+  int64_t* count;
+  uint64_t* tileOffset;   // the caller's scratch: numTiles words
+  int64_t n, numTiles;
+};
+int srt_launch_compact(const CompactArgs* a, int grid, hipStream_t stream);
+
 // srt_lbvh.hip: the device tree builders (blocking) and the closest-hit traversal's pair records
 int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
                    uint8_t* outAxis, int base, int* depthOut);

@@ -675,6 +675,86 @@ static int pathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays,
   return 0;
 }
 
+// srtCompactPathsDevice: every check on the host, then srt_compact.hip's three launches on the caller's stream.  Needs no
+// scene; nothing of the context changes.
+static int64_t compactTiles(int64_t n) { return n <= 0 ? 0 : (n - 1) / SRT_COMPACT_TILE + 1; }
+
+int64_t srtCompactPathsScratchBytes(int64_t n) { return 8 * compactTiles(n); }
+
+static int compactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const void* dActive, const void* dRays, const void* dRng,
+                              const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut, void* dActiveOut, void* dCount,
+                              void* dScratch, void* streamPtr) {
+  const char* what = "srtCompactPathsDevice";
+  if (!ctx) return 1;
+  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
+  if (!dOut && !dActive) return fail(ctx, "%s: no predicate: the outputs and the mask are both null", what);
+  if (checkPointer(ctx, what, "count", dCount, 8)) return 1;
+  if (n == 0) return 0;
+  if (checkPointer(ctx, what, "scratch", dScratch, 8)) return 1;
+  if (dRaysOut && !dRays) return fail(ctx, "%s: compacted rays without rays", what);
+  if (dRngOut && !dRng) return fail(ctx, "%s: compacted rng states without rng states", what);
+  if ((uintptr_t)dOut % 16) return fail(ctx, "%s: the outputs are not aligned to 16 bytes", what);
+  if ((dRaysOut && (uintptr_t)dRays % 4) || (uintptr_t)dRaysOut % 4) return fail(ctx, "%s: the rays are not aligned to 4 bytes", what);
+  if ((dRngOut && (uintptr_t)dRng % 8) || (uintptr_t)dRngOut % 8) return fail(ctx, "%s: the rng states are not aligned to 8 bytes", what);
+  if ((dSlotOut && (uintptr_t)dSlot % 4) || (uintptr_t)dSlotOut % 4) return fail(ctx, "%s: the slots are not aligned to 4 bytes", what);
+  if (dSlotOut && n > 0x7fffffffll) return fail(ctx, "%s: n = %lld does not fit a 32-bit slot", what, (long long)n);
+  // what the kernels write may overlap nothing else they read or write (dActiveOut may BE dActive: an entry owns its byte)
+  struct Range {
+    const char* name;
+    uintptr_t at;
+    uint64_t bytes;
+    bool written;
+  };
+  const uint64_t un = (uint64_t)n;
+  const Range ranges[] = {{"outputs", (uintptr_t)dOut, 32 * un, false},
+                          {"mask", (uintptr_t)dActive, un, false},
+                          {"rays", (uintptr_t)(dRaysOut ? dRays : nullptr), 36 * un, false},
+                          {"rng states", (uintptr_t)(dRngOut ? dRng : nullptr), 8 * un, false},
+                          {"slots", (uintptr_t)(dSlotOut ? dSlot : nullptr), 4 * un, false},
+                          {"compacted rays", (uintptr_t)dRaysOut, 36 * un, true},
+                          {"compacted rng states", (uintptr_t)dRngOut, 8 * un, true},
+                          {"compacted slots", (uintptr_t)dSlotOut, 4 * un, true},
+                          {"compacted mask", (uintptr_t)dActiveOut, un, true},
+                          {"count", (uintptr_t)dCount, 8, true},
+                          {"scratch", (uintptr_t)dScratch, (uint64_t)srtCompactPathsScratchBytes(n), true}};
+  const Range *mask = &ranges[1], *maskOut = &ranges[8];
+  for (const Range& w : ranges) {
+    if (!w.written || !w.at) continue;
+    for (const Range& r : ranges) {
+      if (&r == &w || !r.at || (r.written && &r < &w)) continue;  // a pair of written ranges once
+      if (&w == maskOut && &r == mask && dActiveOut == dActive) continue;
+      if (w.at < r.at + r.bytes && r.at < w.at + w.bytes)
+        return fail(ctx, "%s: the %s overlap the %s", what, w.name, r.name);
+    }
+  }
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  CompactArgs a;
+  a.out = static_cast<const int32_t*>(dOut);
+  a.active = static_cast<const uint8_t*>(dActive);
+  a.rays = static_cast<const uint32_t*>(dRays);
+  a.rng = static_cast<const uint64_t*>(dRng);
+  a.slot = static_cast<const int32_t*>(dSlot);
+  a.raysOut = static_cast<uint32_t*>(dRaysOut);
+  a.rngOut = static_cast<uint64_t*>(dRngOut);
+  a.slotOut = static_cast<int32_t*>(dSlotOut);
+  a.activeOut = static_cast<uint8_t*>(dActiveOut);
+  a.count = static_cast<int64_t*>(dCount);
+  a.tileOffset = static_cast<uint64_t*>(dScratch);
+  a.n = n;
+  a.numTiles = compactTiles(n);
+  const int grid = (int)std::min<int64_t>(a.numTiles, (int64_t)ctx->prop.multiProcessorCount * 8);
+  const int e = srt_launch_compact(&a, grid, static_cast<hipStream_t>(streamPtr));
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+int srtCompactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const void* dActive, const void* dRays, const void* dRng,
+                          const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut, void* dActiveOut, void* dCount,
+                          void* dScratch, void* stream) {
+  SRT_GUARDED(ctx, compactPathsDevice(ctx, n, dOut, dActive, dRays, dRng, dSlot, dRaysOut, dRngOut, dSlotOut, dActiveOut, dCount,
+                                      dScratch, stream));
+}
+
 int srtCameraRaysDevice(SrtContext* ctx, const SrtRenderParams* p, const void* dPixelSample, int64_t n, void* dRays, void* dRng,
                         void* stream) {
   SRT_GUARDED(ctx, cameraRaysDevice(ctx, p, dPixelSample, n, dRays, dRng, stream));

@@ -34,6 +34,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtTraceRaysDevice", "srtOccludedDevice", "srtScatterRays",
            "srtRngKey", "srtCameraRaysDevice", "srtScatterRaysDevice", "srtPathStepDevice",
+           "srtCompactPathsScratchBytes", "srtCompactPathsDevice",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
@@ -138,6 +139,9 @@ lib.srtRngKey.restype = C.c_uint64
 lib.srtCameraRaysDevice.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, C.c_int64, _vp, _vp, _vp]
 lib.srtScatterRaysDevice.argtypes = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]
 lib.srtPathStepDevice.argtypes = [_vp, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]
+lib.srtCompactPathsScratchBytes.argtypes = [C.c_int64]
+lib.srtCompactPathsScratchBytes.restype = C.c_int64
+lib.srtCompactPathsDevice.argtypes = [_vp, C.c_int64] + [_vp] * 12
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
 lib.srtGatherTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
@@ -801,6 +805,80 @@ class Context:
         self._check(lib.srtPathStepDevice(self.h, int(traversal), ptr(rays), n, ptr(active), ptr(rng), ptr(out), ptr(rays_out),
                                           ptr(d_hits), self._stream_handle(stream)))
         return (out, rays_out, d_hits) if hits else (out, rays_out)
+
+    def compact_paths_device(self, out=None, active=None, rays=None, rng=None, slot=None, rays_out=None, rng_out=None, slot_out=None,
+                             active_out=None, slots=True, count=None, scratch=None, stream=None):
+        """srtCompactPathsDevice: the entries that go on, moved in their order to the front of fresh buffers, asynchronous on
+        `stream`.  Kept are the entries whose `out` row (int32 (n, 8), as a step returns it) says SCATTERED and whose `active`
+        byte (uint8 (n,)) is not 0; either may be None, not both -- pass the mask of the step that wrote `out`, because an
+        inactive entry's row is stale.  rays float32 (n, 9), rng int64 (n,), slot int32 (n,): the payloads, each optional;
+        *_out: where the kept rows go (allocated at n rows when None and the input is given; none may be an input).
+        slots: also return the index every kept entry had (`slot` carried through, the identity without one).  active_out:
+        a uint8 (n,) tensor that receives i < count (it may be `active` itself), or True to allocate one.  count: an int64
+        tensor of one element to receive the number kept; scratch: uint8, at least compact_scratch_bytes(n).
+        Returns (rays_out, rng_out, slot_out, active_out, count): None where nothing was asked for, rows behind count as
+        they were, count a 0-dim int64 tensor on the GPU (reading it synchronises)."""
+        import torch
+        first = None
+        if rays is not None:
+            first = rays = self._device_rays(rays)
+        if out is not None:
+            out = self._device_tensor(out, "out", "int32", (-1, 8), first)
+            first = out if first is None else first
+        if active is not None:
+            active = self._device_tensor(active, "active", "uint8", (-1,), first)
+            first = active if first is None else first
+        if out is None and active is None:
+            raise ValueError("out and active must not both be None: one of them is the predicate")
+        n = (out if out is not None else active).shape[0]
+        for name, t in (("rays", rays), ("out", out), ("active", active)):
+            if t is not None and t.shape[0] != n:
+                raise ValueError("%s must have %d rows like the predicate, not %d" % (name, n, t.shape[0]))
+        if rng is not None:
+            rng = self._device_tensor(rng, "rng", "int64", (n,), first)
+        if slot is not None:
+            slot = self._device_tensor(slot, "slot", "int32", (n,), first)
+        for name, given, source in (("rays_out", rays_out, rays), ("rng_out", rng_out, rng)):
+            if given is not None and source is None:
+                raise ValueError("%s without %s" % (name, name[:-4]))
+        if rays is not None:
+            rays_out = torch.empty_like(rays) if rays_out is None else self._device_tensor(rays_out, "rays_out", "float32", (n, 9), first)
+        if rng is not None:
+            rng_out = torch.empty_like(rng) if rng_out is None else self._device_tensor(rng_out, "rng_out", "int64", (n,), first)
+        if slot_out is not None:
+            slot_out = self._device_tensor(slot_out, "slot_out", "int32", (n,), first)
+        elif slots or slot is not None:
+            slot_out = torch.empty((n,), dtype=torch.int32, device=first.device)
+        if active_out is True:
+            active_out = torch.empty((n,), dtype=torch.uint8, device=first.device)
+        elif active_out is not None and active_out is not False:
+            active_out = self._device_tensor(active_out, "active_out", "uint8", (n,), first)
+        else:
+            active_out = None
+        need = self.compact_scratch_bytes(n)
+        if scratch is None:
+            scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=first.device)
+        else:
+            scratch = self._device_tensor(scratch, "scratch", "uint8", (-1,), first)
+            if scratch.shape[0] < need:
+                raise ValueError("scratch must hold %d bytes, not %d" % (need, scratch.shape[0]))
+        if count is None:
+            count = torch.empty((1,), dtype=torch.int64, device=first.device)
+        else:
+            count = self._device_tensor(count, "count", "int64", (1,), first)
+        if n == 0:  # the entry does not write the count of nothing
+            count.zero_()
+        else:
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            self._check(lib.srtCompactPathsDevice(self.h, n, ptr(out), ptr(active), ptr(rays), ptr(rng), ptr(slot), ptr(rays_out),
+                                                  ptr(rng_out), ptr(slot_out), ptr(active_out), ptr(count), ptr(scratch),
+                                                  self._stream_handle(stream)))
+        return rays_out, rng_out, slot_out, active_out, count.reshape(())
+
+    @staticmethod
+    def compact_scratch_bytes(n):
+        """srtCompactPathsScratchBytes: 8 bytes per tile of abi.SRT_COMPACT_TILE entries, 0 for n <= 0."""
+        return int(lib.srtCompactPathsScratchBytes(int(n)))
 
     def scatter_test(self, rays, hits, seed):
         rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)

@@ -12,13 +12,17 @@ _DEAD = -2  # a status no step writes: an entry that was not active in this step
 
 
 def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_FAITHFUL, fused=True, stream=None,
-                    active_counts=None):
+                    active_counts=None, compact=False):
     """The radiance of one path per ray: at most max_bounce steps, then the unwinding.  rays (n, 9) float32 and rng (n,)
     int64 as Context.camera_rays_device returns them; both are overwritten.  fused: one path_step_device per bounce;
     otherwise trace_device(records=True) + scatter_device, which compute the same bytes through an 88-byte record per ray.
     active_counts: a list that receives, per bounce, the number of entries still on their way (a 0-dim tensor: reading it
-    synchronises, so read it after the loop).  Returns (n, 3) float32."""
+    synchronises, so read it after the loop).  compact: every bounce after the first runs on the live entries alone,
+    moved to the front by Context.compact_paths_device (_sample_radiance_compact below): the same bits.  Returns (n, 3)
+    float32."""
     import torch
+    if compact:
+        return _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts)
     n = rays.shape[0]
     bg = torch.tensor([float(c) for c in background], dtype=torch.float32, device=rays.device)
     terminal = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)  # maxBounce steps all scattered: black
@@ -48,11 +52,61 @@ def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TR
     return radiance
 
 
-def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples_per_batch=None, device=None, active_counts=None):
+def _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts):
+    """sample_radiance with the live set compacted between bounces.  Step j runs on the m_j entries that scattered in
+    every step before it (m_0 = n), dense at the front of ping-pong ray and state buffers; its SrtPathOut rows are kept at
+    that length together with the slot list that says which of its rows the m_(j+1) survivors were.  The unwinding goes
+    through those lists innermost first with the same separate multiply and add.  The number kept is read once per
+    bounce (8 bytes, a synchronisation) to size the next step, and the loop stops when nobody is left."""
+    import torch
+    n = rays.shape[0]
+    bg = torch.tensor([float(c) for c in background], dtype=torch.float32, device=rays.device)
+    spare_rays, spare_rng = torch.empty_like(rays), torch.empty_like(rng)
+    scratch = torch.empty((max(ctx.compact_scratch_bytes(n), 8),), dtype=torch.uint8, device=rays.device)
+    steps = []  # per step: (out (m_j, 8) int32, slot (m_(j+1),) int32 or None behind the last step)
+    m, live = n, torch.tensor(n, dtype=torch.int64, device=rays.device)
+    for bounce in range(max_bounce):
+        if active_counts is not None:
+            active_counts.append(live if m else torch.zeros_like(live))
+        if m == 0:
+            continue
+        step_rays, step_rng = rays[:m], rng[:m]
+        if fused:
+            out, _ = ctx.path_step_device(step_rays, step_rng, traversal, rays_out=step_rays, stream=stream)
+        else:
+            _, records = ctx.trace_device(step_rays, traversal, records=True, stream=stream)
+            out, _ = ctx.scatter_device(step_rays, records, step_rng, rays_out=step_rays, stream=stream)
+        if bounce + 1 == max_bounce:
+            steps.append((out, None))
+            break
+        # every entry of this step was live: its status alone is the predicate
+        _, _, slot, _, live = ctx.compact_paths_device(out=out, rays=step_rays, rng=step_rng, rays_out=spare_rays[:m], rng_out=spare_rng[:m],
+                                                       scratch=scratch, stream=stream)
+        m = int(live)
+        steps.append((out, slot[:m]))
+        rays, spare_rays, rng, spare_rng = spare_rays, rays, spare_rng, rng
+    # emitted + newColor * attenuation with emitted = 0, innermost first (main.cpp:49-51): a multiply, then an add
+    inner = None  # the radiance of the entries of the step above
+    for out, slot in reversed(steps):
+        status, colours = out[:, 3], out.view(torch.float32)
+        radiance = torch.zeros((out.shape[0], 3), dtype=torch.float32, device=out.device)
+        radiance = torch.where((status == abi.SRT_PATH_MISS)[:, None], bg, radiance)
+        radiance = torch.where((status == abi.SRT_PATH_ENDED)[:, None], colours[:, 4:7], radiance)
+        if slot is None:  # maxBounce steps all scattered: black, through the last attenuation like every other
+            radiance = torch.where((status == abi.SRT_PATH_SCATTERED)[:, None], radiance * colours[:, 0:3] + 0.0, radiance)
+        elif slot.shape[0]:
+            index = slot.to(torch.int64)
+            radiance.index_copy_(0, index, inner * colours.index_select(0, index)[:, 0:3] + 0.0)
+        inner = radiance
+    return inner if inner is not None else torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+
+
+def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples_per_batch=None, device=None, active_counts=None,
+           compact=False):
     """params.spp samples of every pixel from params.sampleFirst on, through the device path steps: the (H, W, 4) float32
     torch tensor of per-pixel radiance sums (the float running sum in sample-index order) with the sample count in w --
     Context.render_image's accumulation buffer.  samples_per_batch: how many sample indices of the whole frame go through
-    the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  Runs on torch's current stream."""
+    the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  compact: sample_radiance's.  Runs on torch's current stream."""
     import torch
     device = torch.device("cuda" if device is None else device)
     W, H, spp = params.imageWidth, params.imageHeight, params.spp
@@ -69,7 +123,7 @@ def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples
                                         torch.arange(params.sampleFirst + first, params.sampleFirst + first + count, dtype=torch.int32,
                                                      device=device).repeat_interleave(pixels)), dim=1).contiguous()
             rays, rng = ctx.camera_rays_device(params, pixel_sample, stream=stream)
-            radiance = sample_radiance(ctx, rays, rng, params.maxBounce, params.background, traversal, fused, stream, active_counts)
+            radiance = sample_radiance(ctx, rays, rng, params.maxBounce, params.background, traversal, fused, stream, active_counts, compact)
             for k in range(count):
                 image[:, 0:3] += radiance[k * pixels:(k + 1) * pixels]
         image[:, 3] = float(spp)

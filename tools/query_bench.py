@@ -15,7 +15,9 @@ through the only entry there was, not a kernel comparison.
 
 --path-loop measures the device path steps instead (path_loop below): pathloop.render fused and unfused against
 srtRenderTiles on masterchief (reference tree FAITHFUL, PLOC tree CLOSEST) and soup_200k (PLOC, CLOSEST), 4 and 16 spp,
-4 bounces, with the active share of the entries per bounce.
+4 bounces, with the active share of the entries per bounce; the same two loops with the live set compacted between bounces
+(compact=True) alternate with them, and `compact_call` is one srtCompactPathsDevice call behind the first bounce of the
+whole batch (rays, states and slots moved), timed with events like the queries above.
 
 usage: python tools/query_bench.py [--steps 200] [--warmup 5] [--host-steps 3] [--cases masterchief,soup_200k,soup_1m] [--ao-rays 4]
                                    [--ao-radius 0.1] [--ao-png FILE] [--width 1280] [--height 720]
@@ -126,11 +128,28 @@ def measure(ctx, rays, faithful, steps, warmup, host_steps):
     return out, occ
 
 
+def compact_call(ctx, p, traversal, steps, warmup):
+    """One srtCompactPathsDevice call at the batch size of the frame: behind the first bounce of all W * H * spp camera
+    rays, moving rays, states and slots into buffers allocated once."""
+    rays, rng = ctx.camera_rays_device(p)
+    out, _ = ctx.path_step_device(rays, rng, traversal, rays_out=rays)
+    n = rays.shape[0]
+    rays_out, rng_out = torch.empty_like(rays), torch.empty_like(rng)
+    slot_out = torch.empty((n,), dtype=torch.int32, device="cuda")
+    count = torch.empty((1,), dtype=torch.int64, device="cuda")
+    scratch = torch.empty((ctx.compact_scratch_bytes(n),), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    ms = event_ms(stream, lambda: ctx.compact_paths_device(out=out, rays=rays, rng=rng, rays_out=rays_out, rng_out=rng_out, slot_out=slot_out,
+                                                           count=count, scratch=scratch, stream=stream), steps, warmup)
+    return {"n": n, "kept_share": int(count) / float(n), "ms": ms, "steps": steps}
+
+
 def path_loop(a):
     """--path-loop: the user-land path tracer (pathloop.render over srtCameraRaysDevice + srtPathStepDevice, fused, and
     over srtTraceRaysDevice(records) + srtScatterRaysDevice, unfused) against srtRenderTiles of the same samples.
-    Events around whole loops after a warm-up; the three alternate within one session, --loop-reps times, and every
-    figure is the median with the spread (min, max) beside it."""
+    Events around whole loops after a warm-up; these three and the two loops with compaction between bounces alternate
+    within one session, --loop-reps times, and every figure is the median with the spread (min, max) beside it."""
     pathloop = importlib.import_module("sexy-raytracer_amd.pathloop")
     ctx = dev.Context(0)
     cam = dev.make_camera(abi.default_camera_params())
@@ -157,6 +176,8 @@ def path_loop(a):
             p = abi.default_render_params(W, H, spp, bounces, seed=1, traversal=traversal)
             variants = {"fused": lambda: pathloop.render(ctx, p, fused=True, traversal=traversal),
                         "unfused": lambda: pathloop.render(ctx, p, fused=False, traversal=traversal),
+                        "fused_compact": lambda: pathloop.render(ctx, p, fused=True, traversal=traversal, compact=True),
+                        "unfused_compact": lambda: pathloop.render(ctx, p, fused=False, traversal=traversal, compact=True),
                         "render_tiles": lambda: ctx.render_tiles(p, tiles.data_ptr(), stream.cuda_stream)}
             ms = {k: [] for k in variants}
             for rep in range(a.warmup_loops + a.loop_reps):
@@ -175,6 +196,7 @@ def path_loop(a):
             for name, v in ms.items():
                 med = float(np.median(v))
                 entry[name] = {"ms": med, "spread_ms": [min(v), max(v)], "msamples_s": W * H * spp / med * 1e-3}
+            entry["compact_call"] = compact_call(ctx, p, traversal, a.steps, a.warmup)
             out["spp_%d" % spp] = entry
         result["cases"][label] = out
     ctx.close()
