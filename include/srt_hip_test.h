@@ -88,6 +88,18 @@ int srtTestThreadLinks16(const float* nodes8, int32_t numNodes, const int32_t* w
 int srtTestHybridRecords(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, int32_t numTriangles, int32_t numSpheres,
                          int32_t cap, float* outNodes8, int32_t* outWorld, int32_t* outSecond);
 
+/* The regrouped tree of the path-pool kernel's whole-tree form (csrc/srt_regroup.h; tunable "wf_regroup", default 1, 0 = the
+ * kernel walks the reference tree): the reference's leaf records in the reference's order under inner nodes rebuilt by a
+ * surface-area split over contiguous leaf ranges.  Every walk ends at the same (t, primitive); accumulators are bit-identical.
+ * srtTestRegroup (host only, no device): the regrouped array of a flattened node array (the format above) and its world
+ * list -> outNodes8[numNodes x 8]; returns 1, 0 when a tree is not a pre-order tree of two-node / two-primitive nodes, -1 on a
+ * null argument.
+ * srtTestGetRegroup: the uploaded scene's regrouped array and its 16-bit thread links (DevScene::nodesRg / nodeThreadRg) as they
+ * lie in device memory now (after srtRefitScene as well) -> outNodes8[count x 8], outLinks[count]; either may be NULL.
+ * *count = 0 when the upload built none (a tree beyond LDS, a caller-built tree, device-built trees, a box that is not ordered). */
+int srtTestRegroup(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, float* outNodes8);
+int srtTestGetRegroup(SrtContext* ctx, float* outNodes8, int32_t* outLinks, int32_t capacity, int32_t* count);
+
 /* Reads back what the near-child-first traversal walks for world item `item` (host-built and device-built trees alike), as
  * it lies in device memory: the item's slice of DevScene::nodeAxis -> outAxis[count] (the split axis of each node, 3 = none)
  * and of DevScene::nodes2 -> outPairs16[count x 16] (the 64-byte records of csrc/srt_lbvh.hip pairNodes: left child's box

@@ -15,6 +15,7 @@
 
 #include "srt_context.h"
 #include "srt_launch.h"
+#include "srt_regroup.h"
 #include "srt_thread.h"
 
 int fail(SrtContext* ctx, const char* fmt, ...) {
@@ -95,6 +96,9 @@ const TunableName kTunables[] = {
     // 0 = 2 for trees of up to 2^20 nodes (cache-resident: +10 % and more), 1 beyond (HBM-bound soups of 4 M and 10 M
     // triangles lose 5-10 % with 2) -- profiles/r03/hybrid.txt
     {"wf_far_rounds", "SRT_WF_FAR_ROUNDS", &Tunables::wfFarRounds, 0},
+    // path-pool kernel over a whole tree: walk the regrouped tree (srt_regroup.h, DevScene::nodesRg) where the upload built
+    // one.  0 = the reference tree: the same accumulators from about twice the node visits.  Read at every launch.
+    {"wf_regroup", "SRT_WF_REGROUP", &Tunables::wfRegroup, 1},
     // srtDenoise: a-trous levels of step <= this stage their (16 + 4 step)^2 window in LDS, larger steps read through the
     // caches (srt_denoise.hip; 8 at most, 0 = never) -- profiles/r05/denoise_bench.json
     {"denoise_lds_step", "SRT_DENOISE_LDS_STEP", &Tunables::denoiseLdsStep, 4},
@@ -155,6 +159,7 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
 
   DevScene& s = ctx->upload.scene;
   if (!h.nodeThread.empty() && uploadVec(ctx, h.nodeThread, &s.nodeThread)) return 1;
+  if (!h.nodesRg.empty() && (uploadVec(ctx, h.nodesRg, &s.nodesRg) || uploadVec(ctx, h.nodeThreadRg, &s.nodeThreadRg))) return 1;
   if (!h.nodesWf.empty() && (uploadVec(ctx, h.nodesWf, &s.nodesWf) || uploadVec(ctx, h.worldWf, &s.worldWf) || uploadVec(ctx, h.primSecond, &s.primSecond))) return 1;
   if (uploadVec(ctx, h.primClass, &s.primClass, 16) || uploadVec(ctx, h.nodeAxis, &s.nodeAxis, 64) || uploadVec(ctx, h.nodes, &s.nodes) ||
       uploadVec(ctx, h.triTest, &s.triTest) || uploadVec(ctx, h.triFast, &s.triFast) || uploadVec(ctx, h.triShade, &s.triShade) || uploadVec(ctx, h.spheres, &s.spheres) ||
@@ -423,6 +428,29 @@ int srtTestHybridRecords(const float* nodes8, int32_t numNodes, const int32_t* w
   memcpy(outWorld, w.data(), w.size() * sizeof(int32_t));
   memcpy(outSecond, second.data(), second.size() * sizeof(int32_t));
   return resident;
+}
+
+/* include/srt_hip_test.h: host-only hook for srt_regroup.h, and the uploaded scene's regrouped array as it lies on the device */
+int srtTestRegroup(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, float* outNodes8) {
+  if (!nodes8 || !world || !outNodes8 || numNodes < 0 || numWorld < 0) return -1;
+  std::vector<float4> nodes(2 * (size_t)numNodes), out;
+  if (numNodes) memcpy(nodes.data(), nodes8, nodes.size() * sizeof(float4));
+  if (!srtRegroupNodes(nodes, std::vector<int32_t>(world, world + numWorld), out)) return 0;
+  if (numNodes) memcpy(outNodes8, out.data(), out.size() * sizeof(float4));
+  return 1;
+}
+int srtTestGetRegroup(SrtContext* ctx, float* outNodes8, int32_t* outLinks, int32_t capacity, int32_t* count) {
+  if (!ctx || !count) return 1;
+  if (!ctx->upload.haveScene) return fail(ctx, "srtTestGetRegroup: no scene uploaded");
+  const DevScene& s = ctx->upload.scene;
+  *count = s.nodesRg ? s.numNodes : 0;
+  if (!s.nodesRg || (!outNodes8 && !outLinks)) return 0;
+  if (capacity < s.numNodes) return fail(ctx, "srtTestGetRegroup: capacity %d < %d", capacity, s.numNodes);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  HIP_OK(ctx, hipDeviceSynchronize());
+  if (outNodes8) HIP_OK(ctx, hipMemcpy(outNodes8, s.nodesRg, (size_t)s.numNodes * 32, hipMemcpyDeviceToHost));
+  if (outLinks) HIP_OK(ctx, hipMemcpy(outLinks, s.nodeThreadRg, (size_t)s.numNodes * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 /* include/srt_hip_test.h: world item `item`'s slice of DevScene::nodeAxis and DevScene::nodes2, read back as they are */

@@ -27,6 +27,7 @@ struct Tunables {
   int ldsTree;
   int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
   int wfHybrid, wfResidentMax, wfFarRounds;
+  int wfRegroup;
   int denoiseLdsStep;
   int triCert;
 };
@@ -60,6 +61,7 @@ struct Upload {
   std::vector<int32_t> hostTriDevIndex, hostWfIndex;  // HostScene::triDevIndex, wfIndex
   std::vector<uint8_t> itemBoxesStale;                // per world item: itemNodes holds boxes from before a refit
   DeviceBuffer triDevIndex, wfIndex, refitUp, refitArrived;
+  DeviceBuffer refitUpRg;           // the regrouped tree's parent links (scene.nodesRg): refitted in the same pass
   bool refitTables = false;         // refitUp, refitArrived (and wfIndex) exist for this scene
   bool refitLinksStale = false;     // refitUp is not of the current topology: srtRebuildScene has built trees since
   bool geometryDirty = false;       // an update since the last refit: nothing renders

@@ -113,6 +113,13 @@ struct DevScene {
   const DevTexture* textures;
   const uint8_t* texels;  // images of >= 3 bytes per pixel as one dword per texel (RGBA8), others as byte rows
   int32_t texelBytes;     // extent of `texels` (buffer-resource bound: reads past it return 0)
+  // path-pool kernel, whole-tree form: the REGROUPED tree (srt_regroup.h) -- `nodes`' layout, size, node range per world
+  // item and leaf records, other inner nodes over the same leaf sequence -- and its thread links, `nodeThread`'s format.
+  // The production, moments and profiling instances copy it into LDS in place of the reference tree; every walk ends at
+  // the same (t, primitive).  Null: not built (a tree beyond LDS, a caller-built tree, a box that is not ordered), or
+  // switched off for the launch (tunable "wf_regroup", a counting launch, boxOrderedScene lost in a refit).
+  const float4* nodesRg;
+  const int32_t* nodeThreadRg;
 };
 
 struct DevCamera {

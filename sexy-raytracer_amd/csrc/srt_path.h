@@ -188,6 +188,11 @@ __device__ __forceinline__ bool boxHitSign(float4 n0, float4 n1, V3 rp, V3 rq, V
                                            bool& undecided) {
   return srtSlabVerdict<UNIFORM_TMIN, true>(srtSlabEndsSign(n0, n1, slab3(rp), slab3(rq), slab3(m)), tolAbs, tMin, tMax, undecided);
 }
+// boxHit, or for a lane with `gate` set the exact test's gate form for an inner node of the regrouped tree (srt_slab.h
+// srtSlabExactOrGate: one body, the same six divisions)
+__device__ __forceinline__ bool boxHitOrGate(float4 n0, float4 n1, const Ray& r, float tMin, float tMax, bool gate) {
+  return srtSlabExactOrGate(n0, n1, slab3(r.o), slab3(r.d), tMin, tMax, gate);
+}
 // Closest-hit traversal: the conservative use of the same intervals (srtSlabMaybe)
 __device__ __forceinline__ bool boxMaybeHit(float4 lo, float4 hi, V3 r1, V3 m, float tolAbs, float tMin, float tMax, float& tEnter) {
   return srtSlabMaybe<false>(srtSlabEndsMinMax(lo, hi, slab3(r1), slab3(m)), tolAbs, tMin, tMax, tEnter);

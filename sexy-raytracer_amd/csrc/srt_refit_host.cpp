@@ -147,6 +147,11 @@ int refitScene(SrtContext* ctx, void* streamPtr, bool rebuild) {
       const int e = srt_launch_refit_links(s.nodes, n, ctx->upload.refitUp.get<int32_t>(), stream);
       if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
       ctx->upload.refitLinksStale = false;
+      if (s.nodesRg) {  // (a regrouped tree exists only without device builds: its topology is the upload's for good)
+        HIP_OK(ctx, ctx->upload.refitUpRg.reserve((size_t)n * sizeof(int32_t)));
+        const int eRg = srt_launch_refit_links(s.nodesRg, n, ctx->upload.refitUpRg.get<int32_t>(), stream);
+        if (eRg) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)eRg));
+      }
     }
     HIP_OK(ctx, hipMemsetAsync(ctx->upload.refitArrived.get(), 0, (size_t)n * sizeof(int32_t), stream));
     HIP_OK(ctx, hipMemsetAsync(ctx->refitFlag.get(), 0, 16, stream));
@@ -156,6 +161,20 @@ int refitScene(SrtContext* ctx, void* streamPtr, bool rebuild) {
       e = srt_launch_refit_nodes(&s, t.base, t.count, t.time0, t.time1, ctx->upload.refitUp.get<const int32_t>(), ctx->upload.refitArrived.get<int32_t>(),
                                  ctx->refitFlag.get<int32_t>(), t.deviceBuilt ? 1 : 0, stream);
       if (e) break;
+    }
+    if (!e && s.nodesRg) {
+      // The regrouped tree (srt_regroup.h) in the same pass, by the same kernel as it stands: a copy of the scene whose
+      // node array is the regrouped one, its own parent links, the counters zeroed again behind the first pass.  Leaf
+      // boxes come from the same primitive records by the same arithmetic, inner boxes are unions of their children's: the
+      // topology stays valid (any grouping of the leaf sequence is).  flag: host-built items set no bit in this kernel.
+      DevScene rg = s;
+      rg.nodes = s.nodesRg;
+      e = (int)hipMemsetAsync(ctx->upload.refitArrived.get(), 0, (size_t)n * sizeof(int32_t), stream);
+      for (const Upload::Tree& t : ctx->upload.trees) {
+        if (e) break;
+        e = srt_launch_refit_nodes(&rg, t.base, t.count, t.time0, t.time1, ctx->upload.refitUpRg.get<const int32_t>(),
+                                   ctx->upload.refitArrived.get<int32_t>(), ctx->refitFlag.get<int32_t>(), 0, stream);
+      }
     }
     if (!e) e = srt_launch_refit_derived(&s, s.nodesWf ? ctx->upload.wfIndex.get<const int32_t>() : nullptr, ctx->refitFlag.get<int32_t>(), stream);
     if (!e) e = srt_pair_nodes_async(&s, ctx->upload.pairTime0, ctx->upload.pairTime1, const_cast<float4*>(s.nodes2), stream);

@@ -271,6 +271,9 @@ int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTi
     }
   }
   const RenderPlan plan = renderPlan(ctx, p, moments, dList ? listTiles : -1);
+  // The regrouped tree (srt_regroup.h) is walked by the whole-tree path-pool form alone, never by a counting launch, and
+  // only while every box is ordered (its lemma's condition: a refit may have lost it)
+  if (plan.form != 3 || plan.count || ctx->tun.wfRegroup <= 0 || !a.scene.boxOrderedScene) a.scene.nodesRg = nullptr, a.scene.nodeThreadRg = nullptr;
   if (plan.lds > 160 * 1024) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->upload.scene.stackDepth, plan.lds);
   const RenderKernel kernel = plan.form >= 3 ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
   if (plan.lds > 64 * 1024)

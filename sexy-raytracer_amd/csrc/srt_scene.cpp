@@ -16,6 +16,7 @@
 #include <limits>
 #include <random>
 
+#include "srt_regroup.h"
 #include "srt_thread.h"
 
 namespace {
@@ -251,8 +252,10 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
 
   // ---- world: build each bvhNode (consumes the global generator in scene order)
   h.itemNodes.resize(d->numWorld);
+  bool adopted = false;  // a caller-built tree: its inner boxes are the caller's, not unions of its leaves'
   for (int w = 0; w < d->numWorld; ++w) {
     const SrtWorldItem& it = d->world[w];
+    adopted = adopted || (it.kind == SRT_WORLD_BVH && it.nodes);
     if (it.kind == SRT_WORLD_PRIM) {
       h.world.push_back(devRef(~it.first));
       continue;
@@ -492,6 +495,24 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
       if (n > (o.wfResidentMax > 0 ? cap : fitsWhole))
         h.wfResident = srtHybridRecords(h.nodes, h.world, d->numTriangles, d->numSpheres, cap, h.nodesWf, h.worldWf, h.primSecond, &h.wfIndex);
       if (h.nodesWf.empty()) h.wfIndex.clear();
+    }
+    // ---- the regrouped tree (srt_regroup.h) for the path-pool kernel's whole-tree form.  The builder is quadratic in a
+    // tree's leaves at worst, so it runs only for what that form can take: thread links exist, no hybrid records were
+    // made, and the node array fits a CU's LDS beside the smallest pool.  Its lemma wants the reference's inner boxes to
+    // contain their leaves' (the trees built here; a caller-built tree promises nothing) and ordered boxes.  The planes of
+    // its inner boxes are planes of the leaves, so fastDivScene and boxOrderedScene hold for it as they stand.
+    const size_t fitsWholeTree = (160 * 1024 - 64 * sizeof(int32_t) - 18 * 1024) / 32;
+    if (!h.nodeThread.empty() && h.nodesWf.empty() && !adopted && ordered && h.nodes.size() / 2 <= fitsWholeTree &&
+        srtRegroupNodes(h.nodes, h.world, h.nodesRg)) {
+      srtThreadLinks16(h.nodesRg, h.world, d->numTriangles, d->numSpheres, h.nodeThreadRg);
+      bool same = !h.nodeThreadRg.empty();
+      for (const float4& v : h.nodesRg) same = same && (!certified || (fastDivOperand(v.x) && fastDivOperand(v.y) && fastDivOperand(v.z)));
+      for (size_t i = 0; same && i + 1 < h.nodesRg.size(); i += 2)
+        same = srtBoxOrdered(Box{{h.nodesRg[i].x, h.nodesRg[i].y, h.nodesRg[i].z}, {h.nodesRg[i + 1].x, h.nodesRg[i + 1].y, h.nodesRg[i + 1].z}});
+      if (!same) {  // (cannot happen: see srt_regroup.h unite)
+        h.nodesRg.clear();
+        h.nodeThreadRg.clear();
+      }
     }
   }
   // ---- material class per primitive reference (DevScene::primClass)

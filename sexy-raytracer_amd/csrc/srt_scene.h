@@ -75,6 +75,10 @@ struct HostScene {
   std::vector<uint4> shadeRecs;
   std::vector<uint8_t> primClass;
   std::vector<int32_t> nodeThread;  // empty: no 16-bit thread links
+  // the regrouped tree of the path-pool kernel's whole-tree form (srt_regroup.h): nodes' size and node ranges, other inner
+  // nodes over the same leaves, and its own 16-bit thread links.  Empty: not built
+  std::vector<float4> nodesRg;
+  std::vector<int32_t> nodeThreadRg;
   std::vector<float4> nodesWf;      // empty: no hybrid records
   std::vector<int32_t> worldWf, primSecond;
   int32_t wfResident = 0;

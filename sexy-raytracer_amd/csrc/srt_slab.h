@@ -167,6 +167,36 @@ SRT_SLAB_FN bool srtSlabVerdict(const SrtSlabEnds& e, float tolAbs, float tMin, 
   undecided = !(fabsf(diff) > tol);  // also when a NaN got in, and always when tolAbs = +inf
   return diff > tol;
 }
+// ---- the GATE form of the exact test (aabb.h:11-27 with the IEEE divisions), for an inner node of the path-pool kernel's
+// regrouped tree (srt_regroup.h), where a box decides nothing but whether the leaves below it are looked at: it must pass
+// wherever the reference's test passes on a box inside it.  On an axis with a finite non-zero d the reference's quotients
+// are monotone in the plane, so its own arithmetic is nested and is kept.  On an axis with d == +-0 the reference passes
+// min < o < max (quotients -inf, +inf) and the point interval min == max == o (both quotients NaN, which fminf / fmaxf
+// drop), and misses min == o < max (NaN and +inf: tMin becomes +inf) -- not nested: a flat leaf box passes inside a box
+// that misses.  The gate takes the closed interval there, min <= o <= max, written so that a NaN origin passes as it does
+// in the reference; it puts no bound on t.  examples/regroup_probe.cpp checks "leaf passes => gate passes" at these edges.
+// ONE body for both: `gate` false is aabb.h:11-27 operation for operation (srt_path.h boxHit); true switches the d == +-0
+// axes to the closed interval.  The six divisions are shared, so a kernel that judges gates and leaves in one block carries
+// them once (per lane: an inner node of the regrouped tree is a gate, a leaf is not).
+SRT_SLAB_FN void srtSlabExactAxis(float n0, float n1, float o, float d, bool gate, float& tMin, float& tMax, bool& inside) {
+  const float a = (n0 - o) / d, b = (n1 - o) / d;
+  const float lo = fmaxf(fminf(a, b), tMin), hi = fminf(fmaxf(a, b), tMax);
+  const bool closed = gate & (d == 0.0f);
+  tMin = closed ? tMin : lo;
+  tMax = closed ? tMax : hi;
+  inside = inside & !(closed & ((o < n0) | (o > n1)));
+}
+SRT_SLAB_FN bool srtSlabExactOrGate(float4 n0, float4 n1, SrtSlab3 o, SrtSlab3 d, float tMin, float tMax, bool gate) {
+  bool inside = true;
+  srtSlabExactAxis(n0.x, n1.x, o.x, d.x, gate, tMin, tMax, inside);
+  srtSlabExactAxis(n0.y, n1.y, o.y, d.y, gate, tMin, tMax, inside);
+  srtSlabExactAxis(n0.z, n1.z, o.z, d.z, gate, tMin, tMax, inside);
+  return inside & !(tMax <= tMin);
+}
+SRT_SLAB_FN bool srtSlabGateExact(float4 n0, float4 n1, SrtSlab3 o, SrtSlab3 d, float tMin, float tMax) {
+  return srtSlabExactOrGate(n0, n1, o, d, tMin, tMax, true);
+}
+
 // Closest-hit traversal: the same intervals used CONSERVATIVELY -- a box is entered unless it is certainly missed
 // (tMaxA - tMinA < -tol), so no exact fallback is needed: a box entered needlessly costs time, never a hit.
 // Returns the approximate entry distance for near-first ordering.

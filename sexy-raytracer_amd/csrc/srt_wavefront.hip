@@ -99,7 +99,12 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   const unsigned long long laneBelow = (1ull << lane) - 1ull;  // (the hybrid instances' ring operations; unused in the others)
   const uint64_t seedMixed = mix64(a.seed);
   const V3 background = ld3(a.background);
-  const Rsrc rsNodes = makeRsrc(HYBRID ? sc.nodesWf : sc.nodes, sc.numNodes * 32);
+  // The production, moments and profiling instances over a whole tree walk the REGROUPED tree where the launch has one
+  // (DevScene::nodesRg, srt_regroup.h: the same leaves in the same order under other inner nodes -- the same (t, primitive)
+  // at the end of every walk, about half the visits on the headline frame).  Wave-uniform, decided once, here.  The
+  // counting instances always walk the reference tree: their counters and AOV records are the oracle's.
+  const bool regroup = !HYBRID && !COUNT && sc.nodesRg != nullptr;
+  const Rsrc rsNodes = makeRsrc(HYBRID ? sc.nodesWf : (regroup ? sc.nodesRg : sc.nodes), sc.numNodes * 32);
   const Rsrc rsTris = makeRsrc(sc.triTest, HYBRID ? sc.numTris * 48 : 0);  // (the whole-tree instances: where an undecided lane needs it)
   const Rsrc rsFast = makeRsrc(sc.triFast, HYBRID ? 0 : sc.numTris * 64);
   const Rsrc rsSpheres = makeRsrc(sc.spheres, sc.numSpheres * 48);
@@ -123,10 +128,11 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   // (srt_wf_links.h; the hybrid form's records are stored ready-made), empty rings, every context waits for an item
   {
     float4* dst = reinterpret_cast<float4*>(ldsTree);
+    const int32_t* const threads = regroup ? sc.nodeThreadRg : sc.nodeThread;
     for (int i = threadIdx.x; i < resident * 2; i += WF_BLOCK) {
       float4 v = bufLoad4(rsNodes, 16 * i);
       if (!HYBRID) {  // nodesWf holds the threaded records already
-        const int32_t thread = sc.nodeThread[i >> 1];
+        const int32_t thread = threads[i >> 1];
         v.w = __int_as_float((i & 1) ? srtWfMissWord(thread) : srtWfHitWord(__float_as_int(v.w), thread));
       }
       dst[i] = v;
@@ -345,7 +351,14 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           pLanes[8] += __popcll(mu);
           pLanes[7] += mu != 0 ? 1 : 0;
         }
-        if (undecided) hitBox = boxHit(n0, n1, ray, a.tMin, closest);
+        if constexpr (HYBRID || COUNT) {
+          if (undecided) hitBox = boxHit(n0, n1, ray, a.tMin, closest);
+        } else {
+          // An inner node of the regrouped tree is a GATE: what it decides is only whether the leaves below are looked at,
+          // and it must pass wherever one of them would (boxHitOrGate, srt_path.h: closed on an axis with d == +-0).  Leaves,
+          // and every node of the reference tree, get boxHit's own operations from the same call.
+          if (undecided) hitBox = boxHitOrGate(n0, n1, ray, a.tMin, closest, regroup & (__float_as_int(n0.w) >= 0));
+        }
         if constexpr (COUNT) {
           cnt[2]++;
           if (hitBox) cnt[3]++;

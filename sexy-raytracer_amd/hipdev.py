@@ -51,7 +51,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
                 "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
                 "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord", "srtTestGetSlabScene",
-                "srtTestRefinedRcp", "srtTestSlabVisit"]
+                "srtTestRefinedRcp", "srtTestSlabVisit", "srtTestRegroup", "srtTestGetRegroup"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -169,7 +169,11 @@ if hasattr(lib, "srtTestGetSlabScene"):  # (likewise: an SRT_HIP_LIB build from 
 if hasattr(lib, "srtTestRefinedRcp"):  # (likewise: an SRT_HIP_LIB build from before the slab-test hooks)
     lib.srtTestRefinedRcp.argtypes = [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]
     lib.srtTestSlabVisit.argtypes = [_vp, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float)]
-lib.srtRenderAov.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
+if hasattr(lib, "srtTestRegroup"):  # (likewise: an SRT_HIP_LIB build from before the regrouped tree)
+    lib.srtTestRegroup.argtypes = [_vp, C.c_int32, _vp, C.c_int32, _vp]
+    lib.srtTestRegroup.restype = C.c_int32
+    lib.srtTestGetRegroup.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
+lib.srtRenderAov.argtypes =[_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
 lib.srtLastKernelMs.argtypes = [_vp, C.POINTER(C.c_float)]
 lib.srtGetStats.argtypes = [_vp, C.POINTER(abi.SrtStats)]
 lib.srtDeviceInfo.argtypes = [_vp, C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -930,6 +934,17 @@ class Context:
         out = (C.c_int32 * 2)()
         self._check(lib.srtTestGetSlabScene(self.h, out))
         return int(out[0]), int(out[1])
+
+    def regroup(self):
+        """srtTestGetRegroup (include/srt_hip_test.h): the uploaded scene's regrouped node array (n, 8) float32 and its thread
+        links (n,) int32 as they lie in device memory now, or None when the upload built none."""
+        n = C.c_int32(0)
+        self._check(lib.srtTestGetRegroup(self.h, None, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        nodes, links = np.zeros((n.value, 8), np.float32), np.zeros(n.value, np.int32)
+        self._check(lib.srtTestGetRegroup(self.h, nodes.ctypes.data, links.ctypes.data, n.value, C.byref(n)))
+        return nodes, links
 
     def refined_rcp_test(self, first_bits, count):
         """srtTestRefinedRcp (include/srt_hip_test.h): the largest |refinedRcp(d) d - 1| (in double) over the float bit patterns
