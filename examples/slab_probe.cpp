@@ -26,8 +26,9 @@
 //     in: records of 18 words -- lo[3] hi[3] o[3] d[3] r[3] tMin tMax as float32 and an int32, the scene's fast-division word;
 //     out: per record 8 words -- r[3], tolAbs of the min/max setup, tolAbs of the sign setup, an int32 of flags, tEnter of
 //     srtSlabMaybe<false>, 0.  Flags: bit 0 certified, 1 / 2 verdict / undecided of srtSlabVerdict<false, false>, 3 / 4 of
-//     <true, false>, 5 / 6 of <true, true>, 7 srtSlabMaybe<false>, 8 the reference's verdict as restated here.  The layout of
-//     srtTestSlabVisit (include/srt_hip_test.h), which runs the device compile of the same header on the same cases.
+//     <true, false>, 5 / 6 of <true, true>, 7 srtSlabMaybe<false>, 8 the reference's verdict as restated here, 10 the gate
+//     form of the exact test on the same box (srtSlabExactOrGate, gate = true); 9 stays 0 (boxHitLoose is device code).  The
+//     layout of srtTestSlabVisit (include/srt_hip_test.h), which runs the device compile of the same header on the same cases.
 //   srt_slab_probe boxes
 //     srtBoxOrdered (csrc/srt_records.h) on an ordered, a flat, an inverted and two non-finite boxes: `ordered <0|1>` each
 #include <cmath>
@@ -457,7 +458,9 @@ int replay(const char* inPath, const char* outPath) {
     const Eval e = evaluate(c, rec.certifiedScene != 0);
     float tMinR, tMaxR;
     const bool vr = reference(c, tMinR, tMaxR);
-    const int32_t flags = (int32_t)e.certified | e.va << 1 | e.ua << 2 | e.vt << 3 | e.ut << 4 | e.vb << 5 | e.ub << 6 | e.maybeA << 7 | vr << 8;
+    const bool gate = srtSlabExactOrGate(make_float4(c.lo[0], c.lo[1], c.lo[2], 0.0f), make_float4(c.hi[0], c.hi[1], c.hi[2], 0.0f),
+                                         SrtSlab3{c.o[0], c.o[1], c.o[2]}, SrtSlab3{c.d[0], c.d[1], c.d[2]}, c.tMin, c.tMax, true);
+    const int32_t flags = (int32_t)e.certified | e.va << 1 | e.ua << 2 | e.vt << 3 | e.ut << 4 | e.vb << 5 | e.ub << 6 | e.maybeA << 7 | vr << 8 | gate << 10;
     float w[8] = {c.r[0], c.r[1], c.r[2], e.tolAbs, e.tolAbs2, 0.0f, e.tEnterA, 0.0f};
     memcpy(&w[5], &flags, 4);
     if (fwrite(w, sizeof w, 1, out) != 1) break;

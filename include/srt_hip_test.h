@@ -143,7 +143,9 @@ int srtTestGetSlabScene(SrtContext* ctx, int32_t* out2);
  * three refined reciprocals, slabSetup and slabSetupSign -- and per visit.  hOut: 8 words per case,
  *   floats 0-2  the reciprocals;  float 3  tolAbs of slabSetup;  float 4  tolAbs of slabSetupSign;
  *   word 5      flags as int32 bits: bit 0 certified; 1 / 2 verdict / undecided of boxHitApprox<false>; 3 / 4 of boxHitApprox<true>;
- *               5 / 6 of boxHitSign<true>; 7 boxMaybeHit; 8 boxHit (the reference's divisions); 9 boxHitLoose;
+ *               5 / 6 of boxHitSign<true>; 7 boxMaybeHit; 8 boxHit (the reference's divisions); 9 boxHitLoose; 10 boxHitOrGate with
+ *               gate = true: the box judged as an inner node of the path-pool kernel's regrouped tree (closed, and no bound on t,
+ *               on an axis with d = +-0);
  *   float 6     tEnter of boxMaybeHit;  float 7  tEnter of boxHitLoose.
  * Refuses n outside [1, 2^20] and null pointers. */
 int srtTestRefinedRcp(SrtContext* ctx, int64_t firstBits, int64_t count, uint64_t* out2);

@@ -71,8 +71,10 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_slabtest_visit_kernel(const flo
   const bool maybe = boxMaybeHit(n0, n1, rcp, m, tolAbs, tMin, tMax, tEnter);
   const bool exact = boxHit(n0, n1, r, tMin, tMax);
   const bool loose = boxHitLoose(n0, n1, r, tMin, tMax, tEnterLoose);
+  const bool gate = boxHitOrGate(n0, n1, r, tMin, tMax, true);  // the case's box as an inner node of the regrouped tree
   const uint32_t flags = (uint32_t)certified | (uint32_t)vLane << 1 | (uint32_t)uLane << 2 | (uint32_t)vUniform << 3 | (uint32_t)uUniform << 4 |
-                         (uint32_t)vSign << 5 | (uint32_t)uSign << 6 | (uint32_t)maybe << 7 | (uint32_t)exact << 8 | (uint32_t)loose << 9;
+                         (uint32_t)vSign << 5 | (uint32_t)uSign << 6 | (uint32_t)maybe << 7 | (uint32_t)exact << 8 | (uint32_t)loose << 9 |
+                         (uint32_t)gate << 10;
   float* o = out + 8 * (size_t)i;
   o[0] = rcp.x;
   o[1] = rcp.y;

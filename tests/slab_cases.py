@@ -45,6 +45,42 @@ def reference(cases, t_min):
         return ~(t1 <= t0), t0, t1
 
 
+def gate(cases, t_min):
+    """The gate form of the exact test, from DESIGN 6.1 (not from the kernel): the verdict on a box taken as an inner node of
+    the regrouped tree.  On an axis with d == +-0 it passes iff min <= o <= max -- closed, and written so that a NaN origin
+    passes as it does in the reference -- and puts no bound on t; on every other axis it is the reference's arithmetic."""
+    lo, hi, o, d = cases[:, 0:3], cases[:, 3:6], cases[:, 6:9], cases[:, 9:12]
+    t0 = np.full(len(cases), t_min, F)
+    t1 = cases[:, 12].copy()
+    inside = np.ones(len(cases), bool)
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            zero = d[:, k] == 0
+            a = (lo[:, k] - o[:, k]) / d[:, k]
+            b = (hi[:, k] - o[:, k]) / d[:, k]
+            assert a.dtype == F and b.dtype == F
+            t0 = np.where(zero, t0, np.fmax(np.fmin(a, b), t0))
+            t1 = np.where(zero, t1, np.fmin(np.fmax(a, b), t1))
+            inside &= ~zero | (~(o[:, k] < lo[:, k]) & ~(o[:, k] > hi[:, k]))
+        return inside & ~(t1 <= t0)
+
+
+GATE_T_MIN = 0.001
+
+
+def gate_grid():
+    """The nested pairs of tests/test_regroup_host.py (_gate_cases over _axis_cases: shared planes, flat and point boxes, d of
+    +-0, +-2^-20, +-1, +-inf and NaN, origins on planes, off planes and NaN, tMax of +inf and 1.5) as cases of this module:
+    (inner, outer), row i of both the same ray at tMin = GATE_T_MIN, the inner box inside the outer one."""
+    from test_regroup_host import _gate_cases
+    g = _gate_cases()
+    assert (g[:, 18] == F(GATE_T_MIN)).all()
+    assert (g[:, 6:9] <= g[:, 0:3]).all() and (g[:, 0:3] <= g[:, 3:6]).all() and (g[:, 3:6] <= g[:, 9:12]).all()
+    inner = np.concatenate([g[:, 0:6], g[:, 12:18], g[:, 19:20]], axis=1).astype(F)
+    outer = np.concatenate([g[:, 6:12], g[:, 12:18], g[:, 19:20]], axis=1).astype(F)
+    return inner, outer
+
+
 def ulps(x, k):
     """x moved by k float32 steps (k an int array, |k| <= 4)."""
     x = np.array(x, F)

@@ -9,7 +9,11 @@ of the path-pool kernel walks other inner nodes over the reference's leaves, and
   * counters: a counting launch's eight counters with wf_regroup 1 are those with 0 (the counting instances walk the
     reference tree) and, on the libm-free version of the mesh scene, the oracle's;
   * refit: after srtUpdateTriangles + srtUpdateSpheres + srtRefitScene the regrouped array holds the reference leaves' new
-    boxes under unions of them, and the frame is the wf_regroup 0 frame."""
+    boxes under unions of them, and the frame is the wf_regroup 0 frame.
+
+No ray of these frames has a direction component of exactly +-0 (the quad room's quads are axis-aligned, its rays are not), so
+none reaches the gate form of the exact test: tests/test_gpu_planar_frames.py renders frames made of such rays alone and
+pins the regrouped walk's node visits to a replay of the closed gate."""
 import numpy as np
 import pytest
 

@@ -11,7 +11,12 @@
   * walks on rays aimed at the tree's own boxes -- corners, edge midpoints, rays lying in face planes -- in a small scene of
     spheres and axis-aligned triangles: srtTraceRays FAITHFUL equals the oracle's walk in hit and in all four counters,
     and the device queries equal the oracle as in tests/test_gpu_query.py (CLOSEST and occlusion: the brute force), over the
-    reference tree and a device-built one."""
+    reference tree and a device-built one.
+  * the GATE form of the exact test (bit 10: boxHitOrGate with gate = true, what the path-pool kernel calls on an inner node of
+    its regrouped tree) on the classes above and on the nested pairs of tests/test_regroup_host.py -- d of +-0,
+    +-2^-20, +-inf and NaN, origins on planes, off planes and NaN: it is a NumPy float32 statement of the gate written from
+    the design text, it is the host compile's, and boxHit passing on the inner box of a pair implies the gate passing on the
+    outer one."""
 import os
 import subprocess
 
@@ -105,6 +110,7 @@ def test_device_compile_pair_by_pair(ctx, probe, tmp_path, name):
         certified = slab_cases.certified(cases)
         # the reference's divisions on the device, on every case
         assert np.array_equal(bit(8), entered), what
+        assert np.array_equal(bit(10), slab_cases.gate(cases, t_min)), what  # ... and the gate form's closed interval
         assert np.array_equal(bit(0), certified), what
         assert certified.all() if name != "uncertified" else not certified.any()
         # a decided verdict is the reference's; the three certified forms agree
@@ -127,6 +133,7 @@ def test_device_compile_pair_by_pair(ctx, probe, tmp_path, name):
         # the host compile of the same header on the same cases and the device's reciprocals
         host = replay_cases(probe, tmp_path, cases, out[:, 0:3], t_min)
         assert np.array_equal(host[:, 5].view(np.int32) & 0x1ff, flags & 0x1ff), what
+        assert np.array_equal(host[:, 5].view(np.int32) >> 10 & 1, flags >> 10 & 1), what
         assert _same_values(host[:, 3], out[:, 3]) and _same_values(host[:, 4], out[:, 4]) and _same_values(out[:, 3], out[:, 4]), what
         assert _same_values(host[certified, 6], out[certified, 6]), what  # (a NaN end, uncertified rays only: v_max keeps the number)
         assert np.isinf(out[~certified, 3]).all(), what
@@ -136,6 +143,7 @@ def test_device_compile_pair_by_pair(ctx, probe, tmp_path, name):
         assert not (foff & 1).any() and (foff >> 2 & 1).all() and (foff >> 4 & 1).all() and (foff >> 6 & 1).all(), what
         assert not (foff & 0b101010).any() and (foff >> 7 & 1).all() and np.isinf(off[:, 3]).all(), what
         assert np.array_equal(foff >> 8 & 3, flags >> 8 & 3) and _same_values(off[:, 0:3], out[:, 0:3]), what
+        assert np.array_equal(foff >> 10, flags >> 10), what
         undecided = bit(2).mean()
         print(name, t_min, "entered %.3f undecided %.3f" % (entered.mean(), undecided))
         if name in ("aimed", "touch"):
@@ -144,6 +152,30 @@ def test_device_compile_pair_by_pair(ctx, probe, tmp_path, name):
             assert undecided <= 0.01, what
         if name not in ("flat", "uncertified"):
             assert 0.1 <= entered.mean() <= 0.9, what
+
+
+def test_gate_form_on_the_nested_grid(ctx, probe, tmp_path):
+    """slab_cases.gate_grid(): some 2.3 * 10^5 nested pairs of boxes, each box one case of srtTestSlabVisit.  tests/test_slab_host.py
+    makes the same comparisons on the host compile alone and shows that the grid reaches both verdicts on the zero axes."""
+    inner, outer = slab_cases.gate_grid()
+    t = slab_cases.GATE_T_MIN
+    got = {}
+    for name, cases in (("inner", inner), ("outer", outer)):
+        out = ctx.slab_visit_test(cases, t)
+        flags = out[:, 5].view(np.int32)
+        assert not (flags >> 11).any(), name
+        exact, gate = (flags >> 8 & 1).astype(bool), (flags >> 10 & 1).astype(bool)
+        assert np.array_equal(exact, slab_cases.reference(cases, t)[0]), name
+        assert np.array_equal(gate, slab_cases.gate(cases, t)), name
+        host = replay_cases(probe, tmp_path, cases, out[:, 0:3], t)[:, 5].view(np.int32)
+        assert np.array_equal(host >> 10 & 1, flags >> 10 & 1) and np.array_equal(host & 0x1ff, flags & 0x1ff), name
+        assert not (exact & ~gate).any(), name  # the gate never passes less than the reference's test on the same box
+        assert not (flags & 1)[(cases[:, 9:12] == 0).any(axis=1)].any(), name  # a ray with a zero component is never certified
+        got[name] = (exact, gate)
+    bad = np.flatnonzero(got["inner"][0] & ~got["outer"][1])
+    assert len(bad) == 0, (inner[bad[:3]], outer[bad[:3]])
+    assert got["inner"][0].sum() > 10000 and (~got["outer"][1]).sum() > 10000
+    assert (got["inner"][0] & ~got["outer"][0]).any()  # boxHit itself on the outer box does NOT have the property
 
 
 def test_slab_visit_hook_refuses(ctx, dev):

@@ -10,7 +10,10 @@ reference's, the conservative form never rejects a box whose reference interval 
 error of the clamped ends stays inside the proven bound (at most 1 x the verdict's tolerance; 0.71 observed) -- in every class
 the reference both enters and misses at least a tenth of the boxes, except the flat class (never entered: a zero-thickness slab
 gives tMax <= tMin) and the uncertified one.  The same program under the address and undefined-behaviour sanitizers, and its
-replay mode on a handful of cases."""
+replay mode on a handful of cases.
+
+The replay mode's bit 10 is the GATE form of the exact test (srtSlabExactOrGate, gate = true): against the NumPy
+statement slab_cases.gate on every class and on the nested pairs of tests/test_regroup_host.py."""
 import os
 import subprocess
 
@@ -173,6 +176,7 @@ def test_numpy_cases_and_reference_agree_with_the_probe(probe, tmp_path, name):
         flags = out[:, 5].view(np.int32)
         entered, t0, t1 = slab_cases.reference(cases, t_min)
         assert np.array_equal(flags >> 8 & 1, entered.astype(np.int32)), (name, t_min)
+        assert np.array_equal(flags >> 10 & 1, slab_cases.gate(cases, t_min).astype(np.int32)), (name, t_min)  # the gate form on the same box
         assert np.array_equal(flags & 1, slab_cases.certified(cases).astype(np.int32)), (name, t_min)
         assert (flags & 1).all() == (name != "uncertified") and (flags & 1).any() == (name != "uncertified")
         decided = (flags >> 2 & 1) == 0
@@ -185,6 +189,32 @@ def test_numpy_cases_and_reference_agree_with_the_probe(probe, tmp_path, name):
             assert share == 0
         elif name != "uncertified":
             assert 0.1 <= share <= 0.9, (name, t_min, share)
+
+
+def test_gate_bit_on_the_nested_grid(probe, tmp_path):
+    """Bit 10 of the replay mode -- srtSlabExactOrGate with gate = true, the host compile of what the path-pool kernel calls on
+    an inner node of the regrouped tree -- on slab_cases.gate_grid(): it is the NumPy statement of DESIGN 6.1 on every box, it
+    never passes less than the reference's own test on the same box, and the reference passing on the inner box of a nested
+    pair implies the gate passing on the outer one.  The grid reaches what it is for: zero axes on which the closed interval
+    decides either way, and boxes the gate passes while the reference misses them."""
+    inner, outer = slab_cases.gate_grid()
+    with np.errstate(all="ignore"):
+        rcp = np.float32(1) / inner[:, 9:12]
+    t = slab_cases.GATE_T_MIN
+    bits = {}
+    for name, cases in (("inner", inner), ("outer", outer)):
+        flags = replay_cases(probe, tmp_path, cases, rcp, t)[:, 5].view(np.int32)
+        bits[name] = ((flags >> 8 & 1).astype(bool), (flags >> 10 & 1).astype(bool))
+        assert np.array_equal(bits[name][0], slab_cases.reference(cases, t)[0]), name
+        assert np.array_equal(bits[name][1], slab_cases.gate(cases, t)), name
+        assert not (bits[name][0] & ~bits[name][1]).any(), name
+        assert not (flags >> 9 & 1).any()
+    assert not (bits["inner"][0] & ~bits["outer"][1]).any()
+    assert bits["inner"][0].sum() > 10000 and (~bits["outer"][1]).sum() > 10000
+    assert (bits["inner"][0] & ~bits["outer"][0]).any()  # the plain reference test on the outer box does not have the property
+    zero = (outer[:, 9:12] == 0).any(axis=1)
+    assert (zero & bits["outer"][1]).sum() > 1000 and (zero & ~bits["outer"][1]).sum() > 1000
+    assert (bits["outer"][1] & ~bits["outer"][0]).sum() > 1000
 
 
 def test_probe_under_sanitizers(tmp_path):
