@@ -12,25 +12,8 @@
 
 #include "srt_buffer.h"
 #include "srt_device.h"
+#include "srt_plan.h"  // Tunables, the planner
 #include "srt_scene.h"
-
-// Diagnostic tunables of the work distribution and the wave scheduler.  Environment variables give the
-// defaults ONCE, at srtCreate; srtSetTunable (include/srt_hip_test.h) changes them per context.  -1 = the
-// library's own rule.
-struct Tunables {
-  int tileBlock, unitTiles, queues;
-  int shadeMin, primMin, hitMin, fuseMin, nodeBurst;
-  int plocRadius, fastDiv;
-  int chunkScratchMb;
-  int primAgainMin;
-  int keepEighths;
-  int ldsTree;
-  int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
-  int wfHybrid, wfResidentMax, wfFarRounds;
-  int wfRegroup;
-  int denoiseLdsStep;
-  int triCert;
-};
 
 // What belongs to the uploaded scene and is invalid for the next one.  srtUploadScene starts by assigning a fresh Upload,
 // which also frees the previous scene's device memory; a member added here can therefore not survive into the next scene.

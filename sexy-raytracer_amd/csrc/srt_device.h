@@ -188,12 +188,21 @@ struct RenderArgs {
   int32_t* wfError;
 };
 
-// One render launch, decided by srt_render.cpp renderPlan.  form: srtGetLaunchInfo's codes -- 0 srt_render_kernel over node
-// records read through the L1, 1 / 2 srt_render_kernel over the LDS-resident tree with the attenuation stacks in global
-// memory / in LDS, 3 srt_render_wf_kernel over the LDS-resident tree, 4 its hybrid form.  closest, single, count and
-// profile are the template arguments of the instance that runs (srt_launch.h srt_render_kernel_for, srt_render_wf_kernel_for).
+// The form of the render kernel.  The values are srtGetLaunchInfo's codes (launch_info()["lds_tree_mode"]): they stay.
+enum SrtRenderForm : int32_t {
+  SRT_FORM_STACK = 0,             // srt_render_kernel over node records read through the L1, per-lane stacks in LDS
+  SRT_FORM_LDS_TREE = 1,          // srt_render_kernel over the LDS-resident tree, attenuation stacks in global memory
+  SRT_FORM_LDS_TREE_ATT = 2,      // ... attenuation stacks in LDS behind the tree
+  SRT_FORM_PATH_POOL = 3,         // srt_render_wf_kernel over the LDS-resident tree
+  SRT_FORM_PATH_POOL_HYBRID = 4,  // ... its hybrid form: the tree's top in LDS
+};
+inline bool srtFormIsPathPool(SrtRenderForm f) { return f == SRT_FORM_PATH_POOL || f == SRT_FORM_PATH_POOL_HYBRID; }
+inline bool srtFormIsLdsTree(SrtRenderForm f) { return f == SRT_FORM_LDS_TREE || f == SRT_FORM_LDS_TREE_ATT; }
+
+// One render launch, decided by srt_plan.cpp planRender.  closest, single, count and profile are the template arguments of
+// the instance that runs (srt_launch.h srt_render_kernel_for, srt_render_wf_kernel_for).
 struct RenderPlan {
-  int32_t form;
+  SrtRenderForm form;
   bool closest, single, count, profile;
   bool moments;   // srtRenderTilesMoments: the MOMENTS instance of the same form (never counting or profiling)
   int32_t block;  // threads per workgroup

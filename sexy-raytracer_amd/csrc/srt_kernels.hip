@@ -35,6 +35,7 @@
 
 #include "srt_path.h"
 #include "srt_launch.h"
+#include "srt_lds_layout.h"
 
 
 // =================================================================== render
@@ -84,6 +85,8 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
   constexpr int32_t DONE = LDSTREE ? (int32_t)0xFFFF8000 : SRT_REF_DONE;
   typedef typename std::conditional<LDSTREE, int16_t, int32_t>::type StackT;
   extern __shared__ int32_t lds[];
+  // (the carve-up below must match srt_lds_layout.h: srtStackFormLayout, and srtLdsTreeLayout for LDSTREE -- the host sizes
+  // the launch by them)
   // per-thread LDS slots, [slot][thread]: stackDepth+2 traversal slots (slot 0 holds a sentinel, the last
   // one is a spare for the node step's unconditional store), then 3*maxBounce attenuation floats and 3
   // floats of terminal radiance.  LDSTREE: node records first, then the (16-bit) traversal slots.
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(LDSTREE ? SRT_BLOCK_TREE : SRT_BLOCK, LDSTREE ? SRT
   constexpr bool attInLds = !LDSTREE || ATTLDS;
   float* attStack = !attInLds ? a.attScratch + (size_t)blockIdx.x * BLOCK + threadIdx.x
                     : !LDSTREE ? reinterpret_cast<float*>(lds + stackSlots * BLOCK + threadIdx.x)
-                               : reinterpret_cast<float*>(ldsTree + treeBytes + 64) + threadIdx.x;
+                               : reinterpret_cast<float*>(ldsTree + treeBytes + SRT_LDS_TREE_QUEUE_WORDS * 4) + threadIdx.x;
   const int attStride = attInLds ? BLOCK : (int)gridDim.x * BLOCK;
   const int attSlots = attInLds ? 3 * a.maxBounce + 3 : 0;  // LDS slots per thread behind the traversal stack
   const int lane = threadIdx.x & 63;
@@ -779,6 +782,7 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_trace_kernel(const TraceArgs a)
     float tHit;
     int ref = traverse<CLOSEST, true, !CLOSEST>(a.scene, r, in.tMin, in.tMax, stack, tHit, cnt);
     if (cnt.triUndecided) atomicAdd(a.triUndecided, (unsigned long long)cnt.triUndecided);
+    // (the SrtHit fill is written out here and in srt_query.hip: as one inlined function it changed the code of both kernels)
     SrtHit h;
     h.prim = SRT_NO_HIT;
     h.t = 0;
@@ -858,20 +862,20 @@ __global__ void srt_scatter_kernel(const ScatterArgs a) {
 // =================================================================== launch wrappers (host)
 extern "C" {
 
-// the srt_render_kernel instance a plan of form 0-2 names (srt_render.cpp renderPlan)
+// the srt_render_kernel instance a plan of form 0-2 names (srt_plan.cpp planRender)
 RenderKernel srt_render_kernel_for(const RenderPlan* p) {
   if (p->moments) {  // (never counting: srtRenderTilesMoments refuses countStats)
-    if (p->form == 2)
+    if (p->form == SRT_FORM_LDS_TREE_ATT)
       return p->single ? srt_render_kernel<false, false, true, true, true, true> : srt_render_kernel<false, false, false, true, true, true>;
-    if (p->form == 1)
+    if (p->form == SRT_FORM_LDS_TREE)
       return p->single ? srt_render_kernel<false, false, true, true, false, true> : srt_render_kernel<false, false, false, true, false, true>;
     if (p->single) return p->closest ? srt_render_kernel<true, false, true, false, false, true> : srt_render_kernel<false, false, true, false, false, true>;
     return p->closest ? srt_render_kernel<true, false, false, false, false, true> : srt_render_kernel<false, false, false, false, false, true>;
   }
-  if (p->form == 2)
+  if (p->form == SRT_FORM_LDS_TREE_ATT)
     return p->count ? srt_render_kernel<false, true, false, true, true>
                     : p->single ? srt_render_kernel<false, false, true, true, true> : srt_render_kernel<false, false, false, true, true>;
-  if (p->form == 1)
+  if (p->form == SRT_FORM_LDS_TREE)
     return p->count ? srt_render_kernel<false, true, false, true, false>
                     : p->single ? srt_render_kernel<false, false, true, true, false> : srt_render_kernel<false, false, false, true, false>;
   if (p->count) return p->closest ? srt_render_kernel<true, true, false, false, false> : srt_render_kernel<false, true, false, false, false>;

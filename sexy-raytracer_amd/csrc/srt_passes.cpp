@@ -10,6 +10,7 @@
 
 #include "srt_context.h"
 #include "srt_launch.h"
+#include "srt_lds_layout.h"
 
 /* Feature pass (srt_features.hip).  Reads the scene, the camera and the tile_block tunable; writes only the caller's planes
  * and its own tile counter, so a later render sees the context as it was. */
@@ -37,10 +38,10 @@ static int launchFeaturePass(SrtContext* ctx, const SrtRenderParams* p, FeatureA
   // FAITHFUL over a threaded tree that fits a CU's LDS: the stackless walk out of LDS; otherwise the stack walk over
   // scene.nodes (stacks in LDS), which CLOSEST always takes
   const bool closest = p->traversal == SRT_TRAVERSE_CLOSEST;
-  const size_t treeBytes = (size_t)sc.numNodes * 32;
-  const bool ldsTree = !closest && sc.nodeThread != nullptr && treeBytes <= 160 * 1024;
-  const size_t lds = ldsTree ? treeBytes : (size_t)std::max(sc.stackDepth, 1) * SRT_BLOCK * sizeof(int32_t);
-  if (lds > 160 * 1024) return fail(ctx, "features: BVH depth %d needs %zu B of LDS per workgroup", sc.stackDepth, lds);
+  const size_t treeBytes = srtFeatureTreeBytes(sc.numNodes);
+  const bool ldsTree = !closest && sc.nodeThread != nullptr && treeBytes <= SRT_LDS_BYTES;
+  const size_t lds = ldsTree ? treeBytes : srtTraverseStackBytes(sc.stackDepth);
+  if (lds > SRT_LDS_BYTES) return fail(ctx, "features: BVH depth %d needs %zu B of LDS per workgroup", sc.stackDepth, lds);
   int block = 0, perCU = 1;
   int rc = plan(closest, ldsTree, lds, &block, &perCU);
   if (rc) return fail(ctx, "features: kernel setup failed: %s", hipGetErrorString((hipError_t)rc));

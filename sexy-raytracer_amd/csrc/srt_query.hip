@@ -59,6 +59,7 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_query_kernel(const QueryArgs a)
 
     if (MODE != Q_ANY) {
       int4 h4 = make_int4(SRT_NO_HIT, 0, -1, 0);
+      // (srt_trace_kernel's fill, written out: as one inlined function it changed the code of both kernels)
       SrtHit h;
       h.prim = SRT_NO_HIT;
       h.t = 0;

@@ -1,6 +1,6 @@
-// srt_render.cpp -- the render launches of the C ABI (include/srt_hip.h): tile counts and chunk plans, the choice of the
-// render kernel (renderPlan) and its launch over the rank's tiles or a tile list, the moments instance, the resolve, the
-// ray-level test entries, and the rounds of tile-adaptive sampling.
+// srt_render.cpp -- the render launches of the C ABI (include/srt_hip.h): the launch srt_plan.cpp plans, over the rank's
+// tiles or a tile list, the moments instance, the resolve, the ray-level test entries, and the rounds of tile-adaptive
+// sampling.
 
 #include <hip/hip_runtime.h>
 
@@ -10,66 +10,7 @@
 
 #include "srt_context.h"
 #include "srt_launch.h"
-
-namespace {
-
-size_t ldsBytesFor(const SrtContext* ctx, int maxBounce, int stackDepth) {
-  // per-thread stacks plus one word of queue state per wave (srt_render_kernel)
-  return (size_t)(stackDepth + 2 + 3 * maxBounce + 3) * SRT_BLOCK * sizeof(int32_t) + 4 * sizeof(int32_t);
-}
-
-// RenderArgs::fixLimit of a render of `chunks` chunks (srt_path.h toFixed36): exact chunk sums cannot wrap, partial sums of
-// 2^26 / (chunk count rounded up to a power of two) or more count as infinite.  The render and srtTestChunkSum both ask here.
-float chunkFixLimit(int32_t chunks) {
-  int pow2 = 1;
-  while (pow2 < chunks) pow2 *= 2;
-  return 0x1p26f / (float)pow2;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t srtNumTiles(int32_t w, int32_t h) {
-  return ((w + SRT_TILE_W - 1) / SRT_TILE_W) * ((h + SRT_TILE_H - 1) / SRT_TILE_H);
-}
-int32_t srtNumLocalTiles(int32_t w, int32_t h, int32_t stride) {
-  if (stride < 1) stride = 1;
-  return (srtNumTiles(w, h) + stride - 1) / stride;
-}
-
-// Work items per pixel when the caller leaves the choice to the library (sppChunks == 0): about 8 samples per
-// item, at least 128 items per pixel when there are that many samples (down to one sample per item), at most 640.
-// It depends on the sample count alone, so that the chunk boundaries -- and with them the image, bit for bit --
-// are the same for every tile split and GPU count.  Many items per pixel keep the tiles in flight few (a queue's
-// waves pull consecutive items, i.e. the chunks of one tile, then of its neighbour), and SMALL items keep the end
-// of a launch short: the last items to finish are single pixels of the mesh, ten times the average pixel's cost,
-// and a rank's share of a frame feels that tail most.  720p headline at 5000 spp on the LDS-resident-tree kernel
-// (profiles/r02/chunk_policy.txt): whole frame 1069.9 / 1067.9 / 1066.7 / 1068.1 ms with 157 / 314 / 628 / 1250
-// chunks (as long as the chunk slots fit the scratch budget; the atomic path costs 1.2 %); one of 8 ranks' share
-// 148.5 / 142.5 / 139.5 / 138.3 ms (133.7 would be an eighth of the frame).  Low sample counts: 64 spp on the 240p
-// spheres frame run at 4.3 / 5.2 / 6.2 / 7.1 / 7.8 Gsamples/s with 4 / 8 / 16 / 32 / 64 chunks.
-int32_t srtDefaultSppChunks(int32_t spp) {
-  const int32_t bySize = (spp + 7) / 8, byCount = std::min(128, spp);
-  return std::max(1, std::min(640, std::max(bySize, byCount)));
-}
-
-// The chunk count a render of this size will use: `sppChunks` when the caller gives one, else srtDefaultSppChunks(spp),
-// and -1 when an explicit count does not fit.  Work items and chunk slots are indexed with 32-bit integers in the
-// kernels: the slots of one chunk over the WHOLE image (not a rank's share: the plan, and with it the image bit for
-// bit, must not depend on the tile split), plus the padding a work queue's last unit can add (a unit is at most 1024
-// tiles; every queue counts its own items).  1280 x 720 allows 2166 chunks, 1920 x 1080 1003: the default plan
-// (at most 640) always fits images below about 3 Mpixels; beyond that the default is clamped.
-int32_t srtPlanSppChunks(int32_t imageWidth, int32_t imageHeight, int32_t spp, int32_t sppChunks) {
-  if (imageWidth < 1 || imageHeight < 1 || spp < 1 || sppChunks < 0 || sppChunks > spp) return -1;
-  const int64_t perChunk = ((int64_t)srtNumTiles(imageWidth, imageHeight) + 1024 + 64) * SRT_TILE_PIXELS;
-  const int64_t maxChunks = (int64_t)0x7fffffff / perChunk;
-  if (maxChunks < 1) return -1;
-  if (sppChunks > 0) return sppChunks <= maxChunks ? sppChunks : -1;
-  return (int32_t)std::min<int64_t>(srtDefaultSppChunks(spp), maxChunks);
-}
-
-}  // extern "C"
+#include "srt_lds_layout.h"
 
 int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
   if (checkSceneReady(ctx, "render")) return 1;
@@ -84,69 +25,56 @@ int checkParams(SrtContext* ctx, const SrtRenderParams* p) {
   return 0;
 }
 
-// The render launch for these parameters: the kernel form and the instance of it, workgroup and LDS size, the path-pool
-// kernel's rings.  Every choice of kernel is made here; srtRenderTilesImpl allocates and launches what it says.
-// moments: srtRenderTilesMoments -- the same form, grid, block and LDS, its MOMENTS instance (never counting or profiling).
-// listTiles >= 0: a launch over a tile list of that length (srtRenderAdaptive) instead of the rank's share of the image.
-static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bool moments = false, int32_t listTiles = -1) {
-  const DevScene& sc = ctx->upload.scene;
-  const Tunables& tun = ctx->tun;
-  RenderPlan plan{};
-  const bool faithful = p->traversal == SRT_TRAVERSE_FAITHFUL;
-  plan.closest = p->traversal == SRT_TRAVERSE_CLOSEST;
-  plan.count = p->countStats != 0;
-  plan.moments = moments;
-  // FAITHFUL on a scene whose whole node array fits into a CU's LDS: the LDS-resident-tree kernel (srt_render_kernel
-  // LDSTREE), one workgroup of 1024 threads per CU, walking the threaded copy of the tree (no per-lane stack).
-  const size_t ldsTreeBytes = (size_t)sc.numNodes * 32 + 16 * sizeof(int32_t);  // threaded tree: no stacks
-  // (Even trees of a few dozen nodes gain: their frames are shading-bound, and the 128-register kernel keeps a hit's
-  // texel loads in flight together where the 96-register one spills, profiles/r02/lds_tree.txt.)
-  const bool ldsTree = faithful && tun.ldsTree > 0 && sc.numNodes >= tun.ldsTree && ldsTreeBytes <= 160 * 1024 &&
-                       sc.nodeThread != nullptr;  // thread links exist: host-built trees, 15-bit references (srtUploadScene)
-  // ... and when the attenuation stacks fit behind them as well they stay in LDS (form 2): +2 to +5 % on the small
-  // BASELINE scenes; the headline scene's tree leaves no room (form 1: they live in global memory)
-  const size_t attBytes = (size_t)(3 * p->maxBounce + 3) * SRT_BLOCK_TREE * sizeof(float);
-  // The path-pool kernel (srt_wavefront.hip) serves what the LDS-resident tree serves, when its rings fit behind the
-  // tree: one 1024-thread workgroup per CU, wfPool contexts each.  A counting launch runs the counting instance of the
-  // kernel the same launch without counting runs: the counters belong to the kernel under test.
-  // LDS behind the tree: 64 control words, six rings of 16-bit slots, and per context the (t, primitive) its walk ended at:
-  // 18 bytes per context.  Ring capacity = pool size = the largest of 1024, 1536, 2048, 3072, 4096 that fits and does not
-  // exceed the tunable (the headline scene's 129 KB tree leaves room for 1536).
-  // Hybrid form: the tree's top in LDS, the rest read from global memory (scene.nodesWf, built at upload when the tree does
-  // not fit or the tunable wf_resident_max asks for it).
-  const bool hybrid = faithful && sc.nodesWf != nullptr && tun.wavefront > 0 && sc.primClass != nullptr;
-  const size_t wfFixed = (size_t)(hybrid ? sc.wfResident : sc.numNodes) * 32 + 64 * sizeof(int32_t);
-  const size_t wfPerContext = hybrid ? 20 : 18;  // six ring slots of 16 bits, t, the primitive (16 bits; 32 in the hybrid form)
-  // ring counters are 32-bit and a 3 * 2^j ring cannot take their wrap-around: such rings only while a workgroup's
-  // enqueues stay far below 2^32 (about three per sample)
-  const int numLocalTiles = listTiles >= 0 ? listTiles : srtNumLocalTiles(p->imageWidth, p->imageHeight, p->tileStride);
-  const double enqueuesPerGroup = 4.0 * (double)numLocalTiles * SRT_TILE_PIXELS * (double)p->spp / std::max(1, ctx->prop.multiProcessorCount);
-  static const struct { int cap, shift, mul3; } kRings[] = {{4096, 12, 0}, {3072, 10, 1}, {2048, 11, 0}, {1536, 9, 1}, {1024, 10, 0}};
-  for (const auto& r : kRings) {
-    if (r.cap > std::max(1024, tun.wfPool) || wfFixed + wfPerContext * r.cap > 160 * 1024) continue;
-    if (r.mul3 && enqueuesPerGroup > 2.0e9) continue;
-    plan.wfRingCap = r.cap;
-    plan.wfRingShift = r.shift;
-    plan.wfRingMul3 = r.mul3;
-    break;
+// The tile order as a device table (once per image size): the kernel's restart step looks a tile up instead of dividing
+static int tileTableFor(SrtContext* ctx, const SrtRenderParams* p, const RenderArgs& a) {
+  if (ctx->tileTableKey[0] == p->imageWidth && ctx->tileTableKey[1] == p->imageHeight && ctx->tileTableKey[2] == a.tileBlock && ctx->tileTable.get()) return 0;
+  std::vector<uint32_t> table((size_t)a.numTiles);
+  for (int32_t i = 0; i < a.numTiles; ++i) {
+    int tx, ty;
+    srtTileFromOrder(i, a.tilesX, a.tilesY, a.tileBlock, tx, ty);
+    table[i] = (uint32_t)tx | (uint32_t)ty << 16;
   }
-  const bool wavefront = plan.wfRingCap > 0 && (hybrid || (ldsTree && tun.wavefront > 0 && sc.numNodes >= tun.wavefront && sc.primClass != nullptr));
-  if (wavefront) {
-    plan.form = hybrid ? 4 : 3;
-    plan.block = SRT_BLOCK_TREE;
-    plan.lds = wfFixed + wfPerContext * plan.wfRingCap;
-    plan.profile = !plan.count && !plan.moments && tun.wfProfile > 0;  // a counting or moments launch takes no profile
-    // (hybrid form: the single-root instance is worth +12 to +15 % on cache-resident trees and costs 5 % on the HBM-bound
-    // soups of 4 M triangles and more, where the shorter visit only crowds the memory system: profiles/r03/hybrid.txt)
-    plan.single = !plan.profile && sc.numWorld == 1 && (!hybrid || sc.numNodes <= (1 << 20));
-    return plan;
+  ctx->tileTable = DeviceBuffer();  // freed first (as a size change always did), then allocated for this size
+  HIP_OK(ctx, ctx->tileTable.reserve(std::max<size_t>(table.size() * 4, 16)));
+  HIP_OK(ctx, hipMemcpy(ctx->tileTable.get(), table.data(), table.size() * 4, hipMemcpyHostToDevice));
+  ctx->tileTableKey[0] = p->imageWidth;
+  ctx->tileTableKey[1] = p->imageHeight;
+  ctx->tileTableKey[2] = a.tileBlock;
+  return 0;
+}
+
+// Where a launch of more than one chunk leaves its partial sums: a.out / a.chunkStride (scratch path, returns scratchPath =
+// true) or a.fix (atomic path), and with `moments` a.mout / a.mfix behind them.
+// Chunk sums are added exactly (srt_kernels.hip "Chunk sums").  Scratch path (a float4 slot per item, summed by
+// srt_sum_chunks_kernel) while this rank's slots fit the budget, else the atomic path (32 B per pixel, 0.4-1 %
+// slower); the two give the same bits, so the choice may differ from rank to rank.
+static int chunkSumBuffers(SrtContext* ctx, RenderArgs& a, bool moments, size_t tilePixels, hipStream_t stream, bool& scratchPath) {
+  // a moments launch sums its moments plane exactly as the beauty, on the same path: twice the slots or accumulators,
+  // the beauty's first, the moments' behind them
+  const size_t planes = moments ? 2 : 1;
+  const size_t localSlots = planes * tilePixels * a.sppChunks * sizeof(float4);
+  // budget: the tunable, and never more than a quarter of what the device has free right now (a smaller, shared or
+  // partitioned GPU takes the atomic path -- same bits -- instead of failing)
+  size_t budget = (size_t)std::max(0, ctx->tun.chunkScratchMb) * 1024 * 1024, freeB = 0, totalB = 0;
+  if (ctx->chunkScratch.bytes() < localSlots && hipMemGetInfo(&freeB, &totalB) == hipSuccess) budget = std::min(budget, (freeB + ctx->chunkScratch.bytes()) / 4);
+  scratchPath = localSlots <= budget;
+  const size_t need = scratchPath ? localSlots : planes * tilePixels * sizeof(SrtFixedAccum);
+  if (ctx->chunkScratch.reserve(need) != hipSuccess) {
+    (void)hipGetLastError();
+    if (!scratchPath) return fail(ctx, "render: cannot allocate %zu B for the pixel sums", need);
+    scratchPath = false;  // the slots do not fit after all: 32 B per pixel on the atomic path
+    HIP_OK(ctx, ctx->chunkScratch.reserve(planes * tilePixels * sizeof(SrtFixedAccum)));
   }
-  plan.wfRingCap = plan.wfRingShift = plan.wfRingMul3 = 0;
-  plan.form = !ldsTree ? 0 : ldsTreeBytes + attBytes <= 160 * 1024 ? 2 : 1;
-  plan.block = ldsTree ? SRT_BLOCK_TREE : SRT_BLOCK;
-  plan.lds = plan.form == 2 ? ldsTreeBytes + attBytes : ldsTree ? ldsTreeBytes : ldsBytesFor(ctx, p->maxBounce, sc.stackDepth);
-  plan.single = !plan.count && sc.numWorld == 1;  // (the counting instances serve single-root worlds as well)
-  return plan;
+  if (scratchPath) {
+    a.out = ctx->chunkScratch.get<float4>();
+    a.chunkStride = (int32_t)tilePixels;
+    if (moments) a.mout = a.out + tilePixels * a.sppChunks;
+  } else {
+    a.fix = ctx->chunkScratch.get<SrtFixedAccum>();
+    if (moments) a.mfix = a.fix + tilePixels;
+    HIP_OK(ctx, hipMemsetAsync(a.fix, 0, planes * tilePixels * sizeof(SrtFixedAccum), stream));
+  }
+  return 0;
 }
 
 // aov: srtRenderAov's per-pixel records of the ray at bounce aovDepth (counting launches only), else null.
@@ -157,154 +85,65 @@ static RenderPlan renderPlan(const SrtContext* ctx, const SrtRenderParams* p, bo
 // whose tile table is the list.
 int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTiles, void* streamPtr, SrtAovRecord* aov,
                                     int32_t aovDepth, void* dMoments, const uint32_t* dList, int32_t listTiles) {
+  // ---- check
   if (!ctx || !p || !dAccumTiles) return 1;
   if (checkParams(ctx, p)) return 1;
   if (dList && (listTiles < 1 || listTiles > srtNumTiles(p->imageWidth, p->imageHeight) || p->tileStride != 1))
     return fail(ctx, "render: bad tile list of %d tiles", listTiles);
   HIP_OK(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+  const bool moments = dMoments != nullptr;
+  // ---- plan: the kernel and its LDS, the work split, the scheduler thresholds (srt_plan.cpp: arithmetic alone)
+  const LaunchPlan lp = planLaunch(sceneFacts(ctx->upload.scene), ctx->tun, ctx->prop.multiProcessorCount, p, moments, dList ? listTiles : -1);
+  const RenderPlan& plan = lp.render;
   RenderArgs a;
   setImageArgs(a, ctx, p);
   if (dList) a.numTiles = a.numLocalTiles = listTiles;
   a.maxBounce = p->maxBounce;
-  a.sppChunks = p->sppChunks > 0 ? p->sppChunks : srtDefaultSppChunks(p->spp);
-  {
-    // work queues (srt_render_kernel): units of >= 8 consecutive local tiles, about a dozen units per queue,
-    // at most 64 queues.  Measured on the 720p headline frame (ms per launch, 1 rank / one of 8 ranks):
-    // 1 queue 1916 / 253, 16 queues x 8 tiles 1818 / 238, 64 x 8: 1767 / 255, 64 x 16: 1744 / -.
-    const auto pow2Floor = [](int v) { int r = 1; while (2 * r <= v) r *= 2; return r; };
-    int unit = 8;
-    const int unitsAt8 = (a.numLocalTiles + 7) / 8;
-    if (unitsAt8 >= 2 * 12 * SRT_MAX_QUEUES) unit = 8 * pow2Floor(unitsAt8 / (12 * SRT_MAX_QUEUES));
-    a.unitTiles = std::min(1024, std::max(1, ctx->tun.unitTiles > 0 ? ctx->tun.unitTiles : unit));
-    const int units = (a.numLocalTiles + a.unitTiles - 1) / a.unitTiles;
-    // ... and only while every wave still gets a few dozen groups: with few groups per wave (16 spp on a
-    // 10 M-triangle soup: 14 400 groups for 5 120 waves) one counter balances better than stealing does.
-    const int64_t groups = (int64_t)a.numLocalTiles * a.sppChunks, waves = (int64_t)ctx->prop.multiProcessorCount * 20;
-    const int byUnits = pow2Floor(std::max(1, units / 12));
-    const int byGroups = pow2Floor((int)std::max<int64_t>(1, std::min<int64_t>(SRT_MAX_QUEUES, groups / (2 * waves))));
-    a.numQueues = std::min(SRT_MAX_QUEUES, std::max(1, ctx->tun.queues > 0 ? ctx->tun.queues : std::min(byUnits, byGroups)));
-  }
-  {
-    const int32_t planned = srtPlanSppChunks(p->imageWidth, p->imageHeight, p->spp, p->sppChunks);
-    if (planned < 1) return fail(ctx, "render: sppChunks %d x %d tiles exceeds 2^31 work items", p->sppChunks, a.numTiles);
-    a.sppChunks = planned;
-  }
-  a.fixLimit = chunkFixLimit(a.sppChunks);
-  a.numWork = a.numLocalTiles * a.sppChunks * SRT_TILE_PIXELS;
-  a.sppBase = a.spp / a.sppChunks;
-  a.sppRem = a.spp % a.sppChunks;
-  a.numUnits = (a.numLocalTiles + a.unitTiles - 1) / a.unitTiles;
-  a.unitGroups = a.unitTiles * a.sppChunks;
-  a.rcpUnitGroups = 1.0f / (float)a.unitGroups;
-  a.rcpChunks = 1.0f / (float)a.sppChunks;
-  if (!dList && (ctx->tileTableKey[0] != p->imageWidth || ctx->tileTableKey[1] != p->imageHeight || ctx->tileTableKey[2] != a.tileBlock || !ctx->tileTable.get())) {
-    // the tile order as a table (once per image size): the kernel's restart step looks a tile up instead of dividing
-    std::vector<uint32_t> table((size_t)a.numTiles);
-    for (int32_t i = 0; i < a.numTiles; ++i) {
-      int tx, ty;
-      srtTileFromOrder(i, a.tilesX, a.tilesY, a.tileBlock, tx, ty);
-      table[i] = (uint32_t)tx | (uint32_t)ty << 16;
-    }
-    ctx->tileTable = DeviceBuffer();  // freed first (as a size change always did), then allocated for this size
-    HIP_OK(ctx, ctx->tileTable.reserve(std::max<size_t>(table.size() * 4, 16)));
-    HIP_OK(ctx, hipMemcpy(ctx->tileTable.get(), table.data(), table.size() * 4, hipMemcpyHostToDevice));
-    ctx->tileTableKey[0] = p->imageWidth;
-    ctx->tileTableKey[1] = p->imageHeight;
-    ctx->tileTableKey[2] = a.tileBlock;
-  }
+  if (lp.sppChunks < 1) return fail(ctx, "render: sppChunks %d x %d tiles exceeds 2^31 work items", p->sppChunks, a.numTiles);
+  if (!lp.fitsLds) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->upload.scene.stackDepth, plan.lds);
+  setPlanArgs(a, lp);
+  // ---- tile table
+  if (!dList && tileTableFor(ctx, p, a)) return 1;
   a.tileXY = dList ? dList : ctx->tileTable.get<const uint32_t>();
-  // Scheduler defaults by traversal mode (profiles/r02/scheduler_sweep.txt).  FAITHFUL on cache-resident scenes:
-  // node bursts go on while half of their lanes are still at nodes, up to 64 visits, restarts at 24 waiting lanes
-  // (+6 % on the headline frame against 6/8, 32, 16).  The closest-hit traversal over the 64-byte records is bound by
-  // memory latency on large scenes and wants shorter bursts that give up sooner (10 M triangles: 87.6 against 77.8
-  // Msamples/s), and does not care on small ones.
-  const bool closestMode = p->traversal == SRT_TRAVERSE_CLOSEST;
-  a.shadeMin = ctx->tun.shadeMin >= 0 ? ctx->tun.shadeMin : (closestMode ? 16 : 24);
-  a.primMin = ctx->tun.primMin;
-  a.hitMin = ctx->tun.hitMin;
-  a.fuseMin = ctx->tun.fuseMin;
-  a.nodeBurst = std::max(1, ctx->tun.nodeBurst > 0 ? ctx->tun.nodeBurst : (closestMode ? 32 : 64));
-  a.primAgainMin = std::max(1, ctx->tun.primAgainMin);
-  a.keepEighths = std::min(8, ctx->tun.keepEighths >= 0 ? ctx->tun.keepEighths : (closestMode ? 6 : 4));
   a.queue = ctx->dQueue.get<int32_t>();
-  const bool moments = dMoments != nullptr;
   // (a moments launch neither counts nor profiles: its mout / mfix take the places of aov / stats, RenderArgs)
   unsigned long long* const stats = !moments && (p->countStats || ctx->tun.wfProfile > 0) ? ctx->dStats.get<unsigned long long>() : nullptr;
   a.stats = stats;
   a.aov = p->countStats ? aov : nullptr;
   a.aovDepth = aovDepth;
+  // ---- chunk-sum buffers
   const size_t tilePixels = (size_t)a.numLocalTiles * SRT_TILE_PIXELS;
   a.out = static_cast<float4*>(dAccumTiles);
   a.fix = nullptr;
   if (moments) a.mout = static_cast<float4*>(dMoments);
   a.chunkStride = 0;
   bool scratchPath = false;
-  // a moments launch sums its moments plane exactly as the beauty, on the same path: twice the slots or accumulators,
-  // the beauty's first, the moments' behind them
-  const size_t planes = moments ? 2 : 1;
-  if (a.sppChunks > 1) {
-    // Chunk sums are added exactly (srt_kernels.hip "Chunk sums").  Scratch path (a float4 slot per item, summed by
-    // srt_sum_chunks_kernel) while this rank's slots fit the budget, else the atomic path (32 B per pixel, 0.4-1 %
-    // slower); the two give the same bits, so the choice may differ from rank to rank.
-    const size_t localSlots = planes * tilePixels * a.sppChunks * sizeof(float4);
-    // budget: the tunable, and never more than a quarter of what the device has free right now (a smaller, shared or
-    // partitioned GPU takes the atomic path -- same bits -- instead of failing)
-    size_t budget = (size_t)std::max(0, ctx->tun.chunkScratchMb) * 1024 * 1024, freeB = 0, totalB = 0;
-    if (ctx->chunkScratch.bytes() < localSlots && hipMemGetInfo(&freeB, &totalB) == hipSuccess) budget = std::min(budget, (freeB + ctx->chunkScratch.bytes()) / 4);
-    scratchPath = localSlots <= budget;
-    const size_t need = scratchPath ? localSlots : planes * tilePixels * sizeof(SrtFixedAccum);
-    if (ctx->chunkScratch.reserve(need) != hipSuccess) {
-      (void)hipGetLastError();
-      if (!scratchPath) return fail(ctx, "render: cannot allocate %zu B for the pixel sums", need);
-      scratchPath = false;  // the slots do not fit after all: 32 B per pixel on the atomic path
-      HIP_OK(ctx, ctx->chunkScratch.reserve(planes * tilePixels * sizeof(SrtFixedAccum)));
-    }
-    if (scratchPath) {
-      a.out = ctx->chunkScratch.get<float4>();
-      a.chunkStride = (int32_t)tilePixels;
-      if (moments) a.mout = a.out + tilePixels * a.sppChunks;
-    } else {
-      a.fix = ctx->chunkScratch.get<SrtFixedAccum>();
-      if (moments) a.mfix = a.fix + tilePixels;
-      HIP_OK(ctx, hipMemsetAsync(a.fix, 0, planes * tilePixels * sizeof(SrtFixedAccum), stream));
-    }
-  }
-  const RenderPlan plan = renderPlan(ctx, p, moments, dList ? listTiles : -1);
+  if (a.sppChunks > 1 && chunkSumBuffers(ctx, a, moments, tilePixels, stream, scratchPath)) return 1;
   // The regrouped tree (srt_regroup.h) is walked by the whole-tree path-pool form alone, never by a counting launch, and
   // only while every box is ordered (its lemma's condition: a refit may have lost it)
-  if (plan.form != 3 || plan.count || ctx->tun.wfRegroup <= 0 || !a.scene.boxOrderedScene) a.scene.nodesRg = nullptr, a.scene.nodeThreadRg = nullptr;
-  if (plan.lds > 160 * 1024) return fail(ctx, "render: BVH depth %d needs %zu B of LDS per workgroup", ctx->upload.scene.stackDepth, plan.lds);
-  const RenderKernel kernel = plan.form >= 3 ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
+  if (plan.form != SRT_FORM_PATH_POOL || plan.count || ctx->tun.wfRegroup <= 0 || !a.scene.boxOrderedScene) a.scene.nodesRg = nullptr, a.scene.nodeThreadRg = nullptr;
+  const bool pathPool = srtFormIsPathPool(plan.form);
+  const RenderKernel kernel = pathPool ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
   if (plan.lds > 64 * 1024)
     HIP_OK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-  // persistent waves: enough workgroups to fill every CU (the path-pool kernel: one), never more than there is work
+  // persistent waves: as many workgroups as the CUs hold (the path-pool kernel: one each, planned)
   int perCU = 1;
-  if (plan.form < 3 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, plan.block, plan.lds) != hipSuccess || perCU < 1)) perCU = 1;
-  const int wgItems = SRT_TILE_PIXELS * (plan.block / 64);
-  int grid = std::min(ctx->prop.multiProcessorCount * perCU, (a.numWork + wgItems - 1) / wgItems);
-  if (grid < 1) grid = 1;
-  if (plan.form >= 3) {
-    // a workgroup never needs more contexts than it has work items
-    const int64_t itemsPerGroup = ((int64_t)a.numWork + grid - 1) / grid;
-    const int wfPoolSize = (int)std::max<int64_t>(64, std::min<int64_t>(plan.wfRingCap, itemsPerGroup + 63));
-    HIP_OK(ctx, ctx->wfPool.reserve((size_t)grid * wfPoolSize * 128));
+  if (!pathPool && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, plan.block, plan.lds) != hipSuccess || perCU < 1)) perCU = 1;
+  const int grid = pathPool ? lp.wfGrid : planGrid(ctx->prop.multiProcessorCount, perCU, a.numWork, plan.block);
+  // ---- pool buffers
+  if (pathPool) {
+    HIP_OK(ctx, ctx->wfPool.reserve((size_t)grid * lp.wfPoolSize * 128));
     const int hiLevels = std::max(0, p->maxBounce - 4);
-    HIP_OK(ctx, ctx->wfAttHi.reserve(std::max<size_t>(16, (size_t)grid * 3 * hiLevels * wfPoolSize * sizeof(float))));
+    HIP_OK(ctx, ctx->wfAttHi.reserve(std::max<size_t>(16, (size_t)grid * 3 * hiLevels * lp.wfPoolSize * sizeof(float))));
     a.wfPool = ctx->wfPool.get<char>();
     a.wfAttHi = ctx->wfAttHi.get<float>();
-    a.wfPoolSize = wfPoolSize;
-    a.wfRingCap = plan.wfRingCap;
-    a.wfRingShift = plan.wfRingShift;
-    a.wfRingMul3 = plan.wfRingMul3;
-    a.wfSwapMin = ctx->tun.wfSwapMin > 0 ? std::min(64, ctx->tun.wfSwapMin) : (plan.form == 4 ? 16 : 32);
-    a.wfFarRounds = ctx->tun.wfFarRounds > 0 ? std::min(4, ctx->tun.wfFarRounds) : (ctx->upload.scene.numNodes <= (1 << 20) ? 2 : 1);
-    a.wfSwapBig = std::max(a.wfSwapMin, std::min(64, ctx->tun.wfSwapBig));
     HIP_OK(ctx, hipHostGetDevicePointer((void**)&a.wfError, ctx->dWfError, 0));
-  } else if (plan.form == 1) {
-    HIP_OK(ctx, ctx->attScratch.reserve((size_t)(3 * p->maxBounce + 3) * grid * SRT_BLOCK_TREE * sizeof(float)));
+  } else if (plan.form == SRT_FORM_LDS_TREE) {
+    HIP_OK(ctx, ctx->attScratch.reserve((size_t)srtAttSlots(p->maxBounce) * grid * SRT_BLOCK_TREE * sizeof(float)));
     a.attScratch = ctx->attScratch.get<float>();
   }
+  // ---- launch
   HIP_OK(ctx, hipMemsetAsync(a.queue, 0, sizeof(int32_t) * 16 * a.numQueues, stream));
   if (stats) HIP_OK(ctx, hipMemsetAsync(stats, 0, 96 * sizeof(unsigned long long), stream));
   HIP_OK(ctx, hipEventRecord(ctx->evStart, stream));
@@ -315,6 +154,7 @@ int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTi
   if (rc) return fail(ctx, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
   HIP_OK(ctx, hipEventRecord(ctx->evStop, stream));
   ctx->timed = true;
+  // ---- finalise: the exact sums of the chunks' partial sums
   if (a.fix) {
     rc = srt_launch_finalize(a.fix, static_cast<float4*>(dAccumTiles), (int)tilePixels, a.spp, stream);
     if (!rc && moments) rc = srt_launch_finalize(a.mfix, static_cast<float4*>(dMoments), (int)tilePixels, a.spp, stream);
@@ -508,9 +348,8 @@ int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, i
   // srtTestGetTriUndecided's count of this call: a word of the statistics area that no render launch writes
   a.triUndecided = ctx->dStats.get<unsigned long long>() + SRT_STATS_TRI_UNDECIDED;
   if (hipMemset(a.triUndecided, 0, sizeof(unsigned long long)) != hipSuccess) return fail(ctx, "trace: clearing the undecided count");
-  size_t lds = (size_t)std::max(ctx->upload.scene.stackDepth, 1) * 256 * sizeof(int32_t);
-  int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->prop.multiProcessorCount * 8);
-  int e = srt_launch_trace(&a, traversal, grid, lds, nullptr);
+  const size_t lds = srtTraverseStackBytes(ctx->upload.scene.stackDepth);
+  int e = srt_launch_trace(&a, traversal, planEntryGrid(ctx->prop.multiProcessorCount, n), lds, nullptr);
   if (e) return fail(ctx, "trace launch failed: %s", hipGetErrorString((hipError_t)e));
   if (hipDeviceSynchronize() != hipSuccess) return fail(ctx, "trace kernel failed");
   if (hipMemcpy(hits, dHits.get(), n * sizeof(SrtHit), hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "trace: copy out");
@@ -535,9 +374,8 @@ static int queryDevice(SrtContext* ctx, const char* what, const void* dRays, int
   if ((uintptr_t)dHits % 16) return fail(ctx, "%s: the hits are not aligned to 16 bytes", what);
   if ((uintptr_t)dRecords % 4) return fail(ctx, "%s: the records are not aligned to 4 bytes", what);
   const DevScene& sc = ctx->upload.scene;
-  // slot 0 holds the walk's sentinel, the last slot is the spare of its unconditional store (srt_query.hip)
-  const size_t lds = (size_t)(std::max(sc.stackDepth, 1) + 2) * SRT_BLOCK * sizeof(int32_t);
-  if (lds > 160 * 1024) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
+  const size_t lds = srtQueryStackBytes(sc.stackDepth);
+  if (lds > SRT_LDS_BYTES) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
   HIP_OK(ctx, hipSetDevice(ctx->device));
   QueryArgs a;
   a.scene = sc;
@@ -546,8 +384,7 @@ static int queryDevice(SrtContext* ctx, const char* what, const void* dRays, int
   a.records = static_cast<SrtHit*>(dRecords);
   a.occluded = static_cast<uint8_t*>(dOccluded);
   a.n = n;
-  const int grid = (int)std::min<int64_t>((n + SRT_BLOCK - 1) / SRT_BLOCK, (int64_t)ctx->prop.multiProcessorCount * 8);
-  const int e = srt_launch_query(&a, mode, grid, lds, static_cast<hipStream_t>(streamPtr));
+  const int e = srt_launch_query(&a, mode, planEntryGrid(ctx->prop.multiProcessorCount, n), lds, static_cast<hipStream_t>(streamPtr));
   if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -576,9 +413,7 @@ uint64_t srtRngKey(uint64_t seed, uint64_t pixel, uint64_t sample) {  // the low
   return hostMix64(hostMix64(seed) ^ ((pixel << 32) | (sample & 0xffffffffull)));
 }
 
-static int pathGrid(const SrtContext* ctx, int64_t n) {
-  return (int)std::min<int64_t>((n + SRT_BLOCK - 1) / SRT_BLOCK, (int64_t)ctx->prop.multiProcessorCount * 8);
-}
+static int pathGrid(const SrtContext* ctx, int64_t n) { return planEntryGrid(ctx->prop.multiProcessorCount, n); }
 
 // a required device pointer of `what`: non-null and aligned
 static int checkPointer(SrtContext* ctx, const char* what, const char* name, const void* p, int align) {
@@ -660,9 +495,8 @@ static int pathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays,
     return 1;
   if ((uintptr_t)dHits % 16) return fail(ctx, "%s: the hits are not aligned to 16 bytes", what);
   const DevScene& sc = ctx->upload.scene;
-  // the walk's stacks, as queryDevice sizes and bounds them
-  const size_t lds = (size_t)(std::max(sc.stackDepth, 1) + 2) * SRT_BLOCK * sizeof(int32_t);
-  if (lds > 160 * 1024) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
+  const size_t lds = srtQueryStackBytes(sc.stackDepth);  // the walk's stacks, as queryDevice sizes and bounds them
+  if (lds > SRT_LDS_BYTES) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
   HIP_OK(ctx, hipSetDevice(ctx->device));
   PathStepArgs a;
   a.scene = sc;

@@ -16,6 +16,7 @@
 #include <limits>
 #include <random>
 
+#include "srt_lds_layout.h"
 #include "srt_regroup.h"
 #include "srt_thread.h"
 
@@ -489,8 +490,8 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     srtThreadLinks16(h.nodes, h.world, d->numTriangles, d->numSpheres, h.nodeThread);
     if (o.wfHybrid > 0) {
       const size_t n = h.nodes.size() / 2;
-      const size_t fits = (160 * 1024 - 64 * sizeof(int32_t) - 20 * 2048) / 32;       // beside a pool of 2048 contexts
-      const size_t fitsWhole = (160 * 1024 - 64 * sizeof(int32_t) - 18 * 1024) / 32;  // the whole-tree form's smallest pool
+      const size_t fits = srtWfMaxResidentNodes(SRT_WF_HYBRID_POOL, true);  // beside the hybrid form's pool
+      const size_t fitsWhole = srtWfMaxWholeTreeNodes();                    // the whole-tree form's smallest pool
       const size_t cap = o.wfResidentMax > 0 ? std::min<size_t>(fits, (size_t)o.wfResidentMax) : fits;
       if (n > (o.wfResidentMax > 0 ? cap : fitsWhole))
         h.wfResident = srtHybridRecords(h.nodes, h.world, d->numTriangles, d->numSpheres, cap, h.nodesWf, h.worldWf, h.primSecond, &h.wfIndex);
@@ -501,8 +502,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     // made, and the node array fits a CU's LDS beside the smallest pool.  Its lemma wants the reference's inner boxes to
     // contain their leaves' (the trees built here; a caller-built tree promises nothing) and ordered boxes.  The planes of
     // its inner boxes are planes of the leaves, so fastDivScene and boxOrderedScene hold for it as they stand.
-    const size_t fitsWholeTree = (160 * 1024 - 64 * sizeof(int32_t) - 18 * 1024) / 32;
-    if (!h.nodeThread.empty() && h.nodesWf.empty() && !adopted && ordered && h.nodes.size() / 2 <= fitsWholeTree &&
+    if (!h.nodeThread.empty() && h.nodesWf.empty() && !adopted && ordered && h.nodes.size() / 2 <= (size_t)srtWfMaxWholeTreeNodes() &&
         srtRegroupNodes(h.nodes, h.world, h.nodesRg)) {
       srtThreadLinks16(h.nodesRg, h.world, d->numTriangles, d->numSpheres, h.nodeThreadRg);
       bool same = !h.nodeThreadRg.empty();

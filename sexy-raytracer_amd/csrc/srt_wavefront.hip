@@ -30,6 +30,7 @@
 #include "srt_launch.h"
 #include "srt_wf_links.h"
 #include "srt_wf_rings.h"  // the rings, their control words, enqueue and claim
+#include "srt_lds_layout.h"  // WF_CTL_WORDS; srtWfLdsLayout states the carve-up below for the host
 
 #define WF_BLOCK 1024
 #define WF_SET_OF(mask) std::integral_constant<uint32_t, (mask)>()  // the rings an enqueue site can produce
@@ -44,7 +45,6 @@
 // (16-bit slots), then per context the t (float) and the primitive (16 bits) its last walk ended at.
 #define WF_CTL_LIVE 28
 #define WF_CTL_ABORT 29
-#define WF_CTL_WORDS 64
 #define WF_PEND_MISS 0      // context meta word: depth | pend << 8
 #define WF_PEND_TERMINAL 2
 
@@ -90,6 +90,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   char* const ldsTree = reinterpret_cast<char*>(lds);  // LDS offset 0 (the kernel has no other LDS): a node's offset is its address
   const int resident = HYBRID ? sc.wfResident : sc.numNodes;  // nodes [0, resident) are in LDS
   const int treeBytes = resident * 32;
+  // (this carve-up must match srt_lds_layout.h srtWfLdsLayout(resident, RCAP, POOL, HYBRID): the host sizes the launch by it)
   int32_t* const ctl = reinterpret_cast<int32_t*>(ldsTree + treeBytes);
   const int RCAP = a.wfRingCap, POOL = a.wfPoolSize;
   uint16_t* const ringSlots = reinterpret_cast<uint16_t*>(ctl + WF_CTL_WORDS);
@@ -897,14 +898,14 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
 }
 
 extern "C" {
-// the srt_render_wf_kernel instance a plan of form 3 or 4 names (srt_render.cpp renderPlan)
+// the srt_render_wf_kernel instance a plan of form 3 or 4 names (srt_plan.cpp planRender)
 RenderKernel srt_render_wf_kernel_for(const RenderPlan* p) {
   static_assert(WF_BLOCK == SRT_BLOCK_TREE, "srt_render.cpp launches the path-pool kernel with SRT_BLOCK_TREE threads");
   if (p->moments) {  // (never counting or profiling: srtRenderTilesMoments refuses countStats and ignores wf_profile)
-    if (p->form == 4) return p->single ? srt_render_wf_kernel<true, false, true, false, true> : srt_render_wf_kernel<false, false, true, false, true>;
+    if (p->form == SRT_FORM_PATH_POOL_HYBRID) return p->single ? srt_render_wf_kernel<true, false, true, false, true> : srt_render_wf_kernel<false, false, true, false, true>;
     return p->single ? srt_render_wf_kernel<true, false, false, false, true> : srt_render_wf_kernel<false, false, false, false, true>;
   }
-  if (p->form == 4)
+  if (p->form == SRT_FORM_PATH_POOL_HYBRID)
     return p->count     ? (p->single ? srt_render_wf_kernel<true, false, true, true> : srt_render_wf_kernel<false, false, true, true>)
            : p->profile ? srt_render_wf_kernel<false, true, true, false>
                         : (p->single ? srt_render_wf_kernel<true, false, true, false> : srt_render_wf_kernel<false, false, true, false>);

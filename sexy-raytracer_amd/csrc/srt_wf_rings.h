@@ -27,14 +27,19 @@
 #define WF_SET(r) (1u << (r))
 #define WF_SET_ALL ((1u << WF_RINGS) - 1u)
 
-// capacity = (mul3 ? 3 : 1) << shift: 1024, 1536, 2048, 3072, 4096 (srt_render.cpp renderPlan)
+typedef uint16_t SrtWfRingSlot;  // id + 1, 0 = empty
+
+// capacity = (mul3 ? 3 : 1) << shift
 struct SrtWfRingGeom {
   int32_t cap, shift, mul3;
 };
+// Every ring a launch can get, largest first: the planner (srt_plan.cpp planRender) takes the first that fits behind the
+// tree and does not exceed the tunable wf_pool
+constexpr SrtWfRingGeom kSrtWfRings[] = {{4096, 12, 0}, {3072, 10, 1}, {2048, 11, 0}, {1536, 9, 1}, {1024, 10, 0}};
 
 // place of counter value c in a ring: c mod cap.  2^j: exact for every 32-bit c, the counter's wrap included.  3 * 2^j:
 // c = x * 2^j + low, x mod 3 by a multiply-shift that is exact for every 32-bit x; the counter's wrap is NOT a multiple of
-// the capacity, so renderPlan admits these rings only while a workgroup's enqueues stay below 2 * 10^9.
+// the capacity, so planRender admits these rings only while a workgroup's enqueues stay below 2 * 10^9.
 SRT_HD inline uint32_t srtWfRingPos(uint32_t c, SrtWfRingGeom g) {
   if (!g.mul3) return c & (uint32_t)(g.cap - 1);
   const uint32_t x = c >> g.shift;

@@ -390,7 +390,7 @@ def test_cameras(ctx, dev, frames, abi, oracle, k, form):
 # ---------------------------------------------------------------------------------------------------- (d) ring capacities
 def ring_capacity(info, nodes, hybrid):
     """The ring capacity of a path-pool launch from its LDS size: lds = 32 * resident + 256 + (18 | 20) * capacity
-    (srt_render.cpp renderPlan), resident = the whole tree, or 1 to 24 nodes in the forced hybrid form."""
+    (srt_plan.cpp planRender), resident = the whole tree, or 1 to 24 nodes in the forced hybrid form."""
     fits = [c for c in RING_CAPACITIES
             if (info["lds_bytes"] - 256 - (20 if hybrid else 18) * c) in ([32 * r for r in range(1, 25)] if hybrid else [32 * nodes])]
     assert len(fits) == 1, (info, nodes, hybrid, fits)

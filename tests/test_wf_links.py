@@ -19,7 +19,7 @@ from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "sexy-raytracer_amd", "csrc")
 DONE = -(1 << 31)
-# the whole-tree form's admission (srt_scene.cpp flattenScene / srt_render.cpp renderPlan): the tree, 64 control words and the
+# the whole-tree form's admission (srt_scene.cpp flattenScene / srt_plan.cpp planRender): the tree, 64 control words and the
 # smallest pool (1024 contexts of 18 bytes) within a CU's 160 KB of LDS
 MAX_NODES = (160 * 1024 - 64 * 4 - 18 * 1024) // 32
 # srtThreadLinks16 admits 2 * numTriangles < 32766 and 2 * numSpheres + 1 < 32766

@@ -3,7 +3,7 @@ examples/wf_rings_probe.cpp runs the header's own functions.
 
   * srtWfRingPos against c % capacity for the five capacities: 10^6 seeded counters each, and the edges around EVERY
     multiple of the capacity up to the top of the range -- 2^32 - 1 for the 2^j rings, 2 * 10^9 for the 3 * 2^j ones (what
-    renderPlan admits them for).
+    the planner admits them for).  The capacities are the header's table kSrtWfRings, as examples/plan_probe.cpp prints it.
   * a host replay of enqueue's reservation: waves of 64 lanes, each lane with a seeded ring of the call site's set or none,
     their atomics in a seeded interleaving.  Every (ring, place) is handed out exactly once; a wave's places in a ring are
     consecutive, in lane order; the rings' totals match; the replay over the call site's set gives the places of the
@@ -13,6 +13,7 @@ examples/wf_rings_probe.cpp runs the header's own functions.
 What this pins is the ARITHMETIC of the reservation as the header states it for the host (base + the lanes below in the
 ring's mask) and its independence of the set.  The device forms -- v_mbcnt, v_writelane, srtWfEnqueue and srtWfClaim
 themselves -- do not compile for the host: tests/test_gpu_wf_handover.py covers them, frame by frame."""
+import functools
 import os
 import subprocess
 
@@ -24,8 +25,7 @@ from conftest import ROOT
 CSRC = os.path.join(ROOT, "sexy-raytracer_amd", "csrc")
 RINGS = 6
 READY, RESTART, HIT, NEWITEM = 0, 1, 2, 5
-# capacity -> (shift, mul3): srt_render.cpp renderPlan's table
-CAPACITIES = {1024: (10, 0), 1536: (9, 1), 2048: (11, 0), 3072: (10, 1), 4096: (12, 0)}
+CAPS = (1024, 1536, 2048, 3072, 4096)  # the parametrised tests' names; _capacities() holds them to the header's table
 # the call sites of srt_wavefront.hip
 SETS = {
     "swap": (RESTART, HIT, HIT + 1, HIT + 2),
@@ -45,6 +45,15 @@ def probe():
     return _build("srt_wf_rings_probe")
 
 
+@functools.lru_cache(maxsize=None)
+def _capacities():
+    """capacity -> (shift, mul3): csrc/srt_wf_rings.h kSrtWfRings, the planner's table, read from the plan probe's output."""
+    lines = subprocess.check_output([_build("srt_plan_probe"), "limits"], text=True).splitlines()
+    table = {int(c): (int(s), int(m)) for key, c, s, m in (l.split() for l in lines if l.startswith("ring "))}
+    assert sorted(table) == list(CAPS), table
+    return table
+
+
 def _run(exe, mode, blob, d):
     with open(d / "in.bin", "wb") as f:
         f.write(blob)
@@ -54,7 +63,7 @@ def _run(exe, mode, blob, d):
 
 def _top(cap):
     """The largest counter value a ring of this capacity is admitted for: 2^32 - 1, or 2 * 10^9 for the 3 * 2^j ones."""
-    return 2 ** 32 - 1 if not CAPACITIES[cap][1] else 2 * 10 ** 9
+    return 2 ** 32 - 1 if not _capacities()[cap][1] else 2 * 10 ** 9
 
 
 def _edges(cap, first, count):
@@ -64,7 +73,7 @@ def _edges(cap, first, count):
 
 
 def _check_pos(exe, d, cap, c):
-    shift, mul3 = CAPACITIES[cap]
+    shift, mul3 = _capacities()[cap]
     blob = np.array([cap, shift, mul3, len(c)], np.int32).tobytes() + c.astype(np.uint32).tobytes()
     got = _run(exe, "pos", blob, d)
     assert len(got) == len(c)
@@ -72,11 +81,11 @@ def _check_pos(exe, d, cap, c):
     assert len(bad) == 0, (cap, c[bad[:4]], got[bad[:4]])
 
 
-@pytest.mark.parametrize("cap", sorted(CAPACITIES))
+@pytest.mark.parametrize("cap", CAPS)
 def test_ring_pos_is_the_remainder(probe, tmp_path, cap):
     """10^6 seeded counters, the last 8192 values of the range, and the five counters around EVERY multiple of the capacity
     in the range (at most 4.2 M multiples, in chunks of 2^20): every quotient the multiply-shift modulo can meet."""
-    shift, mul3 = CAPACITIES[cap]
+    shift, mul3 = _capacities()[cap]
     assert cap == (3 if mul3 else 1) << shift
     top = _top(cap)
     rng = np.random.default_rng(cap)
@@ -168,7 +177,7 @@ def test_probe_under_sanitizers(tmp_path):
     # (a stand-alone binary with the sanitizers' runtime linked in: the environment is inherited, plus their options)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     for cap in (1536, 4096):
-        shift, mul3 = CAPACITIES[cap]
+        shift, mul3 = _capacities()[cap]
         c = _edges(cap, _top(cap) // cap - 3999, 4000)  # the last 4000 multiples of the range
         blob = np.array([cap, shift, mul3, len(c)], np.int32).tobytes() + c.astype(np.uint32).tobytes()
         with open(tmp_path / "in.bin", "wb") as f:
