@@ -4,6 +4,13 @@
 //   srt_regroup_probe regroup <in.bin> <out.bin>
 //     in:  int32 numNodes, numWorld; the node records (2 x float4 each); the world list (int32 each)
 //     out: int32 1 and the regrouped records, or int32 0 alone (a tree that is not a pre-order tree of two-node / two-primitive nodes)
+//   srt_regroup_probe walk <in.bin> <out.bin>
+//     in:  as for `regroup` (a regrouped array, or any array of such trees)
+//     out: int32 1, int32 count, the keep mask as one int32 per node, then src[count], links[2 x count] (hit word, miss word) and
+//          entry[numWorld] -- the walk sequence of srtRegroupWalk with the link words of csrc/srt_wf_links.h -- or int32 0 alone.
+//          Before it writes, the program follows the links from every entry and checks that it meets each of that tree's
+//          kept records once, in order, that every node word lies inside the sequence, and that srtWfRootWord leaves the
+//          entry words as they are (the launch hands them to the kernel in the world list's place); exit status 3 otherwise.
 //   srt_regroup_probe gate <in.bin> <out.bin>
 //     in:  int32 n; n cases of 20 floats: the leaf box (min.xyz, max.xyz), the gate box (min.xyz, max.xyz), the ray's origin
 //          and direction, tMin, tMax
@@ -42,6 +49,57 @@ static int regroup(FILE* in, FILE* out) {
   return 0;
 }
 
+static int walk(FILE* in, FILE* out) {
+  int32_t n[2];
+  if (fread(n, 4, 2, in) != 2 || n[0] < 0 || n[1] < 0) return 1;
+  std::vector<float4> nodes(2 * (size_t)n[0]);
+  std::vector<int32_t> world(n[1]);
+  if (fread(nodes.data(), sizeof(float4), nodes.size(), in) != nodes.size()) return 1;
+  if (fread(world.data(), 4, world.size(), in) != world.size()) return 1;
+  SrtRegroupWalk w;
+  const int32_t ok = srtRegroupWalk(nodes, world, w) ? 1 : 0;
+  fwrite(&ok, 4, 1, out);
+  if (!ok) return 0;
+  const int32_t count = (int32_t)w.src.size();
+  // the kernel's own decoding of the words: from each entry the walk in which every box passes (a gate: its hit link; a
+  // leaf: its objects, then its miss link) meets the records of that tree one after the other and ends in DONE; a miss link
+  // leads ahead, to a record of the sequence, or is DONE
+  int32_t met = 0;
+  for (size_t k = 0; k < world.size(); ++k) {
+    int32_t cur = w.entry[k];
+    if (srtWfRootWord(cur) != cur) return 3;
+    if (world[k] < 0) {
+      if (cur != srtWfRootWord(world[k]) || !srtWfAtPrim(srtWfLeafFirst(cur)) || srtWfLeafHasSecond(cur)) return 3;
+      continue;
+    }
+    while (cur != SRT_WF_DONE) {
+      if (met >= count || cur != SRT_NODE_REF(met)) return 3;
+      const int32_t hit = w.links[2 * (size_t)met], miss = w.links[2 * (size_t)met + 1];
+      if (miss != SRT_WF_DONE && (!srtWfAtNode(miss) || (miss & 31) || SRT_NODE_INDEX(miss) <= met || SRT_NODE_INDEX(miss) >= count)) return 3;
+      if (!srtWfAtNode(hit) && (hit == SRT_WF_DONE || !srtWfAtPrim(srtWfLeafFirst(hit)))) return 3;
+      // the record's own children, decoded as popNext does: a gate's hit link is a node, a leaf word gives back both objects
+      const int32_t l = srt_regroup_detail::refOf(nodes, 2 * (size_t)w.src[met]), r = srt_regroup_detail::refOf(nodes, 2 * (size_t)w.src[met] + 1);
+      if (srtWfAtNode(hit) != (l >= 0)) return 3;
+      if (l < 0) {
+        if (srtWfLeafFirst(hit) != l || srtWfLeafHasSecond(hit) != (l != r)) return 3;
+        if (l != r && (srtWfLeafFirst(srtWfLeafRest(hit)) != r || srtWfLeafHasSecond(srtWfLeafRest(hit)))) return 3;
+      }
+      cur = srtWfAtNode(hit) ? hit : miss;
+      met++;
+    }
+  }
+  if (met != count) return 3;
+  fwrite(&count, 4, 1, out);
+  for (uint8_t k : w.keep) {
+    const int32_t v = k;
+    fwrite(&v, 4, 1, out);
+  }
+  fwrite(w.src.data(), 4, w.src.size(), out);
+  fwrite(w.links.data(), 4, w.links.size(), out);
+  fwrite(w.entry.data(), 4, w.entry.size(), out);
+  return 0;
+}
+
 static int gate(FILE* in, FILE* out) {
   int32_t n;
   if (fread(&n, 4, 1, in) != 1 || n < 0) return 1;
@@ -66,6 +124,7 @@ int main(int argc, char** argv) {
   if (!in || !out) return 1;
   int rc = 2;
   if (!strcmp(argv[1], "regroup")) rc = regroup(in, out);
+  if (!strcmp(argv[1], "walk")) rc = walk(in, out);
   if (!strcmp(argv[1], "gate")) rc = gate(in, out);
   fclose(in);
   return fclose(out) ? 1 : rc;

@@ -88,9 +88,10 @@ int srtTestThreadLinks16(const float* nodes8, int32_t numNodes, const int32_t* w
 int srtTestHybridRecords(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, int32_t numTriangles, int32_t numSpheres,
                          int32_t cap, float* outNodes8, int32_t* outWorld, int32_t* outSecond);
 
-/* The regrouped tree of the path-pool kernel's whole-tree form (csrc/srt_regroup.h; tunable "wf_regroup", default 1, 0 = the
- * kernel walks the reference tree): the reference's leaf records in the reference's order under inner nodes rebuilt by a
- * surface-area split over contiguous leaf ranges.  Every walk ends at the same (t, primitive); accumulators are bit-identical.
+/* The regrouped tree of the path-pool kernel's whole-tree form (csrc/srt_regroup.h; tunable "wf_regroup": 2, the default =
+ * the kernel walks the regrouped tree's walk sequence, below; 1 = the binary regrouped tree; 0 = the reference tree): the
+ * reference's leaf records in the reference's order under inner nodes rebuilt by a surface-area split over contiguous leaf
+ * ranges.  Every walk ends at the same (t, primitive) under all three; accumulators are bit-identical.
  * srtTestRegroup (host only, no device): the regrouped array of a flattened node array (the format above) and its world
  * list -> outNodes8[numNodes x 8]; returns 1, 0 when a tree is not a pre-order tree of two-node / two-primitive nodes, -1 on a
  * null argument.
@@ -99,6 +100,22 @@ int srtTestHybridRecords(const float* nodes8, int32_t numNodes, const int32_t* w
  * *count = 0 when the upload built none (a tree beyond LDS, a caller-built tree, device-built trees, a box that is not ordered). */
 int srtTestRegroup(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, float* outNodes8);
 int srtTestGetRegroup(SrtContext* ctx, float* outNodes8, int32_t* outLinks, int32_t capacity, int32_t* count);
+
+/* The regrouped tree's WALK SEQUENCE (csrc/srt_regroup.h srtRegroupWalk; tunable "wf_regroup" 2): the regrouped array without
+ * the gates that rarely cull a ray -- gate g with m effective children under its binary parent p is elided when
+ * area(g) * m > area(p) * (m - 1), bottom-up, and so is every inner root; leaves are always kept.  The kept records are
+ * numbered in array order; record j has its source record in the regrouped array (whose box it takes at every launch) and the
+ * two link words of csrc/srt_wf_links.h (srtWfSeqHitWord, srtWfSeqMissWord); a world item has an entry word.
+ * srtTestRegroupWalk (host only, no device): from a regrouped array (srtTestRegroup's output, the format above) and its world
+ * list -> outKeep[numNodes] (1 = kept), outSrc[*count], outLinks[2 x *count] (hit word, miss word), outEntry[numWorld]; outSrc
+ * and outLinks must hold numNodes records.  Returns 1, 0 for an array that is not one of pre-order trees of two-node /
+ * two-primitive nodes, -1 on a null argument.
+ * srtTestGetRegroupWalk: the uploaded scene's sequence as it lies in device memory now (after srtRefitScene as well), same
+ * outputs, any of which may be NULL; `capacity` must be the node count of srtTestGetRegroup at least.  *count = 0 when the
+ * upload built no regrouped tree. */
+int srtTestRegroupWalk(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, uint8_t* outKeep, int32_t* outSrc,
+                       int32_t* outLinks, int32_t* outEntry, int32_t* count);
+int srtTestGetRegroupWalk(SrtContext* ctx, uint8_t* outKeep, int32_t* outSrc, int32_t* outLinks, int32_t* outEntry, int32_t capacity, int32_t* count);
 
 /* Reads back what the near-child-first traversal walks for world item `item` (host-built and device-built trees alike), as
  * it lies in device memory: the item's slice of DevScene::nodeAxis -> outAxis[count] (the split axis of each node, 3 = none)

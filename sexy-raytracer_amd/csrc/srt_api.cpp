@@ -97,8 +97,9 @@ const TunableName kTunables[] = {
     // triangles lose 5-10 % with 2) -- profiles/r03/hybrid.txt
     {"wf_far_rounds", "SRT_WF_FAR_ROUNDS", &Tunables::wfFarRounds, 0},
     // path-pool kernel over a whole tree: walk the regrouped tree (srt_regroup.h, DevScene::nodesRg) where the upload built
-    // one.  0 = the reference tree: the same accumulators from about twice the node visits.  Read at every launch.
-    {"wf_regroup", "SRT_WF_REGROUP", &Tunables::wfRegroup, 1},
+    // one.  2 = its walk sequence, the gates that rarely cull a ray elided (srtRegroupWalk); 1 = the binary regrouped tree;
+    // 0 = the reference tree: the same accumulators from about twice the node visits.  Read at every launch.
+    {"wf_regroup", "SRT_WF_REGROUP", &Tunables::wfRegroup, 2},
     // srtDenoise: a-trous levels of step <= this stage their (16 + 4 step)^2 window in LDS, larger steps read through the
     // caches (srt_denoise.hip; 8 at most, 0 = never) -- profiles/r05/denoise_bench.json
     {"denoise_lds_step", "SRT_DENOISE_LDS_STEP", &Tunables::denoiseLdsStep, 4},
@@ -160,6 +161,8 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   DevScene& s = ctx->upload.scene;
   if (!h.nodeThread.empty() && uploadVec(ctx, h.nodeThread, &s.nodeThread)) return 1;
   if (!h.nodesRg.empty() && (uploadVec(ctx, h.nodesRg, &s.nodesRg) || uploadVec(ctx, h.nodeThreadRg, &s.nodeThreadRg))) return 1;
+  if (!h.walkSeq.empty() && uploadVec(ctx, h.walkSeq, &s.walkSeq)) return 1;
+  s.numWalk = h.walkSeq.empty() ? 0 : h.numWalk;
   if (!h.nodesWf.empty() && (uploadVec(ctx, h.nodesWf, &s.nodesWf) || uploadVec(ctx, h.worldWf, &s.worldWf) || uploadVec(ctx, h.primSecond, &s.primSecond))) return 1;
   if (uploadVec(ctx, h.primClass, &s.primClass, 16) || uploadVec(ctx, h.nodeAxis, &s.nodeAxis, 64) || uploadVec(ctx, h.nodes, &s.nodes) ||
       uploadVec(ctx, h.triTest, &s.triTest) || uploadVec(ctx, h.triFast, &s.triFast) || uploadVec(ctx, h.triShade, &s.triShade) || uploadVec(ctx, h.spheres, &s.spheres) ||
@@ -450,6 +453,45 @@ int srtTestGetRegroup(SrtContext* ctx, float* outNodes8, int32_t* outLinks, int3
   HIP_OK(ctx, hipDeviceSynchronize());
   if (outNodes8) HIP_OK(ctx, hipMemcpy(outNodes8, s.nodesRg, (size_t)s.numNodes * 32, hipMemcpyDeviceToHost));
   if (outLinks) HIP_OK(ctx, hipMemcpy(outLinks, s.nodeThreadRg, (size_t)s.numNodes * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+/* include/srt_hip_test.h: host-only hook for srt_regroup.h srtRegroupWalk, and the uploaded scene's walk sequence as it lies on the device */
+int srtTestRegroupWalk(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, uint8_t* outKeep, int32_t* outSrc,
+                       int32_t* outLinks, int32_t* outEntry, int32_t* count) {
+  if (!nodes8 || !world || !outKeep || !outSrc || !outLinks || !outEntry || !count || numNodes < 0 || numWorld < 0) return -1;
+  std::vector<float4> nodes(2 * (size_t)numNodes);
+  if (numNodes) memcpy(nodes.data(), nodes8, nodes.size() * sizeof(float4));
+  SrtRegroupWalk walk;
+  *count = 0;
+  if (!srtRegroupWalk(nodes, std::vector<int32_t>(world, world + numWorld), walk)) return 0;
+  *count = (int32_t)walk.src.size();
+  if (numNodes) memcpy(outKeep, walk.keep.data(), walk.keep.size());
+  if (*count) memcpy(outSrc, walk.src.data(), walk.src.size() * sizeof(int32_t));
+  if (*count) memcpy(outLinks, walk.links.data(), walk.links.size() * sizeof(int32_t));
+  if (numWorld) memcpy(outEntry, walk.entry.data(), walk.entry.size() * sizeof(int32_t));
+  return 1;
+}
+int srtTestGetRegroupWalk(SrtContext* ctx, uint8_t* outKeep, int32_t* outSrc, int32_t* outLinks, int32_t* outEntry, int32_t capacity, int32_t* count) {
+  if (!ctx || !count) return 1;
+  if (!ctx->upload.haveScene) return fail(ctx, "srtTestGetRegroupWalk: no scene uploaded");
+  const DevScene& s = ctx->upload.scene;
+  *count = s.walkSeq ? s.numWalk : 0;
+  if (!s.walkSeq || (!outKeep && !outSrc && !outLinks && !outEntry)) return 0;
+  if (capacity < s.numNodes) return fail(ctx, "srtTestGetRegroupWalk: capacity %d < %d", capacity, s.numNodes);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  HIP_OK(ctx, hipDeviceSynchronize());
+  std::vector<int32_t> seq(3 * (size_t)s.numWalk + (size_t)s.numWorld);
+  HIP_OK(ctx, hipMemcpy(seq.data(), s.walkSeq, seq.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (outKeep) memset(outKeep, 0, (size_t)s.numNodes);
+  for (int32_t j = 0; j < s.numWalk; ++j) {
+    const int32_t src = seq[3 * (size_t)j];
+    if (src < 0 || src >= s.numNodes) return fail(ctx, "srtTestGetRegroupWalk: record %d has source %d", j, src);
+    if (outKeep) outKeep[src] = 1;
+    if (outSrc) outSrc[j] = src;
+    if (outLinks) outLinks[2 * (size_t)j] = seq[3 * (size_t)j + 1], outLinks[2 * (size_t)j + 1] = seq[3 * (size_t)j + 2];
+  }
+  if (outEntry) memcpy(outEntry, seq.data() + 3 * (size_t)s.numWalk, (size_t)s.numWorld * sizeof(int32_t));
   return 0;
 }
 

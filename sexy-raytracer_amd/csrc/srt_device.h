@@ -120,6 +120,13 @@ struct DevScene {
   // switched off for the launch (tunable "wf_regroup", a counting launch, boxOrderedScene lost in a refit).
   const float4* nodesRg;
   const int32_t* nodeThreadRg;
+  // ... and its WALK SEQUENCE (srt_regroup.h srtRegroupWalk, tunable "wf_regroup" 2): the regrouped tree without the gates
+  // that rarely cull a ray.  Three words per kept record, numWalk records in pre-order: its source record in nodesRg (the
+  // box is read there at every launch: a refit needs nothing here) and its two link words (srt_wf_links.h srtWfSeq*);
+  // behind them one entry word per world item.  The set-up copy fills the first numWalk slots of the LDS tree from it, and
+  // the launch hands the entry words to the kernel in `world`'s place.  Null / 0: not built, or not asked for.
+  const int32_t* walkSeq;
+  int32_t numWalk;
 };
 
 struct DevCamera {

@@ -29,6 +29,7 @@
 
 #include "srt_device.h"
 #include "srt_records.h"
+#include "srt_wf_links.h"
 
 namespace srt_regroup_detail {
 inline int32_t refOf(const std::vector<float4>& nodes, size_t slot) {
@@ -144,5 +145,113 @@ inline bool srtRegroupNodes(const std::vector<float4>& nodes, const std::vector<
       out[2 * (size_t)i + 1].x = b.mx[0], out[2 * (size_t)i + 1].y = b.mx[1], out[2 * (size_t)i + 1].z = b.mx[2];
     }
   }
+  return true;
+}
+
+// ---- the walk sequence: the regrouped tree without the gates that rarely cull a ray (tunable "wf_regroup" 2).
+//
+// An inner node of the regrouped tree is a gate: it must pass wherever one of its leaves would, and nothing else is asked of
+// it.  A gate that ALWAYS passes meets that, so deleting a gate and handing its children to its nearest kept ancestor is one
+// more valid hierarchy over the same leaf sequence: every walk ends at the same (t, primitive).  A visit is the unit of cost,
+// as in SAH's collapse rule: a gate g under its binary parent p, with m EFFECTIVE children -- per binary child one, or that
+// child's own effective children where the child is an elided gate -- is worth its visit only while it fails often enough to
+// save its m children's visits.  With the chance of "a ray that passed p passes g" taken as area(g) / area(p):
+//     elide g  <=>  area(g) * m > area(p) * (m - 1)          (double halfArea, strict: a NaN area never elides)
+// decided bottom-up (the children's verdicts first; p is the parent in the BINARY array whether or not it is kept), and every
+// inner root is elided: nothing lies above it that a miss would save.  Leaves are always kept.
+//
+// The sequence is the kept records in the array's order (pre-order per tree), numbered 0, 1, ... over the whole array, with
+// the link words of srt_wf_links.h (srtWfSeq*): a gate's hit link is the next record, a record's miss link the first kept
+// record behind its subtree.  Boxes are NOT part of it: record j's box is nodesRg[src[j]]'s of the moment, so a refit needs
+// no second pass, and the keep mask stays valid for any boxes (it is a property of the upload, like the grouping).
+struct SrtRegroupWalk {
+  std::vector<uint8_t> keep;   // per record of the binary array: 1 = in the sequence
+  std::vector<int32_t> src;    // per record of the sequence: its record in the binary array
+  std::vector<int32_t> links;  // per record of the sequence: its hit word, its miss word
+  std::vector<int32_t> entry;  // per world item: where its walk starts (srtWfSeqEntryWord)
+};
+
+// rg: a regrouped array (srtRegroupNodes' output; any array of pre-order trees of two-node / two-primitive nodes will do);
+// world: its roots.  Linear in the array.  Returns false, with `out` empty, for anything else.
+inline bool srtRegroupWalk(const std::vector<float4>& rg, const std::vector<int32_t>& world, SrtRegroupWalk& out) {
+  using namespace srt_regroup_detail;
+  const size_t n = rg.size() / 2;
+  out = SrtRegroupWalk();
+  auto fail = [&]() { return out = SrtRegroupWalk(), false; };
+  std::vector<uint8_t> keep(n, 0), seen(n, 0);
+  std::vector<int32_t> parent(n, -1), end(n, 0), children(n, 1), count(world.size(), 0), todo;
+  for (size_t wi = 0; wi < world.size(); ++wi) {
+    if (world[wi] < 0) continue;
+    const int32_t root = SRT_NODE_INDEX(world[wi]);
+    // ---- the tree's extent and every node's binary parent; pre-order: the left child lies right behind its parent
+    todo.assign(1, root);
+    int32_t cnt = 0, last = root;
+    while (!todo.empty()) {
+      const int32_t i = todo.back();
+      todo.pop_back();
+      if (i < 0 || (size_t)i >= n || seen[i]) return fail();
+      seen[i] = 1;
+      cnt++;
+      last = i > last ? i : last;
+      const int32_t l = refOf(rg, 2 * (size_t)i), r = refOf(rg, 2 * (size_t)i + 1);
+      if ((l >= 0) != (r >= 0)) return fail();
+      if (l < 0) continue;
+      const int32_t li = SRT_NODE_INDEX(l), ri = SRT_NODE_INDEX(r);
+      if (li != i + 1 || ri <= li || (size_t)ri >= n) return fail();
+      parent[li] = parent[ri] = i;
+      todo.push_back(ri);
+      todo.push_back(li);
+    }
+    if (last - root + 1 != cnt) return fail();
+    count[wi] = cnt;
+    // ---- the keep mask bottom-up (children lie behind their parent), and where every subtree ends
+    for (int32_t i = root + cnt - 1; i >= root; --i) {
+      const int32_t l = refOf(rg, 2 * (size_t)i), r = refOf(rg, 2 * (size_t)i + 1);
+      if (l < 0) {
+        keep[i] = 1;
+        end[i] = i + 1;
+        continue;
+      }
+      const int32_t li = SRT_NODE_INDEX(l), ri = SRT_NODE_INDEX(r);
+      if (end[li] != ri) return fail();  // (the right child lies right behind the left subtree)
+      end[i] = end[ri];
+      const int32_t m = children[li] + children[ri];
+      const bool elide = i == root || halfArea(boxOfNode(rg, (size_t)i)) * (double)m > halfArea(boxOfNode(rg, (size_t)parent[i])) * (double)(m - 1);
+      keep[i] = elide ? 0 : 1;
+      children[i] = elide ? m : 1;
+    }
+  }
+  // ---- the sequence: numbers in array order, then per tree the links
+  std::vector<int32_t> number(n + 1, -1);
+  for (size_t i = 0; i < n; ++i)
+    if (keep[i]) {
+      number[i] = (int32_t)out.src.size();
+      out.src.push_back((int32_t)i);
+    }
+  out.links.assign(2 * out.src.size(), SRT_WF_DONE);
+  out.entry.resize(world.size());
+  std::vector<int32_t>& next = end;  // (re-used below: end[i] is read before next[i] is written, i descending)
+  for (size_t wi = 0; wi < world.size(); ++wi) {
+    if (world[wi] < 0) {
+      out.entry[wi] = srtWfSeqEntryWord(world[wi], -1);
+      continue;
+    }
+    const int32_t root = SRT_NODE_INDEX(world[wi]), stop = root + count[wi];
+    // next[i]: the number of the first kept record at or behind i in this tree, -1: none
+    int32_t behind = -1;
+    for (int32_t i = stop - 1; i >= root; --i) {
+      const int32_t e = end[i];
+      const int32_t after = e < stop ? next[e] : -1;
+      if (keep[i]) {
+        const int32_t j = number[i];
+        out.links[2 * (size_t)j] = srtWfSeqHitWord(refOf(rg, 2 * (size_t)i), refOf(rg, 2 * (size_t)i + 1), j);
+        out.links[2 * (size_t)j + 1] = srtWfSeqMissWord(after);
+        behind = j;
+      }
+      next[i] = behind;
+    }
+    out.entry[wi] = srtWfSeqEntryWord(world[wi], next[root]);
+  }
+  out.keep.swap(keep);
   return true;
 }

@@ -123,6 +123,13 @@ int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTi
   // The regrouped tree (srt_regroup.h) is walked by the whole-tree path-pool form alone, never by a counting launch, and
   // only while every box is ordered (its lemma's condition: a refit may have lost it)
   if (plan.form != SRT_FORM_PATH_POOL || plan.count || ctx->tun.wfRegroup <= 0 || !a.scene.boxOrderedScene) a.scene.nodesRg = nullptr, a.scene.nodeThreadRg = nullptr;
+  // Its walk sequence (tunable 2): the kernel's set-up copy takes the kept records alone, and walks start at the entry
+  // words behind them, handed over in the world list's place (srt_wf_links.h: srtWfRootWord leaves an entry word as it is;
+  // the path-pool kernel reads `world` for nothing else), so the kernel holds no value it did not hold before
+  if (!a.scene.nodesRg || ctx->tun.wfRegroup < 2 || !a.scene.walkSeq)
+    a.scene.walkSeq = nullptr, a.scene.numWalk = 0;
+  else
+    a.scene.world = a.scene.walkSeq + 3 * (size_t)a.scene.numWalk;
   const bool pathPool = srtFormIsPathPool(plan.form);
   const RenderKernel kernel = pathPool ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
   if (plan.lds > 64 * 1024)

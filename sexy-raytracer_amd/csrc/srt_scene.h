@@ -79,7 +79,11 @@ struct HostScene {
   // nodes over the same leaves, and its own 16-bit thread links.  Empty: not built
   std::vector<float4> nodesRg;
   std::vector<int32_t> nodeThreadRg;
-  std::vector<float4> nodesWf;      // empty: no hybrid records
+  // its walk sequence (srt_regroup.h srtRegroupWalk; DevScene::walkSeq): per kept record (source record in nodesRg, hit
+  // word, miss word), numWalk of them, then one entry word per world item.  Empty with nodesRg
+  std::vector<int32_t> walkSeq;
+  int32_t numWalk = 0;
+  std::vector<float4> nodesWf;     // empty: no hybrid records
   std::vector<int32_t> worldWf, primSecond;
   int32_t wfResident = 0;
   std::vector<std::vector<SrtBvhNode>> itemNodes;  // per world item: its host-built tree (srtGetBvh)

@@ -130,11 +130,23 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
   {
     float4* dst = reinterpret_cast<float4*>(ldsTree);
     const int32_t* const threads = regroup ? sc.nodeThreadRg : sc.nodeThread;
-    for (int i = threadIdx.x; i < resident * 2; i += WF_BLOCK) {
-      float4 v = bufLoad4(rsNodes, 16 * i);
-      if (!HYBRID) {  // nodesWf holds the threaded records already
-        const int32_t thread = threads[i >> 1];
-        v.w = __int_as_float((i & 1) ? srtWfMissWord(thread) : srtWfHitWord(__float_as_int(v.w), thread));
+    // The regrouped tree's WALK SEQUENCE where the launch hands one over (DevScene::walkSeq, srt_regroup.h srtRegroupWalk:
+    // the gates that rarely cull a ray elided): slot j takes its box from the regrouped array's record src[j], as a refit
+    // left it, and its two words ready-made; the slots behind the sequence stay unwritten, no link leads there.  The walks
+    // start at the sequence's entry words, which the launch put in the world list's place.  Nothing below knows of it.
+    const int numSeq = regroup ? sc.numWalk : 0;
+    for (int i = threadIdx.x; i < (numSeq > 0 ? numSeq : resident) * 2; i += WF_BLOCK) {
+      float4 v;
+      if (numSeq > 0) {
+        const int32_t* const rec = sc.walkSeq + 3 * (i >> 1);
+        v = bufLoad4(rsNodes, 32 * rec[0] + 16 * (i & 1));
+        v.w = __int_as_float(rec[1 + (i & 1)]);
+      } else {
+        v = bufLoad4(rsNodes, 16 * i);
+        if (!HYBRID) {  // nodesWf holds the threaded records already
+          const int32_t thread = threads[i >> 1];
+          v.w = __int_as_float((i & 1) ? srtWfMissWord(thread) : srtWfHitWord(__float_as_int(v.w), thread));
+        }
       }
       dst[i] = v;
     }

@@ -1,7 +1,8 @@
 // srt_wf_links.h -- the link words of the path-pool kernel's LDS copy of the tree, whole-tree form (srt_wavefront.hip,
 // HYBRID == false): ONE statement of their encoding for the kernel's prologue, which builds the copy from DevScene::nodes
 // and DevScene::nodeThread, for its walk, which decodes them, and for a host program (examples/wf_links_probe.cpp,
-// tests/test_wf_links.py).  The copy is private to the kernel: no upload, ABI or host structure holds these words.
+// tests/test_wf_links.py).  The copy is private to the kernel; the one place outside it that holds such words is the regrouped
+// tree's walk sequence (DevScene::walkSeq, at the end of this file), whose words the upload makes with the functions here.
 //
 // A lane's position `cur` and a node's two words are 32-bit values of four disjoint kinds:
 //   x >= 0            a node: the BYTE OFFSET of its record in the LDS copy (index * 32; the copy sits at LDS offset 0, so
@@ -55,3 +56,15 @@ SRT_HD inline int32_t srtWfLeafFirst(int32_t leaf) { return (int32_t)(int16_t)le
 SRT_HD inline bool srtWfLeafHasSecond(int32_t leaf) { return (uint32_t)leaf >= 0x80010000u; }
 // the leaf word of the second object alone (only where srtWfLeafHasSecond)
 SRT_HD inline int32_t srtWfLeafRest(int32_t leaf) { return (int32_t)((((uint32_t)leaf >> 16) | 0x80000000u) + 1u); }
+
+// ---- the ELIDED walk sequence (srt_regroup.h srtRegroupWalk; tunable "wf_regroup" 2): the kept records of the regrouped
+// tree, numbered in pre-order, in the first slots of the same LDS copy.  Record j's two words, the same four kinds as above:
+//   n0.w   a gate: the record right behind it (the first kept record of its subtree: leaves are always kept);
+//          a leaf: its leaf word
+//   n1.w   the first kept record behind its subtree (`after`: its number, < 0: none), or SRT_WF_DONE
+// and a world item's entry word: the first kept record of its tree, or the bare primitive's root word.  srtWfRootWord leaves
+// an entry word as it is (a node's offset: itself; a single-object leaf word: the same word again), so a launch may hand
+// the entry words to the kernel in the world list's place.
+SRT_HD inline int32_t srtWfSeqHitWord(int32_t left, int32_t right, int32_t j) { return left >= 0 ? SRT_NODE_REF(j + 1) : srtWfLeafWord(left, right); }
+SRT_HD inline int32_t srtWfSeqMissWord(int32_t after) { return after >= 0 ? SRT_NODE_REF(after) : SRT_WF_DONE; }
+SRT_HD inline int32_t srtWfSeqEntryWord(int32_t ref, int32_t first) { return ref >= 0 ? SRT_NODE_REF(first) : srtWfRootWord(ref); }

@@ -51,7 +51,8 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
 TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetWfProfile", "srtGetLaunchInfo", "srtRenderAov",
                 "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
                 "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord", "srtTestGetSlabScene",
-                "srtTestRefinedRcp", "srtTestSlabVisit", "srtTestRegroup", "srtTestGetRegroup"]
+                "srtTestRefinedRcp", "srtTestSlabVisit", "srtTestRegroup", "srtTestGetRegroup",
+                "srtTestRegroupWalk", "srtTestGetRegroupWalk"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -173,6 +174,10 @@ if hasattr(lib, "srtTestRegroup"):  # (likewise: an SRT_HIP_LIB build from befor
     lib.srtTestRegroup.argtypes = [_vp, C.c_int32, _vp, C.c_int32, _vp]
     lib.srtTestRegroup.restype = C.c_int32
     lib.srtTestGetRegroup.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
+if hasattr(lib, "srtTestRegroupWalk"):  # (likewise: an SRT_HIP_LIB build from before the walk sequence)
+    lib.srtTestRegroupWalk.argtypes = [_vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]
+    lib.srtTestRegroupWalk.restype = C.c_int32
+    lib.srtTestGetRegroupWalk.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
 lib.srtRenderAov.argtypes =[_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
 lib.srtLastKernelMs.argtypes = [_vp, C.POINTER(C.c_float)]
 lib.srtGetStats.argtypes = [_vp, C.POINTER(abi.SrtStats)]
@@ -945,6 +950,20 @@ class Context:
         nodes, links = np.zeros((n.value, 8), np.float32), np.zeros(n.value, np.int32)
         self._check(lib.srtTestGetRegroup(self.h, nodes.ctypes.data, links.ctypes.data, n.value, C.byref(n)))
         return nodes, links
+
+    def regroup_walk(self):
+        """srtTestGetRegroupWalk (include/srt_hip_test.h): the uploaded scene's walk sequence as it lies in device memory now
+        -- (keep (nodes,) uint8, src (records,) int32, links (records, 2) int32: hit and miss word, entry (world items,)
+        int32) -- or None when the upload built none."""
+        n = C.c_int32(0)
+        self._check(lib.srtTestGetRegroupWalk(self.h, None, None, None, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        nodes = len(self.regroup()[0])
+        keep, src, links = np.zeros(nodes, np.uint8), np.zeros(nodes, np.int32), np.zeros((nodes, 2), np.int32)
+        entry = np.zeros(int(self._scene_keep[1].numWorld), np.int32)
+        self._check(lib.srtTestGetRegroupWalk(self.h, keep.ctypes.data, src.ctypes.data, links.ctypes.data, entry.ctypes.data, nodes, C.byref(n)))
+        return keep, src[:n.value].copy(), links[:n.value].copy(), entry
 
     def refined_rcp_test(self, first_bits, count):
         """srtTestRefinedRcp (include/srt_hip_test.h): the largest |refinedRcp(d) d - 1| (in double) over the float bit patterns
