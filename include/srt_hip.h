@@ -984,6 +984,7 @@ int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccl
  * srtPathStepDevice     srtTraceRaysDevice followed by srtScatterRaysDevice in ONE kernel: the form a loop should call (a
  *                       path does not write an 88-byte SrtHit to memory and read it back between the two halves).
  * srtCompactPathsDevice the entries that scattered, moved to the front between two steps (its own block below).
+ * srtTracePathsDevice   the whole loop in one kernel: the radiance of one path per ray (its own block below).
  *   buffers   all DEVICE pointers.  dRays, dRaysOut = SrtRay[n], aligned to 4 bytes.  dRng = uint64_t[n], aligned to 8:
  *             entry i is the generator state of path i (a PCG32 state: one 64-bit LCG step and an XSH-RR output per 32-bit
  *             draw; a float draw is float(u32) * 2^-32, clamped below 1).  Each entry reads it, advances it by exactly the
@@ -1053,6 +1054,47 @@ int srtScatterRaysDevice(SrtContext* ctx, const void* dRays, const void* dRecord
                          void* dRaysOut, void* stream);
 int srtPathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays, int64_t n, const void* dActive, void* dRng,
                       void* dOut, void* dRaysOut, void* dHits, void* stream);
+
+/* srtTracePathsDevice     "the loop" above in ONE kernel: here are rays on the device, give me their path-traced radiance.
+ *                         A lane carries a path from its first ray to its end, unwinds it and takes the next entry from
+ *                         a counter: nothing passes through memory between bounces, no count is read back, and waves
+ *                         are refilled without a compaction pass.
+ *   per entry the path of "the loop" that starts at dRays[i] with the state dRng[i]: at most maxBounce steps of
+ *             srtPathStepDevice(traversal), each on the scattered ray of the step before.  The terminal radiance is
+ *             `background` after MISS, `emitted` after ENDED and 0 after INVALID or when every step scattered; it is
+ *             unwound L = 0.0f + L * attenuation_j per channel (a separate multiply and add), innermost first.
+ *             dResult[i] = {L, the number of steps that ran, the status of the last one}; dRng[i] = the state after the
+ *             path's last draw.  dRays is only read.  With FAITHFUL steps and the rays of srtCameraRaysDevice, a pixel's
+ *             float running sum of its samples' L in sample-index order is srtRenderImage's accumulation buffer bit for
+ *             bit, as for the loop.
+ *   buffers   all DEVICE pointers but `background`.  dRays = SrtRay[n], aligned to 4; dRng = uint64_t[n], aligned to 8;
+ *             dResult = SrtPathRadiance[n], aligned to 16.  background: a HOST pointer to 3 floats, read during the call.
+ *             maxBounce in [0, SRT_MAX_BOUNCE]; with 0 no step runs and every entry is {0, 0, SRT_PATH_SCATTERED}.
+ *   scratch   dScratch, SRT_PATHS_SCRATCH_BYTES bytes aligned to 8, is the caller's.  The call zeroes it on `stream` itself,
+ *             with a memset ahead of the kernel; its contents afterwards are unspecified.  Two calls on one stream may
+ *             share it; calls on different streams need one each.
+ *   async     on `stream`: one memset and one kernel, in which no wave waits for another one.  Allocates nothing, does not
+ *             synchronise, touches no scratch of the context's, and leaves the tunables, the host generator, the chunk
+ *             scratch, srtLastKernelMs, srtGetLaunchInfo, srtGetStats and the temporal history as they were.
+ *   never written  elements at index >= n; anything outside the SRT_PATHS_SCRATCH_BYTES of scratch.
+ *   n == 0    returns 0 and launches nothing.
+ *   FAITHFUL and CLOSEST have the meanings, the tie rule and the conditions of "Ray queries" above: for a ray that is not
+ *             finite the result is unspecified, but the call still terminates and writes element i only.
+ *   errors    (non-zero, message in srtLastError, NOTHING launched, outputs untouched; all decided on the host) no scene
+ *             uploaded; geometry updated and not yet refitted; n < 0; a traversal that is neither value; maxBounce outside
+ *             [0, SRT_MAX_BOUNCE]; a NULL background; with n > 0 a NULL or misaligned dRays (4), dRng (8), dResult (16) or
+ *             dScratch (8); an overlap of dResult, dScratch or dRng with one another or with dRays, each taken at its
+ *             full length (range comparison, as srtCompactPathsDevice's); a tree so deep that the kernel's LDS -- 1 KB per
+ *             pending reference as for the queries, and 3 KB per bounce of maxBounce -- exceeds 160 KB. */
+enum { SRT_PATHS_SCRATCH_BYTES = 64 };
+typedef struct SrtPathRadiance { /* 16 bytes, aligned to 16: one dwordx4 store */
+  float radiance[3];             /* L of "the loop" above */
+  int16_t steps;                 /* steps that ran: 0 .. maxBounce */
+  int16_t status;                /* SRT_PATH_* of the last step that ran; SRT_PATH_SCATTERED: the bounce limit ended the path
+                                    (also when maxBounce == 0 and no step ran) */
+} SrtPathRadiance;
+int srtTracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float background[3],
+                        const void* dRays, int64_t n, void* dRng, void* dResult, void* dScratch, void* stream);
 
 /* srtCompactPathsDevice   stable compaction of the live paths between two steps: the entries that go on move, in their
  *                         order, to the front of fresh ray, state and slot buffers, so that the next step runs on full

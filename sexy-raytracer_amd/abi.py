@@ -18,6 +18,8 @@ SRT_NO_HIT = -1
 # path steps on device buffers (srtScatterRaysDevice / srtPathStepDevice): SrtPathOut.status
 SRT_PATH_INVALID, SRT_PATH_MISS, SRT_PATH_ENDED, SRT_PATH_SCATTERED = -1, 0, 1, 2
 SRT_COMPACT_TILE = 1024  # entries per tile of srtCompactPathsDevice: its scratch is one 64-bit word per tile
+SRT_MAX_BOUNCE = 16  # the largest maxBounce of a render and of srtTracePathsDevice
+SRT_PATHS_SCRATCH_BYTES = 64  # srtTracePathsDevice: the caller's scratch (the counter lanes take their entries from)
 # feature planes (srtRenderFeatureTiles / srtRenderFeatureImage): bit 1 << k selects plane k
 SRT_FEATURE_ALBEDO, SRT_FEATURE_NORMAL, SRT_FEATURE_POSITION, SRT_FEATURE_DEPTH = 1, 2, 4, 8
 SRT_FEATURE_ALL = 15
@@ -112,6 +114,10 @@ class SrtPathOut(C.Structure):  # srtScatterRaysDevice / srtPathStepDevice: 32 b
     _fields_ = [("attenuation", f32 * 3), ("status", i32), ("emitted", f32 * 3), ("prim", i32)]
 
 
+class SrtPathRadiance(C.Structure):  # srtTracePathsDevice: 16 bytes per entry
+    _fields_ = [("radiance", f32 * 3), ("steps", C.c_int16), ("status", C.c_int16)]
+
+
 class SrtRenderParams(C.Structure):
     _fields_ = [("imageWidth", i32), ("imageHeight", i32), ("spp", i32), ("maxBounce", i32),
                 ("seed", u64), ("background", f32 * 3), ("tMin", f32), ("traversal", i32),
@@ -161,6 +167,8 @@ HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("normal",
 RAY_HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("material", "<i4"), ("frontFace", "<i4")])
 PATH_OUT_DTYPE = np.dtype([("attenuation", "<f4", 3), ("status", "<i4"), ("emitted", "<f4", 3), ("prim", "<i4")])
 assert PATH_OUT_DTYPE.itemsize == C.sizeof(SrtPathOut) == 32
+PATH_RADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("steps", "<i2"), ("status", "<i2")])
+assert PATH_RADIANCE_DTYPE.itemsize == C.sizeof(SrtPathRadiance) == 16
 AOV_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("time", "<f4"), ("valid", "<i4"), ("prim", "<i4"), ("t", "<f4"),
                       ("nodeVisits", "<i4"), ("boxPasses", "<i4"), ("triTests", "<i4"), ("sphereTests", "<i4"), ("pad", "<i4", 2)])
 assert AOV_DTYPE.itemsize == 64

@@ -107,6 +107,11 @@ const TunableName kTunables[] = {
     // records, the exact test for the lanes they cannot decide (srt_tri_hit.h): the kernels over an LDS-resident tree and
     // srtTraceRays.  0 = every test is the exact one.  The image, t and every counter are the same either way.
     {"tri_cert", "SRT_TRI_CERT", &Tunables::triCert, 1},
+    // srtTracePathsDevice (srt_paths.hip): a wave claims entries for its idle lanes when at least this many are idle, 1..64
+    // (a wave that is idle altogether always does).  16 = a quarter of the wave: fewer atomics, and fresh coherent rays are
+    // not mixed one by one into a wave of bounced ones; 1 = on every trip, 3-14 % slower on the mesh and 0.6 % faster on
+    // the soup.  The radiance does not depend on it.  Read at every call.
+    {"paths_refill_min", "SRT_PATHS_REFILL_MIN", &Tunables::pathsRefillMin, 16},
 };
 
 // DevScene::triWMax for the tunable "tri_cert": the certificate's overflow guard, or 0 = nothing is certified

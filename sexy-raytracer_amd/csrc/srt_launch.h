@@ -55,6 +55,22 @@ struct CompactArgs {
 };
 int srt_launch_compact(const CompactArgs* a, int grid, hipStream_t stream);
 
+// srt_paths.hip (srtTracePathsDevice): one memset of the counter and ONE persistent kernel on the stream.  The grid is
+// the smaller of ceil(n / SRT_BLOCK) and numCUs * the workgroups of the kernel a CU holds at ldsBytes of dynamic LDS
+// (srtPathsLdsBytes); no workgroup waits for another one, so a grid the device holds only in part is merely slower.
+struct TracePathsArgs {
+  DevScene scene;
+  const float* rays;            // SrtRay[n]: read only
+  uint64_t* rng;                // Pcg::state per entry: read when an entry is claimed, written when its path ends
+  int4* result;                 // SrtPathRadiance[n]
+  unsigned long long* counter;  // the next entry to claim: the first word of the caller's scratch, zeroed by the memset
+  float background[3];
+  int32_t maxBounce;
+  int32_t refillMin;            // idle lanes of a wave before it claims entries, 1..64 (tunable paths_refill_min)
+  int64_t n;
+};
+int srt_launch_paths(const TracePathsArgs* a, int traversal, int numCUs, size_t ldsBytes, size_t scratchBytes, hipStream_t stream);
+
 // srt_lbvh.hip: the device tree builders (blocking) and the closest-hit traversal's pair records
 int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,
                    uint8_t* outAxis, int base, int* depthOut);

@@ -73,6 +73,10 @@ SRT_HD inline SrtStackFormLayout srtStackFormLayout(int stackDepth, int maxBounc
 // srt_query.hip and srt_pathstep.hip (srt_query_walk.h): slot 0 holds the walk's sentinel, the last slot is the spare of its
 // unconditional store
 SRT_HD inline size_t srtQueryStackBytes(int stackDepth) { return (size_t)((stackDepth > 1 ? stackDepth : 1) + 2) * SRT_BLOCK * sizeof(int32_t); }
+// srt_paths.hip: the same walk's slots, then the attenuations of a path's scattered steps [3 * level + channel][thread]
+SRT_HD inline size_t srtPathsLdsBytes(int stackDepth, int maxBounce) {
+  return srtQueryStackBytes(stackDepth) + (size_t)3 * (maxBounce > 0 ? maxBounce : 0) * SRT_BLOCK * sizeof(float);
+}
 // the stack walk of the feature and motion passes and of srtTraceRays (srt_path.h traverse): stackDepth slots
 SRT_HD inline size_t srtTraverseStackBytes(int stackDepth) { return (size_t)(stackDepth > 1 ? stackDepth : 1) * SRT_BLOCK * sizeof(int32_t); }
 // ... which the passes leave for the stackless walk over the whole tree in LDS where that fits

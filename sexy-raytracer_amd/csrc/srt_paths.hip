@@ -1,0 +1,154 @@
+// srt_paths.hip -- whole paths for the rays of a device buffer in ONE kernel (srtTracePathsDevice; include/srt_hip.h "Path
+// steps on device buffers"): a lane carries a path from its first ray to its end, keeps the attenuations of its
+// scattered steps on a per-lane LDS stack, unwinds them in the reference's order, writes the radiance and takes the next
+// entry from a counter.  Nothing passes through memory between bounces and nothing is read back by the host.
+//
+// Persistent, 256 threads, and no wave ever waits for another wave or workgroup: no spin, no flag, no barrier.  The one
+// thing waves share is the 64-bit counter of the next unclaimed entry (the first word of the caller's scratch, zeroed on
+// the stream ahead of the launch).  At the top of a trip the idle lanes of a wave claim entries together, once there are
+// refillMin of them (a quarter of the wave as shipped): one relaxed agent-scope atomic add of their number
+// by one lane, the base broadcast, base + the lane's rank among the idle lanes (srt_compact.hip's ballot / mbcnt idiom)
+// as the lane's entry.  The lanes of a claim hold consecutive entries, so the ray loads of a fresh wave coalesce as the
+// step kernel's do.  The kernel ends because the counter only grows and every path makes at most maxBounce steps.
+//
+// One trip is srt_pathstep.hip's step body on the lane's registers -- queryWalk, the record, the material-range check,
+// shade() -- and nothing of it is restated here.  LDS per workgroup: the walk's [slot][thread] stack (stackDepth + 2
+// slots), then the attenuations [3 * level + channel][thread], 3 * maxBounce slots of the call's own maxBounce
+// (srt_lds_layout.h srtPathsLdsBytes).  DESIGN.md 5.20.
+
+#include <algorithm>
+
+#include "srt_path.h"
+#include "srt_query_walk.h"
+#include "srt_step_rays.h"
+#include "srt_lds_layout.h"
+#include "srt_launch.h"
+
+namespace {
+
+constexpr int WAVE = 64;
+
+// SrtPathRadiance: one dwordx4 store; steps in the low half of the last dword, the status in its high half
+__device__ __forceinline__ void storeRadiance(int4* out, V3 L, int steps, int status) {
+  *out = make_int4(__float_as_int(L.x), __float_as_int(L.y), __float_as_int(L.z), (int)(((uint32_t)status << 16) | ((uint32_t)steps & 0xffffu)));
+}
+
+// MODE: Q_FAITHFUL or Q_CLOSEST
+template <int MODE>
+__global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const TracePathsArgs a) {
+  extern __shared__ int32_t lds[];
+  const DevScene& sc = a.scene;
+  const QueryWalk walk = queryWalkSetup<MODE>(sc, lds);  // [slot][thread]: stackDepth + 2 slots
+  float* const attStack = reinterpret_cast<float*>(lds) + srtQueryStackBytes(sc.stackDepth) / sizeof(int32_t) + threadIdx.x;
+  const Rsrc rsTexels = makeRsrc(sc.texels, sc.texelBytes);
+  const V3 zero = mk(0.0f, 0.0f, 0.0f), background = mk(a.background[0], a.background[1], a.background[2]);
+  const int lane = threadIdx.x & (WAVE - 1);
+  // the lane's path: its entry, the ray of its next step, the generator, the scattered steps so far
+  int64_t i = 0;
+  Ray r;
+  r.o = r.d = zero;
+  r.time = 0.0f;
+  float tMin = 0.0f, tMax = 0.0f;
+  Pcg rng;
+  rng.state = 0;
+  int depth = 0;
+  bool have = false;
+  bool dry = false;  // the counter has passed n: nothing is left to claim (the same in every lane of the wave)
+  while (true) {
+    // ---- refill: every lane of the wave is here, whatever it did in the trip before
+    const unsigned long long idle = __ballot(!have);
+    const int numIdle = __popcll(idle);
+    if (!dry && numIdle >= a.refillMin) {  // refillMin <= 64: a wave that is idle altogether always claims
+      unsigned long long base = 0;
+      if (lane == 0) base = __hip_atomic_fetch_add(a.counter, (unsigned long long)numIdle, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t first = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                             (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)base);
+      dry = first + (uint64_t)numIdle >= (uint64_t)a.n;
+      const int64_t mine = (int64_t)first + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+      if (!have && mine < a.n) {  // a lane whose index lies behind the last entry stays idle for good
+        i = mine;
+        loadRay(a.rays + 9 * i, r, tMin, tMax);
+        rng.state = a.rng[i];
+        depth = 0;
+        have = a.maxBounce > 0;
+        if (!have) storeRadiance(a.result + i, zero, 0, SRT_PATH_SCATTERED);  // no step runs: black, the state as it was
+      }
+    }
+    if (__ballot(have) == 0) {
+      if (dry) break;
+      continue;
+    }
+    // ---- one step of every lane that has a path: srt_path_step_kernel's body
+    if (have) {
+      float closest;
+      bool found;
+      const int hitRef = queryWalk<MODE>(sc, walk, r, tMin, tMax, closest, found);
+      V3 L = background;  // the terminal radiance, should the path end here
+      int status = SRT_PATH_MISS;
+      bool goOn = false;
+      if (hitRef != SRT_REF_DONE) {
+        Record rec;
+        const int pr = ~hitRef;
+        if (pr & 1)
+          sphereRecord(sc, pr >> 1, r, closest, rec, false);
+        else
+          triRecord(sc, pr >> 1, r, closest, rec, false);
+        L = zero;
+        status = SRT_PATH_INVALID;
+        if (!(rec.material >= sc.numMaterials)) {
+          V3 att = zero, emitted;
+          Ray next;
+          next.d = zero;
+          uint32_t fetches = 0;
+          if (shade<false, STEP_WIDE>(sc, rsTexels, r, rec, rng, att, next, emitted, fetches)) {
+            attStack[(3 * depth + 0) * SRT_BLOCK] = att.x;  // depth < maxBounce: a path at the limit has ended
+            attStack[(3 * depth + 1) * SRT_BLOCK] = att.y;
+            attStack[(3 * depth + 2) * SRT_BLOCK] = att.z;
+            r = next;
+            depth++;
+            status = SRT_PATH_SCATTERED;
+            goOn = depth < a.maxBounce;  // out of bounces: black, through every attenuation (main.cpp:36-37)
+          } else {
+            status = SRT_PATH_ENDED;
+            L = emitted;
+          }
+        }
+      }
+      if (!goOn) {
+        const int steps = depth + (status != SRT_PATH_SCATTERED ? 1 : 0);
+        // unwind the recursion: emitted + newColor * attenuation with emitted = 0, innermost first (main.cpp:49-51)
+        for (int j = depth - 1; j >= 0; --j) {
+          const float ax = attStack[(3 * j + 0) * SRT_BLOCK], ay = attStack[(3 * j + 1) * SRT_BLOCK], az = attStack[(3 * j + 2) * SRT_BLOCK];
+          L = mk(0.0f + L.x * ax, 0.0f + L.y * ay, 0.0f + L.z * az);
+        }
+        storeRadiance(a.result + i, L, steps, status);
+        a.rng[i] = rng.state;  // one 8-byte store: the state after the path's last draw
+        have = false;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// traversal: SRT_TRAVERSE_FAITHFUL or SRT_TRAVERSE_CLOSEST; ldsBytes: srtPathsLdsBytes; scratchBytes: what the memset
+// clears from a->counter on
+int srt_launch_paths(const TracePathsArgs* a, int traversal, int numCUs, size_t ldsBytes, size_t scratchBytes, hipStream_t stream) {
+  void (*kernel)(const TracePathsArgs) = traversal == SRT_TRAVERSE_CLOSEST ? srt_paths_kernel<Q_CLOSEST> : srt_paths_kernel<Q_FAITHFUL>;
+  if (ldsBytes > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  // the workgroups that are resident at once: more would only queue behind them and find the counter run out
+  int perCU = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, SRT_BLOCK, ldsBytes) != hipSuccess || perCU < 1) perCU = 1;
+  const int grid = (int)std::min<int64_t>((a->n + SRT_BLOCK - 1) / SRT_BLOCK, (int64_t)numCUs * perCU);
+  const hipError_t e = hipMemsetAsync(a->counter, 0, scratchBytes, stream);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SRT_BLOCK), ldsBytes, stream, *a);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

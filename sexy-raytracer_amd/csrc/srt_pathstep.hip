@@ -11,29 +11,11 @@
 
 #include "srt_path.h"
 #include "srt_query_walk.h"
+#include "srt_step_rays.h"
 #include "srt_launch.h"
 
 namespace {
 
-// The instance of shade() these kernels run: one texel lookup after the other.  With all four in flight (WIDE) the step
-// kernel takes 81 vector registers, one past the 80 that still fit six waves per SIMD; this instance takes 78 (`make
-// resource-usage`).  Both instances compute the same bits (tests/test_shading.py).
-constexpr bool STEP_WIDE = false;
-
-__device__ __forceinline__ void loadRay(const float* in, Ray& r, float& tMin, float& tMax) {
-  r.o = mk(in[0], in[1], in[2]);  // nine dword loads 36 bytes apart per lane
-  r.d = mk(in[3], in[4], in[5]);
-  r.time = in[6];
-  tMin = in[7];
-  tMax = in[8];
-}
-__device__ __forceinline__ void storeRay(float* out, const Ray& r, float tMin, float tMax) {
-  out[0] = r.o.x; out[1] = r.o.y; out[2] = r.o.z;
-  out[3] = r.d.x; out[4] = r.d.y; out[5] = r.d.z;
-  out[6] = r.time;
-  out[7] = tMin;
-  out[8] = tMax;
-}
 // SrtPathOut: two dwordx4 stores
 __device__ __forceinline__ void storeOut(int4* out, V3 att, int status, V3 emitted, int prim) {
   out[0] = make_int4(__float_as_int(att.x), __float_as_int(att.y), __float_as_int(att.z), status);

@@ -24,6 +24,7 @@ struct Tunables {
   int wfRegroup;
   int denoiseLdsStep;
   int triCert;
+  int pathsRefillMin;
 };
 
 // What the planner reads of the uploaded scene (DevScene)

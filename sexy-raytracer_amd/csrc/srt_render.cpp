@@ -599,6 +599,62 @@ int srtCompactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const vo
                                       dScratch, stream));
 }
 
+// srtTracePathsDevice: every check on the host, then srt_paths.hip's memset and its one kernel on the caller's stream.
+// Nothing of the context changes.
+static int tracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float* background, const void* dRays, int64_t n,
+                            void* dRng, void* dResult, void* dScratch, void* streamPtr) {
+  const char* what = "srtTracePathsDevice";
+  if (!ctx) return 1;
+  if (checkSceneReady(ctx, what)) return 1;
+  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
+  if (traversal != SRT_TRAVERSE_FAITHFUL && traversal != SRT_TRAVERSE_CLOSEST)
+    return fail(ctx, "%s: traversal %d is neither SRT_TRAVERSE_FAITHFUL nor SRT_TRAVERSE_CLOSEST", what, traversal);
+  if (maxBounce < 0 || maxBounce > SRT_MAX_BOUNCE) return fail(ctx, "%s: maxBounce = %d is outside [0, %d]", what, maxBounce, SRT_MAX_BOUNCE);
+  if (!background) return fail(ctx, "%s: null background", what);
+  if (n == 0) return 0;
+  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "rng states", dRng, 8) ||
+      checkPointer(ctx, what, "results", dResult, 16) || checkPointer(ctx, what, "scratch", dScratch, 8))
+    return 1;
+  // what the kernel writes may overlap nothing else it reads or writes (srtCompactPathsDevice's range comparison)
+  struct Range {
+    const char* name;
+    uintptr_t at;
+    uint64_t bytes;
+  };
+  const uint64_t un = (uint64_t)n;
+  const Range ranges[] = {{"rays", (uintptr_t)dRays, 36 * un},  // read only: compared with the three written ones
+                          {"rng states", (uintptr_t)dRng, 8 * un},
+                          {"results", (uintptr_t)dResult, 16 * un},
+                          {"scratch", (uintptr_t)dScratch, SRT_PATHS_SCRATCH_BYTES}};
+  for (int w = 1; w < 4; ++w)
+    for (int r = 0; r < w; ++r)
+      if (ranges[w].at < ranges[r].at + ranges[r].bytes && ranges[r].at < ranges[w].at + ranges[w].bytes)
+        return fail(ctx, "%s: the %s overlap the %s", what, ranges[w].name, ranges[r].name);
+  const DevScene& sc = ctx->upload.scene;
+  const size_t lds = srtPathsLdsBytes(sc.stackDepth, maxBounce);
+  if (lds > SRT_LDS_BYTES)
+    return fail(ctx, "%s: BVH depth %d and %d bounces need %zu B of LDS per workgroup", what, sc.stackDepth, maxBounce, lds);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  TracePathsArgs a;
+  a.scene = sc;
+  a.rays = static_cast<const float*>(dRays);
+  a.rng = static_cast<uint64_t*>(dRng);
+  a.result = static_cast<int4*>(dResult);
+  a.counter = static_cast<unsigned long long*>(dScratch);
+  for (int c = 0; c < 3; ++c) a.background[c] = background[c];
+  a.maxBounce = maxBounce;
+  a.refillMin = std::min(std::max(ctx->tun.pathsRefillMin, 1), 64);
+  a.n = n;
+  const int e = srt_launch_paths(&a, traversal, ctx->prop.multiProcessorCount, lds, SRT_PATHS_SCRATCH_BYTES, static_cast<hipStream_t>(streamPtr));
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+int srtTracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float background[3], const void* dRays, int64_t n,
+                        void* dRng, void* dResult, void* dScratch, void* stream) {
+  SRT_GUARDED(ctx, tracePathsDevice(ctx, traversal, maxBounce, background, dRays, n, dRng, dResult, dScratch, stream));
+}
+
 int srtCameraRaysDevice(SrtContext* ctx, const SrtRenderParams* p, const void* dPixelSample, int64_t n, void* dRays, void* dRng,
                         void* stream) {
   SRT_GUARDED(ctx, cameraRaysDevice(ctx, p, dPixelSample, n, dRays, dRng, stream));

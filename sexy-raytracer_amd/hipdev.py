@@ -34,7 +34,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtTraceRaysDevice", "srtOccludedDevice", "srtScatterRays",
            "srtRngKey", "srtCameraRaysDevice", "srtScatterRaysDevice", "srtPathStepDevice",
-           "srtCompactPathsScratchBytes", "srtCompactPathsDevice",
+           "srtCompactPathsScratchBytes", "srtCompactPathsDevice", "srtTracePathsDevice",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
@@ -143,6 +143,7 @@ lib.srtPathStepDevice.argtypes = [_vp, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp,
 lib.srtCompactPathsScratchBytes.argtypes = [C.c_int64]
 lib.srtCompactPathsScratchBytes.restype = C.c_int64
 lib.srtCompactPathsDevice.argtypes = [_vp, C.c_int64] + [_vp] * 12
+lib.srtTracePathsDevice.argtypes = [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), _vp, C.c_int64, _vp, _vp, _vp, _vp]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
 lib.srtGatherTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
@@ -888,6 +889,33 @@ class Context:
     def compact_scratch_bytes(n):
         """srtCompactPathsScratchBytes: 8 bytes per tile of abi.SRT_COMPACT_TILE entries, 0 for n <= 0."""
         return int(lib.srtCompactPathsScratchBytes(int(n)))
+
+    def trace_paths_device(self, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_CLOSEST, scratch=None, stream=None):
+        """srtTracePathsDevice: the path-traced radiance of every ray of a DEVICE tensor in one kernel, asynchronous on
+        `stream` -- at most max_bounce steps of path_step_device per ray, each on the scattered ray of the step before,
+        then the unwinding; no tensor per bounce and no count read back.  rays: float32 (n, 9), only read; rng: int64 (n,),
+        the generator states, advanced IN PLACE to the state after each path's last draw; background: three floats, the
+        radiance of a ray that leaves the scene; scratch: a uint8 tensor of at least abi.SRT_PATHS_SCRATCH_BYTES bytes
+        (allocated when None; calls on one stream may share one).  Returns an int32 tensor (n, 4) laid out as
+        SrtPathRadiance: columns 0..2 viewed as float32 are the radiance, column 3 holds the number of steps that ran in
+        its low 16 bits and the last step's abi.SRT_PATH_* status in its high 16 (result.view(torch.int16)[:, 6] and
+        [:, 7]; SCATTERED: the bounce limit ended the path)."""
+        import torch
+        rays = self._device_rays(rays)
+        n = rays.shape[0]
+        rng = self._device_tensor(rng, "rng", "int64", (n,), rays)
+        if scratch is None:
+            scratch = torch.empty((abi.SRT_PATHS_SCRATCH_BYTES,), dtype=torch.uint8, device=rays.device)
+        else:
+            scratch = self._device_tensor(scratch, "scratch", "uint8", (-1,), rays)
+            if scratch.shape[0] < abi.SRT_PATHS_SCRATCH_BYTES:
+                raise ValueError("scratch must hold %d bytes, not %d" % (abi.SRT_PATHS_SCRATCH_BYTES, scratch.shape[0]))
+        bg = (C.c_float * 3)(*[float(c) for c in background])
+        result = torch.empty((n, 4), dtype=torch.int32, device=rays.device)
+        ptr = (lambda t: t.data_ptr()) if n else (lambda t: None)
+        self._check(lib.srtTracePathsDevice(self.h, int(traversal), int(max_bounce), bg, ptr(rays), n, ptr(rng), ptr(result),
+                                            ptr(scratch), self._stream_handle(stream)))
+        return result
 
     def scatter_test(self, rays, hits, seed):
         rays = np.ascontiguousarray(rays, abi.RAY_DTYPE)

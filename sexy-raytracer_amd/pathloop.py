@@ -12,15 +12,19 @@ _DEAD = -2  # a status no step writes: an entry that was not active in this step
 
 
 def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_FAITHFUL, fused=True, stream=None,
-                    active_counts=None, compact=False):
+                    active_counts=None, compact=False, whole=False):
     """The radiance of one path per ray: at most max_bounce steps, then the unwinding.  rays (n, 9) float32 and rng (n,)
     int64 as Context.camera_rays_device returns them; both are overwritten.  fused: one path_step_device per bounce;
     otherwise trace_device(records=True) + scatter_device, which compute the same bytes through an 88-byte record per ray.
     active_counts: a list that receives, per bounce, the number of entries still on their way (a 0-dim tensor: reading it
     synchronises, so read it after the loop).  compact: every bounce after the first runs on the live entries alone,
-    moved to the front by Context.compact_paths_device (_sample_radiance_compact below): the same bits.  Returns (n, 3)
-    float32."""
+    moved to the front by Context.compact_paths_device (_sample_radiance_compact below): the same bits.  whole: no loop
+    at all -- one Context.trace_paths_device call carries every path from its ray to its radiance in one kernel (the same
+    bits again; rays is then only read, and there are no per-bounce counts to report).  Returns (n, 3) float32."""
     import torch
+    if whole:
+        _check_whole(fused, compact, active_counts)
+        return ctx.trace_paths_device(rays, rng, max_bounce, background, traversal, stream=stream).view(torch.float32)[:, 0:3]
     if compact:
         return _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts)
     n = rays.shape[0]
@@ -101,13 +105,27 @@ def _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, 
     return inner if inner is not None else torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
 
 
+def _check_whole(fused, compact, active_counts):
+    """whole=True has no bounces of its own to fuse, to compact between or to count."""
+    if not fused:
+        raise ValueError("whole=True runs one kernel per batch: fused=False does not apply")
+    if compact:
+        raise ValueError("whole=True refills its waves itself: compact=True does not apply")
+    if active_counts is not None:
+        raise ValueError("whole=True reads no count per bounce: active_counts does not apply")
+
+
 def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples_per_batch=None, device=None, active_counts=None,
-           compact=False):
+           compact=False, whole=False):
     """params.spp samples of every pixel from params.sampleFirst on, through the device path steps: the (H, W, 4) float32
     torch tensor of per-pixel radiance sums (the float running sum in sample-index order) with the sample count in w --
     Context.render_image's accumulation buffer.  samples_per_batch: how many sample indices of the whole frame go through
-    the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  compact: sample_radiance's.  Runs on torch's current stream."""
+    the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  compact: sample_radiance's.
+    whole: a batch is one Context.trace_paths_device call (15 words per entry whatever maxBounce is) followed by the same
+    running sum; not together with active_counts, compact or fused=False.  Runs on torch's current stream."""
     import torch
+    if whole:
+        _check_whole(fused, compact, active_counts)
     device = torch.device("cuda" if device is None else device)
     W, H, spp = params.imageWidth, params.imageHeight, params.spp
     pixels = W * H
@@ -123,7 +141,8 @@ def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples
                                         torch.arange(params.sampleFirst + first, params.sampleFirst + first + count, dtype=torch.int32,
                                                      device=device).repeat_interleave(pixels)), dim=1).contiguous()
             rays, rng = ctx.camera_rays_device(params, pixel_sample, stream=stream)
-            radiance = sample_radiance(ctx, rays, rng, params.maxBounce, params.background, traversal, fused, stream, active_counts, compact)
+            radiance = sample_radiance(ctx, rays, rng, params.maxBounce, params.background, traversal, fused, stream, active_counts, compact,
+                                       whole)
             for k in range(count):
                 image[:, 0:3] += radiance[k * pixels:(k + 1) * pixels]
         image[:, 3] = float(spp)

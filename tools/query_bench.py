@@ -17,7 +17,10 @@ through the only entry there was, not a kernel comparison.
 srtRenderTiles on masterchief (reference tree FAITHFUL, PLOC tree CLOSEST) and soup_200k (PLOC, CLOSEST), 4 and 16 spp,
 4 bounces, with the active share of the entries per bounce; the same two loops with the live set compacted between bounces
 (compact=True) alternate with them, and `compact_call` is one srtCompactPathsDevice call behind the first bounce of the
-whole batch (rays, states and slots moved), timed with events like the queries above.
+whole batch (rays, states and slots moved), timed with events like the queries above.  `whole` is the same frame through
+srtTracePathsDevice (whole=True: one kernel per batch) as the library ships it -- a wave claims entries once a quarter of it
+is idle (tunable paths_refill_min 16) -- and `whole_refill1` with a refill on every trip; `peak_mb` is torch's peak
+allocation over one frame of `whole` and of the compacted fused loop.
 
 usage: python tools/query_bench.py [--steps 200] [--warmup 5] [--host-steps 3] [--cases masterchief,soup_200k,soup_1m] [--ao-rays 4]
                                    [--ao-radius 0.1] [--ao-png FILE] [--width 1280] [--height 720]
@@ -160,6 +163,7 @@ def path_loop(a):
              ("masterchief_ploc_closest", "masterchief", abi.SRT_BUILDER_PLOC, abi.SRT_TRAVERSE_CLOSEST),
              ("soup_200k_ploc_closest", "soup_200k", None, abi.SRT_TRAVERSE_CLOSEST)]
     stream = torch.cuda.current_stream()
+    refill_default = ctx.get_tunable("paths_refill_min")
     for label, case, builder, traversal in cases:
         if case not in a.cases.split(","):
             continue
@@ -174,10 +178,17 @@ def path_loop(a):
         out = {"bvh_depth": ctx.bvh_depth()}
         for spp in (4, 16):
             p = abi.default_render_params(W, H, spp, bounces, seed=1, traversal=traversal)
+
+            def whole(refill_min):
+                ctx.set_tunable("paths_refill_min", refill_min)
+                return pathloop.render(ctx, p, traversal=traversal, whole=True)
+
             variants = {"fused": lambda: pathloop.render(ctx, p, fused=True, traversal=traversal),
                         "unfused": lambda: pathloop.render(ctx, p, fused=False, traversal=traversal),
                         "fused_compact": lambda: pathloop.render(ctx, p, fused=True, traversal=traversal, compact=True),
                         "unfused_compact": lambda: pathloop.render(ctx, p, fused=False, traversal=traversal, compact=True),
+                        "whole": lambda: whole(refill_default),
+                        "whole_refill1": lambda: whole(1),
                         "render_tiles": lambda: ctx.render_tiles(p, tiles.data_ptr(), stream.cuda_stream)}
             ms = {k: [] for k in variants}
             for rep in range(a.warmup_loops + a.loop_reps):
@@ -197,8 +208,18 @@ def path_loop(a):
                 med = float(np.median(v))
                 entry[name] = {"ms": med, "spread_ms": [min(v), max(v)], "msamples_s": W * H * spp / med * 1e-3}
             entry["compact_call"] = compact_call(ctx, p, traversal, a.steps, a.warmup)
+            entry["peak_mb"] = {}
+            for name in ("whole", "fused_compact"):
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                variants[name]()
+                torch.cuda.synchronize()
+                entry["peak_mb"][name] = (torch.cuda.max_memory_allocated() - before) / 2.0 ** 20
             out["spp_%d" % spp] = entry
         result["cases"][label] = out
+    ctx.set_tunable("paths_refill_min", refill_default)
     ctx.close()
     print(json.dumps(result))
 
