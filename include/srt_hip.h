@@ -984,8 +984,9 @@ int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccl
  * srtPathStepDevice     srtTraceRaysDevice followed by srtScatterRaysDevice in ONE kernel: the form a loop should call (a
  *                       path does not write an 88-byte SrtHit to memory and read it back between the two halves).
  * srtCompactPathsDevice the entries that scattered, moved to the front between two steps (its own block below).
+ * srtSortPathsDevice    the same entries, ordered by origin cell and direction octant (its own block below).
  * srtTracePathsDevice   the whole loop in one kernel: the radiance of one path per ray (its own block below).
- *   buffers   all DEVICE pointers.  dRays, dRaysOut = SrtRay[n], aligned to 4 bytes.  dRng = uint64_t[n], aligned to 8:
+ *   buffers  all DEVICE pointers.  dRays, dRaysOut = SrtRay[n], aligned to 4 bytes.  dRng = uint64_t[n], aligned to 8:
  *             entry i is the generator state of path i (a PCG32 state: one 64-bit LCG step and an XSH-RR output per 32-bit
  *             draw; a float draw is float(u32) * 2^-32, clamped below 1).  Each entry reads it, advances it by exactly the
  *             draws its work makes, and writes it back.  dOut = SrtPathOut[n], aligned to 16.  dRecords = SrtHit[n],
@@ -1140,6 +1141,57 @@ int64_t srtCompactPathsScratchBytes(int64_t n);
 int srtCompactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const void* dActive, const void* dRays, const void* dRng,
                           const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut, void* dActiveOut, void* dCount,
                           void* dScratch, void* stream);
+
+/* srtSortPathsDevice      srtCompactPathsDevice with an order: the entries that go on move to the front of fresh ray, state
+ *                         and slot buffers, ordered by the cell of a grid their origin lies in and by the octant their
+ *                         direction points into, so that the lanes of a wave of the next step ask for neighbouring parts
+ *                         of the tree.  Sorting moves bytes: nothing that reaches a pixel is computed, and a loop that
+ *                         sorts between its steps renders the same bits.  Compaction is the case of one key for all.
+ *   keep      srtCompactPathsDevice's keep[i], except that dOut and dActive may BOTH be NULL: every entry is then kept
+ *             (the form for a batch of shadow or ambient-occlusion rays).
+ *   key       a 32-bit word per entry, from dRays[i] (o = its origin, d = its direction) and dBox.  dBox is a DEVICE
+ *             pointer to 6 floats {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z}, aligned to 4; the caller makes it on the stream,
+ *             from bounds it holds or from the origins (a minimum and a maximum over the rows), without reading anything
+ *             back.  cellBits in [1, SRT_SORT_MAX_CELL_BITS] is the number of grid bits per axis.  Per axis a, in float32,
+ *             as three separate operations (no contraction):
+ *               s   = float(1 << cellBits) / (hi_a - lo_a)      a correctly rounded division
+ *               c   = (o_a - lo_a) * s
+ *               q_a = 0 unless c >= 0; otherwise min((int)trunc(c), (1 << cellBits) - 1)
+ *             The rule is total: a NaN c gives cell 0, +inf the last cell, a negative c cell 0 -- so an origin outside
+ *             the box, an axis with hi_a == lo_a (s infinite: c is NaN on lo_a, +-inf elsewhere), an inverted box
+ *             (s negative) and a box with a NaN or an infinity in it need no case of their own and are not errors.
+ *             cell = the Morton interleave of q: bit k of q_x goes to bit 3k, of q_y to bit 3k + 1, of q_z to bit 3k + 2.
+ *             octant = signbit(d_x) | signbit(d_y) << 1 | signbit(d_z) << 2 -- the sign BIT: -0 counts as negative, and a
+ *             NaN has the sign its bit says.  A kept entry has key = cell << 3 | octant; an entry that is not kept has
+ *             key = 1u << (3 * cellBits + 3), above every kept key, and its ray is not read.  The sort runs over bits
+ *             [0, 3 * cellBits + 4) only: fewer cell bits make a cheaper sort.
+ *   order     STABLE by key: entries with equal keys stay in index order.  With count = the number kept and rank(i) = the
+ *             position of i in that order, for every kept i: dRaysOut[rank(i)] = dRays[i] (36 bytes),
+ *             dRngOut[rank(i)] = dRng[i] (8 bytes) and dSlotOut[rank(i)] = dSlot ? dSlot[i] : (int32_t)i.  The
+ *             permutation is a function of the inputs alone.
+ *   payloads, dCount, dActiveOut, never written, overlap
+ *             srtCompactPathsDevice's, word for word, with this call's scratch size, with dRays always read (it is
+ *             required even without dRaysOut, aligned to 4) and with dBox as one more input that no output may overlap.
+ *             dActiveOut may be exactly dActive here too.
+ *   scratch   dScratch, aligned to 8, is the caller's: scratchBytes bytes, at least srtSortPathsScratchBytes(n) (key and
+ *             index of every entry, twice, and the radix sort's temporary storage; about 20 bytes per entry).  That
+ *             function is host only, needs no context, is 0 for n <= 0 and never decreases as n grows: a scratch sized for
+ *             n serves every call with fewer entries.  Its contents afterwards are unspecified.
+ *   async     on `stream`: a memset of dCount, the key kernel, rocPRIM's radix_sort_pairs over (key, index) and the gather
+ *             kernel; no kernel of the library's own waits for another workgroup.  Allocates nothing, does not
+ *             synchronise, touches no scratch of the context's, and leaves the tunables, the host generator, the chunk
+ *             scratch, srtLastKernelMs, srtGetLaunchInfo, srtGetStats and the temporal history as they were.  Needs no
+ *             uploaded scene.
+ *   n == 0    returns 0 and launches nothing; dCount is NOT written.
+ *   errors    (non-zero, message in srtLastError, NOTHING launched, outputs untouched; all decided on the host)
+ *             srtCompactPathsDevice's -- but dOut and dActive both NULL is no error, and n > 2^31 - 1 is refused whether
+ *             or not there is a dSlotOut -- and: cellBits outside [1, SRT_SORT_MAX_CELL_BITS]; with n > 0 a NULL or
+ *             misaligned dBox, a NULL dRays, a scratchBytes below srtSortPathsScratchBytes(n). */
+enum { SRT_SORT_MAX_CELL_BITS = 9 }; /* 27 cell bits, 3 octant bits: at most 31 key bits with the dropped entries' one */
+int64_t srtSortPathsScratchBytes(int64_t n);
+int srtSortPathsDevice(SrtContext* ctx, int64_t n, int32_t cellBits, const void* dBox, const void* dOut, const void* dActive,
+                       const void* dRays, const void* dRng, const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut,
+                       void* dActiveOut, void* dCount, void* dScratch, int64_t scratchBytes, void* stream);
 
 /* material::scatter + material::emitted (material.h:15-21; texture::value through a light's emitted, texture.h:13-16) for
  * n (incoming ray, hit record) pairs, evaluated by the render kernels' own shading function.  hits[i].material indexes

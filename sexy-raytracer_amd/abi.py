@@ -18,6 +18,7 @@ SRT_NO_HIT = -1
 # path steps on device buffers (srtScatterRaysDevice / srtPathStepDevice): SrtPathOut.status
 SRT_PATH_INVALID, SRT_PATH_MISS, SRT_PATH_ENDED, SRT_PATH_SCATTERED = -1, 0, 1, 2
 SRT_COMPACT_TILE = 1024  # entries per tile of srtCompactPathsDevice: its scratch is one 64-bit word per tile
+SRT_SORT_MAX_CELL_BITS = 9  # srtSortPathsDevice: the most grid bits per axis of its key
 SRT_MAX_BOUNCE = 16  # the largest maxBounce of a render and of srtTracePathsDevice
 SRT_PATHS_SCRATCH_BYTES = 64  # srtTracePathsDevice: the caller's scratch (the counter lanes take their entries from)
 # feature planes (srtRenderFeatureTiles / srtRenderFeatureImage): bit 1 << k selects plane k

@@ -55,6 +55,30 @@ struct CompactArgs {
 };
 int srt_launch_compact(const CompactArgs* a, int grid, hipStream_t stream);
 
+// srt_sort.hip (srtSortPathsDevice): a memset of *count, the key kernel, rocPRIM's radix sort over (key, index) between the
+// two halves of the scratch, and the gather kernel, all on the stream; grid = the workgroups of the two kernels.
+// srt_sort_temp_bytes: what that sort asks for as temporary storage at this n and cellBits (host only, launches nothing).
+struct SortArgs {
+  const int32_t* out;     // SrtPathOut[n] as dwords (the status is dword 3 of 8), or null
+  const uint8_t* active;  // or null; both null: every entry is kept
+  const uint32_t* rays;   // required: the key reads the origin and the direction's sign bits
+  const uint64_t* rng;    // payloads in: read only where the output beside them is not null
+  const int32_t* slot;    // null with slotOut: the identity
+  const float* box;       // lo.xyz, hi.xyz on the device
+  uint32_t* raysOut;      // payloads out, each or null
+  uint64_t* rngOut;
+  int32_t* slotOut;
+  uint8_t* activeOut;     // or null; may be `active`
+  int64_t* count;
+  uint32_t *keys, *keysSpare, *index, *indexSpare;  // the caller's scratch: n words each
+  void* temp;             // and the sort's temporary storage behind them
+  size_t tempBytes;
+  int64_t n;
+  int32_t cellBits;
+};
+int srt_sort_temp_bytes(int64_t n, int cellBits, hipStream_t stream, size_t* bytes);
+int srt_launch_sort(const SortArgs* a, int grid, hipStream_t stream);
+
 // srt_paths.hip (srtTracePathsDevice): one memset of the counter and ONE persistent kernel on the stream.  The grid is
 // the smaller of ceil(n / SRT_BLOCK) and numCUs * the workgroups of the kernel a CU holds at ldsBytes of dynamic LDS
 // (srtPathsLdsBytes); no workgroup waits for another one, so a grid the device holds only in part is merely slower.

@@ -519,6 +519,28 @@ static int pathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays,
   return 0;
 }
 
+// The range comparison of srtCompactPathsDevice and srtSortPathsDevice: no written range may overlap a range that is read
+// or another written one, each taken at its full length; null ranges take no part.  maskOut == mask exactly is the one
+// exception (an entry's byte is read before it is written).
+struct PathRange {
+  const char* name;
+  uintptr_t at;
+  uint64_t bytes;
+  bool written;
+};
+static int checkPathRanges(SrtContext* ctx, const char* what, const PathRange* ranges, size_t count, const PathRange* mask,
+                           const PathRange* maskOut) {
+  for (const PathRange* w = ranges; w != ranges + count; ++w) {
+    if (!w->written || !w->at) continue;
+    for (const PathRange* r = ranges; r != ranges + count; ++r) {
+      if (r == w || !r->at || (r->written && r < w)) continue;  // a pair of written ranges once
+      if (w == maskOut && r == mask && w->at == r->at) continue;
+      if (w->at < r->at + r->bytes && r->at < w->at + w->bytes) return fail(ctx, "%s: the %s overlap the %s", what, w->name, r->name);
+    }
+  }
+  return 0;
+}
+
 // srtCompactPathsDevice: every check on the host, then srt_compact.hip's three launches on the caller's stream.  Needs no
 // scene; nothing of the context changes.
 static int64_t compactTiles(int64_t n) { return n <= 0 ? 0 : (n - 1) / SRT_COMPACT_TILE + 1; }
@@ -543,34 +565,19 @@ static int compactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, cons
   if ((dSlotOut && (uintptr_t)dSlot % 4) || (uintptr_t)dSlotOut % 4) return fail(ctx, "%s: the slots are not aligned to 4 bytes", what);
   if (dSlotOut && n > 0x7fffffffll) return fail(ctx, "%s: n = %lld does not fit a 32-bit slot", what, (long long)n);
   // what the kernels write may overlap nothing else they read or write (dActiveOut may BE dActive: an entry owns its byte)
-  struct Range {
-    const char* name;
-    uintptr_t at;
-    uint64_t bytes;
-    bool written;
-  };
   const uint64_t un = (uint64_t)n;
-  const Range ranges[] = {{"outputs", (uintptr_t)dOut, 32 * un, false},
-                          {"mask", (uintptr_t)dActive, un, false},
-                          {"rays", (uintptr_t)(dRaysOut ? dRays : nullptr), 36 * un, false},
-                          {"rng states", (uintptr_t)(dRngOut ? dRng : nullptr), 8 * un, false},
-                          {"slots", (uintptr_t)(dSlotOut ? dSlot : nullptr), 4 * un, false},
-                          {"compacted rays", (uintptr_t)dRaysOut, 36 * un, true},
-                          {"compacted rng states", (uintptr_t)dRngOut, 8 * un, true},
-                          {"compacted slots", (uintptr_t)dSlotOut, 4 * un, true},
-                          {"compacted mask", (uintptr_t)dActiveOut, un, true},
-                          {"count", (uintptr_t)dCount, 8, true},
-                          {"scratch", (uintptr_t)dScratch, (uint64_t)srtCompactPathsScratchBytes(n), true}};
-  const Range *mask = &ranges[1], *maskOut = &ranges[8];
-  for (const Range& w : ranges) {
-    if (!w.written || !w.at) continue;
-    for (const Range& r : ranges) {
-      if (&r == &w || !r.at || (r.written && &r < &w)) continue;  // a pair of written ranges once
-      if (&w == maskOut && &r == mask && dActiveOut == dActive) continue;
-      if (w.at < r.at + r.bytes && r.at < w.at + w.bytes)
-        return fail(ctx, "%s: the %s overlap the %s", what, w.name, r.name);
-    }
-  }
+  const PathRange ranges[] = {{"outputs", (uintptr_t)dOut, 32 * un, false},
+                              {"mask", (uintptr_t)dActive, un, false},
+                              {"rays", (uintptr_t)(dRaysOut ? dRays : nullptr), 36 * un, false},
+                              {"rng states", (uintptr_t)(dRngOut ? dRng : nullptr), 8 * un, false},
+                              {"slots", (uintptr_t)(dSlotOut ? dSlot : nullptr), 4 * un, false},
+                              {"compacted rays", (uintptr_t)dRaysOut, 36 * un, true},
+                              {"compacted rng states", (uintptr_t)dRngOut, 8 * un, true},
+                              {"compacted slots", (uintptr_t)dSlotOut, 4 * un, true},
+                              {"compacted mask", (uintptr_t)dActiveOut, un, true},
+                              {"count", (uintptr_t)dCount, 8, true},
+                              {"scratch", (uintptr_t)dScratch, (uint64_t)srtCompactPathsScratchBytes(n), true}};
+  if (checkPathRanges(ctx, what, ranges, sizeof ranges / sizeof ranges[0], &ranges[1], &ranges[8])) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   CompactArgs a;
   a.out = static_cast<const int32_t*>(dOut);
@@ -597,6 +604,96 @@ int srtCompactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const vo
                           void* dScratch, void* stream) {
   SRT_GUARDED(ctx, compactPathsDevice(ctx, n, dOut, dActive, dRays, dRng, dSlot, dRaysOut, dRngOut, dSlotOut, dActiveOut, dCount,
                                       dScratch, stream));
+}
+
+// srtSortPathsDevice: every check on the host, then srt_sort.hip's memset, key kernel, rocPRIM sort and gather kernel on the
+// caller's stream.  Needs no scene; nothing of the context changes.  The scratch: four arrays of n 32-bit words (key and
+// index, twice: the sort's double buffers), each rounded up to 256 bytes, and behind them the sort's temporary storage.
+// srtSortPathsScratchBytes runs without a device, so that part is a bound that grows with n -- 4 bytes per entry and 64 KB:
+// with double buffers rocPRIM asks for digit histograms and, per block of at least 256 entries, one 32-bit look-back
+// word per digit or one merge partition -- and the call compares what the installed rocPRIM asks for with it.
+static int64_t sortArrayBytes(int64_t n) { return (4 * n + 255) & ~(int64_t)255; }
+static int64_t sortTempBytes(int64_t n) { return sortArrayBytes(n) + 65536; }
+
+int64_t srtSortPathsScratchBytes(int64_t n) { return n <= 0 ? 0 : 4 * sortArrayBytes(n) + sortTempBytes(n); }
+
+static int sortPathsDevice(SrtContext* ctx, int64_t n, int32_t cellBits, const void* dBox, const void* dOut, const void* dActive,
+                           const void* dRays, const void* dRng, const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut,
+                           void* dActiveOut, void* dCount, void* dScratch, int64_t scratchBytes, void* streamPtr) {
+  const char* what = "srtSortPathsDevice";
+  if (!ctx) return 1;
+  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
+  if (n > 0x7fffffffll) return fail(ctx, "%s: n = %lld does not fit a 32-bit index", what, (long long)n);
+  if (cellBits < 1 || cellBits > SRT_SORT_MAX_CELL_BITS)
+    return fail(ctx, "%s: cellBits = %d is outside [1, %d]", what, cellBits, (int)SRT_SORT_MAX_CELL_BITS);
+  if (checkPointer(ctx, what, "count", dCount, 8)) return 1;
+  if (n == 0) return 0;
+  if (checkPointer(ctx, what, "scratch", dScratch, 8) || checkPointer(ctx, what, "box", dBox, 4) ||
+      checkPointer(ctx, what, "rays", dRays, 4))
+    return 1;
+  if (scratchBytes < srtSortPathsScratchBytes(n))
+    return fail(ctx, "%s: the scratch holds %lld bytes, n = %lld needs %lld", what, (long long)scratchBytes, (long long)n,
+                (long long)srtSortPathsScratchBytes(n));
+  if (dRngOut && !dRng) return fail(ctx, "%s: sorted rng states without rng states", what);
+  if ((uintptr_t)dOut % 16) return fail(ctx, "%s: the outputs are not aligned to 16 bytes", what);
+  if ((uintptr_t)dRaysOut % 4) return fail(ctx, "%s: the rays are not aligned to 4 bytes", what);
+  if ((dRngOut && (uintptr_t)dRng % 8) || (uintptr_t)dRngOut % 8) return fail(ctx, "%s: the rng states are not aligned to 8 bytes", what);
+  if ((dSlotOut && (uintptr_t)dSlot % 4) || (uintptr_t)dSlotOut % 4) return fail(ctx, "%s: the slots are not aligned to 4 bytes", what);
+  const uint64_t un = (uint64_t)n;
+  const PathRange ranges[] = {{"outputs", (uintptr_t)dOut, 32 * un, false},
+                              {"mask", (uintptr_t)dActive, un, false},
+                              {"rays", (uintptr_t)dRays, 36 * un, false},
+                              {"rng states", (uintptr_t)(dRngOut ? dRng : nullptr), 8 * un, false},
+                              {"slots", (uintptr_t)(dSlotOut ? dSlot : nullptr), 4 * un, false},
+                              {"box", (uintptr_t)dBox, 24, false},
+                              {"sorted rays", (uintptr_t)dRaysOut, 36 * un, true},
+                              {"sorted rng states", (uintptr_t)dRngOut, 8 * un, true},
+                              {"sorted slots", (uintptr_t)dSlotOut, 4 * un, true},
+                              {"sorted mask", (uintptr_t)dActiveOut, un, true},
+                              {"count", (uintptr_t)dCount, 8, true},
+                              {"scratch", (uintptr_t)dScratch, (uint64_t)srtSortPathsScratchBytes(n), true}};
+  if (checkPathRanges(ctx, what, ranges, sizeof ranges / sizeof ranges[0], &ranges[1], &ranges[9])) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+  size_t tempNeeded = 0;
+  int e = srt_sort_temp_bytes(n, cellBits, stream, &tempNeeded);
+  if (e) return fail(ctx, "%s: the sort's size query failed: %s", what, hipGetErrorString((hipError_t)e));
+  if ((int64_t)tempNeeded > sortTempBytes(n))
+    return fail(ctx, "%s: rocPRIM asks for %zu bytes of temporary storage, the scratch reserves %lld", what, tempNeeded,
+                (long long)sortTempBytes(n));
+  SortArgs a;
+  a.out = static_cast<const int32_t*>(dOut);
+  a.active = static_cast<const uint8_t*>(dActive);
+  a.rays = static_cast<const uint32_t*>(dRays);
+  a.rng = static_cast<const uint64_t*>(dRng);
+  a.slot = static_cast<const int32_t*>(dSlot);
+  a.box = static_cast<const float*>(dBox);
+  a.raysOut = static_cast<uint32_t*>(dRaysOut);
+  a.rngOut = static_cast<uint64_t*>(dRngOut);
+  a.slotOut = static_cast<int32_t*>(dSlotOut);
+  a.activeOut = static_cast<uint8_t*>(dActiveOut);
+  a.count = static_cast<int64_t*>(dCount);
+  char* base = static_cast<char*>(dScratch);
+  const int64_t array = sortArrayBytes(n);
+  a.keys = reinterpret_cast<uint32_t*>(base);
+  a.keysSpare = reinterpret_cast<uint32_t*>(base + array);
+  a.index = reinterpret_cast<uint32_t*>(base + 2 * array);
+  a.indexSpare = reinterpret_cast<uint32_t*>(base + 3 * array);
+  a.temp = base + 4 * array;
+  a.tempBytes = (size_t)sortTempBytes(n);
+  a.n = n;
+  a.cellBits = cellBits;
+  const int grid = (int)std::min<int64_t>((n - 1) / SRT_BLOCK + 1, (int64_t)ctx->prop.multiProcessorCount * 8);
+  e = srt_launch_sort(&a, grid, stream);
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+int srtSortPathsDevice(SrtContext* ctx, int64_t n, int32_t cellBits, const void* dBox, const void* dOut, const void* dActive,
+                       const void* dRays, const void* dRng, const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut,
+                       void* dActiveOut, void* dCount, void* dScratch, int64_t scratchBytes, void* stream) {
+  SRT_GUARDED(ctx, sortPathsDevice(ctx, n, cellBits, dBox, dOut, dActive, dRays, dRng, dSlot, dRaysOut, dRngOut, dSlotOut, dActiveOut,
+                                   dCount, dScratch, scratchBytes, stream));
 }
 
 // srtTracePathsDevice: every check on the host, then srt_paths.hip's memset and its one kernel on the caller's stream.

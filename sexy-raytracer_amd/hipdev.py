@@ -34,7 +34,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtRenderTiles", "srtResolveTiles", "srtRenderImage", "srtRenderFeatureTiles", "srtRenderFeatureImage",
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtTraceRaysDevice", "srtOccludedDevice", "srtScatterRays",
            "srtRngKey", "srtCameraRaysDevice", "srtScatterRaysDevice", "srtPathStepDevice",
-           "srtCompactPathsScratchBytes", "srtCompactPathsDevice", "srtTracePathsDevice",
+           "srtCompactPathsScratchBytes", "srtCompactPathsDevice", "srtSortPathsScratchBytes", "srtSortPathsDevice", "srtTracePathsDevice",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
@@ -143,6 +143,9 @@ lib.srtPathStepDevice.argtypes = [_vp, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp,
 lib.srtCompactPathsScratchBytes.argtypes = [C.c_int64]
 lib.srtCompactPathsScratchBytes.restype = C.c_int64
 lib.srtCompactPathsDevice.argtypes = [_vp, C.c_int64] + [_vp] * 12
+lib.srtSortPathsScratchBytes.argtypes = [C.c_int64]
+lib.srtSortPathsScratchBytes.restype = C.c_int64
+lib.srtSortPathsDevice.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 12 + [C.c_int64, _vp]
 lib.srtTracePathsDevice.argtypes = [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), _vp, C.c_int64, _vp, _vp, _vp, _vp]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
@@ -889,6 +892,101 @@ class Context:
     def compact_scratch_bytes(n):
         """srtCompactPathsScratchBytes: 8 bytes per tile of abi.SRT_COMPACT_TILE entries, 0 for n <= 0."""
         return int(lib.srtCompactPathsScratchBytes(int(n)))
+
+    def sort_paths_device(self, cell_bits, rays=None, out=None, active=None, box=None, rng=None, slot=None, rays_out=None, rng_out=None,
+                          slot_out=None, active_out=None, slots=True, count=None, scratch=None, stream=None):
+        """srtSortPathsDevice: compact_paths_device with an order -- the entries that go on, moved to the front of fresh
+        buffers and stably sorted by (Morton cell of the origin in `box` at cell_bits bits per axis, octant of the
+        direction), asynchronous on `stream`.  rays is required (the key reads it); out and active are compact_paths_device's
+        predicate, and here both may be None: every entry is then kept.  box: a float32 tensor (6,) on the GPU holding
+        lo.xyz, hi.xyz; None computes it from the kept rays' origins with torch ops on `stream` (a torch stream or None,
+        torch's current one) and reads nothing back.  Everything else, and the returned tuple (rays_out, rng_out, slot_out,
+        active_out, count), is compact_paths_device's; scratch: uint8, at least sort_scratch_bytes(n)."""
+        import torch
+        cell_bits = int(cell_bits)
+        if not 1 <= cell_bits <= abi.SRT_SORT_MAX_CELL_BITS:
+            raise ValueError("cell_bits must lie in [1, %d], not %d" % (abi.SRT_SORT_MAX_CELL_BITS, cell_bits))
+        if rays is None:
+            raise ValueError("rays must not be None: the key is made of them")
+        if rng_out is not None and rng is None:
+            raise ValueError("rng_out without rng")
+        if box is None and stream is not None and not hasattr(stream, "cuda_stream"):
+            raise ValueError("box=None runs torch ops on the stream: pass a torch stream or a box")
+        first = rays = self._device_rays(rays)
+        n = rays.shape[0]
+        if n > 2 ** 31 - 1:
+            raise ValueError("n = %d does not fit a 32-bit index" % n)
+        if out is not None:
+            out = self._device_tensor(out, "out", "int32", (-1, 8), first)
+        if active is not None:
+            active = self._device_tensor(active, "active", "uint8", (-1,), first)
+        for name, t in (("out", out), ("active", active)):
+            if t is not None and t.shape[0] != n:
+                raise ValueError("%s must have %d rows like the rays, not %d" % (name, n, t.shape[0]))
+        if rng is not None:
+            rng = self._device_tensor(rng, "rng", "int64", (n,), first)
+        if slot is not None:
+            slot = self._device_tensor(slot, "slot", "int32", (n,), first)
+        if box is not None:
+            box = self._device_tensor(box, "box", "float32", (6,), first)
+        rays_out = torch.empty_like(rays) if rays_out is None else self._device_tensor(rays_out, "rays_out", "float32", (n, 9), first)
+        if rng is not None:
+            rng_out = torch.empty_like(rng) if rng_out is None else self._device_tensor(rng_out, "rng_out", "int64", (n,), first)
+        if slot_out is not None:
+            slot_out = self._device_tensor(slot_out, "slot_out", "int32", (n,), first)
+        elif slots or slot is not None:
+            slot_out = torch.empty((n,), dtype=torch.int32, device=first.device)
+        if active_out is True:
+            active_out = torch.empty((n,), dtype=torch.uint8, device=first.device)
+        elif active_out is not None and active_out is not False:
+            active_out = self._device_tensor(active_out, "active_out", "uint8", (n,), first)
+        else:
+            active_out = None
+        need = self.sort_scratch_bytes(n)
+        if scratch is None:
+            scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=first.device)
+        else:
+            scratch = self._device_tensor(scratch, "scratch", "uint8", (-1,), first)
+            if scratch.shape[0] < need:
+                raise ValueError("scratch must hold %d bytes, not %d" % (need, scratch.shape[0]))
+        if count is None:
+            count = torch.empty((1,), dtype=torch.int64, device=first.device)
+        else:
+            count = self._device_tensor(count, "count", "int64", (1,), first)
+        if n == 0:  # the entry does not write the count of nothing
+            count.zero_()
+        else:
+            if box is None:
+                with torch.cuda.stream(stream):
+                    box = self.origin_box(rays, out, active)
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            self._check(lib.srtSortPathsDevice(self.h, n, cell_bits, ptr(box), ptr(out), ptr(active), ptr(rays), ptr(rng), ptr(slot),
+                                               ptr(rays_out), ptr(rng_out), ptr(slot_out), ptr(active_out), ptr(count), ptr(scratch),
+                                               scratch.shape[0], self._stream_handle(stream)))
+        return rays_out, rng_out, slot_out, active_out, count.reshape(())
+
+    @staticmethod
+    def origin_box(rays, out=None, active=None):
+        """The box sort_paths_device makes with box=None: lo.xyz, hi.xyz over the origins of the kept rows of `rays`, a
+        float32 tensor (6,) made with torch ops on torch's current stream, nothing read back.  No kept row: lo = +inf,
+        hi = -inf, which the key's rule takes like any other box."""
+        import torch
+        origins = rays[:, 0:3]
+        low = high = origins
+        if out is not None or active is not None:
+            keep = torch.ones((rays.shape[0],), dtype=torch.bool, device=rays.device)
+            if active is not None:
+                keep &= active != 0
+            if out is not None:
+                keep &= out[:, 3] == abi.SRT_PATH_SCATTERED
+            low = torch.where(keep[:, None], origins, float("inf"))
+            high = torch.where(keep[:, None], origins, float("-inf"))
+        return torch.cat((low.amin(0), high.amax(0))).contiguous()
+
+    @staticmethod
+    def sort_scratch_bytes(n):
+        """srtSortPathsScratchBytes: 0 for n <= 0, never smaller for a larger n."""
+        return int(lib.srtSortPathsScratchBytes(int(n)))
 
     def trace_paths_device(self, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_CLOSEST, scratch=None, stream=None):
         """srtTracePathsDevice: the path-traced radiance of every ray of a DEVICE tensor in one kernel, asynchronous on

@@ -12,7 +12,7 @@ _DEAD = -2  # a status no step writes: an entry that was not active in this step
 
 
 def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_FAITHFUL, fused=True, stream=None,
-                    active_counts=None, compact=False, whole=False):
+                    active_counts=None, compact=False, whole=False, sort=None):
     """The radiance of one path per ray: at most max_bounce steps, then the unwinding.  rays (n, 9) float32 and rng (n,)
     int64 as Context.camera_rays_device returns them; both are overwritten.  fused: one path_step_device per bounce;
     otherwise trace_device(records=True) + scatter_device, which compute the same bytes through an 88-byte record per ray.
@@ -20,11 +20,17 @@ def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TR
     synchronises, so read it after the loop).  compact: every bounce after the first runs on the live entries alone,
     moved to the front by Context.compact_paths_device (_sample_radiance_compact below): the same bits.  whole: no loop
     at all -- one Context.trace_paths_device call carries every path from its ray to its radiance in one kernel (the same
-    bits again; rays is then only read, and there are no per-bounce counts to report).  Returns (n, 3) float32."""
+    bits again; rays is then only read, and there are no per-bounce counts to report).  sort: None, or the cell bits per
+    axis (1 .. abi.SRT_SORT_MAX_CELL_BITS) of Context.sort_paths_device, which then takes the place of
+    compact_paths_device in the compacted loop: the live entries move to the front AND into the order of their origin's
+    cell and their direction's octant, in the box of their origins -- the same bits once more; not together with whole.
+    Returns (n, 3) float32."""
     import torch
     if whole:
-        _check_whole(fused, compact, active_counts)
+        _check_whole(fused, compact, active_counts, sort)
         return ctx.trace_paths_device(rays, rng, max_bounce, background, traversal, stream=stream).view(torch.float32)[:, 0:3]
+    if sort is not None:
+        return _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts, sort)
     if compact:
         return _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts)
     n = rays.shape[0]
@@ -56,17 +62,20 @@ def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TR
     return radiance
 
 
-def _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts):
+def _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts, sort=None):
     """sample_radiance with the live set compacted between bounces.  Step j runs on the m_j entries that scattered in
     every step before it (m_0 = n), dense at the front of ping-pong ray and state buffers; its SrtPathOut rows are kept at
     that length together with the slot list that says which of its rows the m_(j+1) survivors were.  The unwinding goes
     through those lists innermost first with the same separate multiply and add.  The number kept is read once per
-    bounce (8 bytes, a synchronisation) to size the next step, and the loop stops when nobody is left."""
+    bounce (8 bytes, a synchronisation) to size the next step, and the loop stops when nobody is left.  sort: the cell bits
+    of Context.sort_paths_device, which then moves and orders the survivors; the slot lists of a sort are as injective as
+    those of a compaction, so the unwinding is the same."""
     import torch
     n = rays.shape[0]
     bg = torch.tensor([float(c) for c in background], dtype=torch.float32, device=rays.device)
     spare_rays, spare_rng = torch.empty_like(rays), torch.empty_like(rng)
-    scratch = torch.empty((max(ctx.compact_scratch_bytes(n), 8),), dtype=torch.uint8, device=rays.device)
+    scratch_bytes = ctx.compact_scratch_bytes(n) if sort is None else ctx.sort_scratch_bytes(n)  # for n: for every m <= n
+    scratch = torch.empty((max(scratch_bytes, 8),), dtype=torch.uint8, device=rays.device)
     steps = []  # per step: (out (m_j, 8) int32, slot (m_(j+1),) int32 or None behind the last step)
     m, live = n, torch.tensor(n, dtype=torch.int64, device=rays.device)
     for bounce in range(max_bounce):
@@ -84,8 +93,12 @@ def _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, 
             steps.append((out, None))
             break
         # every entry of this step was live: its status alone is the predicate
-        _, _, slot, _, live = ctx.compact_paths_device(out=out, rays=step_rays, rng=step_rng, rays_out=spare_rays[:m], rng_out=spare_rng[:m],
-                                                       scratch=scratch, stream=stream)
+        if sort is None:
+            _, _, slot, _, live = ctx.compact_paths_device(out=out, rays=step_rays, rng=step_rng, rays_out=spare_rays[:m],
+                                                           rng_out=spare_rng[:m], scratch=scratch, stream=stream)
+        else:
+            _, _, slot, _, live = ctx.sort_paths_device(sort, out=out, rays=step_rays, rng=step_rng, rays_out=spare_rays[:m],
+                                                        rng_out=spare_rng[:m], scratch=scratch, stream=stream)
         m = int(live)
         steps.append((out, slot[:m]))
         rays, spare_rays, rng, spare_rng = spare_rays, rays, spare_rng, rng
@@ -105,27 +118,29 @@ def _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, 
     return inner if inner is not None else torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
 
 
-def _check_whole(fused, compact, active_counts):
-    """whole=True has no bounces of its own to fuse, to compact between or to count."""
+def _check_whole(fused, compact, active_counts, sort=None):
+    """whole=True has no bounces of its own to fuse, to compact or sort between or to count."""
     if not fused:
         raise ValueError("whole=True runs one kernel per batch: fused=False does not apply")
     if compact:
         raise ValueError("whole=True refills its waves itself: compact=True does not apply")
+    if sort is not None:
+        raise ValueError("whole=True refills its waves itself: sort does not apply")
     if active_counts is not None:
         raise ValueError("whole=True reads no count per bounce: active_counts does not apply")
 
 
 def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples_per_batch=None, device=None, active_counts=None,
-           compact=False, whole=False):
+           compact=False, whole=False, sort=None):
     """params.spp samples of every pixel from params.sampleFirst on, through the device path steps: the (H, W, 4) float32
     torch tensor of per-pixel radiance sums (the float running sum in sample-index order) with the sample count in w --
     Context.render_image's accumulation buffer.  samples_per_batch: how many sample indices of the whole frame go through
-    the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  compact: sample_radiance's.
+    the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  compact, sort: sample_radiance's.
     whole: a batch is one Context.trace_paths_device call (15 words per entry whatever maxBounce is) followed by the same
-    running sum; not together with active_counts, compact or fused=False.  Runs on torch's current stream."""
+    running sum; not together with active_counts, compact, sort or fused=False.  Runs on torch's current stream."""
     import torch
     if whole:
-        _check_whole(fused, compact, active_counts)
+        _check_whole(fused, compact, active_counts, sort)
     device = torch.device("cuda" if device is None else device)
     W, H, spp = params.imageWidth, params.imageHeight, params.spp
     pixels = W * H
@@ -142,7 +157,7 @@ def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples
                                                      device=device).repeat_interleave(pixels)), dim=1).contiguous()
             rays, rng = ctx.camera_rays_device(params, pixel_sample, stream=stream)
             radiance = sample_radiance(ctx, rays, rng, params.maxBounce, params.background, traversal, fused, stream, active_counts, compact,
-                                       whole)
+                                       whole, sort)
             for k in range(count):
                 image[:, 0:3] += radiance[k * pixels:(k + 1) * pixels]
         image[:, 3] = float(spp)

@@ -1,0 +1,569 @@
+"""srtSortPathsDevice (include/srt_hip.h "Path steps on device buffers") through the raw entry, the user-land loop with a
+sort between its bounces (sexy-raytracer_amd/pathloop.py, sort=bits), and queries on sorted rays.
+
+ZERO tolerance everywhere: sorting moves bytes.  The reference is tests/sort_ref.py (the predicate, the float32 key step by
+step, np.argsort(kind="stable"), row gathers).  Payload rows are random bytes -- any 64 bits are a generator state, and ray
+rows are compared as bytes; only what the key reads of a ray is made on purpose (the origin, the three sign bits).
+Subnormal origins and box corners are left out: the key's float32 steps are stated for normal operands.
+
+Every buffer is PAD elements longer than n and filled with a sentinel behind element n; the payload outputs are filled
+with it throughout, so that it must also survive behind element `count`; the scratch carries it behind
+srtSortPathsScratchBytes(n), the count behind its 8 bytes, the box behind its 24.
+
+The installed rocPRIM (4.2) sorts up to 1024 pairs in one block, up to 2^20 with its merge sort and anything larger with
+its onesweep radix sort; SIZES covers the three: everything up to 1023 is the block sort, 1025 .. 2^20 the merge sort (2^20
+is the last size it takes), 2^20 + 1 the onesweep sort."""
+import importlib
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+import compact_ref as CR
+import exact_scenes
+import sort_ref as SR
+import tree_build_scenes as S
+
+pytestmark = pytest.mark.gpu
+
+PAD = 64
+SENTINEL = 0x5A
+ROW = {"rays": 36, "rng": 8, "slot": 4, "active_out": 1}
+ROW_IN = {"out": 32, "active": 1, "rays": 36, "rng": 8, "slot": 4}
+STATUSES = (-1, 0, 1, 2)  # INVALID, MISS, ENDED, SCATTERED
+ALL = ("rays", "rng", "slot", "active_out")
+BITS = (1, 5, 9)
+SIZES = [0, 1, 63, 64, 65, 255, 256, 257, 1023, 1025, 2 * 1024 + 3, 70_001, 2 ** 20, 2 ** 20 + 1]
+PATTERNS = ("all", "none", "last", "alternating", "mixed", "equal", "descending", "runs")
+UNIT = np.array([0, 0, 0, 1, 1, 1], np.float32)
+
+
+@pytest.fixture(scope="module")
+def pathloop(srt):
+    return importlib.import_module("sexy-raytracer_amd.pathloop")
+
+
+# ------------------------------------------------------------------------------------------------ inputs
+_payload_cache = {}
+
+
+def _payload(n):
+    """Random bytes for every row of every buffer, made once per size and never changed."""
+    if n not in _payload_cache:
+        g = np.random.default_rng(7000 + n)
+        p = {"out": g.integers(0, 2 ** 32, (n, 8), dtype=np.uint32), "rays": g.integers(0, 2 ** 32, (n, 9), dtype=np.uint32),
+             "rng": g.integers(-2 ** 63, 2 ** 63 - 1, n, dtype=np.int64), "slot": g.integers(-2 ** 31, 2 ** 31 - 1, n, dtype=np.int32)}
+        for a in p.values():
+            a.setflags(write=False)
+        _payload_cache.clear()  # one size at a time: the large ones are tens of megabytes
+        _payload_cache[n] = p
+    return _payload_cache[n]
+
+
+def _origins_of_keys9(key9):
+    """Origins in the unit box whose 9-bit cell | octant key is key9 (the centre of the cell: exact in float32), and the
+    sign bits of its octant."""
+    cell = key9 >> 3
+    q = np.zeros((len(key9), 3), np.uint32)
+    for k in range(9):
+        for a in range(3):
+            q[:, a] |= ((cell >> (3 * k + a)) & 1).astype(np.uint32) << k
+    origins = ((q.astype(np.float32) + np.float32(0.5)) / np.float32(512)).astype(np.float32)
+    signs = np.stack([(key9 >> a) & 1 for a in range(3)], axis=1).astype(np.uint32)
+    return origins, signs
+
+
+def _status_and_mask(keep, g, stale=True):
+    """tests/test_gpu_compact.py's mix: a (status, mask) pair whose predicate is `keep`, the four status values mixed and
+    about half of the dropped entries dropped by the mask alone, behind any status -- SCATTERED included."""
+    n = len(keep)
+    status = np.where(keep, 2, g.choice(STATUSES[:3], n)).astype(np.int32)
+    active = np.where(keep, g.choice((1, 2, 255), n), 1).astype(np.uint8)
+    if stale:
+        masked = ~keep & (g.random(n) < 0.5)
+        status[masked] = g.choice(STATUSES, int(masked.sum()))
+        active[masked] = 0
+    return status, active
+
+
+def _inputs(name, n, seed=0):
+    """{out, status, active, rays, rng, slot} of one keep-and-key pattern; the same for every cellBits."""
+    g = np.random.default_rng(seed)
+    p = _payload(n)
+    rays = p["rays"].copy()
+    origins = (g.random((n, 3), dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)  # a fifth outside
+    signs = None
+    keep = np.ones(n, bool)
+    if name == "none":
+        keep[:] = False
+    elif name == "last":
+        keep = np.arange(n) == n - 1
+    elif name == "alternating":
+        keep = np.arange(n) % 2 == 1
+    elif name == "mixed":
+        keep = g.random(n) < 0.5
+    elif name == "equal":  # one key: stability makes the sort the identity on the kept entries
+        keep = g.random(n) < 0.6
+        origins[:] = np.float32([0.3, 0.6, 0.9])
+        signs = np.tile(np.uint32([1, 0, 1]), (n, 1))
+    elif name == "descending":  # strictly descending at 9 bits, non-increasing with ties at fewer
+        key9 = ((np.arange(n, 0, -1, dtype=np.uint64) * np.uint64(2 ** 30 - 1)) // np.uint64(max(n, 1))).astype(np.uint32)
+        origins, signs = _origins_of_keys9(key9)
+    elif name == "runs":  # runs of 48 equal keys from index 40 on: they straddle 64, 256 and 1024
+        run = (np.arange(n) + 8) // 48
+        key9 = ((run.astype(np.uint64) * np.uint64(2654435761)) % np.uint64(2 ** 30)).astype(np.uint32)
+        origins, signs = _origins_of_keys9(key9)
+        keep = g.random(n) < 0.8
+    rays[:, 0:3] = origins.view(np.uint32)
+    if signs is not None:
+        rays[:, 3:6] = (rays[:, 3:6] & np.uint32(0x7fffffff)) | signs << np.uint32(31)
+    status, active = _status_and_mask(keep, g)
+    out = p["out"].copy()
+    out[:, 3] = status.view(np.uint32)
+    return {"out": out, "status": status, "active": active, "rays": rays, "rng": p["rng"], "slot": p["slot"], "keep": keep}
+
+
+def _padded(rows, n, row_bytes, pad=PAD):
+    """A device byte buffer of n + pad rows: `rows` (or the sentinel where None) in the first n, the sentinel behind."""
+    buf = np.full((n + pad) * row_bytes, SENTINEL, np.uint8)
+    if rows is not None and n:
+        buf[:n * row_bytes] = np.ascontiguousarray(rows).view(np.uint8).ravel()[:n * row_bytes]
+    return torch.from_numpy(buf).cuda()
+
+
+def _upload(d, n, use=("out", "active", "rays", "rng", "slot")):
+    return {k: _padded(d[k], n, ROW_IN[k]) if k in use and d.get(k) is not None else None for k in ROW_IN}
+
+
+def _box(box):
+    return _padded(np.asarray(box, np.float32), 6, 4)
+
+
+def _run(dev, c, n, bits, d_box, d_in, want=ALL, in_place=False, stream=None, scratch_for=None):
+    """One raw call on padded buffers.  Checks every sentinel and that no input changed; returns {count and, as device byte
+    tensors, rays, rng, slot (the first count rows), active_out (n bytes)} with None for what was not asked for."""
+    handle = stream.cuda_stream if stream is not None else None
+    with torch.cuda.stream(stream):
+        before = {k: t.clone() for k, t in d_in.items() if t is not None}
+        box_before = d_box.clone()
+        d_out = {k: _padded(None, n, ROW[k]) if k in want else None for k in ALL}
+        if in_place and "active_out" in want:
+            d_out["active_out"] = d_in["active"]
+        d_count = _padded(None, 1, 8)
+        need = dev.lib.srtSortPathsScratchBytes(n if scratch_for is None else scratch_for)
+        assert need % 8 == 0
+        d_scratch = _padded(None, need // 8, 8)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        rc = dev.lib.srtSortPathsDevice(c.h, n, bits, d_box.data_ptr(), ptr(d_in["out"]), ptr(d_in["active"]), ptr(d_in["rays"]),
+                                        ptr(d_in["rng"]), ptr(d_in["slot"]), ptr(d_out["rays"]), ptr(d_out["rng"]), ptr(d_out["slot"]),
+                                        ptr(d_out["active_out"]), d_count.data_ptr(), d_scratch.data_ptr(), need, handle)
+        assert rc == 0, dev.lib.srtLastError(c.h)
+    (stream or torch.cuda).synchronize()
+    assert bool((d_scratch[dev.lib.srtSortPathsScratchBytes(n):] == SENTINEL).all()), "written beyond the documented scratch size"
+    assert torch.equal(d_box, box_before), "the box changed"
+    for k, t in d_in.items():
+        if t is not None and not (in_place and k == "active"):
+            assert torch.equal(t, before[k]), "input %s changed" % k
+    count_bytes = d_count.cpu().numpy()
+    assert (count_bytes[8:] == SENTINEL).all()
+    if n == 0:
+        assert (count_bytes == SENTINEL).all(), "n == 0 writes no count"
+        count = 0
+    else:
+        count = int(count_bytes[:8].view(np.int64)[0])
+        assert 0 <= count <= n
+    got = {"count": count}
+    for k in ALL:
+        if d_out[k] is None:
+            got[k] = None
+            continue
+        rows = n if k == "active_out" else count
+        assert bool((d_out[k][rows * ROW[k]:] == SENTINEL).all()), "%s written beyond element %d" % (k, rows)
+        got[k] = d_out[k][:rows * ROW[k]]
+    return got
+
+
+def _rows(t, n, row_bytes):
+    return t[:n * row_bytes].view(n, row_bytes)
+
+
+def _assert_is_reference(got, ref, d_in, n, what=None):
+    """Against sort_ref.sort: the count, the mask, and every payload row -- gathered from the device inputs through the
+    reference's index for any size, and byte for byte against the reference's own rows where n is small."""
+    assert got["count"] == ref["count"], what
+    count = ref["count"]
+    index = torch.from_numpy(ref["index"].astype(np.int64)).cuda()
+    for k in ("rays", "rng", "slot"):
+        if got[k] is None:
+            continue
+        if k == "slot" and d_in["slot"] is None:
+            want = torch.from_numpy(ref["index"].astype(np.int32)).cuda().view(torch.uint8).view(count, 4)
+        else:
+            want = _rows(d_in[k], n, ROW[k]).index_select(0, index)
+        assert torch.equal(_rows(got[k], count, ROW[k]), want), (what, k)
+        if n <= 4096:
+            dtype = {"rays": np.uint32, "rng": np.int64, "slot": np.int32}[k]
+            assert got[k].cpu().numpy().tobytes() == np.ascontiguousarray(ref[k], dtype).tobytes(), (what, k)
+    if got["active_out"] is not None:
+        assert got["active_out"].cpu().numpy().tobytes() == ref["active_out"].tobytes(), (what, "active_out")
+
+
+def _ref(d, n, bits, box, use=("status", "active", "rng", "slot")):
+    return SR.sort(n, bits, box, d["rays"], **{k: d[k] for k in use})
+
+
+# ------------------------------------------------------------------------------------------------ 1. sizes and patterns
+@pytest.mark.parametrize("n", SIZES)
+def test_sizes_and_patterns(ctx, dev, n):
+    d_box = _box(UNIT)
+    for k, name in enumerate(PATTERNS):
+        d = _inputs(name, n, seed=100 * k + n % 97)
+        assert np.array_equal(SR.keep(n, d["status"], d["active"]), d["keep"])
+        d_in = _upload(d, n)
+        for bits in BITS:
+            ref = _ref(d, n, bits, UNIT)
+            got = _run(dev, ctx, n, bits, d_box, d_in)
+            _assert_is_reference(got, ref, d_in, n, (n, name, bits))
+            assert got["count"] == int(d["keep"].sum())
+            live = ref["key"][d["keep"]]
+            if name == "descending" and bits == 9 and n > 1:
+                assert (np.diff(live.astype(np.int64)) < 0).all() and ref["index"].tolist() == list(range(n - 1, -1, -1))
+            if name == "runs" and n > 1100:
+                every = SR.keys(d["rays"], UNIT, bits)  # the dropped entries' too
+                assert all(every[edge - 1] == every[edge] for edge in (64, 256, 1024)) and every[39] != every[40]
+            if name == "equal":
+                assert len(set(live.tolist())) <= 1
+        if name == "equal" and n:  # one key: the call is compaction, byte for byte
+            crays, crng, cslot, cactive, ccount = ctx.compact_paths_device(
+                out=_rows(d_in["out"], n, 32).view(torch.int32), active=d_in["active"][:n], rays=_rows(d_in["rays"], n, 36).view(torch.float32),
+                rng=d_in["rng"][:n * 8].view(torch.int64), slot=d_in["slot"][:n * 4].view(torch.int32), active_out=True)
+            m = int(ccount)
+            assert m == got["count"]
+            for k, t in (("rays", crays), ("rng", crng), ("slot", cslot)):
+                assert torch.equal(t[:m].contiguous().view(torch.uint8).view(-1), got[k]), k
+            assert torch.equal(cactive, got["active_out"])
+
+
+# ------------------------------------------------------------------------------------------------ 2. special rays
+def test_special_origins_directions_and_boxes(ctx, dev):
+    inf, nan = np.inf, np.nan
+    special = [0.0, -0.0, 1.0, 3.0, 2.0, 0.5, 3.5, -7.0, 1e30, -1e30, inf, -inf, nan, 1.0625, 2.9999998, 1.0000001]
+    origins = np.array(list(itertools.product(special, repeat=3)), np.float32)
+    n = len(origins)
+    g = np.random.default_rng(5)
+    d = {"rays": g.integers(0, 2 ** 32, (n, 9), dtype=np.uint32), "rng": g.integers(-2 ** 63, 2 ** 63 - 1, n, dtype=np.int64)}
+    d["rays"][:, 0:3] = origins.view(np.uint32)
+    # directions: +-0, +-inf, NaNs of either sign, finite values
+    dirs = np.array([0.0, -0.0, inf, -inf, 1.0, -1.0], np.float32).view(np.uint32).tolist() + [0x7fc00000, 0xffc00000, 0x7f800001, 0xff800001]
+    d["rays"][:, 3:6] = g.choice(np.array(dirs, np.uint32), (n, 3))
+    assert n == 4096
+    d_in = _upload(d, n, use=("rays", "rng"))  # neither a status nor a mask: every entry is kept
+    boxes = {"unit": UNIT, "1..3": [1, 1, 1, 3, 3, 3], "flat in y": [1, 2, 1, 3, 2, 3], "a point": [2, 2, 2, 2, 2, 2],
+             "inverted": [3, 3, 3, 1, 1, 1], "inverted in x": [3, 1, 1, 1, 3, 3], "infinite": [-inf, -inf, -inf, inf, inf, inf],
+             "half infinite": [1, 1, 1, inf, inf, inf], "NaN": [nan, 1, 1, 3, nan, 3], "empty": [inf, inf, inf, -inf, -inf, -inf],
+             "huge": [-1e37, -1e37, -1e37, 1e37, 1e37, 1e37], "off centre": [-7.25, 0.5, 1e-3, 3.5, 0.625, 1e3]}
+    seen = set()
+    for name, box in boxes.items():
+        box = np.asarray(box, np.float32)
+        d_box = _box(box)
+        for bits in BITS:
+            ref = SR.sort(n, bits, box, d["rays"], rng=d["rng"])
+            assert ref["count"] == n
+            got = _run(dev, ctx, n, bits, d_box, d_in, want=("rays", "rng", "slot"))
+            _assert_is_reference(got, ref, d_in, n, (name, bits))
+            seen.add(len(set(ref["key"].tolist())))
+    assert max(seen) > 100 and min(seen) <= 8  # boxes that tell the origins apart, and boxes that leave only the octants
+
+
+# ------------------------------------------------------------------------------------------------ 3. the call's structure
+def test_slots_carry_through_and_compose(ctx, dev):
+    n = 3 * 1024 + 5
+    a = _inputs("mixed", n, seed=5)
+    d_a = _upload(a, n)
+    d_box = _box(UNIT)
+    own = _run(dev, ctx, n, 5, d_box, d_a, want=("slot",))
+    ref1 = _ref(a, n, 5, UNIT)
+    _assert_is_reference(own, ref1, d_a, n, "a caller's slots")
+    d_id = dict(d_a, slot=None)
+    identity = _run(dev, ctx, n, 5, d_box, d_id, want=("rays", "rng", "slot"))
+    ref_id = _ref(a, n, 5, UNIT, use=("status", "active", "rng"))
+    _assert_is_reference(identity, ref_id, d_id, n, "identity")
+    assert identity["slot"].cpu().numpy().view(np.int32).tolist() == ref_id["index"].tolist()
+    assert sorted(ref_id["index"].tolist()) == np.flatnonzero(a["keep"]).tolist() and ref_id["index"].tolist() != sorted(ref_id["index"].tolist())
+    # a second sort of the survivors at another cell size, the first one's slots carried: they name entries of the first buffer
+    m = ref_id["count"]
+    g = np.random.default_rng(6)
+    keep2 = g.random(m) < 0.5
+    status2, active2 = _status_and_mask(keep2, g)
+    out2 = np.zeros((m, 8), np.uint32)
+    out2[:, 3] = status2.view(np.uint32)
+    b = {"out": out2, "status": status2, "active": active2, "rays": ref_id["rays"], "rng": ref_id["rng"], "slot": ref_id["slot"]}
+    d_b = _upload(b, m)
+    assert torch.equal(d_b["rays"][:m * 36], identity["rays"]) and torch.equal(d_b["slot"][:m * 4], identity["slot"])
+    second = _run(dev, ctx, m, 9, d_box, d_b, want=("rng", "slot"))
+    ref2 = _ref(b, m, 9, UNIT)
+    _assert_is_reference(second, ref2, d_b, m, "composition")
+    composed = ref_id["index"][ref2["index"]]
+    assert second["slot"].cpu().numpy().view(np.int32).tolist() == composed.tolist()
+    assert second["rng"].cpu().numpy().tobytes() == a["rng"][composed].tobytes()
+
+
+def test_every_subset_of_the_outputs_in_place_mask_and_a_larger_scratch(ctx, dev):
+    n = 1024 + 300
+    d = _inputs("mixed", n, seed=7)
+    d_in = _upload(d, n)
+    d_box = _box(UNIT)
+    ref = _ref(d, n, 5, UNIT)
+    for size in range(len(ALL) + 1):
+        for want in itertools.combinations(ALL, size):
+            got = _run(dev, ctx, n, 5, d_box, d_in, want=want)
+            _assert_is_reference(got, ref, d_in, n, want)
+            assert [k for k in ALL if got[k] is not None] == list(want)
+    # inputs left out with their outputs; an input without an output is ignored; slots without an input are the identity
+    d_some = dict(d_in, slot=None)
+    got = _run(dev, ctx, n, 5, d_box, d_some, want=("rng", "slot"))
+    _assert_is_reference(got, _ref(d, n, 5, UNIT, use=("status", "active", "rng")), d_some, n, "identity slots")
+    # the predicate's halves alone, and neither
+    for use in (("status",), ("active",), ()):
+        d_part = dict(d_in, out=d_in["out"] if "status" in use else None, active=d_in["active"] if "active" in use else None)
+        r = _ref(d, n, 5, UNIT, use=use + ("rng", "slot"))
+        _assert_is_reference(_run(dev, ctx, n, 5, d_box, d_part), r, d_part, n, use)
+        assert (r["count"] == n) == (use == ())
+    # dActiveOut == dActive: the same bytes as out of place
+    plain = _run(dev, ctx, n, 5, d_box, d_in)
+    d_again = _upload(d, n)
+    in_place = _run(dev, ctx, n, 5, d_box, d_again, in_place=True)
+    assert in_place["count"] == plain["count"]
+    for k in ALL:
+        assert torch.equal(in_place[k], plain[k]), k
+    # a scratch sized for more entries serves
+    assert dev.lib.srtSortPathsScratchBytes(4 * n) > dev.lib.srtSortPathsScratchBytes(n)
+    _assert_is_reference(_run(dev, ctx, n, 5, d_box, d_in, scratch_for=4 * n), ref, d_in, n, "a larger scratch")
+
+
+def test_call_runs_behind_the_ops_that_made_the_rays_and_the_box(ctx, dev):
+    n = 64 * 1024 + 9
+    g = np.random.default_rng(10)
+    rays = g.random((n, 9), dtype=np.float32) - np.float32(0.5)
+    moved = rays + np.float32(0.75)
+    keep = g.random(n) < 0.5
+    status, active = _status_and_mask(keep, g)
+    out = np.zeros((n, 8), np.int32)
+    out[:, 3] = status
+    rng = g.integers(-2 ** 63, 2 ** 63 - 1, n, dtype=np.int64)
+    box = SR.origin_box(moved, keep)
+    ref = SR.sort(n, 7, box, moved, status=status, active=active, rng=rng)
+    side = torch.cuda.Stream()
+    d_rays, d_out, d_active, d_rng = (torch.from_numpy(a).cuda() for a in (rays, out, active, rng))
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        d_rays += 0.75
+        rays_out, rng_out, slot_out, active_out, count = ctx.sort_paths_device(7, rays=d_rays, out=d_out, active=d_active, rng=d_rng,
+                                                                               active_out=True, stream=side)
+        made = ctx.origin_box(d_rays, d_out, d_active)
+    side.synchronize()
+    assert made.cpu().numpy().tobytes() == box.tobytes()
+    assert count.dim() == 0 and count.dtype == torch.int64 and count.is_cuda
+    m = int(count)
+    assert m == ref["count"] == int(keep.sum())
+    assert rays_out[:m].cpu().numpy().tobytes() == ref["rays"].tobytes()
+    assert rng_out[:m].cpu().numpy().tobytes() == ref["rng"].tobytes()
+    assert slot_out[:m].cpu().numpy().tobytes() == ref["slot"].tobytes()
+    assert active_out.cpu().numpy().tobytes() == ref["active_out"].tobytes()
+    torch.cuda.synchronize()
+    # a box of the caller's; the wrapper on nothing; what the wrapper refuses on device tensors
+    got = ctx.sort_paths_device(7, rays=d_rays, out=d_out, active=d_active, box=torch.from_numpy(box).cuda())
+    torch.cuda.synchronize()
+    assert got[2][:m].cpu().numpy().tobytes() == ref["slot"].tobytes() and got[1] is None
+    empty = ctx.sort_paths_device(3, rays=torch.zeros((0, 9), dtype=torch.float32, device="cuda"))
+    assert int(empty[4]) == 0 and tuple(empty[0].shape) == (0, 9) and tuple(empty[2].shape) == (0,)
+    with pytest.raises(ValueError, match="out must have %d rows" % n):
+        ctx.sort_paths_device(7, rays=d_rays, out=d_out[:-1])
+    with pytest.raises(ValueError, match="active must have %d rows" % n):
+        ctx.sort_paths_device(7, rays=d_rays, active=d_active[:-1])
+    with pytest.raises(ValueError, match="scratch must hold"):
+        ctx.sort_paths_device(7, rays=d_rays, scratch=torch.empty((ctx.sort_scratch_bytes(n) - 1,), dtype=torch.uint8, device="cuda"))
+    with pytest.raises(ValueError, match="box must have shape"):
+        ctx.sort_paths_device(7, rays=d_rays, box=torch.zeros((2, 3), dtype=torch.float32, device="cuda"))
+    with pytest.raises(ValueError, match="box must be float32"):
+        ctx.sort_paths_device(7, rays=d_rays, box=torch.zeros((6,), dtype=torch.float64, device="cuda"))
+    with pytest.raises(ValueError, match="rng must have shape"):
+        ctx.sort_paths_device(7, rays=d_rays, rng=d_rng[:-1])
+    with pytest.raises(ValueError, match="count must have shape"):
+        ctx.sort_paths_device(7, rays=d_rays, count=torch.zeros((2,), dtype=torch.int64, device="cuda"))
+
+
+# ------------------------------------------------------------------------------------------------ 4. the loop is the loop
+def _same_image(a, b, what):
+    a, b = a.cpu().numpy(), (b.cpu().numpy() if hasattr(b, "cpu") else b)
+    assert a.shape == b.shape
+    nan = np.isnan(b)
+    assert np.array_equal(np.isnan(a), nan), what
+    assert np.array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan]), what
+
+
+def _assert_sorted_loop_is_the_loop_and_the_render(ctx, abi, pathloop, p, what):
+    """FAITHFUL: sort=b against the plain loop and srtRenderImage; CLOSEST: against the plain loop with CLOSEST steps."""
+    want = ctx.render_image(p, want_rgba=False)[0]
+    live = None
+    for traversal in (abi.SRT_TRAVERSE_FAITHFUL, abi.SRT_TRAVERSE_CLOSEST):
+        plain_counts = []
+        plain = pathloop.render(ctx, p, traversal=traversal, active_counts=plain_counts)
+        if traversal == abi.SRT_TRAVERSE_FAITHFUL:
+            _same_image(plain, want, (what, "the plain loop"))
+        for bits in BITS:
+            counts = []
+            got = pathloop.render(ctx, p, traversal=traversal, sort=bits, active_counts=counts)
+            torch.cuda.synchronize()
+            _same_image(got, plain, (what, traversal, bits))
+            if traversal == abi.SRT_TRAVERSE_FAITHFUL:
+                _same_image(got, want, (what, bits, "against the render"))
+            assert [int(c) for c in counts] == [int(c) for c in plain_counts], (what, traversal, bits)
+            assert len(counts) == p.maxBounce and int(counts[0]) == p.imageWidth * p.imageHeight * p.spp
+        live = [int(c) for c in plain_counts]
+    return live
+
+
+@pytest.mark.parametrize("tier", exact_scenes.TIERS)
+def test_sorted_loop_on_exact_scenes(ctx, abi, camera, pathloop, tier):
+    ctx.upload_scene(exact_scenes.random(abi, 0, tier))
+    ctx.set_camera(camera)
+    for bounces in (1, 4, 16):
+        p = abi.default_render_params(32, 24, 4, bounces, seed=11)
+        _assert_sorted_loop_is_the_loop_and_the_render(ctx, abi, pathloop, p, (tier, bounces))
+    p = abi.default_render_params(32, 24, 4, 4, seed=11)
+    for bits in BITS:
+        whole = pathloop.render(ctx, p, sort=bits)
+        parts = pathloop.render(ctx, p, sort=bits, samples_per_batch=3)
+        unfused = pathloop.render(ctx, p, sort=bits, fused=False)
+        assert torch.equal(whole.view(torch.int32), parts.view(torch.int32))
+        assert torch.equal(whole.view(torch.int32), unfused.view(torch.int32))
+    with pytest.raises(ValueError, match="sort does not apply"):
+        pathloop.render(ctx, p, sort=5, whole=True)
+    with pytest.raises(ValueError, match="cell_bits"):
+        pathloop.render(ctx, p, sort=10)
+
+
+def test_sorted_loop_on_masterchief(ctx, srt, abi, camera, pathloop):
+    ctx.upload_scene(srt.scenes.SCENES["masterchief"]())
+    ctx.set_camera(camera)
+    p = abi.default_render_params(64, 36, 2, 8, seed=5)
+    live = _assert_sorted_loop_is_the_loop_and_the_render(ctx, abi, pathloop, p, "masterchief")
+    assert 0 < live[2] < live[0] // 2  # the set really shrinks: below half by the third bounce
+
+
+# ------------------------------------------------------------------------------------------------ 5. queries on sorted rays
+def test_queries_on_sorted_rays_scattered_back(ctx, abi):
+    ctx.upload_scene(S.soup(abi, 3000, abi.SRT_BUILDER_PLOC))
+    rays = S.random_rays(abi, 20_000)
+    d_rays = torch.from_numpy(np.ascontiguousarray(rays).view(np.float32).reshape(-1, 9).copy()).cuda()
+    n = d_rays.shape[0]
+    hits, occluded = ctx.trace_device(d_rays), ctx.occluded_device(d_rays)
+    torch.cuda.synchronize()
+    assert 0.1 < float(occluded.float().mean()) < 0.9
+    for bits in BITS:
+        sorted_rays, _, slot, _, count = ctx.sort_paths_device(bits, rays=d_rays)  # dOut and dActive both NULL
+        assert int(count) == n
+        index = slot.to(torch.int64)
+        assert sorted(index.tolist()) == list(range(n)) and not torch.equal(sorted_rays, d_rays)
+        back_hits, back_occluded = torch.empty_like(hits), torch.empty_like(occluded)
+        back_hits.index_copy_(0, index, ctx.trace_device(sorted_rays))
+        back_occluded.index_copy_(0, index, ctx.occluded_device(sorted_rays))
+        torch.cuda.synchronize()
+        assert torch.equal(back_hits, hits) and torch.equal(back_occluded, occluded), bits
+
+
+# ------------------------------------------------------------------------------------------------ 6. side effects, errors
+def test_side_effects_and_errors(ctx, dev, abi, camera):
+    ctx.upload_scene(S.soup(abi, 3000, abi.SRT_BUILDER_PLOC))
+    ctx.set_camera(camera)
+    p = abi.default_render_params(64, 36, 2, 4, seed=5)
+    first = ctx.render_image(p)[0]
+    info, ms, stats = ctx.launch_info(), ctx.last_kernel_ms(), ctx.stats()
+    n = 2 * 1024 + 40
+    d = _inputs("mixed", n, seed=12)
+    d_in = _upload(d, n)
+    d_box = _box(UNIT)
+    ref = _ref(d, n, 5, UNIT)
+    _assert_is_reference(_run(dev, ctx, n, 5, d_box, d_in), ref, d_in, n, "good call")
+    assert (ctx.launch_info(), ctx.last_kernel_ms(), ctx.stats()) == (info, ms, stats)
+    assert ctx.render_image(p)[0].tobytes() == first.tobytes()
+    # no scene uploaded is not an error
+    fresh = dev.Context(0)
+    try:
+        _assert_is_reference(_run(dev, fresh, n, 5, d_box, d_in), ref, d_in, n, "no scene")
+    finally:
+        fresh.close()
+
+    # errors: refused on the host, nothing launched, the outputs keep their sentinel.  Every address below is either NULL
+    # or inside a live buffer: a misaligned pointer is a live buffer's address plus a few bytes.
+    outs = {k: _padded(None, n, ROW[k]) for k in ALL}
+    outs["count"] = _padded(None, 1, 8)
+    need = dev.lib.srtSortPathsScratchBytes(n)
+    outs["scratch"] = _padded(None, need // 8, 8)
+    B = d_box.data_ptr()
+    O, A, R, G, SL = (d_in[k].data_ptr() for k in ("out", "active", "rays", "rng", "slot"))
+    RO, GO, SO, AO, CN, SC = (outs[k].data_ptr() for k in ("rays", "rng", "slot", "active_out", "count", "scratch"))
+    assert all(a % 16 == 0 for a in (B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC))
+    call = dev.lib.srtSortPathsDevice
+
+    def refused(rc, text):
+        assert rc != 0 and text in dev.lib.srtLastError(ctx.h), (rc, text, dev.lib.srtLastError(ctx.h))
+        torch.cuda.synchronize()
+        for buf in outs.values():
+            assert bool((buf == SENTINEL).all())
+
+    refused(call(ctx.h, -1, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"negative")
+    refused(call(ctx.h, 2 ** 31, 5, B, O, A, R, G, SL, None, None, None, None, CN, SC, need, None), b"32-bit index")
+    for bits in (0, -1, 10, 32):
+        refused(call(ctx.h, n, bits, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"cellBits")
+    refused(call(ctx.h, 0, 0, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"cellBits")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, None, SC, need, None), b"null count")
+    refused(call(ctx.h, 0, 5, B, O, A, R, G, SL, RO, GO, SO, AO, None, SC, need, None), b"null count")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, None, need, None), b"null scratch")
+    refused(call(ctx.h, n, 5, None, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"null box")
+    refused(call(ctx.h, n, 5, B + 2, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"box are not aligned to 4")
+    refused(call(ctx.h, n, 5, B, O, A, None, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"null rays")
+    refused(call(ctx.h, n, 5, B, O, A, None, G, SL, None, GO, SO, AO, CN, SC, need, None), b"null rays")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need - 1, None), b"the scratch holds")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, 0, None), b"the scratch holds")
+    refused(call(ctx.h, n, 5, B, O, A, R, None, SL, RO, GO, SO, AO, CN, SC, need, None), b"rng states without rng states")
+    refused(call(ctx.h, n, 5, B, O + 8, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"outputs are not aligned to 16")
+    refused(call(ctx.h, n, 5, B, O, A, R + 2, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"rays are not aligned to 4")
+    refused(call(ctx.h, n, 5, B, O, A, R + 2, G, SL, None, GO, SO, AO, CN, SC, need, None), b"rays are not aligned to 4")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO + 2, GO, SO, AO, CN, SC, need, None), b"rays are not aligned to 4")
+    refused(call(ctx.h, n, 5, B, O, A, R, G + 4, SL, RO, GO, SO, AO, CN, SC, need, None), b"rng states are not aligned to 8")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO + 4, SO, AO, CN, SC, need, None), b"rng states are not aligned to 8")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL + 2, RO, GO, SO, AO, CN, SC, need, None), b"slots are not aligned to 4")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO + 2, AO, CN, SC, need, None), b"slots are not aligned to 4")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN + 4, SC, need, None), b"count are not aligned to 8")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC + 4, need, None), b"scratch are not aligned to 8")
+    # overlap: in place, shifted, an output on another output, on the count, on the scratch, on a predicate, on the box
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, R, GO, SO, AO, CN, SC, need, None), b"overlap")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, None, GO, R, AO, CN, SC, need, None), b"overlap")  # the rays are read without dRaysOut
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, G, SO, AO, CN, SC, need, None), b"overlap")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SL, AO, CN, SC, need, None), b"overlap")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, R + 36 * (n - 1), GO, SO, AO, CN, SC, need, None), b"overlap")
+    refused(call(ctx.h, n // 2, 5, B, O, A, R, G, SL, RO, RO + 8 * (n // 2 - 1), SO, AO, CN, SC, need, None), b"overlap")
+    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, GO + 8, SC, need, None), b"overlap")
+    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SO + 8, need, None), b"overlap")
+    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, SC, SC, need, None), b"overlap")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, O, CN, SC, need, None), b"overlap")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, A, AO, CN, SC, need, None), b"overlap")
+    refused(call(ctx.h, n - 1, 5, B, O, A, R, G, SL, RO, GO, SO, A + 1, CN, SC, need, None), b"overlap")  # a shifted mask is not in place
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, O, need, None), b"overlap")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, B + 8, SC, need, None), b"overlap the box")
+    refused(call(ctx.h, n, 5, SO + 16, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"overlap the box")
+    assert call(None, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None) != 0
+    # an input whose output is NULL is ignored, overlaps and misalignment included (the rays are always read)
+    assert call(ctx.h, n, 5, B, O, A, R, GO + 4, SO + 2, None, None, None, None, CN, SC, need, None) == 0, dev.lib.srtLastError(ctx.h)
+    torch.cuda.synchronize()
+    assert int(outs["count"].cpu().numpy()[:8].view(np.int64)[0]) == ref["count"]
+    for k in ALL:
+        assert bool((outs[k] == SENTINEL).all())
+    for k, t in d_in.items():
+        assert t.cpu().numpy()[:n * ROW_IN[k]].tobytes() == np.ascontiguousarray(d[k]).tobytes()
+    with pytest.raises(dev.SrtError, match="overlap"):
+        both = torch.zeros((n, 9), dtype=torch.float32, device="cuda")
+        ctx.sort_paths_device(5, rays=both, rays_out=both)

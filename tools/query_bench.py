@@ -20,11 +20,24 @@ srtRenderTiles on masterchief (reference tree FAITHFUL, PLOC tree CLOSEST) and s
 whole batch (rays, states and slots moved), timed with events like the queries above.  `whole` is the same frame through
 srtTracePathsDevice (whole=True: one kernel per batch) as the library ships it -- a wave claims entries once a quarter of it
 is idle (tunable paths_refill_min 16) -- and `whole_refill1` with a refill on every trip; `peak_mb` is torch's peak
-allocation over one frame of `whole` and of the compacted fused loop.
+allocation over one frame of `whole` and of the compacted fused loop.  --sort-bits 3,5,7,9 adds the fused loop with
+srtSortPathsDevice in the place of the compaction (pathloop.render(sort=b)) at each of those cell sizes, as variants that
+alternate with the others; --variants NAMES keeps the listed variants only (the yardstick of a sorted loop is
+fused_compact measured in the same session).
+
+--sort-ao measures the AO set again with srtSortPathsDevice in front of srtOccludedDevice: `any` on the rays as they are,
+on rays sorted once outside the clock (`sorted_b`), and the sort together with the query (`sort_and_any_b`, the box from
+the origins included), per cell size of --sort-bits; the variants alternate, --warmup-loops + --loop-reps rounds of
+--steps back-to-back calls, median and spread of the rounds.
+--sort-call SPP times --steps srtSortPathsDevice calls behind the first bounce of all W * H * SPP camera rays at the
+first cell size of --sort-bits (run it under a kernel trace for the split into key, sort and gather).
 
 usage: python tools/query_bench.py [--steps 200] [--warmup 5] [--host-steps 3] [--cases masterchief,soup_200k,soup_1m] [--ao-rays 4]
                                    [--ao-radius 0.1] [--ao-png FILE] [--width 1280] [--height 720]
-       python tools/query_bench.py --path-loop [--loop-reps 5] [--warmup-loops 1] [--cases masterchief,soup_200k]"""
+       python tools/query_bench.py --path-loop [--loop-reps 5] [--warmup-loops 1] [--cases masterchief,soup_200k,soup_1m]
+                                   [--sort-bits 3,5,7,9] [--variants fused_compact,fused_sort_3,...]
+       python tools/query_bench.py --sort-ao [--sort-bits 3,5,7,9] [--steps 20] [--loop-reps 5] [--cases ...]
+       python tools/query_bench.py --sort-call 16 [--sort-bits 5] [--steps 5] [--cases soup_200k]"""
 import argparse
 import importlib
 import json
@@ -148,6 +161,95 @@ def compact_call(ctx, p, traversal, steps, warmup):
     return {"n": n, "kept_share": int(count) / float(n), "ms": ms, "steps": steps}
 
 
+def median_and_spread(v):
+    return {"ms": float(np.median(v)), "spread_ms": [min(v), max(v)]}
+
+
+def sort_bits(a):
+    return [int(b) for b in a.sort_bits.split(",") if b]
+
+
+def sort_ao(a):
+    """--sort-ao: srtOccludedDevice on the AO set of every case as it is, on the set sorted once outside the clock, and with
+    the sort (and the box from the origins) inside it."""
+    ctx = dev.Context(0)
+    cam = dev.make_camera(abi.default_camera_params())
+    W, H = a.width, a.height
+    result = {"device": ctx.device_info()["name"], "width": W, "height": H, "ao_rays_per_pixel": a.ao_rays, "steps": a.steps,
+              "reps": a.loop_reps, "note": "ms per call: median and (min, max) over the alternating rounds of `steps` calls", "cases": {}}
+    stream = torch.cuda.Stream()
+    for case in a.cases.split(","):
+        sb = scene(case)
+        ctx.upload_scene(sb)
+        ctx.set_camera(cam)
+        faithful = all(it.builder == abi.SRT_BUILDER_REFERENCE for it in sb.world)
+        p = abi.default_render_params(W, H, 1, 1, seed=1, traversal=abi.SRT_TRAVERSE_FAITHFUL if faithful else abi.SRT_TRAVERSE_CLOSEST)
+        planes = ctx.render_features(p, abi.SRT_FEATURE_NORMAL | abi.SRT_FEATURE_POSITION)
+        rays, _ = ao_rays(planes, a.ao_rays, a.ao_radius * 6.0, 0.5 * (cam.time0 + cam.time1))
+        n = rays.shape[0]
+        scratch = torch.empty((ctx.sort_scratch_bytes(n),), dtype=torch.uint8, device="cuda")
+        rays_out, slot_out = torch.empty_like(rays), torch.empty((n,), dtype=torch.int32, device="cuda")
+        count = torch.empty((1,), dtype=torch.int64, device="cuda")
+        want = ctx.occluded_device(rays)
+        variants = {"any": lambda: ctx.occluded_device(rays, stream=stream)}
+        torch.cuda.synchronize()
+        for b in sort_bits(a):
+            ordered, _, slot, _, _ = ctx.sort_paths_device(b, rays=rays, scratch=scratch)
+            back = torch.empty_like(want)
+            back.index_copy_(0, slot.to(torch.int64), ctx.occluded_device(ordered))
+            assert torch.equal(back, want), "occlusion of the sorted rays, scattered back, differs"
+            variants["sorted_%d" % b] = lambda ordered=ordered: ctx.occluded_device(ordered, stream=stream)
+
+            def both(b=b):
+                ctx.sort_paths_device(b, rays=rays, rays_out=rays_out, slot_out=slot_out, count=count, scratch=scratch, stream=stream)
+                ctx.occluded_device(rays_out, stream=stream)
+            variants["sort_and_any_%d" % b] = both
+        torch.cuda.synchronize()
+        stream.wait_stream(torch.cuda.current_stream())
+        ms = {k: [] for k in variants}
+        for round_ in range(a.warmup_loops + a.loop_reps):
+            for name, fn in variants.items():
+                t = event_ms(stream, fn, a.steps, 1)
+                if round_ >= a.warmup_loops:
+                    ms[name].append(t)
+        out = {"rays": n, "bvh_depth": ctx.bvh_depth(), "occluded_share": float((want != 0).float().mean())}
+        for name, v in ms.items():
+            out[name] = dict(median_and_spread(v), mrays_s=n / float(np.median(v)) * 1e-3)
+        result["cases"][case] = out
+    ctx.close()
+    print(json.dumps(result))
+
+
+def sort_call(a):
+    """--sort-call SPP: srtSortPathsDevice behind the first bounce of all W * H * SPP camera rays of the first case, --steps
+    times at the first cell size, rays, states and slots moved into buffers allocated once, the box made once."""
+    ctx = dev.Context(0)
+    ctx.upload_scene(scene(a.cases.split(",")[0]))
+    ctx.set_camera(dev.make_camera(abi.default_camera_params()))
+    bits = sort_bits(a)[0]
+    p = abi.default_render_params(a.width, a.height, a.sort_call, 4, seed=1, traversal=abi.SRT_TRAVERSE_CLOSEST)
+    rays, rng = ctx.camera_rays_device(p)
+    out, _ = ctx.path_step_device(rays, rng, abi.SRT_TRAVERSE_CLOSEST, rays_out=rays)
+    n = rays.shape[0]
+    box = ctx.origin_box(rays, out)
+    rays_out, rng_out = torch.empty_like(rays), torch.empty_like(rng)
+    slot_out = torch.empty((n,), dtype=torch.int32, device="cuda")
+    count = torch.empty((1,), dtype=torch.int64, device="cuda")
+    scratch = torch.empty((ctx.sort_scratch_bytes(n),), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    ms = event_ms(stream, lambda: ctx.sort_paths_device(bits, rays=rays, out=out, box=box, rng=rng, rays_out=rays_out, rng_out=rng_out,
+                                                        slot_out=slot_out, count=count, scratch=scratch, stream=stream), a.steps, 1)
+    compact_scratch = torch.empty((ctx.compact_scratch_bytes(n),), dtype=torch.uint8, device="cuda")
+    compact_ms = event_ms(stream, lambda: ctx.compact_paths_device(out=out, rays=rays, rng=rng, rays_out=rays_out, rng_out=rng_out,
+                                                                   slot_out=slot_out, count=count, scratch=compact_scratch, stream=stream),
+                          a.steps, 1)
+    print(json.dumps({"device": ctx.device_info()["name"], "case": a.cases.split(",")[0], "n": n, "cell_bits": bits,
+                      "kept_share": int(count) / float(n), "steps": a.steps, "sort_ms": ms, "compact_ms": compact_ms,
+                      "scratch_mb": ctx.sort_scratch_bytes(n) / 2.0 ** 20}))
+    ctx.close()
+
+
 def path_loop(a):
     """--path-loop: the user-land path tracer (pathloop.render over srtCameraRaysDevice + srtPathStepDevice, fused, and
     over srtTraceRaysDevice(records) + srtScatterRaysDevice, unfused) against srtRenderTiles of the same samples.
@@ -161,12 +263,15 @@ def path_loop(a):
               "note": "msamples_s = W * H * spp / median ms; spread = (min ms, max ms) over the alternating repetitions", "cases": {}}
     cases = [("masterchief_reference_faithful", "masterchief", None, abi.SRT_TRAVERSE_FAITHFUL),
              ("masterchief_ploc_closest", "masterchief", abi.SRT_BUILDER_PLOC, abi.SRT_TRAVERSE_CLOSEST),
-             ("soup_200k_ploc_closest", "soup_200k", None, abi.SRT_TRAVERSE_CLOSEST)]
+             ("soup_200k_ploc_closest", "soup_200k", None, abi.SRT_TRAVERSE_CLOSEST),
+             ("soup_1m_ploc_closest", "soup_1m", None, abi.SRT_TRAVERSE_CLOSEST)]
     stream = torch.cuda.current_stream()
     refill_default = ctx.get_tunable("paths_refill_min")
     for label, case, builder, traversal in cases:
         if case not in a.cases.split(","):
             continue
+        if (case == "soup_1m" and not sort_bits(a)) or (label == "masterchief_reference_faithful" and sort_bits(a)):
+            continue  # the sorted loops: masterchief's PLOC tree with CLOSEST steps, and soup_1m as well
         sb = scene(case)
         if builder is not None:
             for it in sb.world:
@@ -190,6 +295,10 @@ def path_loop(a):
                         "whole": lambda: whole(refill_default),
                         "whole_refill1": lambda: whole(1),
                         "render_tiles": lambda: ctx.render_tiles(p, tiles.data_ptr(), stream.cuda_stream)}
+            for b in sort_bits(a):
+                variants["fused_sort_%d" % b] = lambda b=b: pathloop.render(ctx, p, fused=True, traversal=traversal, sort=b)
+            if a.variants:
+                variants = {k: v for k, v in variants.items() if k in a.variants.split(",")}
             ms = {k: [] for k in variants}
             for rep in range(a.warmup_loops + a.loop_reps):
                 for name, fn in variants.items():
@@ -209,7 +318,7 @@ def path_loop(a):
                 entry[name] = {"ms": med, "spread_ms": [min(v), max(v)], "msamples_s": W * H * spp / med * 1e-3}
             entry["compact_call"] = compact_call(ctx, p, traversal, a.steps, a.warmup)
             entry["peak_mb"] = {}
-            for name in ("whole", "fused_compact"):
+            for name in [k for k in ("whole", "fused_compact", "fused_sort_5") if k in variants]:
                 torch.cuda.synchronize()
                 torch.cuda.empty_cache()
                 torch.cuda.reset_peak_memory_stats()
@@ -232,6 +341,10 @@ def main():
     ap.add_argument("--steps", type=int, default=200, help="timed device calls per figure (a call is 0.2 - 3 ms)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--host-steps", type=int, default=3, help="timed srtTraceRays calls (10 - 70 ms each)")
+    ap.add_argument("--sort-bits", default="", help="cell bits per axis of the sorted variants, e.g. 3,5,7,9")
+    ap.add_argument("--variants", default="", help="--path-loop: only these variants")
+    ap.add_argument("--sort-ao", action="store_true", help="srtOccludedDevice on the AO set, sorted and unsorted")
+    ap.add_argument("--sort-call", type=int, default=0, metavar="SPP", help="srtSortPathsDevice calls behind the first bounce of W * H * SPP rays")
     ap.add_argument("--cases", default="masterchief,soup_200k,soup_1m")
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
@@ -241,6 +354,10 @@ def main():
     a = ap.parse_args()
     if a.path_loop:
         return path_loop(a)
+    if a.sort_ao:
+        return sort_ao(a)
+    if a.sort_call:
+        return sort_call(a)
     ctx = dev.Context(0)
     cam = dev.make_camera(abi.default_camera_params())
     W, H = a.width, a.height
