@@ -11,6 +11,13 @@
 //          Before it writes, the program follows the links from every entry and checks that it meets each of that tree's
 //          kept records once, in order, that every node word lies inside the sequence, and that srtWfRootWord leaves the
 //          entry words as they are (the launch hands them to the kernel in the world list's place); exit status 3 otherwise.
+//   srt_regroup_probe head <in.bin> <out.bin>
+//     in:  int32 numNodes, numWorld, numKinds; the node records and the world list with primitives as ~index; one byte per
+//          index, != 0 = a sphere
+//     out: int32 ok, int32 head -- srtRegroupHeadOfKinds: the head word of the sequence's walks over the device's references
+//          ~(index << 1 | sphere), 0 where the walks have none; ok = 0 (and head 0) for an input it refuses.  Where there is a
+//          head the program decodes it as the kernel does and checks that its one or two objects are spheres of the list;
+//          exit status 3 otherwise.
 //   srt_regroup_probe gate <in.bin> <out.bin>
 //     in:  int32 n; n cases of 20 floats: the leaf box (min.xyz, max.xyz), the gate box (min.xyz, max.xyz), the ray's origin
 //          and direction, tMin, tMax
@@ -100,6 +107,27 @@ static int walk(FILE* in, FILE* out) {
   return 0;
 }
 
+static int head(FILE* in, FILE* out) {
+  int32_t n[3];
+  if (fread(n, 4, 3, in) != 3 || n[0] < 0 || n[1] < 0 || n[2] < 0) return 1;
+  std::vector<float4> nodes(2 * (size_t)n[0]);
+  std::vector<int32_t> world(n[1]);
+  std::vector<uint8_t> kinds(n[2]);
+  if (fread(nodes.data(), sizeof(float4), nodes.size(), in) != nodes.size()) return 1;
+  if (fread(world.data(), 4, world.size(), in) != world.size()) return 1;
+  if (fread(kinds.data(), 1, kinds.size(), in) != kinds.size()) return 1;
+  int32_t r[2] = {0, 0};
+  r[0] = srtRegroupHeadOfKinds(nodes, world, kinds.data(), n[2], r[1]) ? 1 : 0;
+  if (!r[0] && r[1] != 0) return 3;
+  if (r[1] != 0) {
+    auto sphereOfList = [&](int32_t ref) { return srtWfAtPrim(ref) && (~ref & 1) && (~ref >> 1) < n[2] && kinds[(size_t)(~ref >> 1)] != 0; };
+    if (world.size() != 1 || !srtWfAtPrim(r[1]) || !sphereOfList(srtWfLeafFirst(r[1]))) return 3;
+    if (srtWfLeafHasSecond(r[1]) && (!sphereOfList(srtWfLeafFirst(srtWfLeafRest(r[1]))) || srtWfLeafHasSecond(srtWfLeafRest(r[1])))) return 3;
+  }
+  fwrite(r, 4, 2, out);
+  return 0;
+}
+
 static int gate(FILE* in, FILE* out) {
   int32_t n;
   if (fread(&n, 4, 1, in) != 1 || n < 0) return 1;
@@ -125,6 +153,7 @@ int main(int argc, char** argv) {
   int rc = 2;
   if (!strcmp(argv[1], "regroup")) rc = regroup(in, out);
   if (!strcmp(argv[1], "walk")) rc = walk(in, out);
+  if (!strcmp(argv[1], "head")) rc = head(in, out);
   if (!strcmp(argv[1], "gate")) rc = gate(in, out);
   fclose(in);
   return fclose(out) ? 1 : rc;

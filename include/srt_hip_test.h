@@ -68,8 +68,9 @@ int srtGetShadeProfile(SrtContext* ctx, uint64_t* out10);
 /* Step profile of the most recent launch of the path-pool kernel's profiling variant (tunable "wf_profile" = 1;
  * csrc/srt_wavefront.hip): out46 = { clocks[12], executions[12], lanes[12] } for the step kinds node visit, primitive
  * test, swap, hit step of class 0 / 1 / 2, restart, idle, lost claim, item pull, visit of a node outside LDS (hybrid form:
- * the clocks are the wait for the records plus the visit), and an eleventh slot whose clocks word counts the primitive-step
- * executions that ran the exact triangle test and whose executions word counts the lanes the triangle certificate left
+ * the clocks are the wait for the records plus the visit; whole-tree form: no clocks, its executions word counts the swap
+ * steps that ran the head of the new rays' walks -- tunable "wf_head" -- and its lanes word those rays), and an eleventh
+ * slot whose clocks word counts the primitive-step executions that ran the exact triangle test and whose executions word counts the lanes the triangle certificate left
  * undecided (its lanes word: the hybrid form's near lanes); scheduling clocks, total wave clocks; then what the
  * scheduling decisions that looked at the rings saw, summed: decisions, lanes at nodes / at primitives / finished / idle,
  * READY fill, fill of the fullest served ring, RESTART fill. */
@@ -116,6 +117,19 @@ int srtTestGetRegroup(SrtContext* ctx, float* outNodes8, int32_t* outLinks, int3
 int srtTestRegroupWalk(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, uint8_t* outKeep, int32_t* outSrc,
                        int32_t* outLinks, int32_t* outEntry, int32_t* count);
 int srtTestGetRegroupWalk(SrtContext* ctx, uint8_t* outKeep, int32_t* outSrc, int32_t* outLinks, int32_t* outEntry, int32_t capacity, int32_t* count);
+
+/* The HEAD of the sequence's walks (csrc/srt_regroup.h SrtRegroupWalk::head; tunable "wf_head", default 1, 0 = off): where the
+ * world list is one tree, record 0 of its sequence is a leaf and every object of that leaf is a sphere, every walk begins with
+ * that leaf's box test, its one or two sphere tests and a jump to its miss word.  The path-pool kernel's whole-tree form then
+ * runs these where its swap step sets a new ray up, for all the new rays of the wave at once, and starts their walks at the
+ * miss word; the head word is the leaf word (csrc/srt_wf_links.h srtWfLeafWord), 0 = no head.  Accumulators are bit-identical.
+ * srtTestWfHead (host only, no device): the word for a node array in srtTestRegroupWalk's format whose primitives are
+ * ~index -- as the CPU oracle's trees have them -- a world list of the same references, and the kind of every primitive,
+ * kinds[index] != 0 = a sphere.  The hook rewrites every reference to the device's ~(index << 1 | sphere) and asks
+ * srtRegroupWalk -> *outHead.  Returns 1; 0 (and *outHead = 0) for an array srtTestRegroupWalk refuses, an index outside
+ * kinds[] or beyond the 15 bits of a leaf word's half; -1 on a null argument. */
+int srtTestWfHead(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, const uint8_t* kinds, int32_t numKinds,
+                  int32_t* outHead);
 
 /* Reads back what the near-child-first traversal walks for world item `item` (host-built and device-built trees alike), as
  * it lies in device memory: the item's slice of DevScene::nodeAxis -> outAxis[count] (the split axis of each node, 3 = none)

@@ -100,6 +100,10 @@ const TunableName kTunables[] = {
     // one.  2 = its walk sequence, the gates that rarely cull a ray elided (srtRegroupWalk); 1 = the binary regrouped tree;
     // 0 = the reference tree: the same accumulators from about twice the node visits.  Read at every launch.
     {"wf_regroup", "SRT_WF_REGROUP", &Tunables::wfRegroup, 2},
+    // path-pool kernel walking the sequence (wf_regroup 2): where every walk begins at a leaf of spheres alone (the headline's
+    // ground: DevScene::wfHead), the swap step tests that leaf for the rays it sets up and starts their walks behind it.
+    // 0 = every walk starts at the sequence's entry.  The same accumulators either way.  Read at every launch.
+    {"wf_head", "SRT_WF_HEAD", &Tunables::wfHead, 1},
     // srtDenoise: a-trous levels of step <= this stage their (16 + 4 step)^2 window in LDS, larger steps read through the
     // caches (srt_denoise.hip; 8 at most, 0 = never) -- profiles/r05/denoise_bench.json
     {"denoise_lds_step", "SRT_DENOISE_LDS_STEP", &Tunables::denoiseLdsStep, 4},
@@ -168,6 +172,7 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   if (!h.nodesRg.empty() && (uploadVec(ctx, h.nodesRg, &s.nodesRg) || uploadVec(ctx, h.nodeThreadRg, &s.nodeThreadRg))) return 1;
   if (!h.walkSeq.empty() && uploadVec(ctx, h.walkSeq, &s.walkSeq)) return 1;
   s.numWalk = h.walkSeq.empty() ? 0 : h.numWalk;
+  s.wfHead = h.walkSeq.empty() ? 0 : h.wfHead;
   if (!h.nodesWf.empty() && (uploadVec(ctx, h.nodesWf, &s.nodesWf) || uploadVec(ctx, h.worldWf, &s.worldWf) || uploadVec(ctx, h.primSecond, &s.primSecond))) return 1;
   if (uploadVec(ctx, h.primClass, &s.primClass, 16) || uploadVec(ctx, h.nodeAxis, &s.nodeAxis, 64) || uploadVec(ctx, h.nodes, &s.nodes) ||
       uploadVec(ctx, h.triTest, &s.triTest) || uploadVec(ctx, h.triFast, &s.triFast) || uploadVec(ctx, h.triShade, &s.triShade) || uploadVec(ctx, h.spheres, &s.spheres) ||
@@ -476,6 +481,14 @@ int srtTestRegroupWalk(const float* nodes8, int32_t numNodes, const int32_t* wor
   if (*count) memcpy(outLinks, walk.links.data(), walk.links.size() * sizeof(int32_t));
   if (numWorld) memcpy(outEntry, walk.entry.data(), walk.entry.size() * sizeof(int32_t));
   return 1;
+}
+/* include/srt_hip_test.h: host-only hook for SrtRegroupWalk::head over an array whose primitives are ~(index into kinds) */
+int srtTestWfHead(const float* nodes8, int32_t numNodes, const int32_t* world, int32_t numWorld, const uint8_t* kinds, int32_t numKinds,
+                  int32_t* outHead) {
+  if (!nodes8 || !world || !kinds || !outHead || numNodes < 0 || numWorld < 0 || numKinds < 0) return -1;
+  std::vector<float4> nodes(2 * (size_t)numNodes);
+  if (numNodes) memcpy(nodes.data(), nodes8, nodes.size() * sizeof(float4));
+  return srtRegroupHeadOfKinds(nodes, std::vector<int32_t>(world, world + numWorld), kinds, numKinds, *outHead) ? 1 : 0;
 }
 int srtTestGetRegroupWalk(SrtContext* ctx, uint8_t* outKeep, int32_t* outSrc, int32_t* outLinks, int32_t* outEntry, int32_t capacity, int32_t* count) {
   if (!ctx || !count) return 1;

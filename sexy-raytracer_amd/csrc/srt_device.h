@@ -127,6 +127,10 @@ struct DevScene {
   // the launch hands the entry words to the kernel in `world`'s place.  Null / 0: not built, or not asked for.
   const int32_t* walkSeq;
   int32_t numWalk;
+  // ... and the HEAD of its walks (SrtRegroupWalk::head, tunable "wf_head"): the leaf word of sequence record 0 where every
+  // walk begins at that leaf and its objects are spheres, else 0.  A launch that does not walk the sequence hands over 0.
+  // The kernel reads it from the argument segment inside its swap step.  (In the four bytes behind numWalk: no field moves.)
+  int32_t wfHead;
 };
 
 struct DevCamera {

@@ -21,7 +21,7 @@ struct Tunables {
   int ldsTree;
   int wavefront, wfPool, wfSwapMin, wfSwapBig, wfProfile;
   int wfHybrid, wfResidentMax, wfFarRounds;
-  int wfRegroup;
+  int wfRegroup, wfHead;
   int denoiseLdsStep;
   int triCert;
   int pathsRefillMin;

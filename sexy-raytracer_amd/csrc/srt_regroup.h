@@ -169,6 +169,11 @@ struct SrtRegroupWalk {
   std::vector<int32_t> src;    // per record of the sequence: its record in the binary array
   std::vector<int32_t> links;  // per record of the sequence: its hit word, its miss word
   std::vector<int32_t> entry;  // per world item: where its walk starts (srtWfSeqEntryWord)
+  // The HEAD of every walk (tunable "wf_head"): record 0's leaf word where the world list is ONE tree whose first kept record
+  // is a leaf of spheres alone (one or two; ~reference & 1), else 0.  No gate stands in front of such a leaf and its hit and
+  // miss words lead to the same successor, so every walk of the scene begins with its box test, its sphere tests and a jump
+  // to its miss word: the path-pool kernel runs them where it sets a new ray up (srt_wavefront.hip swapStep).
+  int32_t head = 0;
 };
 
 // rg: a regrouped array (srtRegroupNodes' output; any array of pre-order trees of two-node / two-primitive nodes will do);
@@ -252,6 +257,38 @@ inline bool srtRegroupWalk(const std::vector<float4>& rg, const std::vector<int3
     }
     out.entry[wi] = srtWfSeqEntryWord(world[wi], next[root]);
   }
+  if (world.size() == 1 && world[0] >= 0 && !out.src.empty()) {
+    const size_t i = (size_t)out.src[0];
+    const int32_t l = refOf(rg, 2 * i), r = refOf(rg, 2 * i + 1);
+    if (l < 0 && (~l & 1) && (~r & 1)) out.head = srtWfLeafWord(l, r);
+  }
   out.keep.swap(keep);
+  return true;
+}
+
+// The head word of an array whose primitive references are ~index into a list of kinds (kinds[index] != 0: a sphere), as the
+// CPU oracle's trees have them, worded over the device's references ~(index << 1 | sphere): srtTestWfHead
+// (include/srt_hip_test.h) and examples/regroup_probe.cpp's mode `head`.  False, with head = 0, for what srtRegroupWalk
+// refuses, an index outside the list or beyond the 15 bits of a leaf word's half (srt_wf_links.h).
+inline bool srtRegroupHeadOfKinds(std::vector<float4> nodes, std::vector<int32_t> world, const uint8_t* kinds, int32_t numKinds, int32_t& head) {
+  head = 0;
+  auto deviceRef = [&](int32_t& ref) {
+    const int32_t index = ~ref;
+    if (index >= numKinds || index > 0x3ffe) return false;
+    ref = ~(index << 1 | (kinds[index] ? 1 : 0));
+    return true;
+  };
+  for (float4& v : nodes) {
+    int32_t ref;
+    memcpy(&ref, &v.w, 4);
+    if (ref >= 0) continue;
+    if (!deviceRef(ref)) return false;
+    memcpy(&v.w, &ref, 4);
+  }
+  for (int32_t& ref : world)
+    if (ref < 0 && !deviceRef(ref)) return false;
+  SrtRegroupWalk walk;
+  if (!srtRegroupWalk(nodes, world, walk)) return false;
+  head = walk.head;
   return true;
 }

@@ -127,9 +127,11 @@ int srtRenderTilesImpl(SrtContext* ctx, const SrtRenderParams* p, void* dAccumTi
   // words behind them, handed over in the world list's place (srt_wf_links.h: srtWfRootWord leaves an entry word as it is;
   // the path-pool kernel reads `world` for nothing else), so the kernel holds no value it did not hold before
   if (!a.scene.nodesRg || ctx->tun.wfRegroup < 2 || !a.scene.walkSeq)
-    a.scene.walkSeq = nullptr, a.scene.numWalk = 0;
+    a.scene.walkSeq = nullptr, a.scene.numWalk = 0, a.scene.wfHead = 0;
   else
     a.scene.world = a.scene.walkSeq + 3 * (size_t)a.scene.numWalk;
+  // ... and the head of its walks (DevScene::wfHead) goes with it, unless the tunable "wf_head" takes it out
+  if (ctx->tun.wfHead <= 0) a.scene.wfHead = 0;
   const bool pathPool = srtFormIsPathPool(plan.form);
   const RenderKernel kernel = pathPool ? srt_render_wf_kernel_for(&plan) : srt_render_kernel_for(&plan);
   if (plan.lds > 64 * 1024)

@@ -517,6 +517,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
       SrtRegroupWalk walk;
       if (!h.nodesRg.empty() && srtRegroupWalk(h.nodesRg, h.world, walk)) {
         h.numWalk = (int32_t)walk.src.size();
+        h.wfHead = walk.head;
         h.walkSeq.reserve(3 * walk.src.size() + walk.entry.size());
         for (size_t j = 0; j < walk.src.size(); ++j) h.walkSeq.insert(h.walkSeq.end(), {walk.src[j], walk.links[2 * j], walk.links[2 * j + 1]});
         h.walkSeq.insert(h.walkSeq.end(), walk.entry.begin(), walk.entry.end());

@@ -83,6 +83,7 @@ struct HostScene {
   // word, miss word), numWalk of them, then one entry word per world item.  Empty with nodesRg
   std::vector<int32_t> walkSeq;
   int32_t numWalk = 0;
+  int32_t wfHead = 0;  // SrtRegroupWalk::head: the leaf word every walk of the sequence begins with, 0 = none
   std::vector<float4> nodesWf;     // empty: no hybrid records
   std::vector<int32_t> worldWf, primSecond;
   int32_t wfResident = 0;

@@ -60,12 +60,35 @@ __device__ __forceinline__ void bufStore1(Rsrc r, int off, uint32_t v) { __built
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const f32x4 LdsVec4;  // a 16-byte slot addressed by its LDS byte offset
 __device__ __forceinline__ uint32_t bufLoad1(Rsrc r, int off) { return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0); }
+
+// sphere::hit on the record at byte offset `off` of DevScene::spheres (through its buffer resource): the one statement for
+// the primitive step and for the head of a walk (swapStep)
+__device__ __forceinline__ bool wfSphereHit(Rsrc rsSpheres, int off, const Ray& ray, float rayA, float tMin, float closest, float& t) {
+  const float4 s0 = bufLoad4(rsSpheres, off), s1 = bufLoad4(rsSpheres, off + 16);
+  V3 center = mk(s0.x, s0.y, s0.z);
+  if (__float_as_int(s1.w) & (1 << 30)) {  // sphere.h:47-52
+    const float4 s2 = bufLoad4(rsSpheres, off + 32);
+    center = center + ((ray.time - s2.x) / (s2.y - s2.x)) * (mk(s1.x, s1.y, s1.z) - center);
+  }
+  return sphereHitV(center, s0.w, ray, rayA, tMin, closest, t);
+}
+
+// DevScene::wfHead of the launch, read from the kernel-argument segment where it is called (the swap step): one scalar
+// load per swap, and no scalar that lives across the traversal loop (the camera row)
+__device__ __forceinline__ int32_t wfHeadFromKernarg() {
+  typedef __attribute__((address_space(4))) const unsigned char ConstByte;
+  typedef __attribute__((address_space(4))) const int32_t ConstWord;
+  ConstByte* p = (ConstByte*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));  // not hoisted out of the loop it is called in
+  return *(ConstWord*)(p + offsetof(RenderArgs, scene) + offsetof(DevScene, wfHead));
+}
 }  // namespace
 
 // SINGLE: the world list is one tree (as in srt_render_kernel).  PROFILE (tunable wf_profile, tools/wf_profile.py): per
 // step kind, the clocks the waves spent in it, its executions and the lanes they served -> RenderArgs::stats[32 + ...]
 // (kinds: 0 node visit, 1 primitive test, 2 swap, 3-5 hit step per class, 6 restart, 7 idle, 8 lost claim, 9 item pull,
-// 10 visit of a node outside LDS -- hybrid form: wait for the records + visit; its clocks are part of kind 0's as well).
+// 10 visit of a node outside LDS -- hybrid form: wait for the records + visit; its clocks are part of kind 0's as well;
+// whole-tree form: no clocks, the swap steps that ran the head of the new rays' walks and the lanes they ran it for).
 #define WF_PROF_KINDS 12
 // HYBRID: the tree does not fit into LDS.  Its top -- the first `resident` records of DevScene::nodesWf, the boxes a ray is
 // most likely to meet -- is kept there, the other records are read from global memory where the walk reaches them; a
@@ -300,14 +323,7 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
           bool ok;
           if (pr & 1) {
             if constexpr (COUNT) cnt[5]++;
-            const int off = (pr >> 1) * 48;
-            const float4 s0 = bufLoad4(rsSpheres, off), s1 = bufLoad4(rsSpheres, off + 16);
-            V3 center = mk(s0.x, s0.y, s0.z);
-            if (__float_as_int(s1.w) & (1 << 30)) {  // sphere.h:47-52
-              const float4 s2 = bufLoad4(rsSpheres, off + 32);
-              center = center + ((ray.time - s2.x) / (s2.y - s2.x)) * (mk(s1.x, s1.y, s1.z) - center);
-            }
-            ok = sphereHitV(center, s0.w, ray, rayA, a.tMin, closest, t);
+            ok = wfSphereHit(rsSpheres, (pr >> 1) * 48, ray, rayA, a.tMin, closest, t);
           } else {
             if constexpr (COUNT) cnt[4]++;
             if constexpr (HYBRID) {
@@ -505,12 +521,47 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
         hitRef = DONE;
       }
       const unsigned long long q2 = PROFILE ? clock64() : 0;
+      // The HEAD of the walks (DevScene::wfHead; the instances that walk the sequence): a leaf word != 0 says that every walk
+      // of this launch begins at that leaf -- no gate in front of it, spheres alone in it, its hit and miss words lead to the
+      // same successor.  Its visit and its one or two sphere tests run here, for all the new rays at once and on wave-uniform
+      // records, and the walks start at its miss word: what the loop would have done with these lanes in a node burst at
+      // partial fill and two primitive rounds shared with lanes at triangles.  Same calls, same values, same order.
+      const int32_t head = !HYBRID && !COUNT ? wfHeadFromKernarg() : 0;
       if (id >= 0) {
         ray.o = mk(A.x, A.y, A.z);
         ray.d = mk(B.x, B.y, B.z);
         ray.time = A.w;
         path = id;
         startTraversal();
+        if constexpr (!HYBRID && !COUNT) {
+          if (head != 0) {
+            // visit()'s verdict for a leaf, bit for bit; `cur` is the entry word, the record's LDS address
+            const LdsVec4* rec = (const LdsVec4*)(uintptr_t)(uint32_t)cur;
+            const f32x4 r0 = rec[0], r1 = rec[1];
+            const float4 n0 = make_float4(r0.x, r0.y, r0.z, r0.w), n1 = make_float4(r1.x, r1.y, r1.z, r1.w);
+            bool undecided;
+            bool hitBox = boxHitSign<true>(n0, n1, rp, rq, negOR, slabTol, a.tMin, closest, undecided);
+            if (__ballot(undecided)) {
+              if (undecided) hitBox = boxHit(n0, n1, ray, a.tMin, closest);
+            }
+            if (hitBox) {
+              float t;
+              const int first = srtWfLeafFirst(head);
+              if (wfSphereHit(rsSpheres, (~first >> 1) * 48, ray, rayA, a.tMin, closest, t)) {
+                closest = t;
+                hitRef = first;
+              }
+              if (srtWfLeafHasSecond(head)) {
+                const int second = srtWfLeafFirst(srtWfLeafRest(head));
+                if (wfSphereHit(rsSpheres, (~second >> 1) * 48, ray, rayA, a.tMin, closest, t)) {
+                  closest = t;
+                  hitRef = second;
+                }
+              }
+            }
+            cur = __float_as_int(n1.w);  // the leaf's miss word (DONE: a tree of this one leaf -- the next swap hands the walk over)
+          }
+        }
         if constexpr (COUNT) {
           // the new ray's bounce, sample and pixel (context words C.w, E.y, E.w): is its walk the AOV record of its pixel?
           aovPixel = -1;
@@ -526,7 +577,11 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
         const unsigned long long q3 = clock64();
         pSaw[5] += q1 - q0;  // swap: claim
         pSaw[6] += q2 - q1;  // swap: hand-over of the finished walks
-        pSaw[7] += q3 - q2;  // swap: new rays arrive, set-up
+        pSaw[7] += q3 - q2;  // swap: new rays arrive, set-up (and the head of their walks)
+        if (head != 0 && __ballot(id >= 0) != 0) {  // kind 10 in this form: swap steps that ran the head, and its lanes
+          pRuns[10]++;
+          pLanes[10] += __popcll(__ballot(id >= 0));
+        }
       }
       prof(2, __popcll(__ballot(fin)) + __popcll(__ballot(id >= 0)));
   };

@@ -52,7 +52,7 @@ TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetW
                 "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
                 "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord", "srtTestGetSlabScene",
                 "srtTestRefinedRcp", "srtTestSlabVisit", "srtTestRegroup", "srtTestGetRegroup",
-                "srtTestRegroupWalk", "srtTestGetRegroupWalk"]
+                "srtTestRegroupWalk", "srtTestGetRegroupWalk", "srtTestWfHead"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -182,6 +182,9 @@ if hasattr(lib, "srtTestRegroupWalk"):  # (likewise: an SRT_HIP_LIB build from b
     lib.srtTestRegroupWalk.argtypes = [_vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]
     lib.srtTestRegroupWalk.restype = C.c_int32
     lib.srtTestGetRegroupWalk.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]
+if hasattr(lib, "srtTestWfHead"):  # (likewise: an SRT_HIP_LIB build from before the head of the walks)
+    lib.srtTestWfHead.argtypes = [_vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.srtTestWfHead.restype = C.c_int32
 lib.srtRenderAov.argtypes =[_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, _vp]
 lib.srtLastKernelMs.argtypes = [_vp, C.POINTER(C.c_float)]
 lib.srtGetStats.argtypes = [_vp, C.POINTER(abi.SrtStats)]
@@ -1135,7 +1138,7 @@ class Context:
         """Step profile of the last path-pool launch with tunable wf_profile = 1 (include/srt_hip_test.h)."""
         out = np.zeros(46, np.uint64)
         self._check(lib.srtGetWfProfile(self.h, out.ctypes.data))
-        kinds = ["node", "prim", "swap", "hit0", "hit1", "hit2", "restart", "idle", "lost_claim", "new_item", "far_node", "unused"]  # "unused": clocks = primitive steps that ran the exact triangle test, runs = undecided lanes
+        kinds = ["node", "prim", "swap", "hit0", "hit1", "hit2", "restart", "idle", "lost_claim", "new_item", "far_node", "unused"]  # "unused": clocks = primitive steps that ran the exact triangle test, runs = undecided lanes; "far_node" in the whole-tree form: runs = swap steps that ran the head of the walks, lanes = the rays they ran it for
         K = len(kinds)
         prof = {k: {"clocks": int(out[i]), "runs": int(out[K + i]), "lanes": int(out[2 * K + i])} for i, k in enumerate(kinds)}
         prof["sched_clocks"], prof["total_clocks"] = int(out[3 * K]), int(out[3 * K + 1])

@@ -1,6 +1,6 @@
 """Step profile of the path-pool kernel (profiling variant, tunable wf_profile = 1): share of wave time, executions,
 mean lane fill and clocks per execution per step kind.  usage: python tools/wf_profile.py [scene [spp [W H]]]
-env: SRT_WF_POOL, SRT_WF_SWAP_MIN, SRT_WF_SWAP_BIG (read at srtCreate)"""
+env: SRT_WF_POOL, SRT_WF_SWAP_MIN, SRT_WF_SWAP_BIG, SRT_WF_HEAD (read at srtCreate)"""
 import importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,7 +31,12 @@ for k in ("node", "far_node", "prim", "swap", "hit0", "hit1", "hit2", "restart",
     v = pr[k]
     print("%-10s %5.1f%% of wave time, %11d executions, mean fill %5.1f lanes, %8.1f clocks/execution, %.3f executions/sample" % (
         k, 100.0 * v["clocks"] / tot, v["runs"], v["lanes"] / max(1, v["runs"]), v["clocks"] / max(1, v["runs"]), v["runs"] / samples))
-if pr["far_node"]["runs"]:
+form = ctx.launch_info()["lds_tree_mode"]
+if form == 3:  # whole-tree form: the slot counts the head of the walks (tunable wf_head), inside the swap step's clocks
+    hd = pr["far_node"]
+    print("head of the walks: %d swap steps ran it (%.1f%% of them), for %.1f lanes on average; %d lanes, %.3f per sample" % (
+        hd["runs"], 100.0 * hd["runs"] / max(1, pr["swap"]["runs"]), hd["lanes"] / max(1, hd["runs"]), hd["lanes"], hd["lanes"] / samples))
+elif pr["far_node"]["runs"]:
     print("hybrid form: the closing visit of a round served %.1f lanes outside LDS and %.1f lanes in LDS on average" % (
         pr["far_node"]["lanes"] / pr["far_node"]["runs"], pr["unused"]["lanes"] / pr["far_node"]["runs"]))
 print("slab certificate: %.4f%% of lane visits undecided, %.2f%% of wave visits ran the IEEE test" % (
