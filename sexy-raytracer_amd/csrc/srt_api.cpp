@@ -1,7 +1,8 @@
 // srt_api.cpp -- host side of the C ABI (include/srt_hip.h): the context (srt_context.h) and its tunables, the upload of a
 // flattened scene (srt_scene.cpp) with the device BVH builds, the BVH queries, timing, statistics and the test hooks
-// (include/srt_hip_test.h).  The render launches are in srt_render.cpp, the passes over a rendered frame in
-// srt_passes.cpp, and the entries that render a whole frame into host buffers compose those in srt_frames.cpp.
+// (include/srt_hip_test.h).  The render launches are in srt_render.cpp, the entries on the caller's device buffers (ray
+// queries, path steps) in srt_rays.cpp, the passes over a rendered frame in srt_passes.cpp, and the entries that render a
+// whole frame into host buffers compose those in srt_frames.cpp.
 
 #include <hip/hip_runtime.h>
 

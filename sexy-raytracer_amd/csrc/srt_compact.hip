@@ -10,10 +10,11 @@
 //            units before its own in the tile + the kept lanes below it in its wave
 // A tile is ROWS rows of SRT_BLOCK consecutive entries; lane t of the workgroup takes entry t of every row, so that the
 // loads of a wave are consecutive and the units of a tile are ordered (row, wave).  The predicate is evaluated twice
-// rather than left in scratch as ballots, and a 36-byte ray row goes from the lane to memory as the
-// step kernels' loadRay / storeRay move it: the kept lanes of a wave write consecutive rows.
+// rather than left in scratch as ballots.  The predicate and the move of a kept entry are srt_payloads.h's
+// keepEntry and moveEntry: the kept lanes of a wave write consecutive rows.
 
 #include "srt_launch.h"
+#include "srt_payloads.h"
 
 namespace {
 
@@ -23,12 +24,8 @@ constexpr int WAVES = SRT_BLOCK / WAVE;
 static_assert(SRT_COMPACT_TILE % SRT_BLOCK == 0 && (SRT_COMPACT_TILE & (SRT_COMPACT_TILE - 1)) == 0, "a tile is whole rows, a power of two");
 static_assert(SRT_COMPACT_SCAN_BLOCK % WAVE == 0 && SRT_COMPACT_SCAN_BLOCK <= 1024, "the scan workgroup");
 
-// keep[i]; false behind the last entry.  Of SrtPathOut only the status dword is read.
-__device__ __forceinline__ bool keepEntry(const CompactArgs& a, int64_t i) {
-  if (i >= a.n) return false;
-  if (a.active && a.active[i] == 0) return false;
-  return !a.out || a.out[8 * i + 3] == SRT_PATH_SCATTERED;
-}
+// keep[i]; false behind the last entry
+__device__ __forceinline__ bool keepBounded(const PathPayloads& p, int64_t i) { return i < p.n && keepEntry(p, i); }
 
 __global__ __launch_bounds__(SRT_BLOCK) void srt_compact_count_kernel(const CompactArgs a) {
   __shared__ uint32_t waveCount[WAVES];
@@ -37,7 +34,7 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_compact_count_kernel(const Comp
     const int64_t first = tile * SRT_COMPACT_TILE + threadIdx.x;
     uint32_t kept = 0;  // of this wave, over the tile's rows
 #pragma unroll
-    for (int k = 0; k < ROWS; ++k) kept += (uint32_t)__popcll(__ballot(keepEntry(a, first + (int64_t)k * SRT_BLOCK)));
+    for (int k = 0; k < ROWS; ++k) kept += (uint32_t)__popcll(__ballot(keepBounded(a.p, first + (int64_t)k * SRT_BLOCK)));
     if (lane == 0) waveCount[wave] = kept;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -83,14 +80,14 @@ __global__ __launch_bounds__(SRT_COMPACT_SCAN_BLOCK) void srt_compact_scan_kerne
 __global__ __launch_bounds__(SRT_BLOCK) void srt_compact_scatter_kernel(const CompactArgs a) {
   __shared__ uint32_t unitCount[ROWS * WAVES];
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-  const int64_t total = *a.count;
+  const int64_t total = *a.p.count;
   for (int64_t tile = blockIdx.x; tile < a.numTiles; tile += gridDim.x) {
     const int64_t first = tile * SRT_COMPACT_TILE + threadIdx.x;
     uint64_t ballot[ROWS];
     // every byte of the mask this lane will overwrite (activeOut may be the mask itself) is read here, before the stores
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) {
-      ballot[k] = __ballot(keepEntry(a, first + (int64_t)k * SRT_BLOCK));
+      ballot[k] = __ballot(keepBounded(a.p, first + (int64_t)k * SRT_BLOCK));
       if (lane == 0) unitCount[k * WAVES + wave] = (uint32_t)__popcll(ballot[k]);
     }
     __syncthreads();
@@ -110,19 +107,9 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_compact_scatter_kernel(const Co
       if ((ballot[k] >> lane) & 1) {
         const uint32_t lo = (uint32_t)ballot[k], hi = (uint32_t)(ballot[k] >> 32);
         const int64_t rank = tileFirst + before[k] + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-        if (a.raysOut) {
-          const uint32_t* in = a.rays + 9 * i;
-          uint32_t* out = a.raysOut + 9 * rank;
-          uint32_t row[9];
-#pragma unroll
-          for (int c = 0; c < 9; ++c) row[c] = in[c];
-#pragma unroll
-          for (int c = 0; c < 9; ++c) out[c] = row[c];
-        }
-        if (a.rngOut) a.rngOut[rank] = a.rng[i];
-        if (a.slotOut) a.slotOut[rank] = a.slot ? a.slot[i] : (int32_t)i;
+        moveEntry(a.p, i, rank);
       }
-      if (a.activeOut && i < a.n) a.activeOut[i] = i < total ? 1 : 0;
+      if (a.p.activeOut && i < a.p.n) a.p.activeOut[i] = i < total ? 1 : 0;
     }
     __syncthreads();  // the next trip writes unitCount again
   }
@@ -136,7 +123,7 @@ int srt_launch_compact(const CompactArgs* a, int grid, hipStream_t stream) {
   hipLaunchKernelGGL(srt_compact_count_kernel, dim3(grid), dim3(SRT_BLOCK), 0, stream, *a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(srt_compact_scan_kernel, dim3(1), dim3(SRT_COMPACT_SCAN_BLOCK), 0, stream, a->tileOffset, a->numTiles, a->count);
+  hipLaunchKernelGGL(srt_compact_scan_kernel, dim3(1), dim3(SRT_COMPACT_SCAN_BLOCK), 0, stream, a->tileOffset, a->numTiles, a->p.count);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(srt_compact_scatter_kernel, dim3(grid), dim3(SRT_BLOCK), 0, stream, *a);

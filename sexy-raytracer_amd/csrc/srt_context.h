@@ -1,6 +1,7 @@
 // srt_context.h -- the context behind the C ABI's SrtContext* and what the host translation units share around it: error
 // reporting, and the device-level entries (srt_api.cpp, srt_render.cpp, srt_passes.cpp) that each other and the whole-frame
-// entries (srt_frames.cpp) compose.  Internal: none of this is exported.
+// entries (srt_frames.cpp) compose.  The entries on the caller's device buffers (srt_rays.cpp) use the context, the error
+// reporting and checkSceneReady, and nothing composes them.  Internal: none of this is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,7 @@
 // srt_frames.cpp -- the blocking entries of the C ABI that render a whole frame into HOST buffers (include/srt_hip.h,
 // srtRenderAov: include/srt_hip_test.h).  Each is a composition of the device-level entries (srt_render.cpp and
-// srt_passes.cpp, declared in srt_context.h) on the null stream, over staging buffers that live for the call.
+// srt_passes.cpp, declared in srt_context.h; none of srt_rays.cpp's) on the null stream, over staging buffers that live
+// for the call.
 
 #include <hip/hip_runtime.h>
 

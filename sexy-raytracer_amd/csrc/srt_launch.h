@@ -36,13 +36,12 @@ int srt_launch_camera_rays(const CameraRaysArgs* a, int grid, hipStream_t stream
 int srt_launch_scatter_device(const ScatterDeviceArgs* a, int grid, hipStream_t stream);
 int srt_launch_path_step(const PathStepArgs* a, int traversal, int grid, size_t ldsBytes, hipStream_t stream);
 
-// srt_compact.hip (srtCompactPathsDevice): count, scan and scatter, three kernels on the stream; grid = the workgroups of
-// the first and the last.  The scan is one workgroup of SRT_COMPACT_SCAN_BLOCK threads, a tile count each per trip.
-#define SRT_COMPACT_SCAN_BLOCK 1024
-struct CompactArgs {
+// What srtCompactPathsDevice and srtSortPathsDevice have in common: the predicate, the payloads in and out, the count.  The
+// host fills and checks it in one place (srt_rays.cpp); srt_payloads.h holds the keep rule and the move of one entry.
+struct PathPayloads {
   const int32_t* out;     // SrtPathOut[n] as dwords (the status is dword 3 of 8), or null
-  const uint8_t* active;  // or null; not both
-  const uint32_t* rays;   // payloads in: read only where the output beside them is not null
+  const uint8_t* active;  // or null; compaction: not both.  The sort: both null keeps every entry
+  const uint32_t* rays;   // payloads in: read only where the output beside them is not null (the sort's key always reads the rays)
   const uint64_t* rng;
   const int32_t* slot;    // null with slotOut: the identity
   uint32_t* raysOut;      // payloads out, each or null
@@ -50,8 +49,16 @@ struct CompactArgs {
   int32_t* slotOut;
   uint8_t* activeOut;     // or null; may be `active`
   int64_t* count;
-  uint64_t* tileOffset;   // the caller's scratch: numTiles words
-  int64_t n, numTiles;
+  int64_t n;
+};
+
+// srt_compact.hip (srtCompactPathsDevice): count, scan and scatter, three kernels on the stream; grid = the workgroups of
+// the first and the last.  The scan is one workgroup of SRT_COMPACT_SCAN_BLOCK threads, a tile count each per trip.
+#define SRT_COMPACT_SCAN_BLOCK 1024
+struct CompactArgs {
+  PathPayloads p;
+  uint64_t* tileOffset;  // the caller's scratch: numTiles words
+  int64_t numTiles;
 };
 int srt_launch_compact(const CompactArgs* a, int grid, hipStream_t stream);
 
@@ -59,21 +66,11 @@ int srt_launch_compact(const CompactArgs* a, int grid, hipStream_t stream);
 // two halves of the scratch, and the gather kernel, all on the stream; grid = the workgroups of the two kernels.
 // srt_sort_temp_bytes: what that sort asks for as temporary storage at this n and cellBits (host only, launches nothing).
 struct SortArgs {
-  const int32_t* out;     // SrtPathOut[n] as dwords (the status is dword 3 of 8), or null
-  const uint8_t* active;  // or null; both null: every entry is kept
-  const uint32_t* rays;   // required: the key reads the origin and the direction's sign bits
-  const uint64_t* rng;    // payloads in: read only where the output beside them is not null
-  const int32_t* slot;    // null with slotOut: the identity
-  const float* box;       // lo.xyz, hi.xyz on the device
-  uint32_t* raysOut;      // payloads out, each or null
-  uint64_t* rngOut;
-  int32_t* slotOut;
-  uint8_t* activeOut;     // or null; may be `active`
-  int64_t* count;
+  PathPayloads p;    // rays required: the key reads the origin and the direction's sign bits
   uint32_t *keys, *keysSpare, *index, *indexSpare;  // the caller's scratch: n words each
-  void* temp;             // and the sort's temporary storage behind them
+  void* temp;        // and the sort's temporary storage behind them
   size_t tempBytes;
-  int64_t n;
+  const float* box;  // lo.xyz, hi.xyz on the device
   int32_t cellBits;
 };
 int srt_sort_temp_bytes(int64_t n, int cellBits, hipStream_t stream, size_t* bytes);

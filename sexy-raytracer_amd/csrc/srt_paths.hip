@@ -11,8 +11,13 @@
 // as the lane's entry.  The lanes of a claim hold consecutive entries, so the ray loads of a fresh wave coalesce as the
 // step kernel's do.  The kernel ends because the counter only grows and every path makes at most maxBounce steps.
 //
-// One trip is srt_pathstep.hip's step body on the lane's registers -- queryWalk, the record, the material-range check,
-// shade() -- and nothing of it is restated here.  LDS per workgroup: the walk's [slot][thread] stack (stackDepth + 2
+// One trip is srt_pathstep.hip's step on the lane's registers.  Shared with it, each written once: the walk
+// (srt_query_walk.h queryWalk), the records (srt_path.h sphereRecord, triRecord), shade() and its instance, and the ray
+// row's loads (srt_step_rays.h STEP_WIDE, loadRay).  Written out here as in srt_path_step_kernel: the branch from the
+// walk's hit reference to one of the two records, without the step kernel's load of the prims[] index, and the
+// material-range check behind it (one function for the two moved this kernel's registers, so each keeps its lines).  The
+// kernel's own: the claim of entries, the attenuation stack and its unwinding, and the one store of the radiance where
+// the step kernel stores an SrtPathOut per bounce.  LDS per workgroup: the walk's [slot][thread] stack (stackDepth + 2
 // slots), then the attenuations [3 * level + channel][thread], 3 * maxBounce slots of the call's own maxBounce
 // (srt_lds_layout.h srtPathsLdsBytes).  DESIGN.md 5.20.
 

@@ -365,410 +365,6 @@ int srtTraceRays(SrtContext* ctx, const SrtRay* rays, int64_t n, SrtHit* hits, i
   return 0;
 }
 
-// srtTraceRaysDevice / srtOccludedDevice (include/srt_hip.h "Ray queries"): every check on the host, then one launch of
-// srt_query.hip on the caller's stream.  Nothing of the context changes: no work area, no event, no plan.
-// anyHit: srtOccludedDevice (dOccluded); otherwise `traversal` selects the walk (dHits, dRecords).
-static int queryDevice(SrtContext* ctx, const char* what, const void* dRays, int64_t n, bool anyHit, int32_t traversal, void* dHits,
-                       void* dRecords, void* dOccluded, void* streamPtr) {
-  if (!ctx) return 1;
-  if (checkSceneReady(ctx, what)) return 1;
-  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
-  if (!anyHit && traversal != SRT_TRAVERSE_FAITHFUL && traversal != SRT_TRAVERSE_CLOSEST)
-    return fail(ctx, "%s: traversal %d is neither SRT_TRAVERSE_FAITHFUL nor SRT_TRAVERSE_CLOSEST", what, traversal);
-  const int mode = anyHit ? 2 : traversal;  // srt_launch_query's modes
-  if (n == 0) return 0;
-  if (!dRays) return fail(ctx, "%s: null rays", what);
-  if (anyHit ? !dOccluded : (!dHits && !dRecords)) return fail(ctx, "%s: no output buffer", what);
-  if ((uintptr_t)dRays % 4) return fail(ctx, "%s: the rays are not aligned to 4 bytes", what);
-  if ((uintptr_t)dHits % 16) return fail(ctx, "%s: the hits are not aligned to 16 bytes", what);
-  if ((uintptr_t)dRecords % 4) return fail(ctx, "%s: the records are not aligned to 4 bytes", what);
-  const DevScene& sc = ctx->upload.scene;
-  const size_t lds = srtQueryStackBytes(sc.stackDepth);
-  if (lds > SRT_LDS_BYTES) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  QueryArgs a;
-  a.scene = sc;
-  a.rays = static_cast<const float*>(dRays);
-  a.hits = static_cast<int4*>(dHits);
-  a.records = static_cast<SrtHit*>(dRecords);
-  a.occluded = static_cast<uint8_t*>(dOccluded);
-  a.n = n;
-  const int e = srt_launch_query(&a, mode, planEntryGrid(ctx->prop.multiProcessorCount, n), lds, static_cast<hipStream_t>(streamPtr));
-  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
-  return 0;
-}
-
-int srtTraceRaysDevice(SrtContext* ctx, const void* dRays, int64_t n, int32_t traversal, void* dHits, void* dRecords, void* stream) {
-  SRT_GUARDED(ctx, queryDevice(ctx, "srtTraceRaysDevice", dRays, n, false, traversal, dHits, dRecords, nullptr, stream));
-}
-
-int srtOccludedDevice(SrtContext* ctx, const void* dRays, int64_t n, void* dOccluded, void* stream) {
-  SRT_GUARDED(ctx, queryDevice(ctx, "srtOccludedDevice", dRays, n, true, 0, nullptr, nullptr, dOccluded, stream));
-}
-
-// srtCameraRaysDevice / srtScatterRaysDevice / srtPathStepDevice (include/srt_hip.h "Path steps on device buffers"):
-// as queryDevice -- every check on the host, then one launch of srt_pathstep.hip on the caller's stream, and nothing of
-// the context changes.
-
-// srt_path.h mix64 on the host (the kernels' copy is device code); tests/test_pathstep_abi.py pins srtRngKey to the oracle
-static uint64_t hostMix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-uint64_t srtRngKey(uint64_t seed, uint64_t pixel, uint64_t sample) {  // the low 32 bits of pixel and of sample
-  return hostMix64(hostMix64(seed) ^ ((pixel << 32) | (sample & 0xffffffffull)));
-}
-
-static int pathGrid(const SrtContext* ctx, int64_t n) { return planEntryGrid(ctx->prop.multiProcessorCount, n); }
-
-// a required device pointer of `what`: non-null and aligned
-static int checkPointer(SrtContext* ctx, const char* what, const char* name, const void* p, int align) {
-  if (!p) return fail(ctx, "%s: null %s", what, name);
-  if ((uintptr_t)p % align) return fail(ctx, "%s: the %s are not aligned to %d bytes", what, name, align);
-  return 0;
-}
-
-static int cameraRaysDevice(SrtContext* ctx, const SrtRenderParams* p, const void* dPixelSample, int64_t n, void* dRays, void* dRng,
-                            void* streamPtr) {
-  const char* what = "srtCameraRaysDevice";
-  if (!ctx) return 1;
-  if (!p) return fail(ctx, "%s: null parameters", what);
-  if (!ctx->haveCamera) return fail(ctx, "%s: no camera set", what);
-  if (p->imageWidth < 2 || p->imageHeight < 2) return fail(ctx, "%s: image must be at least 2x2 (u,v divide by W-1,H-1)", what);
-  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
-  if (!dPixelSample) {
-    if (p->spp < 1) return fail(ctx, "%s: spp must be >= 1 without a list", what);
-    const int64_t all = (int64_t)p->imageWidth * p->imageHeight * p->spp;
-    if (n != all) return fail(ctx, "%s: n = %lld without a list, the frame has %lld samples", what, (long long)n, (long long)all);
-  }
-  if (n == 0) return 0;
-  if ((uintptr_t)dPixelSample % 4) return fail(ctx, "%s: the list is not aligned to 4 bytes", what);
-  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "rng states", dRng, 8)) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  CameraRaysArgs a;
-  a.cam = ctx->cam;
-  a.imageWidth = p->imageWidth;
-  a.imageHeight = p->imageHeight;
-  a.spp = std::max(p->spp, 1);
-  a.sampleFirst = p->sampleFirst;
-  a.seed = p->seed;
-  a.tMin = p->tMin;
-  a.pixelSample = static_cast<const int32_t*>(dPixelSample);
-  a.rays = static_cast<float*>(dRays);
-  a.rng = static_cast<uint64_t*>(dRng);
-  a.n = n;
-  const int e = srt_launch_camera_rays(&a, pathGrid(ctx, n), static_cast<hipStream_t>(streamPtr));
-  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
-  return 0;
-}
-
-static int scatterDevice(SrtContext* ctx, const void* dRays, const void* dRecords, int64_t n, void* dRng, void* dOut, void* dRaysOut,
-                         void* streamPtr) {
-  const char* what = "srtScatterRaysDevice";
-  if (!ctx) return 1;
-  if (checkSceneReady(ctx, what)) return 1;
-  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
-  if (n == 0) return 0;
-  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "records", dRecords, 4) ||
-      checkPointer(ctx, what, "rng states", dRng, 8) || checkPointer(ctx, what, "outputs", dOut, 16) ||
-      checkPointer(ctx, what, "scattered rays", dRaysOut, 4))
-    return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  ScatterDeviceArgs a;
-  a.scene = ctx->upload.scene;
-  a.rays = static_cast<const float*>(dRays);
-  a.records = static_cast<const SrtHit*>(dRecords);
-  a.rng = static_cast<uint64_t*>(dRng);
-  a.out = static_cast<int4*>(dOut);
-  a.raysOut = static_cast<float*>(dRaysOut);
-  a.n = n;
-  const int e = srt_launch_scatter_device(&a, pathGrid(ctx, n), static_cast<hipStream_t>(streamPtr));
-  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
-  return 0;
-}
-
-static int pathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays, int64_t n, const void* dActive, void* dRng, void* dOut,
-                          void* dRaysOut, void* dHits, void* streamPtr) {
-  const char* what = "srtPathStepDevice";
-  if (!ctx) return 1;
-  if (checkSceneReady(ctx, what)) return 1;
-  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
-  if (traversal != SRT_TRAVERSE_FAITHFUL && traversal != SRT_TRAVERSE_CLOSEST)
-    return fail(ctx, "%s: traversal %d is neither SRT_TRAVERSE_FAITHFUL nor SRT_TRAVERSE_CLOSEST", what, traversal);
-  if (n == 0) return 0;
-  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "rng states", dRng, 8) ||
-      checkPointer(ctx, what, "outputs", dOut, 16) || checkPointer(ctx, what, "scattered rays", dRaysOut, 4))
-    return 1;
-  if ((uintptr_t)dHits % 16) return fail(ctx, "%s: the hits are not aligned to 16 bytes", what);
-  const DevScene& sc = ctx->upload.scene;
-  const size_t lds = srtQueryStackBytes(sc.stackDepth);  // the walk's stacks, as queryDevice sizes and bounds them
-  if (lds > SRT_LDS_BYTES) return fail(ctx, "%s: BVH depth %d needs %zu B of LDS per workgroup", what, sc.stackDepth, lds);
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  PathStepArgs a;
-  a.scene = sc;
-  a.rays = static_cast<const float*>(dRays);
-  a.active = static_cast<const uint8_t*>(dActive);
-  a.rng = static_cast<uint64_t*>(dRng);
-  a.out = static_cast<int4*>(dOut);
-  a.raysOut = static_cast<float*>(dRaysOut);
-  a.hits = static_cast<int4*>(dHits);
-  a.n = n;
-  const int e = srt_launch_path_step(&a, traversal, pathGrid(ctx, n), lds, static_cast<hipStream_t>(streamPtr));
-  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
-  return 0;
-}
-
-// The range comparison of srtCompactPathsDevice and srtSortPathsDevice: no written range may overlap a range that is read
-// or another written one, each taken at its full length; null ranges take no part.  maskOut == mask exactly is the one
-// exception (an entry's byte is read before it is written).
-struct PathRange {
-  const char* name;
-  uintptr_t at;
-  uint64_t bytes;
-  bool written;
-};
-static int checkPathRanges(SrtContext* ctx, const char* what, const PathRange* ranges, size_t count, const PathRange* mask,
-                           const PathRange* maskOut) {
-  for (const PathRange* w = ranges; w != ranges + count; ++w) {
-    if (!w->written || !w->at) continue;
-    for (const PathRange* r = ranges; r != ranges + count; ++r) {
-      if (r == w || !r->at || (r->written && r < w)) continue;  // a pair of written ranges once
-      if (w == maskOut && r == mask && w->at == r->at) continue;
-      if (w->at < r->at + r->bytes && r->at < w->at + w->bytes) return fail(ctx, "%s: the %s overlap the %s", what, w->name, r->name);
-    }
-  }
-  return 0;
-}
-
-// srtCompactPathsDevice: every check on the host, then srt_compact.hip's three launches on the caller's stream.  Needs no
-// scene; nothing of the context changes.
-static int64_t compactTiles(int64_t n) { return n <= 0 ? 0 : (n - 1) / SRT_COMPACT_TILE + 1; }
-
-int64_t srtCompactPathsScratchBytes(int64_t n) { return 8 * compactTiles(n); }
-
-static int compactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const void* dActive, const void* dRays, const void* dRng,
-                              const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut, void* dActiveOut, void* dCount,
-                              void* dScratch, void* streamPtr) {
-  const char* what = "srtCompactPathsDevice";
-  if (!ctx) return 1;
-  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
-  if (!dOut && !dActive) return fail(ctx, "%s: no predicate: the outputs and the mask are both null", what);
-  if (checkPointer(ctx, what, "count", dCount, 8)) return 1;
-  if (n == 0) return 0;
-  if (checkPointer(ctx, what, "scratch", dScratch, 8)) return 1;
-  if (dRaysOut && !dRays) return fail(ctx, "%s: compacted rays without rays", what);
-  if (dRngOut && !dRng) return fail(ctx, "%s: compacted rng states without rng states", what);
-  if ((uintptr_t)dOut % 16) return fail(ctx, "%s: the outputs are not aligned to 16 bytes", what);
-  if ((dRaysOut && (uintptr_t)dRays % 4) || (uintptr_t)dRaysOut % 4) return fail(ctx, "%s: the rays are not aligned to 4 bytes", what);
-  if ((dRngOut && (uintptr_t)dRng % 8) || (uintptr_t)dRngOut % 8) return fail(ctx, "%s: the rng states are not aligned to 8 bytes", what);
-  if ((dSlotOut && (uintptr_t)dSlot % 4) || (uintptr_t)dSlotOut % 4) return fail(ctx, "%s: the slots are not aligned to 4 bytes", what);
-  if (dSlotOut && n > 0x7fffffffll) return fail(ctx, "%s: n = %lld does not fit a 32-bit slot", what, (long long)n);
-  // what the kernels write may overlap nothing else they read or write (dActiveOut may BE dActive: an entry owns its byte)
-  const uint64_t un = (uint64_t)n;
-  const PathRange ranges[] = {{"outputs", (uintptr_t)dOut, 32 * un, false},
-                              {"mask", (uintptr_t)dActive, un, false},
-                              {"rays", (uintptr_t)(dRaysOut ? dRays : nullptr), 36 * un, false},
-                              {"rng states", (uintptr_t)(dRngOut ? dRng : nullptr), 8 * un, false},
-                              {"slots", (uintptr_t)(dSlotOut ? dSlot : nullptr), 4 * un, false},
-                              {"compacted rays", (uintptr_t)dRaysOut, 36 * un, true},
-                              {"compacted rng states", (uintptr_t)dRngOut, 8 * un, true},
-                              {"compacted slots", (uintptr_t)dSlotOut, 4 * un, true},
-                              {"compacted mask", (uintptr_t)dActiveOut, un, true},
-                              {"count", (uintptr_t)dCount, 8, true},
-                              {"scratch", (uintptr_t)dScratch, (uint64_t)srtCompactPathsScratchBytes(n), true}};
-  if (checkPathRanges(ctx, what, ranges, sizeof ranges / sizeof ranges[0], &ranges[1], &ranges[8])) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  CompactArgs a;
-  a.out = static_cast<const int32_t*>(dOut);
-  a.active = static_cast<const uint8_t*>(dActive);
-  a.rays = static_cast<const uint32_t*>(dRays);
-  a.rng = static_cast<const uint64_t*>(dRng);
-  a.slot = static_cast<const int32_t*>(dSlot);
-  a.raysOut = static_cast<uint32_t*>(dRaysOut);
-  a.rngOut = static_cast<uint64_t*>(dRngOut);
-  a.slotOut = static_cast<int32_t*>(dSlotOut);
-  a.activeOut = static_cast<uint8_t*>(dActiveOut);
-  a.count = static_cast<int64_t*>(dCount);
-  a.tileOffset = static_cast<uint64_t*>(dScratch);
-  a.n = n;
-  a.numTiles = compactTiles(n);
-  const int grid = (int)std::min<int64_t>(a.numTiles, (int64_t)ctx->prop.multiProcessorCount * 8);
-  const int e = srt_launch_compact(&a, grid, static_cast<hipStream_t>(streamPtr));
-  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
-  return 0;
-}
-
-int srtCompactPathsDevice(SrtContext* ctx, int64_t n, const void* dOut, const void* dActive, const void* dRays, const void* dRng,
-                          const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut, void* dActiveOut, void* dCount,
-                          void* dScratch, void* stream) {
-  SRT_GUARDED(ctx, compactPathsDevice(ctx, n, dOut, dActive, dRays, dRng, dSlot, dRaysOut, dRngOut, dSlotOut, dActiveOut, dCount,
-                                      dScratch, stream));
-}
-
-// srtSortPathsDevice: every check on the host, then srt_sort.hip's memset, key kernel, rocPRIM sort and gather kernel on the
-// caller's stream.  Needs no scene; nothing of the context changes.  The scratch: four arrays of n 32-bit words (key and
-// index, twice: the sort's double buffers), each rounded up to 256 bytes, and behind them the sort's temporary storage.
-// srtSortPathsScratchBytes runs without a device, so that part is a bound that grows with n -- 4 bytes per entry and 64 KB:
-// with double buffers rocPRIM asks for digit histograms and, per block of at least 256 entries, one 32-bit look-back
-// word per digit or one merge partition -- and the call compares what the installed rocPRIM asks for with it.
-static int64_t sortArrayBytes(int64_t n) { return (4 * n + 255) & ~(int64_t)255; }
-static int64_t sortTempBytes(int64_t n) { return sortArrayBytes(n) + 65536; }
-
-int64_t srtSortPathsScratchBytes(int64_t n) { return n <= 0 ? 0 : 4 * sortArrayBytes(n) + sortTempBytes(n); }
-
-static int sortPathsDevice(SrtContext* ctx, int64_t n, int32_t cellBits, const void* dBox, const void* dOut, const void* dActive,
-                           const void* dRays, const void* dRng, const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut,
-                           void* dActiveOut, void* dCount, void* dScratch, int64_t scratchBytes, void* streamPtr) {
-  const char* what = "srtSortPathsDevice";
-  if (!ctx) return 1;
-  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
-  if (n > 0x7fffffffll) return fail(ctx, "%s: n = %lld does not fit a 32-bit index", what, (long long)n);
-  if (cellBits < 1 || cellBits > SRT_SORT_MAX_CELL_BITS)
-    return fail(ctx, "%s: cellBits = %d is outside [1, %d]", what, cellBits, (int)SRT_SORT_MAX_CELL_BITS);
-  if (checkPointer(ctx, what, "count", dCount, 8)) return 1;
-  if (n == 0) return 0;
-  if (checkPointer(ctx, what, "scratch", dScratch, 8) || checkPointer(ctx, what, "box", dBox, 4) ||
-      checkPointer(ctx, what, "rays", dRays, 4))
-    return 1;
-  if (scratchBytes < srtSortPathsScratchBytes(n))
-    return fail(ctx, "%s: the scratch holds %lld bytes, n = %lld needs %lld", what, (long long)scratchBytes, (long long)n,
-                (long long)srtSortPathsScratchBytes(n));
-  if (dRngOut && !dRng) return fail(ctx, "%s: sorted rng states without rng states", what);
-  if ((uintptr_t)dOut % 16) return fail(ctx, "%s: the outputs are not aligned to 16 bytes", what);
-  if ((uintptr_t)dRaysOut % 4) return fail(ctx, "%s: the rays are not aligned to 4 bytes", what);
-  if ((dRngOut && (uintptr_t)dRng % 8) || (uintptr_t)dRngOut % 8) return fail(ctx, "%s: the rng states are not aligned to 8 bytes", what);
-  if ((dSlotOut && (uintptr_t)dSlot % 4) || (uintptr_t)dSlotOut % 4) return fail(ctx, "%s: the slots are not aligned to 4 bytes", what);
-  const uint64_t un = (uint64_t)n;
-  const PathRange ranges[] = {{"outputs", (uintptr_t)dOut, 32 * un, false},
-                              {"mask", (uintptr_t)dActive, un, false},
-                              {"rays", (uintptr_t)dRays, 36 * un, false},
-                              {"rng states", (uintptr_t)(dRngOut ? dRng : nullptr), 8 * un, false},
-                              {"slots", (uintptr_t)(dSlotOut ? dSlot : nullptr), 4 * un, false},
-                              {"box", (uintptr_t)dBox, 24, false},
-                              {"sorted rays", (uintptr_t)dRaysOut, 36 * un, true},
-                              {"sorted rng states", (uintptr_t)dRngOut, 8 * un, true},
-                              {"sorted slots", (uintptr_t)dSlotOut, 4 * un, true},
-                              {"sorted mask", (uintptr_t)dActiveOut, un, true},
-                              {"count", (uintptr_t)dCount, 8, true},
-                              {"scratch", (uintptr_t)dScratch, (uint64_t)srtSortPathsScratchBytes(n), true}};
-  if (checkPathRanges(ctx, what, ranges, sizeof ranges / sizeof ranges[0], &ranges[1], &ranges[9])) return 1;
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-  size_t tempNeeded = 0;
-  int e = srt_sort_temp_bytes(n, cellBits, stream, &tempNeeded);
-  if (e) return fail(ctx, "%s: the sort's size query failed: %s", what, hipGetErrorString((hipError_t)e));
-  if ((int64_t)tempNeeded > sortTempBytes(n))
-    return fail(ctx, "%s: rocPRIM asks for %zu bytes of temporary storage, the scratch reserves %lld", what, tempNeeded,
-                (long long)sortTempBytes(n));
-  SortArgs a;
-  a.out = static_cast<const int32_t*>(dOut);
-  a.active = static_cast<const uint8_t*>(dActive);
-  a.rays = static_cast<const uint32_t*>(dRays);
-  a.rng = static_cast<const uint64_t*>(dRng);
-  a.slot = static_cast<const int32_t*>(dSlot);
-  a.box = static_cast<const float*>(dBox);
-  a.raysOut = static_cast<uint32_t*>(dRaysOut);
-  a.rngOut = static_cast<uint64_t*>(dRngOut);
-  a.slotOut = static_cast<int32_t*>(dSlotOut);
-  a.activeOut = static_cast<uint8_t*>(dActiveOut);
-  a.count = static_cast<int64_t*>(dCount);
-  char* base = static_cast<char*>(dScratch);
-  const int64_t array = sortArrayBytes(n);
-  a.keys = reinterpret_cast<uint32_t*>(base);
-  a.keysSpare = reinterpret_cast<uint32_t*>(base + array);
-  a.index = reinterpret_cast<uint32_t*>(base + 2 * array);
-  a.indexSpare = reinterpret_cast<uint32_t*>(base + 3 * array);
-  a.temp = base + 4 * array;
-  a.tempBytes = (size_t)sortTempBytes(n);
-  a.n = n;
-  a.cellBits = cellBits;
-  const int grid = (int)std::min<int64_t>((n - 1) / SRT_BLOCK + 1, (int64_t)ctx->prop.multiProcessorCount * 8);
-  e = srt_launch_sort(&a, grid, stream);
-  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
-  return 0;
-}
-
-int srtSortPathsDevice(SrtContext* ctx, int64_t n, int32_t cellBits, const void* dBox, const void* dOut, const void* dActive,
-                       const void* dRays, const void* dRng, const void* dSlot, void* dRaysOut, void* dRngOut, void* dSlotOut,
-                       void* dActiveOut, void* dCount, void* dScratch, int64_t scratchBytes, void* stream) {
-  SRT_GUARDED(ctx, sortPathsDevice(ctx, n, cellBits, dBox, dOut, dActive, dRays, dRng, dSlot, dRaysOut, dRngOut, dSlotOut, dActiveOut,
-                                   dCount, dScratch, scratchBytes, stream));
-}
-
-// srtTracePathsDevice: every check on the host, then srt_paths.hip's memset and its one kernel on the caller's stream.
-// Nothing of the context changes.
-static int tracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float* background, const void* dRays, int64_t n,
-                            void* dRng, void* dResult, void* dScratch, void* streamPtr) {
-  const char* what = "srtTracePathsDevice";
-  if (!ctx) return 1;
-  if (checkSceneReady(ctx, what)) return 1;
-  if (n < 0) return fail(ctx, "%s: n = %lld is negative", what, (long long)n);
-  if (traversal != SRT_TRAVERSE_FAITHFUL && traversal != SRT_TRAVERSE_CLOSEST)
-    return fail(ctx, "%s: traversal %d is neither SRT_TRAVERSE_FAITHFUL nor SRT_TRAVERSE_CLOSEST", what, traversal);
-  if (maxBounce < 0 || maxBounce > SRT_MAX_BOUNCE) return fail(ctx, "%s: maxBounce = %d is outside [0, %d]", what, maxBounce, SRT_MAX_BOUNCE);
-  if (!background) return fail(ctx, "%s: null background", what);
-  if (n == 0) return 0;
-  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "rng states", dRng, 8) ||
-      checkPointer(ctx, what, "results", dResult, 16) || checkPointer(ctx, what, "scratch", dScratch, 8))
-    return 1;
-  // what the kernel writes may overlap nothing else it reads or writes (srtCompactPathsDevice's range comparison)
-  struct Range {
-    const char* name;
-    uintptr_t at;
-    uint64_t bytes;
-  };
-  const uint64_t un = (uint64_t)n;
-  const Range ranges[] = {{"rays", (uintptr_t)dRays, 36 * un},  // read only: compared with the three written ones
-                          {"rng states", (uintptr_t)dRng, 8 * un},
-                          {"results", (uintptr_t)dResult, 16 * un},
-                          {"scratch", (uintptr_t)dScratch, SRT_PATHS_SCRATCH_BYTES}};
-  for (int w = 1; w < 4; ++w)
-    for (int r = 0; r < w; ++r)
-      if (ranges[w].at < ranges[r].at + ranges[r].bytes && ranges[r].at < ranges[w].at + ranges[w].bytes)
-        return fail(ctx, "%s: the %s overlap the %s", what, ranges[w].name, ranges[r].name);
-  const DevScene& sc = ctx->upload.scene;
-  const size_t lds = srtPathsLdsBytes(sc.stackDepth, maxBounce);
-  if (lds > SRT_LDS_BYTES)
-    return fail(ctx, "%s: BVH depth %d and %d bounces need %zu B of LDS per workgroup", what, sc.stackDepth, maxBounce, lds);
-  HIP_OK(ctx, hipSetDevice(ctx->device));
-  TracePathsArgs a;
-  a.scene = sc;
-  a.rays = static_cast<const float*>(dRays);
-  a.rng = static_cast<uint64_t*>(dRng);
-  a.result = static_cast<int4*>(dResult);
-  a.counter = static_cast<unsigned long long*>(dScratch);
-  for (int c = 0; c < 3; ++c) a.background[c] = background[c];
-  a.maxBounce = maxBounce;
-  a.refillMin = std::min(std::max(ctx->tun.pathsRefillMin, 1), 64);
-  a.n = n;
-  const int e = srt_launch_paths(&a, traversal, ctx->prop.multiProcessorCount, lds, SRT_PATHS_SCRATCH_BYTES, static_cast<hipStream_t>(streamPtr));
-  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
-  return 0;
-}
-
-int srtTracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float background[3], const void* dRays, int64_t n,
-                        void* dRng, void* dResult, void* dScratch, void* stream) {
-  SRT_GUARDED(ctx, tracePathsDevice(ctx, traversal, maxBounce, background, dRays, n, dRng, dResult, dScratch, stream));
-}
-
-int srtCameraRaysDevice(SrtContext* ctx, const SrtRenderParams* p, const void* dPixelSample, int64_t n, void* dRays, void* dRng,
-                        void* stream) {
-  SRT_GUARDED(ctx, cameraRaysDevice(ctx, p, dPixelSample, n, dRays, dRng, stream));
-}
-
-int srtScatterRaysDevice(SrtContext* ctx, const void* dRays, const void* dRecords, int64_t n, void* dRng, void* dOut, void* dRaysOut,
-                         void* stream) {
-  SRT_GUARDED(ctx, scatterDevice(ctx, dRays, dRecords, n, dRng, dOut, dRaysOut, stream));
-}
-
-int srtPathStepDevice(SrtContext* ctx, int32_t traversal, const void* dRays, int64_t n, const void* dActive, void* dRng, void* dOut,
-                      void* dRaysOut, void* dHits, void* stream) {
-  SRT_GUARDED(ctx, pathStepDevice(ctx, traversal, dRays, n, dActive, dRng, dOut, dRaysOut, dHits, stream));
-}
-
 // test entries: material::scatter known answers through the kernels' own shade(), in the instance `form` selects
 // (bit 0 WIDE, bit 1 COUNT: include/srt_hip_test.h)
 

@@ -12,24 +12,19 @@
 //   sort     rocPRIM's radix_sort_pairs over (key, index) on bits [0, 3 * cellBits + 4), between the two halves of the
 //            scratch's double buffers: stable, so equal keys stay in index order and the dropped entries end up behind
 //            rank count in theirs.
-//   gather   one lane per rank: rank r < count reads order[r] and moves that entry's 36-byte ray row, state and slot as
-//            srt_compact.hip's scatter moves them -- nine dword loads and stores, the stores of a wave consecutive rows;
-//            the loads are scattered, which is what the call costs.  activeOut[r] = r < count: the mask was read by the
+//   gather   one lane per rank: rank r < count reads order[r] and moves that entry's 36-byte ray row, state and slot with
+//            the moveEntry srt_compact.hip's scatter calls (srt_payloads.h) -- the stores of a wave consecutive rows; the
+//            loads are scattered, which is what the call costs.  activeOut[r] = r < count: the mask was read by the
 //            key kernel, a launch earlier on the stream, so activeOut may be the mask itself.
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "srt_launch.h"
+#include "srt_payloads.h"
 
 namespace {
 
 constexpr int WAVE = 64;
-
-// keep[i] of srtCompactPathsDevice, with both predicates optional.  Of SrtPathOut only the status dword is read.
-__device__ __forceinline__ bool keepEntry(const SortArgs& a, int64_t i) {
-  if (a.active && a.active[i] == 0) return false;
-  return !a.out || a.out[8 * i + 3] == SRT_PATH_SCATTERED;
-}
 
 // bit k of q -> bit 3k, for the low 10 bits
 __device__ __forceinline__ uint32_t spread3(uint32_t q) {
@@ -49,6 +44,7 @@ __device__ __forceinline__ uint32_t cellOf(float o, float lo, float scale, uint3
 }
 
 __global__ __launch_bounds__(SRT_BLOCK) void srt_sort_key_kernel(const SortArgs a) {
+  const PathPayloads& p = a.p;
   const int lane = threadIdx.x & (WAVE - 1);
   // the same for every lane of the wave, and outside the loop over its entries: six loads and three divisions per wave
   const float lo[3] = {a.box[0], a.box[1], a.box[2]};
@@ -59,16 +55,16 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_sort_key_kernel(const SortArgs 
   const int64_t stride = (int64_t)gridDim.x * SRT_BLOCK;
   uint32_t kept = 0;  // of this wave; every lane keeps the same value
   // a wave's trips are whole: lanes behind n wait in the ballot
-  for (int64_t first = (int64_t)blockIdx.x * SRT_BLOCK + (threadIdx.x - lane); first < a.n; first += stride) {
+  for (int64_t first = (int64_t)blockIdx.x * SRT_BLOCK + (threadIdx.x - lane); first < p.n; first += stride) {
     const int64_t i = first + lane;
-    const bool keep = i < a.n && keepEntry(a, i);
-    if (i < a.n) {
+    const bool keep = i < p.n && keepEntry(p, i);
+    if (i < p.n) {
       uint32_t key = dead;
       if (keep) {
-        const float* ray = reinterpret_cast<const float*>(a.rays + 9 * i);
+        const float* ray = reinterpret_cast<const float*>(p.rays + 9 * i);
         const uint32_t cell = spread3(cellOf(ray[0], lo[0], scale[0], last)) | spread3(cellOf(ray[1], lo[1], scale[1], last)) << 1 |
                               spread3(cellOf(ray[2], lo[2], scale[2], last)) << 2;
-        const uint32_t octant = a.rays[9 * i + 3] >> 31 | (a.rays[9 * i + 4] >> 31) << 1 | (a.rays[9 * i + 5] >> 31) << 2;
+        const uint32_t octant = p.rays[9 * i + 3] >> 31 | (p.rays[9 * i + 4] >> 31) << 1 | (p.rays[9 * i + 5] >> 31) << 2;
         key = cell << 3 | octant;
       }
       a.keys[i] = key;
@@ -76,29 +72,17 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_sort_key_kernel(const SortArgs 
     }
     kept += (uint32_t)__popcll(__ballot(keep));
   }
-  if (lane == 0 && kept) atomicAdd(reinterpret_cast<unsigned long long*>(a.count), (unsigned long long)kept);
+  if (lane == 0 && kept) atomicAdd(reinterpret_cast<unsigned long long*>(p.count), (unsigned long long)kept);
 }
 
 __global__ __launch_bounds__(SRT_BLOCK) void srt_sort_gather_kernel(const SortArgs a, const uint32_t* order) {
-  const int64_t total = *a.count;
-  const int64_t end = a.activeOut ? a.n : total;
+  const PathPayloads& p = a.p;
+  const int64_t total = *p.count;
+  const int64_t end = p.activeOut ? p.n : total;
   const int64_t stride = (int64_t)gridDim.x * SRT_BLOCK;
   for (int64_t rank = (int64_t)blockIdx.x * SRT_BLOCK + threadIdx.x; rank < end; rank += stride) {
-    if (rank < total) {
-      const int64_t i = order[rank];
-      if (a.raysOut) {
-        const uint32_t* in = a.rays + 9 * i;
-        uint32_t* out = a.raysOut + 9 * rank;
-        uint32_t row[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) row[c] = in[c];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) out[c] = row[c];
-      }
-      if (a.rngOut) a.rngOut[rank] = a.rng[i];
-      if (a.slotOut) a.slotOut[rank] = a.slot ? a.slot[i] : (int32_t)i;
-    }
-    if (a.activeOut) a.activeOut[rank] = rank < total ? 1 : 0;
+    if (rank < total) moveEntry(p, order[rank], rank);
+    if (p.activeOut) p.activeOut[rank] = rank < total ? 1 : 0;
   }
 }
 
@@ -119,14 +103,14 @@ int srt_sort_temp_bytes(int64_t n, int cellBits, hipStream_t stream, size_t* byt
 }
 
 int srt_launch_sort(const SortArgs* a, int grid, hipStream_t stream) {
-  hipError_t e = hipMemsetAsync(a->count, 0, sizeof(int64_t), stream);
+  hipError_t e = hipMemsetAsync(a->p.count, 0, sizeof(int64_t), stream);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(srt_sort_key_kernel, dim3(grid), dim3(SRT_BLOCK), 0, stream, *a);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   rocprim::double_buffer<uint32_t> keys(a->keys, a->keysSpare), index(a->index, a->indexSpare);
   size_t tempBytes = a->tempBytes;
-  e = sortPairs(a->temp, &tempBytes, keys, index, a->n, 3 * a->cellBits + 4, stream);
+  e = sortPairs(a->temp, &tempBytes, keys, index, a->p.n, 3 * a->cellBits + 4, stream);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(srt_sort_gather_kernel, dim3(grid), dim3(SRT_BLOCK), 0, stream, *a, (const uint32_t*)index.current());
   return (int)hipGetLastError();

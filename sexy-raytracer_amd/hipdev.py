@@ -715,6 +715,11 @@ class Context:
         """None (the NULL stream), a raw hipStream_t as an integer, or a torch stream."""
         return getattr(stream, "cuda_stream", stream)
 
+    @staticmethod
+    def _ptr(t, n=1):
+        """The device address of a tensor for a C call: None (NULL) for no tensor, and for any tensor of a call on n = 0 entries."""
+        return t.data_ptr() if t is not None and n else None
+
     def trace_device(self, rays, traversal=abi.SRT_TRAVERSE_CLOSEST, records=False, stream=None):
         """srtTraceRaysDevice: the hit of every ray of a DEVICE tensor, asynchronous on `stream`.  rays: contiguous float32
         (n, 9) on the GPU, one SrtRay per row.  Returns an int32 tensor (n, 4) laid out as SrtRayHit {prim, t's bits,
@@ -797,8 +802,8 @@ class Context:
         rng = self._device_tensor(rng, "rng", "int64", (n,), rays)
         rays_out = torch.empty_like(rays) if rays_out is None else self._device_tensor(rays_out, "rays_out", "float32", (n, 9), rays)
         out = torch.empty((n, 8), dtype=torch.int32, device=rays.device)
-        ptr = (lambda t: t.data_ptr()) if n else (lambda t: None)
-        self._check(lib.srtScatterRaysDevice(self.h, ptr(rays), ptr(records), n, ptr(rng), ptr(out), ptr(rays_out),
+        ptr = self._ptr
+        self._check(lib.srtScatterRaysDevice(self.h, ptr(rays, n), ptr(records, n), n, ptr(rng, n), ptr(out, n), ptr(rays_out, n),
                                              self._stream_handle(stream)))
         return out, rays_out
 
@@ -817,39 +822,19 @@ class Context:
         rays_out = torch.empty_like(rays) if rays_out is None else self._device_tensor(rays_out, "rays_out", "float32", (n, 9), rays)
         out = torch.empty((n, 8), dtype=torch.int32, device=rays.device)
         d_hits = torch.empty((n, 4), dtype=torch.int32, device=rays.device) if hits else None
-        ptr = (lambda t: t.data_ptr() if t is not None else None) if n else (lambda t: None)
-        self._check(lib.srtPathStepDevice(self.h, int(traversal), ptr(rays), n, ptr(active), ptr(rng), ptr(out), ptr(rays_out),
-                                          ptr(d_hits), self._stream_handle(stream)))
+        ptr = self._ptr
+        self._check(lib.srtPathStepDevice(self.h, int(traversal), ptr(rays, n), n, ptr(active, n), ptr(rng, n), ptr(out, n),
+                                          ptr(rays_out, n), ptr(d_hits, n), self._stream_handle(stream)))
         return (out, rays_out, d_hits) if hits else (out, rays_out)
 
-    def compact_paths_device(self, out=None, active=None, rays=None, rng=None, slot=None, rays_out=None, rng_out=None, slot_out=None,
-                             active_out=None, slots=True, count=None, scratch=None, stream=None):
-        """srtCompactPathsDevice: the entries that go on, moved in their order to the front of fresh buffers, asynchronous on
-        `stream`.  Kept are the entries whose `out` row (int32 (n, 8), as a step returns it) says SCATTERED and whose `active`
-        byte (uint8 (n,)) is not 0; either may be None, not both -- pass the mask of the step that wrote `out`, because an
-        inactive entry's row is stale.  rays float32 (n, 9), rng int64 (n,), slot int32 (n,): the payloads, each optional;
-        *_out: where the kept rows go (allocated at n rows when None and the input is given; none may be an input).
-        slots: also return the index every kept entry had (`slot` carried through, the identity without one).  active_out:
-        a uint8 (n,) tensor that receives i < count (it may be `active` itself), or True to allocate one.  count: an int64
-        tensor of one element to receive the number kept; scratch: uint8, at least compact_scratch_bytes(n).
-        Returns (rays_out, rng_out, slot_out, active_out, count): None where nothing was asked for, rows behind count as
-        they were, count a 0-dim int64 tensor on the GPU (reading it synchronises)."""
+    def _path_payloads(self, n, first, rays, rng, slot, rays_out, rng_out, slot_out, active_out, slots, count, scratch, need):
+        """What compact_paths_device and sort_paths_device share behind their predicates: rng and slot validated against n
+        rows on the device of `first`; rays_out and rng_out allocated beside a given input or validated (an output without
+        its input is refused); slot_out allocated when `slots` or a slot came in; active_out a tensor, True to allocate, or
+        None; the scratch allocated or checked against `need` bytes; count allocated or validated, and zeroed for n == 0
+        (the entry does not write the count of nothing).  Returns (rng, slot, (rays_out, rng_out, slot_out, active_out),
+        count, scratch): the four outputs in the order of the C arguments and of the tuple both methods return."""
         import torch
-        first = None
-        if rays is not None:
-            first = rays = self._device_rays(rays)
-        if out is not None:
-            out = self._device_tensor(out, "out", "int32", (-1, 8), first)
-            first = out if first is None else first
-        if active is not None:
-            active = self._device_tensor(active, "active", "uint8", (-1,), first)
-            first = active if first is None else first
-        if out is None and active is None:
-            raise ValueError("out and active must not both be None: one of them is the predicate")
-        n = (out if out is not None else active).shape[0]
-        for name, t in (("rays", rays), ("out", out), ("active", active)):
-            if t is not None and t.shape[0] != n:
-                raise ValueError("%s must have %d rows like the predicate, not %d" % (name, n, t.shape[0]))
         if rng is not None:
             rng = self._device_tensor(rng, "rng", "int64", (n,), first)
         if slot is not None:
@@ -871,7 +856,6 @@ class Context:
             active_out = self._device_tensor(active_out, "active_out", "uint8", (n,), first)
         else:
             active_out = None
-        need = self.compact_scratch_bytes(n)
         if scratch is None:
             scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=first.device)
         else:
@@ -882,14 +866,44 @@ class Context:
             count = torch.empty((1,), dtype=torch.int64, device=first.device)
         else:
             count = self._device_tensor(count, "count", "int64", (1,), first)
-        if n == 0:  # the entry does not write the count of nothing
+        if n == 0:
             count.zero_()
-        else:
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-            self._check(lib.srtCompactPathsDevice(self.h, n, ptr(out), ptr(active), ptr(rays), ptr(rng), ptr(slot), ptr(rays_out),
-                                                  ptr(rng_out), ptr(slot_out), ptr(active_out), ptr(count), ptr(scratch),
-                                                  self._stream_handle(stream)))
-        return rays_out, rng_out, slot_out, active_out, count.reshape(())
+        return rng, slot, (rays_out, rng_out, slot_out, active_out), count, scratch
+
+    def compact_paths_device(self, out=None, active=None, rays=None, rng=None, slot=None, rays_out=None, rng_out=None, slot_out=None,
+                             active_out=None, slots=True, count=None, scratch=None, stream=None):
+        """srtCompactPathsDevice: the entries that go on, moved in their order to the front of fresh buffers, asynchronous on
+        `stream`.  Kept are the entries whose `out` row (int32 (n, 8), as a step returns it) says SCATTERED and whose `active`
+        byte (uint8 (n,)) is not 0; either may be None, not both -- pass the mask of the step that wrote `out`, because an
+        inactive entry's row is stale.  rays float32 (n, 9), rng int64 (n,), slot int32 (n,): the payloads, each optional;
+        *_out: where the kept rows go (allocated at n rows when None and the input is given; none may be an input).
+        slots: also return the index every kept entry had (`slot` carried through, the identity without one).  active_out:
+        a uint8 (n,) tensor that receives i < count (it may be `active` itself), or True to allocate one.  count: an int64
+        tensor of one element to receive the number kept; scratch: uint8, at least compact_scratch_bytes(n).
+        Returns (rays_out, rng_out, slot_out, active_out, count): None where nothing was asked for, rows behind count as
+        they were, count a 0-dim int64 tensor on the GPU (reading it synchronises)."""
+        first = None
+        if rays is not None:
+            first = rays = self._device_rays(rays)
+        if out is not None:
+            out = self._device_tensor(out, "out", "int32", (-1, 8), first)
+            first = out if first is None else first
+        if active is not None:
+            active = self._device_tensor(active, "active", "uint8", (-1,), first)
+            first = active if first is None else first
+        if out is None and active is None:
+            raise ValueError("out and active must not both be None: one of them is the predicate")
+        n = (out if out is not None else active).shape[0]
+        for name, t in (("rays", rays), ("out", out), ("active", active)):
+            if t is not None and t.shape[0] != n:
+                raise ValueError("%s must have %d rows like the predicate, not %d" % (name, n, t.shape[0]))
+        rng, slot, outs, count, scratch = self._path_payloads(n, first, rays, rng, slot, rays_out, rng_out, slot_out, active_out, slots,
+                                                              count, scratch, self.compact_scratch_bytes(n))
+        if n:
+            ptr = self._ptr
+            self._check(lib.srtCompactPathsDevice(self.h, n, ptr(out), ptr(active), ptr(rays), ptr(rng), ptr(slot), *map(ptr, outs),
+                                                  ptr(count), ptr(scratch), self._stream_handle(stream)))
+        return outs + (count.reshape(()),)
 
     @staticmethod
     def compact_scratch_bytes(n):
@@ -926,47 +940,18 @@ class Context:
         for name, t in (("out", out), ("active", active)):
             if t is not None and t.shape[0] != n:
                 raise ValueError("%s must have %d rows like the rays, not %d" % (name, n, t.shape[0]))
-        if rng is not None:
-            rng = self._device_tensor(rng, "rng", "int64", (n,), first)
-        if slot is not None:
-            slot = self._device_tensor(slot, "slot", "int32", (n,), first)
         if box is not None:
             box = self._device_tensor(box, "box", "float32", (6,), first)
-        rays_out = torch.empty_like(rays) if rays_out is None else self._device_tensor(rays_out, "rays_out", "float32", (n, 9), first)
-        if rng is not None:
-            rng_out = torch.empty_like(rng) if rng_out is None else self._device_tensor(rng_out, "rng_out", "int64", (n,), first)
-        if slot_out is not None:
-            slot_out = self._device_tensor(slot_out, "slot_out", "int32", (n,), first)
-        elif slots or slot is not None:
-            slot_out = torch.empty((n,), dtype=torch.int32, device=first.device)
-        if active_out is True:
-            active_out = torch.empty((n,), dtype=torch.uint8, device=first.device)
-        elif active_out is not None and active_out is not False:
-            active_out = self._device_tensor(active_out, "active_out", "uint8", (n,), first)
-        else:
-            active_out = None
-        need = self.sort_scratch_bytes(n)
-        if scratch is None:
-            scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=first.device)
-        else:
-            scratch = self._device_tensor(scratch, "scratch", "uint8", (-1,), first)
-            if scratch.shape[0] < need:
-                raise ValueError("scratch must hold %d bytes, not %d" % (need, scratch.shape[0]))
-        if count is None:
-            count = torch.empty((1,), dtype=torch.int64, device=first.device)
-        else:
-            count = self._device_tensor(count, "count", "int64", (1,), first)
-        if n == 0:  # the entry does not write the count of nothing
-            count.zero_()
-        else:
+        rng, slot, outs, count, scratch = self._path_payloads(n, first, rays, rng, slot, rays_out, rng_out, slot_out, active_out, slots,
+                                                              count, scratch, self.sort_scratch_bytes(n))
+        if n:
             if box is None:
                 with torch.cuda.stream(stream):
                     box = self.origin_box(rays, out, active)
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            ptr = self._ptr
             self._check(lib.srtSortPathsDevice(self.h, n, cell_bits, ptr(box), ptr(out), ptr(active), ptr(rays), ptr(rng), ptr(slot),
-                                               ptr(rays_out), ptr(rng_out), ptr(slot_out), ptr(active_out), ptr(count), ptr(scratch),
-                                               scratch.shape[0], self._stream_handle(stream)))
-        return rays_out, rng_out, slot_out, active_out, count.reshape(())
+                                               *map(ptr, outs), ptr(count), ptr(scratch), scratch.shape[0], self._stream_handle(stream)))
+        return outs + (count.reshape(()),)
 
     @staticmethod
     def origin_box(rays, out=None, active=None):
@@ -1013,9 +998,9 @@ class Context:
                 raise ValueError("scratch must hold %d bytes, not %d" % (abi.SRT_PATHS_SCRATCH_BYTES, scratch.shape[0]))
         bg = (C.c_float * 3)(*[float(c) for c in background])
         result = torch.empty((n, 4), dtype=torch.int32, device=rays.device)
-        ptr = (lambda t: t.data_ptr()) if n else (lambda t: None)
-        self._check(lib.srtTracePathsDevice(self.h, int(traversal), int(max_bounce), bg, ptr(rays), n, ptr(rng), ptr(result),
-                                            ptr(scratch), self._stream_handle(stream)))
+        ptr = self._ptr
+        self._check(lib.srtTracePathsDevice(self.h, int(traversal), int(max_bounce), bg, ptr(rays, n), n, ptr(rng, n), ptr(result, n),
+                                            ptr(scratch, n), self._stream_handle(stream)))
         return result
 
     def scatter_test(self, rays, hits, seed):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import abi_header
+from bad_tensors import bad_tensors
 import compact_ref as CR
 
 
@@ -59,23 +60,13 @@ def test_scratch_bytes_is_the_documented_formula(dev):
     assert dev.Context.compact_scratch_bytes(tile + 1) == 16
 
 
-def _bad_tensors(good, columns):  # tests/test_pathstep_abi.py's
-    other = columns - 1
-    return {"on the GPU": good,  # a CPU tensor, right in everything else
-            "must be": good.double() if good.dtype.is_floating_point else good.to(torch.int16),
-            "shape": torch.zeros((8, other), dtype=good.dtype),
-            "shape ": torch.zeros(8 * columns, dtype=good.dtype),
-            "contiguous": torch.zeros((columns, 8), dtype=good.dtype).t(),
-            "torch tensor": np.zeros((8, columns), np.float32)}
-
-
 def test_wrapper_refuses_a_bad_tensor_before_the_c_call(dev):
     """A context that was never created has no handle: reaching the C call would fail otherwise than by ValueError."""
     c = object.__new__(dev.Context)
-    for what, bad in _bad_tensors(torch.zeros((8, 9), dtype=torch.float32), 9).items():  # each refusal names its own reason
+    for what, bad in bad_tensors(torch.zeros((8, 9), dtype=torch.float32), 9).items():  # each refusal names its own reason
         with pytest.raises(ValueError, match="rays.*" + what.strip()):
             c.compact_paths_device(rays=bad, active=torch.ones((8,), dtype=torch.uint8))
-    for what, bad in _bad_tensors(torch.zeros((8, 8), dtype=torch.int32), 8).items():
+    for what, bad in bad_tensors(torch.zeros((8, 8), dtype=torch.int32), 8).items():
         with pytest.raises(ValueError, match="out.*" + what.strip()):
             c.compact_paths_device(out=bad)
     with pytest.raises(ValueError, match="active.*on the GPU"):

@@ -378,18 +378,18 @@ def test_side_effects_and_errors(ctx, dev, abi, camera):
     refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, SO, AO, CN, SC + 4, None), b"scratch are not aligned to 8")
     refused(call(ctx.h, 2 ** 31, O, A, None, None, None, None, None, SO, None, CN, SC, None), b"32-bit slot")
     # overlap: in place, shifted, an output on another output, on the count, on the scratch, on a predicate
-    refused(call(ctx.h, n, O, A, R, G, SL, R, GO, SO, AO, CN, SC, None), b"overlap")
-    refused(call(ctx.h, n, O, A, R, G, SL, RO, G, SO, AO, CN, SC, None), b"overlap")
-    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, SL, AO, CN, SC, None), b"overlap")
-    refused(call(ctx.h, n, O, A, R, G, SL, R + 36 * (n - 1), GO, SO, AO, CN, SC, None), b"overlap")
-    refused(call(ctx.h, n // 2, O, A, R, G, SL, RO, RO + 8 * (n // 2 - 1), SO, AO, CN, SC, None), b"overlap")
-    refused(call(ctx.h, n // 8, O, A, R, G, SL, RO, GO, SO, AO, GO + 8, SC, None), b"overlap")
-    refused(call(ctx.h, n // 8, O, A, R, G, SL, RO, GO, SO, AO, CN, SO + 8, None), b"overlap")
-    refused(call(ctx.h, n // 8, O, A, R, G, SL, RO, GO, SO, AO, SC, SC, None), b"overlap")
-    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, SO, O, CN, SC, None), b"overlap")
-    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, A, AO, CN, SC, None), b"overlap")
-    refused(call(ctx.h, n - 1, O, A, R, G, SL, RO, GO, SO, A + 1, CN, SC, None), b"overlap")  # a shifted mask is not in place
-    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, SO, AO, CN, O, None), b"overlap")
+    refused(call(ctx.h, n, O, A, R, G, SL, R, GO, SO, AO, CN, SC, None), b"compacted rays overlap the rays")
+    refused(call(ctx.h, n, O, A, R, G, SL, RO, G, SO, AO, CN, SC, None), b"compacted rng states overlap the rng states")
+    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, SL, AO, CN, SC, None), b"compacted slots overlap the slots")
+    refused(call(ctx.h, n, O, A, R, G, SL, R + 36 * (n - 1), GO, SO, AO, CN, SC, None), b"compacted rays overlap the rays")
+    refused(call(ctx.h, n // 2, O, A, R, G, SL, RO, RO + 8 * (n // 2 - 1), SO, AO, CN, SC, None), b"compacted rays overlap the compacted rng states")
+    refused(call(ctx.h, n // 8, O, A, R, G, SL, RO, GO, SO, AO, GO + 8, SC, None), b"compacted rng states overlap the count")
+    refused(call(ctx.h, n // 8, O, A, R, G, SL, RO, GO, SO, AO, CN, SO + 8, None), b"compacted slots overlap the scratch")
+    refused(call(ctx.h, n // 8, O, A, R, G, SL, RO, GO, SO, AO, SC, SC, None), b"count overlap the scratch")
+    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, SO, O, CN, SC, None), b"compacted mask overlap the outputs")
+    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, A, AO, CN, SC, None), b"compacted slots overlap the mask")
+    refused(call(ctx.h, n - 1, O, A, R, G, SL, RO, GO, SO, A + 1, CN, SC, None), b"compacted mask overlap the mask")  # a shifted mask is not in place
+    refused(call(ctx.h, n, O, A, R, G, SL, RO, GO, SO, AO, CN, O, None), b"scratch overlap the outputs")
     assert call(None, n, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, None) != 0
     # an input whose output is NULL is ignored, overlaps and misalignment included
     assert call(ctx.h, n, O, A, RO + 2, GO + 4, SO + 2, None, None, None, None, CN, SC, None) == 0, dev.lib.srtLastError(ctx.h)
@@ -399,6 +399,6 @@ def test_side_effects_and_errors(ctx, dev, abi, camera):
         assert bool((outs[k] == SENTINEL).all())
     for k, t in ins.items():
         assert t.cpu().numpy()[:n * (32 if k == "out" else ROW.get(k, 1))].tobytes() == np.ascontiguousarray(d[k]).tobytes()
-    with pytest.raises(dev.SrtError, match="overlap"):
+    with pytest.raises(dev.SrtError, match="compacted rays overlap the rays"):
         both = torch.zeros((n, 9), dtype=torch.float32, device="cuda")
         ctx.compact_paths_device(active=ins["active"][:n], rays=both, rays_out=both)

@@ -540,21 +540,21 @@ def test_side_effects_and_errors(ctx, dev, abi, camera):
     refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN + 4, SC, need, None), b"count are not aligned to 8")
     refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC + 4, need, None), b"scratch are not aligned to 8")
     # overlap: in place, shifted, an output on another output, on the count, on the scratch, on a predicate, on the box
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, R, GO, SO, AO, CN, SC, need, None), b"overlap")
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, None, GO, R, AO, CN, SC, need, None), b"overlap")  # the rays are read without dRaysOut
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, G, SO, AO, CN, SC, need, None), b"overlap")
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SL, AO, CN, SC, need, None), b"overlap")
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, R + 36 * (n - 1), GO, SO, AO, CN, SC, need, None), b"overlap")
-    refused(call(ctx.h, n // 2, 5, B, O, A, R, G, SL, RO, RO + 8 * (n // 2 - 1), SO, AO, CN, SC, need, None), b"overlap")
-    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, GO + 8, SC, need, None), b"overlap")
-    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SO + 8, need, None), b"overlap")
-    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, SC, SC, need, None), b"overlap")
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, O, CN, SC, need, None), b"overlap")
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, A, AO, CN, SC, need, None), b"overlap")
-    refused(call(ctx.h, n - 1, 5, B, O, A, R, G, SL, RO, GO, SO, A + 1, CN, SC, need, None), b"overlap")  # a shifted mask is not in place
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, O, need, None), b"overlap")
-    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, B + 8, SC, need, None), b"overlap the box")
-    refused(call(ctx.h, n, 5, SO + 16, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"overlap the box")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, R, GO, SO, AO, CN, SC, need, None), b"sorted rays overlap the rays")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, None, GO, R, AO, CN, SC, need, None), b"sorted slots overlap the rays")  # the rays are read without dRaysOut
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, G, SO, AO, CN, SC, need, None), b"sorted rng states overlap the rng states")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SL, AO, CN, SC, need, None), b"sorted slots overlap the slots")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, R + 36 * (n - 1), GO, SO, AO, CN, SC, need, None), b"sorted rays overlap the rays")
+    refused(call(ctx.h, n // 2, 5, B, O, A, R, G, SL, RO, RO + 8 * (n // 2 - 1), SO, AO, CN, SC, need, None), b"sorted rays overlap the sorted rng states")
+    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, GO + 8, SC, need, None), b"sorted rng states overlap the count")
+    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SO + 8, need, None), b"sorted slots overlap the scratch")
+    refused(call(ctx.h, n // 8, 5, B, O, A, R, G, SL, RO, GO, SO, AO, SC, SC, need, None), b"count overlap the scratch")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, O, CN, SC, need, None), b"sorted mask overlap the outputs")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, A, AO, CN, SC, need, None), b"sorted slots overlap the mask")
+    refused(call(ctx.h, n - 1, 5, B, O, A, R, G, SL, RO, GO, SO, A + 1, CN, SC, need, None), b"sorted mask overlap the mask")  # a shifted mask is not in place
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, O, need, None), b"scratch overlap the outputs")
+    refused(call(ctx.h, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, B + 8, SC, need, None), b"count overlap the box")
+    refused(call(ctx.h, n, 5, SO + 16, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None), b"sorted slots overlap the box")
     assert call(None, n, 5, B, O, A, R, G, SL, RO, GO, SO, AO, CN, SC, need, None) != 0
     # an input whose output is NULL is ignored, overlaps and misalignment included (the rays are always read)
     assert call(ctx.h, n, 5, B, O, A, R, GO + 4, SO + 2, None, None, None, None, CN, SC, need, None) == 0, dev.lib.srtLastError(ctx.h)
@@ -564,6 +564,6 @@ def test_side_effects_and_errors(ctx, dev, abi, camera):
         assert bool((outs[k] == SENTINEL).all())
     for k, t in d_in.items():
         assert t.cpu().numpy()[:n * ROW_IN[k]].tobytes() == np.ascontiguousarray(d[k]).tobytes()
-    with pytest.raises(dev.SrtError, match="overlap"):
+    with pytest.raises(dev.SrtError, match="sorted rays overlap the rays"):
         both = torch.zeros((n, 9), dtype=torch.float32, device="cuda")
         ctx.sort_paths_device(5, rays=both, rays_out=both)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import abi_header
+from bad_tensors import bad_tensors
 
 
 def test_prototype_matches_the_header(dev, abi):
@@ -54,21 +55,11 @@ def test_scratch_constant(abi):
     assert found == [str(abi.SRT_MAX_BOUNCE)]
 
 
-def _bad_tensors(good, columns):  # tests/test_pathstep_abi.py's
-    other = columns - 1
-    return {"on the GPU": good,  # a CPU tensor, right in everything else
-            "must be": good.double() if good.dtype.is_floating_point else good.to(torch.int16),
-            "shape": torch.zeros((8, other), dtype=good.dtype),
-            "shape ": torch.zeros(8 * columns, dtype=good.dtype),
-            "contiguous": torch.zeros((columns, 8), dtype=good.dtype).t(),
-            "torch tensor": np.zeros((8, columns), np.float32)}
-
-
 def test_wrapper_refuses_a_bad_tensor_before_the_c_call(dev):
     """A context that was never created has no handle: reaching the C call would fail otherwise than by ValueError."""
     c = object.__new__(dev.Context)
     rng = torch.zeros((8,), dtype=torch.int64)
-    for what, bad in _bad_tensors(torch.zeros((8, 9), dtype=torch.float32), 9).items():  # each refusal names its own reason
+    for what, bad in bad_tensors(torch.zeros((8, 9), dtype=torch.float32), 9).items():  # each refusal names its own reason
         with pytest.raises(ValueError, match="rays.*" + what.strip()):
             c.trace_paths_device(bad, rng, 4, (0.0, 0.0, 0.0))
     # rng is checked behind rays: rays that answer the wrapper's questions as an (8, 9) float32 tensor on a GPU would

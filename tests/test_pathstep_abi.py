@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import abi_header
+from bad_tensors import bad_tensors
 import pathstep_ref as PR
 
 DEVICE_ENTRIES = ("srtCameraRaysDevice", "srtScatterRaysDevice", "srtPathStepDevice")
@@ -59,28 +60,18 @@ def test_path_out_layout_and_status_values(abi):
     assert (abi.SRT_PATH_INVALID, abi.SRT_PATH_MISS, abi.SRT_PATH_ENDED, abi.SRT_PATH_SCATTERED) == (-1, 0, 1, 2)
 
 
-def _bad_tensors(good, columns):
-    other = columns - 1
-    return {"on the GPU": good,  # a CPU tensor, right in everything else
-            "must be": good.double() if good.dtype.is_floating_point else good.to(torch.int16),
-            "shape": torch.zeros((8, other), dtype=good.dtype),
-            "shape ": torch.zeros(8 * columns, dtype=good.dtype),
-            "contiguous": torch.zeros((columns, 8), dtype=good.dtype).t(),
-            "torch tensor": np.zeros((8, columns), np.float32)}
-
-
 def test_wrappers_refuse_a_bad_tensor_before_the_c_call(dev, abi):
     """A context that was never created has no handle: reaching the C call would fail otherwise than by ValueError."""
     c = object.__new__(dev.Context)
     rays = torch.zeros((8, 9), dtype=torch.float32)
     rng = torch.zeros((8,), dtype=torch.int64)
-    for what, bad in _bad_tensors(rays, 9).items():  # each refusal names its own reason
+    for what, bad in bad_tensors(rays, 9).items():  # each refusal names its own reason
         with pytest.raises(ValueError, match=what.strip()):
             c.path_step_device(bad, rng)
         with pytest.raises(ValueError, match=what.strip()):
             c.scatter_device(bad, torch.zeros((8, 22), dtype=torch.int32), rng)
     p = abi.default_render_params(16, 12, 1, 4)
-    for what, bad in _bad_tensors(torch.zeros((8, 2), dtype=torch.int32), 2).items():
+    for what, bad in bad_tensors(torch.zeros((8, 2), dtype=torch.int32), 2).items():
         with pytest.raises(ValueError, match="pixel_sample.*" + what.strip()):
             c.camera_rays_device(p, bad)
 

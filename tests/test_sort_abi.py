@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import abi_header
+from bad_tensors import bad_tensors
 import sort_ref as SR
 
 
@@ -56,16 +57,6 @@ def test_scratch_bytes_is_zero_for_nothing_and_never_decreases(dev):
     assert dev.Context.sort_scratch_bytes(1025) == f(1025) and dev.Context.sort_scratch_bytes(0) == 0
 
 
-def _bad_tensors(good, columns):  # tests/test_pathstep_abi.py's
-    other = columns - 1
-    return {"on the GPU": good,  # a CPU tensor, right in everything else
-            "must be": good.double() if good.dtype.is_floating_point else good.to(torch.int16),
-            "shape": torch.zeros((8, other), dtype=good.dtype),
-            "shape ": torch.zeros(8 * columns, dtype=good.dtype),
-            "contiguous": torch.zeros((columns, 8), dtype=good.dtype).t(),
-            "torch tensor": np.zeros((8, columns), np.float32)}
-
-
 def test_wrapper_refuses_before_the_c_call(dev, abi):
     """A context that was never created has no handle: reaching the C call would fail otherwise than by ValueError."""
     c = object.__new__(dev.Context)
@@ -79,7 +70,7 @@ def test_wrapper_refuses_before_the_c_call(dev, abi):
         c.sort_paths_device(5, rays=rays, rng_out=torch.zeros((8,), dtype=torch.int64))
     with pytest.raises(ValueError, match="torch stream or a box"):
         c.sort_paths_device(5, rays=rays, stream=12345)
-    for what, bad in _bad_tensors(rays, 9).items():  # each refusal names its own reason
+    for what, bad in bad_tensors(rays, 9).items():  # each refusal names its own reason
         with pytest.raises(ValueError, match="rays.*" + what.strip()):
             c.sort_paths_device(5, rays=bad)
 
