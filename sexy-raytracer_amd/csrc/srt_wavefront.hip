@@ -41,10 +41,19 @@
 // The moments instances keep the item's running sum of l_s in B.w and of l_s^2 in C.z (0 in the others): every store of
 // B and C carries them, so they cost no traffic of their own.
 // Control words (LDS, behind the tree): 0..15 the waves' current work queue; 16 + 2r ring r's tail (places reserved),
-// 17 + 2r its head (places claimed) -- one 8-byte read gets both --, 28 live contexts, 29 abort.  Behind them the rings
+// 17 + 2r its head (places claimed) -- one 8-byte read gets both --, 28 live contexts, 29 abort; 32..55 the sphere records
+// of the walks' head leaf (DevScene::wfHead != 0; the whole-tree instances that neither count nor are hybrid): the first
+// object's three 16-byte quads of DevScene::spheres, then the second object's (zeros where the leaf holds one sphere),
+// copied by the set-up of every launch and read-only afterwards.  The other words stay zero.  Behind them the rings
 // (16-bit slots), then per context the t (float) and the primitive (16 bits) its last walk ended at.
 #define WF_CTL_LIVE 28
 #define WF_CTL_ABORT 29
+#define WF_CTL_LEAFREC 32       // first word of the head leaf's two sphere records
+#define WF_CTL_LEAFREC_WORDS 24  // 2 records x 48 bytes
+static_assert(WF_CTL_LEAFREC > WF_CTL_ABORT && WF_CTL_LEAFREC > WF_CTL_LIVE && WF_CTL_LEAFREC > WF_CTL_HEAD(WF_RINGS - 1),
+              "the head leaf's records lie behind the ring words, the live count and the abort word");
+static_assert(WF_CTL_LEAFREC + WF_CTL_LEAFREC_WORDS <= WF_CTL_WORDS, "the head leaf's records lie inside the control block");
+static_assert(WF_CTL_LEAFREC % 4 == 0, "the head leaf's records are read 16 bytes at a time (the block starts at a multiple of 32)");
 #define WF_PEND_MISS 0      // context meta word: depth | pend << 8
 #define WF_PEND_TERMINAL 2
 
@@ -61,16 +70,32 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const f32x4 LdsVec4;  // a 16-byte slot addressed by its LDS byte offset
 __device__ __forceinline__ uint32_t bufLoad1(Rsrc r, int off) { return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0); }
 
-// sphere::hit on the record at byte offset `off` of DevScene::spheres (through its buffer resource): the one statement for
-// the primitive step and for the head of a walk (swapStep)
-__device__ __forceinline__ bool wfSphereHit(Rsrc rsSpheres, int off, const Ray& ray, float rayA, float tMin, float closest, float& t) {
-  const float4 s0 = bufLoad4(rsSpheres, off), s1 = bufLoad4(rsSpheres, off + 16);
+// sphere::hit on a record's loaded quads s0 and s1; `quad2()` hands out the third, asked for where the sphere moves: the one
+// statement for the primitive step and for the head of a walk (swapStep), which differ in where the quads come from
+template <class Quad2>
+__device__ __forceinline__ bool wfSphereHitOn(const float4 s0, const float4 s1, Quad2 quad2, const Ray& ray, float rayA, float tMin,
+                                              float closest, float& t) {
   V3 center = mk(s0.x, s0.y, s0.z);
   if (__float_as_int(s1.w) & (1 << 30)) {  // sphere.h:47-52
-    const float4 s2 = bufLoad4(rsSpheres, off + 32);
+    const float4 s2 = quad2();
     center = center + ((ray.time - s2.x) / (s2.y - s2.x)) * (mk(s1.x, s1.y, s1.z) - center);
   }
   return sphereHitV(center, s0.w, ray, rayA, tMin, closest, t);
+}
+// ... on the record at byte offset `off` of DevScene::spheres, through its buffer resource (the primitive step)
+__device__ __forceinline__ bool wfSphereHit(Rsrc rsSpheres, int off, const Ray& ray, float rayA, float tMin, float closest, float& t) {
+  const float4 s0 = bufLoad4(rsSpheres, off), s1 = bufLoad4(rsSpheres, off + 16);
+  return wfSphereHitOn(s0, s1, [&]() { return bufLoad4(rsSpheres, off + 32); }, ray, rayA, tMin, closest, t);
+}
+// ... and on a record the set-up copied into LDS (the head): its three quads as read there, all of them asked for before
+// the first is used
+struct WfLdsSphere {
+  f32x4 q0, q1, q2;
+};
+__device__ __forceinline__ WfLdsSphere wfLdsSphereLoad(const LdsVec4* rec) { return WfLdsSphere{rec[0], rec[1], rec[2]}; }
+__device__ __forceinline__ bool wfSphereHit(const WfLdsSphere& s, const Ray& ray, float rayA, float tMin, float closest, float& t) {
+  return wfSphereHitOn(make_float4(s.q0.x, s.q0.y, s.q0.z, s.q0.w), make_float4(s.q1.x, s.q1.y, s.q1.z, s.q1.w),
+                       [&]() { return make_float4(s.q2.x, s.q2.y, s.q2.z, s.q2.w); }, ray, rayA, tMin, closest, t);
 }
 
 // DevScene::wfHead of the launch, read from the kernel-argument segment where it is called (the swap step): one scalar
@@ -182,6 +207,17 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
       ctl[WF_CTL_LIVE] = POOL;
     }
     if (threadIdx.x < 16) ctl[threadIdx.x] = (int)(blockIdx.x % (unsigned)a.numQueues);  // the waves' home work queue
+    if constexpr (!HYBRID && !COUNT) {
+      // The sphere records of the walks' head leaf (swapStep), as DevScene::spheres holds them at this launch -- an update of
+      // the spheres between launches needs nothing more: one thread per 16-byte quad, the first object's three and, where the
+      // leaf has a second object, its three (zeros otherwise).  Read-only from the barrier below on.
+      const int32_t leaf = sc.wfHead;
+      const int quad = (int)threadIdx.x - 64;  // (the second wave: the first has the words above to write)
+      if (leaf != 0 && quad >= 0 && quad < (srtWfLeafHasSecond(leaf) ? 6 : 3)) {
+        const int ref = quad < 3 ? srtWfLeafFirst(leaf) : srtWfLeafFirst(srtWfLeafRest(leaf));
+        reinterpret_cast<float4*>(ctl + WF_CTL_LEAFREC)[quad] = bufLoad4(rsSpheres, (~ref >> 1) * 48 + 16 * (quad < 3 ? quad : quad - 3));
+      }
+    }
     __syncthreads();
   }
   int32_t* const waveQueue = ctl + (threadIdx.x >> 6);
@@ -524,8 +560,9 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
       // The HEAD of the walks (DevScene::wfHead; the instances that walk the sequence): a leaf word != 0 says that every walk
       // of this launch begins at that leaf -- no gate in front of it, spheres alone in it, its hit and miss words lead to the
       // same successor.  Its visit and its one or two sphere tests run here, for all the new rays at once and on wave-uniform
-      // records, and the walks start at its miss word: what the loop would have done with these lanes in a node burst at
-      // partial fill and two primitive rounds shared with lanes at triangles.  Same calls, same values, same order.
+      // records (read from LDS, where the set-up put them: control words WF_CTL_LEAFREC..), and the walks start at its miss
+      // word: what the loop would have done with these lanes in a node burst at partial fill and two primitive rounds shared
+      // with lanes at triangles.  Same calls, same values, same order.
       const int32_t head = !HYBRID && !COUNT ? wfHeadFromKernarg() : 0;
       if (id >= 0) {
         ray.o = mk(A.x, A.y, A.z);
@@ -538,6 +575,13 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
             // visit()'s verdict for a leaf, bit for bit; `cur` is the entry word, the record's LDS address
             const LdsVec4* rec = (const LdsVec4*)(uintptr_t)(uint32_t)cur;
             const f32x4 r0 = rec[0], r1 = rec[1];
+            // ... and the leaf's sphere records, from the control words the set-up copied them to: every lane reads the same
+            // slots (a broadcast), and the requests go out with the box's, in front of the box test -- no load of the head
+            // waits for a test, and none goes through the vector memory path
+            const LdsVec4* leafRec = (const LdsVec4*)(ctl + WF_CTL_LEAFREC);
+            // (both slots and the moving quads unconditionally: a branch around the second slot's reads made the compiler wait
+            // for the first slot's before it issued them, a second round trip; a slot of zeros is read and not used)
+            const WfLdsSphere sph1 = wfLdsSphereLoad(leafRec), sph2 = wfLdsSphereLoad(leafRec + 3);
             const float4 n0 = make_float4(r0.x, r0.y, r0.z, r0.w), n1 = make_float4(r1.x, r1.y, r1.z, r1.w);
             bool undecided;
             bool hitBox = boxHitSign<true>(n0, n1, rp, rq, negOR, slabTol, a.tMin, closest, undecided);
@@ -547,13 +591,13 @@ __global__ __launch_bounds__(WF_BLOCK, 4) void srt_render_wf_kernel(const Render
             if (hitBox) {
               float t;
               const int first = srtWfLeafFirst(head);
-              if (wfSphereHit(rsSpheres, (~first >> 1) * 48, ray, rayA, a.tMin, closest, t)) {
+              if (wfSphereHit(sph1, ray, rayA, a.tMin, closest, t)) {
                 closest = t;
                 hitRef = first;
               }
               if (srtWfLeafHasSecond(head)) {
                 const int second = srtWfLeafFirst(srtWfLeafRest(head));
-                if (wfSphereHit(rsSpheres, (~second >> 1) * 48, ray, rayA, a.tMin, closest, t)) {
+                if (wfSphereHit(sph2, ray, rayA, a.tMin, closest, t)) {
                   closest = t;
                   hitRef = second;
                 }
