@@ -30,6 +30,12 @@
 #define SRT_MAT_TYPE_SHIFT 24   /* four bits: SRT_MAT_* (two bits) | SRT_MAT_TEXTURED */
 #define SRT_MAT_TEXTURED 4      /* a pbr material with at least one texture slot in use */
 #define SRT_MAT_FLAGS_SHIFT 28
+// the mode of a texture slot of a material's shading record (DevScene::shadeRecs; the record's layout is in srt_path.h)
+#define SRT_SLOT_NONE 0u
+#define SRT_SLOT_SOLID 1u
+#define SRT_SLOT_IMAGE 2u
+#define SRT_SLOT_GENERIC 3u
+#define SRT_SLOT_CHECKER2 7u  // SRT_SLOT_GENERIC | 4: albedo slot only, colours at +80 / +96 of the record
 
 struct DevMaterial {  // 48 B
   int32_t type;

@@ -532,12 +532,7 @@ __device__ __forceinline__ float schlickGAF(float NdotV, float roughness) {  // 
 //        walking texture -> checker -> solidColor descriptors one dependent load after the other
 // Slot modes: 0 no texture, 1 solid colour (also the magenta of a failed load; lights only), 2 image of >= 3 bytes per
 // pixel with both sides below 2^15 (one dword per texel), 3 anything else (checker, solid colour in a pbr slot, 1- and
-// 2-byte images): texValue on the texture id.
-#define SRT_SLOT_NONE 0u
-#define SRT_SLOT_SOLID 1u
-#define SRT_SLOT_IMAGE 2u
-#define SRT_SLOT_GENERIC 3u
-#define SRT_SLOT_CHECKER2 7u  // SRT_SLOT_GENERIC | 4: albedo slot only, colours at +80 / +96 of the record
+// 2-byte images): texValue on the texture id.  (SRT_SLOT_* in srt_device.h: srt_scene.cpp writes them.)
 // byte offset of the texel an image lookup reads (imagePNG::value, texture.h:129-146)
 __device__ __forceinline__ int texelOffset(int width, int height, int base, float u, float v) {
   u = clampf(u, 0.0f, 1.0f);

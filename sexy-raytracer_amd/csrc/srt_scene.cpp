@@ -1,6 +1,7 @@
 // srt_scene.cpp -- the host stage of srtUploadScene (srt_scene.h): scene validation, the reference-order BVH build,
 // the flattening of a scene into the device record formats, and the host arithmetic of the C ABI (the global
-// generator, srtMakeCamera).  No HIP runtime calls: everything here runs and is tested without a device.
+// generator, srtMakeCamera).  No HIP runtime calls: everything here runs without a device, and validateScene and flattenScene
+// are tested without one (examples/scene_probe.cpp, tests/test_scene_host.py: every array, bit for bit, and under sanitizers).
 //
 // Host arithmetic that feeds the kernels (BVH boxes, per-triangle normals and tangent frames, the camera frame) keeps
 // the reference's operation order; this file is built with -ffp-contract=off and without -march so it rounds like the
@@ -220,9 +221,25 @@ std::string validateScene(const SrtSceneDesc* d) {
   return std::string();
 }
 
-std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene& h) {
-  // ---- primitive records.  Device arrays are indexed by the scene's own triangle /
-  // sphere indices; the owning list index is kept for srtTraceRays' prim output.
+// ------------------------------------------------------------------ the stages of flattenScene, in its order
+namespace {
+
+// ~primListIndex -> device prim ref.  triDevIndex (HostScene::triDevIndex): the device index of a triangle, empty = identity
+int32_t devRef(const SrtSceneDesc* d, const std::vector<int32_t>& triDevIndex, int32_t listRef) {
+  const SrtPrimRef& p = d->prims[~listRef];
+  if (p.type == SRT_PRIM_SPHERE) return ~((p.index << 1) | 1);
+  return ~((triDevIndex.empty() ? p.index : triDevIndex[p.index]) << 1);
+}
+
+// box of node i of a float4 node array (two records per node: min, max)
+Box nodeBox(const std::vector<float4>& nodes, size_t i) {
+  const float4 &mn = nodes[2 * i], &mx = nodes[2 * i + 1];
+  return Box{{mn.x, mn.y, mn.z}, {mx.x, mx.y, mx.z}};
+}
+
+// Primitive records.  Device arrays are indexed by the scene's own triangle / sphere indices; the owning list index is
+// kept for srtTraceRays' prim output.
+void primitiveRecords(const SrtSceneDesc* d, HostScene& h) {
   h.triPrimId.assign(d->numTriangles, -1);
   h.sphPrimId.assign(d->numSpheres, -1);
   for (int i = 0; i < d->numPrims; ++i) {
@@ -242,23 +259,19 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     const SrtSphereIn& s = d->spheres[i];
     sphereRecords(vec3(s.center0), vec3(s.center1), s.time0, s.time1, s.radius, s.material, &h.spheres[3 * (size_t)i]);
   }
-  // device index of a triangle: identity until the trees are built, then the order in which the host-built
-  // trees' leaves reference the triangles (below), so that a leaf's records and its neighbours' sit together
-  std::vector<int32_t> triDevIndex;
-  auto devRef = [&](int32_t listRef) -> int32_t {  // ~primListIndex -> device prim ref
-    const SrtPrimRef& p = d->prims[~listRef];
-    if (p.type == SRT_PRIM_SPHERE) return ~((p.index << 1) | 1);
-    return ~((triDevIndex.empty() ? p.index : triDevIndex[p.index]) << 1);
-  };
+}
 
-  // ---- world: build each bvhNode (consumes the global generator in scene order)
+// The world: builds each bvhNode (consumes the global generator in scene order), adopts the caller-built trees and reserves
+// the node slots of the device-built ones.  Returns whether a tree was adopted: its inner boxes are the caller's, not unions
+// of its leaves'.
+bool buildTrees(const SrtSceneDesc* d, HostScene& h) {
   h.itemNodes.resize(d->numWorld);
-  bool adopted = false;  // a caller-built tree: its inner boxes are the caller's, not unions of its leaves'
+  bool adopted = false;
   for (int w = 0; w < d->numWorld; ++w) {
     const SrtWorldItem& it = d->world[w];
     adopted = adopted || (it.kind == SRT_WORLD_BVH && it.nodes);
     if (it.kind == SRT_WORLD_PRIM) {
-      h.world.push_back(devRef(~it.first));
+      h.world.push_back(devRef(d, h.triDevIndex, ~it.first));
       continue;
     }
     if (!it.nodes && (it.builder == SRT_BUILDER_LBVH || it.builder == SRT_BUILDER_PLOC)) {
@@ -279,8 +292,8 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     h.itemNodes[w].resize(b.nodes.size());
     b.toBvhNodes(h.itemNodes[w].data());
     for (const BuildNode& n : b.nodes) {
-      int32_t l = n.left >= 0 ? SRT_NODE_REF(n.left + base) : devRef(n.left);
-      int32_t r = n.right >= 0 ? SRT_NODE_REF(n.right + base) : devRef(n.right);
+      int32_t l = n.left >= 0 ? SRT_NODE_REF(n.left + base) : devRef(d, h.triDevIndex, n.left);
+      int32_t r = n.right >= 0 ? SRT_NODE_REF(n.right + base) : devRef(d, h.triDevIndex, n.right);
       h.nodes.push_back(make_float4(n.box.mn[0], n.box.mn[1], n.box.mn[2], bitsAs<float>(&l)));
       h.nodes.push_back(make_float4(n.box.mx[0], n.box.mx[1], n.box.mx[2], bitsAs<float>(&r)));
       h.nodeAxis.push_back(n.axis);
@@ -296,13 +309,14 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
       if (b.nodes[i].right >= 0) depth[b.nodes[i].right] = depth[i] + 1;
     }
   }
-  if (h.nodes.size() / 2 > (size_t)SRT_MAX_NODES)
-    return format("scene: %zu BVH nodes exceed the %d the device references can address", h.nodes.size() / 2, SRT_MAX_NODES);
+  return adopted;
+}
 
-  // ---- materials / textures.  typeBits: the material's type and SRT_MAT_TEXTURED, as the primitives' material words
-  // and the shading records carry them
+// Materials, textures and texels; the error text.  typeBits: per material its type and SRT_MAT_TEXTURED, as the primitives'
+// material words and the shading records carry them.
+std::string materialRecords(const SrtSceneDesc* d, HostScene& h, std::vector<int32_t>& typeBits) {
   h.materials.resize(d->numMaterials);
-  std::vector<int32_t> typeBits(d->numMaterials);
+  typeBits.resize(d->numMaterials);
   for (int i = 0; i < d->numMaterials; ++i) {
     const SrtMaterialIn& m = d->materials[i];
     DevMaterial& dm = h.materials[i];
@@ -313,7 +327,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     dm.metalness = m.type == SRT_MAT_METAL ? (m.fuzz < 1.0f ? m.fuzz : 1.0f)  // material.h:89
                    : m.type == SRT_MAT_DIELECTRIC ? m.ir : m.metalness;
     dm.roughness = m.roughness;
-    // which hitRecord fields this material can observe (srt_kernels.hip sphereRecord/triRecord)
+    // which hitRecord fields this material can observe (srt_path.h sphereRecord/triRecord)
     auto readsUv = [&](int tex) {
       if (tex < 0) return false;
       const SrtTextureIn& t = d->textures[tex];
@@ -359,8 +373,12 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     }
     if (h.texels.size() > (size_t)0x7fffff00) return "scene: more than 2 GiB of texels";
   }
-  // ---- the material's flags ride in every primitive's material word (srt_device.h SRT_MAT_FLAGS_SHIFT), and the hit
-  // step's 128-byte shading records (srt_kernels.hip shade)
+  return std::string();
+}
+
+// The material's flags ride in every primitive's material word (srt_device.h SRT_MAT_FLAGS_SHIFT), and the hit step's
+// 128-byte shading records (srt_path.h shade; their layout is under "materials" there); the error text.
+std::string shadingRecords(const SrtSceneDesc* d, const std::vector<int32_t>& typeBits, HostScene& h) {
   if (d->numMaterials > SRT_MAT_INDEX_MASK) return format("scene: more than %d materials", SRT_MAT_INDEX_MASK);
   auto withFlags = [&](float& word) {
     int32_t bits = bitsAs<int32_t>(&word);
@@ -382,24 +400,24 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     if (m.type == SRT_MAT_LIGHT && ids[0] >= 0) {
       const DevTexture& t = h.textures[ids[0]];
       if (t.kind == SRT_TEX_SOLID)
-        r[2] = make_uint4(1, f2u(t.color[0]), f2u(t.color[1]), f2u(t.color[2]));
+        r[2] = make_uint4(SRT_SLOT_SOLID, f2u(t.color[0]), f2u(t.color[1]), f2u(t.color[2]));
       else if (t.kind == SRT_TEX_IMAGE && t.width == 0)
-        r[2] = make_uint4(1, f2u(1.0f), f2u(0.0f), f2u(1.0f));  // failed load: magenta (texture.h:130-131)
+        r[2] = make_uint4(SRT_SLOT_SOLID, f2u(1.0f), f2u(0.0f), f2u(1.0f));  // failed load: magenta (texture.h:130-131)
       else if (t.kind == SRT_TEX_IMAGE && t.bpp >= 3)
-        r[2] = make_uint4(2, (uint32_t)t.width, (uint32_t)t.height, (uint32_t)t.offset);
+        r[2] = make_uint4(SRT_SLOT_IMAGE, (uint32_t)t.width, (uint32_t)t.height, (uint32_t)t.offset);
       else
-        r[2] = make_uint4(3, (uint32_t)ids[0], 0, 0);  // checker, 1- and 2-byte images: texValue
+        r[2] = make_uint4(SRT_SLOT_GENERIC, (uint32_t)ids[0], 0, 0);  // checker, 1- and 2-byte images: texValue
     }
     // +48, +64: the four pbr slots, two dwords each
     uint32_t packed[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int k = 0; k < 4; ++k) {
-      if (ids[k] < 0) continue;  // mode 0: no texture
+      if (ids[k] < 0) continue;  // SRT_SLOT_NONE
       const DevTexture& t = h.textures[ids[k]];
       if (t.kind == SRT_TEX_IMAGE && t.bpp >= 3 && t.width > 0 && t.width < 32768 && t.height < 32768) {
-        packed[2 * k] = 2u | (uint32_t)t.width << 2 | (uint32_t)t.height << 17;
+        packed[2 * k] = SRT_SLOT_IMAGE | (uint32_t)t.width << 2 | (uint32_t)t.height << 17;
         packed[2 * k + 1] = (uint32_t)t.offset;
       } else {
-        packed[2 * k] = 3u;  // everything else goes through texValue on the id
+        packed[2 * k] = SRT_SLOT_GENERIC;  // everything else goes through texValue on the id
         packed[2 * k + 1] = (uint32_t)ids[k];
       }
     }
@@ -408,7 +426,7 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
       const DevTexture& c = h.textures[ids[0]];
       if (c.even >= 0 && c.odd >= 0 && c.even < (int)h.textures.size() && c.odd < (int)h.textures.size() && h.textures[c.even].kind == SRT_TEX_SOLID &&
           h.textures[c.odd].kind == SRT_TEX_SOLID) {
-        packed[0] = 7u;  // SRT_SLOT_CHECKER2
+        packed[0] = SRT_SLOT_CHECKER2;
         r[5] = make_uint4(f2u(h.textures[c.even].color[0]), f2u(h.textures[c.even].color[1]), f2u(h.textures[c.even].color[2]), 0);
         r[6] = make_uint4(f2u(h.textures[c.odd].color[0]), f2u(h.textures[c.odd].color[1]), f2u(h.textures[c.odd].color[2]), 0);
       }
@@ -416,115 +434,127 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     r[3] = make_uint4(packed[0], packed[1], packed[2], packed[3]);
     r[4] = make_uint4(packed[4], packed[5], packed[6], packed[7]);
   }
-  // ---- triangle records in tree order.  Device arrays were filled in the scene's own triangle order; a tree's
-  // leaves reference them at random (a mesh's index order has nothing to do with the median splits), and with
-  // millions of triangles every test is then a 48-byte gather from a cold place.  Renumber the triangles by
-  // their first appearance in the (pre-order) node arrays of the host-built trees: the two triangles of a leaf
-  // and the leaves of a subtree become neighbours in memory.  Triangles no host-built tree references keep
-  // their relative order behind them.  References are rewritten, nothing else changes (primitive ids reported
-  // by srtTraceRays go through triPrimId, which is permuted along).
-  if (d->numTriangles > 1 && !h.nodes.empty()) {
-    std::vector<int32_t> order(d->numTriangles, -1);
-    int32_t next = 0;
-    auto visit = [&](float bits) {
-      const int32_t r = bitsAs<int32_t>(&bits);
-      if (r >= 0 || r == SRT_REF_DONE) return;
-      const int32_t pr = ~r;
-      if ((pr & 1) == 0 && (pr >> 1) < d->numTriangles && order[pr >> 1] < 0) order[pr >> 1] = next++;
-    };
-    for (size_t i = 0; i + 1 < h.nodes.size(); i += 2) {
-      visit(h.nodes[i].w);
-      visit(h.nodes[i + 1].w);
-    }
-    if (next > 0) {
-      for (int32_t i = 0; i < d->numTriangles; ++i)
-        if (order[i] < 0) order[i] = next++;
-      auto remap = [&](int32_t r) {
-        if (r >= 0 || r == SRT_REF_DONE || (~r & 1)) return r;
-        return ~(order[~r >> 1] << 1);
-      };
-      for (float4& v : h.nodes) {
-        const int32_t r = remap(bitsAs<int32_t>(&v.w));
-        v.w = bitsAs<float>(&r);
-      }
-      for (int32_t& wr : h.world) wr = remap(wr);
-      std::vector<float4> tt(h.triTest.size()), ts(h.triShade.size()), tf(h.triFast.size());
-      std::vector<int32_t> tp(h.triPrimId.size());
-      for (int32_t i = 0; i < d->numTriangles; ++i) {
-        const int32_t j = order[i];
-        for (int k = 0; k < 3; ++k) tt[3 * (size_t)j + k] = h.triTest[3 * (size_t)i + k];
-        for (int k = 0; k < 4; ++k) ts[4 * (size_t)j + k] = h.triShade[4 * (size_t)i + k];
-        for (int k = 0; k < SRT_TRI_FAST_SLOTS; ++k) tf[SRT_TRI_FAST_SLOTS * (size_t)j + k] = h.triFast[SRT_TRI_FAST_SLOTS * (size_t)i + k];
-        tp[j] = h.triPrimId[i];
-      }
-      h.triTest.swap(tt);
-      h.triShade.swap(ts);
-      h.triFast.swap(tf);
-      h.triPrimId.swap(tp);
-      triDevIndex.swap(order);  // devRef of the device-built trees below
-    }
+  return std::string();
+}
+
+// Triangle records in tree order.  Device arrays were filled in the scene's own triangle order; a tree's leaves reference them
+// at random (a mesh's index order has nothing to do with the median splits), and with millions of triangles every test is then
+// a 48-byte gather from a cold place.  Renumber the triangles by their first appearance in the (pre-order) node arrays of the
+// host-built trees: the two triangles of a leaf and the leaves of a subtree become neighbours in memory.  Triangles no
+// host-built tree references keep their relative order behind them.  References are rewritten, nothing else changes (primitive
+// ids reported by srtTraceRays go through triPrimId, which is permuted along).  Leaves the renumbering in h.triDevIndex.
+void reorderTriangles(const SrtSceneDesc* d, HostScene& h) {
+  if (d->numTriangles <= 1 || h.nodes.empty()) return;
+  std::vector<int32_t> order(d->numTriangles, -1);
+  int32_t next = 0;
+  auto visit = [&](float bits) {
+    const int32_t r = bitsAs<int32_t>(&bits);
+    if (r >= 0 || r == SRT_REF_DONE) return;
+    const int32_t pr = ~r;
+    if ((pr & 1) == 0 && (pr >> 1) < d->numTriangles && order[pr >> 1] < 0) order[pr >> 1] = next++;
+  };
+  for (size_t i = 0; i + 1 < h.nodes.size(); i += 2) {
+    visit(h.nodes[i].w);
+    visit(h.nodes[i + 1].w);
   }
-  // ---- device-built trees: their primitives as device references.  Their node boxes are unions of primitive boxes, so
-  // fastDiv's certificate covers those as well as the host-built nodes.
-  // The sign form of the slab test asks for ordered boxes as well (a union of ordered boxes is ordered); the slots of the
-  // device-built items are zero here.
-  bool certified = true, ordered = true;
-  for (const float4& v : h.nodes) certified = certified && fastDivOperand(v.x) && fastDivOperand(v.y) && fastDivOperand(v.z);
-  for (size_t i = 0; i + 1 < h.nodes.size(); i += 2)
-    ordered = ordered && srtBoxOrdered(Box{{h.nodes[i].x, h.nodes[i].y, h.nodes[i].z}, {h.nodes[i + 1].x, h.nodes[i + 1].y, h.nodes[i + 1].z}});
+  if (next == 0) return;
+  for (int32_t i = 0; i < d->numTriangles; ++i)
+    if (order[i] < 0) order[i] = next++;
+  auto remap = [&](int32_t r) {
+    if (r >= 0 || r == SRT_REF_DONE || (~r & 1)) return r;
+    return ~(order[~r >> 1] << 1);
+  };
+  for (float4& v : h.nodes) {
+    const int32_t r = remap(bitsAs<int32_t>(&v.w));
+    v.w = bitsAs<float>(&r);
+  }
+  for (int32_t& wr : h.world) wr = remap(wr);
+  auto permute = [&](auto& records, size_t slots) {  // triangle i's `slots` elements to where triangle order[i]'s go
+    typename std::remove_reference<decltype(records)>::type moved(records.size());
+    for (int32_t i = 0; i < d->numTriangles; ++i) std::copy_n(&records[slots * (size_t)i], slots, &moved[slots * (size_t)order[i]]);
+    records.swap(moved);
+  };
+  permute(h.triTest, 3);
+  permute(h.triShade, 4);
+  permute(h.triFast, SRT_TRI_FAST_SLOTS);
+  permute(h.triPrimId, 1);
+  h.triDevIndex.swap(order);
+}
+
+// What holds of every box of the scene, the host-built nodes' and the device-built items' primitives': every coordinate is a
+// fastDivOperand, every box is srtBoxOrdered (srt_records.h)
+struct BoxCertificates {
+  bool certified, ordered;
+};
+
+// Device-built trees: their primitives as device references.  Their node boxes are unions of primitive boxes, so fastDiv's
+// certificate covers those as well as the host-built nodes.  The sign form of the slab test asks for ordered boxes as well
+// (a union of ordered boxes is ordered); the slots of the device-built items are zero here.
+BoxCertificates certifyBoxes(const SrtSceneDesc* d, const SceneOptions& o, HostScene& h) {
+  BoxCertificates c{true, true};
+  for (size_t i = 0; i < h.nodes.size() / 2; ++i) {
+    c.certified = c.certified && fastDivOperands(nodeBox(h.nodes, i));
+    c.ordered = c.ordered && srtBoxOrdered(nodeBox(h.nodes, i));
+  }
   for (DeviceBuild& db : h.deviceBuilds) {
     const SrtWorldItem& it = d->world[db.item];
     db.refs.resize(it.count);
     for (int i = 0; i < it.count; ++i) {
-      db.refs[i] = devRef(~(it.first + i));
+      db.refs[i] = devRef(d, h.triDevIndex, ~(it.first + i));
       const Box pb = primBox(d, it.first + i, it.time0, it.time1);
-      certified = certified && fastDivOperands(pb);
-      ordered = ordered && srtBoxOrdered(pb);
+      c.certified = c.certified && fastDivOperands(pb);
+      c.ordered = c.ordered && srtBoxOrdered(pb);
     }
   }
-  h.fastDivScene = certified ? o.fastDiv : 0;
-  h.boxOrderedScene = ordered ? 1 : 0;
-  // ---- thread links (srt_thread.h): the 16-bit form the LDS-resident-tree kernels walk (DevScene::nodeThread), and for a
-  // tree that does not fit into LDS the path-pool kernel's hybrid records (32-bit references, resident nodes first)
-  if (h.deviceBuilds.empty() && !h.nodes.empty()) {
-    srtThreadLinks16(h.nodes, h.world, d->numTriangles, d->numSpheres, h.nodeThread);
-    if (o.wfHybrid > 0) {
-      const size_t n = h.nodes.size() / 2;
-      const size_t fits = srtWfMaxResidentNodes(SRT_WF_HYBRID_POOL, true);  // beside the hybrid form's pool
-      const size_t fitsWhole = srtWfMaxWholeTreeNodes();                    // the whole-tree form's smallest pool
-      const size_t cap = o.wfResidentMax > 0 ? std::min<size_t>(fits, (size_t)o.wfResidentMax) : fits;
-      if (n > (o.wfResidentMax > 0 ? cap : fitsWhole))
-        h.wfResident = srtHybridRecords(h.nodes, h.world, d->numTriangles, d->numSpheres, cap, h.nodesWf, h.worldWf, h.primSecond, &h.wfIndex);
-      if (h.nodesWf.empty()) h.wfIndex.clear();
-    }
-    // ---- the regrouped tree (srt_regroup.h) for the path-pool kernel's whole-tree form.  The builder is quadratic in a
-    // tree's leaves at worst, so it runs only for what that form can take: thread links exist, no hybrid records were
-    // made, and the node array fits a CU's LDS beside the smallest pool.  Its lemma wants the reference's inner boxes to
-    // contain their leaves' (the trees built here; a caller-built tree promises nothing) and ordered boxes.  The planes of
-    // its inner boxes are planes of the leaves, so fastDivScene and boxOrderedScene hold for it as they stand.
-    if (!h.nodeThread.empty() && h.nodesWf.empty() && !adopted && ordered && h.nodes.size() / 2 <= (size_t)srtWfMaxWholeTreeNodes() &&
-        srtRegroupNodes(h.nodes, h.world, h.nodesRg)) {
-      srtThreadLinks16(h.nodesRg, h.world, d->numTriangles, d->numSpheres, h.nodeThreadRg);
-      bool same = !h.nodeThreadRg.empty();
-      for (const float4& v : h.nodesRg) same = same && (!certified || (fastDivOperand(v.x) && fastDivOperand(v.y) && fastDivOperand(v.z)));
-      for (size_t i = 0; same && i + 1 < h.nodesRg.size(); i += 2)
-        same = srtBoxOrdered(Box{{h.nodesRg[i].x, h.nodesRg[i].y, h.nodesRg[i].z}, {h.nodesRg[i + 1].x, h.nodesRg[i + 1].y, h.nodesRg[i + 1].z}});
-      if (!same) {  // (cannot happen: see srt_regroup.h unite)
-        h.nodesRg.clear();
-        h.nodeThreadRg.clear();
-      }
-      // ---- its walk sequence: the gates that rarely cull a ray elided (linear in the array)
-      SrtRegroupWalk walk;
-      if (!h.nodesRg.empty() && srtRegroupWalk(h.nodesRg, h.world, walk)) {
-        h.numWalk = (int32_t)walk.src.size();
-        h.wfHead = walk.head;
-        h.walkSeq.reserve(3 * walk.src.size() + walk.entry.size());
-        for (size_t j = 0; j < walk.src.size(); ++j) h.walkSeq.insert(h.walkSeq.end(), {walk.src[j], walk.links[2 * j], walk.links[2 * j + 1]});
-        h.walkSeq.insert(h.walkSeq.end(), walk.entry.begin(), walk.entry.end());
-      }
-    }
+  h.fastDivScene = c.certified ? o.fastDiv : 0;
+  h.boxOrderedScene = c.ordered ? 1 : 0;
+  return c;
+}
+
+// What the LDS-resident-tree kernels walk, for a world of host-built trees only.  Thread links (srt_thread.h): the 16-bit
+// form (DevScene::nodeThread), and for a tree that does not fit into LDS the path-pool kernel's hybrid records (32-bit
+// references, resident nodes first).
+void walkForms(const SrtSceneDesc* d, const SceneOptions& o, bool adopted, BoxCertificates c, HostScene& h) {
+  if (!h.deviceBuilds.empty() || h.nodes.empty()) return;
+  srtThreadLinks16(h.nodes, h.world, d->numTriangles, d->numSpheres, h.nodeThread);
+  if (o.wfHybrid > 0) {
+    const size_t n = h.nodes.size() / 2;
+    const size_t fits = srtWfMaxResidentNodes(SRT_WF_HYBRID_POOL, true);  // beside the hybrid form's pool
+    const size_t fitsWhole = srtWfMaxWholeTreeNodes();                    // the whole-tree form's smallest pool
+    const size_t cap = o.wfResidentMax > 0 ? std::min<size_t>(fits, (size_t)o.wfResidentMax) : fits;
+    if (n > (o.wfResidentMax > 0 ? cap : fitsWhole))
+      h.wfResident = srtHybridRecords(h.nodes, h.world, d->numTriangles, d->numSpheres, cap, h.nodesWf, h.worldWf, h.primSecond, &h.wfIndex);
+    if (h.nodesWf.empty()) h.wfIndex.clear();
   }
-  // ---- material class per primitive reference (DevScene::primClass)
+  // ---- the regrouped tree (srt_regroup.h) for the path-pool kernel's whole-tree form.  The builder is quadratic in a
+  // tree's leaves at worst, so it runs only for what that form can take: thread links exist, no hybrid records were
+  // made, and the node array fits a CU's LDS beside the smallest pool.  Its lemma wants the reference's inner boxes to
+  // contain their leaves' (the trees built here; a caller-built tree promises nothing) and ordered boxes.  The planes of
+  // its inner boxes are planes of the leaves, so fastDivScene and boxOrderedScene hold for it as they stand.
+  if (h.nodeThread.empty() || !h.nodesWf.empty() || adopted || !c.ordered || h.nodes.size() / 2 > (size_t)srtWfMaxWholeTreeNodes() ||
+      !srtRegroupNodes(h.nodes, h.world, h.nodesRg))
+    return;
+  srtThreadLinks16(h.nodesRg, h.world, d->numTriangles, d->numSpheres, h.nodeThreadRg);
+  bool same = !h.nodeThreadRg.empty();
+  for (size_t i = 0; same && i < h.nodesRg.size() / 2; ++i)
+    same = (!c.certified || fastDivOperands(nodeBox(h.nodesRg, i))) && srtBoxOrdered(nodeBox(h.nodesRg, i));
+  if (!same) {  // (cannot happen: see srt_regroup.h unite)
+    h.nodesRg.clear();
+    h.nodeThreadRg.clear();
+  }
+  // ---- its walk sequence: the gates that rarely cull a ray elided (linear in the array)
+  SrtRegroupWalk walk;
+  if (!h.nodesRg.empty() && srtRegroupWalk(h.nodesRg, h.world, walk)) {
+    h.numWalk = (int32_t)walk.src.size();
+    h.wfHead = walk.head;
+    h.walkSeq.reserve(3 * walk.src.size() + walk.entry.size());
+    for (size_t j = 0; j < walk.src.size(); ++j) h.walkSeq.insert(h.walkSeq.end(), {walk.src[j], walk.links[2 * j], walk.links[2 * j + 1]});
+    h.walkSeq.insert(h.walkSeq.end(), walk.entry.begin(), walk.entry.end());
+  }
+}
+
+// Material class per primitive reference (DevScene::primClass)
+void primClasses(const SrtSceneDesc* d, HostScene& h) {
   auto classOf = [&](float word, bool sphere) -> uint8_t {
     const int32_t bits = bitsAs<int32_t>(&word);
     const int type = (bits >> SRT_MAT_TYPE_SHIFT) & 3, flags = (bits >> SRT_MAT_FLAGS_SHIFT) & 3;
@@ -534,10 +564,28 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
     // four lookups) would make every hit step of the plain spheres (the ground) run that code too: it goes with "the rest"
     return flags ? 2 : 1;
   };
-  h.triDevIndex.swap(triDevIndex);
   h.primClass.assign((size_t)2 * std::max(d->numTriangles, d->numSpheres) + 2, 2);
   for (int i = 0; i < d->numTriangles; ++i) h.primClass[(size_t)i << 1] = classOf(h.triShade[4 * (size_t)i + 3].w, false);
   for (int i = 0; i < d->numSpheres; ++i) h.primClass[((size_t)i << 1) | 1] = classOf(h.spheres[3 * (size_t)i + 1].w, true);
+}
+
+}  // namespace
+
+// The stages in the one order that works; each call's comment says what it must follow.  (tests/test_scene_host.py pins
+// every member they fill, bit for bit.)
+std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene& h) {
+  primitiveRecords(d, h);
+  const bool adopted = buildTrees(d, h);  // before reorderTriangles: h.triDevIndex is empty, references are in scene order
+  if (h.nodes.size() / 2 > (size_t)SRT_MAX_NODES)
+    return format("scene: %zu BVH nodes exceed the %d the device references can address", h.nodes.size() / 2, SRT_MAX_NODES);
+  std::vector<int32_t> typeBits;
+  std::string err = materialRecords(d, h, typeBits);
+  if (err.empty()) err = shadingRecords(d, typeBits, h);  // after primitiveRecords and materialRecords: tags the material words
+  if (!err.empty()) return err;
+  reorderTriangles(d, h);                           // after buildTrees (its order is their leaves') and shadingRecords (tagged words move)
+  const BoxCertificates c = certifyBoxes(d, o, h);  // after reorderTriangles: the device-built items' references go through it
+  walkForms(d, o, adopted, c, h);                   // after certifyBoxes: regroups only what it certified, and checks the result by it
+  primClasses(d, h);                                // after shadingRecords and reorderTriangles: the tagged words, in device order
   return std::string();
 }
 

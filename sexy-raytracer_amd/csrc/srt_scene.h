@@ -1,6 +1,7 @@
 // srt_scene.h -- the host stage of srtUploadScene: validation, the reference-order BVH build and the flattening of a
 // scene into the device record formats (srt_device.h).  Pure host code (srt_scene.cpp makes no HIP runtime calls);
-// srt_api.cpp uploads what it produces and runs the device builds.
+// srt_api.cpp uploads what it produces and runs the device builds.  validateScene and flattenScene run as a stand-alone host
+// program as well (examples/scene_probe.cpp), which tests/test_scene_host.py pins member by member.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -17,6 +17,10 @@
                           compiles them): the edge set of tests/ref_cases.py and every second ray of trace_<scene>.npz
                           -> hit records and counters, the closest hit (over the tree and by brute force), and the pre-order tree; also for the edge scene (ref_edges.npz).
                           accum_mt / rgba_mt of render_<scene>.npz are asserted to be what the harness renders.
+  flatten_scenes.json     (`python tests/make_golden.py flatten <commit>`, nothing else needed) what csrc/srt_scene.cpp AS OF
+                          <commit> makes of the scenes of tests/scene_host_cases.py: that revision of the file, taken from
+                          git, linked into examples/scene_probe.cpp as it stands; per HostScene member the element count and
+                          SHA-256, the scalars, the texts of validateScene's refusals.  tests/test_scene_host.py.
   reference_models.tar.xz the model files of the reference's data/ directory that test_host_cpp.py loads, packed
                           small (pack_reference_models: data: URIs decoded, the assets/ images they embed cut out,
                           sha256 of every file as shipped); the textures they name are not included.
@@ -175,6 +179,34 @@ def assert_harness_renders(name, sb, p, acc_m, rgba_m):
     assert np.array_equal(rgba[defined], rgba_m[defined]), name
 
 
+def flatten_scenes(commit):
+    """flatten_scenes.json from the srt_scene.cpp of `commit` under today's probe, headers and Makefile flags."""
+    import subprocess
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import scene_host_cases as cases
+    import scene_probe_io as io
+    rel = "sexy-raytracer_amd/csrc/srt_scene.cpp"
+    sha = subprocess.check_output(["git", "-C", ROOT, "rev-parse", commit], text=True).strip()
+    subject = subprocess.check_output(["git", "-C", ROOT, "log", "-1", "--format=%s", sha], text=True).strip()
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, "srt_scene.cpp"), "wb") as f:
+            f.write(subprocess.check_output(["git", "-C", ROOT, "show", "%s:%s" % (sha, rel)]))
+        exe = io.build(os.path.join(d, "srt_scene_probe"), scene_cpp=os.path.join(d, "srt_scene.cpp"))
+        out = {"recorded_with": "%s of the parent commit %s (%s) linked into examples/scene_probe.cpp: python tests/make_golden.py flatten %s"
+                                % (rel, sha, subject, sha[:7]), "scenes": {}, "refusals": {}}
+        for name, make in cases.SCENES.items():
+            sb, options = make(srt)
+            out["scenes"][name] = io.digest(io.flatten(exe, d, sb.desc(), abi, options, int(getattr(sb, "global_rng_draws", 0)))[0])
+            assert "error" not in out["scenes"][name], (name, out["scenes"][name])
+        for name, make in cases.REFUSALS.items():
+            _, desc, carried = make(srt)
+            out["refusals"][name] = io.validate(exe, d, desc, abi, carried)
+            assert io.digest(io.flatten(exe, d, desc, abi, carried=carried)[0]) == {"error": out["refusals"][name]}, name
+    json.dump(out, open(os.path.join(GOLD, "flatten_scenes.json"), "w"), indent=1)
+    print("flatten_scenes.json: %d scenes, %d refusals, from %s" % (len(out["scenes"]), len(out["refusals"]), sha[:7]))
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     from PIL import Image
@@ -252,5 +284,7 @@ def main():
 if __name__ == "__main__":
     if sys.argv[1:] == ["ref"]:  # only the recorded reference results
         reference_fixtures()
+    elif sys.argv[1:2] == ["flatten"]:  # only the recorded flattening, of the given commit's srt_scene.cpp
+        flatten_scenes(sys.argv[2])
     else:
         main()
