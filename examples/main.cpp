@@ -6,6 +6,10 @@
 //   usage: srt_main [--gltf file] [--height H] [--spp N] [--bounces B] [--out file.png] [--chunks K] [--features PREFIX]
 //                  [--denoise FILE.png [--sample-variance]] [--adaptive THRESHOLD --max-spp N]
 //                  [--frames N --orbit DEG [--temporal [--guide-all-samples]]] [--frames N --spin DEG [--tree-cost] [--temporal --motion [PREFIX]]]
+//                  [--direct-light]
+//   --direct-light  the single frame through hipDevice::rtFrameDirect (srtRenderDirectImage): the light sphere is sampled at
+//                     every pbr hit -- the same image in expectation, from other samples; not with --frames, --adaptive,
+//                     --denoise or --features
 //   --features PREFIX also writes the frame's denoiser guides, PREFIX_albedo.png and PREFIX_normal.png (normals n*0.5+0.5)
 //   --denoise FILE.png also writes the frame through the library's a-trous denoiser (its default parameters) to FILE.png
 //   --sample-variance (with --denoise) the denoiser takes its noise estimate from the render's own samples (the per-pixel
@@ -106,7 +110,7 @@ int main(int argc, char** argv) {
   int frames = 0;        // > 0: a sequence, NAME_%03d.png
   float orbit = 0.0f;    // degrees the eye turns about the lookAt point's vertical axis over the sequence
   float spin = 0.0f;     // degrees per frame the model's triangles turn about the vertical axis
-  bool spinning = false, motion = false, treeCost = false;
+  bool spinning = false, motion = false, treeCost = false, directLight = false;
   std::string motionPrefix;
   for (int i = 1; i < argc; i += 2) {
     if (!strcmp(argv[i], "--sample-variance") || !strcmp(argv[i], "--temporal") || !strcmp(argv[i], "--guide-all-samples")) {
@@ -116,6 +120,11 @@ int main(int argc, char** argv) {
     }
     if (!strcmp(argv[i], "--tree-cost")) {
       treeCost = true;
+      --i;
+      continue;
+    }
+    if (!strcmp(argv[i], "--direct-light")) {
+      directLight = true;
       --i;
       continue;
     }
@@ -157,6 +166,10 @@ int main(int argc, char** argv) {
   }
   if (treeCost && !spinning) {
     std::cerr << "ERROR: --tree-cost goes with --spin\n";
+    return 1;
+  }
+  if (directLight && (frames > 0 || adaptive >= 0.0f || !denoise.empty() || !features.empty())) {
+    std::cerr << "ERROR: --direct-light renders one plain frame: not with --frames, --adaptive, --denoise or --features\n";
     return 1;
   }
   const float aspect = 16.0f / 9.0f;
@@ -282,6 +295,8 @@ int main(int argc, char** argv) {
                                        maxSpp > 0 ? maxSpp : numSamples, adaptive, 1, nullptr, &adaptiveStats)) {
       return 1;
     }
+  } else if (directLight) {
+    if (!device.rtFrameDirect(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
   } else if (denoise.empty()) {
     if (!device.rtFrame(target, imageWidth, imageHeight, mainCamera, background, numSamples, maxBounce)) return 1;
   } else {  // one render: the noisy frame and the denoised one

@@ -1097,6 +1097,84 @@ typedef struct SrtPathRadiance { /* 16 bytes, aligned to 16: one dwordx4 store *
 int srtTracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float background[3],
                         const void* dRays, int64_t n, void* dRng, void* dResult, void* dScratch, void* stream);
 
+/* Direct light sampling (next-event estimation) for device paths: at every pbr hit one of the scene's sampled lights is
+ * chosen, a direction inside the cone it subtends is drawn, a shadow ray is walked and the material is evaluated for that
+ * direction.  Opt-in: new entries only; srtRenderTiles and every entry above keep their bits.
+ *
+ * srtGetSampledLights       (host only) which primitives are sampled.
+ * srtDirectLightDevice      the direct term of every hit record: the per-hit piece for a loop of one's own.
+ * srtTracePathsDirectDevice srtTracePathsDevice with the term added at every pbr hit, in one kernel.
+ *
+ *   expectation  pbr's scatter draws sd = unit(n + randomUnitVector) -- cosine-weighted about the shading normal n, pdf
+ *             cos / pi -- and returns att(sd) = (fd + fs) * NdotL WITHOUT dividing by that pdf.  The direct term carries the
+ *             pdf as a weight, so that the estimator converges to the image of the plain one.  It is not the physically
+ *             correct weight.
+ *   lights    S = the spheres whose material is SRT_MAT_LIGHT with a solid-colour emit texture (or one that failed to load:
+ *             magenta), in prims[] order; K = |S|, no cap.  A property of the upload: an update changes no material.
+ *             srtGetSampledLights: *count = K; prims, where not NULL, receives the K prims[] indices (capacity >= K, else an
+ *             error).  Centre, radius and whether the sphere moves are read from its device record where it is used: a light
+ *             moved by srtUpdateSpheres + srtRefitScene is followed with no further call.  Never sampled, and exactly as
+ *             without these entries: triangle lights; lights whose emit texture is an image or a checker; spheres with
+ *             center0 != center1 (listed in S, but choosing one yields nothing and their emission is never dropped).
+ *   the term  at a hit x of ray r whose material is a pbr one of the scene's, when K > 0; s = the path's generator state
+ *             before the hit's scatter draws.  Float operations, each rounded, no contraction; lenSq(v) = (x*x + y*y) + z*z,
+ *             dot3(a, b) = a.x*b.x + (a.y*b.y + a.z*b.z), a scalar times a vector per component.
+ *               1  state = mix64(s ^ 0x5DEECE66D2545F49) seeds a generator of the term's own; s is not advanced.
+ *               2  u is drawn; k = min((int)(u * (float)K), K - 1); c = the sphere's center0, rad its radius;
+ *                  toC = c - x; d2 = lenSq(toC); r2 = rad * rad.  If the sphere moves or d2 <= r2: the term is 0,
+ *                  light = -1, dir = 0, weight = 0, and nothing more is drawn.
+ *               3  (a, b) = the lens disk's draw (y first: b, then a, each lo + (hi - lo) * u on (-1, 1), repeated while
+ *                  (a*a + b*b) + 0*0 >= 1); sD = a*a + b*b; q = r2 / d2; oneMinus = q / (1 + sqrt(1 - q)) (1 - cos of the
+ *                  cone's half angle, without cancellation); m = sD * oneMinus; cosT = 1 - m; sinT = sqrt(m * (2 - m));
+ *                  root = sqrt(sD); (cPhi, sPhi) = sD == 0 ? (1, 0) : (a / root, b / root); w = toC / sqrt(d2) per component;
+ *                  the basis of Duff et al. 2017 about w: sign = copysign(1, w.z); ka = -1 / (sign + w.z);
+ *                  kb = (w.x * w.y) * ka; sx = sign * w.x; t1 = (1 + (sx * w.x) * ka, sign * kb, -sx);
+ *                  t2 = (kb, sign + (w.y * w.y) * ka, -w.y); dir = ((cPhi * sinT) * t1 + (sPhi * sinT) * t2) + cosT * w.
+ *               4  weight = ((float)K * (2 * oneMinus)) * max(dot3(n, dir), 0): K * the cone's solid angle * cos / pi, the
+ *                  pi cancelled.  n = the normal scatter uses (the mapped one where there is a normal map).
+ *               5  the shadow ray {o = x, d = dir, time, tMin, tMax of r} -- the ray scatter would have written had it
+ *                  drawn dir -- is walked with `traversal`; the light is visible iff the walk returns exactly sphere k.
+ *               6  term = visible ? (attEval(dir) * Le_k per channel) * weight : an exact 0.  attEval(dir) is pbr's
+ *                  attenuation (fd + fs) * NdotL from viewVec on with sd = dir as given, on the hit's own texture
+ *                  look-ups; Le_k the light's colour.  A NaN of a roughness-0 material is what the plain path makes too.
+ *   direct    srtDirectLightDevice: dRays = SrtRay[n] (4), dRecords = SrtHit[n] (4) as srtTraceRaysDevice writes them, dRng =
+ *             uint64_t[n] (8), only READ: entry i's state before its scatter draws -- call it before srtScatterRaysDevice.
+ *             dDirect = SrtDirectOut[n], aligned to 16.  A miss, a record whose material is not pbr or not one of the
+ *             scene's, and every entry when K = 0: {0, -1, 0, 0}.  Asynchronous on `stream`, one kernel, allocates nothing.
+ *   whole     srtTracePathsDirectDevice has srtTracePathsDevice's signature, buffers, scratch, checks and guarantees.  The
+ *             term's generator is its own, so every path's bounces, hits, attenuations, steps, status and final dRng are
+ *             srtTracePathsDevice's bit for bit.  A step's hit on a sphere of S loses its emission (terminal 0, status still
+ *             SRT_PATH_ENDED) iff the step before evaluated a term (its hit was pbr, K > 0), the sphere does not move and
+ *             lenSq(c - o) > rad * rad with o the ray's origin: exactly when step 2 could have chosen it, whatever it
+ *             chose.  Camera rays and rays leaving metal or glass keep a light's emission.  Unwinding: L = D_j + L * att_j
+ *             per channel, a separate multiply and add, innermost first, D_j the term of scattered step j (0.0f where none
+ *             was evaluated).  With K = 0 every byte equals srtTracePathsDevice's.  LDS: 6 KB per bounce of maxBounce
+ *             instead of 3.
+ *   errors    as srtPathStepDevice's and srtTracePathsDevice's, decided on the host, nothing launched.  srtDirectLightDevice
+ *             also refuses dDirect overlapping an input.  srtGetSampledLights: no scene, a NULL count, capacity < K. */
+typedef struct SrtDirectOut { /* 32 bytes, aligned to 16: two dwordx4 stores */
+  float radiance[3];          /* the term */
+  int32_t light;              /* the chosen light's prims[] index; -1: none was sampled */
+  float dir[3];               /* the sampled direction (0 when light == -1) */
+  float weight;
+} SrtDirectOut;
+int srtGetSampledLights(SrtContext* ctx, int32_t* prims, int32_t capacity, int32_t* count);
+int srtDirectLightDevice(SrtContext* ctx, int32_t traversal, const void* dRays, const void* dRecords, int64_t n, const void* dRng,
+                         void* dDirect, void* stream);
+int srtTracePathsDirectDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float background[3],
+                              const void* dRays, int64_t n, void* dRng, void* dResult, void* dScratch, void* stream);
+/* srtRenderDirectImage      the frame of p through those entries, blocking, HOST buffers as srtRenderImage's (either may be
+ *             NULL): hAccum = W * H float4, the float running sum of every pixel's sample radiances in sample-index order
+ *             with w their count; hRgba = W * H x 4 bytes, its 8-bit form as the adaptive entries quantise an image
+ *             (mean = sum * (1 / w)).  Per batch of samplesPerBatch sample indices: srtCameraRaysDevice without a list
+ *             (entries pixel-major), srtTracePathsDirectDevice(p->traversal, p->maxBounce, p->background), and one kernel
+ *             that adds each pixel's samples in order.  A batch holds 60 bytes per (pixel, sample); samplesPerBatch = 0
+ *             picks the largest count that keeps a batch at 2^22 entries (at least 1).  The batch size does not change the
+ *             image.  With K = 0 and FAITHFUL steps the two outputs are srtRenderImage's (sppChunks = 1) in every byte.  Of p
+ *             the tile split, sppChunks and countStats are not read.  Errors: srtRenderImage's and the two entries'; a
+ *             negative samplesPerBatch; a batch of 2^31 entries or more. */
+int srtRenderDirectImage(SrtContext* ctx, const SrtRenderParams* p, int32_t samplesPerBatch, float* hAccum, uint8_t* hRgba);
+
 /* srtCompactPathsDevice   stable compaction of the live paths between two steps: the entries that go on move, in their
  *                         order, to the front of fresh ray, state and slot buffers, so that the next step runs on full
  *                         waves instead of on the few live lanes of nearly every wave.  Compaction moves bytes: nothing

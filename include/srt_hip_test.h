@@ -40,6 +40,14 @@ int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAo
 int srtScatterRaysForm(SrtContext* ctx, const SrtRay* rays, const SrtHit* hits, int32_t n, uint64_t seed, int32_t form, float* out13,
                        uint32_t* outFetches);
 
+/* pbr's attenuation for a direction of the caller's: what step 6 of "Direct light sampling" (include/srt_hip.h) calls
+ * attEval -- the kernels' one statement of (fd + fs) * NdotL from viewVec on (csrc/srt_path.h pbrAttenuation, which shade()
+ * evaluates for the direction it drew) on the hit's own texture look-ups.  DEVICE pointers, unlike the other hooks: dRays =
+ * SrtRay[n] (4), dRecords = SrtHit[n] (4) as srtTraceRaysDevice writes them, dDirs = float[n][3] (4), dAtt = float[n][3] (4).
+ * With the direction srtScatterRaysDevice wrote for the entry, dAtt[i] is that call's attenuation bit for bit.  0 for a miss
+ * and for a record whose material is not pbr or not one of the scene's.  One kernel on the NULL stream; does not synchronise. */
+int srtTestEvalScatterDevice(SrtContext* ctx, const void* dRays, const void* dRecords, const void* dDirs, int64_t n, void* dAtt);
+
 /* The exact chunk sum on caller-made partial sums.  hChunks: chunks x n float4, slot [c][i] (rgb partial sums, w the slot's
  * sample count).  path 0: srt_sum_chunks_kernel over the uploaded slots.  path 1: the atomic path -- one thread per slot
  * calls commitFixed on a zeroed SrtFixedAccum[n], then srt_finalize_kernel(samples).  The limit is the one a render of

@@ -119,6 +119,10 @@ class SrtPathRadiance(C.Structure):  # srtTracePathsDevice: 16 bytes per entry
     _fields_ = [("radiance", f32 * 3), ("steps", C.c_int16), ("status", C.c_int16)]
 
 
+class SrtDirectOut(C.Structure):  # srtDirectLightDevice: 32 bytes per entry
+    _fields_ = [("radiance", f32 * 3), ("light", i32), ("dir", f32 * 3), ("weight", f32)]
+
+
 class SrtRenderParams(C.Structure):
     _fields_ = [("imageWidth", i32), ("imageHeight", i32), ("spp", i32), ("maxBounce", i32),
                 ("seed", u64), ("background", f32 * 3), ("tMin", f32), ("traversal", i32),
@@ -170,6 +174,8 @@ PATH_OUT_DTYPE = np.dtype([("attenuation", "<f4", 3), ("status", "<i4"), ("emitt
 assert PATH_OUT_DTYPE.itemsize == C.sizeof(SrtPathOut) == 32
 PATH_RADIANCE_DTYPE = np.dtype([("radiance", "<f4", 3), ("steps", "<i2"), ("status", "<i2")])
 assert PATH_RADIANCE_DTYPE.itemsize == C.sizeof(SrtPathRadiance) == 16
+DIRECT_OUT_DTYPE = np.dtype([("radiance", "<f4", 3), ("light", "<i4"), ("dir", "<f4", 3), ("weight", "<f4")])
+assert DIRECT_OUT_DTYPE.itemsize == C.sizeof(SrtDirectOut) == 32
 AOV_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("time", "<f4"), ("valid", "<i4"), ("prim", "<i4"), ("t", "<f4"),
                       ("nodeVisits", "<i4"), ("boxPasses", "<i4"), ("triTests", "<i4"), ("sphereTests", "<i4"), ("pad", "<i4", 2)])
 assert AOV_DTYPE.itemsize == 64

@@ -231,6 +231,9 @@ static int srtUploadSceneImpl(SrtContext* ctx, const SrtSceneDesc* d) {
   ctx->upload.pairTime0 = t0;
   ctx->upload.pairTime1 = t1;
   ctx->upload.fastDivOption = ctx->tun.fastDiv;
+  const std::vector<int32_t> lights = sampledLights(h);
+  if (uploadVec(ctx, lights, &ctx->upload.sampledLights)) return 1;
+  for (int32_t sphere : lights) ctx->upload.sampledLightPrims.push_back(h.sphPrimId[sphere]);
   ctx->upload.hostTriPrimId = std::move(h.triPrimId);
   ctx->upload.hostSphPrimId = std::move(h.sphPrimId);
   ctx->upload.haveScene = true;

@@ -32,6 +32,11 @@ struct Upload {
   int plocRadius = 0;
   int hostStackDepth = 0, hostBvhDepth = 0;
   std::vector<int32_t> hostTriPrimId, hostSphPrimId;
+  // direct light sampling (srt_scene.h sampledLights): the table on the device -- device sphere indices, which the kernels
+  // get beside their other arguments -- and as prims[] indices for srtGetSampledLights.  Materials never change in an
+  // update, so it is the upload's
+  const int32_t* sampledLights = nullptr;
+  std::vector<int32_t> sampledLightPrims;
   int bvhDepth = 0;
   // srtUpdateTriangles / srtUpdateSpheres / srtRefitScene (srt_refit_host.cpp).  Every tree of the world list with its node
   // slots and times, the host tables the upload left (moved to the device by the first call that needs them), and the

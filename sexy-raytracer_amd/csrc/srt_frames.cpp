@@ -1,13 +1,15 @@
 // srt_frames.cpp -- the blocking entries of the C ABI that render a whole frame into HOST buffers (include/srt_hip.h,
 // srtRenderAov: include/srt_hip_test.h).  Each is a composition of the device-level entries (srt_render.cpp and
-// srt_passes.cpp, declared in srt_context.h; none of srt_rays.cpp's) on the null stream, over staging buffers that live
-// for the call.
+// srt_passes.cpp, declared in srt_context.h; of srt_rays.cpp's only srtRenderDirectImage's two, through the C ABI) on the
+// null stream, over staging buffers that live for the call.
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 
 #include "srt_context.h"
+#include "srt_launch.h"
 
 namespace {
 
@@ -301,6 +303,45 @@ int srtRenderTemporalAdaptiveFrameImpl(SrtContext* ctx, const SrtRenderParams* p
          f.copyOut(hRgba, f.outRgba, f.nPix * 4, "rgba");
 }
 
+// srtRenderDirectImage: the frame through the device-path entries with direct light sampling.  Per batch of sample indices:
+// srtCameraRaysDevice without a list (entries pixel-major), srtTracePathsDirectDevice, and the running sum of every pixel's
+// samples in sample-index order (srt_direct.hip); then the adaptive entries' image-order quantisation.  The three buffers of
+// a batch hold 60 bytes per entry; samplesPerBatch = 0 keeps a batch at 2^22 entries (240 MB) at most.
+int srtRenderDirectImageImpl(SrtContext* ctx, const SrtRenderParams* pIn, int32_t samplesPerBatch, float* hAccum, uint8_t* hRgba) {
+  if (!ctx) return 1;
+  if (!pIn) return fail(ctx, "direct: null parameters");
+  if (samplesPerBatch < 0) return fail(ctx, "direct: samplesPerBatch = %d is negative", samplesPerBatch);
+  FrameStage f(ctx, "direct", pIn);
+  if (checkParams(ctx, &f.p) || f.begin()) return 1;
+  const int64_t nPix = (int64_t)f.nPix;
+  int64_t batch = samplesPerBatch > 0 ? samplesPerBatch : std::max<int64_t>(1, ((int64_t)1 << 22) / nPix);
+  batch = std::min<int64_t>(batch, f.p.spp);
+  if (nPix * batch > 0x7fffffffll) return fail(ctx, "direct: %lld entries per batch do not fit: lower samplesPerBatch", (long long)(nPix * batch));
+  DeviceBuffer rays, rng, result, scratch;
+  const size_t entries = (size_t)(nPix * batch);
+  if (f.reserve(rays, entries * 36) || f.reserve(rng, entries * 8) || f.reserve(result, entries * 16) || f.reserve(scratch, SRT_PATHS_SCRATCH_BYTES) ||
+      f.reserve(f.accum, f.imageBytes) || (hRgba && f.reserve(f.rgba, f.nPix * 4)))
+    return 1;
+  if (hipMemsetAsync(f.accum.get(), 0, f.imageBytes, nullptr) != hipSuccess) return fail(ctx, "direct: memset");
+  const int grid = planEntryGrid(ctx->prop.multiProcessorCount, nPix);
+  for (int32_t first = 0; first < f.p.spp; first += (int32_t)batch) {
+    SrtRenderParams q = f.p;
+    q.spp = (int32_t)std::min<int64_t>(batch, f.p.spp - first);
+    q.sampleFirst = f.p.sampleFirst + first;
+    const int64_t n = nPix * q.spp;
+    if (srtCameraRaysDevice(ctx, &q, nullptr, n, rays.get(), rng.get(), nullptr)) return 1;
+    if (srtTracePathsDirectDevice(ctx, f.p.traversal, f.p.maxBounce, f.p.background, rays.get(), n, rng.get(), result.get(), scratch.get(), nullptr)) return 1;
+    const int e = srt_launch_direct_sum(result.get<const int4>(), f.accum.get<float4>(), nPix, q.spp, grid, nullptr);
+    if (e) return fail(ctx, "direct: launch failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  if (hRgba) {
+    const int e = srt_launch_adaptive_resolve(f.accum.get<const float4>(), f.rgba.get<uint8_t>(), (int)f.nPix, nullptr);
+    if (e) return fail(ctx, "direct: launch failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  if (f.finish()) return 1;
+  return f.copyOut(hRgba, f.rgba, f.nPix * 4, "rgba") || f.copyOut(hAccum, f.accum, f.imageBytes, "accum");
+}
+
 /* include/srt_hip_test.h: the render kernel's own traversal, ray by ray */
 int srtRenderAovImpl(SrtContext* ctx, const SrtRenderParams* pIn, int32_t depth, SrtAovRecord* hOut) {
   if (!ctx || !pIn || !hOut || depth < 0) return 1;
@@ -363,6 +404,9 @@ int srtRenderTemporalAdaptiveGuidedFrame(SrtContext* ctx, const SrtRenderParams*
                                          const SrtDenoiseParams* d, const SrtTemporalParams* t, float* hAccum, float* hDenoised,
                                          uint8_t* hRgba, SrtTemporalAdaptiveStats* stats) {
   SRT_GUARDED(ctx, srtRenderTemporalAdaptiveFrameImpl(ctx, p, ap, d, t, hAccum, hDenoised, hRgba, stats, true));
+}
+int srtRenderDirectImage(SrtContext* ctx, const SrtRenderParams* p, int32_t samplesPerBatch, float* hAccum, uint8_t* hRgba) {
+  SRT_GUARDED(ctx, srtRenderDirectImageImpl(ctx, p, samplesPerBatch, hAccum, hRgba));
 }
 int srtRenderAov(SrtContext* ctx, const SrtRenderParams* p, int32_t depth, SrtAovRecord* hOut) { SRT_GUARDED(ctx, srtRenderAovImpl(ctx, p, depth, hOut)); }
 

@@ -91,6 +91,39 @@ struct TracePathsArgs {
   int64_t n;
 };
 int srt_launch_paths(const TracePathsArgs* a, int traversal, int numCUs, size_t ldsBytes, size_t scratchBytes, hipStream_t stream);
+// ... and its DIRECT instances (srtTracePathsDirectDevice): the same launch with the sampled-light table beside the plain
+// arguments -- DevScene and TracePathsArgs stay as they are -- and ldsBytes = srtPathsDirectLdsBytes
+struct TracePathsDirectArgs {
+  TracePathsArgs p;
+  const int32_t* lights;  // device sphere indices of the sampled lights, prims[] order (Upload::sampledLights)
+  int32_t numLights;
+};
+int srt_launch_paths_direct(const TracePathsDirectArgs* a, int traversal, int numCUs, size_t ldsBytes, size_t scratchBytes, hipStream_t stream);
+
+// srt_direct.hip (srtDirectLightDevice, srtTestEvalScatterDevice): one kernel each, one lane per entry; every pointer is the
+// caller's DEVICE memory but `lights`.  traversal and ldsBytes as srt_launch_path_step's
+struct DirectLightArgs {
+  DevScene scene;
+  const float* rays;       // SrtRay[n]
+  const SrtHit* records;   // SrtHit[n]
+  const uint64_t* rng;     // read only: the state before the hit's scatter draws
+  int4* direct;            // SrtDirectOut[n] as two int4 per entry
+  const int32_t* lights;   // as TracePathsDirectArgs::lights
+  int32_t numLights;
+  int64_t n;
+};
+int srt_launch_direct_light(const DirectLightArgs* a, int traversal, int grid, size_t ldsBytes, hipStream_t stream);
+struct EvalScatterArgs {
+  DevScene scene;
+  const float* rays;
+  const SrtHit* records;
+  const float* dirs;  // float[n][3]: the scattered direction to evaluate
+  float* att;         // float[n][3]
+  int64_t n;
+};
+int srt_launch_eval_scatter(const EvalScatterArgs* a, int grid, hipStream_t stream);
+// srtRenderDirectImage: the `count` SrtPathRadiance of every pixel of a pixel-major batch added to its float4 sum in order
+int srt_launch_direct_sum(const int4* result, float4* accum, int64_t numPixels, int32_t count, int grid, hipStream_t stream);
 
 // srt_lbvh.hip: the device tree builders (blocking) and the closest-hit traversal's pair records
 int srt_lbvh_build(const DevScene* sc, const int32_t* dRefs, int n, float time0, float time1, float4* outNodes,

@@ -77,6 +77,10 @@ SRT_HD inline size_t srtQueryStackBytes(int stackDepth) { return (size_t)((stack
 SRT_HD inline size_t srtPathsLdsBytes(int stackDepth, int maxBounce) {
   return srtQueryStackBytes(stackDepth) + (size_t)3 * (maxBounce > 0 ? maxBounce : 0) * SRT_BLOCK * sizeof(float);
 }
+// ... and its DIRECT instances: per level the attenuation and the direct term, [6 * level + channel][thread]
+SRT_HD inline size_t srtPathsDirectLdsBytes(int stackDepth, int maxBounce) {
+  return srtQueryStackBytes(stackDepth) + (size_t)6 * (maxBounce > 0 ? maxBounce : 0) * SRT_BLOCK * sizeof(float);
+}
 // the stack walk of the feature and motion passes and of srtTraceRays (srt_path.h traverse): stackDepth slots
 SRT_HD inline size_t srtTraverseStackBytes(int stackDepth) { return (size_t)(stackDepth > 1 ? stackDepth : 1) * SRT_BLOCK * sizeof(int32_t); }
 // ... which the passes leave for the stackless walk over the whole tree in LDS where that fits

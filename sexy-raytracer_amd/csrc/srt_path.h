@@ -558,6 +558,93 @@ __device__ __forceinline__ V3 slotValue(const DevScene& sc, Rsrc rsTexels, uint3
   return mk((float)(px & 0xffu), (float)((px >> 8) & 0xffu), (float)((px >> 16) & 0xffu));
 }
 
+// pbrMetallicRoughness::scatter (material.h:156-245) in its two halves, each written once: what the material is at the hit --
+// factors and texture look-ups, before anything is drawn -- and the attenuation (fd + fs) * NdotL for a scattered direction
+// sd, from viewVec on.  shade() draws sd between the two; the direct-light term (srt_direct.h) evaluates the second half for
+// a direction of its own choosing.
+struct PbrInputs {
+  V3 a0, normal;  // albedo (factor, or the texture's value / 255), the shading normal (mapped where there is a normal map)
+  float mt, rg;   // metalness and roughness (factor, or the texture's value clamped)
+  float4 albedo;  // the albedo factor
+};
+template <bool COUNT, bool WIDE>
+__device__ __forceinline__ PbrInputs pbrInputs(const DevScene& sc, Rsrc rsTexels, Rsrc rsMat, int at, const Record& rec, float4 albedo,
+                                               float metalness, float roughness, uint32_t& fetches) {
+  V3 a0 = mk(albedo.x, albedo.y, albedo.z), normal = rec.normal;
+  float mt = metalness, rg = roughness;
+  if (rec.matType & SRT_MAT_TEXTURED) {  // some texture slot is in use: skipped by waves whose hits have none
+    // WIDE: the whole record in one round trip (slots, and the two colours of a checker-of-solids albedo), then the
+    // four texel loads together when any slot is an image (an absent or non-image slot reads texel 0 of the buffer and
+    // ignores it); otherwise each load is made where its value is used
+    const u32x4 tAN = __builtin_amdgcn_raw_buffer_load_b128(rsMat, at + 48, 0, 0), tMR = __builtin_amdgcn_raw_buffer_load_b128(rsMat, at + 64, 0, 0);
+    float4 even = make_float4(0.0f, 0.0f, 0.0f, 0.0f), odd = even;
+    if (WIDE) {
+      even = bufLoad4(rsMat, at + 80);
+      odd = bufLoad4(rsMat, at + 96);
+    }
+    uint32_t pA = 0, pN = 0, pM = 0, pR = 0;
+    const bool anyImage = (tAN.x & 3u) == SRT_SLOT_IMAGE || (tAN.z & 3u) == SRT_SLOT_IMAGE || (tMR.x & 3u) == SRT_SLOT_IMAGE || (tMR.z & 3u) == SRT_SLOT_IMAGE;
+    if (WIDE && anyImage) {
+      pA = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tAN.x, tAN.y, rec.u, rec.v), 0, 0);
+      pN = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tAN.z, tAN.w, rec.u, rec.v), 0, 0);
+      pM = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tMR.x, tMR.y, rec.u, rec.v), 0, 0);
+      pR = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tMR.z, tMR.w, rec.u, rec.v), 0, 0);
+    }
+    auto fetch = [&](uint32_t mw, uint32_t aux, uint32_t early) {
+      return WIDE || (mw & 3u) != SRT_SLOT_IMAGE ? early : __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(mw, aux, rec.u, rec.v), 0, 0);
+    };
+    if ((tAN.x & 7u) == SRT_SLOT_CHECKER2) {
+      // checker(solidColor, solidColor)::value = the chosen colour times 255 (texture.h:45-47), then material.h:165-166
+      if (!WIDE) {
+        even = bufLoad4(rsMat, at + 80);
+        odd = bufLoad4(rsMat, at + 96);
+      }
+      const float4 c = checkerOdd(rec.p) ? odd : even;
+      a0 = mk(c.x * 255.0f, c.y * 255.0f, c.z * 255.0f) / 255.0f;
+    } else if ((tAN.x & 3u) != SRT_SLOT_NONE)
+      a0 = slotValue<COUNT>(sc, rsTexels, tAN.x, tAN.y, fetch(tAN.x, tAN.y, pA), rec.u, rec.v, rec.p, fetches) / 255.0f;
+    if ((tAN.z & 3u) != SRT_SLOT_NONE) {
+      V3 nt = slotValue<COUNT>(sc, rsTexels, tAN.z, tAN.w, fetch(tAN.z, tAN.w, pN), rec.u, rec.v, rec.p, fetches);
+      nt = mk(nt.x - 128.0f, nt.y - 128.0f, nt.z - 128.0f) / 128.0f;  // vec3.h:103-110
+      // Matrix3f(T|B|N) * nt, each row reduced x + (y + z)
+      V3 w = mk(rec.tangent.x * nt.x + (rec.bitangent.x * nt.y + rec.normal.x * nt.z),
+                rec.tangent.y * nt.x + (rec.bitangent.y * nt.y + rec.normal.y * nt.z),
+                rec.tangent.z * nt.x + (rec.bitangent.z * nt.y + rec.normal.z * nt.z));
+      normal = unitv(w);
+    }
+    if ((tMR.x & 3u) != SRT_SLOT_NONE)
+      mt = clampf(slotValue<COUNT>(sc, rsTexels, tMR.x, tMR.y, fetch(tMR.x, tMR.y, pM), rec.u, rec.v, rec.p, fetches).x / 255.0f, 0.0f, 1.0f);
+    if ((tMR.z & 3u) != SRT_SLOT_NONE)
+      rg = clampf(slotValue<COUNT>(sc, rsTexels, tMR.z, tMR.w, fetch(tMR.z, tMR.w, pR), rec.u, rec.v, rec.p, fetches).y / 255.0f, 0.0f, 1.0f);
+  }
+  return PbrInputs{a0, normal, mt, rg, albedo};
+}
+__device__ __forceinline__ V3 pbrAttenuation(const PbrInputs& m, V3 rayDir, V3 sd) {
+  const V3 a0 = m.a0, normal = m.normal;
+  const float4 albedo = m.albedo;
+  const float mt = m.mt, rg = m.rg;
+  V3 viewVec = -unitv(rayDir);
+  V3 halfVec = unitv(sd + viewVec);
+  float NdotL = fmaxf(dot3(normal, sd), 0.0f);
+  float NdotH = fmaxf(dot3(normal, halfVec), 0.0f);
+  float HdotV = fmaxf(dot3(halfVec, viewVec), 0.0f);
+  float NdotV = fmaxf(dot3(normal, viewVec), 0.0f);
+  V3 fr = mk(albedo.x, albedo.y, albedo.z);
+  // lerp(0.4, fr, mt), vec3.h:97-101.  F0 for dielectrics is 0.4 (material.h:228)
+  V3 F0 = mk((1.0f - mt) * 0.4f + mt * fr.x, (1.0f - mt) * 0.4f + mt * fr.y, (1.0f - mt) * 0.4f + mt * fr.z);
+  float D = trowbridgeReitzNDF(NdotH, rg);
+  // fresnelEpic (pbr.h:75-81): pow(2.0f, x) resolves to the double pow, narrowed to float
+  float power = (float)exp2((double)((-5.55473f * HdotV - 6.98316f) * HdotV));
+  V3 F = mk(F0.x + (1.0f - F0.x) * power, F0.y + (1.0f - F0.y) * power, F0.z + (1.0f - F0.z) * power);
+  float G = schlickGAF(NdotL, rg) * schlickGAF(NdotV, rg);
+  V3 fd = a0 / SRT_PI;
+  fd = mk(fd.x * (1.0f - F.x), fd.y * (1.0f - F.y), fd.z * (1.0f - F.z));
+  fd = fd * (1.0f - mt);
+  fd = mk(fd.x * albedo.x, fd.y * albedo.y, fd.z * albedo.z);
+  V3 fs = ((D * F) * G) / (4.0f * NdotV * NdotL + SRT_EPS);
+  return (fd + fs) * NdotL;
+}
+
 // returns false when the path ends here (scatter == false); emitted is always set.
 // WIDE: all four texel loads of a pbr hit in flight at once (the 128-register kernel); otherwise one lookup after the
 // other, which keeps four registers live instead of sixteen (the 96-register kernels spill as it is).
@@ -622,54 +709,8 @@ __device__ __forceinline__ bool shade(const DevScene& sc, Rsrc rsTexels, const R
       return true;
     }
     default: {  // pbrMetallicRoughness::scatter, material.h:156-245
-      V3 a0 = mk(albedo.x, albedo.y, albedo.z), normal = rec.normal;
-      float mt = metalness, rg = roughness;
-      if (rec.matType & SRT_MAT_TEXTURED) {  // some texture slot is in use: skipped by waves whose hits have none
-        // WIDE: the whole record in one round trip (slots, and the two colours of a checker-of-solids albedo), then the
-        // four texel loads together when any slot is an image (an absent or non-image slot reads texel 0 of the buffer and
-        // ignores it); otherwise each load is made where its value is used
-        const u32x4 tAN = __builtin_amdgcn_raw_buffer_load_b128(rsMat, at + 48, 0, 0), tMR = __builtin_amdgcn_raw_buffer_load_b128(rsMat, at + 64, 0, 0);
-        float4 even = make_float4(0.0f, 0.0f, 0.0f, 0.0f), odd = even;
-        if (WIDE) {
-          even = bufLoad4(rsMat, at + 80);
-          odd = bufLoad4(rsMat, at + 96);
-        }
-        uint32_t pA = 0, pN = 0, pM = 0, pR = 0;
-        const bool anyImage = (tAN.x & 3u) == SRT_SLOT_IMAGE || (tAN.z & 3u) == SRT_SLOT_IMAGE || (tMR.x & 3u) == SRT_SLOT_IMAGE || (tMR.z & 3u) == SRT_SLOT_IMAGE;
-        if (WIDE && anyImage) {
-          pA = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tAN.x, tAN.y, rec.u, rec.v), 0, 0);
-          pN = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tAN.z, tAN.w, rec.u, rec.v), 0, 0);
-          pM = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tMR.x, tMR.y, rec.u, rec.v), 0, 0);
-          pR = __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(tMR.z, tMR.w, rec.u, rec.v), 0, 0);
-        }
-        auto fetch = [&](uint32_t mw, uint32_t aux, uint32_t early) {
-          return WIDE || (mw & 3u) != SRT_SLOT_IMAGE ? early : __builtin_amdgcn_raw_buffer_load_b32(rsTexels, slotTexelOffset(mw, aux, rec.u, rec.v), 0, 0);
-        };
-        if ((tAN.x & 7u) == SRT_SLOT_CHECKER2) {
-          // checker(solidColor, solidColor)::value = the chosen colour times 255 (texture.h:45-47), then material.h:165-166
-          if (!WIDE) {
-            even = bufLoad4(rsMat, at + 80);
-            odd = bufLoad4(rsMat, at + 96);
-          }
-          const float4 c = checkerOdd(rec.p) ? odd : even;
-          a0 = mk(c.x * 255.0f, c.y * 255.0f, c.z * 255.0f) / 255.0f;
-        } else if ((tAN.x & 3u) != SRT_SLOT_NONE)
-          a0 = slotValue<COUNT>(sc, rsTexels, tAN.x, tAN.y, fetch(tAN.x, tAN.y, pA), rec.u, rec.v, rec.p, fetches) / 255.0f;
-        if ((tAN.z & 3u) != SRT_SLOT_NONE) {
-          V3 nt = slotValue<COUNT>(sc, rsTexels, tAN.z, tAN.w, fetch(tAN.z, tAN.w, pN), rec.u, rec.v, rec.p, fetches);
-          nt = mk(nt.x - 128.0f, nt.y - 128.0f, nt.z - 128.0f) / 128.0f;  // vec3.h:103-110
-          // Matrix3f(T|B|N) * nt, each row reduced x + (y + z)
-          V3 w = mk(rec.tangent.x * nt.x + (rec.bitangent.x * nt.y + rec.normal.x * nt.z),
-                    rec.tangent.y * nt.x + (rec.bitangent.y * nt.y + rec.normal.y * nt.z),
-                    rec.tangent.z * nt.x + (rec.bitangent.z * nt.y + rec.normal.z * nt.z));
-          normal = unitv(w);
-        }
-        if ((tMR.x & 3u) != SRT_SLOT_NONE)
-          mt = clampf(slotValue<COUNT>(sc, rsTexels, tMR.x, tMR.y, fetch(tMR.x, tMR.y, pM), rec.u, rec.v, rec.p, fetches).x / 255.0f, 0.0f, 1.0f);
-        if ((tMR.z & 3u) != SRT_SLOT_NONE)
-          rg = clampf(slotValue<COUNT>(sc, rsTexels, tMR.z, tMR.w, fetch(tMR.z, tMR.w, pR), rec.u, rec.v, rec.p, fetches).y / 255.0f, 0.0f, 1.0f);
-      }
-
+      const PbrInputs m = pbrInputs<COUNT, WIDE>(sc, rsTexels, rsMat, at, rec, albedo, metalness, roughness, fetches);
+      const V3 normal = m.normal;
       if (COUNT && stamp) stamp[0] = clock64();  // textures done
       V3 sd = normal + unitv(rng.inUnitSphere());  // randomUnitVector, vec3.h:72-74
       if (COUNT && stamp) stamp[1] = clock64();  // direction drawn
@@ -677,26 +718,7 @@ __device__ __forceinline__ bool shade(const DevScene& sc, Rsrc rsTexels, const R
       if ((double)fabsf(sd.x) < 1e-8 && (double)fabsf(sd.y) < 1e-8 && (double)fabsf(sd.z) < 1e-8) sd = normal;
       sd = unitv(sd);
       out.d = sd;
-      V3 viewVec = -unitv(rIn.d);
-      V3 halfVec = unitv(sd + viewVec);
-      float NdotL = fmaxf(dot3(normal, sd), 0.0f);
-      float NdotH = fmaxf(dot3(normal, halfVec), 0.0f);
-      float HdotV = fmaxf(dot3(halfVec, viewVec), 0.0f);
-      float NdotV = fmaxf(dot3(normal, viewVec), 0.0f);
-      V3 fr = mk(albedo.x, albedo.y, albedo.z);
-      // lerp(0.4, fr, mt), vec3.h:97-101.  F0 for dielectrics is 0.4 (material.h:228)
-      V3 F0 = mk((1.0f - mt) * 0.4f + mt * fr.x, (1.0f - mt) * 0.4f + mt * fr.y, (1.0f - mt) * 0.4f + mt * fr.z);
-      float D = trowbridgeReitzNDF(NdotH, rg);
-      // fresnelEpic (pbr.h:75-81): pow(2.0f, x) resolves to the double pow, narrowed to float
-      float power = (float)exp2((double)((-5.55473f * HdotV - 6.98316f) * HdotV));
-      V3 F = mk(F0.x + (1.0f - F0.x) * power, F0.y + (1.0f - F0.y) * power, F0.z + (1.0f - F0.z) * power);
-      float G = schlickGAF(NdotL, rg) * schlickGAF(NdotV, rg);
-      V3 fd = a0 / SRT_PI;
-      fd = mk(fd.x * (1.0f - F.x), fd.y * (1.0f - F.y), fd.z * (1.0f - F.z));
-      fd = fd * (1.0f - mt);
-      fd = mk(fd.x * albedo.x, fd.y * albedo.y, fd.z * albedo.z);
-      V3 fs = ((D * F) * G) / (4.0f * NdotV * NdotL + SRT_EPS);
-      att = (fd + fs) * NdotL;
+      att = pbrAttenuation(m, rIn.d, sd);
       return true;
     }
   }

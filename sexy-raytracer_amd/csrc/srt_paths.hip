@@ -19,13 +19,17 @@
 // kernel's own: the claim of entries, the attenuation stack and its unwinding, and the one store of the radiance where
 // the step kernel stores an SrtPathOut per bounce.  LDS per workgroup: the walk's [slot][thread] stack (stackDepth + 2
 // slots), then the attenuations [3 * level + channel][thread], 3 * maxBounce slots of the call's own maxBounce
-// (srt_lds_layout.h srtPathsLdsBytes).  DESIGN.md 5.20.
+// (srt_lds_layout.h srtPathsLdsBytes).  DESIGN.md 5.20.  The DIRECT instances (srtTracePathsDirectDevice) add srt_direct.h's
+// direct-light term at every pbr hit and keep it beside the attenuation: 6 * maxBounce slots (srtPathsDirectLdsBytes).
+// DESIGN.md 5.23.
 
 #include <algorithm>
+#include <type_traits>
 
 #include "srt_path.h"
 #include "srt_query_walk.h"
 #include "srt_step_rays.h"
+#include "srt_direct.h"
 #include "srt_lds_layout.h"
 #include "srt_launch.h"
 
@@ -38,10 +42,19 @@ __device__ __forceinline__ void storeRadiance(int4* out, V3 L, int steps, int st
   *out = make_int4(__float_as_int(L.x), __float_as_int(L.y), __float_as_int(L.z), (int)(((uint32_t)status << 16) | ((uint32_t)steps & 0xffffu)));
 }
 
-// MODE: Q_FAITHFUL or Q_CLOSEST
-template <int MODE>
-__global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const TracePathsArgs a) {
+__device__ __forceinline__ const TracePathsArgs& plainArgs(const TracePathsArgs& a) { return a; }
+__device__ __forceinline__ const TracePathsArgs& plainArgs(const TracePathsDirectArgs& a) { return a.p; }
+
+// MODE: Q_FAITHFUL or Q_CLOSEST.  DIRECT (srtTracePathsDirectDevice): at a pbr hit the direct term of srt_direct.h is
+// evaluated ahead of shade() from the generator's state as it is there, which it does not advance, and kept beside the
+// step's attenuation -- six LDS slots per level instead of three (srt_lds_layout.h srtPathsDirectLdsBytes); a bounced
+// ray that ends on a light the step before could have chosen drops that light's emission; the unwinding adds each level's
+// term.  Claim, walk, records, shade() and the stores are the plain instance's lines.
+template <int MODE, bool DIRECT = false>
+__global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const std::conditional_t<DIRECT, TracePathsDirectArgs, TracePathsArgs> args) {
   extern __shared__ int32_t lds[];
+  const TracePathsArgs& a = plainArgs(args);
+  constexpr int SLOTS = DIRECT ? 6 : 3;  // per level: the attenuation, and with DIRECT the direct term
   const DevScene& sc = a.scene;
   const QueryWalk walk = queryWalkSetup<MODE>(sc, lds);  // [slot][thread]: stackDepth + 2 slots
   float* const attStack = reinterpret_cast<float*>(lds) + srtQueryStackBytes(sc.stackDepth) / sizeof(int32_t) + threadIdx.x;
@@ -58,6 +71,7 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const TracePathsAr
   rng.state = 0;
   int depth = 0;
   bool have = false;
+  bool sampledBefore = false;  // DIRECT: the step before evaluated a direct term
   bool dry = false;  // the counter has passed n: nothing is left to claim (the same in every lane of the wave)
   while (true) {
     // ---- refill: every lane of the wave is here, whatever it did in the trip before
@@ -75,6 +89,7 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const TracePathsAr
         loadRay(a.rays + 9 * i, r, tMin, tMax);
         rng.state = a.rng[i];
         depth = 0;
+        sampledBefore = false;
         have = a.maxBounce > 0;
         if (!have) storeRadiance(a.result + i, zero, 0, SRT_PATH_SCATTERED);  // no step runs: black, the state as it was
       }
@@ -105,10 +120,23 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const TracePathsAr
           Ray next;
           next.d = zero;
           uint32_t fetches = 0;
+          V3 direct = zero;
+          bool sampled = false;
+          if constexpr (DIRECT) {
+            if (args.numLights > 0 && (rec.matType & 3) == SRT_MAT_PBR) {
+              direct = directTerm<MODE, STEP_WIDE>(sc, walk, rsTexels, args.lights, args.numLights, r, tMin, tMax, rec, rng.state).radiance;
+              sampled = true;
+            }
+          }
           if (shade<false, STEP_WIDE>(sc, rsTexels, r, rec, rng, att, next, emitted, fetches)) {
-            attStack[(3 * depth + 0) * SRT_BLOCK] = att.x;  // depth < maxBounce: a path at the limit has ended
-            attStack[(3 * depth + 1) * SRT_BLOCK] = att.y;
-            attStack[(3 * depth + 2) * SRT_BLOCK] = att.z;
+            attStack[(SLOTS * depth + 0) * SRT_BLOCK] = att.x;  // depth < maxBounce: a path at the limit has ended
+            attStack[(SLOTS * depth + 1) * SRT_BLOCK] = att.y;
+            attStack[(SLOTS * depth + 2) * SRT_BLOCK] = att.z;
+            if constexpr (DIRECT) {
+              attStack[(SLOTS * depth + 3) * SRT_BLOCK] = direct.x;
+              attStack[(SLOTS * depth + 4) * SRT_BLOCK] = direct.y;
+              attStack[(SLOTS * depth + 5) * SRT_BLOCK] = direct.z;
+            }
             r = next;
             depth++;
             status = SRT_PATH_SCATTERED;
@@ -116,15 +144,21 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const TracePathsAr
           } else {
             status = SRT_PATH_ENDED;
             L = emitted;
+            if constexpr (DIRECT) {  // the drop rule: the step before could have chosen this light, whatever it chose
+              if (sampledBefore && (pr & 1) && directCouldChoose(sc, pr >> 1, r.o)) L = zero;
+            }
           }
+          sampledBefore = sampled;
         }
       }
       if (!goOn) {
         const int steps = depth + (status != SRT_PATH_SCATTERED ? 1 : 0);
         // unwind the recursion: emitted + newColor * attenuation with emitted = 0, innermost first (main.cpp:49-51)
         for (int j = depth - 1; j >= 0; --j) {
-          const float ax = attStack[(3 * j + 0) * SRT_BLOCK], ay = attStack[(3 * j + 1) * SRT_BLOCK], az = attStack[(3 * j + 2) * SRT_BLOCK];
-          L = mk(0.0f + L.x * ax, 0.0f + L.y * ay, 0.0f + L.z * az);
+          const float ax = attStack[(SLOTS * j + 0) * SRT_BLOCK], ay = attStack[(SLOTS * j + 1) * SRT_BLOCK], az = attStack[(SLOTS * j + 2) * SRT_BLOCK];
+          V3 D = zero;  // the plain instance's 0.0f
+          if constexpr (DIRECT) D = mk(attStack[(SLOTS * j + 3) * SRT_BLOCK], attStack[(SLOTS * j + 4) * SRT_BLOCK], attStack[(SLOTS * j + 5) * SRT_BLOCK]);
+          L = mk(D.x + L.x * ax, D.y + L.y * ay, D.z + L.z * az);
         }
         storeRadiance(a.result + i, L, steps, status);
         a.rng[i] = rng.state;  // one 8-byte store: the state after the path's last draw
@@ -132,6 +166,23 @@ __global__ __launch_bounds__(SRT_BLOCK) void srt_paths_kernel(const TracePathsAr
       }
     }
   }
+}
+
+// the memset of the counter and the launch of one instance; p: the plain arguments inside a
+template <typename Args>
+int launchPaths(void (*kernel)(const Args), const Args& a, const TracePathsArgs& p, int numCUs, size_t ldsBytes, size_t scratchBytes, hipStream_t stream) {
+  if (ldsBytes > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  // the workgroups that are resident at once: more would only queue behind them and find the counter run out
+  int perCU = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, SRT_BLOCK, ldsBytes) != hipSuccess || perCU < 1) perCU = 1;
+  const int grid = (int)std::min<int64_t>((p.n + SRT_BLOCK - 1) / SRT_BLOCK, (int64_t)numCUs * perCU);
+  const hipError_t e = hipMemsetAsync(p.counter, 0, scratchBytes, stream);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SRT_BLOCK), ldsBytes, stream, a);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -142,18 +193,13 @@ extern "C" {
 // clears from a->counter on
 int srt_launch_paths(const TracePathsArgs* a, int traversal, int numCUs, size_t ldsBytes, size_t scratchBytes, hipStream_t stream) {
   void (*kernel)(const TracePathsArgs) = traversal == SRT_TRAVERSE_CLOSEST ? srt_paths_kernel<Q_CLOSEST> : srt_paths_kernel<Q_FAITHFUL>;
-  if (ldsBytes > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  // the workgroups that are resident at once: more would only queue behind them and find the counter run out
-  int perCU = 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, SRT_BLOCK, ldsBytes) != hipSuccess || perCU < 1) perCU = 1;
-  const int grid = (int)std::min<int64_t>((a->n + SRT_BLOCK - 1) / SRT_BLOCK, (int64_t)numCUs * perCU);
-  const hipError_t e = hipMemsetAsync(a->counter, 0, scratchBytes, stream);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SRT_BLOCK), ldsBytes, stream, *a);
-  return (int)hipGetLastError();
+  return launchPaths(kernel, *a, *a, numCUs, ldsBytes, scratchBytes, stream);
+}
+
+// the DIRECT instances; ldsBytes: srtPathsDirectLdsBytes
+int srt_launch_paths_direct(const TracePathsDirectArgs* a, int traversal, int numCUs, size_t ldsBytes, size_t scratchBytes, hipStream_t stream) {
+  void (*kernel)(const TracePathsDirectArgs) = traversal == SRT_TRAVERSE_CLOSEST ? srt_paths_kernel<Q_CLOSEST, true> : srt_paths_kernel<Q_FAITHFUL, true>;
+  return launchPaths(kernel, *a, a->p, numCUs, ldsBytes, scratchBytes, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // srt_rays.cpp -- the device-buffer entries of the C ABI (include/srt_hip.h "Ray queries", "Path steps on device buffers"):
-// queries, camera rays, scatter, the fused path step, compaction, the sort and whole paths, on the caller's buffers and
-// stream.  Each makes every check on the host and then launches its kernel file; nothing of the context changes -- no
+// queries, camera rays, scatter, the fused path step, compaction, the sort, whole paths and direct light sampling, on the
+// caller's buffers and stream.  Each makes every check on the host and then launches its kernel file; nothing of the context changes -- no
 // work area, no event, no plan.  The refusals several of them make are written once, ahead of them.
 
 #include <hip/hip_runtime.h>
@@ -318,11 +318,11 @@ static int sortPathsDevice(SrtContext* ctx, const PathPayloads& p, int32_t cellB
   return 0;
 }
 
-// ---------------------------------------------------------------- srtTracePathsDevice
-// srt_paths.hip's memset and its one kernel.
-static int tracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float* background, const void* dRays, int64_t n,
-                            void* dRng, void* dResult, void* dScratch, void* streamPtr) {
-  const char* what = "srtTracePathsDevice";
+// ---------------------------------------------------------------- srtTracePathsDevice / srtTracePathsDirectDevice
+// srt_paths.hip's memset and its one kernel.  direct: the DIRECT instance, with the upload's sampled-light table.
+static int tracePathsDevice(SrtContext* ctx, bool direct, int32_t traversal, int32_t maxBounce, const float* background, const void* dRays,
+                            int64_t n, void* dRng, void* dResult, void* dScratch, void* streamPtr) {
+  const char* what = direct ? "srtTracePathsDirectDevice" : "srtTracePathsDevice";
   if (!ctx) return 1;
   if (checkSceneReady(ctx, what) || checkCount(ctx, what, n) || checkTraversal(ctx, what, traversal)) return 1;
   if (maxBounce < 0 || maxBounce > SRT_MAX_BOUNCE) return fail(ctx, "%s: maxBounce = %d is outside [0, %d]", what, maxBounce, SRT_MAX_BOUNCE);
@@ -339,7 +339,7 @@ static int tracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounc
                               {"scratch", (uintptr_t)dScratch, SRT_PATHS_SCRATCH_BYTES, true}};
   if (checkPathRanges(ctx, what, ranges, sizeof ranges / sizeof ranges[0], nullptr, nullptr, true)) return 1;
   const DevScene& sc = ctx->upload.scene;
-  const size_t lds = srtPathsLdsBytes(sc.stackDepth, maxBounce);
+  const size_t lds = direct ? srtPathsDirectLdsBytes(sc.stackDepth, maxBounce) : srtPathsLdsBytes(sc.stackDepth, maxBounce);
   if (checkWalkLds(ctx, what, lds, maxBounce)) return 1;
   HIP_OK(ctx, hipSetDevice(ctx->device));
   TracePathsArgs a;
@@ -352,7 +352,86 @@ static int tracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounc
   a.maxBounce = maxBounce;
   a.refillMin = std::min(std::max(ctx->tun.pathsRefillMin, 1), 64);
   a.n = n;
-  const int e = srt_launch_paths(&a, traversal, ctx->prop.multiProcessorCount, lds, SRT_PATHS_SCRATCH_BYTES, static_cast<hipStream_t>(streamPtr));
+  int e;
+  if (direct) {
+    TracePathsDirectArgs d;
+    d.p = a;
+    d.lights = ctx->upload.sampledLights;
+    d.numLights = (int32_t)ctx->upload.sampledLightPrims.size();
+    e = srt_launch_paths_direct(&d, traversal, ctx->prop.multiProcessorCount, lds, SRT_PATHS_SCRATCH_BYTES, static_cast<hipStream_t>(streamPtr));
+  } else {
+    e = srt_launch_paths(&a, traversal, ctx->prop.multiProcessorCount, lds, SRT_PATHS_SCRATCH_BYTES, static_cast<hipStream_t>(streamPtr));
+  }
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+// ---------------------------------------------------------------- srtGetSampledLights / srtDirectLightDevice / srtTestEvalScatterDevice
+static int getSampledLights(SrtContext* ctx, int32_t* prims, int32_t capacity, int32_t* count) {
+  const char* what = "srtGetSampledLights";
+  if (!ctx) return 1;
+  if (!ctx->upload.haveScene) return fail(ctx, "%s: no scene uploaded", what);
+  if (!count) return fail(ctx, "%s: null count", what);
+  const std::vector<int32_t>& lights = ctx->upload.sampledLightPrims;
+  *count = (int32_t)lights.size();
+  if (prims) {
+    if (capacity < *count) return fail(ctx, "%s: capacity %d < %d", what, capacity, *count);
+    std::copy(lights.begin(), lights.end(), prims);
+  }
+  return 0;
+}
+
+// One launch of srt_direct.hip
+static int directLightDevice(SrtContext* ctx, int32_t traversal, const void* dRays, const void* dRecords, int64_t n, const void* dRng,
+                             void* dDirect, void* streamPtr) {
+  const char* what = "srtDirectLightDevice";
+  if (!ctx) return 1;
+  if (checkSceneReady(ctx, what) || checkCount(ctx, what, n) || checkTraversal(ctx, what, traversal)) return 1;
+  if (n == 0) return 0;
+  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "records", dRecords, 4) ||
+      checkPointer(ctx, what, "rng states", dRng, 8) || checkPointer(ctx, what, "direct terms", dDirect, 16))
+    return 1;
+  const uint64_t un = (uint64_t)n;
+  const PathRange ranges[] = {{"rays", (uintptr_t)dRays, 36 * un, false},
+                              {"records", (uintptr_t)dRecords, sizeof(SrtHit) * un, false},
+                              {"rng states", (uintptr_t)dRng, 8 * un, false},
+                              {"direct terms", (uintptr_t)dDirect, 32 * un, true}};
+  if (checkPathRanges(ctx, what, ranges, sizeof ranges / sizeof ranges[0], nullptr, nullptr)) return 1;
+  const DevScene& sc = ctx->upload.scene;
+  const size_t lds = srtQueryStackBytes(sc.stackDepth);  // the shadow ray's walk, as queryDevice sizes and bounds it
+  if (checkWalkLds(ctx, what, lds)) return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  DirectLightArgs a;
+  a.scene = sc;
+  a.rays = static_cast<const float*>(dRays);
+  a.records = static_cast<const SrtHit*>(dRecords);
+  a.rng = static_cast<const uint64_t*>(dRng);
+  a.direct = static_cast<int4*>(dDirect);
+  a.lights = ctx->upload.sampledLights;
+  a.numLights = (int32_t)ctx->upload.sampledLightPrims.size();
+  a.n = n;
+  const int e = srt_launch_direct_light(&a, traversal, pathGrid(ctx, n), lds, static_cast<hipStream_t>(streamPtr));
+  if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+static int evalScatterDevice(SrtContext* ctx, const void* dRays, const void* dRecords, const void* dDirs, int64_t n, void* dAtt) {
+  const char* what = "srtTestEvalScatterDevice";
+  if (!ctx) return 1;
+  if (checkSceneReady(ctx, what) || checkCount(ctx, what, n)) return 1;
+  if (n == 0) return 0;
+  if (checkPointer(ctx, what, "rays", dRays, 4) || checkPointer(ctx, what, "records", dRecords, 4) ||
+      checkPointer(ctx, what, "directions", dDirs, 4) || checkPointer(ctx, what, "attenuations", dAtt, 4))
+    return 1;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  EvalScatterArgs a;
+  a.scene = ctx->upload.scene;
+  a.rays = static_cast<const float*>(dRays);
+  a.records = static_cast<const SrtHit*>(dRecords);
+  a.dirs = static_cast<const float*>(dDirs);
+  a.att = static_cast<float*>(dAtt);
+  a.n = n;
+  const int e = srt_launch_eval_scatter(&a, pathGrid(ctx, n), nullptr);
   if (e) return fail(ctx, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -406,7 +485,25 @@ int srtSortPathsDevice(SrtContext* ctx, int64_t n, int32_t cellBits, const void*
 
 int srtTracePathsDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float background[3], const void* dRays, int64_t n,
                         void* dRng, void* dResult, void* dScratch, void* stream) {
-  SRT_GUARDED(ctx, tracePathsDevice(ctx, traversal, maxBounce, background, dRays, n, dRng, dResult, dScratch, stream));
+  SRT_GUARDED(ctx, tracePathsDevice(ctx, false, traversal, maxBounce, background, dRays, n, dRng, dResult, dScratch, stream));
+}
+
+int srtTracePathsDirectDevice(SrtContext* ctx, int32_t traversal, int32_t maxBounce, const float background[3], const void* dRays,
+                              int64_t n, void* dRng, void* dResult, void* dScratch, void* stream) {
+  SRT_GUARDED(ctx, tracePathsDevice(ctx, true, traversal, maxBounce, background, dRays, n, dRng, dResult, dScratch, stream));
+}
+
+int srtGetSampledLights(SrtContext* ctx, int32_t* prims, int32_t capacity, int32_t* count) {
+  SRT_GUARDED(ctx, getSampledLights(ctx, prims, capacity, count));
+}
+
+int srtDirectLightDevice(SrtContext* ctx, int32_t traversal, const void* dRays, const void* dRecords, int64_t n, const void* dRng,
+                         void* dDirect, void* stream) {
+  SRT_GUARDED(ctx, directLightDevice(ctx, traversal, dRays, dRecords, n, dRng, dDirect, stream));
+}
+
+int srtTestEvalScatterDevice(SrtContext* ctx, const void* dRays, const void* dRecords, const void* dDirs, int64_t n, void* dAtt) {
+  SRT_GUARDED(ctx, evalScatterDevice(ctx, dRays, dRecords, dDirs, n, dAtt));
 }
 
 }  // extern "C"

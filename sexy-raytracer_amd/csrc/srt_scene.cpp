@@ -589,6 +589,24 @@ std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene
   return std::string();
 }
 
+// From a flattened scene, nothing of which it changes: the spheres whose material is a light with a solid-colour emit slot
+// (SRT_SLOT_SOLID in its shading record), as device sphere indices in prims[] order.  A moving sphere is listed too: whether
+// it moves is read from its record where the table is used.
+std::vector<int32_t> sampledLights(const HostScene& h) {
+  std::vector<std::pair<int32_t, int32_t>> found;  // (prims[] index, device index)
+  const int32_t numMaterials = (int32_t)(h.shadeRecs.size() / 8);
+  for (size_t i = 0; i < h.sphPrimId.size(); ++i) {
+    const int32_t word = bitsAs<int32_t>(&h.spheres[3 * i + 1].w);
+    const int32_t m = word & SRT_MAT_INDEX_MASK;
+    if (m >= numMaterials || h.materials[m].type != SRT_MAT_LIGHT || h.shadeRecs[(size_t)8 * m + 2].x != SRT_SLOT_SOLID) continue;
+    found.emplace_back(h.sphPrimId[i], (int32_t)i);
+  }
+  std::sort(found.begin(), found.end());
+  std::vector<int32_t> out;
+  for (const auto& f : found) out.push_back(f.second);
+  return out;
+}
+
 extern "C" {
 
 float srtHostRandomFloat(void) { return hostRandomFloat(); }

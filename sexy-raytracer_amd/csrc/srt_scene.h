@@ -100,3 +100,7 @@ struct HostScene {
 
 // Flattens a scene that passed validateScene.  Returns the error text, empty on success.
 std::string flattenScene(const SrtSceneDesc* d, const SceneOptions& o, HostScene& out);
+
+// The lights direct sampling chooses from (include/srt_hip.h "Direct light sampling"), from what flattenScene made: device
+// sphere indices in prims[] order.
+std::vector<int32_t> sampledLights(const HostScene& h);

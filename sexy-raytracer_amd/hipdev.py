@@ -35,6 +35,7 @@ EXPORTS = ["srtCreate", "srtDestroy", "srtLastError", "srtMakeCamera", "srtHostR
            "srtDenoise", "srtRenderDenoisedImage", "srtTraceRays", "srtTraceRaysDevice", "srtOccludedDevice", "srtScatterRays",
            "srtRngKey", "srtCameraRaysDevice", "srtScatterRaysDevice", "srtPathStepDevice",
            "srtCompactPathsScratchBytes", "srtCompactPathsDevice", "srtSortPathsScratchBytes", "srtSortPathsDevice", "srtTracePathsDevice",
+           "srtGetSampledLights", "srtDirectLightDevice", "srtTracePathsDirectDevice", "srtRenderDirectImage",
            "srtRenderTilesMoments", "srtRenderImageMoments", "srtDenoiseMoments", "srtRenderDenoisedImageMoments",
            "srtRenderAdaptive", "srtRenderAdaptiveImage",
            "srtTemporalAccumulate", "srtRenderTemporalFrame", "srtTemporalReset",
@@ -52,7 +53,7 @@ TEST_EXPORTS = ["srtSetTunable", "srtGetTunable", "srtGetShadeProfile", "srtGetW
                 "srtScatterRaysForm", "srtTestThreadLinks16", "srtTestHybridRecords", "srtTestGetTreeAux", "srtTestChunkSum",
                 "srtTestDenoiseScratch", "srtTestGetTriUndecided", "srtTestGetTriFast", "srtTestTriFastRecord", "srtTestGetSlabScene",
                 "srtTestRefinedRcp", "srtTestSlabVisit", "srtTestRegroup", "srtTestGetRegroup",
-                "srtTestRegroupWalk", "srtTestGetRegroupWalk", "srtTestWfHead"]
+                "srtTestRegroupWalk", "srtTestGetRegroupWalk", "srtTestWfHead", "srtTestEvalScatterDevice"]
 
 _vp = C.c_void_p
 lib.srtCreate.argtypes = [C.c_int, C.POINTER(_vp)]
@@ -147,6 +148,11 @@ lib.srtSortPathsScratchBytes.argtypes = [C.c_int64]
 lib.srtSortPathsScratchBytes.restype = C.c_int64
 lib.srtSortPathsDevice.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 12 + [C.c_int64, _vp]
 lib.srtTracePathsDevice.argtypes = [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), _vp, C.c_int64, _vp, _vp, _vp, _vp]
+lib.srtTracePathsDirectDevice.argtypes = lib.srtTracePathsDevice.argtypes
+lib.srtGetSampledLights.argtypes = [_vp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
+lib.srtDirectLightDevice.argtypes = [_vp, C.c_int32, _vp, _vp, C.c_int64, _vp, _vp, _vp]
+lib.srtRenderDirectImage.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
+lib.srtTestEvalScatterDevice.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, _vp]
 lib.srtCommGetUniqueId.argtypes = [_vp]
 lib.srtCommInit.argtypes = [_vp, _vp, C.c_int32, C.c_int32]
 lib.srtGatherTiles.argtypes = [_vp, C.POINTER(abi.SrtRenderParams), _vp, _vp, _vp]
@@ -342,6 +348,19 @@ class Context:
         rgba = np.zeros((H, W, 4), np.uint8) if want_rgba else None
         self._check(lib.srtRenderImage(self.h, C.byref(params), accum.ctypes.data if want_accum else None,
                                        rgba.ctypes.data if want_rgba else None))
+        return accum, rgba
+
+    def render_direct_image(self, params, samples_per_batch=0, want_accum=True, want_rgba=True):
+        """srtRenderDirectImage: the frame through camera_rays_device and trace_paths_device(direct=True), samples_per_batch
+        sample indices at a time (0: a default that bounds memory), summed per pixel in sample-index order.  Returns
+        (accum, rgba) as render_image does: another estimator of the same image -- with no sampled light in the scene and
+        FAITHFUL steps, render_image's bytes."""
+        W, H = params.imageWidth, params.imageHeight
+        accum = np.zeros((H, W, 4), np.float32) if want_accum else None
+        rgba = np.zeros((H, W, 4), np.uint8) if want_rgba else None
+        self._check(lib.srtRenderDirectImage(self.h, C.byref(params), int(samples_per_batch),
+                                             accum.ctypes.data_as(C.POINTER(C.c_float)) if want_accum else None,
+                                             rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None))
         return accum, rgba
 
     def render_image_moments(self, params, want_accum=True, want_rgba=True):
@@ -976,7 +995,47 @@ class Context:
         """srtSortPathsScratchBytes: 0 for n <= 0, never smaller for a larger n."""
         return int(lib.srtSortPathsScratchBytes(int(n)))
 
-    def trace_paths_device(self, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_CLOSEST, scratch=None, stream=None):
+    def sampled_lights(self):
+        """srtGetSampledLights: the prims[] indices of the spheres direct light sampling chooses from (light materials with
+        a solid-colour emit texture), an int32 array in prims[] order."""
+        count = C.c_int32(0)
+        self._check(lib.srtGetSampledLights(self.h, None, 0, C.byref(count)))
+        prims = np.zeros(count.value, np.int32)
+        self._check(lib.srtGetSampledLights(self.h, prims.ctypes.data_as(C.POINTER(C.c_int32)), count.value, C.byref(count)))
+        return prims
+
+    def direct_light_device(self, rays, records, rng, traversal=abi.SRT_TRAVERSE_CLOSEST, stream=None):
+        """srtDirectLightDevice: the direct-light term of every (ray, hit record) pair, asynchronous on `stream`: one sampled
+        light is chosen per pbr hit, a direction inside its cone drawn, the shadow ray walked with `traversal`.  rays,
+        records and rng as scatter_device's; rng is only READ (the states before the hits' scatter draws: call this ahead
+        of scatter_device).  Returns an int32 tensor (n, 8) laid out as SrtDirectOut {radiance's bits[3], light, dir's
+        bits[3], weight's bits} (abi.DIRECT_OUT_DTYPE on the host); light is a prims[] index, -1 where nothing was sampled."""
+        import torch
+        rays = self._device_rays(rays)
+        n = rays.shape[0]
+        records = self._device_tensor(records, "records", "int32", (n, C.sizeof(abi.SrtHit) // 4), rays)
+        rng = self._device_tensor(rng, "rng", "int64", (n,), rays)
+        direct = torch.empty((n, 8), dtype=torch.int32, device=rays.device)
+        ptr = self._ptr
+        self._check(lib.srtDirectLightDevice(self.h, int(traversal), ptr(rays, n), ptr(records, n), n, ptr(rng, n), ptr(direct, n),
+                                             self._stream_handle(stream)))
+        return direct
+
+    def eval_scatter_test(self, rays, records, dirs):
+        """srtTestEvalScatterDevice: pbr's attenuation for the directions dirs (n, 3) float32 on the GPU, on the NULL stream:
+        float32 (n, 3), 0 for entries that are not pbr hits."""
+        import torch
+        rays = self._device_rays(rays)
+        n = rays.shape[0]
+        records = self._device_tensor(records, "records", "int32", (n, C.sizeof(abi.SrtHit) // 4), rays)
+        dirs = self._device_tensor(dirs, "dirs", "float32", (n, 3), rays)
+        att = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+        ptr = self._ptr
+        self._check(lib.srtTestEvalScatterDevice(self.h, ptr(rays, n), ptr(records, n), ptr(dirs, n), n, ptr(att, n)))
+        return att
+
+    def trace_paths_device(self, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_CLOSEST, scratch=None, stream=None,
+                           direct=False):
         """srtTracePathsDevice: the path-traced radiance of every ray of a DEVICE tensor in one kernel, asynchronous on
         `stream` -- at most max_bounce steps of path_step_device per ray, each on the scattered ray of the step before,
         then the unwinding; no tensor per bounce and no count read back.  rays: float32 (n, 9), only read; rng: int64 (n,),
@@ -985,7 +1044,8 @@ class Context:
         (allocated when None; calls on one stream may share one).  Returns an int32 tensor (n, 4) laid out as
         SrtPathRadiance: columns 0..2 viewed as float32 are the radiance, column 3 holds the number of steps that ran in
         its low 16 bits and the last step's abi.SRT_PATH_* status in its high 16 (result.view(torch.int16)[:, 6] and
-        [:, 7]; SCATTERED: the bounce limit ended the path)."""
+        [:, 7]; SCATTERED: the bounce limit ended the path).  direct=True: srtTracePathsDirectDevice -- the same paths with
+        the direct-light term of direct_light_device added at every pbr hit; steps, status and rng are the same."""
         import torch
         rays = self._device_rays(rays)
         n = rays.shape[0]
@@ -999,8 +1059,9 @@ class Context:
         bg = (C.c_float * 3)(*[float(c) for c in background])
         result = torch.empty((n, 4), dtype=torch.int32, device=rays.device)
         ptr = self._ptr
-        self._check(lib.srtTracePathsDevice(self.h, int(traversal), int(max_bounce), bg, ptr(rays, n), n, ptr(rng, n), ptr(result, n),
-                                            ptr(scratch, n), self._stream_handle(stream)))
+        entry = lib.srtTracePathsDirectDevice if direct else lib.srtTracePathsDevice
+        self._check(entry(self.h, int(traversal), int(max_bounce), bg, ptr(rays, n), n, ptr(rng, n), ptr(result, n), ptr(scratch, n),
+                          self._stream_handle(stream)))
         return result
 
     def scatter_test(self, rays, hits, seed):

@@ -142,6 +142,26 @@ class hipDevice {
     return true;
   }
 
+  // rtFrame with direct light sampling (include/srt_hip.h srtRenderDirectImage): the same image in expectation from other
+  // samples -- at every pbr hit one of the scene's solid-colour light spheres is sampled.  Single-process only.
+  bool rtFrameDirect(void* frameData, int w, int h, const camera& cam, const color3f& background, int numSamples, int maxBounce,
+                     uint64_t seed = 1, float* accum = nullptr) {
+    if (!ctx) return false;
+    if (ranks > 1) {
+      std::cerr << "ERROR: rtFrameDirect renders on one GPU\n";
+      return false;
+    }
+    if (srtSetCamera(ctx, &cam.data()) != 0) return error();
+    SrtRenderParams p{};
+    p.imageWidth = w; p.imageHeight = h; p.spp = numSamples; p.maxBounce = maxBounce; p.seed = seed;
+    for (int i = 0; i < 3; ++i) p.background[i] = background(i);
+    p.tMin = 0.001f;  // main.cpp:39
+    p.traversal = SRT_TRAVERSE_FAITHFUL;
+    p.tileFirst = 0; p.tileStride = 1;
+    if (srtRenderDirectImage(ctx, &p, 0, accum, static_cast<uint8_t*>(frameData)) != 0) return error();
+    return true;
+  }
+
   // Tile-adaptive sampling (include/srt_hip.h "Adaptive sampling"): numSamples (>= 2) samples everywhere, then doubling rounds
   // for the tiles not yet converged to the display-space standard error `threshold`, up to sppMax samples a pixel.
   // frameData = uint8[w*h*4] (may be null), accum = float[w*h*4] sums with per-pixel counts (may be null), stats may be null.

@@ -11,8 +11,73 @@ from . import abi
 _DEAD = -2  # a status no step writes: an entry that was not active in this step
 
 
+def direct_tables(ctx, scene_builder, spheres=None, device=None):
+    """What the unfused direct-light loop needs of the uploaded scene beside the library's calls, for its drop rule: (lights,
+    prims, pbr) -- lights float32 (k, 4) on the GPU, {centre, radius} of the sampled lights (Context.sampled_lights) that do
+    not move, prims their prims[] indices as a host list of ints, and pbr, a bool tensor over the materials.  scene_builder: the SceneBuilder that was uploaded; spheres:
+    abi.SPHERE_DTYPE records of its spheres as they are now (after update_spheres), or None."""
+    import numpy as np
+    import torch
+    device = torch.device("cuda" if device is None else device)
+    kinds = np.concatenate(scene_builder._prim_chunks)
+    rows, prims = [], []
+    for prim in ctx.sampled_lights().tolist():
+        i = int(kinds[prim, 1])
+        s = scene_builder.spheres[i]
+        c0, c1, radius = (s.center0[:], s.center1[:], s.radius) if spheres is None else (spheres["center0"][i], spheres["center1"][i], spheres["radius"][i])
+        if tuple(np.float32(c0)) == tuple(np.float32(c1)):
+            rows.append([float(v) for v in c0] + [float(radius)])
+            prims.append(int(prim))
+    lights = torch.tensor(rows, dtype=torch.float32, device=device).reshape(-1, 4)
+    pbr = torch.tensor([m.type == abi.SRT_MAT_PBR for m in scene_builder.materials], dtype=torch.bool, device=device)
+    return lights, prims, pbr
+
+
+def _sample_radiance_direct(ctx, rays, rng, max_bounce, background, traversal, stream, tables):
+    """sample_radiance with direct light sampling as a user-land loop: per bounce trace_device(records=True), then
+    direct_light_device on the states as they are BEFORE the scatter, then scatter_device; the drop rule and the unwinding
+    L = D_j + L * att_j are torch ops.  The bits of Context.trace_paths_device(direct=True)."""
+    import torch
+    lights, light_prims, pbr = tables
+    n = rays.shape[0]
+    sampling = len(ctx.sampled_lights()) > 0
+    bg = torch.tensor([float(c) for c in background], dtype=torch.float32, device=rays.device)
+    terminal = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+    active = torch.ones((n,), dtype=torch.bool, device=rays.device)
+    sampled_before = torch.zeros((n,), dtype=torch.bool, device=rays.device)
+    steps = []  # per step: (attenuation, direct term, scattered)
+    for _ in range(max_bounce):
+        rays[:, 8].masked_fill_(~active, 0.0)  # the queries have no mask: a finished entry misses
+        origin = rays[:, 0:3].clone()
+        _, records = ctx.trace_device(rays, traversal, records=True, stream=stream)
+        direct = ctx.direct_light_device(rays, records, rng, traversal, stream=stream)
+        out, _ = ctx.scatter_device(rays, records, rng, rays_out=rays, stream=stream)
+        status = torch.where(active, out[:, 3], torch.full_like(out[:, 3], _DEAD))
+        colours = out.view(torch.float32)
+        scattered = status == abi.SRT_PATH_SCATTERED
+        ended = status == abi.SRT_PATH_ENDED
+        # the drop rule: a bounced ray that ends on a light the step before could have chosen loses that light's emission
+        drop = torch.zeros_like(ended)
+        for k, prim in enumerate(light_prims):
+            v = lights[k, 0:3] - origin
+            far = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2] > lights[k, 3] * lights[k, 3]
+            drop |= (out[:, 7] == prim) & far
+        emitted = torch.where((drop & sampled_before)[:, None], torch.zeros_like(terminal), colours[:, 4:7])
+        terminal = torch.where((status == abi.SRT_PATH_MISS)[:, None], bg, terminal)
+        terminal = torch.where(ended[:, None], emitted, terminal)
+        material = records[:, 17].to(torch.int64).clamp(0, pbr.shape[0] - 1)
+        sampled_before = scattered & pbr[material] & sampling
+        term = torch.where(sampled_before[:, None], direct.view(torch.float32)[:, 0:3], torch.zeros_like(terminal))
+        steps.append((colours[:, 0:3], term, scattered))
+        active = scattered
+    radiance = terminal
+    for attenuation, term, scattered in reversed(steps):
+        radiance = torch.where(scattered[:, None], radiance * attenuation + term, radiance)
+    return radiance
+
+
 def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TRAVERSE_FAITHFUL, fused=True, stream=None,
-                    active_counts=None, compact=False, whole=False, sort=None):
+                    active_counts=None, compact=False, whole=False, sort=None, direct=False):
     """The radiance of one path per ray: at most max_bounce steps, then the unwinding.  rays (n, 9) float32 and rng (n,)
     int64 as Context.camera_rays_device returns them; both are overwritten.  fused: one path_step_device per bounce;
     otherwise trace_device(records=True) + scatter_device, which compute the same bytes through an 88-byte record per ray.
@@ -24,11 +89,21 @@ def sample_radiance(ctx, rays, rng, max_bounce, background, traversal=abi.SRT_TR
     axis (1 .. abi.SRT_SORT_MAX_CELL_BITS) of Context.sort_paths_device, which then takes the place of
     compact_paths_device in the compacted loop: the live entries move to the front AND into the order of their origin's
     cell and their direction's octant, in the box of their origins -- the same bits once more; not together with whole.
+    direct: direct light sampling (include/srt_hip.h "Direct light sampling") -- another estimator of the same image, so
+    other bits.  With whole=True any true value: one Context.trace_paths_device(direct=True) call.  Otherwise the
+    direct_tables() of the uploaded scene: the unfused loop of trace records -> direct_light_device -> scatter_device with
+    the drop rule and the unwinding as torch ops (fused=False; no compaction, sort or counts), the whole form's bits.
     Returns (n, 3) float32."""
     import torch
     if whole:
         _check_whole(fused, compact, active_counts, sort)
-        return ctx.trace_paths_device(rays, rng, max_bounce, background, traversal, stream=stream).view(torch.float32)[:, 0:3]
+        return ctx.trace_paths_device(rays, rng, max_bounce, background, traversal, stream=stream, direct=bool(direct)).view(torch.float32)[:, 0:3]
+    if direct is not False and direct is not None:
+        if fused or compact or sort is not None or active_counts is not None:
+            raise ValueError("direct light sampling as a loop is the unfused one: fused=False, and no compact, sort or active_counts")
+        if direct is True:
+            raise ValueError("direct light sampling as a loop needs direct=direct_tables(ctx, scene_builder)")
+        return _sample_radiance_direct(ctx, rays, rng, max_bounce, background, traversal, stream, direct)
     if sort is not None:
         return _sample_radiance_compact(ctx, rays, rng, max_bounce, background, traversal, fused, stream, active_counts, sort)
     if compact:
@@ -131,13 +206,15 @@ def _check_whole(fused, compact, active_counts, sort=None):
 
 
 def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples_per_batch=None, device=None, active_counts=None,
-           compact=False, whole=False, sort=None):
+           compact=False, whole=False, sort=None, direct=False):
     """params.spp samples of every pixel from params.sampleFirst on, through the device path steps: the (H, W, 4) float32
     torch tensor of per-pixel radiance sums (the float running sum in sample-index order) with the sample count in w --
     Context.render_image's accumulation buffer.  samples_per_batch: how many sample indices of the whole frame go through
     the loop at once (default all; a batch holds about 8 * maxBounce + 25 words per entry: every step's SrtPathOut stays alive for the unwinding).  compact, sort: sample_radiance's.
     whole: a batch is one Context.trace_paths_device call (15 words per entry whatever maxBounce is) followed by the same
-    running sum; not together with active_counts, compact, sort or fused=False.  Runs on torch's current stream."""
+    running sum; not together with active_counts, compact, sort or fused=False.  direct: sample_radiance's -- True with
+    whole=True, direct_tables(ctx, scene_builder) with fused=False; the two forms render the same bits, which are not
+    Context.render_image's (another estimator of the same image).  Runs on torch's current stream."""
     import torch
     if whole:
         _check_whole(fused, compact, active_counts, sort)
@@ -157,7 +234,7 @@ def render(ctx, params, fused=True, traversal=abi.SRT_TRAVERSE_FAITHFUL, samples
                                                      device=device).repeat_interleave(pixels)), dim=1).contiguous()
             rays, rng = ctx.camera_rays_device(params, pixel_sample, stream=stream)
             radiance = sample_radiance(ctx, rays, rng, params.maxBounce, params.background, traversal, fused, stream, active_counts, compact,
-                                       whole, sort)
+                                       whole, sort, direct)
             for k in range(count):
                 image[:, 0:3] += radiance[k * pixels:(k + 1) * pixels]
         image[:, 3] = float(spp)

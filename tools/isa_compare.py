@@ -6,7 +6,8 @@
     python tools/isa_compare.py old/srt_kernels.s new/srt_kernels.s
 
 Every kernel of the old listing must be in the new one under its name with `Lb0E` (a defaulted trailing `false`
-template argument, such as MOMENTS) appended to its template arguments, or under its old name; its instructions and its
+template argument, such as MOMENTS or DIRECT) appended to its template arguments -- whatever its parameter types are then
+spelled as -- or under its old name; its instructions and its
 descriptor (registers, scratch, LDS, argument size) must be identical once label numbers and the kernel's own name are
 normalised.  Kernels only in the new listing are listed with their register counts and scratch size.
 
@@ -63,9 +64,14 @@ def meta(path):
     return out
 
 
-def new_name(old):
-    m = re.match(r"(.*I(?:Lb[01]E)+)(EE?v.*)", old)  # EEv: a kernel in a namespace (a nested name)
-    return m.group(1) + "Lb0E" + m.group(2) if m else old
+def new_name(old, new=()):
+    m = re.match(r"(.*I(?:L[bi]\d+E)+)(EE?v)(.*)", old)  # EEv: a kernel in a namespace (a nested name)
+    if not m:
+        return old
+    name = m.group(1) + "Lb0E" + m.group(2)
+    # the parameter types may now depend on the new argument (srt_paths_kernel<MODE, DIRECT>: conditional_t<DIRECT, ...>)
+    found = [n for n in new if n.startswith(name)]
+    return found[0] if len(found) == 1 else name + m.group(3)
 
 
 def main(old_path, new_path):
@@ -73,7 +79,7 @@ def main(old_path, new_path):
     mo, mn = meta(old_path), meta(new_path)
     bad, matched = 0, set()
     for k, body in sorted(old.items()):
-        n = new_name(k) if new_name(k) in new else k
+        n = new_name(k, new) if new_name(k, new) in new else k
         if n not in new:
             print("MISSING  %s" % k)
             bad += 1

@@ -32,7 +32,11 @@ the origins included), per cell size of --sort-bits; the variants alternate, --w
 --sort-call SPP times --steps srtSortPathsDevice calls behind the first bounce of all W * H * SPP camera rays at the
 first cell size of --sort-bits (run it under a kernel trace for the split into key, sort and gather).
 
-usage: python tools/query_bench.py [--steps 200] [--warmup 5] [--host-steps 3] [--cases masterchief,soup_200k,soup_1m] [--ao-rays 4]
+--direct measures direct light sampling (direct_bench below): plain and direct whole paths at 4 to 256 spp against a
+5000-spp srtRenderImage, RMSE and frame time, and the equal-error time ratio.
+
+usage: python tools/query_bench.py --direct [--cases masterchief,iron,spheres] [--loop-reps 3] [--ref-spp 5000] [--clamp X]
+       python tools/query_bench.py [--steps 200] [--warmup 5] [--host-steps 3] [--cases masterchief,soup_200k,soup_1m] [--ao-rays 4]
                                    [--ao-radius 0.1] [--ao-png FILE] [--width 1280] [--height 720]
        python tools/query_bench.py --path-loop [--loop-reps 5] [--warmup-loops 1] [--cases masterchief,soup_200k,soup_1m]
                                    [--sort-bits 3,5,7,9] [--variants fused_compact,fused_sort_3,...]
@@ -333,9 +337,70 @@ def path_loop(a):
     print(json.dumps(result))
 
 
+def direct_bench(a):
+    """--direct: what direct light sampling buys in samples and costs in time.  Per case (--cases, default
+    masterchief,iron,spheres) at --width x --height, 4 bounces, FAITHFUL: the reference is srtRenderImage at --ref-spp (5000);
+    plain whole paths (pathloop.render(whole=True)) and direct ones (direct=True) at 4, 16, 64 and 256 spp, each --loop-reps
+    times alternating, events around the whole frame, --direct-batch sample indices per batch for both; RMSE of the mean
+    radiance against the reference over the pixels finite in all three (--clamp X clamps the radiance first; default: no
+    clamp).  equal_error: for each direct point, the plain frame time that
+    reaches the same RMSE -- interpolated, or extrapolated along the last segment, on plain's (log time, log RMSE) points --
+    over the direct frame time: above 1 direct sampling pays.  The reference's own noise is a floor under both."""
+    pathloop = importlib.import_module("sexy-raytracer_amd.pathloop")
+    ctx = dev.Context(0)
+    cam = dev.make_camera(abi.default_camera_params())
+    W, H, bounces = a.width, a.height, 4
+    stream = torch.cuda.current_stream()
+    result = {"device": ctx.device_info()["name"], "width": W, "height": H, "max_bounce": bounces, "ref_spp": a.ref_spp, "clamp": a.clamp if np.isfinite(a.clamp) else None,
+              "reps": a.loop_reps, "batch": a.direct_batch, "cases": {}}
+    for case in a.cases.split(","):
+        ctx.upload_scene(scene(case))
+        ctx.set_camera(cam)
+        ref_acc, _ = ctx.render_image(abi.default_render_params(W, H, a.ref_spp, bounces, seed=99), want_rgba=False)
+        ref = np.minimum(ref_acc[..., :3] / ref_acc[..., 3:4], F(a.clamp)).astype(np.float64)
+        out = {"sampled_lights": int(len(ctx.sampled_lights())), "points": {}}
+        for spp in (4, 16, 64, 256):
+            p = abi.default_render_params(W, H, spp, bounces, seed=1)
+            ms, image = {"plain": [], "direct": []}, {}
+            for rep in range(1 + a.loop_reps):
+                for name in ("plain", "direct"):
+                    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    start.record(stream)
+                    img = pathloop.render(ctx, p, whole=True, direct=(name == "direct"), samples_per_batch=a.direct_batch)
+                    stop.record(stream)
+                    stop.synchronize()
+                    if rep:
+                        ms[name].append(start.elapsed_time(stop))
+                    image[name] = img
+            means = {k: np.minimum((v[..., :3] / v[..., 3:4]).cpu().numpy(), F(a.clamp)).astype(np.float64) for k, v in image.items()}
+            ok = np.isfinite(ref).all(axis=-1) & np.isfinite(means["plain"]).all(axis=-1) & np.isfinite(means["direct"]).all(axis=-1)
+            point = {"finite_share": float(ok.mean())}
+            for name in ("plain", "direct"):
+                point[name] = {"ms": float(np.median(ms[name])), "spread_ms": [min(ms[name]), max(ms[name])],
+                               "rmse": float(np.sqrt(((means[name][ok] - ref[ok]) ** 2).mean()))}
+            out["points"]["spp_%d" % spp] = point
+        pts = [out["points"]["spp_%d" % s] for s in (4, 16, 64, 256)]
+        lt = np.log([q["plain"]["ms"] for q in pts])
+        le = np.log([q["plain"]["rmse"] for q in pts])
+        out["equal_error"] = {}
+        for s, q in zip((4, 16, 64, 256), pts):
+            e = np.log(q["direct"]["rmse"])
+            k = int(np.clip(np.searchsorted(-le, -e) - 1, 0, len(le) - 2))  # le falls with time
+            t = lt[k] + (e - le[k]) * (lt[k + 1] - lt[k]) / (le[k + 1] - le[k])
+            out["equal_error"]["spp_%d" % s] = {"plain_ms_for_direct_rmse": float(np.exp(t)), "time_ratio": float(np.exp(t) / q["direct"]["ms"]),
+                                                "extrapolated": bool(e < le[-1] or e > le[0])}
+        result["cases"][case] = out
+    ctx.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--path-loop", action="store_true", help="measure pathloop.render (fused / unfused) against srtRenderTiles instead")
+    ap.add_argument("--direct", action="store_true", help="direct light sampling against plain whole paths: RMSE and frame time (direct_bench)")
+    ap.add_argument("--ref-spp", type=int, default=5000, help="--direct: samples of the srtRenderImage reference")
+    ap.add_argument("--clamp", type=float, default=float("inf"), help="--direct: radiance is clamped to this before the RMSE (default: not at all)")
+    ap.add_argument("--direct-batch", type=int, default=4, help="--direct: sample indices per batch of both estimators")
     ap.add_argument("--loop-reps", type=int, default=5, help="--path-loop: timed repetitions of every variant, alternating")
     ap.add_argument("--warmup-loops", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed device calls per figure (a call is 0.2 - 3 ms)")
@@ -352,6 +417,10 @@ def main():
     ap.add_argument("--ao-radius", type=float, default=0.1, help="AO tMax as a share of the scene's extent (6 units)")
     ap.add_argument("--ao-png", default=None)
     a = ap.parse_args()
+    if a.direct:
+        if a.cases == ap.get_default("cases"):
+            a.cases = "masterchief,iron,spheres"
+        return direct_bench(a)
     if a.path_loop:
         return path_loop(a)
     if a.sort_ao:
